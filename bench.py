@@ -12,13 +12,15 @@ independent, so ranks never communicate on the data path (weak scaling; `--mode 
 frame across the ranks instead: strong scaling, BASELINE config 5).  Rank 0 prints ONE JSON line.
 
 BASELINE.json's metric is "Mpixels/sec (Mandelbrot & Droste @8192x8192)": `value` is the Mandelbrot frame
-rate (config 1, the configuration the >= 100x target is quoted on).  The default line carries every other
+rate (config 1, the configuration the >= 100x target is quoted on).  A plain run sets up, warms up, times the
+--steps frames and prints the line (`ms_per_step`: wall time of one timed step); `--dump-outputs DIR` also writes
+what the last timed step rendered (dump_outputs).  With `--full` the line also carries every other
 BASELINE config next to it, each with its own kernel time, roofline, verification against the CPU oracle
 and CPU baseline: "droste" (config 2: defaults and -DNoTransparency=1), "gauss" (config 3: gaussian_blur
 sigma = 20 px at 16384^2) and "pond" (config 4: the 120-frame Pond animation, t = frame/120), plus
 "host_delivered" -- the rate with the frame's last byte in a host buffer (SURVEY 8d's end point,
 PCIe-inclusive; never `value`).  After the timed region sampled row bands of the last timed frame are
-compared with the CPU oracle ("verified").
+compared with the CPU oracle ("verified"), and a per-launch pass adds the per-kernel times.
 """
 import argparse
 import glob
@@ -178,6 +180,7 @@ class Workload:
 
 
 PER_LAUNCH_PASS_FRAMES = 40
+DUMP_BYTES = 48 << 20                   # --dump-outputs: at most this much of the frame, as float32
 KERNEL_MS_NOTE = ("kernel_ms: GPU time per step over the timed region, from one HIP event before its first and one behind its "
                   "last launch on the launch stream (back-to-back launches overlap at their edges, so this can be below the "
                   "isolated duration); kernel_ms_per_launch_events / kernel_ms_per_kernel: an untimed pass right after it with "
@@ -219,6 +222,20 @@ def timed_frames(torch, wl, steps, warmup, stream, first_frame=0):
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     return el, e0.elapsed_time(e1) / steps
+
+
+def dump_outputs(torch, np, out, rows, dest):
+    """--dump-outputs: the RGBA8 frame the last timed step left in HBM (`out`, rows [lo, hi) of it rendered by this rank:
+    what render_rows hands its caller), as float32 in DIR/frame.npy [R, W, 4], with the frame row of each in
+    DIR/frame_rows.npy (float64 [R]).  Every row when that stays within DUMP_BYTES, else a fixed (seeded) sample of rows."""
+    lo, hi = rows
+    w = out.shape[1]
+    n = min(hi - lo, max(1, DUMP_BYTES // (w * 4 * 4)))
+    idx = np.arange(lo, hi) if n == hi - lo else np.sort(np.random.default_rng(0).choice(np.arange(lo, hi), n, replace=False))
+    frame = out[torch.as_tensor(idx, device=out.device)].cpu().numpy().astype(np.float32)
+    os.makedirs(dest, exist_ok=True)
+    np.save(os.path.join(dest, "frame.npy"), frame)
+    np.save(os.path.join(dest, "frame_rows.npy"), idx.astype(np.float64))
 
 
 def settle_clocks(torch, render_one, target_ms, batch=16, cap_frames=2000):
@@ -494,6 +511,11 @@ def main():
     ap.add_argument("--specialize", type=int, default=1,
                     help="1 = user-value specialising JIT (default), 0 = generic kernel reading user values at run time")
     ap.add_argument("--cpu-rows", type=int, default=0, help="rows of the frame timed on the CPU (0 = auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: verification against the CPU oracle, host-delivered rate, "
+                         "per-launch kernel times, generic-kernel comparison, CPU baseline, the other BASELINE configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last one rendered as DIR/*.npy (float32; see dump_outputs)")
     args = ap.parse_args()
 
     env_world = int(os.environ["WORLD_SIZE"]) if "WORLD_SIZE" in os.environ else None
@@ -567,8 +589,11 @@ def main():
     elapsed = comm.max(elapsed)
     per_rank_ms = comm.gather(my_kernel_ms)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, np, wl.out, (row_lo, row_hi), args.dump_outputs)
+
     last_frame = frame_of(args.steps - 1)
-    extras = not args.no_extras
+    extras = args.full and not args.no_extras
     # ---- every rank: its own rows of its last timed frame against the oracle; the host-delivered rate ----
     images = None
     my_ok, my_v = True, None
@@ -592,13 +617,15 @@ def main():
         hsame_all = comm.sum(0.0 if hsame else 1.0) == 0.0
 
     # (behind the verification: that one looks at the frame the timed region left in the output buffer)
-    launch_ms, native = per_launch_pass(torch, wl, step, min(args.steps, PER_LAUNCH_PASS_FRAMES))
+    launch_ms, native = None, []
+    if args.full:
+        launch_ms, native = per_launch_pass(torch, wl, step, min(args.steps, PER_LAUNCH_PASS_FRAMES))
     if rank == 0:
         mpix = w * h * args.steps * (1 if stripes else world) / 1e6
         value = mpix / elapsed
         k_ms = my_kernel_ms
         per_kernel = None
-        if args.workload == "gauss":
+        if args.workload == "gauss" and args.full:
             per = {}
             for label, ms in native:
                 per.setdefault(label, []).append(ms)

@@ -10,7 +10,7 @@ import pytest
 
 from tests.conftest import ROOT
 
-COMMON = ["--steps", "40", "--warmup", "4", "--settle-ms", "100", "--no-configs", "--no-cpu-baseline", "--no-generic"]
+COMMON = ["--full", "--steps", "40", "--warmup", "4", "--settle-ms", "100", "--no-configs", "--no-cpu-baseline", "--no-generic"]
 
 
 def run_bench(*extra):

@@ -9,7 +9,7 @@ O=gpurun_out/r02m
 mkdir -p $O
 echo "${MM_COMMIT:-unknown}" > $O/commit.txt
 WL="${@:-mandelbrot ident pond droste droste_nt gauss}"
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 for w in $WL; do
   case $w in
     droste_nt) ARGS="--workload droste -D NoTransparency=1" ;;

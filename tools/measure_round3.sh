@@ -10,7 +10,7 @@ O=gpurun_out/r03m
 mkdir -p $O
 echo "${MM_COMMIT:-unknown}" > $O/commit.txt
 WL="${@:-mandelbrot ident pond droste droste_nt gauss}"
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err
 for w in $WL; do
   case $w in
