@@ -87,6 +87,17 @@ const char *mmhip_filter_ir_json(mmhip_filter *f);        /* IR dump after the o
 const char *mmhip_filter_ir_json_raw(mmhip_filter *f);
 const char *mmhip_filter_kernel_source(mmhip_filter *f);  /* the HIP C++ handed to hiprtc */
 int mmhip_filter_num_native_calls(const mmhip_filter *f);
+/* The launch geometry of the filter's pixel kernel over rows [0, num_rows) of a region_w-wide region, as
+   mmhip_render takes it (MMHIP_PPT included): out[MMHIP_GEOMETRY_FIELDS] receives, in this order,
+   tiles_x, tiles_y, wg1 (workgroups at one row per work-item, the rows-per-item choice's input), nwg (workgroups
+   launched), ppt (rows per work-item), tile_w, tile_h, unroll (MM_UNROLL), pair_mode, single_pixel, xcd_order,
+   tiles_magic (0: plain division) and xcd_full (workgroups that XCD order 2 swizzles).  No GPU needed. */
+enum { MMHIP_GEOMETRY_FIELDS = 13 };
+int mmhip_filter_launch_geometry(const mmhip_filter *f, int region_w, int num_rows, int64_t *out);
+/* closure images the filter renders whole (render_image's closure branch), and the geometry of closure #closure's
+   own launch over a width x height frame (same fields) */
+int mmhip_filter_num_closures(const mmhip_filter *f);
+int mmhip_filter_closure_launch_geometry(const mmhip_filter *f, int closure, int width, int height, int64_t *out);
 /* hiprtc-compiles for gfx950 and (if a device is present) loads the module.
    load_module = 0 only compiles (usable without a GPU).  Returns code size. */
 long mmhip_filter_jit(mmhip_filter *f, int load_module);

@@ -42,6 +42,9 @@ SYMBOLS = {
     "mmhip_filter_ir_json_raw": (C.c_char_p, [C.c_void_p]),
     "mmhip_filter_kernel_source": (C.c_char_p, [C.c_void_p]),
     "mmhip_filter_num_native_calls": (C.c_int, [C.c_void_p]),
+    "mmhip_filter_launch_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "mmhip_filter_num_closures": (C.c_int, [C.c_void_p]),
+    "mmhip_filter_closure_launch_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "mmhip_filter_jit": (C.c_long, [C.c_void_p, C.c_int]),
     "mmhip_filter_jit_seconds": (C.c_double, [C.c_void_p]),
     "mmhip_invoke": (C.c_void_p, [C.c_void_p, C.c_int, C.c_int]),
@@ -87,7 +90,7 @@ BACKEND_SYMBOLS = {
     "mathmap_hip_release_invocation": (None, [C.c_void_p]),
 }
 
-# test scaffolding of the reference-ABI tier: tests/libmathmap_hip_selftest.so (built from csrc/abi_selftest.cpp,
+# test scaffolding of the reference-ABI tier: mathmap_amd/libmathmap_hip_selftest.so (built from csrc/abi_selftest.cpp,
 # linked against the product library; not part of it)
 SELFTEST_SYMBOLS = {
     "mmhip_selftest_abi_roundtrip": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -97,7 +100,7 @@ SELFTEST_SYMBOLS = {
     "mmhip_selftest_eval_unary": (C.c_int, [C.c_int, C.c_uint, C.c_ulonglong, C.c_void_p]),
     "mmhip_selftest_eval_binary": (C.c_int, [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_void_p]),
 }
-SELFTEST_PATH = os.path.join(os.path.dirname(_HERE), "tests", "libmathmap_hip_selftest.so")
+SELFTEST_PATH = os.path.join(_HERE, "libmathmap_hip_selftest.so")
 _selftest = None
 
 

@@ -15,6 +15,9 @@ from ._lib import Options, UservalInfo, lib
 
 UV_INT, UV_FLOAT, UV_BOOL, UV_COLOR, UV_CURVE, UV_GRADIENT, UV_IMAGE = range(7)
 EDGE_COLOR, EDGE_WRAP, EDGE_REFLECT, EDGE_ROTATE = range(4)
+# mmhip_filter_launch_geometry's out[] (include/mmhip.h)
+GEOMETRY_FIELDS = ("tiles_x", "tiles_y", "wg1", "nwg", "ppt", "tile_w", "tile_h", "unroll", "pair_mode", "single_pixel",
+                   "xcd_order", "tiles_magic", "xcd_full")
 
 
 class MathMapError(RuntimeError):
@@ -137,6 +140,23 @@ class Filter:
     @property
     def num_native_calls(self):
         return lib().mmhip_filter_num_native_calls(self._h)
+
+    def launch_geometry(self, region_w, num_rows, closure=None):
+        """How the pixel kernel is launched over `num_rows` rows of a `region_w`-wide region (the geometry mmhip_render
+        takes, MMHIP_PPT included) -- or, with `closure` = k, how closure image #k is launched over a region_w x
+        num_rows frame.  A dict of the GEOMETRY_FIELDS."""
+        out = (C.c_int64 * len(GEOMETRY_FIELDS))()
+        if closure is None:
+            rc = lib().mmhip_filter_launch_geometry(self._h, region_w, num_rows, out)
+        else:
+            rc = lib().mmhip_filter_closure_launch_geometry(self._h, closure, region_w, num_rows, out)
+        if rc != 0:
+            raise MathMapError(_err())
+        return dict(zip(GEOMETRY_FIELDS, out))
+
+    @property
+    def num_closures(self):
+        return lib().mmhip_filter_num_closures(self._h)
 
     def jit(self, load=False):
         """hiprtc-compiles the kernel string for gfx950; returns the code-object size."""

@@ -1,5 +1,5 @@
 // Device side of the every-float check of the real one-argument math ops (test scaffolding: linked into
-// tests/libmathmap_hip_selftest.so, not into the product library).  The kernel evaluates what a JIT kernel computes for
+// mathmap_amd/libmathmap_hip_selftest.so, not into the product library).  The kernel evaluates what a JIT kernel computes for
 // `op` of a float -- the functions hipgen.cpp names -- on runs of consecutive float bit patterns; the caller compares with
 // glibc's double function rounded to float (oracle/libm_ref.c, same op numbering).  No host run can exercise the platform's
 // (OCML's) functions, which most of these ops are; this does, for every argument.

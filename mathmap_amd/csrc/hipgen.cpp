@@ -1254,6 +1254,7 @@ struct Generator {
             int xo = 2;
             (void)stmts;
             if (const char *e = getenv("MMHIP_XCD_ORDER")) xo = atoi(e);
+            ks.xcd_order = xo;
             out << "#define MM_XCD_ORDER " << xo << "\n";
         }
         if (const char *e = getenv("MMHIP_PAIR_MASKS")) out << "#define MM_PAIR_MASKS " << atoi(e) << "\n";
@@ -1267,6 +1268,7 @@ struct Generator {
         ks.unroll = opt.unroll > 0 ? opt.unroll : auto_unroll();
         pair_mode = opt.unroll <= 0 && !getenv("MMHIP_UNROLL") && ks.row_values == 0 && pair_eligible();   // (row values are per pixel of a pair)
         if (pair_mode) { ks.unroll = 2; pair_infer_bools(); }
+        ks.pair_mode = pair_mode;
         out << "#define MM_UNROLL " << ks.unroll << "\n";
         out << "#define MM_NATIVE_REC_BYTES " << (int)MM_NATIVE_REC_BYTES << "\n#define MM_NATIVE_DYN_CALLS " << (int)MM_NATIVE_DYN_CALLS << "\n";
         // float-argument sin/cos (mm_fastmath.h), the same text the host verifier compiles; it
@@ -1438,6 +1440,7 @@ MM_DEV mm_image mm_native_result_in_loop(const mm_args &A, int &n, int sites) {
         }
         if (ks.single_pixel) {
             ks.unroll = 1;
+            ks.pair_mode = false;
             out << "  const int rl = row0;   // A.ppt is 1 for this kernel (KernelSource::single_pixel)\n"
                    "  if (rl >= A.num_rows) return;\n"
                    "  const float y = A.ytab[rl];    // CALC_VIRTUAL_Y(first_row + rl, ...), once per row by the prologue\n"

@@ -654,14 +654,54 @@ static int upload_tables(mmhip_invocation *inv, hipStream_t s) {
     return 0;
 }
 
-static int rows_per_item(const KernelSource &ks, int tiles_x, int num_rows) {
+// The launch geometry of a pixel kernel over `num_rows` rows of a `region_w`-wide region: the one place both launch
+// sites (mmhip_render, render_closure) and mmhip_filter_launch_geometry take it from.
+struct LaunchGeometry {
+    int tiles_x = 0, tiles_y = 0;
+    long wg1 = 0;                 // workgroups at one row per work-item: what the rows-per-item choice is made from
+    long nwg = 0;                 // workgroups of the launch
+    int ppt = 1;                  // rows per work-item (mm_args.ppt)
+    uint32_t tiles_magic = 0;     // mm_args.tiles_magic
+};
+
+static LaunchGeometry launch_geometry(const KernelSource &ks, int region_w, int num_rows) {
+    LaunchGeometry g;
+    g.tiles_x = (region_w + ks.tile_w - 1) / ks.tile_w;
     // rows per work-item: enough workgroups must remain to fill 256 CUs several times over
-    const long wg1 = (long)tiles_x * ((num_rows + ks.tile_h - 1) / ks.tile_h);
-    int ppt = wg1 >= 262144 ? 16 : wg1 >= 131072 ? 8 : wg1 >= 32768 ? 4 : wg1 >= 8192 ? 2 : 1;
+    g.wg1 = (long)g.tiles_x * ((num_rows + ks.tile_h - 1) / ks.tile_h);
+    int ppt = g.wg1 >= 262144 ? 16 : g.wg1 >= 131072 ? 8 : g.wg1 >= 32768 ? 4 : g.wg1 >= 8192 ? 2 : 1;
     if (const char *e = getenv("MMHIP_PPT")) ppt = std::max(1, atoi(e));
     if (ks.single_pixel) ppt = 1;
     const int u = std::max(1, ks.unroll);          // the kernel steps MM_UNROLL rows at a time
-    return (ppt + u - 1) / u * u;
+    g.ppt = (ppt + u - 1) / u * u;
+    g.tiles_y = (num_rows + ks.tile_h * g.ppt - 1) / (ks.tile_h * g.ppt);
+    g.nwg = (long)g.tiles_x * g.tiles_y;
+    g.tiles_magic = tile_division_magic(g.tiles_x, g.nwg);
+    return g;
+}
+
+static int geometry_out(const KernelSource &ks, int region_w, int num_rows, int64_t *out) {
+    if (region_w < 1 || num_rows < 1) return fail("launch geometry: empty region");
+    const LaunchGeometry g = launch_geometry(ks, region_w, num_rows);
+    // the kernel's XCD order 2 swizzles the first `full' workgroups: whole rounds of 8 runs of 2^m tiles (hipgen.cpp)
+    int m = 0;
+    for (unsigned v = (unsigned)(g.tiles_x > 1 ? g.tiles_x - 1 : 1); v; v >>= 1) ++m;
+    const int64_t v[MMHIP_GEOMETRY_FIELDS] = {g.tiles_x, g.tiles_y, g.wg1, g.nwg, g.ppt, ks.tile_w, ks.tile_h, ks.unroll,
+                                              ks.pair_mode, ks.single_pixel, ks.xcd_order, (int64_t)g.tiles_magic,
+                                              (g.nwg >> (m + 3)) << (m + 3)};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+int mmhip_filter_launch_geometry(const mmhip_filter *f, int region_w, int num_rows, int64_t *out) {
+    return geometry_out(f->ks, region_w, num_rows, out);
+}
+
+int mmhip_filter_num_closures(const mmhip_filter *f) { return (int)f->closures.size(); }
+
+int mmhip_filter_closure_launch_geometry(const mmhip_filter *f, int closure, int width, int height, int64_t *out) {
+    if (closure < 0 || closure >= (int)f->closures.size()) return fail("launch geometry: no such closure image");
+    return geometry_out(f->closures[closure].ks, width, height, out);
 }
 
 // render_image's closure branch (builtins.c:273-298): closure image #cid of the filter rendered over the
@@ -765,10 +805,9 @@ static int render_closure(mmhip_invocation *inv, mmhip_filter *f, int cid, const
     a.out = st.map;
     a.xtab = st.d_xtab;
     a.ytab = st.d_ytab;
-    const int tiles_x = (w + ck.ks.tile_w - 1) / ck.ks.tile_w;
-    a.ppt = rows_per_item(ck.ks, tiles_x, h);
-    const int tiles_y = (h + ck.ks.tile_h * a.ppt - 1) / (ck.ks.tile_h * a.ppt);
-    a.tiles_magic = tile_division_magic(tiles_x, (long)tiles_x * tiles_y);
+    const LaunchGeometry geo = launch_geometry(ck.ks, w, h);
+    a.ppt = geo.ppt;
+    a.tiles_magic = geo.tiles_magic;
     char *xy = st.d_xy;
     void *params[] = {&a, &xy};
     const int n = std::max(w, h);
@@ -829,7 +868,7 @@ static int render_closure(mmhip_invocation *inv, mmhip_filter *f, int cid, const
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipMemcpy(inv->d_images, inv->images.data(), inv->images.size() * sizeof(HImageDesc), hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipModuleLaunchKernel(ck.f_pix, (unsigned)((long)tiles_x * tiles_y), 1, 1, 256, 1, 1, 0, s, params, nullptr));
+    HIP_TRY(hipModuleLaunchKernel(ck.f_pix, (unsigned)geo.nwg, 1, 1, 256, 1, 1, 0, s, params, nullptr));
     return 0;
 }
 
@@ -1215,12 +1254,11 @@ int mmhip_render(mmhip_invocation *inv, int frame, float t, int region_x, int re
             inv->pro_generation = inv->table_generation;
         }
     }
-    int tiles_x = (region_w + f->ks.tile_w - 1) / f->ks.tile_w;
-    a.ppt = rows_per_item(f->ks, tiles_x, a.num_rows);
-    int tiles_y = (a.num_rows + f->ks.tile_h * a.ppt - 1) / (f->ks.tile_h * a.ppt);
-    long nwg = (long)tiles_x * tiles_y;
+    const LaunchGeometry geo = launch_geometry(f->ks, region_w, a.num_rows);
+    const long nwg = geo.nwg;
     if (nwg > 0x7fffffffL) return fail("region too large for one launch");
-    a.tiles_magic = tile_division_magic(tiles_x, nwg);
+    a.ppt = geo.ppt;
+    a.tiles_magic = geo.tiles_magic;
     if (inv->timing) {
         if (next_event_pair(inv) != 0) return -1;
         HIP_TRY(hipEventRecord(inv->ev0, s));
