@@ -56,8 +56,7 @@ struct ModuleInfo {
     std::function<mmhip_filter *(const KernelOptions &, std::string *)> build;
     std::map<mmabi_input_drawable_t *, DrawableCopy> drawables;
     std::map<const float *, void *> floatmaps;
-    void *staging = nullptr;
-    size_t staging_bytes = 0;
+    DeviceBuffer staging;
 };
 
 std::mutex g_registry_mu;
@@ -477,23 +476,17 @@ void hip_calc_lines(mmabi_slice_t *slice, mmabi_image_t *closure, int first_row,
     int bpp = inv->output_bpp;
     size_t dev_stride = floatmap ? (size_t)frame->frame_render_width * 16 : (size_t)slice->region_width * bpp;
     size_t need = dev_stride * rows;
-    if (need > mi->staging_bytes) {
-        if (mi->staging) (void)hipFree(mi->staging);
-        mi->staging = nullptr;
-        mi->staging_bytes = 0;
-        if (hipMalloc(&mi->staging, need) != hipSuccess) { host_error("HIP backend: out of device memory"); return; }
-        mi->staging_bytes = need;
-    }
+    if (mi->staging.grow(need) != hipSuccess) { host_error("HIP backend: out of device memory"); return; }
     int rc = mmhip_render(hi, frame->current_frame, frame->current_t, slice->region_x, slice->region_y, slice->region_width,
-                          slice->region_height, first_row, last_row, mi->staging, (int)dev_stride, bpp, floatmap, nullptr);
+                          slice->region_height, first_row, last_row, mi->staging.get(), (int)dev_stride, bpp, floatmap, nullptr);
     if (rc != 0) { host_error(std::string("HIP backend: ") + mmhip_last_error()); return; }
     mmhip_sync(hi);
     if (floatmap) {
         // rows are frame_render_width float4s apart on both sides (new_template.c.in:297); only the
         // region's columns were rendered
-        (void)hipMemcpy2D(q, dev_stride, mi->staging, dev_stride, (size_t)slice->region_width * 16, (size_t)rows, hipMemcpyDeviceToHost);
+        (void)hipMemcpy2D(q, dev_stride, mi->staging.get(), dev_stride, (size_t)slice->region_width * 16, (size_t)rows, hipMemcpyDeviceToHost);
     } else {
-        (void)hipMemcpy2D(q, (size_t)inv->row_stride, mi->staging, dev_stride, dev_stride, (size_t)rows, hipMemcpyDeviceToHost);
+        (void)hipMemcpy2D(q, (size_t)inv->row_stride, mi->staging.get(), dev_stride, dev_stride, (size_t)rows, hipMemcpyDeviceToHost);
     }
     // new_template.c.in:307-308
     if (!inv->supersampling && inv->rows_finished)
@@ -761,7 +754,6 @@ void unload_hip_code(void *module_info) {
         mmhip_filter_free(v.second.flt);
     }
     for (auto &d : mi->drawables) if (d.second.dev) (void)hipFree(d.second.dev);
-    if (mi->staging) (void)hipFree(mi->staging);
     delete mi;
 }
 
@@ -785,9 +777,7 @@ void mathmap_hip_invalidate_drawable(mmabi_input_drawable_t *drawable) {
     if (d != mi->drawables.end()) {
         for (auto &v : mi->variants)            // no invocation may keep the freed pointer bound
             for (auto &i : v.second.invs)
-                if (i.second)
-                    for (auto &img : i.second->images)
-                        if (img.data == d->second.dev) { img.kind = IMG_NULL; img.data = nullptr; i.second->tables_dirty = true; ++i.second->input_generation; }
+                if (i.second) mmhip_unbind_image(i.second, d->second.dev);
         (void)hipDeviceSynchronize();
         if (d->second.dev) (void)hipFree(d->second.dev);
         mi->drawables.erase(d);

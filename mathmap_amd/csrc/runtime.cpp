@@ -319,6 +319,8 @@ mmhip_invocation *mmhip_invoke(mmhip_filter *f, int img_width, int img_height) {
     const auto &uvs = f->module.main->uservals;
     inv->uv.resize(std::max<size_t>(uvs.size(), 1));
     inv->image_slot_of_uv.assign(uvs.size(), -1);
+    HImageDesc null_desc{};
+    null_desc.kind = IMG_NULL;
     for (const UservalInfo &u : uvs) {   // defaults: userval.c:361-409
         HUserval &v = inv->uv[u.index];
         v.i = 0;
@@ -344,87 +346,49 @@ mmhip_invocation *mmhip_invoke(mmhip_filter *f, int img_width, int img_height) {
             case UvKind::Image: {
                 int slot = (int)inv->images.size();
                 inv->image_slot_of_uv[u.index] = slot;
-                HImageDesc d{};
-                d.kind = IMG_NULL;
-                inv->images.push_back(d);
+                inv->images.push_back(null_desc);
                 v.image = slot;
                 break;
             }
         }
     }
     inv->native_slot_base = (int)inv->images.size();
-    for (size_t k = 0; k < f->ks.natives.size(); ++k) {
-        HImageDesc d{};
-        d.kind = IMG_NULL;
-        inv->images.push_back(d);
-    }
+    inv->natives.resize(f->ks.natives.size());
+    inv->images.resize(inv->images.size() + inv->natives.size(), null_desc);
     inv->closure_state.resize(f->closures.size());
     for (size_t c = 0; c < f->closures.size(); ++c) {      // the closure kernels' own native-filter results: slots of their own
         auto &st = inv->closure_state[c];
         st.native_slot_base = (int)inv->images.size();
-        st.native_maps.assign(f->closures[c].ks.natives.size(), nullptr);
-        for (size_t k = 0; k < f->closures[c].ks.natives.size(); ++k) {
-            HImageDesc d{};
-            d.kind = IMG_NULL;
-            inv->images.push_back(d);
-        }
+        st.native_results.resize(f->closures[c].ks.natives.size());
+        inv->images.resize(inv->images.size() + st.native_results.size(), null_desc);
     }
-    inv->native_maps.assign(f->ks.natives.size(), nullptr);
-    inv->native_map_size.assign(f->ks.natives.size(), {0, 0});
-    inv->native_gen.assign(f->ks.natives.size(), 0);
-    inv->native_memo_deps.assign(f->ks.natives.size(), {});
-    inv->native_memo.resize(f->ks.natives.size());
-    inv->native_memo_gen.assign(f->ks.natives.size(), 0);
-    inv->native_seen.resize(f->ks.natives.size());
-    inv->native_seen_gen.assign(f->ks.natives.size(), ~0ULL);
-    inv->native_rows.assign(f->ks.natives.size(), {0, 0});
-    if (inv->images.empty()) { HImageDesc d{}; d.kind = IMG_NULL; inv->images.push_back(d); }
+    if (inv->images.empty()) inv->images.push_back(null_desc);
     auto bail = [&](const char *what, hipError_t e) -> mmhip_invocation * {
         fail(std::string(what) + ": " + hipGetErrorString(e));
         return nullptr;
     };
     hipError_t e;
-    if ((e = hipStreamCreate(&inv->stream)) != hipSuccess) return bail("hipStreamCreate", e);
-    if ((e = hipMalloc((void **)&inv->d_uv, inv->uv.size() * sizeof(HUserval))) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMalloc((void **)&inv->d_images, inv->images.size() * sizeof(HImageDesc))) != hipSuccess) return bail("hipMalloc", e);
+    if ((e = hipStreamCreate(&inv->stream.s)) != hipSuccess) return bail("hipStreamCreate", e);
+    if ((e = inv->d_uv.grow(inv->uv.size() * sizeof(HUserval))) != hipSuccess) return bail("hipMalloc", e);
+    if ((e = inv->d_images.grow(inv->images.size() * sizeof(HImageDesc))) != hipSuccess) return bail("hipMalloc", e);
+    if ((e = inv->d_curves.grow(inv->curves.size() * 4)) != hipSuccess) return bail("hipMalloc", e);
+    if ((e = inv->d_gradients.grow(inv->gradients.size() * 4)) != hipSuccess) return bail("hipMalloc", e);
     const int xy_bytes = std::max(f->ks.xy_bytes, 256);
-    if ((e = hipMalloc((void **)&inv->d_xy, xy_bytes)) != hipSuccess) return bail("hipMalloc", e);
-    if (!inv->curves.empty() && (e = hipMalloc((void **)&inv->d_curves, inv->curves.size() * 4)) != hipSuccess) return bail("hipMalloc", e);
-    if (!inv->gradients.empty() && (e = hipMalloc((void **)&inv->d_gradients, inv->gradients.size() * 4)) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMemset(inv->d_xy, 0, xy_bytes)) != hipSuccess) return bail("hipMemset", e);
-    inv->xy_cap = xy_bytes;
+    if ((e = inv->launch.xy.grow(xy_bytes, DeviceBuffer::no_wait, true)) != hipSuccess) return bail("hipMalloc", e);
     return inv.release();
 }
 
-void mmhip_invocation_free(mmhip_invocation *inv) {
-    if (!inv) return;
-    if (inv->stream) (void)hipStreamSynchronize(inv->stream);
-    for (void *p : inv->owned) (void)hipFree(p);
-    for (void *p : inv->native_maps) if (p) (void)hipFree(p);
-    if (inv->ss_lines) (void)hipFree(inv->ss_lines);
-    for (auto &c : inv->closure_state) {
-        if (c.map) (void)hipFree(c.map);
-        if (c.d_xy) (void)hipFree(c.d_xy);
-        if (c.d_xtab) (void)hipFree(c.d_xtab);
-        if (c.d_ytab) (void)hipFree(c.d_ytab);
-        for (void *p : c.native_maps) if (p) (void)hipFree(p);
-    }
-    inv->ws.release();
-    if (inv->d_uv) (void)hipFree(inv->d_uv);
-    if (inv->d_images) (void)hipFree(inv->d_images);
-    if (inv->d_xy) (void)hipFree(inv->d_xy);
-    if (inv->d_xtab) (void)hipFree(inv->d_xtab);
-    if (inv->d_ytab) (void)hipFree(inv->d_ytab);
-    if (inv->d_rowtab) (void)hipFree(inv->d_rowtab);
-    if (inv->d_curves) (void)hipFree(inv->d_curves);
-    if (inv->d_gradients) (void)hipFree(inv->d_gradients);
-    for (auto &p : inv->ev_pool) {
+// Once the invocation's stream is idle the members go: the buffers are freed, the stream is destroyed last.
+mmhip_invocation::~mmhip_invocation() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    ws.release();
+    for (auto &p : ev_pool) {
         (void)hipEventDestroy(p.first);
         (void)hipEventDestroy(p.second);
     }
-    if (inv->stream) (void)hipStreamDestroy(inv->stream);
-    delete inv;
 }
+
+void mmhip_invocation_free(mmhip_invocation *inv) { delete inv; }
 
 static const UservalInfo *uv_info(mmhip_invocation *inv, int index, UvKind kind) {
     const auto &uvs = inv->f->module.main->uservals;
@@ -493,15 +457,47 @@ static void fill_drawable_desc(HImageDesc &d, const void *data, int w, int h) {
     d.ax = d.bx = d.ay = d.by = 0.f;
 }
 
+// A native float map (the result of a native filter, or a closure image rendered for one) as the kernels read it.
+static HImageDesc floatmap_desc(const void *data, int w, int h) {
+    HImageDesc d{};
+    d.data = data;
+    d.w = w;
+    d.h = h;
+    d.kind = IMG_FLOATMAP;
+    d.num_frames = 1;
+    d.ax = d.bx = (float)((float)(w - 1) / 2.0);     // floatmap.c:39-41
+    d.ay = d.by = (float)((float)(h - 1) / 2.0);
+    d.ay *= -1.0f;
+    return d;
+}
+
+// An input image was bound or unbound: the tables go up again, and every native result is stale.
+static void input_changed(mmhip_invocation *inv) {
+    inv->tables_dirty = true;
+    ++inv->input_generation;
+}
+
 int mmhip_set_image_device(mmhip_invocation *inv, int index, const void *device_rgba32, int width, int height) {
     const UservalInfo *u = uv_info(inv, index, UvKind::Image);
     if (!u) return -1;
     int slot = inv->image_slot_of_uv[index];
     fill_drawable_desc(inv->images[slot], device_rgba32, width, height);
-    inv->tables_dirty = true;
-    ++inv->input_generation;
+    input_changed(inv);
     return 0;
 }
+
+}  // extern "C"
+
+void mmhip_unbind_image(mmhip_invocation *inv, const void *data) {
+    for (HImageDesc &img : inv->images)
+        if (img.data == data) {
+            img.kind = IMG_NULL;
+            img.data = nullptr;
+            input_changed(inv);
+        }
+}
+
+extern "C" {
 
 int mmhip_set_image_host(mmhip_invocation *inv, int index, const uint8_t *pixels, int width, int height, int channels) {
     if (channels != 3 && channels != 4) return fail("channels must be 3 or 4");
@@ -513,20 +509,20 @@ int mmhip_set_image_host(mmhip_invocation *inv, int index, const uint8_t *pixels
         uint32_t a = channels == 4 ? p[3] : 255u;
         packed[i] = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | a;
     }
-    void *d = nullptr;
-    HIP_TRY(hipMalloc(&d, n * 4));
-    HIP_TRY(hipMemcpy(d, packed.data(), n * 4, hipMemcpyHostToDevice));
+    DeviceBuffer d;
+    HIP_TRY(d.grow(n * 4));
+    HIP_TRY(hipMemcpy(d.get(), packed.data(), n * 4, hipMemcpyHostToDevice));
     // the upload this one replaces (if it was ours) is freed once nothing in flight reads it
     const void *old = inv->images[inv->image_slot_of_uv[index]].data;
-    for (size_t i = 0; i < inv->owned.size(); ++i)
-        if (inv->owned[i] == old) {
+    for (auto it = inv->owned.begin(); it != inv->owned.end(); ++it)
+        if (it->get() == old) {
             (void)hipDeviceSynchronize();     // renders may have been queued on caller streams
-            (void)hipFree(inv->owned[i]);
-            inv->owned.erase(inv->owned.begin() + i);
+            inv->owned.erase(it);
             break;
         }
-    inv->owned.push_back(d);
-    return mmhip_set_image_device(inv, index, d, width, height);
+    const void *dev = d.get();
+    inv->owned.push_back(std::move(d));
+    return mmhip_set_image_device(inv, index, dev, width, height);
 }
 
 int mmhip_set_curve(mmhip_invocation *inv, int index, const float *values1024) {
@@ -641,14 +637,19 @@ double mmhip_last_kernel_ms(mmhip_invocation *inv) {
     return ms;
 }
 
+// the image table to the device, once nothing in flight on `s` still reads the old one
+static int upload_image_table(mmhip_invocation *inv, hipStream_t s) {
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(inv->d_images.get(), inv->images.data(), inv->images.size() * sizeof(HImageDesc), hipMemcpyHostToDevice));
+    return 0;
+}
+
 static int upload_tables(mmhip_invocation *inv, hipStream_t s) {
     if (!inv->tables_dirty) return 0;
-    // make sure nothing in flight still reads the old tables
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(inv->d_uv, inv->uv.data(), inv->uv.size() * sizeof(HUserval), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(inv->d_images, inv->images.data(), inv->images.size() * sizeof(HImageDesc), hipMemcpyHostToDevice));
-    if (inv->d_curves) HIP_TRY(hipMemcpy(inv->d_curves, inv->curves.data(), inv->curves.size() * 4, hipMemcpyHostToDevice));
-    if (inv->d_gradients) HIP_TRY(hipMemcpy(inv->d_gradients, inv->gradients.data(), inv->gradients.size() * 4, hipMemcpyHostToDevice));
+    if (upload_image_table(inv, s) != 0) return -1;
+    HIP_TRY(hipMemcpy(inv->d_uv.get(), inv->uv.data(), inv->uv.size() * sizeof(HUserval), hipMemcpyHostToDevice));
+    if (inv->d_curves) HIP_TRY(hipMemcpy(inv->d_curves.get(), inv->curves.data(), inv->curves.size() * 4, hipMemcpyHostToDevice));
+    if (inv->d_gradients) HIP_TRY(hipMemcpy(inv->d_gradients.get(), inv->gradients.data(), inv->gradients.size() * 4, hipMemcpyHostToDevice));
     inv->tables_dirty = false;
     ++inv->table_generation;
     return 0;
@@ -702,6 +703,17 @@ int mmhip_filter_num_closures(const mmhip_filter *f) { return (int)f->closures.s
 int mmhip_filter_closure_launch_geometry(const mmhip_filter *f, int closure, int width, int height, int64_t *out) {
     if (closure < 0 || closure >= (int)f->closures.size()) return fail("launch geometry: no such closure image");
     return geometry_out(f->closures[closure].ks, width, height, out);
+}
+
+// The buffers of a launch of `ks` over `num_rows` rows of a `region_w`-wide region, grown on demand (stream order protects
+// re-use): coordinate tables, with `rows` the per-row values, and the frame constants (zero-filled when new).
+static int grow_launch_buffers(LaunchBuffers &b, const KernelSource &ks, int region_w, int num_rows, bool rows, hipStream_t s) {
+    auto wait = [s] { return hipStreamSynchronize(s); };
+    HIP_TRY(b.xtab.grow((size_t)region_w * sizeof(float), wait));
+    HIP_TRY(b.ytab.grow((size_t)num_rows * sizeof(float), wait));
+    if (rows) HIP_TRY(b.rowtab.grow((size_t)ks.row_values * num_rows * sizeof(float), wait));
+    HIP_TRY(b.xy.grow(std::max(ks.xy_bytes, 256), wait, true));
+    return 0;
 }
 
 // render_image's closure branch (builtins.c:273-298): closure image #cid of the filter rendered over the
@@ -766,30 +778,17 @@ static int render_closure(mmhip_invocation *inv, mmhip_filter *f, int cid, const
     mmhip_closure_kernel &ck = f->closures[cid];
     auto &st = inv->closure_state[cid];
     const int w = main_args.render_width, h = main_args.render_height;
-    if (st.map && (st.w != w || st.h != h)) {
+    if (st.map && (st.w != w || st.h != h)) {      // the map and the closure's own native maps follow the render size
         HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(st.map);
-        st.map = nullptr;
-        for (void *&p : st.native_maps) { if (p) (void)hipFree(p); p = nullptr; }
+        st.map.reset();
+        for (DeviceBuffer &m : st.native_results) m.reset();
     }
-    if (!st.map) { HIP_TRY(hipMalloc(&st.map, (size_t)w * h * 16)); st.w = w; st.h = h; }
-    if (w > st.xtab_cap) {
-        if (st.d_xtab) { HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(st.d_xtab); }
-        HIP_TRY(hipMalloc((void **)&st.d_xtab, (size_t)w * sizeof(float)));
-        st.xtab_cap = w;
+    if (!st.map) {
+        HIP_TRY(st.map.grow((size_t)w * h * 16));
+        st.w = w;
+        st.h = h;
     }
-    if (h > st.ytab_cap) {
-        if (st.d_ytab) { HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(st.d_ytab); }
-        HIP_TRY(hipMalloc((void **)&st.d_ytab, (size_t)h * sizeof(float)));
-        st.ytab_cap = h;
-    }
-    const int xy_bytes = std::max(ck.ks.xy_bytes, 256);
-    if (xy_bytes > st.xy_cap) {
-        if (st.d_xy) { HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(st.d_xy); }
-        HIP_TRY(hipMalloc((void **)&st.d_xy, xy_bytes));
-        HIP_TRY(hipMemset(st.d_xy, 0, xy_bytes));
-        st.xy_cap = xy_bytes;
-    }
+    if (grow_launch_buffers(st.launch, ck.ks, w, h, false, s) != 0) return -1;
     // (t and frame stay the frame's own: the closure's *arguments* are values of the main filter's code at the current
     // time; the closure's body is lowered with t = 0.0 and frame = 0 as literals, lower.cpp native_image_argument)
     HArgs a = main_args;
@@ -802,13 +801,13 @@ static int render_closure(mmhip_invocation *inv, mmhip_filter *f, int cid, const
     a.output_bpp = 4;
     a.row_stride = w * 4;
     a.floatmap = 1;
-    a.out = st.map;
-    a.xtab = st.d_xtab;
-    a.ytab = st.d_ytab;
+    a.out = st.map.get();
+    a.xtab = st.launch.xtab.get<float>();
+    a.ytab = st.launch.ytab.get<float>();
     const LaunchGeometry geo = launch_geometry(ck.ks, w, h);
     a.ppt = geo.ppt;
     a.tiles_magic = geo.tiles_magic;
-    char *xy = st.d_xy;
+    char *xy = st.launch.xy.get<char>();
     void *params[] = {&a, &xy};
     const int n = std::max(w, h);
     a.native_slot_base = st.native_slot_base;
@@ -819,7 +818,7 @@ static int render_closure(mmhip_invocation *inv, mmhip_filter *f, int cid, const
         // map of the closure's own.  Like the closure image itself these are recomputed on every render (the reference
         // gives the closure a fresh id: nothing of it is ever found in the cache).
         std::vector<char> host(ck.ks.xy_bytes);
-        HIP_TRY(hipMemcpyAsync(host.data(), st.d_xy, host.size(), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(host.data(), xy, host.size(), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         std::vector<RecordedCall> calls;
         if (recorded_calls(ck.ks, host, &calls) != 0) return -1;
@@ -829,12 +828,11 @@ static int render_closure(mmhip_invocation *inv, mmhip_filter *f, int cid, const
             const HNativeRec &rec = call.rec;
             // a call of the main code's copy: the main code has its result already (same_native_call)
             bool aliased = false;
-            static const bool no_alias = getenv("MMHIP_NO_NATIVE_ALIAS") != nullptr;      // (experiments: run every recorded call)
             for (const RecordedCall &m : main_done) {
-                if (no_alias) break;
                 const int mslot = inv->native_slot_base + (int)m.k;
-                if (!same_native_call(call, m, alias, st.native_slot_base) || !inv->native_maps[m.k] || inv->images[mslot].kind != IMG_FLOATMAP ||
-                    inv->images[mslot].w != w || inv->images[mslot].h != h || inv->native_rows[m.k].first > 0 || inv->native_rows[m.k].second < h)
+                const NativeEntry &me = inv->natives[m.k];
+                if (!same_native_call(call, m, alias, st.native_slot_base) || !me.map || inv->images[mslot].kind != IMG_FLOATMAP ||
+                    inv->images[mslot].w != w || inv->images[mslot].h != h || me.rows.first > 0 || me.rows.second < h)
                     continue;
                 inv->images[st.native_slot_base + (int)k] = inv->images[mslot];      // the same map under the render kernel's handle
                 alias[k] = mslot;
@@ -845,41 +843,25 @@ static int render_closure(mmhip_invocation *inv, mmhip_filter *f, int cid, const
             for (int i = 0; i < rec.nargs && i < 4; ++i)
                 if (rec.args[i].kind == 2 && rec.args[i].img.idx <= -2)
                     return fail("a filter closure rendered for a native filter hands another closure to a native filter: not supported");
-            if (!st.native_maps[k]) HIP_TRY(hipMalloc(&st.native_maps[k], (size_t)w * h * 16));
-            inv->ws.env.supersampling = f->kopt.supersampling;
-            inv->ws.env.edge_x = f->kopt.edge_x;
-            inv->ws.env.edge_y = f->kopt.edge_y;
-            inv->ws.env.edge_color_x = inv->edge_color_x;
-            inv->ws.env.edge_color_y = inv->edge_color_y;
+            HIP_TRY(st.native_results[k].grow((size_t)w * h * 16));
             std::string err;
             int lo = 0, hi = h;
-            if (run_native_filter(*call.func, rec, inv->images, w, h, (float *)st.native_maps[k], inv->ws, s, &err, &lo, &hi) != 0)
+            if (run_native_filter(*call.func, rec, inv->images, w, h, st.native_results[k].get<float>(), inv->ws, s, &err, &lo, &hi) != 0)
                 return fail(err);
-            HImageDesc &d = inv->images[st.native_slot_base + (int)k];
-            d.data = st.native_maps[k];
-            d.w = w;
-            d.h = h;
-            d.kind = IMG_FLOATMAP;
-            d.num_frames = 1;
-            d.ax = d.bx = (float)((float)(d.w - 1) / 2.0);     // floatmap.c:39-41
-            d.ay = d.by = (float)((float)(d.h - 1) / 2.0);
-            d.ay *= -1.0f;
+            inv->images[st.native_slot_base + (int)k] = floatmap_desc(st.native_results[k].get(), w, h);
         }
-        HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipMemcpy(inv->d_images, inv->images.data(), inv->images.size() * sizeof(HImageDesc), hipMemcpyHostToDevice));
+        if (upload_image_table(inv, s) != 0) return -1;
     }
     HIP_TRY(hipModuleLaunchKernel(ck.f_pix, (unsigned)geo.nwg, 1, 1, 256, 1, 1, 0, s, params, nullptr));
     return 0;
 }
 
-static int run_natives(mmhip_invocation *inv, mmhip_filter *f, const HArgs &a, hipStream_t s, bool *direct_written) {
-    std::vector<char> host(f->ks.xy_bytes);
-    HIP_TRY(hipMemcpyAsync(host.data(), inv->d_xy, host.size(), hipMemcpyDeviceToHost, s));
-    // Direct output (hipgen.cpp find_direct_native): the pixel is native result k sampled at (x, y).
-    // If every sample position of this launch is the pixel's own centre -- get_floatmap_pixel's
-    // lrintf(ax x + bx) (builtins.c:247-265) evaluated here for each column and row with the
-    // coordinates the prologue just computed -- the native filter may write the RGBA8 pixels itself.
-    NativeDirectOut direct;
+// Direct output (hipgen.cpp find_direct_native): the pixel is native result k sampled at (x, y).
+// If every sample position of this launch is the pixel's own centre -- get_floatmap_pixel's
+// lrintf(ax x + bx) (builtins.c:247-265) evaluated here for each column and row with the
+// coordinates the prologue just computed -- the native filter may write the RGBA8 pixels itself.
+// Waits for `s', and with it for what the caller queued there before (the frame constants' read-back).
+static int direct_output(const mmhip_filter *f, const HArgs &a, hipStream_t s, NativeDirectOut *direct) {
     const bool try_direct = f->ks.direct_native >= 0 && !a.floatmap && a.output_bpp == 4 && (a.row_stride & 3) == 0 &&
                             ((uintptr_t)a.out & 3) == 0 && !getenv("MMHIP_NO_DIRECT_NATIVE");
     std::vector<float> xt, yt;
@@ -890,139 +872,139 @@ static int run_natives(mmhip_invocation *inv, mmhip_filter *f, const HArgs &a, h
         HIP_TRY(hipMemcpyAsync(yt.data(), a.ytab, yt.size() * sizeof(float), hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
-    if (try_direct) {
-        const float ax = (float)((float)(a.render_width - 1) / 2.0), bx = ax;       // floatmap.c:39-41
-        const float by = (float)((float)(a.render_height - 1) / 2.0), ay = by * -1.0f;
-        bool identity = true;
-        for (int c = 0; c < a.region_width && identity; ++c) identity = lrintf(ax * xt[c] + bx) == (long)a.region_x + c;
-        for (int r = 0; r < a.num_rows && identity; ++r) identity = lrintf(ay * yt[r] + by) == (long)a.first_row + r;
-        if (identity) {
-            direct.out = a.out;
-            direct.row_stride = a.row_stride;
-            direct.first_row = a.first_row;
-            direct.num_rows = a.num_rows;
-            direct.region_x = a.region_x;
-            direct.region_w = a.region_width;
-        }
+    if (!try_direct) return 0;
+    const HImageDesc m = floatmap_desc(nullptr, a.render_width, a.render_height);
+    for (int c = 0; c < a.region_width; ++c)
+        if (lrintf(m.ax * xt[c] + m.bx) != (long)a.region_x + c) return 0;
+    for (int r = 0; r < a.num_rows; ++r)
+        if (lrintf(m.ay * yt[r] + m.by) != (long)a.first_row + r) return 0;
+    direct->out = a.out;
+    direct->row_stride = a.row_stride;
+    direct->first_row = a.first_row;
+    direct->num_rows = a.num_rows;
+    direct->region_x = a.region_x;
+    direct->region_w = a.region_width;
+    return 0;
+}
+
+// Closure images among the arguments (index -2 - id, mm_closure_image): rendered into float maps now and
+// handed to the native filter as such, in `images_k' (a copy of the image table, left empty when the call has
+// none).  The reference gives every closure image a fresh id (image_new_id), so a call on a closure never hits
+// the cache: always recomputed here too.
+static int render_closure_args(mmhip_invocation *inv, mmhip_filter *f, const HArgs &a, hipStream_t s,
+                               const std::vector<RecordedCall> &done, HNativeRec &rec, std::vector<HImageDesc> &images_k) {
+    for (int i = 0; i < rec.nargs && i < 4; ++i) {
+        HImage &img = rec.args[i].img;
+        if (rec.args[i].kind != 2 || img.idx > -2) continue;
+        const int cid = -2 - img.idx;
+        if (cid >= (int)f->closures.size()) return fail("internal: closure image without a render kernel");
+        if (render_closure(inv, f, cid, a, s, done) != 0) return -1;
+        if (images_k.empty()) images_k = inv->images;
+        img.idx = (int)images_k.size();
+        img.pw = a.render_width;
+        img.ph = a.render_height;
+        img.xf = img.yf = 1.0f;      // a plain map: the closure's render kernel has applied the
+        img.resized = 0;             // wrapper's factors to its coordinates already (lower.cpp)
+        images_k.push_back(floatmap_desc(inv->closure_state[cid].map.get(), a.render_width, a.render_height));
     }
+    return 0;
+}
+
+// memo (native-filters/cache.c:110-147): same arguments on unchanged inputs -> keep the map.  `deps' receives the
+// generations of the native maps among the call's image arguments (cache.c keys on image ids).
+static bool memo_hit(const mmhip_invocation *inv, const NativeEntry &e, const HNativeRec &rec, int want_lo, int want_hi,
+                     std::vector<unsigned long long> *deps) {
+    for (int i = 0; i < rec.nargs && i < 4; ++i)
+        if (rec.args[i].kind == 2 && rec.args[i].img.idx >= inv->native_slot_base &&
+            rec.args[i].img.idx < inv->native_slot_base + (int)inv->natives.size())
+            deps->push_back(inv->natives[rec.args[i].img.idx - inv->native_slot_base].gen);
+    return e.map && e.memo_gen == inv->input_generation && memcmp(&e.memo, &rec, sizeof rec) == 0 && e.memo_deps == *deps &&
+           e.rows.first <= want_lo && e.rows.second >= want_hi;
+}
+
+// Native entry k's map goes (the caller has waited for what reads it), and with it its memo and its image-table entry.
+static void drop_native_map(mmhip_invocation *inv, size_t k, bool *table_changed) {
+    NativeEntry &e = inv->natives[k];
+    e.map.reset();
+    e.memo_gen = e.seen_gen = ~0ULL;
+    e.rows = {0, 0};
+    HImageDesc &d = inv->images[inv->native_slot_base + (int)k];
+    d.kind = IMG_NULL;
+    d.data = nullptr;
+    *table_changed = true;
+}
+
+static int run_natives(mmhip_invocation *inv, mmhip_filter *f, const HArgs &a, hipStream_t s, bool *direct_written) {
+    std::vector<char> host(f->ks.xy_bytes);
+    HIP_TRY(hipMemcpyAsync(host.data(), inv->launch.xy.get(), host.size(), hipMemcpyDeviceToHost, s));
+    NativeDirectOut direct;
+    if (direct_output(f, a, s, &direct) != 0) return -1;
+    inv->ws.env.supersampling = f->kopt.supersampling;      // (render_closure runs its native filters with these too)
+    inv->ws.env.edge_x = f->kopt.edge_x;
+    inv->ws.env.edge_y = f->kopt.edge_y;
+    inv->ws.env.edge_color_x = inv->edge_color_x;
+    inv->ws.env.edge_color_y = inv->edge_color_y;
+    // rows of the maps this launch may read: everything, or -- opt-in, full-frame regions only --
+    // the stripe being rendered (the filter samples the map within its own rows +- margin)
+    int want_lo = 0, want_hi = a.render_height;
+    if (inv->native_row_margin >= 0 && a.region_x == 0 && a.region_y == 0 && a.region_width == a.render_width &&
+        a.region_height == a.render_height) {
+        want_lo = std::max(0, a.first_row - inv->native_row_margin);
+        want_hi = std::min(a.render_height, a.first_row + a.num_rows + inv->native_row_margin);
+    }
+    // A launch that covers the whole frame needs the map for nothing but the memo.  The first time
+    // an argument set is seen it is therefore not written (16 of the second pass's 20 B/px); a
+    // second request for the same set -- an animation that keeps the blur's arguments -- computes
+    // it once more, with the map, and is memoised from then on.
+    const bool whole = a.region_x == 0 && a.region_y == 0 && a.region_width == a.render_width &&
+                       a.region_height == a.render_height && a.first_row == 0 && a.num_rows == a.render_height;
     bool table_changed = false;
     std::vector<RecordedCall> calls, done;      // done: calls whose maps stand (what a closure's render kernel may refer to)
     if (recorded_calls(f->ks, host, &calls) != 0) return -1;
     for (const RecordedCall &call : calls) {
         const size_t k = call.k;
+        NativeEntry &e = inv->natives[k];
         HNativeRec rec = call.rec;
-        int slot = inv->native_slot_base + (int)k;
-        // memo (native-filters/cache.c:110-147): same arguments on unchanged inputs -> keep the map
-        // rows of the map this launch may read: everything, or -- opt-in, full-frame regions only --
-        // the stripe being rendered (the filter samples the map within its own rows +- margin)
-        int want_lo = 0, want_hi = a.render_height;
-        if (inv->native_row_margin >= 0 && a.region_x == 0 && a.region_y == 0 && a.region_width == a.render_width &&
-            a.region_height == a.render_height) {
-            want_lo = std::max(0, a.first_row - inv->native_row_margin);
-            want_hi = std::min(a.render_height, a.first_row + a.num_rows + inv->native_row_margin);
-        }
         // A map belongs to the render size it was allocated for: the GIMP flow renders a small preview
         // and then the full image on one invocation (mathmap.c:2191-2223).  On a change the map is
         // reallocated and everything remembered about it dropped.
-        if (inv->native_maps[k] && (inv->native_map_size[k].first != a.render_width || inv->native_map_size[k].second != a.render_height)) {
+        if (e.map && (e.w != a.render_width || e.h != a.render_height)) {
             HIP_TRY(hipDeviceSynchronize());
-            (void)hipFree(inv->native_maps[k]);
-            inv->native_maps[k] = nullptr;
-            inv->native_memo_gen[k] = ~0ULL;
-            inv->native_seen_gen[k] = ~0ULL;
-            inv->native_rows[k] = {0, 0};
-            inv->images[slot].kind = IMG_NULL;
-            inv->images[slot].data = nullptr;
-            table_changed = true;
+            drop_native_map(inv, k, &table_changed);
         }
-        // Closure images among the arguments (index -2 - id, mm_closure_image): rendered into float maps now and
-        // handed to the native filter as such.  The reference gives every closure image a fresh id
-        // (image_new_id), so a call on a closure never hits the cache: always recomputed here too.
-        std::vector<HImageDesc> images_k;                 // inv->images + the rendered closures, only when needed
-        bool has_closure_arg = false;
-        for (int i = 0; i < rec.nargs && i < 4; ++i) {
-            if (rec.args[i].kind != 2 || rec.args[i].img.idx > -2) continue;
-            const int cid = -2 - rec.args[i].img.idx;
-            if (cid >= (int)f->closures.size()) return fail("internal: closure image without a render kernel");
-            if (render_closure(inv, f, cid, a, s, done) != 0) return -1;
-            if (images_k.empty()) images_k = inv->images;
-            HImageDesc d{};
-            d.data = inv->closure_state[cid].map;
-            d.w = a.render_width;
-            d.h = a.render_height;
-            d.kind = IMG_FLOATMAP;
-            d.num_frames = 1;
-            d.ax = d.bx = (float)((float)(d.w - 1) / 2.0);
-            d.ay = d.by = (float)((float)(d.h - 1) / 2.0);
-            d.ay *= -1.0f;
-            rec.args[i].img.idx = (int)images_k.size();
-            rec.args[i].img.pw = d.w;
-            rec.args[i].img.ph = d.h;
-            rec.args[i].img.xf = rec.args[i].img.yf = 1.0f;      // a plain map: the closure's render kernel has applied the
-            rec.args[i].img.resized = 0;                          // wrapper's factors to its coordinates already (lower.cpp)
-            images_k.push_back(d);
-            has_closure_arg = true;
-        }
-        // generations of the native maps among this call's image arguments (cache.c keys on image ids)
+        std::vector<HImageDesc> images_k;
+        if (render_closure_args(inv, f, a, s, done, rec, images_k) != 0) return -1;
         std::vector<unsigned long long> deps;
-        for (int i = 0; i < rec.nargs && i < 4; ++i)
-            if (rec.args[i].kind == 2 && rec.args[i].img.idx >= inv->native_slot_base &&
-                rec.args[i].img.idx < inv->native_slot_base + (int)inv->native_gen.size())
-                deps.push_back(inv->native_gen[rec.args[i].img.idx - inv->native_slot_base]);
-        if (!has_closure_arg && inv->native_maps[k] && inv->native_memo_gen[k] == inv->input_generation &&
-            memcmp(&inv->native_memo[k], &rec, sizeof rec) == 0 && inv->native_memo_deps[k] == deps &&
-            inv->native_rows[k].first <= want_lo && inv->native_rows[k].second >= want_hi) {
+        if (memo_hit(inv, e, rec, want_lo, want_hi, &deps) && images_k.empty()) {
             done.push_back(call);
             continue;
         }
-        size_t bytes = (size_t)a.render_width * a.render_height * 16;
-        if (!inv->native_maps[k]) {
-            HIP_TRY(hipMalloc(&inv->native_maps[k], bytes));
-            inv->native_map_size[k] = {a.render_width, a.render_height};
-        }
+        HIP_TRY(e.map.grow((size_t)a.render_width * a.render_height * 16));
+        e.w = a.render_width;
+        e.h = a.render_height;
         std::string err;
         int got_lo = want_lo, got_hi = want_hi;
         NativeDirectOut *dk = (direct.out && (int)k == f->ks.direct_native) ? &direct : nullptr;
-        // A launch that covers the whole frame needs the map for nothing but the memo.  The first time
-        // an argument set is seen it is therefore not written (16 of the second pass's 20 B/px); a
-        // second request for the same set -- an animation that keeps the blur's arguments -- computes
-        // it once more, with the map, and is memoised from then on.
-        const bool whole = a.region_x == 0 && a.region_y == 0 && a.region_width == a.render_width &&
-                           a.region_height == a.render_height && a.first_row == 0 && a.num_rows == a.render_height;
         if (dk) {
-            dk->skip_map = whole && !(inv->native_seen_gen[k] == inv->input_generation && inv->native_memo_deps[k] == deps &&
-                                      memcmp(&inv->native_seen[k], &rec, sizeof rec) == 0);
-            inv->native_seen[k] = rec;
-            inv->native_seen_gen[k] = inv->input_generation;
+            dk->skip_map = whole && !(e.seen_gen == inv->input_generation && e.memo_deps == deps && memcmp(&e.seen, &rec, sizeof rec) == 0);
+            e.seen = rec;
+            e.seen_gen = inv->input_generation;
         }
-        inv->ws.env.supersampling = f->kopt.supersampling;
-        inv->ws.env.edge_x = f->kopt.edge_x;
-        inv->ws.env.edge_y = f->kopt.edge_y;
-        inv->ws.env.edge_color_x = inv->edge_color_x;
-        inv->ws.env.edge_color_y = inv->edge_color_y;
-        int rc = run_native_filter(*call.func, rec, has_closure_arg ? images_k : inv->images, a.render_width, a.render_height,
-                                   (float *)inv->native_maps[k], inv->ws, s, &err, &got_lo, &got_hi, dk);
-        if (rc != 0) return fail(err);
-        inv->native_gen[k] = ++inv->native_gen_counter;
-        inv->native_memo_deps[k] = deps;
+        if (run_native_filter(*call.func, rec, images_k.empty() ? inv->images : images_k, a.render_width, a.render_height,
+                              e.map.get<float>(), inv->ws, s, &err, &got_lo, &got_hi, dk) != 0)
+            return fail(err);
+        e.gen = ++inv->native_gen_counter;
+        e.memo_deps = deps;
         if (dk && dk->written) *direct_written = true;
         if (dk && dk->written && dk->skip_map) {       // nothing to memoise, no map to describe
-            inv->native_memo_gen[k] = ~0ULL;
-            inv->native_rows[k] = {0, 0};
+            e.memo_gen = ~0ULL;
+            e.rows = {0, 0};
             continue;
         }
-        HImageDesc &d = inv->images[slot];
-        d.data = inv->native_maps[k];
-        d.w = a.render_width;
-        d.h = a.render_height;
-        d.kind = IMG_FLOATMAP;
-        d.num_frames = 1;
-        d.ax = d.bx = (float)((float)(d.w - 1) / 2.0);     // floatmap.c:39-41
-        d.ay = d.by = (float)((float)(d.h - 1) / 2.0);
-        d.ay *= -1.0f;
-        inv->native_memo[k] = rec;
-        inv->native_memo_gen[k] = inv->input_generation;
-        inv->native_rows[k] = {got_lo, got_hi};
+        inv->images[inv->native_slot_base + (int)k] = floatmap_desc(e.map.get(), a.render_width, a.render_height);
+        e.memo = rec;
+        e.memo_gen = inv->input_generation;
+        e.rows = {got_lo, got_hi};
         table_changed = true;
         done.push_back(call);
     }
@@ -1032,23 +1014,12 @@ static int run_natives(mmhip_invocation *inv, mmhip_filter *f, const HArgs &a, h
         std::vector<char> used(f->ks.natives.size(), 0);
         for (const RecordedCall &call : calls) used[call.k] = 1;
         for (size_t k = (size_t)f->ks.native_sites; k < f->ks.natives.size(); ++k) {
-            if (used[k] || !inv->native_maps[k]) continue;
+            if (used[k] || !inv->natives[k].map) continue;
             HIP_TRY(hipStreamSynchronize(s));
-            (void)hipFree(inv->native_maps[k]);
-            inv->native_maps[k] = nullptr;
-            inv->native_memo_gen[k] = ~0ULL;
-            inv->native_seen_gen[k] = ~0ULL;
-            inv->native_rows[k] = {0, 0};
-            HImageDesc &d = inv->images[inv->native_slot_base + (int)k];
-            d.kind = IMG_NULL;
-            d.data = nullptr;
-            table_changed = true;
+            drop_native_map(inv, k, &table_changed);
         }
     }
-    if (table_changed) {
-        HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipMemcpy(inv->d_images, inv->images.data(), inv->images.size() * sizeof(HImageDesc), hipMemcpyHostToDevice));
-    }
+    if (table_changed && upload_image_table(inv, s) != 0) return -1;
     return 0;
 }
 
@@ -1185,47 +1156,20 @@ int mmhip_render(mmhip_invocation *inv, int frame, float t, int region_x, int re
     a.floatmap = floatmap;
     a.edge_color_x = inv->edge_color_x;
     a.edge_color_y = inv->edge_color_y;
-    a.uservals = inv->d_uv;
-    a.images = inv->d_images;
+    a.uservals = inv->d_uv.get<HUserval>();
+    a.images = inv->d_images.get<HImageDesc>();
     a.num_images = (uint32_t)inv->images.size();
-    a.curves = inv->d_curves;
-    a.gradients = inv->d_gradients;
+    a.curves = inv->d_curves.get();
+    a.gradients = inv->d_gradients.get();
     a.out = out_device;
     a.native_slot_base = inv->native_slot_base;
-
-    // coordinate tables (grown on demand; stream order protects re-use)
-    if (region_w > inv->xtab_cap) {
-        if (inv->d_xtab) { HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(inv->d_xtab); }
-        HIP_TRY(hipMalloc((void **)&inv->d_xtab, (size_t)region_w * sizeof(float)));
-        inv->xtab_cap = region_w;
-    }
-    if (a.num_rows > inv->ytab_cap) {
-        if (inv->d_ytab) { HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(inv->d_ytab); }
-        HIP_TRY(hipMalloc((void **)&inv->d_ytab, (size_t)a.num_rows * sizeof(float)));
-        inv->ytab_cap = a.num_rows;
-    }
-    a.xtab = inv->d_xtab;
-    a.ytab = inv->d_ytab;
-    if (f->ks.row_values > 0) {
-        const size_t need = (size_t)f->ks.row_values * (size_t)a.num_rows;
-        if (need > inv->rowtab_cap) {
-            if (inv->d_rowtab) { HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(inv->d_rowtab); }
-            inv->d_rowtab = nullptr;
-            inv->rowtab_cap = 0;
-            HIP_TRY(hipMalloc((void **)&inv->d_rowtab, need * sizeof(float)));
-            inv->rowtab_cap = need;
-            inv->pro_filter = nullptr;           // the table is new: fill it
-        }
-        a.rowtab = inv->d_rowtab;
-    }
-
-    if (f->ks.xy_bytes > inv->xy_cap) {
-        if (inv->d_xy) { HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(inv->d_xy); }
-        HIP_TRY(hipMalloc((void **)&inv->d_xy, f->ks.xy_bytes));
-        HIP_TRY(hipMemset(inv->d_xy, 0, f->ks.xy_bytes));
-        inv->xy_cap = f->ks.xy_bytes;
-    }
-    char *xy = inv->d_xy;
+    const size_t rowtab_bytes = inv->launch.rowtab.bytes;
+    if (grow_launch_buffers(inv->launch, f->ks, region_w, a.num_rows, f->ks.row_values > 0, s) != 0) return -1;
+    if (inv->launch.rowtab.bytes != rowtab_bytes) inv->pro_filter = nullptr;     // the per-row table is new: fill it
+    a.xtab = inv->launch.xtab.get<float>();
+    a.ytab = inv->launch.ytab.get<float>();
+    if (f->ks.row_values > 0) a.rowtab = inv->launch.rowtab.get<float>();
+    char *xy = inv->launch.xy.get<char>();
     void *params[] = {&a, &xy};
     bool direct_written = false;      // a native filter wrote this launch's pixels itself (run_natives)
     {
@@ -1281,15 +1225,9 @@ int mmhip_render_supersampled(mmhip_invocation *inv, int frame, float t, int reg
     const size_t long_bytes = (size_t)(region_w + 1) * bpp * region_h;
     const size_t short_bytes = (size_t)region_w * bpp * region_h;
     // own allocation: the nested renders run native filters, which reallocate inv->ws
-    if (long_bytes + short_bytes > inv->ss_bytes) {
-        if (inv->ss_lines) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(inv->ss_lines); }
-        inv->ss_lines = nullptr;
-        inv->ss_bytes = 0;
-        if (hipMalloc(&inv->ss_lines, long_bytes + short_bytes) != hipSuccess)
-            return fail("out of device memory for the supersampling lines");
-        inv->ss_bytes = long_bytes + short_bytes;
-    }
-    unsigned char *tmp = (unsigned char *)inv->ss_lines;
+    if (inv->ss_lines.grow(long_bytes + short_bytes, hipDeviceSynchronize) != hipSuccess)
+        return fail("out of device memory for the supersampling lines");
+    unsigned char *tmp = inv->ss_lines.get<unsigned char>();
     const float ox = inv->sampling_offset_x, oy = inv->sampling_offset_y;
     // long slice: region_width + 1 columns, offsets -0.5 (invocation_init_slice, :892)
     inv->sampling_offset_x = -0.5f;

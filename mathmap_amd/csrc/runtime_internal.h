@@ -54,7 +54,71 @@ struct mmhip_filter {
     // they control): no generic code/kernels, every render goes through spec_cache
 };
 
+// A device allocation the owner frees by going out of scope.
+struct DeviceBuffer {
+    void *p = nullptr;
+    size_t bytes = 0;
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer &&o) noexcept : p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept {
+        if (this != &o) { reset(); p = std::exchange(o.p, nullptr); bytes = std::exchange(o.bytes, 0); }
+        return *this;
+    }
+    ~DeviceBuffer() { reset(); }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    template <class T = void> T *get() const { return (T *)p; }
+    explicit operator bool() const { return p != nullptr; }
+    static hipError_t no_wait() { return hipSuccess; }
+    // At least `need` bytes: a larger request frees the old buffer once `wait()` has returned hipSuccess (what may still
+    // read it is the caller's to say) and allocates a new one, zero-filled with `zero`.  A failed allocation leaves the
+    // buffer empty, so that the next call allocates again.
+    template <class Wait = hipError_t (*)()> hipError_t grow(size_t need, Wait wait = no_wait, bool zero = false) {
+        if (need <= bytes) return hipSuccess;
+        if (p) {
+            const hipError_t e = wait();
+            if (e != hipSuccess) return e;
+            reset();
+        }
+        hipError_t e = hipMalloc(&p, need);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        bytes = need;
+        if (zero && (e = hipMemset(p, 0, need)) != hipSuccess) reset();
+        return e;
+    }
+};
+
+// What a launch's kernels keep besides the tables and the output: frame constants, per-column / per-row coordinates,
+// per-row values (mm_rows: [value][row]).
+struct LaunchBuffers { DeviceBuffer xy, xtab, ytab, rowtab; };
+
+// Native call entry k (KernelSource::natives[k]): its float4 map and what is remembered about it.
+struct NativeEntry {
+    DeviceBuffer map;
+    int w = 0, h = 0;                          // the render size the map was allocated for
+    // Every recomputation of the map gets a new generation (the reference gives every native result a new image id,
+    // cache.c:65-68); the memo records the generations of the native maps among its image arguments, so a consumer is
+    // recomputed when its producer was.
+    unsigned long long gen = 0;
+    mm::HNativeRec memo{};                     // args of the call that produced the map
+    unsigned long long memo_gen = 0;
+    std::vector<unsigned long long> memo_deps;
+    mm::HNativeRec seen{};                     // last argument set whose map was asked for (direct output: materialised on its second use)
+    unsigned long long seen_gen = ~0ULL;
+    std::pair<int, int> rows{0, 0};            // rows of the map that are valid
+};
+
+// The invocation's own stream: its first member, so that it is destroyed after every buffer.
+struct OwnedStream {
+    hipStream_t s = nullptr;
+    OwnedStream() = default;
+    OwnedStream(const OwnedStream &) = delete;
+    ~OwnedStream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+
 struct mmhip_invocation {
+    ~mmhip_invocation();
+    OwnedStream stream;
     mmhip_filter *f = nullptr;
     int img_w = 0, img_h = 0, render_w = 0, render_h = 0;
     std::vector<mm::HUserval> uv;
@@ -62,33 +126,24 @@ struct mmhip_invocation {
     std::vector<int> image_slot_of_uv;     // userval index -> image table slot (or -1)
     std::vector<float> curves;             // [n_curves][1024] (userval.h:37, userval.c:282-311)
     std::vector<uint32_t> gradients;       // [n_gradients][1024] packed 0xRRGGBBAA
-    float *d_curves = nullptr;
-    uint32_t *d_gradients = nullptr;
+    DeviceBuffer d_uv, d_images, d_curves, d_gradients;
     int native_slot_base = 0;
-    mm::HUserval *d_uv = nullptr;
-    mm::HImageDesc *d_images = nullptr;
     bool tables_dirty = true;
-    std::vector<void *> owned;             // device buffers we allocated for input images
-    std::vector<void *> native_maps;       // float4 maps produced by native filters
-    std::vector<std::pair<int, int>> native_map_size;   // render size native_maps[k] was allocated for
-    // Every recomputation of map k gets a new generation (the reference gives every native result a
-    // new image id, cache.c:65-68); a memo entry records the generations of the native maps among its
-    // image arguments, so a consumer is recomputed when its producer was.
-    std::vector<unsigned long long> native_gen;
-    std::vector<std::vector<unsigned long long>> native_memo_deps;
+    std::vector<DeviceBuffer> owned;       // device buffers we allocated for input images
+    std::vector<NativeEntry> natives;
     unsigned long long native_gen_counter = 0;
-    // closure images rendered for native filters: float map + the sub-launch's own constant buffer / tables
-    struct ClosureState { void *map = nullptr; int w = 0, h = 0; char *d_xy = nullptr; int xy_cap = 0;
-                          float *d_xtab = nullptr, *d_ytab = nullptr; int xtab_cap = 0, ytab_cap = 0;
-                          int native_slot_base = 0; std::vector<void *> native_maps; };   // native filters the closure's own code calls
+    // closure images rendered for native filters: float map, the sub-launch's own buffers, the maps of the native
+    // filters the closure's own code calls
+    struct ClosureState {
+        DeviceBuffer map;
+        int w = 0, h = 0;
+        LaunchBuffers launch;
+        int native_slot_base = 0;
+        std::vector<DeviceBuffer> native_results;
+    };
     std::vector<ClosureState> closure_state;
-    void *ss_lines = nullptr;              // the two slices of a supersampled render (own allocation:
-    size_t ss_bytes = 0;                   // native filters reallocate `ws` underneath a nested render)
-    std::vector<mm::HNativeRec> native_memo;   // args of the call that produced native_maps[k]
-    std::vector<unsigned long long> native_memo_gen;
-    std::vector<mm::HNativeRec> native_seen;   // last argument set whose map was asked for (direct output: materialised on its second use)
-    std::vector<unsigned long long> native_seen_gen;
-    std::vector<std::pair<int, int>> native_rows;   // rows of native_maps[k] that are valid
+    DeviceBuffer ss_lines;                 // the two slices of a supersampled render (own allocation: native filters
+                                           // reallocate `ws` underneath a nested render)
     int native_row_margin = -1;                     // mmhip_set_native_row_margin
     long direct_native_launches = 0;                // mmhip_direct_native_launches
     // the prologue kernel is skipped while nothing it reads has changed (mmhip_render)
@@ -97,13 +152,7 @@ struct mmhip_invocation {
     void *pro_stream = nullptr;
     unsigned long long pro_generation = 0, table_generation = 1;
     unsigned long long input_generation = 1;
-    char *d_xy = nullptr;
-    int xy_cap = 0;
-    float *d_xtab = nullptr, *d_ytab = nullptr;   // per-column / per-row coordinates of the current launch
-    int xtab_cap = 0, ytab_cap = 0;
-    float *d_rowtab = nullptr;                    // per-row values of the current launch (mm_rows): [value][row]
-    size_t rowtab_cap = 0;
-    hipStream_t stream = nullptr;
+    LaunchBuffers launch;                  // of the main kernels (mmhip_render)
     uint32_t edge_color_x = 0, edge_color_y = 0;
     float sampling_offset_x = 0.f, sampling_offset_y = 0.f;
     bool timing = false;
@@ -123,3 +172,6 @@ extern thread_local std::string g_mmhip_err;   // message behind mmhip_last_erro
 // create, fill f->module (filters, main) and f->code, then finalize (passes + codegen).
 mmhip_filter *mmhip_filter_new_empty();
 bool mmhip_filter_finalize(mmhip_filter *f, const mm::KernelOptions &ko, std::string *err);
+
+// Unbinds every image-table entry that refers to `data` (a device buffer about to be freed).
+void mmhip_unbind_image(mmhip_invocation *inv, const void *data);

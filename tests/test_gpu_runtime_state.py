@@ -9,6 +9,7 @@ import mathmap_amd as mm
 from tests import filters as F
 from oracle.ccgen import CpuFilter, render_supersampled
 from tests.gpu_util import make_invocation, render_device, stats
+from tests.test_gpu_closures import BLUR_OF_BLURRING_CLOSURE
 
 pytestmark = pytest.mark.gpu
 
@@ -21,14 +22,16 @@ end
 """
 
 
-def test_render_size_change_reallocates_native_maps():
+@pytest.mark.parametrize("src,uv", [(F.GAUSS_DIRECT, {"hdev": 0.03, "vdev": 0.02}), (BLUR_OF_BLURRING_CLOSURE, {"s": 0.03})],
+                         ids=["gauss_direct", "blurring_closure"])
+def test_render_size_change_reallocates_native_results(src, uv):
     """Preview (small render size) then the full size, then the preview again, on ONE invocation: the
     blur's float map must follow the render size (it used to stay preview-sized: a device heap
-    overflow) and the memo must not return the other size's map."""
+    overflow) and the memo must not return the other size's map.  With a closure handed to the blur
+    (blurring_closure) the closure's own float map and native maps follow the render size as well."""
     w, h = 320, 200
     img = F.synthetic_image(w, h, seed=5)
-    uv = {"hdev": 0.03, "vdev": 0.02}
-    flt, inv = make_invocation(F.GAUSS_DIRECT, w, h, uv, {"in": img})
+    flt, inv = make_invocation(src, w, h, uv, {"in": img})
     cf = CpuFilter(flt.ir_json_raw)
     for rw, rh in ((80, 50), (w, h), (80, 50), (160, 100)):
         inv.set_render_size(rw, rh)
