@@ -38,6 +38,9 @@ enum { MMHIP_UV_INT = 0, MMHIP_UV_FLOAT = 1, MMHIP_UV_BOOL = 2, MMHIP_UV_COLOR =
 /* edge behaviours (mathmap.h:134-147) */
 enum { MMHIP_EDGE_COLOR = 0, MMHIP_EDGE_WRAP = 1, MMHIP_EDGE_REFLECT = 2, MMHIP_EDGE_ROTATE = 3 };
 
+/* gaussian_blur's arithmetic (mmhip_options.gauss_mode) */
+enum { MMHIP_GAUSS_EXACT = 0, MMHIP_GAUSS_TOLERANCE = 1 };
+
 typedef struct mmhip_options {
     int intersample;      /* 1 = bilinear input sampling (CLI -i), 0 = nearest */
     int supersampling;    /* affects the nearest fetch only (builtins.c:154-158) */
@@ -49,7 +52,17 @@ typedef struct mmhip_options {
     int pixel_inc;        /* drawable_get_pixel_inc (mathmap.c:1320-1327): the stride of the preview's image source
                              (fast_image_source_scale) the bilinear fetch interpolates over (builtins.c:186-216);
                              0 or 1 = full-resolution sources, the CLI's and every final render's case */
-    int reserved[6];
+    int gauss_mode;       /* MMHIP_GAUSS_EXACT (default): gaussian_blur's float map equals the reference's bit for bit.
+                             MMHIP_GAUSS_TOLERANCE (an extension): a faster chain (fma recurrences, lines split into
+                             segments) whose RGBA8 output differs from the exact chain's by at most 1 per channel (its
+                             float values by a few f32 ulps), used only where nothing but those bytes leaves the blur:
+                             the render writes RGBA8 straight from the blur (a filter like examples/Blur/Gaussian Blur.mm
+                             at pixel centres) over the whole frame, the blur's map is not kept (the first render of an
+                             argument set: the second is memoised and exact), the input is a drawable (not a float map, a
+                             closure or another native result), and both deviations are at least 0.5 px.  Everything else
+                             -- float-map output, row bands, stripes, supersampling, memoised maps -- runs the exact chain.
+                             Not part of the kernel source.  Other values: mmhip_compile* fails. */
+    int reserved[5];
 } mmhip_options;
 
 typedef struct mmhip_userval_info {
@@ -86,6 +99,7 @@ const char *mmhip_filter_ir_json(mmhip_filter *f);        /* IR dump after the o
    mmhip_compile_ir_json and of the test oracle (oracle/ccgen.py) */
 const char *mmhip_filter_ir_json_raw(mmhip_filter *f);
 const char *mmhip_filter_kernel_source(mmhip_filter *f);  /* the HIP C++ handed to hiprtc */
+int mmhip_filter_gauss_mode(const mmhip_filter *f);       /* the options' gauss_mode the filter was compiled with */
 int mmhip_filter_num_native_calls(const mmhip_filter *f);
 /* The launch geometry of the filter's pixel kernel over rows [0, num_rows) of a region_w-wide region, as
    mmhip_render takes it (MMHIP_PPT included): out[MMHIP_GEOMETRY_FIELDS] receives, in this order,
@@ -159,6 +173,9 @@ int mmhip_drain_native_kernel_ms(mmhip_invocation *inv, char *names, double *out
    examples/Blur/Gaussian Blur.mm, whose pixel is the blurred map sampled at the pixel centre: the
    blur's last kernel packs the output (new_template.c.in:279-293) and the pixel kernel is skipped. */
 long mmhip_direct_native_launches(mmhip_invocation *inv);
+/* Launches of this invocation whose pixels gaussian_blur's tolerance chain wrote (gauss_mode MMHIP_GAUSS_TOLERANCE and the
+   conditions stated at mmhip_options.gauss_mode). */
+long mmhip_tolerance_blur_launches(mmhip_invocation *inv);
 
 /* device memory helpers for callers without their own allocator */
 void *mmhip_device_alloc(size_t bytes);

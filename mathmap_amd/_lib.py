@@ -14,7 +14,8 @@ LIB_PATH = os.path.join(_HERE, "libmathmap_hip.so")
 class Options(C.Structure):
     _fields_ = [("intersample", C.c_int), ("supersampling", C.c_int),
                 ("edge_behaviour_x", C.c_int), ("edge_behaviour_y", C.c_int),
-                ("tile_w", C.c_int), ("specialize_uservals", C.c_int), ("pixel_inc", C.c_int), ("reserved", C.c_int * 6)]
+                ("tile_w", C.c_int), ("specialize_uservals", C.c_int), ("pixel_inc", C.c_int),
+                ("gauss_mode", C.c_int), ("reserved", C.c_int * 5)]
 
 
 class UservalInfo(C.Structure):
@@ -41,6 +42,7 @@ SYMBOLS = {
     "mmhip_filter_ir_json": (C.c_char_p, [C.c_void_p]),
     "mmhip_filter_ir_json_raw": (C.c_char_p, [C.c_void_p]),
     "mmhip_filter_kernel_source": (C.c_char_p, [C.c_void_p]),
+    "mmhip_filter_gauss_mode": (C.c_int, [C.c_void_p]),
     "mmhip_filter_num_native_calls": (C.c_int, [C.c_void_p]),
     "mmhip_filter_launch_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "mmhip_filter_num_closures": (C.c_int, [C.c_void_p]),
@@ -56,6 +58,7 @@ SYMBOLS = {
     "mmhip_set_native_row_margin": (C.c_int, [C.c_void_p, C.c_int]),
     "mmhip_drain_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "mmhip_direct_native_launches": (C.c_long, [C.c_void_p]),
+    "mmhip_tolerance_blur_launches": (C.c_long, [C.c_void_p]),
     "mmhip_drain_native_kernel_ms": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int]),
     "mmhip_set_curve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mmhip_set_gradient": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
@@ -99,6 +102,7 @@ SELFTEST_SYMBOLS = {
     "mmhip_selftest_set_pixel_inc": (None, [C.c_int]),
     "mmhip_selftest_eval_unary": (C.c_int, [C.c_int, C.c_uint, C.c_ulonglong, C.c_void_p]),
     "mmhip_selftest_eval_binary": (C.c_int, [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_void_p]),
+    "mmhip_selftest_gauss_tolerance_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
 }
 SELFTEST_PATH = os.path.join(_HERE, "libmathmap_hip_selftest.so")
 _selftest = None

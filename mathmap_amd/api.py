@@ -14,6 +14,8 @@ import numpy as np
 from ._lib import Options, UservalInfo, lib
 
 UV_INT, UV_FLOAT, UV_BOOL, UV_COLOR, UV_CURVE, UV_GRADIENT, UV_IMAGE = range(7)
+# mmhip_options.gauss_mode (include/mmhip.h)
+GAUSS_MODES = {"exact": 0, "tolerance": 1}
 EDGE_COLOR, EDGE_WRAP, EDGE_REFLECT, EDGE_ROTATE = range(4)
 # mmhip_filter_launch_geometry's out[] (include/mmhip.h)
 GEOMETRY_FIELDS = ("tiles_x", "tiles_y", "wg1", "nwg", "ppt", "tile_w", "tile_h", "unroll", "pair_mode", "single_pixel",
@@ -32,14 +34,18 @@ class Filter:
     """A compiled .mm filter (front-end + IR + generated HIP kernel string)."""
 
     def __init__(self, source="", intersample=True, supersampling=False, edge_x=EDGE_COLOR, edge_y=EDGE_COLOR,
-                 tile_w=0, specialize=False, constants=None, ir_json=None, _handle=None, pixel_inc=1):
+                 tile_w=0, specialize=False, constants=None, ir_json=None, _handle=None, pixel_inc=1, gauss_mode="exact"):
         """`source`: .mm text; or `ir_json`: an IR dump (mmhip_filter_ir_json_raw / the reference-ABI importer's
         form) -- the IR-level entry point.  `constants` (name -> number) bakes scalar user values in as literals.
         `pixel_inc` > 1: the bilinear fetch interpolates over a source sampled at that stride (the GIMP preview's
-        fast image source, builtins.c:186-216)."""
+        fast image source, builtins.c:186-216).  `gauss_mode`: "exact" (default), or "tolerance" -- gaussian_blur's
+        faster chain, within 1 per RGBA8 channel of exact, where the render writes the blur's bytes directly (the
+        conditions are stated at mmhip_options.gauss_mode in include/mmhip.h)."""
+        if gauss_mode not in GAUSS_MODES:
+            raise MathMapError("gauss_mode must be one of %s, not %r" % (", ".join(sorted(GAUSS_MODES)), gauss_mode))
         self._source = source
         self._kwargs = dict(intersample=intersample, supersampling=supersampling, edge_x=edge_x, edge_y=edge_y,
-                            tile_w=tile_w, pixel_inc=pixel_inc)
+                            tile_w=tile_w, pixel_inc=pixel_inc, gauss_mode=gauss_mode)
         if _handle is not None:
             self._h = _handle
             return
@@ -51,6 +57,7 @@ class Filter:
         o.tile_w = tile_w
         o.pixel_inc = pixel_inc
         o.specialize_uservals = 1 if specialize else 0
+        o.gauss_mode = GAUSS_MODES[gauss_mode]
         if ir_json is not None:
             self._h = lib().mmhip_compile_ir_json(ir_json.encode(), C.byref(o))
         else:
@@ -136,6 +143,12 @@ class Filter:
     @property
     def kernel_source(self):
         return lib().mmhip_filter_kernel_source(self._h).decode()
+
+    @property
+    def gauss_mode(self):
+        """The gauss_mode the library compiled this filter with: "exact" or "tolerance"."""
+        mode = lib().mmhip_filter_gauss_mode(self._h)
+        return {v: k for k, v in GAUSS_MODES.items()}[mode]
 
     @property
     def num_native_calls(self):
@@ -289,6 +302,10 @@ class Invocation:
     def direct_native_launches(self):
         """Launches whose pixels a native filter wrote itself (pixel kernel skipped)."""
         return lib().mmhip_direct_native_launches(self._h)
+
+    def tolerance_blur_launches(self):
+        """Launches whose pixels gaussian_blur's tolerance chain wrote (Filter(gauss_mode="tolerance"))."""
+        return lib().mmhip_tolerance_blur_launches(self._h)
 
     def render(self, t=0.0, frame=0):
         """Renders the whole frame and returns it as a uint8 [H,W,4] array (RGBA)."""

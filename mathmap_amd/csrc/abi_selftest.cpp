@@ -15,6 +15,7 @@
 #include "../../include/mathmap_hip_backend.h"
 #include "../../include/mmhip.h"
 #include "front.h"
+#include "runtime_internal.h"
 
 namespace mm { void load_ir_json(Module &mod, FilterCode &code, const char *json); }   // ir_json.cpp
 
@@ -509,6 +510,39 @@ int mmhip_selftest_abi_roundtrip(const char *source, int intersample, const uint
         g_selftest_err = e.what();
         return -3;
     }
+}
+
+// gaussian_blur(in, hdev, vdev) of an RGB8 host image through the tolerance chain (mmhip_options.gauss_mode), with the
+// float map written as well -- the product never writes it on that chain (nothing reads it) -- into `map`
+// (float[h][w][4]), so that a test can bound its float error directly.  0 on success.
+int mmhip_selftest_gauss_tolerance_map(const uint8_t *rgb, int w, int h, float hdev, float vdev, float *map) {
+    static const char *src = "stretched filter gauss_direct (stretched image in, float hdev: 0-1 (0.01), float vdev: 0-1 (0.01))\n"
+                             "  soft = gaussian_blur(in, hdev, vdev);\n"
+                             "  soft(xy)\n"
+                             "end\n";
+    mmhip_options o;
+    mmhip_default_options(&o);
+    o.gauss_mode = MMHIP_GAUSS_TOLERANCE;
+    std::unique_ptr<mmhip_filter, void (*)(mmhip_filter *)> f(mmhip_compile(src, &o), mmhip_filter_free);
+    if (!f || mmhip_filter_jit(f.get(), 1) < 0) { g_selftest_err = mmhip_last_error(); return -1; }
+    std::unique_ptr<mmhip_invocation, void (*)(mmhip_invocation *)> inv(mmhip_invoke(f.get(), w, h), mmhip_invocation_free);
+    if (!inv) { g_selftest_err = mmhip_last_error(); return -1; }
+    std::unique_ptr<void, void (*)(void *)> out(mmhip_device_alloc((size_t)w * h * 4), mmhip_device_free);
+    char hv[32], vv[32];
+    snprintf(hv, sizeof hv, "%.9g", hdev);
+    snprintf(vv, sizeof vv, "%.9g", vdev);
+    inv->ws.keep_tolerance_map = true;
+    if (!out || mmhip_set_by_name(inv.get(), "hdev", hv) != 0 || mmhip_set_by_name(inv.get(), "vdev", vv) != 0 ||
+        mmhip_set_image_host(inv.get(), 0, rgb, w, h, 3) != 0 ||
+        mmhip_render(inv.get(), 0, 0.0f, 0, 0, w, h, 0, h, out.get(), w * 4, 4, 0, nullptr) != 0 || mmhip_sync(inv.get()) != 0) {
+        g_selftest_err = out ? mmhip_last_error() : "out of device memory";
+        return -1;
+    }
+    if (inv->tolerance_blur_launches != 1 || inv->natives.size() != 1 || !inv->natives[0].map) {
+        g_selftest_err = "the render did not take the tolerance chain";
+        return -2;
+    }
+    return mmhip_copy_to_host(map, inv->natives[0].map.get(), (size_t)w * h * 16) == 0 ? 0 : -1;
 }
 
 }  // extern "C"

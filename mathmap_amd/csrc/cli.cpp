@@ -45,6 +45,10 @@ void usage() {
            "  -s, --size=WIDTHxHEIGHT     sets the output image size\n"
            "  -c, --cache=NUM             cache NUM input images (default %d)\n"
            "  -g, --generator=GEN         generate plug-in code with GEN\n"
+           "Extensions of the HIP command line:\n"
+           "      --gauss-mode=MODE       gaussian_blur arithmetic: exact (default, the\n"
+           "                              reference's values) or tolerance (faster, RGBA8\n"
+           "                              output within 1 per channel of exact)\n"
            "\n"
            "Report bugs and suggestions to schani@complang.tuwien.ac.at\n",
            cache_size);
@@ -170,14 +174,14 @@ struct Define { std::string name, value; };
 
 enum {
     OPT_VERSION = 256, OPT_HELP, OPT_HTMLDOC, OPT_BENCH_NO_OUTPUT, OPT_BENCH_ONLY_COMPILE,
-    OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT
+    OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE
 };
 
 int main(int argc, char **argv) {
     std::string script;
     bool have_script = false, htmldoc = false, bench_no_output = false, bench_no_backend = false;
     int antialiasing = 0, supersampling = 0, img_width = 0, img_height = 0, size_is_set = 0;
-    int bench_render_count = 1, num_frames = 1;
+    int bench_render_count = 1, num_frames = 1, gauss_mode = MMHIP_GAUSS_EXACT;
     const char *generator = nullptr;
     std::vector<Define> defines;
     static struct option long_options[] = {
@@ -190,7 +194,7 @@ int main(int argc, char **argv) {
         {"bench-no-compile-time-limit", no_argument, 0, OPT_BENCH_NO_COMPILE_TIME_LIMIT},
         {"bench-no-backend", no_argument, 0, OPT_BENCH_NO_BACKEND},
         {"bench-render-count", required_argument, 0, OPT_BENCH_RENDER_COUNT},
-        {"frames", required_argument, 0, 'F'}, {0, 0, 0, 0}};
+        {"frames", required_argument, 0, 'F'}, {"gauss-mode", required_argument, 0, OPT_GAUSS_MODE}, {0, 0, 0, 0}};
     for (;;) {
         int idx;
         int option = getopt_long(argc, argv, "f:ioF:D:c:g:s:", long_options, &idx);
@@ -234,6 +238,11 @@ int main(int argc, char **argv) {
             case OPT_BENCH_NO_OUTPUT: bench_no_output = true; break;
             case OPT_BENCH_NO_COMPILE_TIME_LIMIT: break;
             case OPT_BENCH_NO_BACKEND: bench_no_backend = true; break;
+            case OPT_GAUSS_MODE:
+                if (!strcmp(optarg, "exact")) gauss_mode = MMHIP_GAUSS_EXACT;
+                else if (!strcmp(optarg, "tolerance")) gauss_mode = MMHIP_GAUSS_TOLERANCE;
+                else { fprintf(stderr, "Error: --gauss-mode takes exact or tolerance.\n"); return 1; }
+                break;
             default: usage(); return 1;
         }
     }
@@ -253,6 +262,7 @@ int main(int argc, char **argv) {
     mmhip_default_options(&opts);
     opts.intersample = antialiasing;
     opts.supersampling = supersampling;
+    opts.gauss_mode = gauss_mode;
     // an extension next to the reference's options: a script whose first character is '{' (which no .mm text can
     // start with) is a compiled filter in the IR dump form of mmhip_filter_ir_json_raw, e.g. the output of another
     // front-end; everything after compilation is the same

@@ -306,6 +306,7 @@ void load_ir_json(Module &mod, FilterCode &code, const char *json) {
 }  // namespace mm
 
 extern "C" mmhip_filter *mmhip_compile_ir_json(const char *json, const mmhip_options *opts) {
+    if (!mmhip_check_options(opts)) return nullptr;
     mmhip_filter *f = mmhip_filter_new_empty();
     try {
         f->code.reset(new mm::FilterCode());

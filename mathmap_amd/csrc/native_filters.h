@@ -23,8 +23,10 @@ struct NativeEnv {
 // Scratch buffers reused across calls (sized for the largest map seen).
 struct NativeWorkspace {
     NativeEnv env;                              // set by the runtime before every run_native_filter
+    bool gauss_tolerance = false;               // so is this: the filter's gauss_mode is MMHIP_GAUSS_TOLERANCE (include/mmhip.h)
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
+    bool keep_tolerance_map = false;            // test hook (abi_selftest.cpp): the tolerance chain writes the map too
     void *reserve(size_t bytes);
     void release();
     // per-kernel timing of a native filter's own launches (mmhip_enable_timing): one HIP event pair per
@@ -67,6 +69,7 @@ struct NativeDirectOut {
     int first_row = 0, num_rows = 0, region_x = 0, region_w = 0;
     bool skip_map = false;        // in: the caller will not read the float map (it is not memoised): do not write it
     bool written = false;         // out; with skip_map the map's contents are then undefined
+    bool tolerance = false;       // out: written by gaussian_blur's tolerance chain (gauss_mode)
 };
 
 int run_native_filter(const std::string &func, const HNativeRec &rec, const std::vector<HImageDesc> &images,

@@ -222,6 +222,56 @@ __device__ __forceinline__ double iir_step_anticausal(double s0, double s1, doub
     return acc;
 }
 
+// How a sweep takes one interior step; the sweeps below are templates on it.
+// ExactStep: the reference's operations in its order, each rounded on its own (the default chain).
+struct ExactStep {
+    template <bool S0_NOT_NEG_ZERO>
+    static __device__ __forceinline__ double causal(double s0, double s1, double s2, double s3, double s4, double v1, double v2,
+                                                    double v3, double v4, const double *n, const double *d) {
+        return iir_step_causal<S0_NOT_NEG_ZERO>(s0, s1, s2, s3, s4, v1, v2, v3, v4, n, d);
+    }
+    template <bool S0_FINITE>
+    static __device__ __forceinline__ double anticausal(double s0, double s1, double s2, double s3, double s4, double v1, double v2,
+                                                        double v3, double v4, const double *n, const double *d) {
+        return iir_step_anticausal<S0_FINITE>(s0, s1, s2, s3, s4, v1, v2, v3, v4, n, d);
+    }
+    static __device__ __forceinline__ double any(double s0, double s1, double s2, double s3, double s4, double v1, double v2,
+                                                 double v3, double v4, const double *n, const double *d) {
+        return iir_step(s0, s1, s2, s3, s4, v1, v2, v3, v4, n, d);
+    }
+};
+// FmaStep (MMHIP_GAUSS_TOLERANCE): the same sum reassociated into fmas, v_k = fma(-d1, v(k-1), p_k), where p_k gathers
+// the inputs and v(k-2..k-4) -- v(k-2) last -- so that the only operation on the dependence through v(k-1) is one fma
+// (against five for ExactStep), and 9 f64 operations per step instead of 17.  Rounding differs from the reference's by
+// a few f64 ulps of the state, which the recurrence carries along at that level.
+struct FmaStep {
+    static __device__ __forceinline__ double tail(double p, double s1, double s2, double s3, double s4, double v1, double v2,
+                                                  double v3, double v4, const double *n, const double *d) {
+        p = __builtin_fma(n[1], s1, p);
+        p = __builtin_fma(n[2], s2, p);
+        p = __builtin_fma(n[3], s3, p);
+        p = __builtin_fma(n[4], s4, p);
+        p = __builtin_fma(-d[4], v4, p);
+        p = __builtin_fma(-d[3], v3, p);
+        p = __builtin_fma(-d[2], v2, p);
+        return __builtin_fma(-d[1], v1, p);
+    }
+    template <bool S0_NOT_NEG_ZERO>
+    static __device__ __forceinline__ double causal(double s0, double s1, double s2, double s3, double s4, double v1, double v2,
+                                                    double v3, double v4, const double *n, const double *d) {
+        return tail(n[0] * s0, s1, s2, s3, s4, v1, v2, v3, v4, n, d);
+    }
+    template <bool S0_FINITE>      // n_m[0] = +0: the term is +-0 for a finite s0 (see iir_step_anticausal)
+    static __device__ __forceinline__ double anticausal(double s0, double s1, double s2, double s3, double s4, double v1, double v2,
+                                                        double v3, double v4, const double *n, const double *d) {
+        return tail(S0_FINITE ? 0.0 : n[0] * s0, s1, s2, s3, s4, v1, v2, v3, v4, n, d);
+    }
+    static __device__ __forceinline__ double any(double s0, double s1, double s2, double s3, double s4, double v1, double v2,
+                                                 double v3, double v4, const double *n, const double *d) {
+        return tail(n[0] * s0, s1, s2, s3, s4, v1, v2, v3, v4, n, d);
+    }
+};
+
 // steps 0..3 of a sweep (gauss.c:178-190: fewer than 4 predecessors, the rest uses the edge value)
 __device__ __forceinline__ double iir_edge_step(int j, double s0, double s1, double s2, double s3, double v1, double v2,
                                                 double v3, const double *n, const double *d, const double *bd,
@@ -333,7 +383,7 @@ struct IirState { double s1, s2, s3, s4, v1, v2, v3, v4; };
 // 512).  FAST: every block of the group and every block prefetched by it is a full interior block of
 // the segment -- straight-line code without a branch, which is also what lets the compiler count
 // the outstanding loads exactly instead of waiting for all of them at a join.
-template <bool FAST, class Src>
+template <bool FAST, class Step, class Src>
 __device__ __forceinline__ void causal_group(const Src &src, typename Src::raw_t (&ring)[IIR_PF + 1][IIR_U], IirState &st,
                                              double *__restrict__ ck, unsigned stride, unsigned lane, int kb0, int k0, int s0,
                                              int s1, float initial, const IirCoef &c) {
@@ -365,7 +415,7 @@ __device__ __forceinline__ void causal_group(const Src &src, typename Src::raw_t
 #pragma unroll
                 for (int u = 0; u < IIR_U; ++u) {
                     const double s0v = (double)src.decode(cur[u]);
-                    const double acc = iir_step_causal<Src::not_neg_zero>(s0v, s1_, s2, s3, s4, v1, v2, v3, v4, c.n_p, c.d_p);
+                    const double acc = Step::template causal<Src::not_neg_zero>(s0v, s1_, s2, s3, s4, v1, v2, v3, v4, c.n_p, c.d_p);
                     s4 = s3; s3 = s2; s2 = s1_; s1_ = s0v;
                     v4 = v3; v3 = v2; v2 = v1; v1 = acc;
                 }
@@ -376,7 +426,7 @@ __device__ __forceinline__ void causal_group(const Src &src, typename Src::raw_t
                     if (k < s1) {
                         const double s0v = (double)src.decode(cur[u]);
                         const double acc = (kb == k0 && u < 4) ? iir_edge_step(u, s0v, s1_, s2, s3, v1, v2, v3, c.n_p, c.d_p, c.bd_p, initial)
-                                                                : iir_step(s0v, s1_, s2, s3, s4, v1, v2, v3, v4, c.n_p, c.d_p);
+                                                                : Step::any(s0v, s1_, s2, s3, s4, v1, v2, v3, v4, c.n_p, c.d_p);
                         s4 = s3; s3 = s2; s2 = s1_; s1_ = s0v;
                         v4 = v3; v3 = v2; v2 = v1; v1 = acc;
                     }
@@ -387,7 +437,7 @@ __device__ __forceinline__ void causal_group(const Src &src, typename Src::raw_t
     st = IirState{s1_, s2, s3, s4, v1, v2, v3, v4};
 }
 
-template <class Src>
+template <class Step, class Src>
 __device__ __forceinline__ void causal_sweep(const Src &src, double *__restrict__ ck, unsigned stride, unsigned lane, int k0,
                                              int s0, int s1, const IirCoef &c) {
     const float initial = src.decode(src.fetch(k0));
@@ -403,15 +453,15 @@ __device__ __forceinline__ void causal_sweep(const Src &src, double *__restrict_
     const int G = (IIR_PF + 1) * IIR_U;
     int kb0 = k0;
     do {        // the group with the edge steps, and a segment's warm-up groups (no checkpoints)
-        causal_group<false>(src, ring, st, ck, stride, lane, kb0, k0, s0, s1, initial, c);
+        causal_group<false, Step>(src, ring, st, ck, stride, lane, kb0, k0, s0, s1, initial, c);
         kb0 += G;
     } while (kb0 < s0 && kb0 < s1);
-    for (; kb0 + (2 * IIR_PF + 1) * IIR_U <= s1; kb0 += G) causal_group<true>(src, ring, st, ck, stride, lane, kb0, k0, s0, s1, initial, c);
-    for (; kb0 < s1; kb0 += G) causal_group<false>(src, ring, st, ck, stride, lane, kb0, k0, s0, s1, initial, c);
+    for (; kb0 + (2 * IIR_PF + 1) * IIR_U <= s1; kb0 += G) causal_group<true, Step>(src, ring, st, ck, stride, lane, kb0, k0, s0, s1, initial, c);
+    for (; kb0 < s1; kb0 += G) causal_group<false, Step>(src, ring, st, ck, stride, lane, kb0, k0, s0, s1, initial, c);
 }
 
 // One block of the causal recurrence re-run from its checkpoint (block 0: from the edge).
-template <bool GUARD, class Src>
+template <bool GUARD, class Step, class Src>
 __device__ __forceinline__ void rerun_block(const Src &src, int b, int n, const typename Src::raw_t *in, const typename Src::raw_t *r4,
                                             const double *ckv, const IirCoef &c, float initial_p, double *vc) {
     const int kb = b * IIR_U;
@@ -421,7 +471,7 @@ __device__ __forceinline__ void rerun_block(const Src &src, int b, int n, const 
     for (int u = 0; u < IIR_U; ++u) {
         if (!GUARD) {
             const double s0 = (double)src.decode(in[u]);
-            const double acc = iir_step_causal<Src::not_neg_zero>(s0, cs1, cs2, cs3, cs4, cv1, cv2, cv3, cv4, c.n_p, c.d_p);
+            const double acc = Step::template causal<Src::not_neg_zero>(s0, cs1, cs2, cs3, cs4, cv1, cv2, cv3, cv4, c.n_p, c.d_p);
             vc[u] = acc;
             cs4 = cs3; cs3 = cs2; cs2 = cs1; cs1 = s0;
             cv4 = cv3; cv3 = cv2; cv2 = cv1; cv1 = acc;
@@ -430,7 +480,7 @@ __device__ __forceinline__ void rerun_block(const Src &src, int b, int n, const 
             if (kb + u < n) {
                 const double s0 = (double)src.decode(in[u]);
                 const double acc = (b == 0 && u < 4) ? iir_edge_step(u, s0, cs1, cs2, cs3, cv1, cv2, cv3, c.n_p, c.d_p, c.bd_p, initial_p)
-                                                     : iir_step(s0, cs1, cs2, cs3, cs4, cv1, cv2, cv3, cv4, c.n_p, c.d_p);
+                                                     : Step::any(s0, cs1, cs2, cs3, cs4, cv1, cv2, cv3, cv4, c.n_p, c.d_p);
                 vc[u] = acc;
                 cs4 = cs3; cs3 = cs2; cs2 = cs1; cs1 = s0;
                 cv4 = cv3; cv3 = cv2; cv2 = cv1; cv1 = acc;
@@ -446,7 +496,7 @@ __device__ __forceinline__ void rerun_block(const Src &src, int b, int n, const 
 // from memory.
 // Segment [sg0, sg1) of the line: the anticausal recurrence starts at k1 - 1, k1 = min(n, sg1 + halo)
 // (at k1 < n as if k1 were the line's end) and runs unrecorded down to sg1 first.
-template <class Src>
+template <class Step, class Src>
 __device__ __forceinline__ void anticausal_sweep(const Src &src, const double *__restrict__ ck, unsigned stride, unsigned clane,
                                                  int n, int sg0, int sg1, int k1,
                                                  const IirCoef &c, float *tw, int lane, long line0, int lines,
@@ -471,7 +521,7 @@ __device__ __forceinline__ void anticausal_sweep(const Src &src, const double *_
 #pragma unroll
                 for (int u = IIR_U - 1; u >= 0; --u) {
                     const double s0 = (double)src.decode(cur_s[u]);
-                    const double acc = iir_step(s0, s1, s2, s3, s4, v1, v2, v3, v4, c.n_m, c.d_m);
+                    const double acc = Step::any(s0, s1, s2, s3, s4, v1, v2, v3, v4, c.n_m, c.d_m);
                     s4 = s3; s3 = s2; s2 = s1; s1 = s0;
                     v4 = v3; v3 = v2; v2 = v1; v1 = acc;
                 }
@@ -484,7 +534,7 @@ __device__ __forceinline__ void anticausal_sweep(const Src &src, const double *_
                         const double s0 = (double)src.decode(cur_s[u]);
                         double acc;
                         if (j < 4) acc = iir_edge_step(j, s0, s1, s2, s3, v1, v2, v3, c.n_m, c.d_m, c.bd_m, initial_m);
-                        else acc = iir_step(s0, s1, s2, s3, s4, v1, v2, v3, v4, c.n_m, c.d_m);
+                        else acc = Step::any(s0, s1, s2, s3, s4, v1, v2, v3, v4, c.n_m, c.d_m);
                         s4 = s3; s3 = s2; s2 = s1; s1 = s0;
                         v4 = v3; v3 = v2; v2 = v1; v1 = acc;
                     }
@@ -539,7 +589,7 @@ __device__ __forceinline__ void anticausal_sweep(const Src &src, const double *_
             for (int u = 0; u < IIR_U; ++u) {
                 {
                     const double s0 = (double)src.decode(nxt.s[u]);
-                    const double acc = iir_step_causal<Src::not_neg_zero>(s0, cs1, cs2, cs3, cs4, cv1, cv2, cv3, cv4, c.n_p, c.d_p);
+                    const double acc = Step::template causal<Src::not_neg_zero>(s0, cs1, cs2, cs3, cs4, cv1, cv2, cv3, cv4, c.n_p, c.d_p);
                     nxt.vc[u] = acc;
                     cs4 = cs3; cs3 = cs2; cs2 = cs1; cs1 = s0;
                     cv4 = cv3; cv3 = cv2; cv2 = cv1; cv1 = acc;
@@ -547,7 +597,7 @@ __device__ __forceinline__ void anticausal_sweep(const Src &src, const double *_
                 {
                     const int ua = IIR_U - 1 - u;
                     const double s0 = (double)src.decode(cur.s[ua]);
-                    const double acc = iir_step_anticausal<Src::finite>(s0, s1, s2, s3, s4, v1, v2, v3, v4, c.n_m, c.d_m);
+                    const double acc = Step::template anticausal<Src::finite>(s0, s1, s2, s3, s4, v1, v2, v3, v4, c.n_m, c.d_m);
                     tw[ll * (IIR_U * 4 + 4) + ua * 4 + ch] = (float)(cur.vc[ua] + acc);   // transfer_pixels, gauss.c:117-124
                     s4 = s3; s3 = s2; s2 = s1; s1 = s0;
                     v4 = v3; v3 = v2; v2 = v1; v1 = acc;
@@ -555,8 +605,8 @@ __device__ __forceinline__ void anticausal_sweep(const Src &src, const double *_
             }
         } else {
             if (b > bbeg) {
-                if (interior_causal(b - 1)) rerun_block<false>(src, b - 1, n, nxt.s, nxt.r4, nxt.ck, c, initial_p, nxt.vc);
-                else rerun_block<true>(src, b - 1, n, nxt.s, nxt.r4, nxt.ck, c, initial_p, nxt.vc);
+                if (interior_causal(b - 1)) rerun_block<false, Step>(src, b - 1, n, nxt.s, nxt.r4, nxt.ck, c, initial_p, nxt.vc);
+                else rerun_block<true, Step>(src, b - 1, n, nxt.s, nxt.r4, nxt.ck, c, initial_p, nxt.vc);
             }
 #pragma unroll
             for (int u = IIR_U - 1; u >= 0; --u) {
@@ -566,7 +616,7 @@ __device__ __forceinline__ void anticausal_sweep(const Src &src, const double *_
                     const double s0 = (double)src.decode(cur.s[u]);
                     double acc;
                     if (j < 4) acc = iir_edge_step(j, s0, s1, s2, s3, v1, v2, v3, c.n_m, c.d_m, c.bd_m, initial_m);
-                    else acc = iir_step(s0, s1, s2, s3, s4, v1, v2, v3, v4, c.n_m, c.d_m);
+                    else acc = Step::any(s0, s1, s2, s3, s4, v1, v2, v3, v4, c.n_m, c.d_m);
                     tw[ll * (IIR_U * 4 + 4) + u * 4 + ch] = (float)(cur.vc[u] + acc);   // transfer_pixels, gauss.c:117-124
                     s4 = s3; s3 = s2; s2 = s1; s1 = s0;
                     v4 = v3; v3 = v2; v2 = v1; v1 = acc;
@@ -606,7 +656,7 @@ __device__ __forceinline__ void anticausal_sweep(const Src &src, const double *_
     // prologue: the last block's inputs and causal values, the one before it on its way
     load_block(std::false_type{}, nblocks - 1, slot[0]);
     if (nblocks - 1 > bbeg) load_block(std::false_type{}, nblocks - 2, slot[1]);
-    rerun_block<true>(src, nblocks - 1, n, slot[0].s, slot[0].r4, slot[0].ck, c, initial_p, slot[0].vc);
+    rerun_block<true, Step>(src, nblocks - 1, n, slot[0].s, slot[0].r4, slot[0].ck, c, initial_p, slot[0].vc);
     int b = nblocks - 1;
     const int fast_floor = (bbeg > 1 ? bbeg : 1) + 4;         // lowest b whose group is all-FAST: b-4 >= max(bbeg, 1)
     for (; b >= bbeg && b * IIR_U + 2 * IIR_U > k1; b -= 3) group(std::false_type{}, b);      // the group at the line's end
@@ -622,17 +672,19 @@ __device__ __forceinline__ void anticausal_sweep(const Src &src, const double *_
 // are exp(-1.783/sigma) and exp(-1.723/sigma) (gauss.c:57-58), so after halo = 22.7 sigma steps the
 // influence of the different start has decayed by e^-39 ~ 1e-17 before the first value that is
 // kept.  The true ends of a line keep the reference's start-up.
-template <class Src>
+// Step: ExactStep (the default chain), or FmaStep for the tolerance chain (the same kernels, instantiated on it: rocprof
+// tells the two apart by the template argument, mmhip_drain_native_kernel_ms by the labels of launch_sweeps).
+template <class Src, class Step = ExactStep>
 __global__ void __launch_bounds__(256) k_iir_causal(Src in, double *__restrict__ ckpt, LineArgs g, IirCoef c) {
     const unsigned sgi = blockIdx.x / g.lane_blocks, lb = blockIdx.x % g.lane_blocks;
     const long L = (long)lb * 256 + threadIdx.x;
     const long stride = (long)g.lines * 4;
     if (L >= stride) return;
     const int s0 = (int)sgi * g.seg, s1 = min(g.n, s0 + g.seg), k0 = max(0, s0 - g.halo);
-    causal_sweep(in.for_lane(L), ckpt, (unsigned)stride, (unsigned)L, k0, s0, s1, c);
+    causal_sweep<Step>(in.for_lane(L), ckpt, (unsigned)stride, (unsigned)L, k0, s0, s1, c);
 }
 
-template <class Src>
+template <class Src, class Step = ExactStep>
 __global__ void __launch_bounds__(256) k_iir_anticausal_T(Src in, const double *__restrict__ ckpt, float *__restrict__ outT,
                                                           LineArgs g, IirCoef c, PackOut po) {
     // wave-private staging tile: 16 lines x IIR_U steps x 4 channels, line stride padded by 4 floats
@@ -645,7 +697,7 @@ __global__ void __launch_bounds__(256) k_iir_anticausal_T(Src in, const double *
     const bool active = L < stride;
     const long Lc = active ? L : 0;      // idle lanes of the last wave shadow lane 0; their tile rows are never written out
     const int s0 = (int)sgi * g.seg, s1 = min(g.n, s0 + g.seg), k1 = s1 < g.n ? min(g.n, s1 + g.halo) : g.n;
-    anticausal_sweep(in.for_lane(Lc), ckpt, (unsigned)stride, (unsigned)Lc, g.n, s0, s1, k1, c, tile[wave], lane, line0, g.lines, outT, po, active);
+    anticausal_sweep<Step>(in.for_lane(Lc), ckpt, (unsigned)stride, (unsigned)Lc, g.n, s0, s1, k1, c, tile[wave], lane, line0, g.lines, outT, po, active);
 }
 
 // How to split lines of n steps, `lines` of them, for a recurrence of standard deviation sigma.
@@ -657,18 +709,14 @@ __global__ void __launch_bounds__(256) k_iir_anticausal_T(Src in, const double *
 // + halo steps, at a rate set by the waves a SIMD holds: 1024 SIMDs, and a second wave hides the
 // first one's scalar and memory instructions), =N forces N.  Measured at 16384^2, sigma 20 px: 8.85 ->
 // 8.13 ms with two segments; the gain is large only for frames too small to give every SIMD a wave.
-LineArgs plan_segments(int n, int lines, float sigma) {
+// The count by the model: segments no shorter than min_seg, `forced` > 0 picks that count instead.
+LineArgs split_lines(int n, int lines, int halo, int min_seg, int forced) {
     LineArgs g{n, lines, ((n + IIR_U - 1) / IIR_U) * IIR_U, 0, (unsigned)(((long)lines * 4 + 255) / 256)};
-    const char *env = getenv("MMHIP_GAUSS_SEGMENTS");
-    if (!env || !*env) return g;
-    const int forced = strcmp(env, "auto") ? atoi(env) : 0;
-    if (strcmp(env, "auto") && forced <= 1) return g;
-    const int halo = (((int)ceil(22.7 * (double)sigma) + 2 + IIR_U - 1) / IIR_U) * IIR_U;
     const double waves = (double)g.lane_blocks * 4.0;
     double best = 0.0;
     for (int ns = 1; ns <= 64; ++ns) {
         const int seg = (((n + ns - 1) / ns + IIR_U - 1) / IIR_U) * IIR_U;
-        if (ns > 1 && (seg < halo || (long)seg * (ns - 1) >= n)) break;     // too short to pay / empty last segment
+        if (ns > 1 && (seg < min_seg || (long)seg * (ns - 1) >= n)) break;     // too short to pay / empty last segment
         const double per_simd = ceil(waves * ns / 1024.0);
         const double cost = (double)(seg + (ns > 1 ? halo : 0)) * std::max(1.0, 0.53 * per_simd);
         if (forced > 0 ? ns == forced : (ns == 1 || cost < best * 0.97)) {
@@ -680,7 +728,41 @@ LineArgs plan_segments(int n, int lines, float sigma) {
     return g;
 }
 
+LineArgs plan_segments(int n, int lines, float sigma) {
+    const char *env = getenv("MMHIP_GAUSS_SEGMENTS");
+    const int forced = env && *env && strcmp(env, "auto") ? atoi(env) : 0;
+    if (!env || !*env || (strcmp(env, "auto") && forced <= 1)) return split_lines(n, lines, 0, 0, 1);
+    const int halo = (((int)ceil(22.7 * (double)sigma) + 2 + IIR_U - 1) / IIR_U) * IIR_U;
+    return split_lines(n, lines, halo, halo, forced);
+}
+
+// The tolerance chain's split: always by the model, segments down to two blocks.  From 1024^2 to 16384^2 it gives every
+// SIMD two waves or more: they run side by side in the causal kernel (164 VGPRs); the anticausal kernel's three-slot
+// pipeline needs ~345 registers and takes them one after the other.  Its halo is 14 sigma (+2, rounded up to a block): the start-up's influence then decays by
+// exp(-1.723 * 14) = 3.2e-11 (the slower pole, gauss.c:57-58) before the first value kept, below the f64 noise the
+// reassociated recurrence carries anyway at sigma >= 14 px, and far below an f32 ulp.
+int tolerance_halo(float sigma) { return (((int)ceil(14.0 * (double)sigma) + 2 + IIR_U - 1) / IIR_U) * IIR_U; }
+
+LineArgs plan_tolerance(int n, int lines, float sigma) { return split_lines(n, lines, tolerance_halo(sigma), 2 * IIR_U, 0); }
+
 unsigned segment_count(const LineArgs &g) { return (unsigned)((g.n + g.seg - 1) / g.seg); }
+
+// The two sweeps of one pass: the exact chain's kernels, or the tolerance chain's under labels of their own
+// (mmhip_drain_native_kernel_ms; rocprof tells them apart by the kernel names).
+struct SweepNames { const char *causal, *anticausal; };
+
+template <class Src>
+void launch_sweeps(NativeWorkspace &ws, hipStream_t s, bool tol, SweepNames exact, SweepNames tolerance, const Src &src,
+                   double *ck, float *outT, const LineArgs &g, const IirCoef &c, const PackOut &po) {
+    const unsigned blocks = g.lane_blocks * segment_count(g);
+    if (tol) {
+        ws.timed_launch(tolerance.causal, s, [&] { k_iir_causal<Src, FmaStep><<<blocks, 256, 0, s>>>(src, ck, g, c); });
+        ws.timed_launch(tolerance.anticausal, s, [&] { k_iir_anticausal_T<Src, FmaStep><<<blocks, 256, 0, s>>>(src, ck, outT, g, c, po); });
+    } else {
+        ws.timed_launch(exact.causal, s, [&] { k_iir_causal<<<blocks, 256, 0, s>>>(src, ck, g, c); });
+        ws.timed_launch(exact.anticausal, s, [&] { k_iir_anticausal_T<<<blocks, 256, 0, s>>>(src, ck, outT, g, c, po); });
+    }
+}
 
 // ---- K5: FIR path for sigma < 0.5 px on either axis (gauss.c:264-639) ----------------------------
 // make_rle_curve on the host (double exp, float taps), then per axis: a statistics kernel
@@ -903,45 +985,49 @@ int gaussian_blur(const HNativeRec &rec, const std::vector<HImageDesc> &images, 
     const int hn = y1 - y0;
     // the scan kernels index a block of rows with 32-bit element offsets (MapSrc::at)
     if ((long)std::max(w, hn) * 4 * 20 * 8 >= (1L << 32)) { *err = "gaussian_blur: frame too large for the scan kernels"; return -1; }
+    const bool pack = direct && direct->out && direct->first_row >= y0 && direct->first_row + direct->num_rows <= y1;
+    // The tolerance chain (mmhip_options::gauss_mode, include/mmhip.h) where nothing but the RGBA8 pixels of a whole frame
+    // leaves it: the runtime packs them from this call and keeps no map (skip_map), and the input is a drawable (bytes / 255,
+    // finite).  Everywhere else the exact chain runs.
+    const bool tol = ws.gauss_tolerance && in.kind == IMG_DRAWABLE && pack && direct->skip_map && y0 == 0 && y1 == h;
+    const LineArgs gv = tol ? plan_tolerance(hn, w, vs) : plan_segments(hn, w, vs);
+    const LineArgs gh = tol ? plan_tolerance(w, hn, hs) : plan_segments(w, hn, hs);
     // vertical pass first (gauss.c:155-201): lines = columns, n = rows of the window; result transposed
     // into mapT[w][hn][4].  Its two sweeps read the input where it lies: the float map, or --
     // identity mapping -- the drawable itself: no intermediate map, 4 instead of 16 B/px.
     find_iir_constants(c, vs);
     {
-        const LineArgs g = plan_segments(hn, w, vs);
-        const unsigned blocks = g.lane_blocks * segment_count(g);
+        const SweepNames ex{"iir_causal_vertical", "iir_anticausal_vertical"}, tn{"iir_tol_causal_vertical", "iir_tol_anticausal_vertical"};
+        const PackOut po{nullptr, 0, 0, 0, 0, 0, 1};
         if (in.kind == IMG_FLOATMAP || !identity) {
             const MapSrc src{(in.kind == IMG_FLOATMAP ? (const float *)in.data : out_map) + (long)y0 * w * 4, (unsigned)w * 4u, 0u};
-            ws.timed_launch("iir_causal_vertical", s, [&] { k_iir_causal<<<blocks, 256, 0, s>>>(src, scratch, g, c); });
-            ws.timed_launch("iir_anticausal_vertical", s, [&] { k_iir_anticausal_T<<<blocks, 256, 0, s>>>(src, scratch, mapT, g, c, PackOut{nullptr, 0, 0, 0, 0, 0, 1}); });
+            launch_sweeps(ws, s, tol, ex, tn, src, scratch, mapT, gv, c, po);
         } else {
             const DrawableSrc src{(const uint32_t *)in.data + (long)y0 * in.w, (unsigned)in.w, 0u, 0};
-            ws.timed_launch("iir_causal_vertical", s, [&] { k_iir_causal<<<blocks, 256, 0, s>>>(src, scratch, g, c); });
-            ws.timed_launch("iir_anticausal_vertical", s, [&] { k_iir_anticausal_T<<<blocks, 256, 0, s>>>(src, scratch, mapT, g, c, PackOut{nullptr, 0, 0, 0, 0, 0, 1}); });
+            launch_sweeps(ws, s, tol, ex, tn, src, scratch, mapT, gv, c, po);
         }
     }
     // horizontal pass (gauss.c:203-252): in mapT the window's rows are the "columns"; transposing again
     // restores the original layout, written to rows [y0, y1) of out_map
     find_iir_constants(c, hs);
     {
-        const LineArgs g = plan_segments(w, hn, hs);
-        const unsigned blocks = g.lane_blocks * segment_count(g);
+        const SweepNames ex{"iir_causal_horizontal", "iir_anticausal_horizontal"}, tn{"iir_tol_causal_horizontal", "iir_tol_anticausal_horizontal"};
         // lines of this pass are rows of the window [y0, y1), steps are columns
         PackOut po{nullptr, 0, 0, 0, 0, 0, 1};
-        if (direct && direct->out && direct->first_row >= y0 && direct->first_row + direct->num_rows <= y1) {
+        if (pack) {
             po = PackOut{(unsigned char *)direct->out, (long)direct->row_stride, direct->first_row - y0,
                          direct->first_row + direct->num_rows - y0, direct->region_x, direct->region_x + direct->region_w,
-                         direct->skip_map ? 0 : 1};
+                         direct->skip_map && !(tol && ws.keep_tolerance_map) ? 0 : 1};
             direct->written = true;
+            direct->tolerance = tol;
         }
+        float *outT = out_map + (long)y0 * w * 4;
         if (in.kind == IMG_FLOATMAP) {
             const MapSrc src{mapT, (unsigned)hn * 4u, 0u};
-            ws.timed_launch("iir_causal_horizontal", s, [&] { k_iir_causal<<<blocks, 256, 0, s>>>(src, scratch, g, c); });
-            ws.timed_launch("iir_anticausal_horizontal", s, [&] { k_iir_anticausal_T<<<blocks, 256, 0, s>>>(src, scratch, out_map + (long)y0 * w * 4, g, c, po); });
+            launch_sweeps(ws, s, tol, ex, tn, src, scratch, outT, gh, c, po);
         } else {      // the first pass read bytes: its output is finite
             const FiniteMapSrc src{mapT, (unsigned)hn * 4u, 0u};
-            ws.timed_launch("iir_causal_horizontal", s, [&] { k_iir_causal<<<blocks, 256, 0, s>>>(src, scratch, g, c); });
-            ws.timed_launch("iir_anticausal_horizontal", s, [&] { k_iir_anticausal_T<<<blocks, 256, 0, s>>>(src, scratch, out_map + (long)y0 * w * 4, g, c, po); });
+            launch_sweeps(ws, s, tol, ex, tn, src, scratch, outT, gh, c, po);
         }
     }
     if (hipGetLastError() != hipSuccess) { *err = "gaussian_blur: kernel launch failed"; return -1; }

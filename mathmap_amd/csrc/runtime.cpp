@@ -57,6 +57,14 @@ std::string cache_dir() {
 
 }  // namespace
 
+bool mmhip_check_options(const mmhip_options *opts) {
+    if (opts && opts->gauss_mode != MMHIP_GAUSS_EXACT && opts->gauss_mode != MMHIP_GAUSS_TOLERANCE) {
+        g_err = "options: gauss_mode " + std::to_string(opts->gauss_mode) + " is neither MMHIP_GAUSS_EXACT (0) nor MMHIP_GAUSS_TOLERANCE (1)";
+        return false;
+    }
+    return true;
+}
+
 extern "C" {
 
 const char *mmhip_last_error(void) { return g_err.c_str(); }
@@ -79,6 +87,7 @@ static void generate_closure_kernels(mmhip_filter *f, const KernelOptions &ko) {
 }
 
 static mmhip_filter *compile_source(const char *source, const mmhip_options *opts, const std::map<int, Primary> *consts) {
+    if (!mmhip_check_options(opts)) return nullptr;
     std::unique_ptr<mmhip_filter> f(new mmhip_filter());
     try {
         parse_module(f->module, source);
@@ -207,6 +216,7 @@ int mmhip_filter_userval_info(const mmhip_filter *f, int index, mmhip_userval_in
 const char *mmhip_filter_ir_json(mmhip_filter *f) { return f->ir_json.c_str(); }
 const char *mmhip_filter_ir_json_raw(mmhip_filter *f) { return f->ir_json_raw.c_str(); }
 const char *mmhip_filter_kernel_source(mmhip_filter *f) { return f->ks.source.c_str(); }
+int mmhip_filter_gauss_mode(const mmhip_filter *f) { return f->opts.gauss_mode; }
 int mmhip_filter_num_native_calls(const mmhip_filter *f) { return f->ks.native_sites; }
 double mmhip_filter_jit_seconds(const mmhip_filter *f) { return f->jit_seconds; }
 
@@ -615,6 +625,7 @@ static int next_event_pair(mmhip_invocation *inv) {
 // Durations (ms) of the pixel kernel of every timed launch since the last drain, oldest first;
 // waits for the last of them.  Returns how many were written (at most `cap`).
 long mmhip_direct_native_launches(mmhip_invocation *inv) { return inv->direct_native_launches; }
+long mmhip_tolerance_blur_launches(mmhip_invocation *inv) { return inv->tolerance_blur_launches; }
 
 int mmhip_drain_kernel_ms(mmhip_invocation *inv, double *out_ms, int cap) {
     int n = 0;
@@ -944,6 +955,7 @@ static int run_natives(mmhip_invocation *inv, mmhip_filter *f, const HArgs &a, h
     inv->ws.env.edge_y = f->kopt.edge_y;
     inv->ws.env.edge_color_x = inv->edge_color_x;
     inv->ws.env.edge_color_y = inv->edge_color_y;
+    inv->ws.gauss_tolerance = f->opts.gauss_mode == MMHIP_GAUSS_TOLERANCE;
     // rows of the maps this launch may read: everything, or -- opt-in, full-frame regions only --
     // the stripe being rendered (the filter samples the map within its own rows +- margin)
     int want_lo = 0, want_hi = a.render_height;
@@ -996,6 +1008,7 @@ static int run_natives(mmhip_invocation *inv, mmhip_filter *f, const HArgs &a, h
         e.gen = ++inv->native_gen_counter;
         e.memo_deps = deps;
         if (dk && dk->written) *direct_written = true;
+        if (dk && dk->written && dk->tolerance) ++inv->tolerance_blur_launches;
         if (dk && dk->written && dk->skip_map) {       // nothing to memoise, no map to describe
             e.memo_gen = ~0ULL;
             e.rows = {0, 0};
@@ -1054,6 +1067,8 @@ static mmhip_filter *compile_ir_specialized(const mmhip_filter *f, const std::ma
         }
         std::string err;
         if (!mmhip_filter_finalize(sp, f->kopt, &err)) throw CompileError(err);
+        sp->opts = f->opts;
+        sp->opts.specialize_uservals = 0;
     } catch (const std::exception &e) {
         g_err = e.what();
         mmhip_filter_free(sp);

@@ -146,6 +146,7 @@ struct mmhip_invocation {
                                            // reallocate `ws` underneath a nested render)
     int native_row_margin = -1;                     // mmhip_set_native_row_margin
     long direct_native_launches = 0;                // mmhip_direct_native_launches
+    long tolerance_blur_launches = 0;               // mmhip_tolerance_blur_launches
     // the prologue kernel is skipped while nothing it reads has changed (mmhip_render)
     mm::HArgs pro_args{};
     const mmhip_filter *pro_filter = nullptr;
@@ -172,6 +173,8 @@ extern thread_local std::string g_mmhip_err;   // message behind mmhip_last_erro
 // create, fill f->module (filters, main) and f->code, then finalize (passes + codegen).
 mmhip_filter *mmhip_filter_new_empty();
 bool mmhip_filter_finalize(mmhip_filter *f, const mm::KernelOptions &ko, std::string *err);
+// false (and mmhip_last_error) for options mmhip_compile* refuses
+bool mmhip_check_options(const mmhip_options *opts);
 
 // Unbinds every image-table entry that refers to `data` (a device buffer about to be freed).
 void mmhip_unbind_image(mmhip_invocation *inv, const void *data);
