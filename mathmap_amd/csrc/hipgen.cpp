@@ -18,7 +18,7 @@
 //
 // Environment hooks for experiments (never needed for correct operation): MMHIP_UNROLL, MMHIP_TILE_W,
 // MMHIP_SINGLE_PIXEL, MMHIP_PAIR, MMHIP_PAIR_DEBUG, MMHIP_WAVES_PER_EU, MMHIP_NO_FETCHED_RESULT, MMHIP_NO_SAME_TAPS, MMHIP_NO_OUTSIDE_SHORTCUT, MMHIP_PAIR_MASKS, MMHIP_NT_STORE,
-// MMHIP_MAX_CALL_DEPTH here; MMHIP_NO_CSE in passes.cpp; MMHIP_PPT, MMHIP_HIPRTC_FLAGS, MMHIP_NO_CACHE, MMHIP_CACHE_DIR,
+// MMHIP_PAIR_EXIT, MMHIP_PAIR_EXIT_TAIL, MMHIP_MAX_CALL_DEPTH here; MMHIP_NO_CSE in passes.cpp; MMHIP_PPT, MMHIP_HIPRTC_FLAGS, MMHIP_NO_CACHE, MMHIP_CACHE_DIR,
 // MMHIP_SOURCE_OVERRIDE in runtime.cpp.
 //
 // Statement printing follows the reference's backends/cc.c:192-397 (one C variable
@@ -524,7 +524,8 @@ struct Generator {
     // flow (Mandelbrot and its relatives), the two pixels a work-item renders per loop step are
     // evaluated together: every SSA value is a 2-vector (x component: the first pixel), `if`s are
     // if-converted (both sides evaluated -- the slice is pure -- and the exit phis select), a `while`
-    // runs while either pixel is active with the loop phis frozen per pixel by a select.  Each component
+    // runs while either pixel is active with the loop phis frozen per pixel by a select (with lane masks: only
+    // at the back edges at which a lane leaves, see pair_while_exit).  Each component
     // sees exactly the scalar kernel's operations in the scalar kernel's order.  What it buys: a gfx950
     // SIMD hands a wave an issue slot every ~4 cycles, in which the wave can issue two independent vector
     // instructions (2 cycles each) -- a single pixel's dependent chain uses half of that, whatever the
@@ -683,8 +684,11 @@ struct Generator {
 
     // operand as a 2-vector of the wanted type (mm_vf / mm_vi broadcast scalars and convert int -> float)
     std::string pbool(const Primary &p) {        // operand as mm_bb
-        if (p.kind == Primary::IntConst) return p.i ? "mm_bu(true)" : "mm_bu(false)";
-        if (p.kind == Primary::Val && p.value->index < 0) return "mm_bu(false)";
+        const std::string bu = pair_exit ? "mm_xbu(" : "mm_bu(";      // (exit-driven loops: no exec in the broadcast either)
+        if (p.kind == Primary::IntConst) return bu + (p.i ? "true)" : "false)");
+        if (p.kind == Primary::Val && p.value->index < 0) return bu + "false)";
+        // (a uniform value that is not a literal goes through the ballot of mm_bu: a select between 64-bit constants on a
+        // uniform bool is a v_cndmask_b32 pair to this compiler, and the mask would sit in vector registers)
         if (pair_uniform.count(p.value)) return "mm_bu((bool)u" + vname(p.value) + ")";
         if (pair_bools.count(p.value)) return vname(p.value);
         return "mm_tob(" + pprim(p, Ty::Int) + ")";
@@ -746,12 +750,13 @@ struct Generator {
         }
         // the truth-valued operators: a pair of bools; as an int (0 / 1) only if the value is used as one
         std::string b;
-        if (!strcmp(cn, "NOT")) b = "mm_notb(" + pbool(r.args[0]) + ")";
+        const std::string notb = pair_exit ? "mm_xnotb(" : "mm_notb(";
+        if (!strcmp(cn, "NOT")) b = notb + pbool(r.args[0]) + ")";
         else if (!strcmp(cn, "EQ") && pair_prim_bool(r.args[0]) && pair_prim_bool(r.args[1])) {
             // b == 0 is !b, b == 1 is b, otherwise the equivalence of two truth values
             const Primary &x = r.args[0], &y = r.args[1];
-            if (y.kind == Primary::IntConst) b = y.i ? pbool(x) : "mm_notb(" + pbool(x) + ")";
-            else if (x.kind == Primary::IntConst) b = x.i ? pbool(y) : "mm_notb(" + pbool(y) + ")";
+            if (y.kind == Primary::IntConst) b = y.i ? pbool(x) : notb + pbool(x) + ")";
+            else if (x.kind == Primary::IntConst) b = x.i ? pbool(y) : notb + pbool(y) + ")";
             else b = "mm_eqb(" + pbool(x) + ", " + pbool(y) + ")";
         } else {
             bool done = false;
@@ -815,8 +820,10 @@ struct Generator {
                 // a plain copy of an invariant scalar stays a broadcast (nothing to gain); ops on uniform values do not
                 if (ok && s->rhs.kind == Rhs::Prim && !(s->rhs.prim.kind == Primary::Val && pair_uniform.count(s->rhs.prim.value))) ok = false;
                 // truth values stay pairs of bools built from the (broadcast) uniform operands: the compiler evaluates such a
-                // comparison on the scalar unit anyway, and keeps the pair in lane masks only in that form (checked in the ISA)
-                if (ok && pair_bools.count(s->lhs)) ok = false;
+                // comparison on the scalar unit anyway, and keeps the pair in lane masks only in that form (checked in the ISA).
+                // With lane masks that no longer holds -- the ballot of a uniform comparison is a v_cmp per iteration -- so the
+                // exit-driven loops (pair_exit) keep them as scalar bools, broadcast with mm_bu where a pair is wanted.
+                if (ok && pair_bools.count(s->lhs) && !pair_exit) ok = false;
                 if (ok) pair_uniform.insert(s->lhs);
             } else if (s->kind == Stmt::If) {
                 pair_mark_uniform(s->then_);
@@ -847,12 +854,252 @@ struct Generator {
         return ivs;
     }
 
+    // ---- exit-driven loops (MM_PAIR_EXIT, lane masks only) ------------------------------------------------
+    // A pixel's `active` bit is monotone: it clears once.  The value a loop phi has after the loop is the value it
+    // had at the back edge at which its pixel's bit cleared, so nothing has to be selected at any other back edge.
+    // The loop runs in two levels: the inner do-while is the likely path (the phis' running copies take their next
+    // values unconditionally, `left = active & ~cond` is two s_andn2_b64, one scalar test), the outer level is the
+    // exit block: every phi that is read after the loop has an exit copy, initialised with the phi's initial value
+    // and written there for the lanes in `left`, which are then cleared from `active`.  Every lane that ever was
+    // active is written exactly once, at the back edge and with the value of the last select that changed it in
+    // the per-iteration form, so the results are the same bits.  (Two levels, one exit each: with two exits from
+    // one loop the compiler's control-flow passes rebuild the conditions as lane masks and copy the phis' registers
+    // at the back edge; profiles/r05_pair_loop_isa.txt has the counts of the shapes tried.)
+    //
+    // A wave-uniform conjunct of the loop condition -- `n < 31` of an escape-time loop: a comparison of uniform ints
+    // such that the condition is false for every lane once it has one value -- is not ANDed into the masks at all:
+    // inside the loop its name is bound to the value it has while the loop runs (the compiler folds the logic built
+    // on it), the comparison itself is made at the back edge on the scalar unit, and when it ends the loop every
+    // active lane leaves.  Only taken when no phi that is read after the loop depends on the conjunct (in the last
+    // iteration its name holds the wrong value).  Looking at one iteration is enough for that: in every iteration but the
+    // last the bound name *is* the conjunct's value, so whatever the phis carry into a later iteration is right; wrong
+    // values only arise in the last iteration, no iteration follows it, and what it leaves behind is read through the
+    // exit copies alone -- whose next values the scan has shown not to depend on the conjunct.  The conjunct's own
+    // operands are read at the end of the body, before the phis step.  The back edge is one asm statement then (MM_PAIR_EXIT_TAIL, default
+    // 1): the compiler combines the two tests as lane masks (s_cselect_b64, s_and_b64 with exec, branch on vcc:
+    // 12 scalar instructions per iteration), the statement needs 6 and the loop 9.
+    bool pair_exit = false;
+    bool pair_exit_asm_tail = true;
+    const Stmt *pair_split_def = nullptr;      // the uniform conjunct's defining statement, while its loop body is printed
+    bool pair_split_leave = false;             // the value with which it ends the loop
+    struct PairBody {                          // what pair_find_split needs to know about a loop body
+        std::set<const Value *> defs;
+        std::map<const Value *, const Stmt *> if_of;      // exit phi of an `if` -> the if
+        std::vector<const Stmt *> order;                  // assignments and if-phis in program order
+        bool nested_loop = false;
+    };
+    void pair_scan_body(const Block &b, PairBody &pb) const {
+        for (const Stmt *s : b) {
+            if (!s->in_pixel) continue;
+            if (s->kind == Stmt::Assign) { pb.defs.insert(s->lhs); pb.order.push_back(s); }
+            if (s->kind == Stmt::While) pb.nested_loop = true;
+            if (s->kind == Stmt::If) {
+                pair_scan_body(s->then_, pb);
+                pair_scan_body(s->else_, pb);
+                for (const Stmt *ph : s->phis)
+                    if (ph->in_pixel) { pb.defs.insert(ph->lhs); pb.if_of[ph->lhs] = s; pb.order.push_back(ph); }
+            }
+        }
+    }
+    // three-valued truth of `p` (0, 1, -1: unknown) when the value `l` is `lv` and nothing else is known
+    int pair_eval3(const Primary &p, const PairBody &pb, const Value *l, int lv, int depth = 0) const {
+        if (p.kind == Primary::IntConst) return p.i == 0 ? 0 : p.i == 1 ? 1 : -1;
+        if (p.kind != Primary::Val || depth > 32) return -1;
+        if (p.value->index < 0) return 0;
+        if (p.value == l) return lv;
+        if (!pb.defs.count(p.value) || !pair_bools.count(p.value)) return -1;
+        const Stmt *d = p.value->def;
+        if (!d) return -1;
+        if (d->kind == Stmt::Phi) {
+            auto it = pb.if_of.find(p.value);
+            if (it == pb.if_of.end() || d->rhs.kind != Rhs::Prim || d->rhs2.kind != Rhs::Prim) return -1;
+            const Primary &cp = it->second->cond.prim;
+            const int c = pair_eval3(cp, pb, l, lv, depth + 1);
+            // `c ? c : b` is `c ? 1 : b`, `c ? a : c` is `c ? a : 0`
+            const bool same1 = cp.kind == Primary::Val && d->rhs.prim.kind == Primary::Val && d->rhs.prim.value == cp.value && pair_bools.count(cp.value);
+            const bool same2 = cp.kind == Primary::Val && d->rhs2.prim.kind == Primary::Val && d->rhs2.prim.value == cp.value && pair_bools.count(cp.value);
+            const int a = same1 ? 1 : pair_eval3(d->rhs.prim, pb, l, lv, depth + 1);
+            const int b = same2 ? 0 : pair_eval3(d->rhs2.prim, pb, l, lv, depth + 1);
+            if (c == 1) return a;
+            if (c == 0) return b;
+            return a == b ? a : -1;
+        }
+        if (d->kind != Stmt::Assign) return -1;
+        if (d->rhs.kind == Rhs::Prim) return pair_eval3(d->rhs.prim, pb, l, lv, depth + 1);
+        if (d->rhs.kind != Rhs::Op) return -1;
+        const char *cn = d->rhs.op->cname;
+        if (!strcmp(cn, "NOT")) { const int x = pair_eval3(d->rhs.args[0], pb, l, lv, depth + 1); return x < 0 ? -1 : !x; }
+        if (!strcmp(cn, "EQ") && pair_prim_bool(d->rhs.args[0]) && pair_prim_bool(d->rhs.args[1])) {
+            const int x = pair_eval3(d->rhs.args[0], pb, l, lv, depth + 1), y = pair_eval3(d->rhs.args[1], pb, l, lv, depth + 1);
+            return x < 0 || y < 0 ? -1 : x == y;
+        }
+        return -1;
+    }
+    // the uniform conjunct of w's condition, if there is one that may be split off: sets pair_split_leave
+    const Stmt *pair_find_split(const Stmt *w, const std::set<const Value *> &outside) {
+        if (w->cond.prim.kind != Primary::Val) return nullptr;
+        PairBody pb;
+        pair_scan_body(w->body, pb);
+        if (pb.nested_loop) return nullptr;
+        // the condition at the back edge: the condition phi's next value
+        const Stmt *cph = nullptr;
+        for (const Stmt *ph : w->phis) if (ph->in_pixel && ph->lhs == w->cond.prim.value) cph = ph;
+        if (!cph || cph->rhs2.kind != Rhs::Prim) return nullptr;
+        for (const Stmt *d : pb.order) {
+            if (d->kind != Stmt::Assign || !pair_uniform.count(d->lhs) || !pair_bools.count(d->lhs) || d->rhs.kind != Rhs::Op) continue;
+            const char *cn = d->rhs.op->cname;
+            if ((strcmp(cn, "LESS") && strcmp(cn, "LEQ") && strcmp(cn, "EQ")) || d->rhs.args.size() != 2) continue;
+            if (d->rhs.args[0].type() != Ty::Int || d->rhs.args[1].type() != Ty::Int) continue;
+            for (int lv = 0; lv < 2; ++lv) {
+                if (pair_eval3(cph->rhs2.prim, pb, d->lhs, lv) != 0) continue;
+                // what depends on the conjunct must not reach a phi that is read after the loop
+                std::set<const Value *> dep{d->lhs};
+                auto in = [&](const Primary &p) { return p.kind == Primary::Val && dep.count(p.value) > 0; };
+                for (const Stmt *q : pb.order) {
+                    bool dp = false;
+                    if (q->kind == Stmt::Assign) { if (q->rhs.kind == Rhs::Prim) dp = in(q->rhs.prim); for (const Primary &a : q->rhs.args) dp = dp || in(a); }
+                    else dp = in(pb.if_of.at(q->lhs)->cond.prim) || in(q->rhs.prim) || in(q->rhs2.prim);
+                    if (dp) dep.insert(q->lhs);
+                }
+                bool ok = true;
+                for (const Stmt *ph : w->phis)
+                    if (ph->in_pixel && outside.count(ph->lhs) && in(ph->rhs2.prim)) ok = false;
+                if (!ok) continue;
+                pair_split_leave = lv != 0;
+                return d;
+            }
+        }
+        return nullptr;
+    }
+    // operand of the back edge's scalar comparison: a literal, or the uniform value in a scalar register
+    bool pair_tail_operand(const Primary &p, std::string &text, std::vector<std::string> &inputs, int first_input) {
+        if (p.kind == Primary::IntConst) { text = std::to_string(p.i); return true; }
+        if (p.kind != Primary::Val) return false;
+        text = "%" + std::to_string(first_input + (int)inputs.size());
+        inputs.push_back("__builtin_amdgcn_readfirstlane((int)(" + prim(p, PIXEL) + "))");
+        return true;
+    }
+    void pair_while_exit(Stmt *s, const std::string &ind, const std::string &mask) {
+        const std::string id = std::to_string(pair_ids++), a = "mm_a" + id, l = "mm_l" + id, I2 = ind + "    ";
+        std::set<const Value *> outside;
+        pair_uses(code.body, s, outside);
+        for (int i = 0; i < 4; ++i) outside.insert(code.result[i]);
+        for (Stmt *ph : s->phis)
+            if (ph->in_pixel) out << ind << vname(ph->lhs) << " = " << pval_as(ph->rhs.prim, ph->lhs) << ";\n";
+        // exit copies: what a pixel that never enters the loop sees is the initial value
+        int k = 0;
+        for (Stmt *ph : s->phis)
+            if (ph->in_pixel) {
+                if (outside.count(ph->lhs))
+                    out << ind << (pair_bools.count(ph->lhs) ? "mm_bb" : pair_ctype(ph->lhs->var->type)) << " " << a << "_e" << k << " = " << vname(ph->lhs) << ";\n";
+                ++k;
+            }
+        const std::vector<const Stmt *> ivs = pair_find_uniform_ivs(s);
+        std::set<const Value *> iv_set;
+        for (const Stmt *ph : ivs) {
+            iv_set.insert(ph->lhs);
+            pair_uniform.erase(ph->lhs);       // the initial value is printed with the ordinary names
+            const std::string init = prim(ph->rhs.prim, PIXEL);
+            pair_uniform.insert(ph->lhs);
+            out << ind << (ph->lhs->var->type == Ty::Float ? "float u" : "int u") << vname(ph->lhs) << " = " << init << ";\n";
+        }
+        const Stmt *split = pair_find_split(s, outside);
+        const bool leave = pair_split_leave;
+        out << ind << "mm_bb " << a << " = mm_andb(" << mask << ", " << pbool(s->cond.prim) << ");\n";
+        out << ind << "while (" << a << ".x | " << a << ".y) {\n";
+        // the back edge's scalar comparison as one asm statement: its operands
+        std::vector<std::string> tail_inputs;
+        std::string tail_o0, tail_o1;
+        const bool asm_tail = split && pair_exit_asm_tail &&
+                              !(split->rhs.args[0].kind == Primary::IntConst && split->rhs.args[1].kind == Primary::IntConst) &&
+                              pair_tail_operand(split->rhs.args[0], tail_o0, tail_inputs, 8) && pair_tail_operand(split->rhs.args[1], tail_o1, tail_inputs, 8);
+        out << ind << "  mm_bb " << l << ";" << (asm_tail ? " unsigned long " + l + "_u, " + l + "_t;" : split ? " bool " + l + "_b;" : "") << "\n";
+        out << ind << "  do {\n";
+        const Stmt *outer_split = pair_split_def;
+        const bool outer_leave = pair_split_leave;
+        pair_split_def = split;
+        pair_split_leave = leave;
+        pair_stmts(s->body, I2, a);
+        pair_split_def = outer_split;
+        pair_split_leave = outer_leave;
+        // The conjunct stands for a statement of the body: its operands are read here, before the phis and the induction
+        // variables take their next values (an operand may be such a phi: `m = n; n = n + 1` with `m < 6` as the bound).
+        if (asm_tail)
+            for (size_t i = 0; i < tail_inputs.size(); ++i) {
+                out << I2 << "const int " << l << "_o" << i << " = " << tail_inputs[i] << ";\n";
+                tail_inputs[i] = l + "_o" + std::to_string(i);
+            }
+        else if (split)
+            out << I2 << l << "_b = (bool)(" << rhs(split->rhs, PIXEL, split, split->lhs->var) << ") == " << (leave ? "true" : "false") << ";\n";
+        // back edge: a parallel copy (temporaries first), nothing selected
+        k = 0;
+        for (Stmt *ph : s->phis)
+            if (ph->in_pixel && !iv_set.count(ph->lhs))
+                out << I2 << "const " << (pair_bools.count(ph->lhs) ? "mm_bb" : pair_ctype(ph->lhs->var->type)) << " " << a << "_n" << k++
+                    << " = " << pval_as(ph->rhs2.prim, ph->lhs) << ";\n";
+        k = 0;
+        for (Stmt *ph : s->phis)
+            if (ph->in_pixel && !iv_set.count(ph->lhs)) out << I2 << vname(ph->lhs) << " = " << a << "_n" << k++ << ";\n";
+        for (const Stmt *ph : ivs) out << I2 << "u" << vname(ph->lhs) << " = " << prim(ph->rhs2.prim, PIXEL) << ";\n";
+        // lanes that leave at this back edge
+        const std::string c = pbool(s->cond.prim);
+        const std::string lx = a + ".x & ~" + c + ".x", ly = a + ".y & ~" + c + ".y";
+        if (asm_tail) {
+            // SCC = the conjunct; _u = all ones when it ends the loop; left = active & ~cond; _t = _u | left.x | left.y
+            const char *cn = split->rhs.op->cname;
+            const char *cmp = !strcmp(cn, "LESS") ? "s_cmp_lt_i32" : !strcmp(cn, "LEQ") ? "s_cmp_le_i32" : "s_cmp_eq_i32";
+            out << I2 << "const mm_bb " << l << "_c = " << c << ";\n";
+            out << I2 << "asm(\"" << cmp << " " << tail_o0 << ", " << tail_o1 << "\\n\\ts_cselect_b64 %2, " << (leave ? "-1, 0" : "0, -1")
+                << "\\n\\ts_andn2_b64 %0, %4, %6\\n\\ts_andn2_b64 %1, %5, %7\\n\\ts_or_b64 %3, %2, %0\\n\\ts_or_b64 %3, %3, %1\"\n"
+                << I2 << "    : \"=&s\"(" << l << ".x), \"=&s\"(" << l << ".y), \"=&s\"(" << l << "_u), \"=&s\"(" << l << "_t)\n"
+                << I2 << "    : \"s\"(" << a << ".x), \"s\"(" << a << ".y), \"s\"(" << l << "_c.x), \"s\"(" << l << "_c.y)";
+            for (const std::string &in : tail_inputs) out << ", \"s\"(" << in << ")";
+            out << " : \"scc\");\n";
+            out << ind << "  } while (" << l << "_t == 0);\n";
+            // the uniform conjunct has ended the loop: every lane that was still active leaves
+            out << ind << "  " << l << ".x |= " << a << ".x & " << l << "_u; " << l << ".y |= " << a << ".y & " << l << "_u;\n";
+        } else if (split) {
+            out << I2 << l << " = mm_bb{" << lx << ", " << ly << "};\n";
+            out << ind << "  } while (!" << l << "_b && (" << l << ".x | " << l << ".y) == 0);\n";
+            out << ind << "  if (" << l << "_b) " << l << " = " << a << ";      // the uniform conjunct has ended the loop: every active lane leaves\n";
+        } else {
+            out << I2 << l << " = mm_bb{" << lx << ", " << ly << "};\n";
+            out << ind << "  } while ((" << l << ".x | " << l << ".y) == 0);\n";
+        }
+        // exit block: the phis hold their next values; a uniform induction variable's is its scalar twin's
+        k = 0;
+        for (Stmt *ph : s->phis)
+            if (ph->in_pixel) {
+                if (outside.count(ph->lhs)) {
+                    std::string nv = vname(ph->lhs);
+                    if (iv_set.count(ph->lhs))
+                        nv = ph->lhs->var->type == Ty::Float ? "mm_vf((float)u" + nv + ")" : "mm_vi(mm_s2v((int)u" + nv + "))";
+                    out << ind << "  " << a << "_e" << k << " = mm_sel2(" << l << ", " << nv << ", " << a << "_e" << k << ");\n";
+                }
+                ++k;
+            }
+        out << ind << "  " << a << ".x &= ~" << l << ".x; " << a << ".y &= ~" << l << ".y;\n";
+        out << ind << "}\n";
+        // after the loop a phi is read through its exit copy
+        k = 0;
+        for (Stmt *ph : s->phis)
+            if (ph->in_pixel) {
+                if (outside.count(ph->lhs)) out << ind << vname(ph->lhs) << " = " << a << "_e" << k << ";\n";
+                ++k;
+            }
+        for (const Stmt *ph : ivs) pair_uniform.erase(ph->lhs);
+    }
+
     // `mask`: the expression (mm_bb) under which the block runs
     void pair_stmts(Block &b, const std::string &ind, const std::string &mask) {
         for (Stmt *s : b) {
             if (!s->in_pixel) continue;
             switch (s->kind) {
                 case Stmt::Assign:
+                    if (s == pair_split_def) {       // tested at the back edge (pair_while_exit): inside the loop it holds
+                        out << ind << "const bool u" << vname(s->lhs) << " = " << (pair_split_leave ? "false" : "true") << ";\n";
+                        break;
+                    }
                     if (pair_uniform.count(s->lhs)) {       // scalar statement, the scalar kernel's own expression
                         const char *ty = pair_bools.count(s->lhs) ? "bool" : s->lhs->var->type == Ty::Float ? "float" : "int";
                         out << ind << "const " << ty << " u" << vname(s->lhs) << " = " << rhs(s->rhs, PIXEL, s, s->lhs->var) << ";\n";
@@ -864,7 +1111,7 @@ struct Generator {
                     const std::string c = "mm_c" + std::to_string(pair_ids++);
                     out << ind << "const mm_bb " << c << " = " << pbool(s->cond.prim) << ";\n";
                     pair_stmts(s->then_, ind, "mm_andb(" + mask + ", " + c + ")");
-                    pair_stmts(s->else_, ind, "mm_andb(" + mask + ", mm_notb(" + c + "))");
+                    pair_stmts(s->else_, ind, "mm_andb(" + mask + (pair_exit ? ", mm_xnotb(" : ", mm_notb(") + c + "))");
                     for (Stmt *ph : s->phis)
                         if (ph->in_pixel)
                             out << ind << vname(ph->lhs) << " = mm_sel2(" << c << ", " << pval_as(ph->rhs.prim, ph->lhs) << ", "
@@ -872,6 +1119,7 @@ struct Generator {
                     break;
                 }
                 case Stmt::While: {
+                    if (pair_exit) { pair_while_exit(s, ind, mask); break; }
                     const std::string a = "mm_a" + std::to_string(pair_ids++);
                     std::set<const Value *> outside;
                     pair_uses(code.body, s, outside);
@@ -1268,6 +1516,11 @@ struct Generator {
         ks.unroll = opt.unroll > 0 ? opt.unroll : auto_unroll();
         pair_mode = opt.unroll <= 0 && !getenv("MMHIP_UNROLL") && ks.row_values == 0 && pair_eligible();   // (row values are per pixel of a pair)
         if (pair_mode) { ks.unroll = 2; pair_infer_bools(); }
+        {   // exit-driven pair loops (pair_while_exit): lane masks only; MMHIP_PAIR_EXIT=0 keeps the per-iteration selects
+            const char *pe = getenv("MMHIP_PAIR_EXIT"), *pm = getenv("MMHIP_PAIR_MASKS"), *pt = getenv("MMHIP_PAIR_EXIT_TAIL");
+            pair_exit = pair_mode && (!pe || atoi(pe)) && (!pm || atoi(pm));
+            pair_exit_asm_tail = !pt || atoi(pt);
+        }
         ks.pair_mode = pair_mode;
         out << "#define MM_UNROLL " << ks.unroll << "\n";
         out << "#define MM_NATIVE_REC_BYTES " << (int)MM_NATIVE_REC_BYTES << "\n#define MM_NATIVE_DYN_CALLS " << (int)MM_NATIVE_DYN_CALLS << "\n";
@@ -1347,6 +1600,17 @@ MM_DEV mm_image mm_native_result_in_loop(const mm_args &A, int &n, int sites) {
 }
 )";
         emit_functions();
+        if (pair_exit)      // emitted here, not in the device prelude: the other kernels' text, and keys, stay as they were
+            out << R"(#define MM_PAIR_EXIT 1
+// exit-driven pair loops (hipgen.cpp pair_while_exit).  mm_xnotb: a lane mask's bits outside exec are never read -- selects
+// read their own lane's bit, and every mask a branch tests is ANDed with one that lies inside exec -- so NOT needs no re-AND
+// and a broadcast no ballot.
+MM_DEV mm_bb mm_xnotb(mm_bb a) { return mm_bb{~a.x, ~a.y}; }
+MM_DEV mm_bb mm_xbu(bool u) { const unsigned long m = u ? ~0ul : 0ul; return mm_bb{m, m}; }      // a literal truth value, likewise
+// a wave-uniform int for the exit copies, moved from its scalar register where it is wanted (as an ordinary operand it
+// would pull the loop counter, and the loop's bound test, onto the vector unit)
+MM_DEV int mm_s2v(int u) { int r; asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(__builtin_amdgcn_readfirstlane(u))); return r; }
+)";
         // ---- prologue ----
         ks.prologue_uses_time = hoisted_uses_time(code.body);
         ks.prologue_name = "mm_prologue";
