@@ -137,6 +137,25 @@ int mmhip_set_by_name(mmhip_invocation *inv, const char *name, const char *value
 int mmhip_set_image_host(mmhip_invocation *inv, int index, const uint8_t *pixels, int width, int height, int channels);
 /* Input image already resident in HBM as packed 0xRRGGBBAA uint32 per pixel. */
 int mmhip_set_image_device(mmhip_invocation *inv, int index, const void *device_rgba32, int width, int height);
+/* Multi-frame input (an extension; the reference's drawables carry num_frames cache entries, mathmap_cmdline.c:131-184):
+   num_frames frames of width x height, packed one after the other -- color_t[num_frames][height][width] in HBM, host
+   pixels frame by frame in the single-image format.  The two setters above are the num_frames = 1 case.
+     - in(xy, n) reads frame (int)n -- truncated toward zero as x86-64 converts it, so -0.5 is frame 0 and NaN or a value
+       beyond int is none; plain in(xy) passes t and reads frame (int)t.  n may differ from pixel to pixel.
+     - Per tap, in the reference's order: an unbound image is white; the edge behaviour is applied; x outside gives
+       edge colour x; y outside edge colour y; then a frame outside [0, num_frames) gives opaque white.  An edge colour
+       wins over a bad frame.
+     - All frames have one size; scale and middle are those of one frame.
+     - Native filters and render() sample ORIG_VAL(x, y, image, 0.0) (builtins.c:273-343 render_image): gaussian_blur(in, ..),
+       convolve, render(in) and the direct RGBA8 blur output (exact and tolerance chains) read FRAME 0 of a sequence.
+     - Float maps (native results, closure images) have one frame and ignore the frame number.
+     - The reference-ABI tier (mathmap_hip_backend.h) binds one frame per drawable.
+   Errors: num_frames < 1; a total byte count that overflows or cannot be allocated; height * num_frames of
+   2^31 rows or more (the generic fetch counts the sequence's rows in an int).  Rebinding makes native results stale. */
+int mmhip_set_image_sequence_host(mmhip_invocation *inv, int index, const uint8_t *pixels, int width, int height, int channels,
+                                  int num_frames);
+int mmhip_set_image_sequence_device(mmhip_invocation *inv, int index, const void *device_rgba32, int width, int height,
+                                    int num_frames);
 int mmhip_set_edge_colors(mmhip_invocation *inv, uint32_t color_x, uint32_t color_y);
 int mmhip_set_render_size(mmhip_invocation *inv, int render_width, int render_height);
 /* sub-pixel sampling offset of the slice (mathmap.h:219; -0.5 for the second supersampling pass) */

@@ -65,6 +65,8 @@ SYMBOLS = {
     "mmhip_set_by_name": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p]),
     "mmhip_set_image_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "mmhip_set_image_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "mmhip_set_image_sequence_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mmhip_set_image_sequence_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "mmhip_set_edge_colors": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "mmhip_set_render_size": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mmhip_set_sampling_offset": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),

@@ -186,6 +186,17 @@ class Filter:
         return Invocation(self, width, height)
 
 
+def as_image_sequence(array):
+    """A host image ([H,W,3|4]) or image sequence ([N,H,W,3|4]) as the contiguous uint8 [N,H,W,C] array that
+    mmhip_set_image_sequence_host takes."""
+    a = np.ascontiguousarray(array, dtype=np.uint8)
+    if a.ndim == 3:
+        a = a[None]
+    if a.ndim != 4 or a.shape[0] < 1:
+        raise MathMapError("an image is [H,W,3|4], an image sequence [N,H,W,3|4] with N >= 1; got shape %s" % (tuple(np.shape(array)),))
+    return a
+
+
 class Invocation:
     """A filter bound to a canvas size, user values and input images (all in HBM)."""
 
@@ -248,18 +259,22 @@ class Invocation:
         self._check(lib().mmhip_set_gradient(self._h, u["index"], a.ctypes.data_as(C.c_void_p)))
 
     def set_image(self, name, array):
-        """Binds a host uint8 array [H,W,3|4] as input drawable (uploaded once to HBM)."""
+        """Binds a host uint8 array as input drawable (uploaded once to HBM): [H,W,3|4] is one image,
+        [N,H,W,3|4] a sequence of N frames of one size.  in(xy, n) reads frame (int)n of it (plain
+        in(xy): frame (int)t), and opaque white where there is no such frame; gaussian_blur, convolve
+        and render() read frame 0."""
         u = self._index(name)
-        a = np.ascontiguousarray(array, dtype=np.uint8)
-        h, w, c = a.shape
-        self._check(lib().mmhip_set_image_host(self._h, u["index"], a.ctypes.data_as(C.c_void_p), w, h, c))
+        a = as_image_sequence(array)
+        n, h, w, c = a.shape
+        self._check(lib().mmhip_set_image_sequence_host(self._h, u["index"], a.ctypes.data_as(C.c_void_p), w, h, c, n))
 
-    def set_image_device(self, name, device_ptr, width, height, keepalive=None):
-        """Binds a packed 0xRRGGBBAA uint32 image already resident in HBM."""
+    def set_image_device(self, name, device_ptr, width, height, keepalive=None, num_frames=1):
+        """Binds a packed 0xRRGGBBAA uint32 image already resident in HBM; with num_frames > 1, that
+        many frames of width x height one after the other ([N,H,W] uint32)."""
         u = self._index(name)
+        self._check(lib().mmhip_set_image_sequence_device(self._h, u["index"], C.c_void_p(device_ptr), width, height, num_frames))
         if keepalive is not None:
             self._keep.append(keepalive)
-        self._check(lib().mmhip_set_image_device(self._h, u["index"], C.c_void_p(device_ptr), width, height))
 
     def set_native_row_margin(self, margin):
         """Striped frames: let native filters (gaussian_blur) fill only the rows a stripe render

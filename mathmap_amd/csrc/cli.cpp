@@ -49,6 +49,11 @@ void usage() {
            "      --gauss-mode=MODE       gaussian_blur arithmetic: exact (default, the\n"
            "                              reference's values) or tolerance (faster, RGBA8\n"
            "                              output within 1 per channel of exact)\n"
+           "      --input-frames=NUM      an input image whose file name contains a\n"
+           "                              conversion like %%d is a sequence: frames 0 to\n"
+           "                              NUM-1 are read from the files so named (all of\n"
+           "                              one size) and in(xy, n) reads frame n; with -F,\n"
+           "                              in(xy, frame) processes a clip frame by frame\n"
            "\n"
            "Report bugs and suggestions to schani@complang.tuwien.ac.at\n",
            cache_size);
@@ -170,18 +175,39 @@ bool write_png_rgb(const char *path, const unsigned char *rgba, int w, int h) {
 
 struct Define { std::string name, value; };
 
+// --input-frames: a define's value with exactly one %d-style conversion (%d, %04d, ...; %% is a literal percent sign)
+// names one file per frame.  0: no conversion, 1: such a pattern, -1: anything else snprintf must not be handed.
+int frame_pattern(const std::string &v) {
+    int conversions = 0;
+    for (size_t i = 0; i < v.size(); ++i) {
+        if (v[i] != '%') continue;
+        if (i + 1 < v.size() && v[i + 1] == '%') { ++i; continue; }
+        size_t j = i + 1;
+        while (j < v.size() && isdigit((unsigned char)v[j])) ++j;
+        if (j >= v.size() || v[j] != 'd' || j - i > 6) return -1;
+        ++conversions;
+        i = j;
+    }
+    return conversions == 0 ? 0 : conversions == 1 ? 1 : -1;
+}
+std::string frame_file(const std::string &pattern, int frame) {
+    char name[4096];
+    snprintf(name, sizeof name, pattern.c_str(), frame);
+    return name;
+}
+
 }  // namespace
 
 enum {
     OPT_VERSION = 256, OPT_HELP, OPT_HTMLDOC, OPT_BENCH_NO_OUTPUT, OPT_BENCH_ONLY_COMPILE,
-    OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE
+    OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE, OPT_INPUT_FRAMES
 };
 
 int main(int argc, char **argv) {
     std::string script;
     bool have_script = false, htmldoc = false, bench_no_output = false, bench_no_backend = false;
     int antialiasing = 0, supersampling = 0, img_width = 0, img_height = 0, size_is_set = 0;
-    int bench_render_count = 1, num_frames = 1, gauss_mode = MMHIP_GAUSS_EXACT;
+    int bench_render_count = 1, num_frames = 1, input_frames = 0, gauss_mode = MMHIP_GAUSS_EXACT;
     const char *generator = nullptr;
     std::vector<Define> defines;
     static struct option long_options[] = {
@@ -194,7 +220,8 @@ int main(int argc, char **argv) {
         {"bench-no-compile-time-limit", no_argument, 0, OPT_BENCH_NO_COMPILE_TIME_LIMIT},
         {"bench-no-backend", no_argument, 0, OPT_BENCH_NO_BACKEND},
         {"bench-render-count", required_argument, 0, OPT_BENCH_RENDER_COUNT},
-        {"frames", required_argument, 0, 'F'}, {"gauss-mode", required_argument, 0, OPT_GAUSS_MODE}, {0, 0, 0, 0}};
+        {"frames", required_argument, 0, 'F'}, {"gauss-mode", required_argument, 0, OPT_GAUSS_MODE},
+        {"input-frames", required_argument, 0, OPT_INPUT_FRAMES}, {0, 0, 0, 0}};
     for (;;) {
         int idx;
         int option = getopt_long(argc, argv, "f:ioF:D:c:g:s:", long_options, &idx);
@@ -243,6 +270,13 @@ int main(int argc, char **argv) {
                 else if (!strcmp(optarg, "tolerance")) gauss_mode = MMHIP_GAUSS_TOLERANCE;
                 else { fprintf(stderr, "Error: --gauss-mode takes exact or tolerance.\n"); return 1; }
                 break;
+            case OPT_INPUT_FRAMES: {
+                char *end = nullptr;
+                long n = strtol(optarg, &end, 10);
+                if (end == optarg || *end || n < 1 || n > 1000000) { fprintf(stderr, "Error: --input-frames takes a number of frames, at least 1.\n"); return 1; }
+                input_frames = (int)n;
+                break;
+            }
             default: usage(); return 1;
         }
     }
@@ -257,6 +291,10 @@ int main(int argc, char **argv) {
     }
     if (htmldoc) { fprintf(stderr, "Error: --htmldoc is not supported by the HIP command line.\n"); return 1; }
     if (generator) { fprintf(stderr, "Unknown generator `%s'\n", generator); return 1; }
+    // the file of frame `frame` of an image define: the name itself unless --input-frames makes it a pattern
+    auto is_pattern = [&](const Define &d) { return input_frames && frame_pattern(d.value) == 1; };
+    auto sequence_of = [&](const Define &d) { return is_pattern(d) ? input_frames : 1; };
+    auto file_of = [&](const Define &d, int frame) { return is_pattern(d) ? frame_file(d.value, frame) : d.value; };
 
     mmhip_options opts;
     mmhip_default_options(&opts);
@@ -278,6 +316,15 @@ int main(int argc, char **argv) {
         return nullptr;
     };
     int nuv = mmhip_filter_num_uservals(flt);
+    for (int i = 0; i < nuv && input_frames; ++i) {      // (the defines of image user values only: other values may hold a '%')
+        mmhip_userval_info info;
+        mmhip_filter_userval_info(flt, i, &info);
+        const Define *d = info.kind == MMHIP_UV_IMAGE ? lookup(info.name) : nullptr;
+        if (d && frame_pattern(d->value) < 0) {
+            fprintf(stderr, "Error: `%s': with --input-frames an image file name takes one conversion like %%d or %%04d.\n", d->value.c_str());
+            return 1;
+        }
+    }
     std::vector<unsigned char> pixels;
     if (!size_is_set)
         for (int i = 0; i < nuv; ++i) {
@@ -286,8 +333,8 @@ int main(int argc, char **argv) {
             if (info.kind != MMHIP_UV_IMAGE) continue;
             const Define *d = lookup(info.name);
             if (!d) { fprintf(stderr, "Error: No value defined for input image `%s'.\n", info.name); return 1; }
-            if (!read_png(d->value.c_str(), pixels, img_width, img_height)) {
-                fprintf(stderr, "Error: Could not read input image `%s'.\n", d->value.c_str());
+            if (!read_png(file_of(*d, 0).c_str(), pixels, img_width, img_height)) {
+                fprintf(stderr, "Error: Could not read input image `%s'.\n", file_of(*d, 0).c_str());
                 return 1;
             }
             size_is_set = 1;
@@ -310,12 +357,26 @@ int main(int argc, char **argv) {
             case MMHIP_UV_FLOAT: mmhip_set_float(inv, i, (float)strtod(d->value.c_str(), nullptr)); break;
             case MMHIP_UV_BOOL: mmhip_set_bool(inv, i, (int)(float)atoi(d->value.c_str())); break;
             case MMHIP_UV_IMAGE: {
-                int w, h;
-                if (!read_png(d->value.c_str(), pixels, w, h)) {
-                    fprintf(stderr, "Error: Could not read input image `%s'.\n", d->value.c_str());
-                    return 1;
+                // one file, or with --input-frames and a %d in the name one file per frame, all of one size
+                const int n = sequence_of(*d);
+                std::vector<unsigned char> frames;
+                int w = 0, h = 0;
+                for (int k = 0; k < n; ++k) {
+                    const std::string file = file_of(*d, k);
+                    int fw, fh;
+                    if (!read_png(file.c_str(), pixels, fw, fh)) {
+                        fprintf(stderr, "Error: Could not read input image `%s'.\n", file.c_str());
+                        return 1;
+                    }
+                    if (k > 0 && (fw != w || fh != h)) {
+                        fprintf(stderr, "Error: Input image `%s' is %dx%d, but frame 0 of `%s' is %dx%d: all frames of an input must have one size.\n",
+                                file.c_str(), fw, fh, info.name, w, h);
+                        return 1;
+                    }
+                    w = fw; h = fh;
+                    frames.insert(frames.end(), pixels.begin(), pixels.begin() + (size_t)w * h * 3);
                 }
-                if (mmhip_set_image_host(inv, i, pixels.data(), w, h, 3) != 0) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
+                if (mmhip_set_image_sequence_host(inv, i, frames.data(), w, h, 3, n) != 0) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
                 break;
             }
             default:

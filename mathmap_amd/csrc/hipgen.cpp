@@ -18,7 +18,7 @@
 //
 // Environment hooks for experiments (never needed for correct operation): MMHIP_UNROLL, MMHIP_TILE_W,
 // MMHIP_SINGLE_PIXEL, MMHIP_PAIR, MMHIP_PAIR_DEBUG, MMHIP_WAVES_PER_EU, MMHIP_NO_FETCHED_RESULT, MMHIP_NO_SAME_TAPS, MMHIP_NO_OUTSIDE_SHORTCUT, MMHIP_PAIR_MASKS, MMHIP_NT_STORE,
-// MMHIP_PAIR_EXIT, MMHIP_PAIR_EXIT_TAIL, MMHIP_MAX_CALL_DEPTH here; MMHIP_NO_CSE in passes.cpp; MMHIP_PPT, MMHIP_HIPRTC_FLAGS, MMHIP_NO_CACHE, MMHIP_CACHE_DIR,
+// MMHIP_PAIR_EXIT, MMHIP_PAIR_EXIT_TAIL, MMHIP_FRAME_HOT, MMHIP_MAX_CALL_DEPTH here; MMHIP_NO_CSE in passes.cpp; MMHIP_PPT, MMHIP_HIPRTC_FLAGS, MMHIP_NO_CACHE, MMHIP_CACHE_DIR,
 // MMHIP_SOURCE_OVERRIDE in runtime.cpp.
 //
 // Statement printing follows the reference's backends/cc.c:192-397 (one C variable
@@ -256,12 +256,16 @@ struct Generator {
                         return "MM_SQRT_LESS_POW2(" + prim(d->rhs.args[0], sl) + ", " + float_literal((float)(k * k)) + "f)";
                     }
                 }
+                if (sl == PIXEL && hot_mode && hot_frame_sites.count(stmt))      // frame number computed per pixel
+                    return std::string(stmt == fetched_result ? "mm_tuple_of_sums(mm_rs[mm_u] = mm_orig_val_sums_hotf(A, " : "mm_orig_val_hotf(A, ") +
+                           prim(r.args[0], sl) + ", " + prim(r.args[1], sl) + ", " + prim(r.args[2], sl) + ", " + prim(r.args[3], sl) + ", " +
+                           vname(r.args[2].value) + "_desc, mm_bad)" + (stmt == fetched_result ? ")" : "");
                 if (sl == PIXEL && hot_mode && stmt == fetched_result)
                     return "mm_tuple_of_sums(mm_rs[mm_u] = mm_orig_val_sums_hot(A, " + prim(r.args[0], sl) + ", " + prim(r.args[1], sl) + ", " +
-                           prim(r.args[2], sl) + ", " + vname(r.args[2].value) + "_desc, mm_bad))";
+                           prim(r.args[2], sl) + ", " + site_desc(stmt) + ", mm_bad))";
                 if (sl == PIXEL && hot_mode && hot_sites.count(stmt))
                     return "mm_orig_val_hot(A, " + prim(r.args[0], sl) + ", " + prim(r.args[1], sl) + ", " + prim(r.args[2], sl) +
-                           ", " + vname(r.args[2].value) + "_desc, mm_bad)";
+                           ", " + site_desc(stmt) + ", mm_bad)";
                 if (sl == PIXEL && !strcmp(cn, "ORIG_VAL") && r.args.size() == 4 && r.args[2].kind == Primary::Val &&
                     preloaded_desc.count(r.args[2].value))
                     return "mm_orig_val_d(A, " + prim(r.args[0], sl) + ", " + prim(r.args[1], sl) + ", " + prim(r.args[2], sl) +
@@ -380,6 +384,12 @@ struct Generator {
 
     std::set<const Value *> preloaded_desc;   // image values whose descriptor is loaded before the pixel loop
     std::set<const Stmt *> hot_sites;         // ORIG_VAL statements eligible for mm_orig_val_hot
+    std::set<const Stmt *> hot_frame_sites;   // ... for mm_orig_val_hotf: the frame number differs per pixel
+    std::map<const Stmt *, std::string> site_view;      // hot sites that read through a descriptor of their own
+    std::string site_desc(const Stmt *s) const {
+        auto it = site_view.find(s);
+        return it != site_view.end() ? it->second : vname(s->rhs.args[2].value) + "_desc";
+    }
     bool hot_mode = false;
     // The hot fetch whose four channels are the filter's result, unchanged (the last statement of every pure
     // distortion: `in(f(xy))`): the hot loop then keeps the fetch's rounded byte sums and stores them directly
@@ -396,29 +406,54 @@ struct Generator {
                 d->rhs.args[0].kind != Primary::Val || d->rhs.args[1].kind != Primary::IntConst || d->rhs.args[1].i != i)
                 return nullptr;
             const Stmt *f = d->rhs.args[0].value->def;
-            if (!f || f->parent || !hot_sites.count(f) || (fetch && f != fetch)) return nullptr;
+            if (!f || f->parent || !(hot_sites.count(f) || hot_frame_sites.count(f)) || (fetch && f != fetch)) return nullptr;
             fetch = f;
         }
         return fetch;
     }
 
-    // ORIG_VALs of the pixel slice whose image descriptor is preloaded and whose frame
-    // argument is a literal or a frame constant: their "bound drawable, valid frame" test can
-    // be made once per work-item.  Appends one condition per site.
-    void find_hot_fetches(const Block &b, std::vector<std::string> &conds) {
+    // ORIG_VAL statements of the pixel slice that read through a preloaded descriptor, in program order
+    void collect_fetch_sites(const Block &b, std::vector<const Stmt *> &sites) const {
         for (const Stmt *s : b) {
             if (!s->in_pixel) continue;
             if (s->kind == Stmt::Assign && s->rhs.kind == Rhs::Op && !strcmp(s->rhs.op->cname, "ORIG_VAL") &&
-                s->rhs.args.size() == 4 && s->rhs.args[2].kind == Primary::Val && preloaded_desc.count(s->rhs.args[2].value)) {
-                const Primary &f = s->rhs.args[3];
-                const bool frame_const = f.is_const() || (f.kind == Primary::Val && transfer_off.count(f.value));
-                if (frame_const) {
-                    hot_sites.insert(s);
-                    conds.push_back("mm_fetch_is_hot(" + vname(s->rhs.args[2].value) + "_desc, (int)(" + prim(f, PIXEL) + "))");
+                s->rhs.args.size() == 4 && s->rhs.args[2].kind == Primary::Val && preloaded_desc.count(s->rhs.args[2].value))
+                sites.push_back(s);
+            if (s->kind == Stmt::If) { collect_fetch_sites(s->then_, sites); collect_fetch_sites(s->else_, sites); }
+            if (s->kind == Stmt::While) collect_fetch_sites(s->body, sites);
+        }
+    }
+    // ORIG_VALs of the pixel slice whose image descriptor is preloaded: their "bound drawable" test can be made once
+    // per work-item.  Two kinds of site.  The frame argument is a literal or a frame constant (hot_sites): "valid frame"
+    // is tested there too, and the descriptor's hot pointer becomes that frame (mm_fetch_is_hot).  The sites of an image
+    // that do not all name the same frame (a temporal blend) get a descriptor each (views).  The frame argument is
+    // computed per pixel (hot_frame_sites, slit-scan): the fetch selects the frame itself, without a branch
+    // (mm_orig_val_hotf); MMHIP_FRAME_HOT=0 leaves such a site to the generic fetch, as before there were sequences.
+    // Appends one condition per site.
+    void find_hot_fetches(const Block &b, std::vector<std::string> &views, std::vector<std::string> &conds) {
+        std::vector<const Stmt *> sites;
+        collect_fetch_sites(b, sites);
+        auto frame_const = [&](const Primary &f) { return f.is_const() || (f.kind == Primary::Val && transfer_off.count(f.value)); };
+        std::map<const Value *, std::set<std::string>> frames_of;
+        for (const Stmt *s : sites)
+            if (frame_const(s->rhs.args[3])) frames_of[s->rhs.args[2].value].insert(prim(s->rhs.args[3], PIXEL));
+        const char *fh = getenv("MMHIP_FRAME_HOT");
+        const bool frame_hot = !fh || atoi(fh) != 0;
+        for (const Stmt *s : sites) {
+            const Primary &f = s->rhs.args[3];
+            const std::string desc = vname(s->rhs.args[2].value) + "_desc";
+            if (frame_const(f)) {
+                hot_sites.insert(s);
+                if (frames_of[s->rhs.args[2].value].size() > 1) {
+                    const std::string view = "mm_fv" + std::to_string(site_view.size());
+                    views.push_back("const mm_image_desc " + view + " = mm_frame_view(" + desc + ");");
+                    site_view[s] = view;
                 }
+                conds.push_back("mm_fetch_is_hot(" + site_desc(s) + ", (int)(" + prim(f, PIXEL) + "))");
+            } else if (frame_hot) {
+                hot_frame_sites.insert(s);
+                conds.push_back("mm_fetch_is_hot_any(" + desc + ")");
             }
-            if (s->kind == Stmt::If) { find_hot_fetches(s->then_, conds); find_hot_fetches(s->else_, conds); }
-            if (s->kind == Stmt::While) find_hot_fetches(s->body, conds);
         }
     }
 
@@ -1804,10 +1839,11 @@ MM_DEV int mm_s2v(int u) { int r; asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(__built
         // takes over from the same mm_p: for everything when the hot conditions do not hold, and for a
         // work-item that met an invalid coordinate (mm_bad), whose garbage the reference converts in a
         // way only the generic fetch imitates.
-        std::vector<std::string> hot_conds;
-        find_hot_fetches(code.body, hot_conds);
+        std::vector<std::string> hot_views, hot_conds;
+        find_hot_fetches(code.body, hot_views, hot_conds);
         out << "  int mm_p = 0;\n";
         if (ks.unroll > 1 && !hot_conds.empty()) {
+            for (const std::string &v : hot_views) out << "  " << v << "\n";
             out << "  bool mm_hot = true;\n";
             for (const std::string &c : hot_conds) out << "  mm_hot = mm_hot && " << c << ";\n";
             out << "  if (mm_hot) {\n";
@@ -1819,6 +1855,8 @@ MM_DEV int mm_s2v(int u) { int r; asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(__built
             out << "  }\n";
         } else {
             hot_sites.clear();
+            hot_frame_sites.clear();
+            site_view.clear();
         }
         emit_loop("  ", false);
         out << "}\n";

@@ -47,13 +47,19 @@ struct mm_image { int idx; int pw; int ph; float xf; float yf; int resized; };
 enum { MM_IMG_DRAWABLE = 0, MM_IMG_FLOATMAP = 1, MM_IMG_NULL = 2 };
 
 // One entry of the image table in HBM (input drawables and float maps).
-struct mm_image_desc {
-    const void *data;      // drawable: color_t[h][w] (0xRRGGBBAA); floatmap: float[h][w][4]
-    int w, h;
+struct mm_image_entry {
+    const void *data;      // drawable: color_t[num_frames][h][w] (0xRRGGBBAA), frames contiguous; floatmap: float[h][w][4]
+    int w, h;              // of one frame
     int kind;
-    int num_frames;
+    int num_frames;        // drawables: frames behind `data` (mathmap_cmdline.c:131-184 cache_entries[frame]); float maps: 1
     float scale_x, scale_y, middle_x, middle_y;   // userval.c:262-280
     float ax, bx, ay, by;                          // floatmap.c:30-46
+};
+// A table entry as a kernel holds it (in SGPRs), plus the frame its hot fetches read: `hot` is `data` advanced to the
+// frame that mm_fetch_is_hot accepted -- once per work-item, so a hot tap's address arithmetic does not know about
+// frames.  (mutable: the generated code declares its descriptors const.)  The generic fetch never reads it.
+struct mm_image_desc : mm_image_entry {
+    mutable const void *hot;
 };
 
 union mm_userval { int i; float f; color_t c; int image; };
@@ -75,7 +81,7 @@ struct mm_args {
     int floatmap;                     // 1: write float4 instead of bytes
     color_t edge_color_x, edge_color_y;
     const mm_userval *uservals;
-    const mm_image_desc *images;
+    const mm_image_entry *images;
     const void *curves;               // float[n][1024]
     const void *gradients;            // color_t[n][1024]
     void *out;
@@ -507,22 +513,42 @@ typedef const __attribute__((address_space(1))) float4 *mm_gmap;
 // Texel (cx, cy) of a hot image, in range.  mm_fetch_is_hot guarantees w, h < 2^24 and
 // 4*w*h < 2^32, so the byte offset is one 24-bit multiply-add in 32 bits and the load takes
 // the scalar base + 32-bit vector offset form (no 64-bit address arithmetic per tap).
-MM_DEV color_t mm_load_texel(const mm_image_desc &d, int cx, int cy) {
+// `base` is the first texel of the frame: the descriptor's `hot` pointer (scalar), or a lane's own frame (mm_frame_tap).
+typedef const __attribute__((address_space(1))) char *mm_gbytes;
+MM_DEV color_t mm_load_texel(const mm_image_desc &d, mm_gbytes base, int cx, int cy) {
     const unsigned boff = (__umul24((unsigned)cy, (unsigned)d.w) + (unsigned)cx) << 2;
-    return *(mm_gpix)((const __attribute__((address_space(1))) char *)d.data + boff);
+    return *(mm_gpix)(base + boff);
 }
 
+// The frame of a hot fetch whose frame number differs from pixel to pixel (slit-scan: in(xy, frame + 8 * x)): the
+// frame's first texel, and whether the number names no frame.  The address always lies inside the sequence (frame 0
+// for a number out of range) so that the taps load without a branch; `white` is selected afterwards, *before* the edge
+// colours, which keeps the reference's order (x outside, y outside, bad frame: mathmap_cmdline.c:131-184).
+// mm_fetch_is_hot_any guarantees 4*w*h < 2^32: the offset is one v_mad_u64_u32 on the scalar base, once per fetch.
+struct mm_frame_tap { mm_gbytes base; bool white; };
+MM_DEV mm_frame_tap mm_select_frame(const mm_image_desc &d, float f) {
+    const int frame = mm_f2i(f);
+    mm_frame_tap ft;
+    ft.white = (unsigned)frame >= (unsigned)d.num_frames;
+    const unsigned frame_bytes = (__umul24((unsigned)d.w, (unsigned)d.h)) << 2;
+    ft.base = (mm_gbytes)d.data + (unsigned long)(ft.white ? 0u : (unsigned)frame) * frame_bytes;
+    return ft;
+}
+MM_DEV mm_frame_tap mm_hot_frame(const mm_image_desc &d) { mm_frame_tap ft; ft.base = (mm_gbytes)d.hot; ft.white = false; return ft; }
+
 // get_pixel (mathmap_cmdline.c:131-184 / mathmap.c:1195-1209).
-// Hot variant: `d` is a bound drawable and `frame` is valid (both wave-uniform, tested once by
-// the caller).  Written without branches: the texel is always loaded from the clamped
+// Hot variant: `d` is a bound drawable (wave-uniform, tested once by the caller) and `ft` the frame to read: the
+// descriptor's own (valid, wave-uniform: ft.white is the constant false and folds away) or a lane's (mm_select_frame).
+// Written without branches: the texel is always loaded from the clamped
 // coordinates (in bounds for any bound image) and the edge colours are selected afterwards,
 // so the taps of a fetch -- and of the next unrolled pixel -- form one basic block and their
 // loads are in flight together.
-MM_DEV color_t mm_get_pixel(const mm_args &A, const mm_image_desc &d, int x, int y) {
+MM_DEV color_t mm_get_pixel(const mm_args &A, const mm_image_desc &d, const mm_frame_tap &ft, int x, int y) {
     mm_apply_edge_behaviour(x, y, d.w, d.h);
     const bool out_x = x < 0 || x >= d.w, out_y = y < 0 || y >= d.h;
     const int cx = x < 0 ? 0 : (x >= d.w ? d.w - 1 : x), cy = y < 0 ? 0 : (y >= d.h ? d.h - 1 : y);
-    color_t v = mm_load_texel(d, cx, cy);
+    color_t v = mm_load_texel(d, ft.base, cx, cy);
+    if (ft.white) v = MAKE_RGBA_COLOR(255, 255, 255, 255);
     if (out_y) v = A.edge_color_y;       // (measured: the four taps' selects are 8 % of Ident's kernel time)
     if (out_x) v = A.edge_color_x;
     return v;
@@ -536,17 +562,35 @@ MM_DEV color_t mm_get_pixel_cold(const mm_args &A, const mm_image_desc &d, int x
     mm_apply_edge_behaviour(x, y, d.w, d.h);
     if (x < 0 || x >= d.w) return A.edge_color_x;
     if (y < 0 || y >= d.h) return A.edge_color_y;
-    if (frame < 0 || frame >= d.num_frames) return MAKE_RGBA_COLOR(255, 255, 255, 255);
-    return ((mm_gpix)d.data)[(long)y * d.w + x];
+    // frame < 0 || frame >= num_frames in one compare (num_frames is never negative): the compare this saves pays for
+    // the add below, so that a single image's tap costs what it did before there were sequences
+    if ((unsigned)frame >= (unsigned)d.num_frames) return MAKE_RGBA_COLOR(255, 255, 255, 255);
+    // row `frame * h + y` of the sequence: the runtime binds no sequence of 2^31 rows or more (mmhip_set_image_sequence_*),
+    // so the frame is one 32-bit multiply (scalar where the number is frame-constant) and an add, and only where a texel
+    // is loaded.  DESIGN section 7 has what the 64-bit offset frame * w * h cost Droste instead.
+    // (the row number is not negative: converted as unsigned, it needs no sign extension)
+    return ((mm_gpix)d.data)[(long)(unsigned)(frame * d.h + y) * d.w + x];
 }
+// A bound drawable whose frames are small enough for mm_load_texel's 32-bit offsets: all a hot fetch with a per-pixel
+// frame number (mm_orig_val_hotf) needs to know once per work-item.
+MM_DEV bool mm_fetch_is_hot_any(const mm_image_desc &d) {
+    return d.kind == MM_IMG_DRAWABLE && d.w < (1 << 24) && d.h < (1 << 24) && (long)d.w * d.h < (1L << 30);
+}
+// ... and for a frame-constant frame number, that it names a frame: d.hot becomes that frame (64-bit, scalar, once
+// per work-item), which is all the hot taps see of it.
 MM_DEV bool mm_fetch_is_hot(const mm_image_desc &d, int frame) {
-    return d.kind == MM_IMG_DRAWABLE && frame >= 0 && frame < d.num_frames && d.w < (1 << 24) && d.h < (1 << 24) &&
-           (long)d.w * d.h < (1L << 30);
+    const bool hot = mm_fetch_is_hot_any(d) && frame >= 0 && frame < d.num_frames;
+    d.hot = (const color_t *)d.data + (hot ? (long)frame * ((long)d.w * d.h) : 0L);
+    return hot;
 }
+// The descriptor of one fetch site, where the sites of an image do not all read the same frame (a temporal blend):
+// each gets its own `hot` from its own mm_fetch_is_hot.
+MM_DEV mm_image_desc mm_frame_view(const mm_image_desc &d) { return d; }
 
-// HOT: the caller has established mm_fetch_is_hot(d, frame) for the whole launch.
+// HOT: the caller has established mm_fetch_is_hot(d, frame) (or mm_fetch_is_hot_any(d), `ft` from mm_select_frame)
+// for the whole launch.
 template <bool HOT>
-MM_DEV color_t mm_orig_val_pixel(const mm_args &A, const mm_image_desc &d, float x, float y, int frame) {
+MM_DEV color_t mm_orig_val_pixel(const mm_args &A, const mm_image_desc &d, const mm_frame_tap &ft, float x, float y, int frame) {
     x = (x + d.middle_x) * d.scale_x;
     y = -((y - d.middle_y) * d.scale_y);
 #if !MM_SUPERSAMPLING
@@ -557,7 +601,7 @@ MM_DEV color_t mm_orig_val_pixel(const mm_args &A, const mm_image_desc &d, float
     y = y + 0.5f;
 #endif
     // floor((double)x) of a float is the float floor: identical integer
-    if (HOT) return mm_get_pixel(A, d, mm_f2i(floorf(x)), mm_f2i(floorf(y)));
+    if (HOT) return mm_get_pixel(A, d, ft, mm_f2i(floorf(x)), mm_f2i(floorf(y)));
     return mm_get_pixel_cold(A, d, mm_f2i(floorf(x)), mm_f2i(floorf(y)), frame);
 }
 
@@ -594,11 +638,15 @@ MM_DEV mm_image_desc mm_load_desc(const mm_args &A, mm_image img) {
         d.w = d.h = 0;
         d.kind = MM_IMG_NULL;
         d.num_frames = 0;
+        d.hot = nullptr;
         d.scale_x = d.scale_y = d.middle_x = d.middle_y = 0.0f;
         d.ax = d.bx = d.ay = d.by = 0.0f;
         return d;
     }
-    return A.images[img.idx];
+    mm_image_desc d;
+    static_cast<mm_image_entry &>(d) = A.images[img.idx];
+    d.hot = d.data;
+    return d;
 }
 
 MM_DEV mm_tup<4> mm_intersample_tuple_cold(const mm_args &A, const mm_image_desc &d, float x, float y, int frame);
@@ -610,7 +658,7 @@ MM_DEV mm_tup<4> mm_orig_val_d(const mm_args &A, float x, float y, mm_image img,
 #if MM_INTERSAMPLE
     return mm_intersample_tuple_cold(A, d, x, y, mm_f2i(f));
 #else
-    return mm_tuple_from_color(mm_orig_val_pixel<false>(A, d, x, y, mm_f2i(f)));
+    return mm_tuple_from_color(mm_orig_val_pixel<false>(A, d, mm_frame_tap{}, x, y, mm_f2i(f)));
 #endif
 }
 // The fetch of the kernel's hot variant: the image is a bound drawable and the frame valid
@@ -635,10 +683,9 @@ MM_DEV bool mm_taps_all_inside(const mm_image_desc &d, int x1, int y1) {
     return (__builtin_amdgcn_ballot_w64((unsigned)x1 >= (unsigned)(d.w - 1)) |
             __builtin_amdgcn_ballot_w64((unsigned)y1 >= (unsigned)(d.h - 1))) == 0;
 }
-MM_DEV void mm_load_taps_inside(const mm_image_desc &d, int x1, int y1, color_t &p1, color_t &p2, color_t &p3, color_t &p4) {
+MM_DEV void mm_load_taps_inside(const mm_image_desc &d, mm_gbytes base, int x1, int y1, color_t &p1, color_t &p2, color_t &p3, color_t &p4) {
     typedef unsigned mm_u2 __attribute__((ext_vector_type(2)));
     typedef const __attribute__((address_space(1))) mm_u2 *mm_gpix2;
-    const __attribute__((address_space(1))) char *base = (const __attribute__((address_space(1))) char *)d.data;
     const unsigned boff = (__umul24((unsigned)y1, (unsigned)d.w) + (unsigned)x1) << 2;
     const mm_u2 top = *(mm_gpix2)(base + boff), bot = *(mm_gpix2)(base + (boff + ((unsigned)d.w << 2)));
     p1 = top.x; p3 = top.y; p2 = bot.x; p4 = bot.y;
@@ -659,7 +706,7 @@ MM_DEV void mm_bilinear_sums(color_t p1, color_t p2, color_t p3, color_t p4, flo
     ba = ba + mm_f2{(float)BLUE(p4), (float)ALPHA(p4)} * p4fact;
 }
 
-MM_DEV mm_bilinear mm_intersample_sums_hot(const mm_args &A, const mm_image_desc &d, float x, float y, bool &bad) {
+MM_DEV mm_bilinear mm_intersample_sums_hot(const mm_args &A, const mm_image_desc &d, const mm_frame_tap &ft, float x, float y, bool &bad) {
     x = (x + d.middle_x) * d.scale_x;
     y = -((y - d.middle_y) * d.scale_y);
     // A coordinate the reference's (int) conversion turns into INT_MIN (NaN, infinite, beyond +-2^31 px) raises
@@ -677,8 +724,8 @@ MM_DEV mm_bilinear mm_intersample_sums_hot(const mm_args &A, const mm_image_desc
     y = ok_y ? y : 0.0f;
     const int x1 = (int)(floor((double)(x / (float)MM_PIXEL_INC)) * (double)MM_PIXEL_INC), x2 = x1 + MM_PIXEL_INC;
     const int y1 = (int)(floor((double)(y / (float)MM_PIXEL_INC)) * (double)MM_PIXEL_INC), y2 = y1 + MM_PIXEL_INC;
-    const color_t p1 = mm_get_pixel(A, d, x1, y1), p2 = mm_get_pixel(A, d, x1, y2);
-    const color_t p3 = mm_get_pixel(A, d, x2, y1), p4 = mm_get_pixel(A, d, x2, y2);
+    const color_t p1 = mm_get_pixel(A, d, ft, x1, y1), p2 = mm_get_pixel(A, d, ft, x1, y2);
+    const color_t p3 = mm_get_pixel(A, d, ft, x2, y1), p4 = mm_get_pixel(A, d, ft, x2, y2);
     mm_f2 rg, ba;
     mm_bilinear_sums(p1, p2, p3, p4, (x - (float)x1) / (float)MM_PIXEL_INC, (y - (float)y1) / (float)MM_PIXEL_INC, rg, ba);
 #else
@@ -689,10 +736,12 @@ MM_DEV mm_bilinear mm_intersample_sums_hot(const mm_args &A, const mm_image_desc
     const int x1 = (int)floorf(x), x2 = x1 + 1;
     const int y1 = (int)floorf(y), y2 = y1 + 1;
     color_t p1, p2, p3, p4;
-    if (__builtin_expect(mm_taps_all_inside(d, x1, y1), 1)) mm_load_taps_inside(d, x1, y1, p1, p2, p3, p4);
-    else {
-        p1 = mm_get_pixel(A, d, x1, y1); p2 = mm_get_pixel(A, d, x1, y2);
-        p3 = mm_get_pixel(A, d, x2, y1); p4 = mm_get_pixel(A, d, x2, y2);
+    if (__builtin_expect(mm_taps_all_inside(d, x1, y1), 1)) {
+        mm_load_taps_inside(d, ft.base, x1, y1, p1, p2, p3, p4);
+        if (ft.white) p1 = p2 = p3 = p4 = MAKE_RGBA_COLOR(255, 255, 255, 255);     // (no tap is outside: nothing to override it)
+    } else {
+        p1 = mm_get_pixel(A, d, ft, x1, y1); p2 = mm_get_pixel(A, d, ft, x1, y2);
+        p3 = mm_get_pixel(A, d, ft, x2, y1); p4 = mm_get_pixel(A, d, ft, x2, y2);
     }
     mm_f2 rg, ba;
     mm_bilinear_sums(p1, p2, p3, p4, x - x1, y - y1, rg, ba);
@@ -767,8 +816,8 @@ MM_DEV mm_tup<4> mm_intersample_tuple_cold(const mm_args &A, const mm_image_desc
     return t;
 }
 
-MM_DEV mm_tup<4> mm_intersample_tuple_hot(const mm_args &A, const mm_image_desc &d, float x, float y, bool &bad) {
-    const mm_bilinear s = mm_intersample_sums_hot(A, d, x, y, bad);
+MM_DEV mm_tup<4> mm_intersample_tuple_hot(const mm_args &A, const mm_image_desc &d, const mm_frame_tap &ft, float x, float y, bool &bad) {
+    const mm_bilinear s = mm_intersample_sums_hot(A, d, ft, x, y, bad);
     const mm_f2 rg = mm_bytes_to_unit(s.rg), ba = mm_bytes_to_unit(s.ba);
     mm_tup<4> t;
     t.v[0] = rg.x; t.v[1] = rg.y; t.v[2] = ba.x; t.v[3] = ba.y;
@@ -780,7 +829,13 @@ MM_DEV mm_tup<4> mm_intersample_tuple_hot(const mm_args &A, const mm_image_desc 
 MM_DEV mm_bilinear mm_orig_val_sums_hot(const mm_args &A, float x, float y, mm_image img, const mm_image_desc &d, bool &bad) {
     x *= img.resized ? img.xf : 1.0f;
     y *= img.resized ? img.yf : 1.0f;
-    return mm_intersample_sums_hot(A, d, x, y, bad);
+    return mm_intersample_sums_hot(A, d, mm_hot_frame(d), x, y, bad);
+}
+// ... with a per-pixel frame number (mm_select_frame): the four taps share the frame
+MM_DEV mm_bilinear mm_orig_val_sums_hotf(const mm_args &A, float x, float y, mm_image img, float f, const mm_image_desc &d, bool &bad) {
+    x *= img.resized ? img.xf : 1.0f;
+    y *= img.resized ? img.yf : 1.0f;
+    return mm_intersample_sums_hot(A, d, mm_select_frame(d, f), x, y, bad);
 }
 MM_DEV mm_tup<4> mm_tuple_of_sums(const mm_bilinear &s) {
     const mm_f2 rg = mm_bytes_to_unit(s.rg), ba = mm_bytes_to_unit(s.ba);
@@ -793,9 +848,21 @@ MM_DEV mm_tup<4> mm_orig_val_hot(const mm_args &A, float x, float y, mm_image im
     x *= img.resized ? img.xf : 1.0f;
     y *= img.resized ? img.yf : 1.0f;
 #if MM_INTERSAMPLE
-    return mm_intersample_tuple_hot(A, d, x, y, bad);
+    return mm_intersample_tuple_hot(A, d, mm_hot_frame(d), x, y, bad);
 #else
-    return mm_tuple_from_color(mm_orig_val_pixel<true>(A, d, x, y, 0));
+    return mm_tuple_from_color(mm_orig_val_pixel<true>(A, d, mm_hot_frame(d), x, y, 0));
+#endif
+}
+// The hot fetch of a site whose frame number is computed per pixel: the caller has established mm_fetch_is_hot_any(d)
+// once per work-item; the frame test is a select (mm_select_frame), so the unrolled pixels' loads still overlap.
+MM_DEV mm_tup<4> mm_orig_val_hotf(const mm_args &A, float x, float y, mm_image img, float f, const mm_image_desc &d, bool &bad) {
+    x *= img.resized ? img.xf : 1.0f;
+    y *= img.resized ? img.yf : 1.0f;
+    const mm_frame_tap ft = mm_select_frame(d, f);
+#if MM_INTERSAMPLE
+    return mm_intersample_tuple_hot(A, d, ft, x, y, bad);
+#else
+    return mm_tuple_from_color(mm_orig_val_pixel<true>(A, d, ft, x, y, 0));
 #endif
 }
 MM_DEV mm_tup<4> mm_orig_val(const mm_args &A, float x, float y, mm_image img, float f) {

@@ -11,8 +11,8 @@ struct HImage { int idx; int pw; int ph; float xf; float yf; int resized; };
 
 enum { IMG_DRAWABLE = 0, IMG_FLOATMAP = 1, IMG_NULL = 2 };
 
-struct HImageDesc {
-    const void *data;
+struct HImageDesc {          // mm_image_entry
+    const void *data;        // drawable: num_frames frames of w x h packed texels, one after the other
     int w, h;
     int kind;
     int num_frames;
@@ -62,7 +62,7 @@ struct HNativeArg { int kind; int i; float f; HImage img; };
 struct HNativeRec { int executed; int index; int nargs; int pad; HNativeArg args[4]; };
 
 static_assert(sizeof(HImage) == 24, "mm_image layout");
-static_assert(sizeof(HImageDesc) == 56, "mm_image_desc layout");
+static_assert(sizeof(HImageDesc) == 56, "mm_image_entry layout");
 static_assert(sizeof(HNativeArg) == 36, "mm_narg_t layout");
 static_assert(sizeof(HArgs) == 168, "mm_args layout");
 

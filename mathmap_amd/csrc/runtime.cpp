@@ -454,12 +454,13 @@ int mmhip_set_by_name(mmhip_invocation *inv, const char *name, const char *value
     return fail(std::string("filter has no user value `") + name + "'");
 }
 
-static void fill_drawable_desc(HImageDesc &d, const void *data, int w, int h) {
+// `data` holds num_frames frames of w x h texels, one after the other; scale and middle are those of one frame
+static void fill_drawable_desc(HImageDesc &d, const void *data, int w, int h, int num_frames) {
     d.data = data;
     d.w = w;
     d.h = h;
     d.kind = IMG_DRAWABLE;
-    d.num_frames = 1;
+    d.num_frames = num_frames;
     d.scale_x = (float)((w - 1) / 2.0);    // userval.c:272-276
     d.scale_y = (float)((h - 1) / 2.0);
     d.middle_x = 1.0f;
@@ -487,13 +488,32 @@ static void input_changed(mmhip_invocation *inv) {
     ++inv->input_generation;
 }
 
-int mmhip_set_image_device(mmhip_invocation *inv, int index, const void *device_rgba32, int width, int height) {
+// Bytes of num_frames packed frames, or false where the count is not a size (a negative extent, overflow) or the
+// sequence has more rows than an int counts.
+static bool sequence_bytes(int width, int height, int num_frames, size_t &bytes) {
+    if (width < 0 || height < 0 || num_frames < 1) return false;
+    size_t texels = 0;
+    // (the generic fetch addresses row frame * height + y of the sequence in an int: mm_get_pixel_cold)
+    if ((uint64_t)height * (uint64_t)num_frames > (uint64_t)INT32_MAX) return false;
+    return !__builtin_mul_overflow((size_t)width, (size_t)height, &texels) && !__builtin_mul_overflow(texels, (size_t)num_frames, &texels) &&
+           !__builtin_mul_overflow(texels, (size_t)4, &bytes) && bytes <= (size_t)PTRDIFF_MAX;
+}
+
+int mmhip_set_image_sequence_device(mmhip_invocation *inv, int index, const void *device_rgba32, int width, int height, int num_frames) {
+    // (the arguments first: what is wrong with them does not depend on the invocation)
+    if (num_frames < 1) return fail("num_frames must be at least 1");
+    size_t bytes = 0;
+    if (!sequence_bytes(width, height, num_frames, bytes)) return fail("image sequence: the size overflows (fewer than 2^31 rows in all, and a byte count that fits)");
     const UservalInfo *u = uv_info(inv, index, UvKind::Image);
     if (!u) return -1;
     int slot = inv->image_slot_of_uv[index];
-    fill_drawable_desc(inv->images[slot], device_rgba32, width, height);
+    fill_drawable_desc(inv->images[slot], device_rgba32, width, height, num_frames);
     input_changed(inv);
     return 0;
+}
+
+int mmhip_set_image_device(mmhip_invocation *inv, int index, const void *device_rgba32, int width, int height) {
+    return mmhip_set_image_sequence_device(inv, index, device_rgba32, width, height, 1);
 }
 
 }  // extern "C"
@@ -509,19 +529,28 @@ void mmhip_unbind_image(mmhip_invocation *inv, const void *data) {
 
 extern "C" {
 
-int mmhip_set_image_host(mmhip_invocation *inv, int index, const uint8_t *pixels, int width, int height, int channels) {
+int mmhip_set_image_sequence_host(mmhip_invocation *inv, int index, const uint8_t *pixels, int width, int height, int channels,
+                                  int num_frames) {
     if (channels != 3 && channels != 4) return fail("channels must be 3 or 4");
+    if (num_frames < 1) return fail("num_frames must be at least 1");
+    size_t bytes = 0;
+    if (!sequence_bytes(width, height, num_frames, bytes)) return fail("image sequence: the size overflows (fewer than 2^31 rows in all, and a byte count that fits)");
     if (!uv_info(inv, index, UvKind::Image)) return -1;
-    size_t n = (size_t)width * height;
-    std::vector<uint32_t> packed(n);
-    for (size_t i = 0; i < n; ++i) {
-        const uint8_t *p = pixels + i * channels;
-        uint32_t a = channels == 4 ? p[3] : 255u;
-        packed[i] = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | a;
-    }
+    const size_t n = (size_t)width * height;
+    // one frame at a time through one staging buffer: the frames land one after the other
+    std::vector<uint32_t> packed;
+    try { packed.resize(n); } catch (const std::bad_alloc &) { return fail("image sequence: out of host memory"); }
     DeviceBuffer d;
-    HIP_TRY(d.grow(n * 4));
-    HIP_TRY(hipMemcpy(d.get(), packed.data(), n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(d.grow(bytes));
+    for (int k = 0; k < num_frames; ++k) {
+        const uint8_t *frame = pixels + (size_t)k * n * channels;
+        for (size_t i = 0; i < n; ++i) {
+            const uint8_t *p = frame + i * channels;
+            uint32_t a = channels == 4 ? p[3] : 255u;
+            packed[i] = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | a;
+        }
+        HIP_TRY(hipMemcpy((char *)d.get() + (size_t)k * n * 4, packed.data(), n * 4, hipMemcpyHostToDevice));
+    }
     // the upload this one replaces (if it was ours) is freed once nothing in flight reads it
     const void *old = inv->images[inv->image_slot_of_uv[index]].data;
     for (auto it = inv->owned.begin(); it != inv->owned.end(); ++it)
@@ -532,7 +561,11 @@ int mmhip_set_image_host(mmhip_invocation *inv, int index, const uint8_t *pixels
         }
     const void *dev = d.get();
     inv->owned.push_back(std::move(d));
-    return mmhip_set_image_device(inv, index, dev, width, height);
+    return mmhip_set_image_sequence_device(inv, index, dev, width, height, num_frames);
+}
+
+int mmhip_set_image_host(mmhip_invocation *inv, int index, const uint8_t *pixels, int width, int height, int channels) {
+    return mmhip_set_image_sequence_host(inv, index, pixels, width, height, channels, 1);
 }
 
 int mmhip_set_curve(mmhip_invocation *inv, int index, const float *values1024) {
