@@ -112,6 +112,22 @@ int mmhip_filter_launch_geometry(const mmhip_filter *f, int region_w, int num_ro
    own launch over a width x height frame (same fields) */
 int mmhip_filter_num_closures(const mmhip_filter *f);
 int mmhip_filter_closure_launch_geometry(const mmhip_filter *f, int closure, int width, int height, int64_t *out);
+/* The same 13 fields for one frame of a clip render of `frames` frames (mmhip_render_clip): the rows-per-item choice
+   is made from the workgroups of all frames together, so ppt grows with the clip's length; nwg and tiles_y are one
+   frame's.  frames = 1 gives mmhip_filter_launch_geometry's values.  No GPU needed. */
+int mmhip_filter_clip_launch_geometry(const mmhip_filter *f, int region_w, int num_rows, int frames, int64_t *out);
+/* How mmhip_render_clip cuts such a clip into launches: out[MMHIP_CLIP_PLAN_FIELDS] receives grid_x (gridDim.x: nwg
+   rounded up to a multiple of 8), frames_per_batch (gridDim.y of a full batch: at most 65 535, grid_x * frames * 256
+   below 2^31, and no more than the environment's MMHIP_CLIP_MAX_FRAMES, which is read once; 0 where the clip is
+   rendered frame by frame), batches (pixel launches of the call) and shared_slot (1: the frame constants do not read
+   t or frame, one prologue serves every frame).  No GPU needed. */
+enum { MMHIP_CLIP_PLAN_FIELDS = 4 };
+int mmhip_filter_clip_batch_plan(const mmhip_filter *f, int region_w, int num_rows, int frames, int64_t *out);
+/* The clip variant of the module -- kernels mm_prologue_clip, mm_rows_clip (filters with a per-row slice) and
+   mm_pixels_clip: the text of mmhip_filter_kernel_source with the kernels' heads replaced -- and its gfx950 compile
+   (like mmhip_filter_jit).  Built on the first clip render of the filter, cached on it and on disk. */
+const char *mmhip_filter_clip_kernel_source(mmhip_filter *f);
+long mmhip_filter_jit_clip(mmhip_filter *f, int load_module);
 /* hiprtc-compiles for gfx950 and (if a device is present) loads the module.
    load_module = 0 only compiles (usable without a GPU).  Returns code size. */
 long mmhip_filter_jit(mmhip_filter *f, int load_module);
@@ -171,6 +187,31 @@ int mmhip_set_sampling_offset(mmhip_invocation *inv, float offset_x, float offse
    Asynchronous. */
 int mmhip_render(mmhip_invocation *inv, int frame, float t, int region_x, int region_y, int region_w, int region_h,
                  int first_row, int last_row, void *out_device, int row_stride, int bpp, int floatmap, void *stream);
+/* Renders a clip (an extension): the rows [first_row, last_row) of the region for num_frames frames of an animation,
+   frame i at animation parameters frames[i] / ts[i] into out_device + i * frame_stride.  Everything else is
+   mmhip_render's; frame i receives exactly the bytes mmhip_render(inv, frames[i], ts[i], ...) writes.
+     - frames and ts are host arrays of num_frames entries; they are copied before the call returns.  Frame numbers
+       and t need be neither consecutive nor monotone.
+     - frame_stride (bytes) is at least one frame's band -- (rows - 1) * row_stride + region_w * bpp, for float maps
+       rows * 16 * render_width -- and otherwise free; bytes between the bands are not touched.
+     - One prologue launch, one launch of the per-row slice (filters that have one) and one pixel launch render a whole
+       batch of frames: at most 65 535 frames and 2^31 work-items per launch (mmhip_filter_clip_batch_plan), more frames
+       become several batches on the same stream.  A filter whose frame constants do not read t or frame evaluates
+       them once per call.
+     - Filters that call native filters (gaussian_blur, ...) or render closure images need the host between the
+       prologue and the pixels of every frame: for them the call is a loop of mmhip_render.  Nothing is refused;
+       mmhip_clip_batched_launches tells the two apart.
+     - Asynchronous like mmhip_render.  With mmhip_enable_timing, mmhip_drain_kernel_ms reports one entry per batch.
+     - Supersampling is not batched: use mmhip_render_supersampled per frame.
+   Errors: num_frames < 1; frames or ts NULL; a frame_stride smaller than the band; mmhip_render's own. */
+int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int region_x, int region_y,
+                      int region_w, int region_h, int first_row, int last_row, void *out_device, int row_stride,
+                      int64_t frame_stride, int bpp, int floatmap, void *stream);
+/* Batched pixel launches (mm_pixels_clip) of this invocation so far: one per batch of a clip render, none for a
+   filter mmhip_render_clip renders frame by frame.  mmhip_clip_prologue_frames: the frames whose frame constants the
+   clip prologue evaluated (one per call where they do not read t or frame). */
+long mmhip_clip_batched_launches(mmhip_invocation *inv);
+long mmhip_clip_prologue_frames(mmhip_invocation *inv);
 /* The CLI's -o: supersampled render of a region (two slices + 1-1-2-1-1 / 6 byte combine,
    call_invocation, mathmap_common.c:880-927).  Compile the filter with supersampling = 1. */
 int mmhip_render_supersampled(mmhip_invocation *inv, int frame, float t, int region_x, int region_y, int region_w,

@@ -45,6 +45,10 @@ SYMBOLS = {
     "mmhip_filter_gauss_mode": (C.c_int, [C.c_void_p]),
     "mmhip_filter_num_native_calls": (C.c_int, [C.c_void_p]),
     "mmhip_filter_launch_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "mmhip_filter_clip_launch_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "mmhip_filter_clip_batch_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "mmhip_filter_clip_kernel_source": (C.c_char_p, [C.c_void_p]),
+    "mmhip_filter_jit_clip": (C.c_long, [C.c_void_p, C.c_int]),
     "mmhip_filter_num_closures": (C.c_int, [C.c_void_p]),
     "mmhip_filter_closure_launch_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "mmhip_filter_jit": (C.c_long, [C.c_void_p, C.c_int]),
@@ -72,6 +76,10 @@ SYMBOLS = {
     "mmhip_set_sampling_offset": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
     "mmhip_render": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "mmhip_render_clip": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "mmhip_clip_batched_launches": (C.c_long, [C.c_void_p]),
+    "mmhip_clip_prologue_frames": (C.c_long, [C.c_void_p]),
     "mmhip_render_supersampled": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mmhip_render_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),

@@ -20,6 +20,8 @@ EDGE_COLOR, EDGE_WRAP, EDGE_REFLECT, EDGE_ROTATE = range(4)
 # mmhip_filter_launch_geometry's out[] (include/mmhip.h)
 GEOMETRY_FIELDS = ("tiles_x", "tiles_y", "wg1", "nwg", "ppt", "tile_w", "tile_h", "unroll", "pair_mode", "single_pixel",
                    "xcd_order", "tiles_magic", "xcd_full")
+# mmhip_filter_clip_batch_plan's out[]
+CLIP_PLAN_FIELDS = ("grid_x", "frames_per_batch", "batches", "shared_slot")
 
 
 class MathMapError(RuntimeError):
@@ -166,6 +168,34 @@ class Filter:
         if rc != 0:
             raise MathMapError(_err())
         return dict(zip(GEOMETRY_FIELDS, out))
+
+    def clip_launch_geometry(self, region_w, num_rows, frames):
+        """The geometry of one frame of a `frames`-frame clip render (render_clip): GEOMETRY_FIELDS, with the
+        rows per work-item chosen from the workgroups of all frames together; frames=1 is launch_geometry."""
+        out = (C.c_int64 * len(GEOMETRY_FIELDS))()
+        if lib().mmhip_filter_clip_launch_geometry(self._h, region_w, num_rows, frames, out) != 0:
+            raise MathMapError(_err())
+        return dict(zip(GEOMETRY_FIELDS, out))
+
+    def clip_batch_plan(self, region_w, num_rows, frames):
+        """How render_clip cuts a `frames`-frame clip into launches: a dict of the CLIP_PLAN_FIELDS
+        (frames_per_batch 0: the filter is rendered frame by frame)."""
+        out = (C.c_int64 * len(CLIP_PLAN_FIELDS))()
+        if lib().mmhip_filter_clip_batch_plan(self._h, region_w, num_rows, frames, out) != 0:
+            raise MathMapError(_err())
+        return dict(zip(CLIP_PLAN_FIELDS, out))
+
+    @property
+    def clip_kernel_source(self):
+        """The clip variant of kernel_source: kernels mm_prologue_clip, mm_rows_clip, mm_pixels_clip."""
+        return lib().mmhip_filter_clip_kernel_source(self._h).decode()
+
+    def jit_clip(self, load=False):
+        """hiprtc-compiles the clip variant for gfx950; returns the code-object size."""
+        n = lib().mmhip_filter_jit_clip(self._h, 1 if load else 0)
+        if n < 0:
+            raise MathMapError(_err())
+        return n
 
     @property
     def num_closures(self):
@@ -338,6 +368,65 @@ class Invocation:
             row_stride = rw * bpp
         self._check(lib().mmhip_render(self._h, frame, t, rx, ry, rw, rh, first_row, last_row, C.c_void_p(out_ptr),
                                        row_stride, bpp, 1 if floatmap else 0, C.c_void_p(stream)))
+
+    def render_clip(self, num_frames=None, frames=None, ts=None, out_ptr=None, rows=None, region=None, row_stride=None,
+                    frame_stride=None, bpp=4, floatmap=False, stream=0):
+        """Renders a clip in batched launches (mmhip_render_clip): frame i at frame number frames[i] and time ts[i].
+        `num_frames`=N alone is the CLI's animation: frame = i, t = (float)i / (float)N.  `rows` = (first_row,
+        last_row) and `region`, `row_stride`, `bpp`, `floatmap`, `stream` as in render_rows; frame i lands
+        `frame_stride` bytes (default: one frame's band) behind frame i - 1.  Without `out_ptr` returns the frames as a
+        uint8 [N,H,W,4] array; with it the call is asynchronous and the frames stay in HBM."""
+        from .striping import animation_frame_t
+        if frames is None and ts is None:
+            if num_frames is None:
+                raise MathMapError("render_clip: give num_frames, or frames and ts")
+            frames = list(range(num_frames))
+            ts = [animation_frame_t(i, num_frames) for i in frames]
+        elif frames is None or ts is None:
+            raise MathMapError("render_clip: frames and ts go together")
+        frames = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        ts = np.ascontiguousarray(ts, dtype=np.float32).reshape(-1)
+        if num_frames is None:
+            num_frames = len(frames)
+        if len(frames) != num_frames or len(ts) != num_frames:
+            raise MathMapError("render_clip: frames and ts must have num_frames = %d entries" % num_frames)
+        rx, ry, rw, rh = region if region is not None else (0, 0, self.render_width, self.render_height)
+        first_row, last_row = rows if rows is not None else (ry, ry + rh)
+        fp, tp = frames.ctypes.data_as(C.POINTER(C.c_int)), ts.ctypes.data_as(C.POINTER(C.c_float))
+        if out_ptr is not None:
+            if row_stride is None:
+                row_stride = rw * bpp
+            if frame_stride is None:
+                n_rows = max(min(last_row, ry + rh) - max(first_row, 0), 0)
+                frame_stride = n_rows * (16 * self.render_width if floatmap else row_stride)
+            self._check(lib().mmhip_render_clip(self._h, num_frames, fp, tp, rx, ry, rw, rh, first_row, last_row,
+                                                C.c_void_p(out_ptr), row_stride, frame_stride, bpp, 1 if floatmap else 0,
+                                                C.c_void_p(stream)))
+            return None
+        if rows is not None or region is not None or floatmap or bpp != 4 or row_stride is not None or frame_stride is not None:
+            raise MathMapError("render_clip without out_ptr returns whole RGBA frames: pass out_ptr for bands, regions and other formats")
+        out = np.empty((num_frames, self.render_height, self.render_width, 4), dtype=np.uint8)
+        if num_frames < 1:
+            raise MathMapError("render_clip: num_frames must be at least 1")
+        dev = lib().mmhip_device_alloc(out.nbytes)
+        if not dev:
+            raise MathMapError(_err())
+        try:
+            self._check(lib().mmhip_render_clip(self._h, num_frames, fp, tp, rx, ry, rw, rh, first_row, last_row,
+                                                C.c_void_p(dev), rw * 4, rw * 4 * rh, 4, 0, None))
+            self.sync()
+            self._check(lib().mmhip_copy_to_host(out.ctypes.data_as(C.c_void_p), C.c_void_p(dev), out.nbytes))
+        finally:
+            lib().mmhip_device_free(C.c_void_p(dev))
+        return out
+
+    def clip_batched_launches(self):
+        """Batched pixel launches of render_clip so far (0 for filters it renders frame by frame)."""
+        return lib().mmhip_clip_batched_launches(self._h)
+
+    def clip_prologue_frames(self):
+        """Frames whose frame constants render_clip's prologue evaluated (1 per call where they do not read t or frame)."""
+        return lib().mmhip_clip_prologue_frames(self._h)
 
     def render_supersampled(self, out_ptr, t=0.0, frame=0, bpp=4, stream=0):
         """The CLI's -o (supersampling) for the whole frame, into device memory at out_ptr."""

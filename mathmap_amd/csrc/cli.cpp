@@ -10,6 +10,7 @@
 #include <getopt.h>
 #include <zlib.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -54,6 +55,9 @@ void usage() {
            "                              NUM-1 are read from the files so named (all of\n"
            "                              one size) and in(xy, n) reads frame n; with -F,\n"
            "                              in(xy, frame) processes a clip frame by frame\n"
+           "      --batch-frames=NUM      with -F, render NUM frames per batched GPU\n"
+           "                              launch (default 1: frame by frame); the files\n"
+           "                              are the same\n"
            "\n"
            "Report bugs and suggestions to schani@complang.tuwien.ac.at\n",
            cache_size);
@@ -200,14 +204,14 @@ std::string frame_file(const std::string &pattern, int frame) {
 
 enum {
     OPT_VERSION = 256, OPT_HELP, OPT_HTMLDOC, OPT_BENCH_NO_OUTPUT, OPT_BENCH_ONLY_COMPILE,
-    OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE, OPT_INPUT_FRAMES
+    OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE, OPT_INPUT_FRAMES, OPT_BATCH_FRAMES
 };
 
 int main(int argc, char **argv) {
     std::string script;
     bool have_script = false, htmldoc = false, bench_no_output = false, bench_no_backend = false;
     int antialiasing = 0, supersampling = 0, img_width = 0, img_height = 0, size_is_set = 0;
-    int bench_render_count = 1, num_frames = 1, input_frames = 0, gauss_mode = MMHIP_GAUSS_EXACT;
+    int bench_render_count = 1, num_frames = 1, input_frames = 0, gauss_mode = MMHIP_GAUSS_EXACT, batch_frames = 1;
     const char *generator = nullptr;
     std::vector<Define> defines;
     static struct option long_options[] = {
@@ -221,7 +225,8 @@ int main(int argc, char **argv) {
         {"bench-no-backend", no_argument, 0, OPT_BENCH_NO_BACKEND},
         {"bench-render-count", required_argument, 0, OPT_BENCH_RENDER_COUNT},
         {"frames", required_argument, 0, 'F'}, {"gauss-mode", required_argument, 0, OPT_GAUSS_MODE},
-        {"input-frames", required_argument, 0, OPT_INPUT_FRAMES}, {0, 0, 0, 0}};
+        {"input-frames", required_argument, 0, OPT_INPUT_FRAMES}, {"batch-frames", required_argument, 0, OPT_BATCH_FRAMES},
+        {0, 0, 0, 0}};
     for (;;) {
         int idx;
         int option = getopt_long(argc, argv, "f:ioF:D:c:g:s:", long_options, &idx);
@@ -275,6 +280,13 @@ int main(int argc, char **argv) {
                 long n = strtol(optarg, &end, 10);
                 if (end == optarg || *end || n < 1 || n > 1000000) { fprintf(stderr, "Error: --input-frames takes a number of frames, at least 1.\n"); return 1; }
                 input_frames = (int)n;
+                break;
+            }
+            case OPT_BATCH_FRAMES: {
+                char *end = nullptr;
+                long n = strtol(optarg, &end, 10);
+                if (end == optarg || *end || n < 1 || n > 65535) { fprintf(stderr, "Error: --batch-frames takes a number of frames, 1 to 65535.\n"); return 1; }
+                batch_frames = (int)n;
                 break;
             }
             default: usage(); return 1;
@@ -386,10 +398,42 @@ int main(int argc, char **argv) {
     }
 
     std::vector<unsigned char> output((size_t)img_width * img_height * 4);
-    void *dev = mmhip_device_alloc(output.size());
+    auto write_frame = [&](int frame) {
+        char name[4096];
+        if (num_frames > 1 && strstr(output_filename, "%")) snprintf(name, sizeof name, output_filename, frame);
+        else snprintf(name, sizeof name, "%s", output_filename);
+        if (!write_png_rgb(name, output.data(), img_width, img_height)) {
+            fprintf(stderr, "Error: Cannot open file `%s' for writing: %s\n", name, strerror(errno));
+            return false;
+        }
+        return true;
+    };
+    // --batch-frames=K: K frames per clip render (one batched launch where the filter allows it), then the files one by
+    // one; a batch's frames stay under 1 GiB of device memory.  (Supersampled frames are rendered one at a time.)
+    if (supersampling) batch_frames = 1;
+    batch_frames = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch_frames, num_frames), ((size_t)1 << 30) / output.size()));
+    void *dev = mmhip_device_alloc(output.size() * batch_frames);
     if (!dev) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
     for (int render_num = 0; render_num < bench_render_count; ++render_num) {
-        for (int frame = 0; frame < num_frames; ++frame) {
+        for (int first = 0; batch_frames > 1 && first < num_frames; first += batch_frames) {
+            const int n = std::min(batch_frames, num_frames - first);
+            std::vector<int> frames(n);
+            std::vector<float> ts(n);
+            for (int i = 0; i < n; ++i) {
+                frames[i] = first + i;
+                ts[i] = (float)(first + i) / (float)num_frames;       // mathmap_cmdline.c:835
+            }
+            if (mmhip_render_clip(inv, n, frames.data(), ts.data(), 0, 0, img_width, img_height, 0, img_height, dev, img_width * 4,
+                                  (int64_t)output.size(), 4, 0, nullptr) != 0 || mmhip_sync(inv) != 0) {
+                fprintf(stderr, "Error: %s\n", mmhip_last_error());
+                return 1;
+            }
+            for (int i = 0; i < n && !bench_no_output; ++i) {
+                if (mmhip_copy_to_host(output.data(), (char *)dev + (size_t)i * output.size(), output.size()) != 0) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
+                if (!write_frame(first + i)) return 1;
+            }
+        }
+        for (int frame = 0; batch_frames == 1 && frame < num_frames; ++frame) {
             float t = (float)frame / (float)num_frames;       // mathmap_cmdline.c:835
             int rc = supersampling
                          ? mmhip_render_supersampled(inv, frame, t, 0, 0, img_width, img_height, dev, img_width * 4, 4, nullptr)
@@ -397,13 +441,7 @@ int main(int argc, char **argv) {
             if (rc != 0 || mmhip_sync(inv) != 0) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
             if (bench_no_output) continue;
             if (mmhip_copy_to_host(output.data(), dev, output.size()) != 0) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
-            char name[4096];
-            if (num_frames > 1 && strstr(output_filename, "%")) snprintf(name, sizeof name, output_filename, frame);
-            else snprintf(name, sizeof name, "%s", output_filename);
-            if (!write_png_rgb(name, output.data(), img_width, img_height)) {
-                fprintf(stderr, "Error: Cannot open file `%s' for writing: %s\n", name, strerror(errno));
-                return 1;
-            }
+            if (!write_frame(frame)) return 1;
         }
     }
     mmhip_device_free(dev);

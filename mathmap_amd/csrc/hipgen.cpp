@@ -1299,6 +1299,11 @@ struct Generator {
         emit_source();
     }
 
+    // The clip variant (mm_*_clip, one launch for many frames) is this same text with the kernels' heads replaced: the
+    // spans of `out` that differ are recorded while the text is emitted, so every body statement is emitted once, for both.
+    size_t mark() { return (size_t)out.tellp(); }
+    void clip_splice(size_t begin, const std::string &text) { ks.clip_splices.push_back({begin, mark(), text}); }
+
     std::vector<Value *> pro_defs, pix_defs;
     std::set<Value *> pro_uses, pix_uses;
 
@@ -1650,11 +1655,21 @@ MM_DEV int mm_s2v(int u) { int r; asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(__built
         ks.prologue_uses_time = hoisted_uses_time(code.body);
         ks.prologue_name = "mm_prologue";
         ks.pixel_name = "mm_pixels";
+        size_t head = mark();
         out << "extern \"C\" __global__ void __launch_bounds__(256) mm_prologue(mm_args A, char *XY) {\n";
         out << "  {\n    const int gid = blockIdx.x * 256 + threadIdx.x;\n"
                "    if (gid < A.region_width) A.xtab[gid] = CALC_VIRTUAL_X(gid + A.region_x, A.frame_render_width, A.sampling_offset_x);\n"
                "    if (gid < A.num_rows) A.ytab[gid] = CALC_VIRTUAL_Y(A.first_row + gid, A.frame_render_height, A.sampling_offset_y);\n"
-               "    if (gid != 0) return;\n  }\n  MM_INTERNALS\n";
+               "    if (gid != 0) return;\n  }\n";
+        // one grid row per frame of the batch; the coordinate tables depend on the geometry alone: the first row writes them
+        clip_splice(head, std::string(clip_prelude()) +
+               "extern \"C\" __global__ void __launch_bounds__(256) mm_prologue_clip(mm_args A, char *XY, const mm_clip C) {\n"
+               "  MM_CLIP_ENTRY\n"
+               "  {\n    const int gid = blockIdx.x * 256 + threadIdx.x;\n"
+               "    if (fi == 0 && gid < A.region_width) A.xtab[gid] = CALC_VIRTUAL_X(gid + A.region_x, A.frame_render_width, A.sampling_offset_x);\n"
+               "    if (fi == 0 && gid < A.num_rows) A.ytab[gid] = CALC_VIRTUAL_Y(A.first_row + gid, A.frame_render_height, A.sampling_offset_y);\n"
+               "    if (gid != 0) return;\n  }\n");
+        out << "  MM_INTERNALS\n";
         if (!(fn_root ? fn_root : &code)->functions.empty()) out << "  const int col = 0, rl = 0; unsigned mm_rand_ctr = 0; (void)col; (void)rl; (void)mm_rand_ctr;\n";
         decls(pro_defs, "  ", true);
         if (!ks.natives.empty()) {      // no call recorded yet this frame
@@ -1667,8 +1682,11 @@ MM_DEV int mm_s2v(int u) { int r; asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(__built
         out << "}\n\n";
         // ---- rows kernel: the per-row slice, one lane per row of the launch ----
         if (ks.row_values > 0) {
-            out << "extern \"C\" __global__ void __launch_bounds__(256) mm_rows(mm_args A, const char *__restrict__ XY) {\n"
-                   "  const int rl = blockIdx.x * 256 + threadIdx.x;\n"
+            head = mark();
+            out << "extern \"C\" __global__ void __launch_bounds__(256) mm_rows(mm_args A, const char *__restrict__ XY) {\n";
+            clip_splice(head, "extern \"C\" __global__ void __launch_bounds__(256) mm_rows_clip(mm_args A, const char *__restrict__ XY, const mm_clip C) {\n"
+                              "  MM_CLIP_ENTRY\n");
+            out << "  const int rl = blockIdx.x * 256 + threadIdx.x;\n"
                    "  if (rl >= A.num_rows) return;\n"
                    "  MM_INTERNALS\n"
                    "  const float y = A.ytab[rl];    // CALC_VIRTUAL_Y(first_row + rl, ...), by the prologue\n"
@@ -1691,14 +1709,22 @@ MM_DEV int mm_s2v(int u) { int r; asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(__built
         // ---- pixel kernel ----
         // experiment hook: ask the register allocator for a minimum occupancy (waves per SIMD)
         if (const char *e = getenv("MMHIP_WAVES_PER_EU")) out << "__attribute__((amdgpu_waves_per_eu(" << atoi(e) << "))) ";
-        out << R"(extern "C" __global__ void __launch_bounds__(256) mm_pixels(mm_args A, const char *__restrict__ XY) {
-  MM_INTERNALS
+        head = mark();
+        out << "extern \"C\" __global__ void __launch_bounds__(256) mm_pixels(mm_args A, const char *__restrict__ XY) {\n";
+        // (the grid's x extent is padded to a multiple of 8, so that a workgroup's XCD is bid & 7 in every frame)
+        clip_splice(head, "extern \"C\" __global__ void __launch_bounds__(256) mm_pixels_clip(mm_args A, const char *__restrict__ XY, const mm_clip C) {\n"
+                          "  if ((int)blockIdx.x >= C.nwg) return;      // padding workgroup\n"
+                          "  MM_CLIP_ENTRY\n");
+        out << R"(  MM_INTERNALS
   // XCD-aware tile order (MM_XCD_ORDER, above): workgroups are dealt round-robin to the 8 XCDs; give each
   // XCD one contiguous band of tiles so neighbouring gathers share its L2 -- or, for a kernel that reads nothing,
   // take the tiles in dispatch order so that cheap and expensive regions of the frame are spread over all XCDs.
   const int tiles_x = (A.region_width + MM_TILE_W - 1) / MM_TILE_W;
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
+)";
+        head = mark();
+        out << "  const int nwg = gridDim.x;\n";
+        clip_splice(head, "  const int nwg = C.nwg;      // the frame's workgroups (gridDim.x is padded)\n");
+        out << R"(  const int bid = blockIdx.x;
 #if MM_XCD_ORDER == 1
   const int xcd = bid & 7, q = bid >> 3;
   const int per = nwg >> 3, rem = nwg & 7;
@@ -1911,6 +1937,37 @@ MM_DEV int mm_s2v(int u) { int r; asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(__built
 };
 
 }  // namespace
+
+// What the clip kernels have besides mm_args: the batch's {t, frame} table and the distances between the frames' outputs,
+// frame-constant slots and row tables (0 where all frames share one: KernelSource::prologue_uses_time false).  The entry
+// block makes the by-value mm_args the frame's own -- fi is wave-uniform, so the table entry is a scalar load ahead of
+// every store -- and the unchanged body follows.
+const char *clip_prelude() {
+    return "struct mm_clip_frame { float t; int frame; };\n"
+           "struct mm_clip { const mm_clip_frame *frames; long long frame_stride; int xy_stride; int rowtab_stride; int nwg; int pad; };\n"
+           "#define MM_CLIP_ENTRY \\\n"
+           "  const int fi = blockIdx.y; \\\n"
+           "  { const mm_clip_frame mm_cf = C.frames[fi]; A.t = mm_cf.t; A.frame = mm_cf.frame; } \\\n"
+           "  A.out = (char *)A.out + (long long)fi * C.frame_stride; \\\n"
+           "  XY += (long long)fi * C.xy_stride; \\\n"
+           "  if (A.rowtab) A.rowtab += (long long)fi * C.rowtab_stride;\n";
+}
+
+void clip_kernel_source(const KernelSource &ks, std::string *source, std::string *key) {
+    source->clear();
+    size_t at = 0;
+    for (const KernelSource::Splice &sp : ks.clip_splices) {
+        source->append(ks.source, at, sp.begin - at);
+        source->append(sp.text);
+        at = sp.end;
+    }
+    source->append(ks.source, at, std::string::npos);
+    unsigned long long h = 1469598103934665603ull;      // FNV-1a, like the single-frame text's key
+    for (unsigned char c : *source) { h ^= c; h *= 1099511628211ull; }
+    char buf[32];
+    snprintf(buf, sizeof buf, "%016llx", h);
+    *key = buf;
+}
 
 KernelSource generate_hip(FilterCode &code, const KernelOptions &opt, FilterCode *functions_of) {
     Generator g(code, opt);

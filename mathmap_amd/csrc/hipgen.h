@@ -51,10 +51,17 @@ struct KernelSource {
     std::string rows_name;
     int direct_native = -1;       // index into natives: the pixel is that result sampled at (x, y) and nothing else
     std::string key;              // cache key (hash of source)
+    // The clip variant of the module (mm_prologue_clip, mm_rows_clip, mm_pixels_clip): `source` with these spans
+    // replaced, in order -- the kernels' heads; every body is the same text (clip_kernel_source)
+    struct Splice { size_t begin, end; std::string text; };
+    std::vector<Splice> clip_splices;
 };
 
 // `functions_of`: the code whose `functions` (filter_$name bodies) `code` may call; null = its own
 KernelSource generate_hip(FilterCode &code, const KernelOptions &opt, FilterCode *functions_of = nullptr);
+// the clip variant's text and its cache key, built from `ks.source` on demand
+void clip_kernel_source(const KernelSource &ks, std::string *source, std::string *key);
+const char *clip_prelude();
 const char *device_prelude();
 const char *device_noise_prelude();   // mm_noise_device.h
 const char *device_fastmath_prelude();   // mm_fastmath.h + tables

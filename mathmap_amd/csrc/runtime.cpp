@@ -192,6 +192,7 @@ void mmhip_filter_free(mmhip_filter *f) {
     for (auto &p : f->spec_cache) mmhip_filter_free(p.second);
     for (mmhip_closure_kernel &ck : f->closures) if (ck.mod) (void)hipModuleUnload(ck.mod);
     if (f->mod) (void)hipModuleUnload(f->mod);
+    if (f->clip_mod) (void)hipModuleUnload(f->clip_mod);
     delete f;
 }
 
@@ -314,6 +315,35 @@ long mmhip_filter_jit(mmhip_filter *f, int load_module) {
     }
     f->jit_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return (long)f->code_object.size();
+}
+
+// The clip variant's text (hipgen.cpp clip_kernel_source), made when it is first asked for.
+static const mm::KernelSource &clip_source(mmhip_filter *f) {
+    if (f->clip_ks.source.empty()) {
+        clip_kernel_source(f->ks, &f->clip_ks.source, &f->clip_ks.key);
+        f->clip_ks.prologue_name = "mm_prologue_clip";
+        f->clip_ks.rows_name = "mm_rows_clip";
+        f->clip_ks.pixel_name = "mm_pixels_clip";
+    }
+    return f->clip_ks;
+}
+
+const char *mmhip_filter_clip_kernel_source(mmhip_filter *f) { return clip_source(f).source.c_str(); }
+
+long mmhip_filter_jit_clip(mmhip_filter *f, int load_module) {
+    auto t0 = std::chrono::steady_clock::now();
+    const mm::KernelSource &ks = clip_source(f);
+    if (jit_source(ks, f->clip_code_object) != 0) return -1;
+    if (load_module && !f->clip_loaded) {
+        if (load_kernels(ks, f->clip_code_object, &f->clip_mod, &f->f_pix_clip, &f->f_pro_clip) != 0) return -1;
+        if (f->ks.row_values > 0) {
+            hipError_t e = hipModuleGetFunction(&f->f_rows_clip, f->clip_mod, ks.rows_name.c_str());
+            if (e != hipSuccess) return fail(std::string("hipModuleGetFunction(rows): ") + hipGetErrorString(e));
+        }
+        f->clip_loaded = true;
+    }
+    f->jit_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return (long)f->clip_code_object.size();
 }
 
 // ---------------------------------------------------------------------------
@@ -709,12 +739,14 @@ struct LaunchGeometry {
     uint32_t tiles_magic = 0;     // mm_args.tiles_magic
 };
 
+// rows per work-item for that many workgroups at one row each: enough workgroups must remain to fill 256 CUs several times over
+static int rows_per_item(long wgs) { return wgs >= 262144 ? 16 : wgs >= 131072 ? 8 : wgs >= 32768 ? 4 : wgs >= 8192 ? 2 : 1; }
+
 static LaunchGeometry launch_geometry(const KernelSource &ks, int region_w, int num_rows) {
     LaunchGeometry g;
     g.tiles_x = (region_w + ks.tile_w - 1) / ks.tile_w;
-    // rows per work-item: enough workgroups must remain to fill 256 CUs several times over
     g.wg1 = (long)g.tiles_x * ((num_rows + ks.tile_h - 1) / ks.tile_h);
-    int ppt = g.wg1 >= 262144 ? 16 : g.wg1 >= 131072 ? 8 : g.wg1 >= 32768 ? 4 : g.wg1 >= 8192 ? 2 : 1;
+    int ppt = rows_per_item(g.wg1);
     if (const char *e = getenv("MMHIP_PPT")) ppt = std::max(1, atoi(e));
     if (ks.single_pixel) ppt = 1;
     const int u = std::max(1, ks.unroll);          // the kernel steps MM_UNROLL rows at a time
@@ -725,9 +757,44 @@ static LaunchGeometry launch_geometry(const KernelSource &ks, int region_w, int 
     return g;
 }
 
-static int geometry_out(const KernelSource &ks, int region_w, int num_rows, int64_t *out) {
+// The geometry of one frame of a clip launch (mm_pixels_clip over `frames` frames at once): the rows-per-item choice is
+// made from the workgroups of the whole batch -- a 1920x1080 frame alone is too small to share a work-item's start-up
+// cost between rows, 120 of them are not -- but a work-item's rows stay rows of its own frame: no more of them than the
+// frame has tile rows (or than the frame alone would get).  With frames = 1 this is launch_geometry.
+static LaunchGeometry clip_launch_geometry(const KernelSource &ks, int region_w, int num_rows, int frames) {
+    LaunchGeometry g = launch_geometry(ks, region_w, num_rows);
+    const int tile_rows = (num_rows + ks.tile_h - 1) / ks.tile_h;
+    int ppt = std::min(rows_per_item(g.wg1 * std::max(frames, 1)), std::max(rows_per_item(g.wg1), tile_rows));
+    if (const char *e = getenv("MMHIP_PPT")) ppt = std::max(1, atoi(e));
+    if (ks.single_pixel) ppt = 1;
+    const int u = std::max(1, ks.unroll);
+    g.ppt = (ppt + u - 1) / u * u;
+    g.tiles_y = (num_rows + ks.tile_h * g.ppt - 1) / (ks.tile_h * g.ppt);
+    g.nwg = (long)g.tiles_x * g.tiles_y;
+    g.tiles_magic = tile_division_magic(g.tiles_x, g.nwg);
+    return g;
+}
+
+// How a clip of `frames` frames is cut into launches: gridDim.x is the frame's workgroups rounded up to a multiple of 8
+// (a workgroup's XCD is then blockIdx.x & 7 in every grid row), gridDim.y at most 65 535 frames, the grid below 2^31
+// work-items, and MMHIP_CLIP_MAX_FRAMES (read once) lowers the frames per launch.  max_frames 0: one frame alone is too
+// large for the grid, and the clip is rendered frame by frame.
+struct ClipPlan { long grid_x = 0; int max_frames = 0; };
+static ClipPlan clip_plan(const LaunchGeometry &g) {
+    static const int env_cap = [] {
+        const char *e = getenv("MMHIP_CLIP_MAX_FRAMES");
+        return e && atoi(e) > 0 ? atoi(e) : 65535;
+    }();
+    ClipPlan p;
+    p.grid_x = (g.nwg + 7) / 8 * 8;
+    const long by_items = ((1L << 23) - 1) / p.grid_x;      // grid_x * frames * 256 < 2^31
+    p.max_frames = (int)std::min<long>(std::min(65535, env_cap), by_items);
+    return p;
+}
+
+static int geometry_out(const KernelSource &ks, int region_w, int num_rows, int64_t *out, int clip_frames = 0) {
     if (region_w < 1 || num_rows < 1) return fail("launch geometry: empty region");
-    const LaunchGeometry g = launch_geometry(ks, region_w, num_rows);
+    const LaunchGeometry g = clip_frames > 0 ? clip_launch_geometry(ks, region_w, num_rows, clip_frames) : launch_geometry(ks, region_w, num_rows);
     // the kernel's XCD order 2 swizzles the first `full' workgroups: whole rounds of 8 runs of 2^m tiles (hipgen.cpp)
     int m = 0;
     for (unsigned v = (unsigned)(g.tiles_x > 1 ? g.tiles_x - 1 : 1); v; v >>= 1) ++m;
@@ -740,6 +807,22 @@ static int geometry_out(const KernelSource &ks, int region_w, int num_rows, int6
 
 int mmhip_filter_launch_geometry(const mmhip_filter *f, int region_w, int num_rows, int64_t *out) {
     return geometry_out(f->ks, region_w, num_rows, out);
+}
+
+int mmhip_filter_clip_launch_geometry(const mmhip_filter *f, int region_w, int num_rows, int frames, int64_t *out) {
+    if (frames < 1) return fail("clip launch geometry: num_frames must be at least 1");
+    return geometry_out(f->ks, region_w, num_rows, out, frames);
+}
+
+int mmhip_filter_clip_batch_plan(const mmhip_filter *f, int region_w, int num_rows, int frames, int64_t *out) {
+    if (frames < 1) return fail("clip batch plan: num_frames must be at least 1");
+    if (region_w < 1 || num_rows < 1) return fail("clip batch plan: empty region");
+    const bool batched = f->ks.natives.empty() && f->closures.empty();
+    const ClipPlan p = clip_plan(clip_launch_geometry(f->ks, region_w, num_rows, frames));
+    const int64_t per = batched ? p.max_frames : 0;
+    const int64_t v[MMHIP_CLIP_PLAN_FIELDS] = {p.grid_x, per, per ? (frames + per - 1) / per : 0, !f->ks.prologue_uses_time};
+    memcpy(out, v, sizeof v);
+    return 0;
 }
 
 int mmhip_filter_num_closures(const mmhip_filter *f) { return (int)f->closures.size(); }
@@ -1169,18 +1252,9 @@ static mmhip_filter *active_filter(mmhip_invocation *inv, int frame = 0, float t
     return sp ? sp : f;
 }
 
-int mmhip_render(mmhip_invocation *inv, int frame, float t, int region_x, int region_y, int region_w, int region_h,
-                 int first_row, int last_row, void *out_device, int row_stride, int bpp, int floatmap, void *stream) {
-    mmhip_filter *f = active_filter(inv, frame, t);
-    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
-    if (bpp < 1 || bpp > 4) return fail("output_bpp must be 1..4");
-    if (region_w <= 0 || region_h <= 0) return fail("empty region");
-    // new_template.c.in:238-239
-    if (first_row < 0) first_row = 0;
-    if (last_row > region_y + region_h) last_row = region_y + region_h;
-    if (last_row <= first_row) return 0;
-    if (upload_tables(inv, s) != 0) return -1;
-
+// mm_args of a render of rows [first_row, last_row) of a region, without the launch's own buffers and geometry
+static HArgs render_args(const mmhip_invocation *inv, int frame, float t, int region_x, int region_y, int region_w, int region_h,
+                         int first_row, int last_row, void *out_device, int row_stride, int bpp, int floatmap) {
     HArgs a{};
     a.img_width = inv->img_w;
     a.img_height = inv->img_h;
@@ -1211,6 +1285,22 @@ int mmhip_render(mmhip_invocation *inv, int frame, float t, int region_x, int re
     a.gradients = inv->d_gradients.get();
     a.out = out_device;
     a.native_slot_base = inv->native_slot_base;
+    return a;
+}
+
+int mmhip_render(mmhip_invocation *inv, int frame, float t, int region_x, int region_y, int region_w, int region_h,
+                 int first_row, int last_row, void *out_device, int row_stride, int bpp, int floatmap, void *stream) {
+    mmhip_filter *f = active_filter(inv, frame, t);
+    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
+    if (bpp < 1 || bpp > 4) return fail("output_bpp must be 1..4");
+    if (region_w <= 0 || region_h <= 0) return fail("empty region");
+    // new_template.c.in:238-239
+    if (first_row < 0) first_row = 0;
+    if (last_row > region_y + region_h) last_row = region_y + region_h;
+    if (last_row <= first_row) return 0;
+    if (upload_tables(inv, s) != 0) return -1;
+
+    HArgs a = render_args(inv, frame, t, region_x, region_y, region_w, region_h, first_row, last_row, out_device, row_stride, bpp, floatmap);
     const size_t rowtab_bytes = inv->launch.rowtab.bytes;
     if (grow_launch_buffers(inv->launch, f->ks, region_w, a.num_rows, f->ks.row_values > 0, s) != 0) return -1;
     if (inv->launch.rowtab.bytes != rowtab_bytes) inv->pro_filter = nullptr;     // the per-row table is new: fill it
@@ -1260,6 +1350,114 @@ int mmhip_render(mmhip_invocation *inv, int frame, float t, int region_x, int re
     if (inv->timing) {
         HIP_TRY(hipEventRecord(inv->ev1, s));
         inv->ev_valid = true;
+    }
+    return 0;
+}
+
+long mmhip_clip_batched_launches(mmhip_invocation *inv) { return inv->clip_batched_launches; }
+long mmhip_clip_prologue_frames(mmhip_invocation *inv) { return inv->clip_prologue_frames; }
+
+// mm_clip of the clip kernels (hipgen.cpp clip_prelude)
+struct HClipFrame { float t; int frame; };
+struct HClip { const HClipFrame *frames; long long frame_stride; int xy_stride; int rowtab_stride; int nwg; int pad; };
+static_assert(sizeof(HClip) == 32, "mm_clip layout");
+
+int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int region_x, int region_y,
+                      int region_w, int region_h, int first_row, int last_row, void *out_device, int row_stride,
+                      int64_t frame_stride, int bpp, int floatmap, void *stream) {
+    if (num_frames < 1) return fail("render_clip: num_frames must be at least 1");
+    if (!frames || !ts) return fail("render_clip: frames and ts must be arrays of num_frames entries");
+    if (bpp < 1 || bpp > 4) return fail("output_bpp must be 1..4");
+    if (region_w <= 0 || region_h <= 0) return fail("empty region");
+    if (first_row < 0) first_row = 0;
+    if (last_row > region_y + region_h) last_row = region_y + region_h;
+    if (last_row <= first_row) return 0;
+    const int num_rows = last_row - first_row;
+    // what one frame's band occupies: the next frame must begin behind it
+    const int64_t band = floatmap ? (int64_t)num_rows * 16 * inv->render_w
+                                  : (int64_t)(num_rows - 1) * row_stride + (int64_t)region_w * bpp;
+    if (frame_stride < band)
+        return fail("render_clip: frame_stride " + std::to_string(frame_stride) + " is smaller than one frame's band (" +
+                    std::to_string(band) + " bytes)");
+    mmhip_filter *f = active_filter(inv, frames[0], ts[0]);
+    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
+    const LaunchGeometry geo = clip_launch_geometry(f->ks, region_w, num_rows, num_frames);
+    const ClipPlan plan = clip_plan(geo);
+    if (!f->ks.natives.empty() || !f->closures.empty() || plan.max_frames < 1) {
+        // native filters run the host between prologue and pixels of every frame: frame by frame, the same result
+        for (int i = 0; i < num_frames; ++i)
+            if (mmhip_render(inv, frames[i], ts[i], region_x, region_y, region_w, region_h, first_row, last_row,
+                             (char *)out_device + (int64_t)i * frame_stride, row_stride, bpp, floatmap, stream) != 0)
+                return -1;
+        return 0;
+    }
+    if (mmhip_filter_jit_clip(f, 1) < 0) return -1;
+    if (upload_tables(inv, s) != 0) return -1;
+
+    HArgs a = render_args(inv, frames[0], ts[0], region_x, region_y, region_w, region_h, first_row, last_row, out_device, row_stride, bpp, floatmap);
+    const bool per_frame = f->ks.prologue_uses_time;      // else one frame-constant slot and one row table for all frames
+    const bool rows = f->ks.row_values > 0;
+    const int per_batch = std::min(num_frames, plan.max_frames);
+    const size_t xy_stride = ((size_t)std::max(f->ks.xy_bytes, 256) + 255) / 256 * 256;
+    const size_t rowtab_stride = (size_t)f->ks.row_values * num_rows;      // floats
+    const int slots = per_frame ? per_batch : 1;
+    if (rowtab_stride * slots > (size_t)INT32_MAX || xy_stride * slots > (size_t)INT32_MAX)
+        return fail("render_clip: the batch's row tables are too large; lower MMHIP_CLIP_MAX_FRAMES");
+    // the coordinate tables are the single-frame path's, rewritten here: its prologue must run again
+    if (grow_launch_buffers(inv->launch, f->ks, region_w, num_rows, false, s) != 0) return -1;
+    inv->pro_filter = nullptr;
+    auto wait = [s] { return hipStreamSynchronize(s); };
+    HIP_TRY(inv->clip.xy.grow(xy_stride * slots, wait, true));
+    if (rows) HIP_TRY(inv->clip.rowtab.grow(rowtab_stride * slots * sizeof(float), wait));
+    // the {t, frame} table of the whole call, copied now: the caller's arrays are free when this returns
+    ClipBuffers::Table &tab = inv->clip.table[inv->clip.next_table++ & 1];
+    if (tab.pending) HIP_TRY(hipEventSynchronize(tab.uploaded));
+    tab.pending = false;
+    const size_t tab_bytes = (size_t)num_frames * sizeof(HClipFrame);
+    HIP_TRY(tab.host.grow(tab_bytes));
+    HIP_TRY(tab.dev.grow(tab_bytes, wait));
+    if (!tab.uploaded) HIP_TRY(hipEventCreateWithFlags(&tab.uploaded, hipEventDisableTiming));
+    HClipFrame *hf = (HClipFrame *)tab.host.p;
+    for (int i = 0; i < num_frames; ++i) hf[i] = HClipFrame{ts[i], frames[i]};
+    HIP_TRY(hipMemcpyAsync(tab.dev.get(), hf, tab_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(tab.uploaded, s));
+    tab.pending = true;
+
+    a.xtab = inv->launch.xtab.get<float>();
+    a.ytab = inv->launch.ytab.get<float>();
+    if (rows) a.rowtab = inv->clip.rowtab.get<float>();
+    a.ppt = geo.ppt;
+    a.tiles_magic = geo.tiles_magic;
+    char *xy = inv->clip.xy.get<char>();
+    HClip c{};
+    c.frame_stride = frame_stride;
+    c.xy_stride = per_frame ? (int)xy_stride : 0;
+    c.rowtab_stride = per_frame ? (int)rowtab_stride : 0;
+    c.nwg = (int)geo.nwg;
+    void *params[] = {&a, &xy, &c};
+    const unsigned pro_x = (unsigned)((std::max(region_w, num_rows) + 255) / 256), rows_x = (unsigned)((num_rows + 255) / 256);
+    for (int b0 = 0; b0 < num_frames; b0 += per_batch) {
+        const int n = std::min(per_batch, num_frames - b0);
+        a.out = (char *)out_device + (int64_t)b0 * frame_stride;
+        c.frames = tab.dev.get<HClipFrame>() + b0;
+        // frame constants (and the per-row slice): one grid row per frame -- or, where they do not depend on t and frame,
+        // frame 0's once for the whole call
+        const unsigned pro_frames = per_frame ? (unsigned)n : b0 == 0 ? 1u : 0u;
+        if (pro_frames) {
+            HIP_TRY(hipModuleLaunchKernel(f->f_pro_clip, pro_x, pro_frames, 1, 256, 1, 1, 0, s, params, nullptr));
+            if (rows) HIP_TRY(hipModuleLaunchKernel(f->f_rows_clip, rows_x, pro_frames, 1, 256, 1, 1, 0, s, params, nullptr));
+            inv->clip_prologue_frames += pro_frames;
+        }
+        if (inv->timing) {
+            if (next_event_pair(inv) != 0) return -1;
+            HIP_TRY(hipEventRecord(inv->ev0, s));
+        }
+        HIP_TRY(hipModuleLaunchKernel(f->f_pix_clip, (unsigned)plan.grid_x, (unsigned)n, 1, 256, 1, 1, 0, s, params, nullptr));
+        ++inv->clip_batched_launches;
+        if (inv->timing) {
+            HIP_TRY(hipEventRecord(inv->ev1, s));
+            inv->ev_valid = true;
+        }
     }
     return 0;
 }

@@ -41,6 +41,12 @@ struct mmhip_filter {
     hipFunction_t f_rows = nullptr;           // the per-row slice's kernel (KernelSource::row_values > 0)
     bool loaded = false;
     double jit_seconds = 0;
+    // the clip variant of the module (mmhip_render_clip): text, code object and kernels, built on the first clip render
+    mm::KernelSource clip_ks;                 // source, key and kernel names only
+    std::vector<char> clip_code_object;
+    hipModule_t clip_mod = nullptr;
+    hipFunction_t f_pro_clip = nullptr, f_rows_clip = nullptr, f_pix_clip = nullptr;
+    bool clip_loaded = false;
     // user-value specialisation (specialize.cpp): kernels with the scalar user values baked in,
     // keyed by the value bytes; owned by this filter
     std::string source;
@@ -90,6 +96,41 @@ struct DeviceBuffer {
 // What a launch's kernels keep besides the tables and the output: frame constants, per-column / per-row coordinates,
 // per-row values (mm_rows: [value][row]).
 struct LaunchBuffers { DeviceBuffer xy, xtab, ytab, rowtab; };
+
+// Host memory the device reads directly (page-locked), freed by its owner.
+struct PinnedBuffer {
+    void *p = nullptr;
+    size_t bytes = 0;
+    PinnedBuffer() = default;
+    PinnedBuffer(const PinnedBuffer &) = delete;
+    PinnedBuffer &operator=(const PinnedBuffer &) = delete;
+    ~PinnedBuffer() { if (p) (void)hipHostFree(p); }
+    hipError_t grow(size_t need) {
+        if (need <= bytes) return hipSuccess;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+        const hipError_t e = hipHostMalloc(&p, need, hipHostMallocDefault);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        bytes = need;
+        return hipSuccess;
+    }
+};
+
+// What the batches of a clip render keep (mmhip_render_clip): one frame-constant slot and one row table per frame of a
+// batch (a single one of each where the prologue does not read t or frame), and the {t, frame} table of the call.  The
+// table goes up from page-locked memory; two of them alternate, so that a call need not wait for the one before it.
+struct ClipBuffers {
+    DeviceBuffer xy, rowtab;
+    struct Table {
+        PinnedBuffer host;
+        DeviceBuffer dev;
+        hipEvent_t uploaded = nullptr;      // recorded behind the table's copy: the host side may be rewritten after it
+        bool pending = false;
+        ~Table() { if (uploaded) (void)hipEventDestroy(uploaded); }
+    } table[2];
+    unsigned next_table = 0;
+};
 
 // Native call entry k (KernelSource::natives[k]): its float4 map and what is remembered about it.
 struct NativeEntry {
@@ -154,6 +195,9 @@ struct mmhip_invocation {
     unsigned long long pro_generation = 0, table_generation = 1;
     unsigned long long input_generation = 1;
     LaunchBuffers launch;                  // of the main kernels (mmhip_render)
+    ClipBuffers clip;                      // of the clip kernels (mmhip_render_clip)
+    long clip_batched_launches = 0;        // mmhip_clip_batched_launches
+    long clip_prologue_frames = 0;         // mmhip_clip_prologue_frames
     uint32_t edge_color_x = 0, edge_color_y = 0;
     float sampling_offset_x = 0.f, sampling_offset_y = 0.f;
     bool timing = false;
