@@ -1,0 +1,660 @@
+// Pair mode of the HIP generator: two pixels of a work-item evaluated in lockstep as 2-vectors.
+//
+// For a pixel body that is nothing but int/float arithmetic, comparisons and structured control
+// flow (Mandelbrot and its relatives), the two pixels a work-item renders per loop step are
+// evaluated together: every SSA value is a 2-vector (x component: the first pixel), `if`s are
+// if-converted (both sides evaluated -- the slice is pure -- and the exit phis select), a `while`
+// runs while either pixel is active with the loop phis frozen per pixel by a select (with lane masks: only
+// at the back edges at which a lane leaves, see exit_driven_iteration).  Each component
+// sees exactly the scalar kernel's operations in the scalar kernel's order.  What it buys: a gfx950
+// SIMD hands a wave an issue slot every ~4 cycles, in which the wave can issue two independent vector
+// instructions (2 cycles each) -- a single pixel's dependent chain uses half of that, whatever the
+// occupancy (tools/pk_rate.hip: dependent v_mul/v_add 4.25 cycles per instruction at 8 waves per SIMD,
+// two independent chains 2.4).  The pair's components are kept as separate scalars, so the
+// instruction stream alternates between the two pixels; as v_pk_*_f32 (MM_PAIR_SCALAR=0) the same
+// work issues in one 4-cycle instruction and gains much less (Mandelbrot 8192^2: 0.372 ms one pixel
+// at a time, 0.360 packed, 0.313 interleaved).
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <set>
+
+#include "hipgen_internal.h"
+
+namespace mm {
+namespace hipgen {
+namespace {
+
+struct PairGen final : PairMode {
+    PairEnv env;
+    std::ostream &out;
+    FilterCode &code;
+    std::set<const Value *> defs;      // values defined in the pixel slice (vectors in pair mode)
+    // Int values that only ever hold a truth value (results of comparisons, NOT, the literals 0 / 1 and
+    // phis / copies of such): kept as a pair of bools (mm_bb), which the compiler keeps in scalar lane masks
+    // where their logic is scalar arithmetic -- as ints they would cost two vector instructions per operation.
+    std::set<const Value *> bools;
+    std::set<const Value *> uniform;   // wave-uniform values of the loops being printed (mark_uniform)
+    int ids = 0;                       // names of masks: mm_c<id>, mm_a<id>, mm_l<id>
+    // exit-driven loops (exit_driven_iteration): they need lane masks; MMHIP_PAIR_EXIT=0 keeps the per-iteration selects
+    const bool exit = env.knobs.pair_exit.value_or(1) && env.knobs.pair_masks.value_or(1);
+    const Stmt *split_def = nullptr;   // the uniform conjunct's defining statement, while its loop body is printed
+    bool split_leave = false;          // the value with which it ends the loop
+
+    explicit PairGen(const PairEnv &e) : env(e), out(e.out), code(e.code) {}
+
+    bool is_uniform(const Value *v) const override { return uniform.count(v) > 0; }
+
+    // ---- which bodies are covered ----
+    static bool scalar_ty(Ty t) { return t == Ty::Int || t == Ty::Float; }
+    static bool prim_ok(const Primary &p) {
+        if (p.kind == Primary::IntConst || p.kind == Primary::FloatConst) return true;
+        return p.kind == Primary::Val && scalar_ty(p.value->var->type);
+    }
+    static bool rhs_ok(const Rhs &r) {
+        if (r.kind == Rhs::Prim) return prim_ok(r.prim);
+        if (r.kind == Rhs::Internal) return r.internal == "x" || r.internal == "y";
+        if (r.kind != Rhs::Op) return false;
+        static const char *ok[] = {"ADD", "SUB", "MUL", "NEG", "DIV", "LESS", "LEQ", "EQ", "NOT", "sqrt"};
+        bool found = false;
+        for (const char *o : ok) found = found || !strcmp(r.op->cname, o);
+        if (!found) return false;
+        for (const Primary &a : r.args) if (!prim_ok(a)) return false;
+        if (!strcmp(r.op->cname, "sqrt") && r.args[0].type() != Ty::Float) return false;
+        if (!strcmp(r.op->cname, "NOT") && r.args[0].type() != Ty::Int) return false;
+        return true;
+    }
+    bool block_ok(const Block &b) const {
+        for (const Stmt *s : b) {
+            if (!s->in_pixel) continue;
+            switch (s->kind) {
+                case Stmt::Assign:
+                    if (!s->lhs || !scalar_ty(s->lhs->var->type) || !rhs_ok(s->rhs)) {
+                        if (env.knobs.pair_debug)
+                            fprintf(stderr, "pair mode: statement not covered (%s)\n",
+                                    s->rhs.kind == Rhs::Op ? s->rhs.op->cname : s->rhs.kind == Rhs::Internal ? s->rhs.internal.c_str() : "rhs kind");
+                        return false;
+                    }
+                    break;
+                case Stmt::If:
+                case Stmt::While:
+                    if (s->cond.kind != Rhs::Prim || !prim_ok(s->cond.prim) || s->cond.prim.type() != Ty::Int) return false;
+                    for (const Stmt *ph : s->phis) {
+                        if (!ph->in_pixel) continue;
+                        if (!scalar_ty(ph->lhs->var->type) || ph->rhs.kind != Rhs::Prim || ph->rhs2.kind != Rhs::Prim ||
+                            !prim_ok(ph->rhs.prim) || !prim_ok(ph->rhs2.prim))
+                            return false;
+                    }
+                    if (s->kind == Stmt::If ? !(block_ok(s->then_) && block_ok(s->else_)) : !block_ok(s->body)) return false;
+                    break;
+                default: break;
+            }
+        }
+        return true;
+    }
+    bool eligible() const {
+        if (!env.opt.fast_math_exact) return false;
+        const bool force = env.knobs.pair.has_value();          // 0: never, 1: whenever the body is covered, unset: small bodies
+        if (force && !*env.knobs.pair) return false;
+        const int stmts = env.pixel_stmts;
+        // measured at 8192^2: Mandelbrot with its parameters baked in (24 statements) 0.372 -> 0.355 ms, the generic
+        // quaternion form (57 statements, four loop-carried components to keep per pixel) 0.75 -> 0.86 ms
+        if (env.pixel_fetches || stmts < 4 || stmts > (force ? 400 : 40)) return false;
+        const bool dbg = env.knobs.pair_debug;
+        for (int i = 0; i < 4; ++i)
+            if (!code.result[i] || !scalar_ty(code.result[i]->var->type)) {
+                if (dbg) fprintf(stderr, "pair mode: result %d is not an int / float value\n", i);
+                return false;
+            }
+        const bool ok = block_ok(code.body);
+        if (dbg) fprintf(stderr, "pair mode: body %s (%d statements)\n", ok ? "covered" : "not covered", stmts);
+        return ok;
+    }
+
+    // ---- truth values ----
+    // does `d` define a truth value, given that its operands do where `operand` says so?
+    template <class P> static bool truth_def(const Stmt *d, P operand) {
+        if (d->kind == Stmt::Phi) return d->rhs.kind == Rhs::Prim && d->rhs2.kind == Rhs::Prim && operand(d->rhs.prim) && operand(d->rhs2.prim);
+        if (d->kind != Stmt::Assign) return false;
+        if (d->rhs.kind == Rhs::Prim) return operand(d->rhs.prim);
+        return d->rhs.kind == Rhs::Op && is_truth_op(d->rhs.op->cname);
+    }
+    // a frame constant (scalar, defined in the hoisted slice) that holds a truth value
+    static bool const_is_bool(const Value *v, int depth) {
+        if (!v || depth > 12 || v->var->type != Ty::Int) return false;
+        if (v->index < 0) return true;                      // uninitialised: reads as 0
+        return v->def && truth_def(v->def, [&](const Primary &p) {
+            return p.kind == Primary::IntConst ? p.i == 0 || p.i == 1 : p.kind == Primary::Val && const_is_bool(p.value, depth + 1);
+        });
+    }
+    bool prim_bool(const Primary &p) const {
+        if (p.kind == Primary::IntConst) return p.i == 0 || p.i == 1;
+        if (p.kind != Primary::Val) return false;
+        if (p.value->index < 0) return p.value->var->type == Ty::Int;
+        if (bools.count(p.value)) return true;
+        return !defs.count(p.value) && const_is_bool(p.value, 0);
+    }
+    void infer_bools() {
+        std::vector<const Stmt *> idefs;      // the statements (assignments and phis) that define the slice's int values
+        for (Value *v : env.pix_defs) {
+            defs.insert(v);
+            if (v->var->type == Ty::Int && v->def && v->def->lhs == v) idefs.push_back(v->def);
+        }
+        for (const Stmt *d : idefs) bools.insert(d->lhs);            // optimistic, then remove until stable
+        for (bool changed = true; changed;) {
+            changed = false;
+            for (const Stmt *d : idefs)
+                if (bools.count(d->lhs) && !truth_def(d, [&](const Primary &p) { return prim_bool(p); })) { bools.erase(d->lhs); changed = true; }
+        }
+    }
+    // values read outside the body of loop `w` (statements of other blocks, other loops' phis, the results):
+    // only those of w's phis, and its condition, have to keep their value once a pixel has left the loop
+    void uses_outside(const Block &b, const Stmt *skip, std::set<const Value *> &uses) const {
+        auto use = [&](const Primary &p) { if (p.kind == Primary::Val) uses.insert(p.value); };
+        auto use_rhs = [&](const Rhs &r) { if (r.kind == Rhs::Prim) use(r.prim); for (const Primary &a : r.args) use(a); };
+        for (const Stmt *s : b) {
+            if (!s->in_pixel) continue;
+            if (s->kind == Stmt::Assign) use_rhs(s->rhs);
+            if (s->kind == Stmt::If) {
+                use_rhs(s->cond);
+                uses_outside(s->then_, skip, uses);
+                uses_outside(s->else_, skip, uses);
+                for (const Stmt *ph : s->phis) if (ph->in_pixel) { use_rhs(ph->rhs); use_rhs(ph->rhs2); }
+            }
+            if (s->kind == Stmt::While) {
+                for (const Stmt *ph : s->phis) if (ph->in_pixel) { use_rhs(ph->rhs); if (s != skip) use_rhs(ph->rhs2); }
+                if (s != skip) { use_rhs(s->cond); uses_outside(s->body, skip, uses); }
+            }
+        }
+    }
+
+    // ---- expressions ----
+    // operand as a 2-vector of the wanted type (mm_vf / mm_vi broadcast scalars and convert int -> float)
+    std::string pbool(const Primary &p) {        // operand as mm_bb
+        const std::string bu = exit ? "mm_xbu(" : "mm_bu(";      // (exit-driven loops: no exec in the broadcast either)
+        if (p.kind == Primary::IntConst) return bu + (p.i ? "true)" : "false)");
+        if (p.kind == Primary::Val && p.value->index < 0) return bu + "false)";
+        // (a uniform value that is not a literal goes through the ballot of mm_bu: a select between 64-bit constants on a
+        // uniform bool is a v_cndmask_b32 pair to this compiler, and the mask would sit in vector registers)
+        if (uniform.count(p.value)) return "mm_bu((bool)u" + vname(p.value) + ")";
+        if (bools.count(p.value)) return vname(p.value);
+        return "mm_tob(" + pprim(p, Ty::Int) + ")";
+    }
+    std::string pprim(const Primary &p, Ty want) {
+        const char *w = want == Ty::Float ? "mm_vf(" : "mm_vi(";
+        if (p.kind == Primary::IntConst) return std::string(w) + std::to_string(p.i) + ")";
+        if (p.kind == Primary::FloatConst) return std::string(w) + float_literal(p.f) + "f)";
+        if (p.value->index < 0) return std::string(w) + "0)";
+        if (uniform.count(p.value))
+            return std::string(w) + (p.value->var->type == Ty::Float ? "(float)u" : "(int)u") + vname(p.value) + ")";
+        return std::string(w) + vname(p.value) + ")";
+    }
+    static Ty arith_ty(const Rhs &r) {
+        for (const Primary &a : r.args) if (a.type() == Ty::Float) return Ty::Float;
+        return Ty::Int;
+    }
+    std::string prhs(const Rhs &r, const Value *lhs) {
+        const Ty lhs_ty = lhs->var->type;
+        const bool as_bool = bools.count(lhs) > 0;
+        if (r.kind == Rhs::Prim) return as_bool ? pbool(r.prim) : pprim(r.prim, lhs_ty);
+        if (r.kind == Rhs::Internal) return r.internal == "x" ? "mm_vf(x)" : "mm_y2";
+        const char *cn = r.op->cname;
+        const Ty t = arith_ty(r);
+        const char *op = !strcmp(cn, "ADD") ? "+" : !strcmp(cn, "SUB") ? "-" : !strcmp(cn, "MUL") ? "*" : !strcmp(cn, "LESS") ? "<"
+                         : !strcmp(cn, "LEQ") ? "<=" : !strcmp(cn, "EQ") ? "==" : nullptr;
+        const bool compares = op && (op[0] == '<' || op[0] == '=');
+        // An int value next to a float literal: the scalar kernel's literal is a double (cc.c prints them so),
+        // C computes (double)i op literal and the assignment rounds once -- (float)i first would round twice
+        // for |i| >= 2^24.  Same arithmetic here, per component.
+        if (op && r.args.size() == 2 && ((r.args[0].type() == Ty::Int && r.args[1].kind == Primary::FloatConst) ||
+                                         (r.args[1].type() == Ty::Int && r.args[0].kind == Primary::FloatConst))) {
+            auto comp = [&](const Primary &p, const char *c) {
+                if (p.kind == Primary::FloatConst) return "(double)" + float_literal(p.f) + "f";
+                return "(double)" + pprim(p, Ty::Int) + "." + c;
+            };
+            const std::string ex = comp(r.args[0], "x") + " " + op + " " + comp(r.args[1], "x");
+            const std::string ey = comp(r.args[0], "y") + " " + op + " " + comp(r.args[1], "y");
+            if (compares) {
+                const std::string b = "mm_bl(" + ex + ", " + ey + ")";
+                return as_bool ? b : "mm_vi(" + b + ")";
+            }
+            return "mm_pf{(float)(" + ex + "), (float)(" + ey + ")}";
+        }
+        if (op && !compares) return "(" + pprim(r.args[0], t) + " " + op + " " + pprim(r.args[1], t) + ")";
+        if (!strcmp(cn, "NEG")) return "(-" + pprim(r.args[0], t) + ")";
+        if (!strcmp(cn, "sqrt")) return "mm_sqrt2(" + pprim(r.args[0], Ty::Float) + ")";
+        if (!strcmp(cn, "DIV")) {
+            if (r.args[1].kind == Primary::FloatConst || r.args[1].kind == Primary::IntConst) {      // x / +-2^k = x * 2^-k, exactly
+                const float c = r.args[1].kind == Primary::FloatConst ? r.args[1].f : (float)r.args[1].i;
+                if (is_pow2_divisor(c)) return "(" + pprim(r.args[0], Ty::Float) + " * " + float_literal(1.0f / c) + "f)";
+            }
+            return "(" + pprim(r.args[0], Ty::Float) + " / " + pprim(r.args[1], Ty::Float) + ")";
+        }
+        // the truth-valued operators: a pair of bools; as an int (0 / 1) only if the value is used as one
+        std::string b;
+        const std::string notb = exit ? "mm_xnotb(" : "mm_notb(";
+        if (!strcmp(cn, "NOT")) b = notb + pbool(r.args[0]) + ")";
+        else if (!strcmp(cn, "EQ") && prim_bool(r.args[0]) && prim_bool(r.args[1])) {
+            // b == 0 is !b, b == 1 is b, otherwise the equivalence of two truth values
+            const Primary &x = r.args[0], &y = r.args[1];
+            if (y.kind == Primary::IntConst) b = y.i ? pbool(x) : notb + pbool(x) + ")";
+            else if (x.kind == Primary::IntConst) b = x.i ? pbool(y) : notb + pbool(y) + ")";
+            else b = "mm_eqb(" + pbool(x) + ", " + pbool(y) + ")";
+        } else {
+            // sqrt(a) < 2^k  ->  0 <= a < 4^k, like the scalar generator (hipgen.cpp rhs)
+            float kk = 0;
+            const Primary *sq = sqrt_less_pow2(r, &kk);
+            if (sq && env.value_visible(sq->value)) {
+                const std::string a = pprim(*sq, Ty::Float), k2 = "mm_vf(" + float_literal(kk) + "f)";
+                b = nonneg_or_nan(sq->value, 0) ? "mm_lt(" + a + ", " + k2 + ")"
+                                                : "mm_andb(mm_lt(" + a + ", " + k2 + "), mm_le(mm_vf(0.0f), " + a + "))";
+            } else {
+                const char *fn = !strcmp(cn, "LESS") ? "mm_lt(" : !strcmp(cn, "LEQ") ? "mm_le(" : "mm_eq(";
+                b = fn + pprim(r.args[0], t) + ", " + pprim(r.args[1], t) + ")";
+            }
+        }
+        return as_bool ? b : "mm_vi(" + b + ")";
+    }
+    std::string pair_ctype(const Value *v) const {      // the C type of a value's pair
+        return bools.count(v) ? "mm_bb" : v->var->type == Ty::Float ? "mm_pf" : "mm_pi";
+    }
+    std::string pval_as(const Primary &p, const Value *lhs) {      // operand in the representation of `lhs`
+        return bools.count(lhs) ? pbool(p) : pprim(p, lhs->var->type);
+    }
+
+    // ---- wave-uniform values inside a loop ----
+    // A loop phi that starts from a literal or a frame constant
+    // and is stepped by one -- `n = n + 1`, the iteration counter of every escape-time filter -- holds the same
+    // value in every lane and in both pixels for as long as they are in the loop, and so does everything
+    // computed from such values and loop-invariant scalars alone (`n + 1`, `n < 31`).  Those are kept as plain
+    // scalars (the compiler holds them in SGPRs and evaluates them on the scalar unit: uniform inside a loop
+    // with divergent exits) instead of as per-lane pairs; the per-pixel copy a phi needs after the loop is one
+    // select per iteration instead of an add, a compare and a select.  Values of pixels that have left the loop
+    // are don't-cares inside it, exactly as before.
+    bool invariant_scalar(const Primary &p) const {
+        if (p.kind == Primary::IntConst || p.kind == Primary::FloatConst) return true;
+        if (p.kind != Primary::Val) return false;
+        return p.value->index < 0 || !defs.count(p.value);          // uninitialised (0) or a frame constant
+    }
+    bool uniform_operand(const Primary &p) const {
+        return invariant_scalar(p) || (p.kind == Primary::Val && uniform.count(p.value));
+    }
+    void mark_uniform(const Block &b) {      // forward pass over a loop body (SSA: definitions precede uses)
+        for (const Stmt *s : b) {
+            if (!s->in_pixel) continue;
+            if (s->kind == Stmt::Assign && s->rhs.kind != Rhs::Internal) {
+                bool ok = s->rhs.kind == Rhs::Prim ? uniform_operand(s->rhs.prim) : s->rhs.kind == Rhs::Op;
+                if (ok && s->rhs.kind == Rhs::Op)
+                    for (const Primary &a : s->rhs.args) ok = ok && uniform_operand(a);
+                // a plain copy of an invariant scalar stays a broadcast (nothing to gain); ops on uniform values do not
+                if (ok && s->rhs.kind == Rhs::Prim && !(s->rhs.prim.kind == Primary::Val && uniform.count(s->rhs.prim.value))) ok = false;
+                // truth values stay pairs of bools built from the (broadcast) uniform operands: the compiler evaluates such a
+                // comparison on the scalar unit anyway, and keeps the pair in lane masks only in that form (checked in the ISA).
+                // With lane masks that no longer holds -- the ballot of a uniform comparison is a v_cmp per iteration -- so the
+                // exit-driven loops keep them as scalar bools, broadcast with mm_bu where a pair is wanted.
+                if (ok && bools.count(s->lhs) && !exit) ok = false;
+                if (ok) uniform.insert(s->lhs);
+            } else if (s->kind == Stmt::If) {
+                mark_uniform(s->then_);
+                mark_uniform(s->else_);
+            }
+        }
+    }
+    // the phis of `w` that are uniform induction variables; marks them and what follows from them
+    std::vector<const Stmt *> find_uniform_ivs(const Stmt *w) {
+        std::vector<const Stmt *> ivs;
+        if (env.knobs.pair_no_uniform) return ivs;
+        for (const Stmt *ph : w->phis) {
+            if (!ph->in_pixel || ph->rhs.kind != Rhs::Prim || ph->rhs2.kind != Rhs::Prim) continue;
+            if (!scalar_ty(ph->lhs->var->type) || bools.count(ph->lhs)) continue;
+            if (!invariant_scalar(ph->rhs.prim) || ph->rhs2.prim.kind != Primary::Val) continue;
+            const Stmt *d = ph->rhs2.prim.value->def;
+            if (!d || d->kind != Stmt::Assign || d->parent != w || d->rhs.kind != Rhs::Op || d->rhs.args.size() != 2) continue;
+            const char *cn = d->rhs.op->cname;
+            const Primary &a0 = d->rhs.args[0], &a1 = d->rhs.args[1];
+            const bool self0 = a0.kind == Primary::Val && a0.value == ph->lhs, self1 = a1.kind == Primary::Val && a1.value == ph->lhs;
+            const bool step = (!strcmp(cn, "ADD") && ((self0 && invariant_scalar(a1)) || (self1 && invariant_scalar(a0)))) ||
+                              (!strcmp(cn, "SUB") && self0 && invariant_scalar(a1));
+            if (!step) continue;
+            ivs.push_back(ph);
+            uniform.insert(ph->lhs);
+        }
+        if (!ivs.empty()) mark_uniform(w->body);
+        return ivs;
+    }
+
+    // ---- the uniform conjunct of an exit-driven loop's condition (see exit_driven_iteration) ----
+    struct Body {                                          // what find_split needs to know about a loop body
+        std::set<const Value *> defs;
+        std::map<const Value *, const Stmt *> if_of;      // exit phi of an `if` -> the if
+        std::vector<const Stmt *> order;                  // assignments and if-phis in program order
+        bool nested_loop = false;
+    };
+    void scan_body(const Block &b, Body &pb) const {
+        for (const Stmt *s : b) {
+            if (!s->in_pixel) continue;
+            if (s->kind == Stmt::Assign) { pb.defs.insert(s->lhs); pb.order.push_back(s); }
+            if (s->kind == Stmt::While) pb.nested_loop = true;
+            if (s->kind == Stmt::If) {
+                scan_body(s->then_, pb);
+                scan_body(s->else_, pb);
+                for (const Stmt *ph : s->phis)
+                    if (ph->in_pixel) { pb.defs.insert(ph->lhs); pb.if_of[ph->lhs] = s; pb.order.push_back(ph); }
+            }
+        }
+    }
+    // three-valued truth of `p` (0, 1, -1: unknown) when the value `l` is `lv` and nothing else is known
+    int eval3(const Primary &p, const Body &pb, const Value *l, int lv, int depth = 0) const {
+        if (p.kind == Primary::IntConst) return p.i == 0 ? 0 : p.i == 1 ? 1 : -1;
+        if (p.kind != Primary::Val || depth > 32) return -1;
+        if (p.value->index < 0) return 0;
+        if (p.value == l) return lv;
+        if (!pb.defs.count(p.value) || !bools.count(p.value)) return -1;
+        const Stmt *d = p.value->def;
+        if (!d) return -1;
+        if (d->kind == Stmt::Phi) {
+            auto it = pb.if_of.find(p.value);
+            if (it == pb.if_of.end() || d->rhs.kind != Rhs::Prim || d->rhs2.kind != Rhs::Prim) return -1;
+            const Primary &cp = it->second->cond.prim;
+            const int c = eval3(cp, pb, l, lv, depth + 1);
+            // `c ? c : b` is `c ? 1 : b`, `c ? a : c` is `c ? a : 0`
+            const bool same1 = cp.kind == Primary::Val && d->rhs.prim.kind == Primary::Val && d->rhs.prim.value == cp.value && bools.count(cp.value);
+            const bool same2 = cp.kind == Primary::Val && d->rhs2.prim.kind == Primary::Val && d->rhs2.prim.value == cp.value && bools.count(cp.value);
+            const int a = same1 ? 1 : eval3(d->rhs.prim, pb, l, lv, depth + 1);
+            const int b = same2 ? 0 : eval3(d->rhs2.prim, pb, l, lv, depth + 1);
+            if (c == 1) return a;
+            if (c == 0) return b;
+            return a == b ? a : -1;
+        }
+        if (d->kind != Stmt::Assign) return -1;
+        if (d->rhs.kind == Rhs::Prim) return eval3(d->rhs.prim, pb, l, lv, depth + 1);
+        if (d->rhs.kind != Rhs::Op) return -1;
+        const char *cn = d->rhs.op->cname;
+        if (!strcmp(cn, "NOT")) { const int x = eval3(d->rhs.args[0], pb, l, lv, depth + 1); return x < 0 ? -1 : !x; }
+        if (!strcmp(cn, "EQ") && prim_bool(d->rhs.args[0]) && prim_bool(d->rhs.args[1])) {
+            const int x = eval3(d->rhs.args[0], pb, l, lv, depth + 1), y = eval3(d->rhs.args[1], pb, l, lv, depth + 1);
+            return x < 0 || y < 0 ? -1 : x == y;
+        }
+        return -1;
+    }
+    // the uniform conjunct of w's condition, if there is one that may be split off; `leave`: the value with which it ends the loop
+    const Stmt *find_split(const Stmt *w, const std::set<const Value *> &outside, bool &leave) const {
+        if (w->cond.prim.kind != Primary::Val) return nullptr;
+        Body pb;
+        scan_body(w->body, pb);
+        if (pb.nested_loop) return nullptr;
+        // the condition at the back edge: the condition phi's next value
+        const Stmt *cph = nullptr;
+        for (const Stmt *ph : w->phis) if (ph->in_pixel && ph->lhs == w->cond.prim.value) cph = ph;
+        if (!cph || cph->rhs2.kind != Rhs::Prim) return nullptr;
+        for (const Stmt *d : pb.order) {
+            if (d->kind != Stmt::Assign || !uniform.count(d->lhs) || !bools.count(d->lhs) || d->rhs.kind != Rhs::Op) continue;
+            if (!is_truth_op(d->rhs.op->cname) || d->rhs.args.size() != 2) continue;      // a comparison (NOT has one operand)
+            if (d->rhs.args[0].type() != Ty::Int || d->rhs.args[1].type() != Ty::Int) continue;
+            for (int lv = 0; lv < 2; ++lv) {
+                if (eval3(cph->rhs2.prim, pb, d->lhs, lv) != 0) continue;
+                // what depends on the conjunct must not reach a phi that is read after the loop
+                std::set<const Value *> dep{d->lhs};
+                auto in = [&](const Primary &p) { return p.kind == Primary::Val && dep.count(p.value) > 0; };
+                for (const Stmt *q : pb.order) {
+                    bool dp = false;
+                    if (q->kind == Stmt::Assign) { if (q->rhs.kind == Rhs::Prim) dp = in(q->rhs.prim); for (const Primary &a : q->rhs.args) dp = dp || in(a); }
+                    else dp = in(pb.if_of.at(q->lhs)->cond.prim) || in(q->rhs.prim) || in(q->rhs2.prim);
+                    if (dp) dep.insert(q->lhs);
+                }
+                bool ok = true;
+                for (const Stmt *ph : w->phis)
+                    if (ph->in_pixel && outside.count(ph->lhs) && in(ph->rhs2.prim)) ok = false;
+                if (!ok) continue;
+                leave = lv != 0;
+                return d;
+            }
+        }
+        return nullptr;
+    }
+    // operand of the back edge's scalar comparison: a literal, or the uniform value in a scalar register
+    bool tail_operand(const Primary &p, std::string &text, std::vector<std::string> &inputs, int first_input) {
+        if (p.kind == Primary::IntConst) { text = std::to_string(p.i); return true; }
+        if (p.kind != Primary::Val) return false;
+        text = "%" + std::to_string(first_input + (int)inputs.size());
+        inputs.push_back("__builtin_amdgcn_readfirstlane((int)(" + env.prim(p) + "))");
+        return true;
+    }
+
+    // ---- loops ----
+    struct Loop {
+        Stmt *s;
+        std::string ind, a;                       // indentation; the mask of the pixels still in the loop (mm_bb)
+        std::set<const Value *> outside;          // phis that are read after the loop
+        std::vector<const Stmt *> ivs;            // uniform induction variables: a scalar twin, read inside the loop instead of the pair
+        std::vector<std::pair<const Stmt *, std::string>> exit_copy;      // exit-driven: a phi of `outside` and the name of its exit copy
+        bool is_iv(const Stmt *ph) const { return std::find(ivs.begin(), ivs.end(), ph) != ivs.end(); }
+    };
+    // Back edge: the phis take their next values -- a parallel copy, temporaries first -- and the induction variables'
+    // scalar twins theirs.  `select`: a phi that is read after the loop keeps its value once its pixel has left;
+    // without it the pairs of the induction variables are not kept up at all.
+    void step_phis(const Loop &w, const std::string &I, bool select) {
+        std::vector<Stmt *> phis;
+        for (Stmt *ph : w.s->phis) if (ph->in_pixel && (select || !w.is_iv(ph))) phis.push_back(ph);
+        for (size_t k = 0; k < phis.size(); ++k) {
+            const std::string nv = pval_as(phis[k]->rhs2.prim, phis[k]->lhs);
+            out << I << "const " << pair_ctype(phis[k]->lhs) << " " << w.a << "_n" << k << " = "
+                << (select && w.outside.count(phis[k]->lhs) ? "mm_sel2(" + w.a + ", " + nv + ", " + vname(phis[k]->lhs) + ")" : nv) << ";\n";
+        }
+        for (size_t k = 0; k < phis.size(); ++k) out << I << vname(phis[k]->lhs) << " = " << w.a << "_n" << k << ";\n";
+        for (const Stmt *ph : w.ivs) out << I << "u" << vname(ph->lhs) << " = " << env.prim(ph->rhs2.prim) << ";\n";
+    }
+    // Per-iteration selects (no lane masks, or MMHIP_PAIR_EXIT=0): one iteration and its back edge.
+    void selecting_iteration(const Loop &w) {
+        Stmt *s = w.s;
+        const std::string &ind = w.ind, &a = w.a;
+        stmts(s->body, ind + "  ", a);
+        // A phi that is read after the loop, and the loop condition, keep their value once their pixel has left the
+        // loop (after the loop a phi is read through this per-pixel copy); the others may run on.
+        step_phis(w, ind + "  ", true);
+        out << ind << "  " << a << " = mm_andb(" << a << ", " << pbool(s->cond.prim) << ");\n";
+    }
+    // Exit-driven loops (MM_PAIR_EXIT, lane masks only).
+    // A pixel's `active` bit is monotone: it clears once.  The value a loop phi has after the loop is the value it
+    // had at the back edge at which its pixel's bit cleared, so nothing has to be selected at any other back edge.
+    // The loop runs in two levels: the inner do-while is the likely path (the phis' running copies take their next
+    // values unconditionally, `left = active & ~cond` is two s_andn2_b64, one scalar test), the outer level is the
+    // exit block: every phi that is read after the loop has an exit copy, initialised with the phi's initial value
+    // and written there for the lanes in `left`, which are then cleared from `active`.  Every lane that ever was
+    // active is written exactly once, at the back edge and with the value of the last select that changed it in
+    // the per-iteration form, so the results are the same bits.  (Two levels, one exit each: with two exits from
+    // one loop the compiler's control-flow passes rebuild the conditions as lane masks and copy the phis' registers
+    // at the back edge; profiles/r05_pair_loop_isa.txt has the counts of the shapes tried.)
+    //
+    // A wave-uniform conjunct of the loop condition -- `n < 31` of an escape-time loop: a comparison of uniform ints
+    // such that the condition is false for every lane once it has one value -- is not ANDed into the masks at all:
+    // inside the loop its name is bound to the value it has while the loop runs (the compiler folds the logic built
+    // on it), the comparison itself is made at the back edge on the scalar unit, and when it ends the loop every
+    // active lane leaves.  Only taken when no phi that is read after the loop depends on the conjunct (in the last
+    // iteration its name holds the wrong value).  Looking at one iteration is enough for that: in every iteration but the
+    // last the bound name *is* the conjunct's value, so whatever the phis carry into a later iteration is right; wrong
+    // values only arise in the last iteration, no iteration follows it, and what it leaves behind is read through the
+    // exit copies alone -- whose next values the scan has shown not to depend on the conjunct.  The conjunct's own
+    // operands are read at the end of the body, before the phis step.  The back edge is one asm statement then (MM_PAIR_EXIT_TAIL, default
+    // 1): the compiler combines the two tests as lane masks (s_cselect_b64, s_and_b64 with exec, branch on vcc:
+    // 12 scalar instructions per iteration), the statement needs 6 and the loop 9.
+    void exit_driven_iteration(const Loop &w, const std::string &l) {
+        Stmt *s = w.s;
+        const std::string &ind = w.ind, &a = w.a, I2 = ind + "    ";
+        bool leave = false;
+        const Stmt *split = find_split(s, w.outside, leave);
+        // the back edge's scalar comparison as one asm statement: its operands
+        std::vector<std::string> tail_inputs;
+        std::string tail_o0, tail_o1;
+        const bool asm_tail = split && env.knobs.pair_exit_tail.value_or(1) &&
+                              !(split->rhs.args[0].kind == Primary::IntConst && split->rhs.args[1].kind == Primary::IntConst) &&
+                              tail_operand(split->rhs.args[0], tail_o0, tail_inputs, 8) && tail_operand(split->rhs.args[1], tail_o1, tail_inputs, 8);
+        out << ind << "  mm_bb " << l << ";" << (asm_tail ? " unsigned long " + l + "_u, " + l + "_t;" : split ? " bool " + l + "_b;" : "") << "\n";
+        out << ind << "  do {\n";
+        const Stmt *outer_split = split_def;
+        const bool outer_leave = split_leave;
+        split_def = split;
+        split_leave = leave;
+        stmts(s->body, I2, a);
+        split_def = outer_split;
+        split_leave = outer_leave;
+        // The conjunct stands for a statement of the body: its operands are read here, before the phis and the induction
+        // variables take their next values (an operand may be such a phi: `m = n; n = n + 1` with `m < 6` as the bound).
+        if (asm_tail)
+            for (size_t i = 0; i < tail_inputs.size(); ++i) {
+                out << I2 << "const int " << l << "_o" << i << " = " << tail_inputs[i] << ";\n";
+                tail_inputs[i] = l + "_o" + std::to_string(i);
+            }
+        else if (split)
+            out << I2 << l << "_b = (bool)(" << env.rhs(split) << ") == " << (leave ? "true" : "false") << ";\n";
+        step_phis(w, I2, false);      // nothing selected
+        // lanes that leave at this back edge
+        const std::string c = pbool(s->cond.prim);
+        const std::string lx = a + ".x & ~" + c + ".x", ly = a + ".y & ~" + c + ".y";
+        if (asm_tail) {
+            // SCC = the conjunct; _u = all ones when it ends the loop; left = active & ~cond; _t = _u | left.x | left.y
+            const char *cn = split->rhs.op->cname;
+            const char *cmp = !strcmp(cn, "LESS") ? "s_cmp_lt_i32" : !strcmp(cn, "LEQ") ? "s_cmp_le_i32" : "s_cmp_eq_i32";
+            out << I2 << "const mm_bb " << l << "_c = " << c << ";\n";
+            out << I2 << "asm(\"" << cmp << " " << tail_o0 << ", " << tail_o1 << "\\n\\ts_cselect_b64 %2, " << (leave ? "-1, 0" : "0, -1")
+                << "\\n\\ts_andn2_b64 %0, %4, %6\\n\\ts_andn2_b64 %1, %5, %7\\n\\ts_or_b64 %3, %2, %0\\n\\ts_or_b64 %3, %3, %1\"\n"
+                << I2 << "    : \"=&s\"(" << l << ".x), \"=&s\"(" << l << ".y), \"=&s\"(" << l << "_u), \"=&s\"(" << l << "_t)\n"
+                << I2 << "    : \"s\"(" << a << ".x), \"s\"(" << a << ".y), \"s\"(" << l << "_c.x), \"s\"(" << l << "_c.y)";
+            for (const std::string &in : tail_inputs) out << ", \"s\"(" << in << ")";
+            out << " : \"scc\");\n";
+            out << ind << "  } while (" << l << "_t == 0);\n";
+            // the uniform conjunct has ended the loop: every lane that was still active leaves
+            out << ind << "  " << l << ".x |= " << a << ".x & " << l << "_u; " << l << ".y |= " << a << ".y & " << l << "_u;\n";
+        } else if (split) {
+            out << I2 << l << " = mm_bb{" << lx << ", " << ly << "};\n";
+            out << ind << "  } while (!" << l << "_b && (" << l << ".x | " << l << ".y) == 0);\n";
+            out << ind << "  if (" << l << "_b) " << l << " = " << a << ";      // the uniform conjunct has ended the loop: every active lane leaves\n";
+        } else {
+            out << I2 << l << " = mm_bb{" << lx << ", " << ly << "};\n";
+            out << ind << "  } while ((" << l << ".x | " << l << ".y) == 0);\n";
+        }
+        // exit block: the phis hold their next values; a uniform induction variable's is its scalar twin's
+        for (const auto &e : w.exit_copy) {
+            std::string nv = vname(e.first->lhs);
+            if (w.is_iv(e.first)) nv = e.first->lhs->var->type == Ty::Float ? "mm_vf((float)u" + nv + ")" : "mm_vi(mm_s2v((int)u" + nv + "))";
+            out << ind << "  " << e.second << " = mm_sel2(" << l << ", " << nv << ", " << e.second << ");\n";
+        }
+        out << ind << "  " << a << ".x &= ~" << l << ".x; " << a << ".y &= ~" << l << ".y;\n";
+    }
+    // A `while` under `mask`: runs while either pixel is in it.  The two shapes share everything but the iteration.
+    void while_loop(Stmt *s, const std::string &ind, const std::string &mask) {
+        const std::string id = std::to_string(ids++);
+        Loop w{s, ind, "mm_a" + id, {}, {}, {}};
+        uses_outside(code.body, s, w.outside);
+        for (int i = 0; i < 4; ++i) w.outside.insert(code.result[i]);
+        // (selects freeze the condition too: it is tested again after its pixel has left)
+        if (!exit && s->cond.prim.kind == Primary::Val) w.outside.insert(s->cond.prim.value);
+        for (Stmt *ph : s->phis)
+            if (ph->in_pixel) out << ind << vname(ph->lhs) << " = " << pval_as(ph->rhs.prim, ph->lhs) << ";\n";
+        if (exit) {      // exit copies of the phis that are read after the loop: a pixel that never enters it sees the initial value
+            int k = 0;
+            for (Stmt *ph : s->phis) {
+                if (!ph->in_pixel) continue;
+                if (w.outside.count(ph->lhs)) w.exit_copy.push_back({ph, w.a + "_e" + std::to_string(k)});
+                ++k;      // (numbered like the phis)
+            }
+            for (const auto &e : w.exit_copy) out << ind << pair_ctype(e.first->lhs) << " " << e.second << " = " << vname(e.first->lhs) << ";\n";
+        }
+        w.ivs = find_uniform_ivs(s);
+        for (const Stmt *ph : w.ivs) {
+            uniform.erase(ph->lhs);       // the initial value is printed with the ordinary names
+            const std::string init = env.prim(ph->rhs.prim);
+            uniform.insert(ph->lhs);
+            out << ind << (ph->lhs->var->type == Ty::Float ? "float u" : "int u") << vname(ph->lhs) << " = " << init << ";\n";
+        }
+        out << ind << "mm_bb " << w.a << " = mm_andb(" << mask << ", " << pbool(s->cond.prim) << ");\n";
+        out << ind << "while (" << w.a << ".x | " << w.a << ".y) {\n";
+        if (exit) exit_driven_iteration(w, "mm_l" + id);
+        else selecting_iteration(w);
+        out << ind << "}\n";
+        for (const auto &e : w.exit_copy) out << ind << vname(e.first->lhs) << " = " << e.second << ";\n";      // read through it from here on
+        for (const Stmt *ph : w.ivs) uniform.erase(ph->lhs);
+    }
+
+    // ---- statements; `mask`: the expression (mm_bb) under which the block runs ----
+    void stmts(Block &b, const std::string &ind, const std::string &mask) {
+        for (Stmt *s : b) {
+            if (!s->in_pixel) continue;
+            switch (s->kind) {
+                case Stmt::Assign:
+                    if (s == split_def) {       // tested at the back edge (exit_driven_iteration): inside the loop it holds
+                        out << ind << "const bool u" << vname(s->lhs) << " = " << (split_leave ? "false" : "true") << ";\n";
+                        break;
+                    }
+                    if (uniform.count(s->lhs)) {       // scalar statement, the scalar kernel's own expression
+                        const char *ty = bools.count(s->lhs) ? "bool" : s->lhs->var->type == Ty::Float ? "float" : "int";
+                        out << ind << "const " << ty << " u" << vname(s->lhs) << " = " << env.rhs(s) << ";\n";
+                        break;
+                    }
+                    out << ind << vname(s->lhs) << " = " << prhs(s->rhs, s->lhs) << ";\n";
+                    break;
+                case Stmt::If: {
+                    const std::string c = "mm_c" + std::to_string(ids++);
+                    out << ind << "const mm_bb " << c << " = " << pbool(s->cond.prim) << ";\n";
+                    stmts(s->then_, ind, "mm_andb(" + mask + ", " + c + ")");
+                    stmts(s->else_, ind, "mm_andb(" + mask + (exit ? ", mm_xnotb(" : ", mm_notb(") + c + "))");
+                    for (Stmt *ph : s->phis)
+                        if (ph->in_pixel)
+                            out << ind << vname(ph->lhs) << " = mm_sel2(" << c << ", " << pval_as(ph->rhs.prim, ph->lhs) << ", "
+                                << pval_as(ph->rhs2.prim, ph->lhs) << ");\n";
+                    break;
+                }
+                case Stmt::While: while_loop(s, ind, mask); break;
+                default: break;
+            }
+        }
+    }
+
+    // (this text is part of the kernels' cache keys: it still names the function as it was called when it was written)
+    void emit_helpers() override {
+        if (exit)      // emitted behind the preludes, not in the device prelude: the other kernels' text, and keys, stay as they were
+            out << R"(#define MM_PAIR_EXIT 1
+// exit-driven pair loops (hipgen.cpp pair_while_exit).  mm_xnotb: a lane mask's bits outside exec are never read -- selects
+// read their own lane's bit, and every mask a branch tests is ANDed with one that lies inside exec -- so NOT needs no re-AND
+// and a broadcast no ballot.
+MM_DEV mm_bb mm_xnotb(mm_bb a) { return mm_bb{~a.x, ~a.y}; }
+MM_DEV mm_bb mm_xbu(bool u) { const unsigned long m = u ? ~0ul : 0ul; return mm_bb{m, m}; }      // a literal truth value, likewise
+// a wave-uniform int for the exit copies, moved from its scalar register where it is wanted (as an ordinary operand it
+// would pull the loop counter, and the loop's bound test, onto the vector unit)
+MM_DEV int mm_s2v(int u) { int r; asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(__builtin_amdgcn_readfirstlane(u))); return r; }
+)";
+    }
+    // two pixels (rows mm_p and mm_p + 1 of this work-item's column) in lockstep
+    void emit_pixel_loop(const std::string &I) override {
+        out << "#pragma unroll 1\n" << I << "for (; mm_p < A.ppt; mm_p += 2) {\n"
+            << I << "  // vertically adjacent pixels: they mostly take the same path (a wave covers 16 x 8 pixels per step)\n"
+            << I << "  const int rl_a = row0 + (int)(threadIdx.x / MM_TILE_W) + mm_p * MM_TILE_H, rl_b = rl_a + 1;\n"
+            << I << "  const int row_a = rl_a < A.num_rows ? rl_a : A.num_rows - 1, row_b = rl_b < A.num_rows ? rl_b : A.num_rows - 1;\n"
+            << I << "  const mm_pf mm_y2 = {A.ytab[row_a], A.ytab[row_b]};    // CALC_VIRTUAL_Y per row, by the prologue\n";
+        std::set<Value *> seen;
+        for (Value *v : env.pix_defs)
+            if (v->index >= 0 && seen.insert(v).second) out << I << "  " << pair_ctype(v) << " " << vname(v) << ";\n";
+        stmts(code.body, I + "  ", "mm_bu(true)");
+        out << I << "  mm_tup<4> mm_ra, mm_rb;\n";
+        for (int i = 0; i < 4; ++i) {
+            const std::string v = pprim(Primary::V(code.result[i]), Ty::Float);
+            out << I << "  mm_ra.v[" << i << "] = " << v << ".x; mm_rb.v[" << i << "] = " << v << ".y;\n";
+        }
+        out << I << "  // a row past the end was evaluated as the last row: storing it there again writes the same bytes\n"
+            << I << "  mm_store_pixel(A, row_a, col, mm_ra);\n"
+            << I << "  mm_store_pixel(A, row_b, col, mm_rb);\n" << I << "}\n";
+    }
+};
+
+}  // namespace
+
+std::unique_ptr<PairMode> make_pair_mode(const PairEnv &env) {
+    std::unique_ptr<PairGen> g(new PairGen(env));
+    if (!g->eligible()) return nullptr;
+    g->infer_bools();
+    return g;
+}
+
+}  // namespace hipgen
+}  // namespace mm

@@ -1,4 +1,4 @@
-"""Probe filters for the exit-driven pair-mode loops (hipgen.cpp pair_while_exit), one per case of the new code.
+"""Probe filters for the exit-driven pair-mode loops (hipgen_pair.cpp exit_driven_iteration), one per case of the new code.
 
 Each probe is project text, arithmetic only (so it runs in pair mode), and writes what tells its case apart into its
 channels: an iteration count n as n / 8 (byte round(n * 31.875): distinct for n = 0..8), a per-lane value as itself.

@@ -1,4 +1,4 @@
-"""Exit-driven pair-mode loops (hipgen.cpp pair_while_exit), the part that needs no GPU: the off switch restores the
+"""Exit-driven pair-mode loops (hipgen_pair.cpp exit_driven_iteration), the part that needs no GPU: the off switch restores the
 parent's kernel text, kernels outside pair mode do not change at all, and every probe of tests/pair_exit_probes.py
 exercises the case it stands for (checked with the oracle alone)."""
 import hashlib

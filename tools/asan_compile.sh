@@ -6,7 +6,7 @@ B=/tmp/mm_asan
 mkdir -p $B
 S=mathmap_amd/csrc
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -I$S -Iinclude -o $B/driver tools/asan_compile_driver.cpp \
-    $S/ir.cpp $S/parser.cpp $S/gen.cpp $S/lower.cpp $S/builtins.cpp $S/passes.cpp $S/specialize.cpp $S/hipgen.cpp \
+    $S/ir.cpp $S/parser.cpp $S/gen.cpp $S/lower.cpp $S/builtins.cpp $S/passes.cpp $S/specialize.cpp $S/hipgen.cpp $S/hipgen_pair.cpp \
     $S/prelude_blob.cpp $S/noise_prelude_blob.cpp $S/noise_table_blob.cpp $S/fastmath_blob.cpp
 python3 - > $B/filters.txt <<'PY'
 import importlib.util, sys, glob

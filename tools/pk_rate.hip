@@ -1,5 +1,5 @@
 // Microbenchmark: issue rate of v_pk_add_f32 / v_pk_mul_f32 against v_add_f32 / v_mul_f32 (no FMA
-// contraction), dependent chains, 8 waves per SIMD -- what bounds hipgen.cpp's pair mode.
+// contraction), dependent chains, 8 waves per SIMD -- what bounds the generator's pair mode (hipgen_pair.cpp).
 // hipcc --offload-arch=gfx950 -O3 -ffp-contract=off tools/pk_rate.hip -o /tmp/pk_rate
 #include <hip/hip_runtime.h>
 #include <cstdio>
