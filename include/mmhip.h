@@ -123,6 +123,15 @@ int mmhip_filter_clip_launch_geometry(const mmhip_filter *f, int region_w, int n
    t or frame, one prologue serves every frame).  No GPU needed. */
 enum { MMHIP_CLIP_PLAN_FIELDS = 4 };
 int mmhip_filter_clip_batch_plan(const mmhip_filter *f, int region_w, int num_rows, int frames, int64_t *out);
+/* The native batches of such a clip at render size render_w x render_h: out[MMHIP_CLIP_NATIVE_PLAN_FIELDS] receives
+   eligible (1: every native call of the filter is a gaussian_blur the batches take, see mmhip_render_clip),
+   frames_per_batch (the smallest of mmhip_filter_clip_batch_plan's cap, 65 535 jobs and MMHIP_CLIP_NATIVE_BYTES /
+   bytes_per_frame; the environment variable is read once, default 8 GiB; 0: below 2, the clip is rendered frame by
+   frame), batches, and bytes_per_frame (per call site the checkpoints, 8 B/px rounded up to blocks of 16 steps, the
+   16 B/px intermediate and a 16 B/px map). */
+enum { MMHIP_CLIP_NATIVE_PLAN_FIELDS = 4 };
+int mmhip_filter_clip_native_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int render_h, int frames,
+                                  int64_t *out);
 /* The clip variant of the module -- kernels mm_prologue_clip, mm_rows_clip (filters with a per-row slice) and
    mm_pixels_clip: the text of mmhip_filter_kernel_source with the kernels' heads replaced -- and its gfx950 compile
    (like mmhip_filter_jit).  Built on the first clip render of the filter, cached on it and on disk. */
@@ -163,7 +172,8 @@ int mmhip_set_image_device(mmhip_invocation *inv, int index, const void *device_
        wins over a bad frame.
      - All frames have one size; scale and middle are those of one frame.
      - Native filters and render() sample ORIG_VAL(x, y, image, 0.0) (builtins.c:273-343 render_image): gaussian_blur(in, ..),
-       convolve, render(in) and the direct RGBA8 blur output (exact and tolerance chains) read FRAME 0 of a sequence.
+       convolve, render(in) and the direct RGBA8 blur output (exact and tolerance chains) read FRAME 0 of a sequence
+       (the default; mmhip_set_native_input_frame makes it the render's own frame).
      - Float maps (native results, closure images) have one frame and ignore the frame number.
      - The reference-ABI tier (mathmap_hip_backend.h) binds one frame per drawable.
    Errors: num_frames < 1; a total byte count that overflows or cannot be allocated; height * num_frames of
@@ -172,6 +182,19 @@ int mmhip_set_image_sequence_host(mmhip_invocation *inv, int index, const uint8_
                                   int num_frames);
 int mmhip_set_image_sequence_device(mmhip_invocation *inv, int index, const void *device_rgba32, int width, int height,
                                     int num_frames);
+/* Which frame of a bound sequence native filters read (gaussian_blur, render(), convolve, half_convolve,
+   visualize_fft; an extension).  The reference's render_image samples its argument at frame 0 (ORIG_VAL(fx, fy, image,
+   0.0), builtins/builtins.c:334), so gaussian_blur(in, ...) on a sequence blurs frame 0 in every output frame:
+     MMHIP_NATIVE_FRAME_ZERO (default)  that behaviour, byte for byte;
+     MMHIP_NATIVE_FRAME_CURRENT         an argument that is a bound drawable of more than one frame is read at the
+                                        render's own frame number (mmhip_render's `frame`, frames[i] of a clip): the
+                                        native filter sees that frame as a single image.
+   In `current` mode a render whose frame number the sequence does not have fails, with a message naming the filter and
+   the frame; it never reads another frame instead.  Closure images keep the reference's rule (their body runs at frame
+   0); in(xy, n) in filter code is not affected.  A result computed from one frame is never reused for another: the frame
+   number is part of what the native results' memo compares.  Errors: a mode that is neither constant. */
+enum { MMHIP_NATIVE_FRAME_ZERO = 0, MMHIP_NATIVE_FRAME_CURRENT = 1 };
+int mmhip_set_native_input_frame(mmhip_invocation *inv, int mode);
 int mmhip_set_edge_colors(mmhip_invocation *inv, uint32_t color_x, uint32_t color_y);
 int mmhip_set_render_size(mmhip_invocation *inv, int render_width, int render_height);
 /* sub-pixel sampling offset of the slice (mathmap.h:219; -0.5 for the second supersampling pass) */
@@ -201,6 +224,14 @@ int mmhip_render(mmhip_invocation *inv, int frame, float t, int region_x, int re
      - Filters that call native filters (gaussian_blur, ...) or render closure images need the host between the
        prologue and the pixels of every frame: for them the call is a loop of mmhip_render.  Nothing is refused;
        mmhip_clip_batched_launches tells the two apart.
+     - ... except filters whose native calls are all gaussian_blur outside loops (no closure images, gauss_mode exact,
+       MMHIP_GAUSS_SEGMENTS unset, no native row margin): one prologue launch over a batch, one read-back of its
+       records, every distinct blur of a call site in one launch set over the frames, then the pixel launch over
+       per-frame image tables -- or none, where the blurs write the frames' RGBA8 bytes themselves.  The bytes are the
+       loop's.  A batch holding a call the batched blur does not take (a deviation below half a pixel, an input of
+       another size or under a non-identity mapping) is rendered by the loop.  mmhip_filter_clip_native_plan and the
+       mmhip_clip_native_* counters report this path; mmhip_clip_batched_launches and mmhip_clip_prologue_frames
+       stay those of filters without native calls.
      - Asynchronous like mmhip_render.  With mmhip_enable_timing, mmhip_drain_kernel_ms reports one entry per batch.
      - Supersampling is not batched: use mmhip_render_supersampled per frame.
    Errors: num_frames < 1; frames or ts NULL; a frame_stride smaller than the band; mmhip_render's own. */
@@ -212,6 +243,12 @@ int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, 
    clip prologue evaluated (one per call where they do not read t or frame). */
 long mmhip_clip_batched_launches(mmhip_invocation *inv);
 long mmhip_clip_prologue_frames(mmhip_invocation *inv);
+/* The native batches of clip renders so far (filters whose native calls are gaussian_blur): batches run, blurs computed
+   in them (frames of a batch with equal arguments share one), and frames whose bytes a blur wrote itself (no pixel
+   launch).  A batch that fell back to the loop counts in none of them. */
+long mmhip_clip_native_batches(mmhip_invocation *inv);
+long mmhip_clip_native_blurs(mmhip_invocation *inv);
+long mmhip_clip_native_direct_frames(mmhip_invocation *inv);
 /* The CLI's -o: supersampled render of a region (two slices + 1-1-2-1-1 / 6 byte combine,
    call_invocation, mathmap_common.c:880-927).  Compile the filter with supersampling = 1. */
 int mmhip_render_supersampled(mmhip_invocation *inv, int frame, float t, int region_x, int region_y, int region_w,

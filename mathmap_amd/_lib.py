@@ -47,6 +47,7 @@ SYMBOLS = {
     "mmhip_filter_launch_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "mmhip_filter_clip_launch_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "mmhip_filter_clip_batch_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "mmhip_filter_clip_native_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "mmhip_filter_clip_kernel_source": (C.c_char_p, [C.c_void_p]),
     "mmhip_filter_jit_clip": (C.c_long, [C.c_void_p, C.c_int]),
     "mmhip_filter_num_closures": (C.c_int, [C.c_void_p]),
@@ -60,6 +61,7 @@ SYMBOLS = {
     "mmhip_set_bool": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mmhip_set_color": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float]),
     "mmhip_set_native_row_margin": (C.c_int, [C.c_void_p, C.c_int]),
+    "mmhip_set_native_input_frame": (C.c_int, [C.c_void_p, C.c_int]),
     "mmhip_drain_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "mmhip_direct_native_launches": (C.c_long, [C.c_void_p]),
     "mmhip_tolerance_blur_launches": (C.c_long, [C.c_void_p]),
@@ -80,6 +82,9 @@ SYMBOLS = {
                                     C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "mmhip_clip_batched_launches": (C.c_long, [C.c_void_p]),
     "mmhip_clip_prologue_frames": (C.c_long, [C.c_void_p]),
+    "mmhip_clip_native_batches": (C.c_long, [C.c_void_p]),
+    "mmhip_clip_native_blurs": (C.c_long, [C.c_void_p]),
+    "mmhip_clip_native_direct_frames": (C.c_long, [C.c_void_p]),
     "mmhip_render_supersampled": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mmhip_render_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),

@@ -16,12 +16,16 @@ from ._lib import Options, UservalInfo, lib
 UV_INT, UV_FLOAT, UV_BOOL, UV_COLOR, UV_CURVE, UV_GRADIENT, UV_IMAGE = range(7)
 # mmhip_options.gauss_mode (include/mmhip.h)
 GAUSS_MODES = {"exact": 0, "tolerance": 1}
+# mmhip_set_native_input_frame's modes
+NATIVE_INPUT_FRAMES = {"zero": 0, "current": 1}
 EDGE_COLOR, EDGE_WRAP, EDGE_REFLECT, EDGE_ROTATE = range(4)
 # mmhip_filter_launch_geometry's out[] (include/mmhip.h)
 GEOMETRY_FIELDS = ("tiles_x", "tiles_y", "wg1", "nwg", "ppt", "tile_w", "tile_h", "unroll", "pair_mode", "single_pixel",
                    "xcd_order", "tiles_magic", "xcd_full")
 # mmhip_filter_clip_batch_plan's out[]
 CLIP_PLAN_FIELDS = ("grid_x", "frames_per_batch", "batches", "shared_slot")
+# mmhip_filter_clip_native_plan's out[]
+CLIP_NATIVE_PLAN_FIELDS = ("eligible", "frames_per_batch", "batches", "bytes_per_frame")
 
 
 class MathMapError(RuntimeError):
@@ -185,6 +189,16 @@ class Filter:
             raise MathMapError(_err())
         return dict(zip(CLIP_PLAN_FIELDS, out))
 
+    def clip_native_plan(self, region_w, num_rows, frames, render_w=None, render_h=None):
+        """How render_clip batches the gaussian_blur calls of a `frames`-frame clip at render size render_w x render_h
+        (default: the region's): a dict of the CLIP_NATIVE_PLAN_FIELDS (eligible 0: the filter's native calls are not
+        batched; frames_per_batch 0: rendered frame by frame)."""
+        out = (C.c_int64 * len(CLIP_NATIVE_PLAN_FIELDS))()
+        rw, rh = region_w if render_w is None else render_w, num_rows if render_h is None else render_h
+        if lib().mmhip_filter_clip_native_plan(self._h, region_w, num_rows, rw, rh, frames, out) != 0:
+            raise MathMapError(_err())
+        return dict(zip(CLIP_NATIVE_PLAN_FIELDS, out))
+
     @property
     def clip_kernel_source(self):
         """The clip variant of kernel_source: kernels mm_prologue_clip, mm_rows_clip, mm_pixels_clip."""
@@ -292,7 +306,7 @@ class Invocation:
         """Binds a host uint8 array as input drawable (uploaded once to HBM): [H,W,3|4] is one image,
         [N,H,W,3|4] a sequence of N frames of one size.  in(xy, n) reads frame (int)n of it (plain
         in(xy): frame (int)t), and opaque white where there is no such frame; gaussian_blur, convolve
-        and render() read frame 0."""
+        and render() read frame 0 (set_native_input_frame("current"): the render's own frame)."""
         u = self._index(name)
         a = as_image_sequence(array)
         n, h, w, c = a.shape
@@ -310,6 +324,14 @@ class Invocation:
         """Striped frames: let native filters (gaussian_blur) fill only the rows a stripe render
         reads, +- `margin` rows, plus their own halo.  -1 restores whole maps."""
         self._check(lib().mmhip_set_native_row_margin(self._h, margin))
+
+    def set_native_input_frame(self, mode):
+        """Which frame of a bound image sequence native filters (gaussian_blur, render(), convolve, ...) read: "zero"
+        (default, the reference's behaviour) or "current", the frame number of the render (frames[i] of a clip) -- a
+        frame the sequence does not have is then an error."""
+        if mode not in NATIVE_INPUT_FRAMES:
+            raise MathMapError("native input frame must be one of %s, not %r" % (", ".join(sorted(NATIVE_INPUT_FRAMES)), mode))
+        self._check(lib().mmhip_set_native_input_frame(self._h, NATIVE_INPUT_FRAMES[mode]))
 
     def set_render_size(self, render_width, render_height):
         """Renders the canvas at another pixel size (the GIMP preview, mathmap.c:2191-2223);
@@ -427,6 +449,18 @@ class Invocation:
     def clip_prologue_frames(self):
         """Frames whose frame constants render_clip's prologue evaluated (1 per call where they do not read t or frame)."""
         return lib().mmhip_clip_prologue_frames(self._h)
+
+    def clip_native_batches(self):
+        """Batches of render_clip whose gaussian_blur calls ran batched over the frames."""
+        return lib().mmhip_clip_native_batches(self._h)
+
+    def clip_native_blurs(self):
+        """Blurs computed in those batches (frames with equal arguments share one)."""
+        return lib().mmhip_clip_native_blurs(self._h)
+
+    def clip_native_direct_frames(self):
+        """Frames of those batches whose bytes a blur wrote itself (no pixel launch)."""
+        return lib().mmhip_clip_native_direct_frames(self._h)
 
     def render_supersampled(self, out_ptr, t=0.0, frame=0, bpp=4, stream=0):
         """The CLI's -o (supersampling) for the whole frame, into device memory at out_ptr."""

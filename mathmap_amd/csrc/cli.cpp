@@ -55,6 +55,10 @@ void usage() {
            "                              NUM-1 are read from the files so named (all of\n"
            "                              one size) and in(xy, n) reads frame n; with -F,\n"
            "                              in(xy, frame) processes a clip frame by frame\n"
+           "      --native-input-frame=MODE  which frame of an --input-frames sequence\n"
+           "                              gaussian_blur, render() and convolve read:\n"
+           "                              zero (default, like the reference) or current\n"
+           "                              (the frame being rendered)\n"
            "      --batch-frames=NUM      with -F, render NUM frames per batched GPU\n"
            "                              launch (default 1: frame by frame); the files\n"
            "                              are the same\n"
@@ -204,7 +208,8 @@ std::string frame_file(const std::string &pattern, int frame) {
 
 enum {
     OPT_VERSION = 256, OPT_HELP, OPT_HTMLDOC, OPT_BENCH_NO_OUTPUT, OPT_BENCH_ONLY_COMPILE,
-    OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE, OPT_INPUT_FRAMES, OPT_BATCH_FRAMES
+    OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE, OPT_INPUT_FRAMES, OPT_BATCH_FRAMES,
+    OPT_NATIVE_INPUT_FRAME
 };
 
 int main(int argc, char **argv) {
@@ -212,6 +217,7 @@ int main(int argc, char **argv) {
     bool have_script = false, htmldoc = false, bench_no_output = false, bench_no_backend = false;
     int antialiasing = 0, supersampling = 0, img_width = 0, img_height = 0, size_is_set = 0;
     int bench_render_count = 1, num_frames = 1, input_frames = 0, gauss_mode = MMHIP_GAUSS_EXACT, batch_frames = 1;
+    int native_input_frame = MMHIP_NATIVE_FRAME_ZERO;
     const char *generator = nullptr;
     std::vector<Define> defines;
     static struct option long_options[] = {
@@ -226,6 +232,7 @@ int main(int argc, char **argv) {
         {"bench-render-count", required_argument, 0, OPT_BENCH_RENDER_COUNT},
         {"frames", required_argument, 0, 'F'}, {"gauss-mode", required_argument, 0, OPT_GAUSS_MODE},
         {"input-frames", required_argument, 0, OPT_INPUT_FRAMES}, {"batch-frames", required_argument, 0, OPT_BATCH_FRAMES},
+        {"native-input-frame", required_argument, 0, OPT_NATIVE_INPUT_FRAME},
         {0, 0, 0, 0}};
     for (;;) {
         int idx;
@@ -274,6 +281,11 @@ int main(int argc, char **argv) {
                 if (!strcmp(optarg, "exact")) gauss_mode = MMHIP_GAUSS_EXACT;
                 else if (!strcmp(optarg, "tolerance")) gauss_mode = MMHIP_GAUSS_TOLERANCE;
                 else { fprintf(stderr, "Error: --gauss-mode takes exact or tolerance.\n"); return 1; }
+                break;
+            case OPT_NATIVE_INPUT_FRAME:
+                if (!strcmp(optarg, "zero")) native_input_frame = MMHIP_NATIVE_FRAME_ZERO;
+                else if (!strcmp(optarg, "current")) native_input_frame = MMHIP_NATIVE_FRAME_CURRENT;
+                else { fprintf(stderr, "Error: --native-input-frame takes zero or current.\n"); return 1; }
                 break;
             case OPT_INPUT_FRAMES: {
                 char *end = nullptr;
@@ -356,6 +368,7 @@ int main(int argc, char **argv) {
 
     mmhip_invocation *inv = mmhip_invoke(flt, img_width, img_height);
     if (!inv) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
+    if (mmhip_set_native_input_frame(inv, native_input_frame) != 0) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
     for (int i = 0; i < nuv; ++i) {
         mmhip_userval_info info;
         mmhip_filter_userval_info(flt, i, &info);

@@ -1002,7 +1002,7 @@ MM_DEV mm_image mm_native_result_in_loop(const mm_args &A, int &n, int sites) {
                    "    if (gid != 0) return;\n  }\n";
         };
         emit(KERNEL + "mm_prologue(mm_args A, char *XY) {\n" + tables(""),
-             clip_prelude() + KERNEL + "mm_prologue_clip(mm_args A, char *XY, const mm_clip C) {\n  MM_CLIP_ENTRY\n" + tables("fi == 0 && "));
+             (ks.natives.empty() ? clip_prelude() : clip_prelude_natives()) + KERNEL + "mm_prologue_clip(mm_args A, char *XY, const mm_clip C) {\n  MM_CLIP_ENTRY\n" + tables("fi == 0 && "));
         out << "  MM_INTERNALS\n";
         if (!(fn_root ? fn_root : &code)->functions.empty()) out << "  const int col = 0, rl = 0; unsigned mm_rand_ctr = 0; (void)col; (void)rl; (void)mm_rand_ctr;\n";
         decls(pro_defs, "  ", true);
@@ -1214,6 +1214,21 @@ const char *clip_prelude() {
            "  A.out = (char *)A.out + (long long)fi * C.frame_stride; \\\n"
            "  XY += (long long)fi * C.xy_stride; \\\n"
            "  if (A.rowtab) A.rowtab += (long long)fi * C.rowtab_stride;\n";
+}
+
+// The same for a filter that calls native filters: every frame of a batch has an image table of its own (its native
+// results), images_stride entries behind the previous frame's (0 while all frames read one table: the prologue).  A text
+// of its own, so that the clip text of every other filter stays what it was.
+const char *clip_prelude_natives() {
+    return "struct mm_clip_frame { float t; int frame; };\n"
+           "struct mm_clip { const mm_clip_frame *frames; long long frame_stride; int xy_stride; int rowtab_stride; int nwg; int images_stride; };\n"
+           "#define MM_CLIP_ENTRY \\\n"
+           "  const int fi = blockIdx.y; \\\n"
+           "  { const mm_clip_frame mm_cf = C.frames[fi]; A.t = mm_cf.t; A.frame = mm_cf.frame; } \\\n"
+           "  A.out = (char *)A.out + (long long)fi * C.frame_stride; \\\n"
+           "  XY += (long long)fi * C.xy_stride; \\\n"
+           "  if (A.rowtab) A.rowtab += (long long)fi * C.rowtab_stride; \\\n"
+           "  A.images += (long long)fi * C.images_stride;\n";
 }
 
 void clip_kernel_source(const KernelSource &ks, std::string *source, std::string *key) {

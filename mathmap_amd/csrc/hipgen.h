@@ -62,6 +62,7 @@ KernelSource generate_hip(FilterCode &code, const KernelOptions &opt, FilterCode
 // the clip variant's text and its cache key, built from `ks.source` on demand
 void clip_kernel_source(const KernelSource &ks, std::string *source, std::string *key);
 const char *clip_prelude();
+const char *clip_prelude_natives();   // ... of a filter with native-filter calls: mm_clip.images_stride
 const char *device_prelude();
 const char *device_noise_prelude();   // mm_noise_device.h
 const char *device_fastmath_prelude();   // mm_fastmath.h + tables

@@ -77,6 +77,42 @@ int run_native_filter(const std::string &func, const HNativeRec &rec, const std:
                       std::string *err, int *row_lo, int *row_hi,    // in: rows wanted, out: rows filled
                       NativeDirectOut *direct = nullptr);
 
+// ---- gaussian_blur over the frames of a clip (mmhip_render_clip) ----
+// One computation of a batch: a gaussian_blur call whose image argument is either a bound drawable of the render size
+// under the identity mapping or an earlier computation's float map, and whose deviations are at least half a pixel
+// (the recursive chain, exact).  gaussian_blur_batchable says whether a recorded call is one, by the decisions of the
+// single-frame chain itself; `ckpt_bytes` / `map_bytes` (either may be null) receive what one job needs of each.
+bool gaussian_blur_batchable(const HNativeRec &rec, const HImageDesc *images, int num_images, int render_w, int render_h,
+                             const NativeEnv &env, size_t *ckpt_bytes, size_t *map_bytes);
+void gaussian_blur_batch_job_bytes(int render_w, int render_h, size_t *ckpt_bytes, size_t *map_bytes);
+struct GaussClipJob {
+    HNativeRec rec;                 // the call as the prologue recorded it
+    const HImageDesc *images;       // the image table of the job's frame (rec's image argument indexes it)
+    int num_images;
+    double *ckpt;                   // ckpt_bytes of its own
+    float *mapT;                    // map_bytes of its own: the first pass's transposed result
+    float *out_map;                 // map_bytes: the result (unused where the launch writes no map)
+    unsigned char *pack_out;        // the first byte of the job's band of RGBA8 pixels (direct output), or null
+};
+// What all jobs of one gaussian_blur_batch share.  `direct`: rows, columns and row stride of the bands the second pass
+// packs (its `out` is not read: every job has its own pack_out); null = no job packs.
+struct GaussClipLaunch {
+    int render_w = 0, render_h = 0;
+    const NativeDirectOut *direct = nullptr;
+    bool write_map = true;          // false: only the packed pixels leave the second pass
+};
+// Device-table bytes gaussian_blur_batch needs for `jobs` jobs.
+size_t gaussian_blur_batch_table_bytes(size_t jobs);
+// Fills `host_table` (gaussian_blur_batch_table_bytes) for the jobs; `device_table` is where the caller is going to copy
+// it before gaussian_blur_batch_launch runs.  Returns the groups to launch (jobs of one source type each) in `groups`.
+struct GaussClipGroup { bool drawable; unsigned jobs; const void *vertical, *horizontal; unsigned pitch; };
+int gaussian_blur_batch_tables(const std::vector<GaussClipJob> &jobs, const GaussClipLaunch &launch, const NativeEnv &env,
+                               char *host_table, const char *device_table, std::vector<GaussClipGroup> *groups, std::string *err);
+// Four launches per group (iir_causal_vertical_clip, iir_anticausal_vertical_clip, iir_causal_horizontal_clip,
+// iir_anticausal_horizontal_clip), timed through ws.timed_launch.
+int gaussian_blur_batch_launch(const std::vector<GaussClipGroup> &groups, const GaussClipLaunch &launch, NativeWorkspace &ws,
+                               hipStream_t s, std::string *err);
+
 // native_fft.hip: convolve / half_convolve / visualize_fft (native-filters/convolve.c)
 int fft_native_filter(const std::string &func, const HNativeRec &rec, const std::vector<HImageDesc> &images, int render_w,
                       int render_h, float *out_map, NativeWorkspace &ws, hipStream_t stream, std::string *err);

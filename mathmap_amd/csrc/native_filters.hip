@@ -700,6 +700,72 @@ __global__ void __launch_bounds__(256) k_iir_anticausal_T(Src in, const double *
     anticausal_sweep<Step>(in.for_lane(Lc), ckpt, (unsigned)stride, (unsigned)Lc, g.n, s0, s1, k1, c, tile[wave], lane, line0, g.lines, outT, po, active);
 }
 
+// ---- the sweeps over the jobs of a clip batch --------------------------------------------------
+// Frames of a clip are independent: grid row blockIdx.y is one blur of one frame (a job), and a 1920x1080 pass that
+// alone offers 30 (vertical) or 17 (horizontal) workgroups to 256 CUs fills them from nine frames on.  What differs
+// between the jobs of a launch -- source, checkpoints, outputs, coefficients (sigma may follow t) -- is an entry of a
+// device table; everything else stays a by-value argument.  The entry is wave-uniform and copied into locals before
+// any store, so it arrives by scalar loads like the kernel arguments of the single-frame kernels; the sweeps are those
+// kernels' own, one segment per line: the same operations in the same order, the same values bit for bit.
+struct IirClipJob { const void *src; double *ckpt; float *outT; unsigned char *pack_out; IirCoef c; };
+
+// A pointer read from the job table is a generic one to the compiler where the single-frame kernels' pointer arguments
+// are known to be global: generic (flat) loads and stores are counted on two wait counters and may complete out of order,
+// so the sweeps' prefetch pipeline would wait for all of them at every block.  The table holds device-memory pointers
+// only: say so (through an integer, a cast pair the compiler folds away again).
+template <class T> __device__ __forceinline__ T *device_memory(T *p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (T *)(__attribute__((address_space(1))) T *)(uintptr_t)p;
+#else
+    return p;
+#endif
+}
+
+template <class Src> __device__ __forceinline__ Src clip_source(const void *p, unsigned pitch);
+template <> __device__ __forceinline__ MapSrc clip_source<MapSrc>(const void *p, unsigned pitch) { return MapSrc{(const float *)p, pitch, 0u}; }
+template <> __device__ __forceinline__ FiniteMapSrc clip_source<FiniteMapSrc>(const void *p, unsigned pitch) { return FiniteMapSrc{(const float *)p, pitch, 0u}; }
+template <> __device__ __forceinline__ DrawableSrc clip_source<DrawableSrc>(const void *p, unsigned pitch) { return DrawableSrc{(const uint32_t *)p, pitch, 0u, 0}; }
+
+// pitch: MapSrc's stride (lines * 4 floats) or DrawableSrc's source width in pixels
+template <class Src, class Step = ExactStep>
+__global__ void __launch_bounds__(256) k_iir_causal_clip(const IirClipJob *__restrict__ jobs, unsigned pitch, LineArgs g) {
+    const IirClipJob *__restrict__ job = jobs + blockIdx.y;
+    const void *const src = device_memory(job->src);
+    double *const ckpt = device_memory(job->ckpt);
+    const IirCoef c = job->c;
+    // (segment arithmetic as in k_iir_causal: the host passes one segment, so sgi is 0 -- written out as constants the
+    // sweep compiles to another code shape that takes 256 registers instead of 168)
+    const unsigned sgi = blockIdx.x / g.lane_blocks, lb = blockIdx.x % g.lane_blocks;
+    const long L = (long)lb * 256 + threadIdx.x;
+    const long stride = (long)g.lines * 4;
+    if (L >= stride) return;
+    const int s0 = (int)sgi * g.seg, s1 = min(g.n, s0 + g.seg), k0 = max(0, s0 - g.halo);
+    causal_sweep<Step>(clip_source<Src>(src, pitch).for_lane(L), ckpt, (unsigned)stride, (unsigned)L, k0, s0, s1, c);
+}
+
+// po.out is the job's own pack_out (null: this job packs nothing); the argument's is not read
+template <class Src, class Step = ExactStep>
+__global__ void __launch_bounds__(256) k_iir_anticausal_T_clip(const IirClipJob *__restrict__ jobs, unsigned pitch, LineArgs g, PackOut po) {
+    __shared__ float tile[4][16 * (IIR_U * 4 + 4)];
+    const IirClipJob *__restrict__ job = jobs + blockIdx.y;
+    const void *const src = device_memory(job->src);
+    const double *const ckpt = device_memory(job->ckpt);
+    float *const outT = device_memory(job->outT);
+    unsigned char *const pack_out = device_memory(job->pack_out);
+    const IirCoef c = job->c;
+    po.out = pack_out;
+    const unsigned sgi = blockIdx.x / g.lane_blocks, lb = blockIdx.x % g.lane_blocks;      // sgi is 0: see k_iir_causal_clip
+    const long L = (long)lb * 256 + threadIdx.x;
+    const long stride = (long)g.lines * 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long line0 = ((long)lb * 256 + (long)wave * 64) >> 2;
+    const bool active = L < stride;
+    const long Lc = active ? L : 0;      // as in k_iir_anticausal_T
+    const int s0 = (int)sgi * g.seg, s1 = min(g.n, s0 + g.seg), k1 = s1 < g.n ? min(g.n, s1 + g.halo) : g.n;
+    anticausal_sweep<Step>(clip_source<Src>(src, pitch).for_lane(Lc), ckpt, (unsigned)stride, (unsigned)Lc, g.n, s0, s1, k1, c, tile[wave], lane, line0,
+                           g.lines, outT, po, active);
+}
+
 // How to split lines of n steps, `lines` of them, for a recurrence of standard deviation sigma.
 // Off by default -- one segment, every value identical to the reference's: a warmed-up segment start
 // agrees with the full sweep only to the recurrence's own rounding-noise floor (~1e-14 relative in
@@ -894,15 +960,36 @@ int gauss_rle(float *map, float *tmp, int w, int h, float hs, float vs, NativeWo
     return 0;
 }
 
-int gaussian_blur(const HNativeRec &rec, const std::vector<HImageDesc> &images, int rw, int rh, float *out_map,
-                  NativeWorkspace &ws, hipStream_t s, std::string *err, int *rows_lo, int *rows_hi, NativeDirectOut *direct) {
-    const int row_lo = *rows_lo, row_hi = *rows_hi;
-    *rows_lo = 0;             // paths that fill the whole map leave it so; the windowed IIR path narrows it
-    *rows_hi = rh;
+// What gaussian_blur decides from a call's arguments before anything is launched: the one place the single-frame chain
+// and the clip batches (gaussian_blur_batch) take it from, so that the two cannot drift.
+struct GaussPlan {
+    const HImageDesc *in = nullptr;     // the image argument
+    int w = 0, h = 0;                   // of the result (and of every intermediate)
+    float hs = 0.f, vs = 0.f;           // standard deviations in pixels (gauss.c:659-660)
+    bool fir = false;                   // gauss.c:662-665: a deviation below half a pixel takes the FIR path
+    bool identity = false;              // a drawable whose render_image mapping is the identity: the first pass reads it in place
+    size_t ckpt_bytes = 0;              // the sweeps' checkpoints, the larger of the two passes
+    size_t scratch_bytes = 0;           // ... with what the FIR path keeps there, rounded
+    size_t map_bytes = 0;               // one float4 map
+};
+
+// 4 doubles per line and channel every IIR_U steps, the larger of the two passes
+size_t checkpoint_bytes(int w, int h) {
+    const size_t ck_v = (size_t)((h + IIR_U - 1) / IIR_U) * 4 * ((size_t)w * 4) * sizeof(double);
+    const size_t ck_h = (size_t)((w + IIR_U - 1) / IIR_U) * 4 * ((size_t)h * 4) * sizeof(double);
+    return std::max(ck_v, ck_h);
+}
+
+// the scan kernels index a block of rows with 32-bit element offsets (MapSrc::at)
+bool scan_offsets_fit(int w, int hn) { return (long)std::max(w, hn) * 4 * 20 * 8 < (1L << 32); }
+
+int plan_gaussian_blur(const HNativeRec &rec, const HImageDesc *images, int num_images, int rw, int rh, const NativeEnv &env,
+                       GaussPlan *p, std::string *err) {
     const HImage &img = rec.args[0].img;
-    float hdev = rec.args[1].f, vdev = rec.args[2].f;
-    if (img.idx < 0 || img.idx >= (int)images.size()) { *err = "gaussian_blur: input is not a bitmap image"; return -1; }
+    const float hdev = rec.args[1].f, vdev = rec.args[2].f;
+    if (img.idx < 0 || img.idx >= num_images) { *err = "gaussian_blur: input is not a bitmap image"; return -1; }
     const HImageDesc &in = images[img.idx];
+    p->in = &in;
     int w = rw, h = rh;
     if (in.kind == IMG_FLOATMAP) {
         w = in.w;
@@ -912,17 +999,58 @@ int gaussian_blur(const HNativeRec &rec, const std::vector<HImageDesc> &images, 
         *err = "gaussian_blur: input image is not bound";
         return -1;
     }
+    p->w = w;
+    p->h = h;
     // gauss.c:659-660 (float products, fabs)
     const float ax = (float)((float)(w - 1) / 2.0);
     float ay = (float)((float)(h - 1) / 2.0);
     ay *= -1.0f;
-    float hs = (float)fabs(hdev * ax), vs = (float)fabs(vdev * ay);
+    p->hs = (float)fabs(hdev * ax);
+    p->vs = (float)fabs(vdev * ay);
     // workspace: the scans' checkpoints (4 doubles per line*channel every IIR_U steps, the larger of
     // the two passes; also covers the FIR path's flags and taps) followed by the intermediate map
-    const size_t ck_v = (size_t)((h + IIR_U - 1) / IIR_U) * 4 * ((size_t)w * 4) * sizeof(double);
-    const size_t ck_h = (size_t)((w + IIR_U - 1) / IIR_U) * 4 * ((size_t)h * 4) * sizeof(double);
-    const size_t scratch_bytes = ((std::max(ck_v, ck_h) + (size_t)std::max(w, h) * 64 + (size_t)(w + h) * sizeof(int) + 65536) + 255) & ~(size_t)255;
-    const size_t map_bytes = (size_t)w * h * 4 * sizeof(float);
+    p->ckpt_bytes = checkpoint_bytes(w, h);
+    p->scratch_bytes = ((p->ckpt_bytes + (size_t)std::max(w, h) * 64 + (size_t)(w + h) * sizeof(int) + 65536) + 255) & ~(size_t)255;
+    p->map_bytes = (size_t)w * h * 4 * sizeof(float);
+    p->fir = p->hs < 0.5f || p->vs < 0.5f;     // gauss.c:662-665
+    // Does render_image map output pixel (x, y) to texel (x, y)?  Evaluated on the host with the
+    // operations of k_render_drawable (IEEE float: same results), once per row and column.
+    bool identity = !p->fir && in.kind == IMG_DRAWABLE && in.w == w && in.h == h;
+    if (identity) {
+        const float ax = (float)((float)(w - 1) / 2.0), bx = ax;
+        const float by = (float)((float)(h - 1) / 2.0);
+        const float ay2 = (float)(by * -1.0);
+        for (int i = 0; i < w && identity; ++i) {
+            float x = ((float)i - bx) / ax;
+            if (img.resized) x *= img.xf;
+            x = (x + in.middle_x) * in.scale_x;
+            if (!env.supersampling) x += 0.5;
+            identity = (int)floor((double)x) == i;
+        }
+        for (int i = 0; i < h && identity; ++i) {
+            float y = ((float)i - by) / ay2;
+            if (img.resized) y *= img.yf;
+            y = -((y - in.middle_y) * in.scale_y);
+            if (!env.supersampling) y += 0.5;
+            identity = (int)floor((double)y) == i;
+        }
+    }
+    p->identity = identity;
+    return 0;
+}
+
+int gaussian_blur(const HNativeRec &rec, const std::vector<HImageDesc> &images, int rw, int rh, float *out_map,
+                  NativeWorkspace &ws, hipStream_t s, std::string *err, int *rows_lo, int *rows_hi, NativeDirectOut *direct) {
+    const int row_lo = *rows_lo, row_hi = *rows_hi;
+    *rows_lo = 0;             // paths that fill the whole map leave it so; the windowed IIR path narrows it
+    *rows_hi = rh;
+    GaussPlan plan;
+    if (plan_gaussian_blur(rec, images.data(), (int)images.size(), rw, rh, ws.env, &plan, err) != 0) return -1;
+    const HImage &img = rec.args[0].img;
+    const HImageDesc &in = *plan.in;
+    const int w = plan.w, h = plan.h;
+    const float hs = plan.hs, vs = plan.vs;
+    const size_t scratch_bytes = plan.scratch_bytes, map_bytes = plan.map_bytes;
     char *wsp = (char *)ws.reserve(scratch_bytes + map_bytes);
     if (!wsp) { *err = "gaussian_blur: out of device memory for the scan workspace"; return -1; }
     double *scratch = (double *)wsp;
@@ -939,33 +1067,12 @@ int gaussian_blur(const HNativeRec &rec, const std::vector<HImageDesc> &images, 
         }
         return 0;
     };
-    if (hs < 0.5f || vs < 0.5f) {     // gauss.c:662-665
+    if (plan.fir) {
         if (render_input() != 0) return -1;
         return gauss_rle(out_map, mapT, w, h, hs, vs, ws, wsp, s, err);
     }
     IirCoef c;
-    // Does render_image map output pixel (x, y) to texel (x, y)?  Evaluated on the host with the
-    // operations of k_render_drawable (IEEE float: same results), once per row and column.
-    bool identity = in.kind == IMG_DRAWABLE && in.w == w && in.h == h;
-    if (identity) {
-        const float ax = (float)((float)(w - 1) / 2.0), bx = ax;
-        const float by = (float)((float)(h - 1) / 2.0);
-        const float ay2 = (float)(by * -1.0);
-        for (int i = 0; i < w && identity; ++i) {
-            float x = ((float)i - bx) / ax;
-            if (img.resized) x *= img.xf;
-            x = (x + in.middle_x) * in.scale_x;
-            if (!ws.env.supersampling) x += 0.5;
-            identity = (int)floor((double)x) == i;
-        }
-        for (int i = 0; i < h && identity; ++i) {
-            float y = ((float)i - by) / ay2;
-            if (img.resized) y *= img.yf;
-            y = -((y - in.middle_y) * in.scale_y);
-            if (!ws.env.supersampling) y += 0.5;
-            identity = (int)floor((double)y) == i;
-        }
-    }
+    const bool identity = plan.identity;
     if (in.kind == IMG_DRAWABLE && !identity && render_input() != 0) return -1;
     // Row window: a caller that only reads rows [row_lo, row_hi) (one GPU's stripe of a striped
     // frame; inputs are replicated on every GPU, so the halo is computed locally, not exchanged)
@@ -983,8 +1090,7 @@ int gaussian_blur(const HNativeRec &rec, const std::vector<HImageDesc> &images, 
         if (y1 <= y0) return 0;
     }
     const int hn = y1 - y0;
-    // the scan kernels index a block of rows with 32-bit element offsets (MapSrc::at)
-    if ((long)std::max(w, hn) * 4 * 20 * 8 >= (1L << 32)) { *err = "gaussian_blur: frame too large for the scan kernels"; return -1; }
+    if (!scan_offsets_fit(w, hn)) { *err = "gaussian_blur: frame too large for the scan kernels"; return -1; }
     const bool pack = direct && direct->out && direct->first_row >= y0 && direct->first_row + direct->num_rows <= y1;
     // The tolerance chain (mmhip_options::gauss_mode, include/mmhip.h) where nothing but the RGBA8 pixels of a whole frame
     // leaves it: the runtime packs them from this call and keeps no map (skip_map), and the input is a drawable (bytes / 255,
@@ -1035,6 +1141,94 @@ int gaussian_blur(const HNativeRec &rec, const std::vector<HImageDesc> &images, 
 }
 
 }  // namespace
+
+void gaussian_blur_batch_job_bytes(int render_w, int render_h, size_t *ckpt_bytes, size_t *map_bytes) {
+    *ckpt_bytes = (checkpoint_bytes(render_w, render_h) + 255) & ~(size_t)255;
+    *map_bytes = (size_t)render_w * render_h * 4 * sizeof(float);
+}
+
+bool gaussian_blur_batchable(const HNativeRec &rec, const HImageDesc *images, int num_images, int render_w, int render_h,
+                             const NativeEnv &env, size_t *ckpt_bytes, size_t *map_bytes) {
+    GaussPlan p;
+    std::string err;
+    if (rec.nargs < 3 || rec.args[0].kind != 2 || plan_gaussian_blur(rec, images, num_images, render_w, render_h, env, &p, &err) != 0) return false;
+    if (ckpt_bytes) *ckpt_bytes = (p.ckpt_bytes + 255) & ~(size_t)255;
+    if (map_bytes) *map_bytes = p.map_bytes;
+    return !p.fir && (p.in->kind == IMG_FLOATMAP || p.identity) && scan_offsets_fit(p.w, p.h);
+}
+
+size_t gaussian_blur_batch_table_bytes(size_t jobs) { return 2 * jobs * sizeof(IirClipJob); }
+
+int gaussian_blur_batch_tables(const std::vector<GaussClipJob> &jobs, const GaussClipLaunch &launch, const NativeEnv &env,
+                               char *host_table, const char *device_table, std::vector<GaussClipGroup> *groups, std::string *err) {
+    groups->clear();
+    IirClipJob *host = (IirClipJob *)host_table;
+    const IirClipJob *dev = (const IirClipJob *)device_table;
+    size_t at = 0;
+    for (int drawable = 0; drawable < 2; ++drawable) {      // float-map sources, then drawables: one source type per launch
+        const size_t first = at;
+        std::vector<const GaussClipJob *> mine;
+        unsigned pitch = 0;
+        for (const GaussClipJob &j : jobs) {
+            GaussPlan p;
+            if (plan_gaussian_blur(j.rec, j.images, j.num_images, launch.render_w, launch.render_h, env, &p, err) != 0) return -1;
+            if (p.fir || !(p.in->kind == IMG_FLOATMAP || p.identity) || !scan_offsets_fit(p.w, p.h)) {
+                *err = "gaussian_blur_batch: internal: a job the batch cannot run";
+                return -1;
+            }
+            if ((p.in->kind == IMG_DRAWABLE) != (drawable != 0)) continue;
+            // (a drawable's pitch is its width, the render width under the identity mapping: one value for the group)
+            pitch = drawable ? (unsigned)p.in->w : (unsigned)p.w * 4u;
+            IirClipJob v{p.in->data, j.ckpt, j.mapT, nullptr, {}};
+            find_iir_constants(v.c, p.vs);
+            host[at++] = v;
+            mine.push_back(&j);
+        }
+        if (mine.empty()) continue;
+        const size_t second = at;
+        for (const GaussClipJob *j : mine) {
+            GaussPlan p;
+            if (plan_gaussian_blur(j->rec, j->images, j->num_images, launch.render_w, launch.render_h, env, &p, err) != 0) return -1;
+            IirClipJob h{j->mapT, j->ckpt, j->out_map, launch.direct ? j->pack_out : nullptr, {}};
+            find_iir_constants(h.c, p.hs);
+            host[at++] = h;
+        }
+        groups->push_back(GaussClipGroup{drawable != 0, (unsigned)mine.size(), dev + first, dev + second, pitch});
+    }
+    return 0;
+}
+
+int gaussian_blur_batch_launch(const std::vector<GaussClipGroup> &groups, const GaussClipLaunch &launch, NativeWorkspace &ws,
+                               hipStream_t s, std::string *err) {
+    const int w = launch.render_w, h = launch.render_h;
+    // one segment per line (the exact chain without MMHIP_GAUSS_SEGMENTS): vertical pass lines = columns, then lines = rows
+    const LineArgs gv = split_lines(h, w, 0, 0, 1), gh = split_lines(w, h, 0, 0, 1);
+    const PackOut none{nullptr, 0, 0, 0, 0, 0, 1};
+    PackOut po = none;
+    if (launch.direct) {
+        const NativeDirectOut &d = *launch.direct;
+        po = PackOut{nullptr, (long)d.row_stride, d.first_row, d.first_row + d.num_rows, d.region_x, d.region_x + d.region_w, launch.write_map ? 1 : 0};
+    }
+    for (const GaussClipGroup &g : groups) {
+        if (g.jobs < 1 || g.jobs > 65535) { *err = "gaussian_blur_batch: a launch takes 1 to 65535 jobs"; return -1; }
+        const IirClipJob *jv = (const IirClipJob *)g.vertical, *jh = (const IirClipJob *)g.horizontal;
+        const dim3 grid_v(gv.lane_blocks, g.jobs), grid_h(gh.lane_blocks, g.jobs);
+        const unsigned pitch_h = (unsigned)h * 4u;      // of the transposed intermediate: its lines are the frame's rows
+        if (g.drawable) {      // the first pass reads bytes: its output is finite
+            ws.timed_launch("iir_causal_vertical_clip", s, [&] { k_iir_causal_clip<DrawableSrc><<<grid_v, 256, 0, s>>>(jv, g.pitch, gv); });
+            ws.timed_launch("iir_anticausal_vertical_clip", s, [&] { k_iir_anticausal_T_clip<DrawableSrc><<<grid_v, 256, 0, s>>>(jv, g.pitch, gv, none); });
+            ws.timed_launch("iir_causal_horizontal_clip", s, [&] { k_iir_causal_clip<FiniteMapSrc><<<grid_h, 256, 0, s>>>(jh, pitch_h, gh); });
+            ws.timed_launch("iir_anticausal_horizontal_clip", s, [&] { k_iir_anticausal_T_clip<FiniteMapSrc><<<grid_h, 256, 0, s>>>(jh, pitch_h, gh, po); });
+        } else {
+            ws.timed_launch("iir_causal_vertical_clip", s, [&] { k_iir_causal_clip<MapSrc><<<grid_v, 256, 0, s>>>(jv, g.pitch, gv); });
+            ws.timed_launch("iir_anticausal_vertical_clip", s, [&] { k_iir_anticausal_T_clip<MapSrc><<<grid_v, 256, 0, s>>>(jv, g.pitch, gv, none); });
+            ws.timed_launch("iir_causal_horizontal_clip", s, [&] { k_iir_causal_clip<MapSrc><<<grid_h, 256, 0, s>>>(jh, pitch_h, gh); });
+            ws.timed_launch("iir_anticausal_horizontal_clip", s, [&] { k_iir_anticausal_T_clip<MapSrc><<<grid_h, 256, 0, s>>>(jh, pitch_h, gh, po); });
+        }
+    }
+    if (hipGetLastError() != hipSuccess) { *err = "gaussian_blur_batch: kernel launch failed"; return -1; }
+    return 0;
+}
 
 void launch_render_drawable(const HImageDesc &in, const HImage &img, const NativeEnv &env, float *dst, int w, int h, hipStream_t s) {
     render_drawable_impl(in, img, env, dst, w, h, s);

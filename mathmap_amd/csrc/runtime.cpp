@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <map>
 #include <memory>
 #include <sstream>
 #include <string>
@@ -626,6 +627,14 @@ int mmhip_set_native_row_margin(mmhip_invocation *inv, int margin) {
     return 0;
 }
 
+int mmhip_set_native_input_frame(mmhip_invocation *inv, int mode) {
+    if (mode != MMHIP_NATIVE_FRAME_ZERO && mode != MMHIP_NATIVE_FRAME_CURRENT)
+        return fail("native input frame: mode " + std::to_string(mode) + " is neither MMHIP_NATIVE_FRAME_ZERO (0) nor MMHIP_NATIVE_FRAME_CURRENT (1)");
+    if (inv->native_input_frame != mode) ++inv->input_generation;      // what the native results were computed from changes
+    inv->native_input_frame = mode;
+    return 0;
+}
+
 int mmhip_set_edge_colors(mmhip_invocation *inv, uint32_t cx, uint32_t cy) {
     inv->edge_color_x = cx;
     inv->edge_color_y = cy;
@@ -850,18 +859,18 @@ static int grow_launch_buffers(LaunchBuffers &b, const KernelSource &ks, int reg
 // were made: entry k of ks.natives (a call site outside loops, or the n-th dynamic entry of the in-loop sites) and its
 // record.  The record's `pad' is the call's number within the frame (mm_native_call in hipgen.cpp).
 struct RecordedCall { size_t k; HNativeRec rec; const std::string *func; };
-static int recorded_calls(const KernelSource &ks, const std::vector<char> &host, std::vector<RecordedCall> *calls) {
+static int recorded_calls(const KernelSource &ks, const char *host, std::vector<RecordedCall> *calls) {
     calls->clear();
     if (ks.natives.empty()) return 0;
     int ctr[4];
-    memcpy(ctr, host.data() + ks.native_ctr_offset, sizeof ctr);
+    memcpy(ctr, host + ks.native_ctr_offset, sizeof ctr);
     if (ctr[2])
         return fail("native filters are called more than " + std::to_string((int)MM_NATIVE_DYN_CALLS) +
                     " times from inside a loop of the frame-constant code: not supported");
     for (size_t k = 0; k < ks.natives.size(); ++k) {
         RecordedCall c;
         c.k = k;
-        memcpy(&c.rec, host.data() + ks.natives[k].record_offset, sizeof c.rec);
+        memcpy(&c.rec, host + ks.natives[k].record_offset, sizeof c.rec);
         if (!c.rec.executed) continue;
         if (c.rec.index < 0 || c.rec.index >= ks.native_sites) return fail("internal: native call record names no call site");
         c.func = &ks.natives[c.rec.index].func;
@@ -948,7 +957,7 @@ static int render_closure(mmhip_invocation *inv, mmhip_filter *f, int cid, const
         HIP_TRY(hipMemcpyAsync(host.data(), xy, host.size(), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         std::vector<RecordedCall> calls;
-        if (recorded_calls(ck.ks, host, &calls) != 0) return -1;
+        if (recorded_calls(ck.ks, host.data(), &calls) != 0) return -1;
         std::vector<int> alias(ck.ks.natives.size(), -1);
         for (const RecordedCall &call : calls) {
             const size_t k = call.k;
@@ -988,9 +997,23 @@ static int render_closure(mmhip_invocation *inv, mmhip_filter *f, int cid, const
 // lrintf(ax x + bx) (builtins.c:247-265) evaluated here for each column and row with the
 // coordinates the prologue just computed -- the native filter may write the RGBA8 pixels itself.
 // Waits for `s', and with it for what the caller queued there before (the frame constants' read-back).
+static bool direct_output_wanted(const mmhip_filter *f, const HArgs &a) {
+    return f->ks.direct_native >= 0 && !a.floatmap && a.output_bpp == 4 && (a.row_stride & 3) == 0 && ((uintptr_t)a.out & 3) == 0 &&
+           !getenv("MMHIP_NO_DIRECT_NATIVE");
+}
+
+// xt, yt: the launch's coordinate tables as the prologue wrote them
+static bool samples_own_pixels(const HArgs &a, const std::vector<float> &xt, const std::vector<float> &yt) {
+    const HImageDesc m = floatmap_desc(nullptr, a.render_width, a.render_height);
+    for (int c = 0; c < a.region_width; ++c)
+        if (lrintf(m.ax * xt[c] + m.bx) != (long)a.region_x + c) return false;
+    for (int r = 0; r < a.num_rows; ++r)
+        if (lrintf(m.ay * yt[r] + m.by) != (long)a.first_row + r) return false;
+    return true;
+}
+
 static int direct_output(const mmhip_filter *f, const HArgs &a, hipStream_t s, NativeDirectOut *direct) {
-    const bool try_direct = f->ks.direct_native >= 0 && !a.floatmap && a.output_bpp == 4 && (a.row_stride & 3) == 0 &&
-                            ((uintptr_t)a.out & 3) == 0 && !getenv("MMHIP_NO_DIRECT_NATIVE");
+    const bool try_direct = direct_output_wanted(f, a);
     std::vector<float> xt, yt;
     if (try_direct) {
         xt.resize(a.region_width);
@@ -1000,11 +1023,7 @@ static int direct_output(const mmhip_filter *f, const HArgs &a, hipStream_t s, N
     }
     HIP_TRY(hipStreamSynchronize(s));
     if (!try_direct) return 0;
-    const HImageDesc m = floatmap_desc(nullptr, a.render_width, a.render_height);
-    for (int c = 0; c < a.region_width; ++c)
-        if (lrintf(m.ax * xt[c] + m.bx) != (long)a.region_x + c) return 0;
-    for (int r = 0; r < a.num_rows; ++r)
-        if (lrintf(m.ay * yt[r] + m.by) != (long)a.first_row + r) return 0;
+    if (!samples_own_pixels(a, xt, yt)) return 0;
     direct->out = a.out;
     direct->row_stride = a.row_stride;
     direct->first_row = a.first_row;
@@ -1037,15 +1056,41 @@ static int render_closure_args(mmhip_invocation *inv, mmhip_filter *f, const HAr
     return 0;
 }
 
+// MMHIP_NATIVE_FRAME_CURRENT: an argument that is a bound sequence (a drawable of more than one frame) is read at the
+// render's frame number -- the call sees a one-frame view of it, in `images_k' (a copy of the image table, made here if
+// the call has none yet).  `frame_key' becomes that frame number: part of what the memo and the direct output's `seen'
+// record compare, so that one frame's result never answers for another's.  A frame the sequence does not have is an error.
+enum { NO_FRAME_KEY = INT32_MIN };
+static int view_sequence_args(const mmhip_invocation *inv, int frame, const std::string &func, const HNativeRec &rec,
+                              std::vector<HImageDesc> &images_k, int *frame_key) {
+    *frame_key = NO_FRAME_KEY;
+    if (inv->native_input_frame != MMHIP_NATIVE_FRAME_CURRENT) return 0;
+    for (int i = 0; i < rec.nargs && i < 4; ++i) {
+        const int idx = rec.args[i].img.idx;
+        if (rec.args[i].kind != 2 || idx < 0 || idx >= inv->native_slot_base) continue;
+        const HImageDesc &d = inv->images[idx];
+        if (d.kind != IMG_DRAWABLE || d.num_frames <= 1) continue;
+        if (frame < 0 || frame >= d.num_frames)
+            return fail((func == "RENDER" ? std::string("render()") : func.rfind("native_filter_", 0) == 0 ? func.substr(14) : func) + ": frame " + std::to_string(frame) + " is outside the input sequence (" + std::to_string(d.num_frames) +
+                        " frames; native input frame mode `current')");
+        if (images_k.empty()) images_k = inv->images;
+        HImageDesc &v = images_k[idx];
+        v.data = (const char *)d.data + (size_t)frame * d.w * d.h * 4;
+        v.num_frames = 1;
+        *frame_key = frame;
+    }
+    return 0;
+}
+
 // memo (native-filters/cache.c:110-147): same arguments on unchanged inputs -> keep the map.  `deps' receives the
 // generations of the native maps among the call's image arguments (cache.c keys on image ids).
-static bool memo_hit(const mmhip_invocation *inv, const NativeEntry &e, const HNativeRec &rec, int want_lo, int want_hi,
+static bool memo_hit(const mmhip_invocation *inv, const NativeEntry &e, const HNativeRec &rec, int frame_key, int want_lo, int want_hi,
                      std::vector<unsigned long long> *deps) {
     for (int i = 0; i < rec.nargs && i < 4; ++i)
         if (rec.args[i].kind == 2 && rec.args[i].img.idx >= inv->native_slot_base &&
             rec.args[i].img.idx < inv->native_slot_base + (int)inv->natives.size())
             deps->push_back(inv->natives[rec.args[i].img.idx - inv->native_slot_base].gen);
-    return e.map && e.memo_gen == inv->input_generation && memcmp(&e.memo, &rec, sizeof rec) == 0 && e.memo_deps == *deps &&
+    return e.map && e.memo_gen == inv->input_generation && e.memo_frame == frame_key && memcmp(&e.memo, &rec, sizeof rec) == 0 && e.memo_deps == *deps &&
            e.rows.first <= want_lo && e.rows.second >= want_hi;
 }
 
@@ -1088,7 +1133,7 @@ static int run_natives(mmhip_invocation *inv, mmhip_filter *f, const HArgs &a, h
                        a.region_height == a.render_height && a.first_row == 0 && a.num_rows == a.render_height;
     bool table_changed = false;
     std::vector<RecordedCall> calls, done;      // done: calls whose maps stand (what a closure's render kernel may refer to)
-    if (recorded_calls(f->ks, host, &calls) != 0) return -1;
+    if (recorded_calls(f->ks, host.data(), &calls) != 0) return -1;
     for (const RecordedCall &call : calls) {
         const size_t k = call.k;
         NativeEntry &e = inv->natives[k];
@@ -1102,8 +1147,11 @@ static int run_natives(mmhip_invocation *inv, mmhip_filter *f, const HArgs &a, h
         }
         std::vector<HImageDesc> images_k;
         if (render_closure_args(inv, f, a, s, done, rec, images_k) != 0) return -1;
+        const bool closure_args = !images_k.empty();      // never memoised (render_closure_args)
+        int frame_key = NO_FRAME_KEY;
+        if (view_sequence_args(inv, a.frame, *call.func, rec, images_k, &frame_key) != 0) return -1;
         std::vector<unsigned long long> deps;
-        if (memo_hit(inv, e, rec, want_lo, want_hi, &deps) && images_k.empty()) {
+        if (memo_hit(inv, e, rec, frame_key, want_lo, want_hi, &deps) && !closure_args) {
             done.push_back(call);
             continue;
         }
@@ -1114,8 +1162,10 @@ static int run_natives(mmhip_invocation *inv, mmhip_filter *f, const HArgs &a, h
         int got_lo = want_lo, got_hi = want_hi;
         NativeDirectOut *dk = (direct.out && (int)k == f->ks.direct_native) ? &direct : nullptr;
         if (dk) {
-            dk->skip_map = whole && !(e.seen_gen == inv->input_generation && e.memo_deps == deps && memcmp(&e.seen, &rec, sizeof rec) == 0);
+            dk->skip_map = whole && !(e.seen_gen == inv->input_generation && e.seen_frame == frame_key && e.memo_deps == deps &&
+                                      memcmp(&e.seen, &rec, sizeof rec) == 0);
             e.seen = rec;
+            e.seen_frame = frame_key;
             e.seen_gen = inv->input_generation;
         }
         if (run_native_filter(*call.func, rec, images_k.empty() ? inv->images : images_k, a.render_width, a.render_height,
@@ -1132,6 +1182,7 @@ static int run_natives(mmhip_invocation *inv, mmhip_filter *f, const HArgs &a, h
         }
         inv->images[inv->native_slot_base + (int)k] = floatmap_desc(e.map.get(), a.render_width, a.render_height);
         e.memo = rec;
+        e.memo_frame = frame_key;
         e.memo_gen = inv->input_generation;
         e.rows = {got_lo, got_hi};
         table_changed = true;
@@ -1356,11 +1407,283 @@ int mmhip_render(mmhip_invocation *inv, int frame, float t, int region_x, int re
 
 long mmhip_clip_batched_launches(mmhip_invocation *inv) { return inv->clip_batched_launches; }
 long mmhip_clip_prologue_frames(mmhip_invocation *inv) { return inv->clip_prologue_frames; }
+long mmhip_clip_native_batches(mmhip_invocation *inv) { return inv->clip_native_batches; }
+long mmhip_clip_native_blurs(mmhip_invocation *inv) { return inv->clip_native_blurs; }
+long mmhip_clip_native_direct_frames(mmhip_invocation *inv) { return inv->clip_native_direct_frames; }
 
-// mm_clip of the clip kernels (hipgen.cpp clip_prelude)
+// mm_clip of the clip kernels (hipgen.cpp clip_prelude; images_stride is `pad' in the text of filters without native calls)
 struct HClipFrame { float t; int frame; };
-struct HClip { const HClipFrame *frames; long long frame_stride; int xy_stride; int rowtab_stride; int nwg; int pad; };
+struct HClip { const HClipFrame *frames; long long frame_stride; int xy_stride; int rowtab_stride; int nwg; int images_stride; };
 static_assert(sizeof(HClip) == 32, "mm_clip layout");
+
+// ---- clip batches of filters whose native calls are gaussian_blur ----
+// May the native calls of `f' run as batches over the frames of a clip?  Every call site a gaussian_blur outside loops,
+// no closure images, the exact chain with one segment per line, whole maps.
+static bool clip_native_eligible(const mmhip_filter *f, int native_row_margin) {
+    if (f->ks.natives.empty() || f->ks.native_sites != (int)f->ks.natives.size() || !f->closures.empty()) return false;
+    for (const NativeCall &nc : f->ks.natives)
+        if (nc.func != "native_filter_gaussian_blur") return false;
+    const char *seg = getenv("MMHIP_GAUSS_SEGMENTS");
+    return f->opts.gauss_mode == MMHIP_GAUSS_EXACT && !(seg && *seg) && native_row_margin < 0;
+}
+
+// Frames per batch: the clip plan's, at most 65 535 jobs per launch, and what MMHIP_CLIP_NATIVE_BYTES (read once,
+// default 8 GiB) holds of one frame's checkpoints, intermediate and result of every call site.  Below 2 the clip is
+// rendered frame by frame.
+struct ClipNativePlan { bool eligible = false; int per_batch = 0; size_t bytes_per_frame = 0; };
+static ClipNativePlan clip_native_plan(const mmhip_filter *f, int native_row_margin, const ClipPlan &plan, int render_w, int render_h) {
+    static const size_t budget = [] {
+        const char *e = getenv("MMHIP_CLIP_NATIVE_BYTES");
+        const long long v = e ? atoll(e) : 0;
+        return v > 0 ? (size_t)v : (size_t)8 << 30;
+    }();
+    ClipNativePlan p;
+    p.eligible = clip_native_eligible(f, native_row_margin);
+    if (!p.eligible || render_w < 1 || render_h < 1) return p;
+    size_t ck = 0, map = 0;
+    gaussian_blur_batch_job_bytes(render_w, render_h, &ck, &map);
+    p.bytes_per_frame = (size_t)f->ks.native_sites * (ck + 2 * map);
+    const size_t by_bytes = budget / p.bytes_per_frame;
+    const int per = (int)std::min<size_t>(std::min(plan.max_frames, 65535), by_bytes);
+    p.per_batch = per < 2 ? 0 : per;
+    return p;
+}
+
+int mmhip_filter_clip_native_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int render_h, int frames, int64_t *out) {
+    if (frames < 1) return fail("clip native plan: num_frames must be at least 1");
+    if (region_w < 1 || num_rows < 1 || render_w < 1 || render_h < 1) return fail("clip native plan: empty region");
+    const ClipPlan cp = clip_plan(clip_launch_geometry(f->ks, region_w, num_rows, frames));
+    const ClipNativePlan p = clip_native_plan(f, -1, cp, render_w, render_h);
+    const int64_t v[MMHIP_CLIP_NATIVE_PLAN_FIELDS] = {p.eligible, p.per_batch, p.per_batch ? (frames + p.per_batch - 1) / p.per_batch : 0,
+                                                      (int64_t)p.bytes_per_frame};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+// What one call of mmhip_render_clip hands its batches.
+struct ClipCall {
+    mmhip_invocation *inv;
+    mmhip_filter *f;
+    hipStream_t s;
+    HArgs a;                   // out: the first frame of the call
+    HClip c;                   // frames: the call's table
+    char *xy;
+    LaunchGeometry geo;
+    ClipPlan plan;
+    bool per_frame, rows;
+    size_t xy_stride;
+    int64_t frame_stride;
+    const int *frames;
+    const float *ts;
+    void *stream_arg;
+    // native batches: the records of the shared slot (read with the first batch) and whether the launch samples a
+    // native map at every pixel's own centre (decided once per call)
+    std::vector<char> records;
+    int direct_ok = -1;
+};
+
+// Frames [b0, b0 + n) of a clip of a filter whose native calls are all gaussian_blur: one prologue launch, one read-back
+// of all its records, every distinct blur of a call site in one gaussian_blur_batch, one pixel launch over per-frame
+// image tables -- or none, where the blurs pack the frames' bytes themselves.  A batch with a call the batched blur does
+// not take (a FIR deviation, an input of another size, ...) is rendered frame by frame before anything of it is written.
+static int clip_native_batch(ClipCall &cc, int b0, int n) {
+    mmhip_invocation *inv = cc.inv;
+    mmhip_filter *f = cc.f;
+    hipStream_t s = cc.s;
+    const KernelSource &ks = f->ks;
+    HArgs a = cc.a;
+    HClip c = cc.c;
+    char *xy = cc.xy;
+    a.out = (char *)cc.a.out + (int64_t)b0 * cc.frame_stride;
+    c.frames = cc.c.frames + b0;
+    c.images_stride = 0;          // the prologue (and the per-row slice) of every frame reads the invocation's table
+    void *params[] = {&a, &xy, &c};
+    const int num_rows = a.num_rows, region_w = a.region_width;
+    const unsigned pro_x = (unsigned)((std::max(region_w, num_rows) + 255) / 256), rows_x = (unsigned)((num_rows + 255) / 256);
+    const unsigned pro_frames = cc.per_frame ? (unsigned)n : b0 == 0 ? 1u : 0u;
+    if (pro_frames) {
+        HIP_TRY(hipModuleLaunchKernel(f->f_pro_clip, pro_x, pro_frames, 1, 256, 1, 1, 0, s, params, nullptr));
+        if (cc.rows) HIP_TRY(hipModuleLaunchKernel(f->f_rows_clip, rows_x, pro_frames, 1, 256, 1, 1, 0, s, params, nullptr));
+        cc.records.resize(cc.xy_stride * pro_frames);
+        HIP_TRY(hipMemcpyAsync(cc.records.data(), xy, cc.records.size(), hipMemcpyDeviceToHost, s));
+    }
+    std::vector<float> xt, yt;
+    const bool ask_direct = cc.direct_ok < 0 && direct_output_wanted(f, a) && (cc.frame_stride & 3) == 0;
+    if (ask_direct) {
+        xt.resize(region_w);
+        yt.resize(num_rows);
+        HIP_TRY(hipMemcpyAsync(xt.data(), a.xtab, xt.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(yt.data(), a.ytab, yt.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));      // (and with it for the batch before this one: its buffers are free)
+    if (cc.direct_ok < 0) cc.direct_ok = ask_direct && samples_own_pixels(a, xt, yt) ? 1 : 0;
+    auto frame_by_frame = [&]() -> int {
+        for (int i = b0; i < b0 + n; ++i)
+            if (mmhip_render(inv, cc.frames[i], cc.ts[i], a.region_x, a.region_y, a.region_width, a.region_height, a.first_row,
+                             a.first_row + a.num_rows, (char *)cc.a.out + (int64_t)i * cc.frame_stride, a.row_stride, a.output_bpp, a.floatmap,
+                             cc.stream_arg) != 0)
+                return -1;
+        return 0;
+    };
+
+    // Computations: in call order, frames share one where the call site, the record and the computations behind its
+    // native-map arguments are equal -- what the memo does for a loop of single renders.
+    // (view: the image table with the sequence argument's frame in place, MMHIP_NATIVE_FRAME_CURRENT; else empty)
+    struct Comp { size_t k; HNativeRec rec; int frame; std::vector<HImageDesc> view; float *map = nullptr; };
+    const int sites = ks.native_sites, base = inv->native_slot_base;
+    std::vector<Comp> comps;
+    std::vector<int> of_frame((size_t)n * sites, -1);      // [frame][site] -> computation
+    std::map<std::string, int> known;
+    std::vector<char> is_dep;
+    std::vector<RecordedCall> calls;
+    for (int i = 0; i < n; ++i) {
+        if (recorded_calls(ks, cc.records.data() + (cc.per_frame ? (size_t)i * cc.xy_stride : 0), &calls) != 0) return -1;
+        size_t last_k = 0;
+        for (size_t q = 0; q < calls.size(); ++q) {
+            const RecordedCall &call = calls[q];
+            if (q > 0 && call.k <= last_k) return frame_by_frame();      // the sites are not in call order: not expected outside loops
+            last_k = call.k;
+            std::string key((const char *)&call.k, sizeof call.k);
+            key.append((const char *)&call.rec, sizeof call.rec);
+            for (int j = 0; j < call.rec.nargs && j < 4; ++j) {
+                const HNativeArg &arg = call.rec.args[j];
+                if (arg.kind != 2 || arg.img.idx < base || arg.img.idx >= base + sites) continue;
+                const int dep = of_frame[(size_t)i * sites + (arg.img.idx - base)];
+                key.append((const char *)&dep, sizeof dep);
+                if (dep >= 0) is_dep[dep] = 1;
+            }
+            std::vector<HImageDesc> view;
+            int frame_key = NO_FRAME_KEY;
+            if (view_sequence_args(inv, cc.frames[b0 + i], *call.func, call.rec, view, &frame_key) != 0) return -1;
+            key.append((const char *)&frame_key, sizeof frame_key);
+            auto it = known.find(key);
+            if (it == known.end()) {
+                it = known.emplace(key, (int)comps.size()).first;
+                comps.push_back(Comp{call.k, call.rec, i, std::move(view)});
+                is_dep.push_back(0);
+            }
+            of_frame[(size_t)i * sites + call.k] = it->second;
+        }
+    }
+    // direct output: the direct call's blur packs frame i's bytes -- every frame has a blur of its own there, and nothing else reads it
+    bool direct = cc.direct_ok == 1 && ((uintptr_t)a.out & 3) == 0;
+    if (direct) {
+        std::vector<char> taken(comps.size(), 0);
+        for (int i = 0; i < n && direct; ++i) {
+            const int id = of_frame[(size_t)i * sites + ks.direct_native];
+            direct = id >= 0 && !taken[id] && !is_dep[id];
+            if (direct) taken[id] = 1;
+        }
+    }
+    // buffers: checkpoints and intermediate per job of the largest site, a map per computation that is read
+    size_t ck_bytes = 0, map_bytes = 0;
+    gaussian_blur_batch_job_bytes(a.render_width, a.render_height, &ck_bytes, &map_bytes);
+    std::vector<size_t> per_site(sites, 0);
+    size_t kept = 0;
+    for (const Comp &cp : comps) {
+        ++per_site[cp.k];
+        if (!(direct && (int)cp.k == ks.direct_native)) ++kept;
+    }
+    const size_t jobs_max = comps.empty() ? 0 : *std::max_element(per_site.begin(), per_site.end());
+    const size_t images_n = inv->images.size();
+    const size_t images_bytes = ((size_t)n * images_n * sizeof(HImageDesc) + 255) & ~(size_t)255;
+    const size_t tables_bytes = images_bytes + gaussian_blur_batch_table_bytes(comps.size());
+    ClipNativeBuffers &nb = inv->clip_native;
+    auto idle = [] { return hipSuccess; };      // the stream has just been waited for
+    HIP_TRY(nb.work.grow(jobs_max * (ck_bytes + map_bytes), idle));
+    HIP_TRY(nb.maps.grow(kept * map_bytes, idle));
+    HIP_TRY(nb.tables.grow(tables_bytes, idle));
+    if (nb.uploaded_pending) HIP_TRY(hipEventSynchronize(nb.uploaded));
+    nb.uploaded_pending = false;
+    HIP_TRY(nb.host.grow(tables_bytes));
+    {
+        size_t m = 0;
+        for (Comp &cp : comps)
+            if (!(direct && (int)cp.k == ks.direct_native)) cp.map = (float *)(nb.maps.get<char>() + (m++) * map_bytes);
+    }
+    // every frame's image table: the invocation's, the native slots this frame's maps (the null image where a call did not execute)
+    HImageDesc *tables = (HImageDesc *)nb.host.p;
+    HImageDesc null_desc{};
+    null_desc.kind = IMG_NULL;
+    for (int i = 0; i < n; ++i) {
+        HImageDesc *t = tables + (size_t)i * images_n;
+        std::copy(inv->images.begin(), inv->images.end(), t);
+        for (int k = 0; k < sites; ++k) {
+            const int id = of_frame[(size_t)i * sites + k];
+            t[base + k] = id >= 0 && comps[id].map ? floatmap_desc(comps[id].map, a.render_width, a.render_height) : null_desc;
+        }
+    }
+    inv->ws.env.supersampling = f->kopt.supersampling;
+    inv->ws.env.edge_x = f->kopt.edge_x;
+    inv->ws.env.edge_y = f->kopt.edge_y;
+    inv->ws.env.edge_color_x = inv->edge_color_x;
+    inv->ws.env.edge_color_y = inv->edge_color_y;
+    inv->ws.gauss_tolerance = false;
+    // (a computation's own slot is still null in its frame's table while it is planned; a later one finds its map there)
+    for (const Comp &cp : comps) {
+        const int idx = cp.rec.args[0].img.idx;
+        const HImageDesc *t = cp.view.empty() ? tables + (size_t)cp.frame * images_n : cp.view.data();
+        const bool own_result = idx >= base && idx < base + sites && of_frame[(size_t)cp.frame * sites + (idx - base)] >= 0 && (size_t)(idx - base) < cp.k;
+        const bool bound_input = idx >= 0 && idx < base;
+        if (!(own_result || bound_input) ||
+            !gaussian_blur_batchable(cp.rec, t, (int)images_n, a.render_width, a.render_height, inv->ws.env, nullptr, nullptr))
+            return frame_by_frame();
+    }
+    // the job tables of every site, behind the image tables; one copy takes all of them up
+    NativeDirectOut dout;
+    dout.row_stride = a.row_stride;
+    dout.first_row = a.first_row;
+    dout.num_rows = a.num_rows;
+    dout.region_x = a.region_x;
+    dout.region_w = a.region_width;
+    std::vector<std::vector<GaussClipGroup>> groups(sites);
+    std::vector<GaussClipLaunch> launches(sites);
+    size_t at = images_bytes;
+    std::string err;
+    for (int k = 0; k < sites; ++k) {
+        std::vector<GaussClipJob> jobs;
+        const bool packs = direct && k == ks.direct_native;
+        for (size_t id = 0; id < comps.size(); ++id) {
+            const Comp &cp = comps[id];
+            if ((int)cp.k != k) continue;
+            char *w = nb.work.get<char>() + jobs.size() * (ck_bytes + map_bytes);
+            jobs.push_back(GaussClipJob{cp.rec, cp.view.empty() ? tables + (size_t)cp.frame * images_n : cp.view.data(), (int)images_n, (double *)w, (float *)(w + ck_bytes), cp.map,
+                                        packs ? (unsigned char *)a.out + (int64_t)cp.frame * cc.frame_stride : nullptr});
+        }
+        launches[k].render_w = a.render_width;
+        launches[k].render_h = a.render_height;
+        launches[k].direct = packs ? &dout : nullptr;
+        launches[k].write_map = !packs;
+        if (jobs.empty()) continue;
+        if (gaussian_blur_batch_tables(jobs, launches[k], inv->ws.env, (char *)nb.host.p + at, nb.tables.get<char>() + at, &groups[k], &err) != 0)
+            return fail(err);
+        at += gaussian_blur_batch_table_bytes(jobs.size());
+    }
+    if (!nb.uploaded) HIP_TRY(hipEventCreateWithFlags(&nb.uploaded, hipEventDisableTiming));
+    HIP_TRY(hipMemcpyAsync(nb.tables.get(), nb.host.p, tables_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(nb.uploaded, s));
+    nb.uploaded_pending = true;
+    for (int k = 0; k < sites; ++k)
+        if (!groups[k].empty() && gaussian_blur_batch_launch(groups[k], launches[k], inv->ws, s, &err) != 0) return fail(err);
+    ++inv->clip_native_batches;
+    inv->clip_native_blurs += (long)comps.size();
+    if (direct) {
+        inv->clip_native_direct_frames += n;
+        return 0;
+    }
+    a.images = nb.tables.get<HImageDesc>();
+    c.images_stride = (int)images_n;
+    if (inv->timing) {
+        if (next_event_pair(inv) != 0) return -1;
+        HIP_TRY(hipEventRecord(inv->ev0, s));
+    }
+    HIP_TRY(hipModuleLaunchKernel(f->f_pix_clip, (unsigned)cc.plan.grid_x, (unsigned)n, 1, 256, 1, 1, 0, s, params, nullptr));
+    if (inv->timing) {
+        HIP_TRY(hipEventRecord(inv->ev1, s));
+        inv->ev_valid = true;
+    }
+    return 0;
+}
 
 int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int region_x, int region_y,
                       int region_w, int region_h, int first_row, int last_row, void *out_device, int row_stride,
@@ -1383,8 +1706,11 @@ int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, 
     hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
     const LaunchGeometry geo = clip_launch_geometry(f->ks, region_w, num_rows, num_frames);
     const ClipPlan plan = clip_plan(geo);
-    if (!f->ks.natives.empty() || !f->closures.empty() || plan.max_frames < 1) {
+    const bool natives = !f->ks.natives.empty();
+    const ClipNativePlan nplan = natives ? clip_native_plan(f, inv->native_row_margin, plan, inv->render_w, inv->render_h) : ClipNativePlan();
+    if ((natives && nplan.per_batch < 1) || !f->closures.empty() || plan.max_frames < 1) {
         // native filters run the host between prologue and pixels of every frame: frame by frame, the same result
+        // (but for gaussian_blur calls the batches below take)
         for (int i = 0; i < num_frames; ++i)
             if (mmhip_render(inv, frames[i], ts[i], region_x, region_y, region_w, region_h, first_row, last_row,
                              (char *)out_device + (int64_t)i * frame_stride, row_stride, bpp, floatmap, stream) != 0)
@@ -1397,7 +1723,7 @@ int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, 
     HArgs a = render_args(inv, frames[0], ts[0], region_x, region_y, region_w, region_h, first_row, last_row, out_device, row_stride, bpp, floatmap);
     const bool per_frame = f->ks.prologue_uses_time;      // else one frame-constant slot and one row table for all frames
     const bool rows = f->ks.row_values > 0;
-    const int per_batch = std::min(num_frames, plan.max_frames);
+    const int per_batch = std::min(num_frames, natives ? nplan.per_batch : plan.max_frames);
     const size_t xy_stride = ((size_t)std::max(f->ks.xy_bytes, 256) + 255) / 256 * 256;
     const size_t rowtab_stride = (size_t)f->ks.row_values * num_rows;      // floats
     const int slots = per_frame ? per_batch : 1;
@@ -1434,6 +1760,13 @@ int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, 
     c.xy_stride = per_frame ? (int)xy_stride : 0;
     c.rowtab_stride = per_frame ? (int)rowtab_stride : 0;
     c.nwg = (int)geo.nwg;
+    if (natives) {
+        ClipCall cc{inv, f, s, a, c, xy, geo, plan, per_frame, rows, xy_stride, frame_stride, frames, ts, stream, {}, -1};
+        cc.c.frames = tab.dev.get<HClipFrame>();
+        for (int b0 = 0; b0 < num_frames; b0 += per_batch)
+            if (clip_native_batch(cc, b0, std::min(per_batch, num_frames - b0)) != 0) return -1;
+        return 0;
+    }
     void *params[] = {&a, &xy, &c};
     const unsigned pro_x = (unsigned)((std::max(region_w, num_rows) + 255) / 256), rows_x = (unsigned)((num_rows + 255) / 256);
     for (int b0 = 0; b0 < num_frames; b0 += per_batch) {

@@ -132,6 +132,17 @@ struct ClipBuffers {
     unsigned next_table = 0;
 };
 
+// What the native batches of a clip render keep (clip_native_batch in runtime.cpp), apart from the single-frame path's
+// maps and workspace: checkpoints and intermediates of one call site's jobs, the maps of a batch's blurs, and the tables
+// the kernels index by frame and by job (every frame's image table, then the job tables), which go up from page-locked memory.
+struct ClipNativeBuffers {
+    DeviceBuffer work, maps, tables;
+    PinnedBuffer host;
+    hipEvent_t uploaded = nullptr;          // recorded behind the tables' copy: `host' may be rewritten after it
+    bool uploaded_pending = false;
+    ~ClipNativeBuffers() { if (uploaded) (void)hipEventDestroy(uploaded); }
+};
+
 // Native call entry k (KernelSource::natives[k]): its float4 map and what is remembered about it.
 struct NativeEntry {
     DeviceBuffer map;
@@ -141,6 +152,7 @@ struct NativeEntry {
     // recomputed when its producer was.
     unsigned long long gen = 0;
     mm::HNativeRec memo{};                     // args of the call that produced the map
+    int memo_frame = 0, seen_frame = 0;        // ... and the frame of a sequence it read (MMHIP_NATIVE_FRAME_CURRENT; else NO_FRAME_KEY)
     unsigned long long memo_gen = 0;
     std::vector<unsigned long long> memo_deps;
     mm::HNativeRec seen{};                     // last argument set whose map was asked for (direct output: materialised on its second use)
@@ -186,6 +198,7 @@ struct mmhip_invocation {
     DeviceBuffer ss_lines;                 // the two slices of a supersampled render (own allocation: native filters
                                            // reallocate `ws` underneath a nested render)
     int native_row_margin = -1;                     // mmhip_set_native_row_margin
+    int native_input_frame = 0;                     // mmhip_set_native_input_frame
     long direct_native_launches = 0;                // mmhip_direct_native_launches
     long tolerance_blur_launches = 0;               // mmhip_tolerance_blur_launches
     // the prologue kernel is skipped while nothing it reads has changed (mmhip_render)
@@ -198,6 +211,10 @@ struct mmhip_invocation {
     ClipBuffers clip;                      // of the clip kernels (mmhip_render_clip)
     long clip_batched_launches = 0;        // mmhip_clip_batched_launches
     long clip_prologue_frames = 0;         // mmhip_clip_prologue_frames
+    ClipNativeBuffers clip_native;         // of the native batches of a clip render
+    long clip_native_batches = 0;          // mmhip_clip_native_batches
+    long clip_native_blurs = 0;            // mmhip_clip_native_blurs
+    long clip_native_direct_frames = 0;    // mmhip_clip_native_direct_frames
     uint32_t edge_color_x = 0, edge_color_y = 0;
     float sampling_offset_x = 0.f, sampling_offset_y = 0.f;
     bool timing = false;
