@@ -866,6 +866,7 @@ struct Generator {
                                           [this](const Value *v) { return value_visible(v, PIXEL); }});
         if (pair) ks.unroll = 2;
         ks.pair_mode = pair != nullptr;
+        ks.pair_exit = pair && pair->exit_driven();
         out << "#define MM_UNROLL " << ks.unroll << "\n";
         out << "#define MM_NATIVE_REC_BYTES " << (int)MM_NATIVE_REC_BYTES << "\n#define MM_NATIVE_DYN_CALLS " << (int)MM_NATIVE_DYN_CALLS << "\n";
     }
@@ -1242,6 +1243,8 @@ void clip_kernel_source(const KernelSource &ks, std::string *source, std::string
     source->append(ks.source, at, std::string::npos);
     *key = text_key(*source);      // like the single-frame text's key
 }
+
+bool pair_peel_enabled() { return Knobs().pair_peel.value_or(0) != 0; }
 
 KernelSource generate_hip(FilterCode &code, const KernelOptions &opt, FilterCode *functions_of) {
     const Knobs knobs;      // this compile's reading of the environment

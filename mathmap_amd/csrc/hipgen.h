@@ -46,6 +46,7 @@ struct KernelSource {
     bool prologue_uses_time = true;   // frame-constant code reads t or frame: re-run it for every frame
     bool single_pixel = false;    // kernel renders exactly one pixel per work-item: launch with ppt = 1
     bool pair_mode = false;       // the pixel loop evaluates two vertically adjacent rows in lockstep (unroll 2)
+    bool pair_exit = false;       // ... with exit-driven loops: the kernels for which a peeled first trip is kept
     int xcd_order = 2;            // MM_XCD_ORDER: workgroup -> tile order of the pixel kernel
     int row_values = 0;           // > 0: kernel `mm_rows` fills that many per-row values (mm_args.rowtab) before the pixel kernel
     std::string rows_name;
@@ -59,6 +60,9 @@ struct KernelSource {
 
 // `functions_of`: the code whose `functions` (filter_$name bodies) `code` may call; null = its own
 KernelSource generate_hip(FilterCode &code, const KernelOptions &opt, FilterCode *functions_of = nullptr);
+// Is peeling first loop trips (peel_first_trips, passes.h) switched on?  MMHIP_PAIR_PEEL=1: on (default off).  The caller peels a specialised
+// filter's code, generates, and compiles again without peeling unless the kernel came out in exit-driven pair mode.
+bool pair_peel_enabled();
 // the clip variant's text and its cache key, built from `ks.source` on demand
 void clip_kernel_source(const KernelSource &ks, std::string *source, std::string *key);
 const char *clip_prelude();

@@ -28,7 +28,10 @@ struct Knobs {
     bool pair_debug = env_int("MMHIP_PAIR_DEBUG").has_value();        // say on stderr why a body is not covered (same text)
     std::optional<int> pair_masks = env_int("MMHIP_PAIR_MASKS");      // #define MM_PAIR_MASKS; 0: truth values as ints, no exit-driven loops
     std::optional<int> pair_exit = env_int("MMHIP_PAIR_EXIT");        // 0: pair-mode loops keep the per-iteration selects
-    std::optional<int> pair_exit_tail = env_int("MMHIP_PAIR_EXIT_TAIL");   // 0: an exit-driven loop's back edge is left to the compiler
+    // an exit-driven loop's back edge: 0 left to the compiler, 1 compare and mask (s_cmp, s_cselect_b64), unset / 2 counted (carry)
+    std::optional<int> pair_exit_tail = env_int("MMHIP_PAIR_EXIT_TAIL");
+    std::optional<int> pair_pack = env_int("MMHIP_PAIR_PACK");        // 0: pair kernels store through mm_store_pixel, a pixel at a time
+    std::optional<int> pair_peel = env_int("MMHIP_PAIR_PEEL");        // 1: peel a first trip that folds off the loops of specialised pair kernels (pair_peel_enabled; default off: not measured yet)
     bool pair_no_uniform = env_int("MMHIP_PAIR_NO_UNIFORM").has_value();   // no wave-uniform scalars in pair-mode loops
     std::optional<int> nt_store = env_int("MMHIP_NT_STORE");          // #define MM_NT_STORE, instead of "the kernel fetches"
     std::optional<int> xcd_order = env_int("MMHIP_XCD_ORDER");        // workgroup -> tile order 0 / 1 / 2 (default 2)
@@ -68,6 +71,7 @@ struct PairEnv {
 };
 struct PairMode {
     virtual ~PairMode() {}
+    virtual bool exit_driven() const = 0;                 // loops in the exit-driven form (lane masks, MMHIP_PAIR_EXIT)
     virtual bool is_uniform(const Value *v) const = 0;    // kept as a wave-uniform scalar `u<name>` where the text now stands
     virtual void emit_helpers() = 0;                      // device functions of this kernel alone, behind the preludes
     virtual void emit_pixel_loop(const std::string &ind) = 0;   // the whole `for (; mm_p < A.ppt; mm_p += 2)` loop

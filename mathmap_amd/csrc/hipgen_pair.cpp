@@ -39,11 +39,14 @@ struct PairGen final : PairMode {
     int ids = 0;                       // names of masks: mm_c<id>, mm_a<id>, mm_l<id>
     // exit-driven loops (exit_driven_iteration): they need lane masks; MMHIP_PAIR_EXIT=0 keeps the per-iteration selects
     const bool exit = env.knobs.pair_exit.value_or(1) && env.knobs.pair_masks.value_or(1);
+    // the kernel's own result pack (emit_helpers): with the exit-driven loops, so that MMHIP_PAIR_EXIT=0 is the earlier text
+    const bool pack = exit && env.knobs.pair_pack.value_or(1);
     const Stmt *split_def = nullptr;   // the uniform conjunct's defining statement, while its loop body is printed
     bool split_leave = false;          // the value with which it ends the loop
 
     explicit PairGen(const PairEnv &e) : env(e), out(e.out), code(e.code) {}
 
+    bool exit_driven() const override { return exit; }
     bool is_uniform(const Value *v) const override { return uniform.count(v) > 0; }
 
     // ---- which bodies are covered ----
@@ -429,6 +432,11 @@ struct PairGen final : PairMode {
         std::set<const Value *> outside;          // phis that are read after the loop
         std::vector<const Stmt *> ivs;            // uniform induction variables: a scalar twin, read inside the loop instead of the pair
         std::vector<std::pair<const Stmt *, std::string>> exit_copy;      // exit-driven: a phi of `outside` and the name of its exit copy
+        // counted back edge (plan_counted): the uniform bound as the carry of one s_add_u32
+        bool counted = false;
+        unsigned count_step = 0;                  // what the counter gains per trip: |step| of the induction variable
+        const Stmt *count_iv = nullptr;           // the induction variable whose scalar twin is computed from the counter, if any
+        std::string count_twin;                   // ... and the expression that does so
         bool is_iv(const Stmt *ph) const { return std::find(ivs.begin(), ivs.end(), ph) != ivs.end(); }
     };
     // Back edge: the phis take their next values -- a parallel copy, temporaries first -- and the induction variables'
@@ -443,7 +451,101 @@ struct PairGen final : PairMode {
                 << (select && w.outside.count(phis[k]->lhs) ? "mm_sel2(" + w.a + ", " + nv + ", " + vname(phis[k]->lhs) + ")" : nv) << ";\n";
         }
         for (size_t k = 0; k < phis.size(); ++k) out << I << vname(phis[k]->lhs) << " = " << w.a << "_n" << k << ";\n";
-        for (const Stmt *ph : w.ivs) out << I << "u" << vname(ph->lhs) << " = " << env.prim(ph->rhs2.prim) << ";\n";
+        for (const Stmt *ph : w.ivs)
+            if (ph != w.count_iv) out << I << "u" << vname(ph->lhs) << " = " << env.prim(ph->rhs2.prim) << ";\n";
+    }
+    // Counted back edge (MMHIP_PAIR_EXIT_TAIL unset or 2).  The uniform conjunct compares an int that gains a literal step s per
+    // trip -- an induction variable (its value before the step) or its stepped value -- with a loop-invariant bound, and the
+    // loop runs while the comparison holds (LESS, LEQ and their negations) or until the two are equal (the negation of EQ, s =
+    // +-1).  Then the back edge at which it ends the loop is known when the loop is entered: with o the operand's value one
+    // step before the first test and D the distance it has to cover -- `o < B`, s > 0: D = B - o; `o <= B`: one more; `B < o`,
+    // s < 0: D = o - B; ... -- it is the first at which trips * |s| >= D.  A counter k = 2^32 - D that gains |s| per trip wraps
+    // around exactly there, so one s_add_u32 steps it and leaves the bound's verdict in SCC (its carry), where the compare-and-mask
+    // tail steps the induction variable and compares (s_add_i32, s_cmp); and since nothing clobbers SCC in between, one s_cselect_b64
+    // folds the verdict into the `left` word (-1: every lane leaves) where that tail builds a mask and ORs it in.  D <= 0 --
+    // the comparison fails before the first step: it fails at the first test as well, the operand moves away -- counts as 1.
+    // A literal distance that does not fit the counter (above 2^32 - 1) keeps the compare-and-mask tail; a run-time distance is
+    // clamped to 2^32 - 1 there (more than four billion trips: not reachable in practice).
+    // In the exit block k < |s| says that the counter has wrapped.  (An operand that overflows int before it reaches the
+    // bound is undefined in the scalar kernel's C; here the loop then ends where the exact sum reaches the bound.)
+    // With literal initial value and bound the induction variable's scalar twin is a function of k, u = init +- (k - k0): it is
+    // computed from k at the top of the body -- for nothing if only the bound reads it -- and is not stepped on its own.
+    // Anything else (a bound on a lagging copy, `==` as the running condition, a step that is no literal or points away from
+    // the bound) keeps the compare-and-mask tail.
+    // The relation under which a loop with the uniform conjunct `a0 CN a1` runs, the operand on side `side` advancing by `step`:
+    // the comparison itself, or -- `leave`: the conjunct's truth ends the loop -- its negation, which swaps the sides and turns
+    // `<` into `<=` (!(a < b) is b <= a).  Covered: the operand moves towards the bound of `<` (`inclusive`: `<=`), or, for the
+    // negation of `==`, by +-1:
+    //   o <  B / o <= B   operand left    up          B <  o / B <= o   operand right   down          o != B   either side   +-1
+    static bool counted_relation(const char *cn, bool leave, int side, long step, bool &inclusive) {
+        if (!strcmp(cn, "EQ")) { inclusive = false; return leave && (step == 1 || step == -1); }
+        const bool advancing_left = leave ? side == 1 : side == 0;
+        inclusive = leave ? !strcmp(cn, "LESS") : !strcmp(cn, "LEQ");
+        return advancing_left ? step > 0 : step < 0;
+    }
+    void plan_counted(Loop &w, const std::string &l) {
+        if (env.knobs.pair_exit_tail.value_or(2) < 2) return;
+        bool leave = false;
+        const Stmt *split = find_split(w.s, w.outside, leave);
+        if (!split) return;
+        const char *cn = split->rhs.op->cname;
+        const bool eq = !strcmp(cn, "EQ");
+        // the advancing operand: which side, which induction variable, its step, its value one step before the first test
+        int side = -1;
+        const Stmt *iv = nullptr;
+        long step = 0;
+        bool stepped = false;
+        for (int i = 0; i < 2 && side < 0; ++i) {
+            const Primary &p = split->rhs.args[i];
+            if (p.kind != Primary::Val) continue;
+            for (const Stmt *ph : w.ivs) {
+                if (ph->lhs->var->type != Ty::Int) continue;
+                const Stmt *d = ph->rhs2.prim.value->def;
+                const bool self0 = d->rhs.args[0].kind == Primary::Val && d->rhs.args[0].value == ph->lhs;
+                const Primary &c = d->rhs.args[self0 ? 1 : 0];
+                if (c.kind != Primary::IntConst || (p.value != ph->lhs && p.value != d->lhs)) continue;
+                side = i; iv = ph; stepped = p.value == d->lhs;
+                step = !strcmp(d->rhs.op->cname, "SUB") ? -(long)c.i : (long)c.i;
+            }
+        }
+        if (side < 0 || step == 0 || step > 0x7fffffffL || step < -0x7fffffffL) return;
+        const Primary &bound = split->rhs.args[1 - side], &init = iv->rhs.prim;
+        if (!invariant_scalar(bound) || bound.type() != Ty::Int || init.type() != Ty::Int) return;
+        bool inclusive = false;
+        if (!counted_relation(cn, leave, side, step, inclusive)) return;
+        const bool up = step > 0;
+        const long pre = stepped ? 0 : -step;              // the operand one step before the first test: init + pre
+        auto lit = [](const Primary &p, long &v) {
+            if (p.kind == Primary::IntConst) { v = p.i; return true; }
+            if (p.kind == Primary::Val && p.value->index < 0) { v = 0; return true; }
+            return false;
+        };
+        long iv0 = 0, b0 = 0;
+        const std::string k = l + "_k";
+        if (lit(init, iv0) && lit(bound, b0)) {
+            long d = up ? b0 - (iv0 + pre) : (iv0 + pre) - b0;
+            if (eq) d &= 0xffffffffL; else d += inclusive ? 1 : 0;
+            if (!eq && d > 0xffffffffL) return;      // (more trips than the counter holds: the compare-and-mask tail)
+            const bool exact = eq || d > 0;
+            if (!exact) d = 1;
+            const unsigned k0 = 0u - (unsigned)d;
+            out << w.ind << "unsigned " << k << " = " << k0 << "u;\n";
+            if (exact) {
+                w.count_iv = iv;
+                const unsigned c = up ? (unsigned)iv0 - k0 : (unsigned)iv0 + k0;
+                w.count_twin = "(int)(" + std::to_string(c) + "u " + (up ? "+ " : "- ") + k + ")";
+            }
+        } else {
+            uniform.erase(iv->lhs);       // the initial value is printed with the ordinary names
+            const std::string o = "((long)(" + env.prim(init) + ") + " + std::to_string(pre) + "l)", b = "(long)(" + env.prim(bound) + ")";
+            uniform.insert(iv->lhs);
+            const std::string d = (up ? b + " - " + o : o + " - " + b) + (inclusive ? " + 1l" : "");
+            out << w.ind << "const long " << k << "_d = " << d << ";\n";
+            out << w.ind << "unsigned " << k << " = __builtin_amdgcn_readfirstlane(0u - (unsigned)("
+                << (eq ? k + "_d" : k + "_d <= 0l ? 1l : " + k + "_d > 0xffffffffl ? 0xffffffffl : " + k + "_d") << "));\n";
+        }
+        w.counted = true;
+        w.count_step = (unsigned)(up ? step : -step);
     }
     // Per-iteration selects (no lane masks, or MMHIP_PAIR_EXIT=0): one iteration and its back edge.
     void selecting_iteration(const Loop &w) {
@@ -476,9 +578,11 @@ struct PairGen final : PairMode {
     // last the bound name *is* the conjunct's value, so whatever the phis carry into a later iteration is right; wrong
     // values only arise in the last iteration, no iteration follows it, and what it leaves behind is read through the
     // exit copies alone -- whose next values the scan has shown not to depend on the conjunct.  The conjunct's own
-    // operands are read at the end of the body, before the phis step.  The back edge is one asm statement then (MM_PAIR_EXIT_TAIL, default
-    // 1): the compiler combines the two tests as lane masks (s_cselect_b64, s_and_b64 with exec, branch on vcc:
-    // 12 scalar instructions per iteration), the statement needs 6 and the loop 9.
+    // operands are read at the end of the body, before the phis step.  The back edge is one asm statement then: left to itself
+    // (MMHIP_PAIR_EXIT_TAIL=0) the compiler combines the two tests as lane masks (s_cselect_b64, s_and_b64 with exec, branch on
+    // vcc: 12 scalar instructions per iteration); comparing and masking in the statement (s_cmp, s_cselect_b64, two s_andn2_b64,
+    // two s_or_b64: MMHIP_PAIR_EXIT_TAIL=1, and every bound plan_counted does not cover) the loop needs 9; counted (the default
+    // where plan_counted applies) it needs 7.
     void exit_driven_iteration(const Loop &w, const std::string &l) {
         Stmt *s = w.s;
         const std::string &ind = w.ind, &a = w.a, I2 = ind + "    ";
@@ -487,11 +591,13 @@ struct PairGen final : PairMode {
         // the back edge's scalar comparison as one asm statement: its operands
         std::vector<std::string> tail_inputs;
         std::string tail_o0, tail_o1;
-        const bool asm_tail = split && env.knobs.pair_exit_tail.value_or(1) &&
+        const bool asm_tail = split && !w.counted && env.knobs.pair_exit_tail.value_or(1) &&
                               !(split->rhs.args[0].kind == Primary::IntConst && split->rhs.args[1].kind == Primary::IntConst) &&
                               tail_operand(split->rhs.args[0], tail_o0, tail_inputs, 8) && tail_operand(split->rhs.args[1], tail_o1, tail_inputs, 8);
-        out << ind << "  mm_bb " << l << ";" << (asm_tail ? " unsigned long " + l + "_u, " + l + "_t;" : split ? " bool " + l + "_b;" : "") << "\n";
+        out << ind << "  mm_bb " << l << ";"
+            << (w.counted ? " unsigned long " + l + "_t;" : asm_tail ? " unsigned long " + l + "_u, " + l + "_t;" : split ? " bool " + l + "_b;" : "") << "\n";
         out << ind << "  do {\n";
+        if (w.count_iv) out << I2 << "const int u" << vname(w.count_iv->lhs) << " = " << w.count_twin << ";\n";
         const Stmt *outer_split = split_def;
         const bool outer_leave = split_leave;
         split_def = split;
@@ -506,13 +612,23 @@ struct PairGen final : PairMode {
                 out << I2 << "const int " << l << "_o" << i << " = " << tail_inputs[i] << ";\n";
                 tail_inputs[i] = l + "_o" + std::to_string(i);
             }
-        else if (split)
+        else if (split && !w.counted)
             out << I2 << l << "_b = (bool)(" << env.rhs(split) << ") == " << (leave ? "true" : "false") << ";\n";
         step_phis(w, I2, false);      // nothing selected
         // lanes that leave at this back edge
         const std::string c = pbool(s->cond.prim);
         const std::string lx = a + ".x & ~" + c + ".x", ly = a + ".y & ~" + c + ".y";
-        if (asm_tail) {
+        if (w.counted) {
+            // left = active & ~cond; _t = left.x | left.y, or all ones when the counter wraps: the bound ends the loop
+            out << I2 << "const mm_bb " << l << "_c = " << c << ";\n";
+            out << I2 << "asm(\"s_andn2_b64 %0, %4, %6\\n\\ts_andn2_b64 %1, %5, %7\\n\\ts_or_b64 %3, %0, %1\\n\\ts_add_u32 %2, %2, " << w.count_step
+                << "\\n\\ts_cselect_b64 %3, -1, %3\"\n"
+                << I2 << "    : \"=&s\"(" << l << ".x), \"=&s\"(" << l << ".y), \"+s\"(" << l << "_k), \"=&s\"(" << l << "_t)\n"
+                << I2 << "    : \"s\"(" << a << ".x), \"s\"(" << a << ".y), \"s\"(" << l << "_c.x), \"s\"(" << l << "_c.y) : \"scc\");\n";
+            out << ind << "  } while (" << l << "_t == 0);\n";
+            out << ind << "  if (" << l << "_k < " << w.count_step << "u) " << l << " = " << a << ";      // the counter has wrapped: every active lane leaves\n";
+            if (w.count_iv) out << ind << "  u" << vname(w.count_iv->lhs) << " = " << w.count_twin << ";\n";
+        } else if (asm_tail) {
             // SCC = the conjunct; _u = all ones when it ends the loop; left = active & ~cond; _t = _u | left.x | left.y
             const char *cn = split->rhs.op->cname;
             const char *cmp = !strcmp(cn, "LESS") ? "s_cmp_lt_i32" : !strcmp(cn, "LEQ") ? "s_cmp_le_i32" : "s_cmp_eq_i32";
@@ -568,6 +684,7 @@ struct PairGen final : PairMode {
             uniform.insert(ph->lhs);
             out << ind << (ph->lhs->var->type == Ty::Float ? "float u" : "int u") << vname(ph->lhs) << " = " << init << ";\n";
         }
+        if (exit) plan_counted(w, "mm_l" + id);
         out << ind << "mm_bb " << w.a << " = mm_andb(" << mask << ", " << pbool(s->cond.prim) << ");\n";
         out << ind << "while (" << w.a << ".x | " << w.a << ".y) {\n";
         if (exit) exit_driven_iteration(w, "mm_l" + id);
@@ -624,6 +741,94 @@ MM_DEV mm_bb mm_xbu(bool u) { const unsigned long m = u ? ~0ul : 0ul; return mm_
 // would pull the loop counter, and the loop's bound test, onto the vector unit)
 MM_DEV int mm_s2v(int u) { int r; asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(__builtin_amdgcn_readfirstlane(u))); return r; }
 )";
+        emit_store_pair();
+    }
+
+    // ---- the result pack of this kernel ----
+    // mm_store_pixel packs four channels it knows nothing about, once per pixel.  Here the channels are known: which of them
+    // are the same SSA value (a grey result is one value three times) and which are literals (alpha = 1 of every filter that
+    // does not compute one).  mm_store_pair, emitted for this kernel alone, stores both pixels of a step: on the RGBA8 path
+    // (bpp 4, no floatmap) every distinct value is clamped and converted once, all of them inside one round-toward-zero
+    // window, a literal channel is its byte -- floor(255 clamp(c)), what mm_pack_rgba8 computes -- and v_perm_b32 puts byte 0
+    // of each converted value where its channels are.  Every other output format goes through mm_store_pixel as before.
+    struct Pack {
+        std::vector<const Value *> vals;      // the distinct values that are converted
+        int src[4];                           // per channel: index into vals, or -1: a literal
+        float lit[4];
+    };
+    static bool literal_of(const Value *v, float &f, int depth = 0) {
+        if (!v || depth > 8) return false;
+        if (v->index < 0) { f = 0; return true; }      // uninitialised: reads as 0
+        const Stmt *d = v->def;
+        if (!d || d->kind != Stmt::Assign || d->lhs != v || d->rhs.kind != Rhs::Prim) return false;
+        const Primary &p = d->rhs.prim;
+        if (p.kind == Primary::IntConst) { f = (float)p.i; return true; }
+        if (p.kind == Primary::FloatConst) { f = p.f; return v->var->type == Ty::Float && f == f; }
+        return p.kind == Primary::Val && p.value->var->type == v->var->type && literal_of(p.value, f, depth + 1);
+    }
+    bool plan_pack(Pack &pk) const {
+        if (!pack) return false;
+        for (int i = 0; i < 4; ++i) {
+            const Value *v = code.result[i];
+            pk.src[i] = -1;
+            if (literal_of(v, pk.lit[i])) continue;
+            const auto it = std::find(pk.vals.begin(), pk.vals.end(), v);
+            pk.src[i] = (int)(it - pk.vals.begin());
+            if (it == pk.vals.end()) pk.vals.push_back(v);
+        }
+        return !pk.vals.empty();
+    }
+    void emit_store_pair() {
+        Pack pk;
+        if (!plan_pack(pk)) return;
+        const int n = (int)pk.vals.size();
+        unsigned k = 0;                       // the literal channels' bytes, in place
+        for (int i = 0; i < 4; ++i)
+            if (pk.src[i] < 0) {
+                const float c = pk.lit[i] < 0.0f ? 0.0f : pk.lit[i] > 1.0f ? 1.0f : pk.lit[i];
+                k |= (unsigned)(255.0 * (double)c) << (8 * i);
+            }
+        // v_perm_b32 selectors: 0x00 / 0x04: byte 0 of the second / first operand, 0x0c: a zero byte
+        auto sel = [&](int second, int first) {
+            unsigned s = 0;
+            for (int i = 0; i < 4; ++i) s |= (pk.src[i] == second && second >= 0 ? 0x00u : pk.src[i] == first && first >= 0 ? 0x04u : 0x0cu) << (8 * i);
+            return s;
+        };
+        auto hex = [](unsigned v) { char b[16]; snprintf(b, sizeof b, "0x%08xu", v); return std::string(b); };
+        auto word = [&](const char *px) {
+            auto u = [&](int j) { return std::string("u") + px + std::to_string(j); };
+            if (n == 1) {      // the literals' bytes come from the constant word: its byte i for channel i
+                unsigned s1 = 0;
+                for (int i = 0; i < 4; ++i) s1 |= (pk.src[i] == 0 ? 0x04u : (unsigned)i) << (8 * i);
+                return "__builtin_amdgcn_perm(" + u(0) + ", " + hex(k) + ", " + hex(s1) + ")";
+            }
+            std::string w = "__builtin_amdgcn_perm(" + u(1) + ", " + u(0) + ", " + hex(sel(0, 1)) + ")";
+            if (n > 2) w += " | __builtin_amdgcn_perm(" + (n > 3 ? u(3) : u(2)) + ", " + u(2) + ", " + hex(sel(2, n > 3 ? 3 : -1)) + ")";
+            return k ? w + " | " + hex(k) : w;
+        };
+        out << "// this kernel's result pack (hipgen_pair.cpp emit_store_pair): both pixels of a step, " << n << " distinct value" << (n > 1 ? "s" : "")
+            << " per pixel, literal bytes " << hex(k) << "\n"
+            << "MM_DEV void mm_store_pair(const mm_args &A, int row_a, int row_b, int col";
+        for (int j = 0; j < n; ++j) out << ", float a" << j << ", float b" << j;
+        out << ") {\n  if (__builtin_expect(!A.floatmap && A.output_bpp == 4, 1)) {\n   ";
+        for (int j = 0; j < n; ++j) out << " a" << j << " = mm_clamp01(a" << j << "); b" << j << " = mm_clamp01(b" << j << ");";
+        out << "\n    unsigned";
+        for (int j = 0; j < n; ++j) out << (j ? ", " : " ") << "ua" << j << ", ub" << j;
+        out << ";\n    asm volatile(\"s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3\\n\\t\"\n";
+        for (int j = 0; j < 2 * n; ++j) out << "                 \"v_fma_f32 %" << j << ", %" << 2 * n + j << ", %" << 4 * n << ", %" << 4 * n + 1 << "\\n\\t\"\n";
+        out << "                 \"s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\"\n                 :";
+        for (int j = 0; j < n; ++j) out << (j ? ", " : " ") << "\"=&v\"(ua" << j << "), \"=&v\"(ub" << j << ")";
+        out << "\n                 :";
+        for (int j = 0; j < n; ++j) out << " \"v\"(a" << j << "), \"v\"(b" << j << "),";
+        out << " \"s\"(255.0f), \"v\"(8388608.0f));\n"
+            << "    MM_STORE_U32((unsigned *)((unsigned char *)A.out + (long)row_a * A.row_stride + (long)col * 4), " << word("a") << ");\n"
+            << "    MM_STORE_U32((unsigned *)((unsigned char *)A.out + (long)row_b * A.row_stride + (long)col * 4), " << word("b") << ");\n"
+            << "    return;\n  }\n  mm_tup<4> ra, rb;\n";
+        for (int i = 0; i < 4; ++i) {
+            if (pk.src[i] < 0) out << "  ra.v[" << i << "] = rb.v[" << i << "] = " << float_literal(pk.lit[i]) << "f;\n";
+            else out << "  ra.v[" << i << "] = a" << pk.src[i] << "; rb.v[" << i << "] = b" << pk.src[i] << ";\n";
+        }
+        out << "  mm_store_pixel(A, row_a, col, ra);\n  mm_store_pixel(A, row_b, col, rb);\n}\n";
     }
     // two pixels (rows mm_p and mm_p + 1 of this work-item's column) in lockstep
     void emit_pixel_loop(const std::string &I) override {
@@ -636,6 +841,17 @@ MM_DEV int mm_s2v(int u) { int r; asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(__built
         for (Value *v : env.pix_defs)
             if (v->index >= 0 && seen.insert(v).second) out << I << "  " << pair_ctype(v) << " " << vname(v) << ";\n";
         stmts(code.body, I + "  ", "mm_bu(true)");
+        Pack pk;
+        if (plan_pack(pk)) {
+            out << I << "  // a row past the end was evaluated as the last row: storing it there again writes the same bytes\n"
+                << I << "  mm_store_pair(A, row_a, row_b, col";
+            for (const Value *v : pk.vals) {
+                const std::string e = pprim(Primary::V(const_cast<Value *>(v)), Ty::Float);
+                out << ", " << e << ".x, " << e << ".y";
+            }
+            out << ");\n" << I << "}\n";
+            return;
+        }
         out << I << "  mm_tup<4> mm_ra, mm_rb;\n";
         for (int i = 0; i < 4; ++i) {
             const std::string v = pprim(Primary::V(code.result[i]), Ty::Float);

@@ -13,6 +13,8 @@ bool common_subexpressions(FilterCode &code);
 void optimize(FilterCode &code);
 void analyze_frame_constants(FilterCode &code);
 void specialize_constants(FilterCode &code);   // specialize.cpp
+// Copies the first trip of loops that are provably entered in front of them where it folds (specialize.cpp); true: some loop was peeled
+bool peel_first_trips(FilterCode &code);
 // Folds `op` applied to literal arguments with the C semantics of its macro; false when the
 // op is not one of the foldable arithmetic / comparison ops.  specialize.cpp
 bool fold_constant_op(const OpInfo *op, const std::vector<Primary> &args, Primary &out);

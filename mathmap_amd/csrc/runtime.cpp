@@ -87,7 +87,7 @@ static void generate_closure_kernels(mmhip_filter *f, const KernelOptions &ko) {
     }
 }
 
-static mmhip_filter *compile_source(const char *source, const mmhip_options *opts, const std::map<int, Primary> *consts) {
+static mmhip_filter *compile_source(const char *source, const mmhip_options *opts, const std::map<int, Primary> *consts, bool peel = true) {
     if (!mmhip_check_options(opts)) return nullptr;
     std::unique_ptr<mmhip_filter> f(new mmhip_filter());
     try {
@@ -97,6 +97,9 @@ static mmhip_filter *compile_source(const char *source, const mmhip_options *opt
         f->code = lower_filter(f->module, f->module.main, consts);
         f->ir_json_raw = dump_ir(*f->code);
         if (consts) specialize_constants(*f->code);
+        // a first loop trip that folds is peeled for kernels in exit-driven pair mode only; whether this one is shows when
+        // it has been generated, so the peeled code is a trial: kept below, or the filter is compiled again without it
+        const bool peeled = consts && peel && pair_peel_enabled() && peel_first_trips(*f->code);
         optimize(*f->code);
         analyze_frame_constants(*f->code);
         for (auto &sub : f->code->closure_renders) {
@@ -121,6 +124,7 @@ static mmhip_filter *compile_source(const char *source, const mmhip_options *opt
         f->kopt = ko;
         f->ir_json = dump_ir(*f->code);
         f->ks = generate_hip(*f->code, ko);
+        if (peeled && !f->ks.pair_exit) return compile_source(source, opts, consts, false);
         generate_closure_kernels(f.get(), ko);
     } catch (const CompileError &e) {
         g_err = e.what();
@@ -1221,19 +1225,24 @@ static void bake_uservals(Block &b, const std::map<int, Primary> &consts) {
     }
 }
 
-static mmhip_filter *compile_ir_specialized(const mmhip_filter *f, const std::map<int, Primary> &consts) {
+static mmhip_filter *compile_ir_specialized(const mmhip_filter *f, const std::map<int, Primary> &consts, bool peel = true) {
     mmhip_filter *sp = mmhip_filter_new_empty();
     try {
         sp->code.reset(new FilterCode());
         load_ir_json(sp->module, *sp->code, (f->ir_json_raw.empty() ? f->ir_json : f->ir_json_raw).c_str());
         bake_uservals(sp->code->body, consts);
         specialize_constants(*sp->code);
+        const bool peeled = peel && pair_peel_enabled() && peel_first_trips(*sp->code);      // a trial, as in compile_source
         for (auto &sub : sp->code->closure_renders) {
             bake_uservals(sub->body, consts);
             specialize_constants(*sub);
         }
         std::string err;
         if (!mmhip_filter_finalize(sp, f->kopt, &err)) throw CompileError(err);
+        if (peeled && !sp->ks.pair_exit) {
+            mmhip_filter_free(sp);
+            return compile_ir_specialized(f, consts, false);
+        }
         sp->opts = f->opts;
         sp->opts.specialize_uservals = 0;
     } catch (const std::exception &e) {

@@ -325,6 +325,243 @@ void specialize_constants(FilterCode &code) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// Peeling a first trip that folds: `while (c) B` becomes `B0; while (c) B`
+// ---------------------------------------------------------------------------
+// A specialised loop often enters with literals in its phis (Mandelbrot: c = 0, iter = 0).  The phis hide them from the
+// constant propagation above -- the meet of the initial and the next value is Bottom -- so the first trip computes
+// `0 * 0 + p` and `0 < 31` for every pixel.  Where the entry condition, evaluated on the phis' initial values, is
+// the literal true, the first trip is copied in front of the loop with those values substituted (B0), and the phis start
+// from what B0 leaves.  In B0 only folds that are exact for every input are made: an operator all of whose operands are
+// literals, through fold_impl; sqrt of a literal whose root is exact (a perfect square: any correct sqrt returns it);
+// an `if` on a literal condition keeps its live side.  `0 + x` stays an addition (x may be -0), `x * 0` with a
+// per-pixel x stays a product.
+// Rule: a loop is peeled when B0 has at most three quarters of the body's statements (assignments, phis and control
+// statements, counted through nested blocks), i.e. at least a quarter of the first trip folds away; a loop whose first trip
+// is no cheaper than any other only grows the kernel.
+namespace {
+
+struct Peel {
+    using Map = std::map<const Value *, Primary>;
+    FilterCode &code;
+    std::map<const Value *, const Stmt *> if_of;      // exit phi of an `if` -> the if
+    bool any = false;
+    // counting pass of clone(): nothing is allocated, values the copy would define stay unmapped (an unmapped value is no
+    // literal, like the copy's new value), so the same operations fold and `emitted` is what the real copy will have
+    bool dry = false;
+
+    explicit Peel(FilterCode &c) : code(c) { scan(c.body); }
+
+    void scan(const Block &b) {
+        for (const Stmt *s : b) {
+            if (s->kind == Stmt::If) {
+                for (const Stmt *ph : s->phis) if_of[ph->lhs] = s;
+                scan(s->then_);
+                scan(s->else_);
+            } else if (s->kind == Stmt::While)
+                scan(s->body);
+        }
+    }
+    static bool is_lit(const Primary &p) { return p.kind == Primary::IntConst || p.kind == Primary::FloatConst; }
+    static bool truthy(const Primary &p) { return p.kind == Primary::IntConst ? p.i != 0 : p.f != 0.0f; }
+
+    // an operator on literals, exactly; the result converted like the assignment to a variable of type `lhs` does
+    static bool fold_exact(const OpInfo *op, const std::vector<Primary> &a, Ty lhs, Primary &out) {
+        if (!op->pure) return false;
+        for (const Primary &p : a) if (!is_lit(p)) return false;
+        if (!strcmp(op->cname, "sqrt") && a.size() == 1) {
+            const double x = as_double(a[0]), r = std::sqrt(x);
+            if (!(x >= 0.0) || r * r != x || (double)(float)r != r) return false;
+            out = Primary::F((float)r);
+        } else if (!fold_impl(op, a, out))
+            return false;
+        return convert_to(lhs, out);
+    }
+    // the value of `p` where it is a literal by exact folds of the straight-line code and the `if`s that define it
+    bool const_eval(const Primary &p, Primary &out, int depth = 0) const {
+        if (is_lit(p)) { out = p; return true; }
+        if (p.kind != Primary::Val || depth > 64) return false;
+        const Value *v = p.value;
+        const Ty t = v->var->type;
+        if (v->index < 0) { out = Primary::I(0); return convert_to(t, out); }      // uninitialised: reads as 0
+        const Stmt *d = v->def;
+        if (!d) return false;
+        if (d->kind == Stmt::Assign && d->rhs.kind == Rhs::Prim) return const_eval(d->rhs.prim, out, depth + 1) && convert_to(t, out);
+        if (d->kind == Stmt::Assign && d->rhs.kind == Rhs::Op) {
+            std::vector<Primary> a(d->rhs.args.size());
+            for (size_t i = 0; i < a.size(); ++i) if (!const_eval(d->rhs.args[i], a[i], depth + 1)) return false;
+            return fold_exact(d->rhs.op, a, t, out);
+        }
+        auto it = if_of.find(v);
+        if (d->kind != Stmt::Phi || it == if_of.end() || it->second->cond.kind != Rhs::Prim) return false;
+        Primary c;
+        if (!const_eval(it->second->cond.prim, c, depth + 1)) return false;
+        const Rhs &side = truthy(c) ? d->rhs : d->rhs2;
+        return side.kind == Rhs::Prim && const_eval(side.prim, out, depth + 1) && convert_to(t, out);
+    }
+
+    static int count(const Block &b) {
+        int n = 0;
+        for (const Stmt *s : b) {
+            ++n;
+            if (s->kind == Stmt::If) n += (int)s->phis.size() + count(s->then_) + count(s->else_);
+            if (s->kind == Stmt::While) n += (int)s->phis.size() + count(s->body);
+        }
+        return n;
+    }
+    static Primary mapped(const Map &m, const Primary &p) {
+        if (p.kind == Primary::Val) { auto it = m.find(p.value); if (it != m.end()) return it->second; }
+        return p;
+    }
+    static Rhs mapped(const Map &m, const Rhs &r) {
+        Rhs o = r;
+        if (o.kind == Rhs::Prim) o.prim = mapped(m, o.prim);
+        for (Primary &a : o.args) a = mapped(m, a);
+        return o;
+    }
+    Stmt *new_def(Stmt::Kind k, const Stmt *like, Stmt *parent, Map &m) {
+        Stmt *n = code.new_stmt(k);
+        n->lhs = code.new_value(like->lhs->var);
+        n->lhs->def = n;
+        n->parent = parent;
+        n->closure_id = like->closure_id;
+        m[like->lhs] = Primary::V(n->lhs);
+        return n;
+    }
+    // `lhs = p`: a literal that converts becomes the value itself, anything else a copy
+    void bind(const Stmt *like, const Primary &p, Block &out, Stmt *parent, Map &m, int &emitted) {
+        Primary lit = p;
+        if (is_lit(p) && convert_to(like->lhs->var->type, lit)) { m[like->lhs] = lit; return; }
+        ++emitted;
+        if (dry) return;
+        Stmt *n = new_def(Stmt::Assign, like, parent, m);
+        n->rhs = Rhs::P(p);
+        out.push_back(n);
+    }
+    // copies `b` with the operands mapped, folding what is exact; `emitted`: the statements the copy has
+    void clone(const Block &b, Block &out, Stmt *parent, Map &m, int &emitted) {
+        for (const Stmt *s : b) {
+            if (s->kind == Stmt::Assign) {
+                Rhs r = mapped(m, s->rhs);
+                Primary lit;
+                if (r.kind == Rhs::Prim) { bind(s, r.prim, out, parent, m, emitted); continue; }
+                if (r.kind == Rhs::Op && fold_exact(r.op, r.args, s->lhs->var->type, lit)) { m[s->lhs] = lit; continue; }
+                ++emitted;
+                if (dry) continue;
+                Stmt *n = new_def(Stmt::Assign, s, parent, m);
+                n->rhs = r;
+                out.push_back(n);
+            } else if (s->kind == Stmt::If) {
+                const Rhs c = mapped(m, s->cond);
+                if (c.kind == Rhs::Prim && is_lit(c.prim)) {      // the live side, the exit phis as copies
+                    const bool t = truthy(c.prim);
+                    clone(t ? s->then_ : s->else_, out, parent, m, emitted);
+                    for (const Stmt *ph : s->phis) bind(ph, mapped(m, t ? ph->rhs : ph->rhs2).prim, out, parent, m, emitted);
+                    continue;
+                }
+                emitted += 1 + (int)s->phis.size();
+                if (dry) {
+                    clone(s->then_, out, parent, m, emitted);
+                    clone(s->else_, out, parent, m, emitted);
+                    continue;
+                }
+                Stmt *n = code.new_stmt(Stmt::If);
+                n->parent = parent;
+                n->cond = c;
+                clone(s->then_, n->then_, n, m, emitted);
+                clone(s->else_, n->else_, n, m, emitted);
+                for (const Stmt *ph : s->phis) {
+                    const Rhs a = mapped(m, ph->rhs), b2 = mapped(m, ph->rhs2);
+                    Stmt *np = new_def(Stmt::Phi, ph, n, m);
+                    np->rhs = a;
+                    np->rhs2 = b2;
+                    n->phis.push_back(np);
+                }
+                out.push_back(n);
+            } else if (s->kind == Stmt::While) {
+                emitted += 1 + (int)s->phis.size();
+                if (dry) { clone(s->body, out, parent, m, emitted); continue; }
+                Stmt *n = code.new_stmt(Stmt::While);
+                n->parent = parent;
+                std::vector<Stmt *> nps;
+                for (const Stmt *ph : s->phis) {
+                    const Rhs init = mapped(m, ph->rhs);      // evaluated in the enclosing scope
+                    Stmt *np = new_def(Stmt::Phi, ph, n, m);
+                    np->rhs = init;
+                    n->phis.push_back(np);
+                    nps.push_back(np);
+                }
+                n->cond = mapped(m, s->cond);
+                clone(s->body, n->body, n, m, emitted);
+                for (size_t i = 0; i < nps.size(); ++i) nps[i]->rhs2 = mapped(m, s->phis[i]->rhs2);
+                out.push_back(n);
+            }
+        }
+    }
+    static bool plain(const Block &b) {      // only statements the copy knows how to make
+        for (const Stmt *s : b) {
+            if (s->kind == Stmt::Assign) { if (s->rhs.kind != Rhs::Prim && s->rhs.kind != Rhs::Op && s->rhs.kind != Rhs::Internal) return false; }
+            else if (s->kind == Stmt::If) {
+                if (!plain(s->then_) || !plain(s->else_)) return false;
+                for (const Stmt *ph : s->phis) if (ph->rhs.kind != Rhs::Prim || ph->rhs2.kind != Rhs::Prim) return false;
+            } else if (s->kind == Stmt::While) {
+                if (!plain(s->body)) return false;
+                for (const Stmt *ph : s->phis) if (ph->rhs.kind != Rhs::Prim || ph->rhs2.kind != Rhs::Prim) return false;
+            } else
+                return false;
+        }
+        return true;
+    }
+    bool peel(Stmt *w, Block &out) {
+        if (w->cond.kind != Rhs::Prim || w->cond.prim.kind != Primary::Val || !plain(w->body)) return false;
+        const Stmt *cph = nullptr;
+        for (const Stmt *ph : w->phis) {
+            if (ph->rhs.kind != Rhs::Prim || ph->rhs2.kind != Rhs::Prim) return false;
+            if (ph->lhs == w->cond.prim.value) cph = ph;
+        }
+        Primary c0;
+        if (!cph || !const_eval(cph->rhs.prim, c0) || !truthy(c0)) return false;      // not provably entered
+        Map m0;
+        for (const Stmt *ph : w->phis) {
+            Primary init;
+            m0[ph->lhs] = const_eval(ph->rhs.prim, init) ? init : ph->rhs.prim;
+        }
+        // the rule (above), on a counting pass: a loop that is not peeled leaves the code as it was, value numbers included
+        Block b0;
+        Map m = m0;
+        int emitted = 0;
+        dry = true;
+        clone(w->body, b0, w->parent, m, emitted);
+        dry = false;
+        if (emitted * 4 > count(w->body) * 3) return false;
+        m = m0;
+        clone(w->body, b0, w->parent, m, emitted);
+        for (Stmt *ph : w->phis) ph->rhs = Rhs::P(mapped(m, ph->rhs2.prim));
+        for (Stmt *s : b0) out.push_back(s);
+        return true;
+    }
+    void walk(Block &b) {
+        Block out;
+        for (Stmt *s : b) {
+            if (s->kind == Stmt::If) { walk(s->then_); walk(s->else_); }
+            if (s->kind == Stmt::While) {
+                walk(s->body);
+                if (peel(s, out)) any = true;
+            }
+            out.push_back(s);
+        }
+        b.swap(out);
+    }
+};
+
+}  // namespace
+
+bool peel_first_trips(FilterCode &code) {
+    Peel p(code);
+    p.walk(code.body);
+    return p.any;
+}
+
 bool fold_constant_op(const OpInfo *op, const std::vector<Primary> &args, Primary &out) { return fold_impl(op, args, out); }
 
 }  // namespace mm
