@@ -233,7 +233,7 @@ int mmhip_render(mmhip_invocation *inv, int frame, float t, int region_x, int re
        mmhip_clip_native_* counters report this path; mmhip_clip_batched_launches and mmhip_clip_prologue_frames
        stay those of filters without native calls.
      - Asynchronous like mmhip_render.  With mmhip_enable_timing, mmhip_drain_kernel_ms reports one entry per batch.
-     - Supersampling is not batched: use mmhip_render_supersampled per frame.
+     - Supersampled clips (the CLI's -o) are mmhip_render_clip_supersampled's: two of these calls and one combine per batch.
    Errors: num_frames < 1; frames or ts NULL; a frame_stride smaller than the band; mmhip_render's own. */
 int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int region_x, int region_y,
                       int region_w, int region_h, int first_row, int last_row, void *out_device, int row_stride,
@@ -253,6 +253,34 @@ long mmhip_clip_native_direct_frames(mmhip_invocation *inv);
    call_invocation, mathmap_common.c:880-927).  Compile the filter with supersampling = 1. */
 int mmhip_render_supersampled(mmhip_invocation *inv, int frame, float t, int region_x, int region_y, int region_w,
                               int region_h, void *out_device, int row_stride, int bpp, void *stream);
+/* A supersampled clip (an extension): frame i at out_device + i * frame_stride receives exactly the bytes
+   mmhip_render_supersampled(inv, frames[i], ts[i], region..., row_stride, bpp, stream) writes; bytes between rows and
+   between frames are not touched.  frames, ts, frame_stride and the errors are mmhip_render_clip's; asynchronous.
+     - The clip is cut into batches.  Per batch: mmhip_render_clip of the long slices (region_w + 1 columns, sampling
+       offsets -0.5) into a temporary of the invocation's whose rows are a multiple of 16 bytes apart, mmhip_render_clip
+       of the short slices (offsets 0), and one launch of the combine over all frames of the batch -- two batched pixel
+       launches and one combine where the loop makes three launches and two prologues per frame.  The invocation's own
+       sampling offsets are put back on every return.
+     - Frames per batch: what either slice's clip launch takes at once (mmhip_filter_clip_batch_plan's caps), at most
+       65 535, and MMHIP_CLIP_SS_BYTES (read once, default 2 GiB) / bytes_per_frame, where bytes_per_frame = region_h *
+       (long_pitch + region_w * bpp) and long_pitch is (region_w + 1) * bpp rounded up to 16.
+     - Filters that call native filters or render closure images are not batched: for them the call is the loop of
+       mmhip_render_supersampled (their nested renders share the native results between the two slices of a frame).
+       Nothing is refused and the bytes are the same; mmhip_clip_supersampled_batches stays 0.
+     - mmhip_clip_batched_launches rises by 2 per batch (the nested clip calls'), mmhip_clip_supersampled_batches by 1.
+       With mmhip_enable_timing the pixel entries are the nested calls' and the combine is reported by
+       mmhip_drain_native_kernel_ms as supersample_combine_clip. */
+int mmhip_render_clip_supersampled(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts,
+                                   int region_x, int region_y, int region_w, int region_h, void *out_device, int row_stride,
+                                   int64_t frame_stride, int bpp, void *stream);
+long mmhip_clip_supersampled_batches(mmhip_invocation *inv);
+/* How mmhip_render_clip_supersampled renders `frames` frames of a region (needs no GPU).  out[] receives
+   MMHIP_CLIP_SS_PLAN_FIELDS values: batched (0: the loop of mmhip_render_supersampled), frames_per_batch, batches,
+   bytes_per_frame (the two slices of one frame in the temporary), long_pitch (bytes between the long slice's rows), and
+   the rows_per_item and pixels_per_item of the combine kernel (a work-item combines pixels_per_item adjacent pixels
+   over rows_per_item rows). */
+enum { MMHIP_CLIP_SS_PLAN_FIELDS = 7 };
+int mmhip_filter_clip_supersample_plan(const mmhip_filter *f, int region_w, int region_h, int bpp, int frames, int64_t *out);
 /* Convenience: whole frame to a host RGBA8 buffer (width*height*4 bytes); synchronous. */
 int mmhip_render_host(mmhip_invocation *inv, int frame, float t, uint8_t *out_rgba);
 int mmhip_sync(mmhip_invocation *inv);

@@ -26,6 +26,8 @@ GEOMETRY_FIELDS = ("tiles_x", "tiles_y", "wg1", "nwg", "ppt", "tile_w", "tile_h"
 CLIP_PLAN_FIELDS = ("grid_x", "frames_per_batch", "batches", "shared_slot")
 # mmhip_filter_clip_native_plan's out[]
 CLIP_NATIVE_PLAN_FIELDS = ("eligible", "frames_per_batch", "batches", "bytes_per_frame")
+# mmhip_filter_clip_supersample_plan's out[]
+CLIP_SS_PLAN_FIELDS = ("batched", "frames_per_batch", "batches", "bytes_per_frame", "long_pitch", "rows_per_item", "pixels_per_item")
 
 
 class MathMapError(RuntimeError):
@@ -198,6 +200,14 @@ class Filter:
         if lib().mmhip_filter_clip_native_plan(self._h, region_w, num_rows, rw, rh, frames, out) != 0:
             raise MathMapError(_err())
         return dict(zip(CLIP_NATIVE_PLAN_FIELDS, out))
+
+    def clip_supersample_plan(self, region_w, region_h, frames, bpp=4):
+        """How render_clip(supersample=True) renders a `frames`-frame clip of a region: a dict of the CLIP_SS_PLAN_FIELDS
+        (batched 0: the loop of single supersampled renders)."""
+        out = (C.c_int64 * len(CLIP_SS_PLAN_FIELDS))()
+        if lib().mmhip_filter_clip_supersample_plan(self._h, region_w, region_h, bpp, frames, out) != 0:
+            raise MathMapError(_err())
+        return dict(zip(CLIP_SS_PLAN_FIELDS, out))
 
     @property
     def clip_kernel_source(self):
@@ -392,13 +402,18 @@ class Invocation:
                                        row_stride, bpp, 1 if floatmap else 0, C.c_void_p(stream)))
 
     def render_clip(self, num_frames=None, frames=None, ts=None, out_ptr=None, rows=None, region=None, row_stride=None,
-                    frame_stride=None, bpp=4, floatmap=False, stream=0):
+                    frame_stride=None, bpp=4, floatmap=False, stream=0, supersample=False):
         """Renders a clip in batched launches (mmhip_render_clip): frame i at frame number frames[i] and time ts[i].
         `num_frames`=N alone is the CLI's animation: frame = i, t = (float)i / (float)N.  `rows` = (first_row,
         last_row) and `region`, `row_stride`, `bpp`, `floatmap`, `stream` as in render_rows; frame i lands
         `frame_stride` bytes (default: one frame's band) behind frame i - 1.  Without `out_ptr` returns the frames as a
-        uint8 [N,H,W,4] array; with it the call is asynchronous and the frames stay in HBM."""
+        uint8 [N,H,W,4] array; with it the call is asynchronous and the frames stay in HBM.
+        `supersample`=True renders the CLI's -o frames (mmhip_render_clip_supersampled; compile the filter with
+        supersampling=True): whole regions of bytes only, so `rows` or `floatmap` with it is a ValueError; without
+        `out_ptr` it returns a uint8 [N,H,W,bpp] array."""
         from .striping import animation_frame_t
+        if supersample and (floatmap or rows is not None):
+            raise ValueError("render_clip: supersample=True renders whole regions of bytes: neither floatmap nor rows")
         if frames is None and ts is None:
             if num_frames is None:
                 raise MathMapError("render_clip: give num_frames, or frames and ts")
@@ -415,6 +430,8 @@ class Invocation:
         rx, ry, rw, rh = region if region is not None else (0, 0, self.render_width, self.render_height)
         first_row, last_row = rows if rows is not None else (ry, ry + rh)
         fp, tp = frames.ctypes.data_as(C.POINTER(C.c_int)), ts.ctypes.data_as(C.POINTER(C.c_float))
+        if supersample:
+            return self._render_clip_supersampled(num_frames, fp, tp, out_ptr, (rx, ry, rw, rh), row_stride, frame_stride, bpp, stream)
         if out_ptr is not None:
             if row_stride is None:
                 row_stride = rw * bpp
@@ -441,6 +458,37 @@ class Invocation:
         finally:
             lib().mmhip_device_free(C.c_void_p(dev))
         return out
+
+    def _render_clip_supersampled(self, num_frames, fp, tp, out_ptr, region, row_stride, frame_stride, bpp, stream):
+        rx, ry, rw, rh = region
+        if row_stride is None:
+            row_stride = rw * bpp
+        if frame_stride is None:
+            frame_stride = rh * row_stride
+        if out_ptr is not None:
+            self._check(lib().mmhip_render_clip_supersampled(self._h, num_frames, fp, tp, rx, ry, rw, rh, C.c_void_p(out_ptr),
+                                                             row_stride, frame_stride, bpp, C.c_void_p(stream)))
+            return None
+        if row_stride != rw * bpp or frame_stride != rh * rw * bpp:
+            raise MathMapError("render_clip without out_ptr returns packed frames: pass out_ptr for padded rows and frames")
+        if num_frames < 1:
+            raise MathMapError("render_clip: num_frames must be at least 1")
+        out = np.empty((num_frames, rh, rw, bpp), dtype=np.uint8)
+        dev = lib().mmhip_device_alloc(out.nbytes)
+        if not dev:
+            raise MathMapError(_err())
+        try:
+            self._check(lib().mmhip_render_clip_supersampled(self._h, num_frames, fp, tp, rx, ry, rw, rh, C.c_void_p(dev),
+                                                             row_stride, frame_stride, bpp, None))
+            self.sync()
+            self._check(lib().mmhip_copy_to_host(out.ctypes.data_as(C.c_void_p), C.c_void_p(dev), out.nbytes))
+        finally:
+            lib().mmhip_device_free(C.c_void_p(dev))
+        return out
+
+    def clip_supersampled_batches(self):
+        """Batches render_clip(supersample=True) ran batched (0 for filters it renders frame by frame)."""
+        return lib().mmhip_clip_supersampled_batches(self._h)
 
     def clip_batched_launches(self):
         """Batched pixel launches of render_clip so far (0 for filters it renders frame by frame)."""

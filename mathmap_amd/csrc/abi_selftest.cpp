@@ -545,4 +545,69 @@ int mmhip_selftest_gauss_tolerance_map(const uint8_t *rgb, int w, int h, float h
     return mmhip_copy_to_host(map, inv->natives[0].map.get(), (size_t)w * h * 16) == 0 ? 0 : -1;
 }
 
+// The two supersampling combines on the same slices (tools/clip_ss_cost.py, tests/test_gpu_clip_supersample.py): `frames`
+// frames of w x h slices of pseudo-random bytes (every frame its own copy, for either kernel), combined frame by frame by launch_supersample_combine (what
+// mmhip_render_supersampled runs) and by one launch_supersample_combine_clip, alternating for `rounds` rounds with device
+// events around each; ms[2 * r] receives the old kernel's milliseconds for all frames of round r, ms[2 * r + 1] the new
+// one's.  Returns the number of output bytes in which the two differ (0 is what is wanted), or -1.
+long mmhip_selftest_combine_ms(int w, int h, int bpp, int frames, int rounds, double *ms) {
+    if (w < 1 || h < 1 || bpp < 1 || bpp > 4 || frames < 1 || frames > 65535 || rounds < 1) { g_selftest_err = "combine: bad arguments"; return -1; }
+    const size_t packed = (size_t)(w + 1) * bpp, pitch = mm::supersample_clip_long_pitch(w, bpp), short_row = (size_t)w * bpp;
+    const size_t long_old = packed * h, long_new = pitch * h, short_bytes = short_row * h, out_bytes = short_row * h;
+    std::vector<unsigned char> host(long_old + short_bytes);
+    uint64_t x = 0x9e3779b97f4a7c15ull;
+    for (size_t i = 0; i < host.size(); ++i) {
+        x ^= x << 13; x ^= x >> 7; x ^= x << 17;
+        host[i] = (unsigned char)(x >> 32);
+    }
+    DeviceBuffer old_slices, new_longs, new_shorts, out_old, out_new;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto ok = [](hipError_t e) { if (e != hipSuccess) g_selftest_err = std::string("combine: ") + hipGetErrorString(e); return e == hipSuccess; };
+    long result = -1;
+    std::string err;
+    mm::NativeWorkspace ws;
+    do {
+        if (!ok(old_slices.grow(host.size() * frames)) || !ok(new_longs.grow(long_new * frames)) || !ok(new_shorts.grow(short_bytes * frames)) ||
+            !ok(out_old.grow(out_bytes * frames)) || !ok(out_new.grow(out_bytes * frames)) || !ok(hipEventCreate(&e0)) || !ok(hipEventCreate(&e1)))
+            break;
+        if (!ok(hipMemcpy(old_slices.get(), host.data(), host.size(), hipMemcpyHostToDevice)) || !ok(hipMemset(new_longs.get(), 0x5a, long_new * frames)))
+            break;
+        bool copied = true;
+        for (int i = 0; i < frames && copied; ++i)
+            copied = (i == 0 || ok(hipMemcpy(old_slices.get<unsigned char>() + i * host.size(), old_slices.get(), host.size(), hipMemcpyDeviceToDevice))) &&
+                     ok(hipMemcpy2D(new_longs.get<unsigned char>() + i * long_new, pitch, old_slices.get(), packed, packed, h, hipMemcpyDeviceToDevice)) &&
+                     ok(hipMemcpy(new_shorts.get<unsigned char>() + i * short_bytes, old_slices.get<unsigned char>() + long_old, short_bytes, hipMemcpyDeviceToDevice));
+        if (!copied) break;
+        bool ran = true;
+        for (int r = -1; r < rounds && ran; ++r) {          // round -1 warms up
+            float t_old = 0, t_new = 0;
+            ran = ok(hipEventRecord(e0, nullptr));
+            for (int i = 0; i < frames; ++i)
+                mm::launch_supersample_combine(old_slices.get<unsigned char>() + i * host.size(), old_slices.get<unsigned char>() + i * host.size() + long_old,
+                                               out_old.get<unsigned char>() + i * out_bytes, w, h, bpp, (int)short_row, nullptr);
+            ran = ran && ok(hipEventRecord(e1, nullptr)) && ok(hipEventSynchronize(e1)) && ok(hipEventElapsedTime(&t_old, e0, e1)) && ok(hipEventRecord(e0, nullptr));
+            if (ran && mm::launch_supersample_combine_clip(new_longs.get<unsigned char>(), new_shorts.get<unsigned char>(), out_new.get<unsigned char>(), w, h,
+                                                          bpp, (int)short_row, (int64_t)out_bytes, frames, ws, nullptr, &err) != 0) {
+                g_selftest_err = err;
+                ran = false;
+            }
+            ran = ran && ok(hipEventRecord(e1, nullptr)) && ok(hipEventSynchronize(e1)) && ok(hipEventElapsedTime(&t_new, e0, e1));
+            if (r >= 0) { ms[2 * r] = t_old; ms[2 * r + 1] = t_new; }
+        }
+        if (!ran) break;
+        std::vector<unsigned char> a(out_bytes), b(out_bytes);
+        long differ = 0;
+        bool read = true;
+        for (int i = 0; i < frames && read; ++i) {
+            read = ok(hipMemcpy(a.data(), out_old.get<unsigned char>() + i * out_bytes, out_bytes, hipMemcpyDeviceToHost)) &&
+                   ok(hipMemcpy(b.data(), out_new.get<unsigned char>() + i * out_bytes, out_bytes, hipMemcpyDeviceToHost));
+            for (size_t k = 0; k < out_bytes && read; ++k) differ += a[k] != b[k];
+        }
+        if (read) result = differ;
+    } while (false);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return result;
+}
+
 }  // extern "C"

@@ -422,8 +422,7 @@ int main(int argc, char **argv) {
         return true;
     };
     // --batch-frames=K: K frames per clip render (one batched launch where the filter allows it), then the files one by
-    // one; a batch's frames stay under 1 GiB of device memory.  (Supersampled frames are rendered one at a time.)
-    if (supersampling) batch_frames = 1;
+    // one; a batch's frames stay under 1 GiB of device memory.  With -o the clip is a supersampled one.
     batch_frames = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch_frames, num_frames), ((size_t)1 << 30) / output.size()));
     void *dev = mmhip_device_alloc(output.size() * batch_frames);
     if (!dev) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
@@ -436,8 +435,12 @@ int main(int argc, char **argv) {
                 frames[i] = first + i;
                 ts[i] = (float)(first + i) / (float)num_frames;       // mathmap_cmdline.c:835
             }
-            if (mmhip_render_clip(inv, n, frames.data(), ts.data(), 0, 0, img_width, img_height, 0, img_height, dev, img_width * 4,
-                                  (int64_t)output.size(), 4, 0, nullptr) != 0 || mmhip_sync(inv) != 0) {
+            const int rc = supersampling
+                               ? mmhip_render_clip_supersampled(inv, n, frames.data(), ts.data(), 0, 0, img_width, img_height, dev,
+                                                                img_width * 4, (int64_t)output.size(), 4, nullptr)
+                               : mmhip_render_clip(inv, n, frames.data(), ts.data(), 0, 0, img_width, img_height, 0, img_height, dev,
+                                                   img_width * 4, (int64_t)output.size(), 4, 0, nullptr);
+            if (rc != 0 || mmhip_sync(inv) != 0) {
                 fprintf(stderr, "Error: %s\n", mmhip_last_error());
                 return 1;
             }

@@ -124,5 +124,16 @@ void launch_render_drawable(const HImageDesc &in, const HImage &img, const Nativ
 
 void launch_supersample_combine(const unsigned char *longs, const unsigned char *shorts, unsigned char *out, int w, int h,
                                 int bpp, int out_stride, hipStream_t s);
+// The combine over `frames` supersampled frames of a clip in one launch (k_supersample_combine_clip): frame i's long slice
+// at longs + i * h * long_pitch with rows supersample_clip_long_pitch(w, bpp) bytes apart, its short slice at shorts +
+// i * h * w * bpp (packed), its output at out + i * frame_stride.  A work-item combines SS_CLIP_PIXELS adjacent pixels
+// over SS_CLIP_ROWS rows; supersample_clip_items: the work-items of one frame (the launch takes fewer than 2^31).
+// Timed through ws.timed_launch as supersample_combine_clip.
+constexpr int SS_CLIP_ROWS = 8, SS_CLIP_PIXELS = 4;
+size_t supersample_clip_long_pitch(int w, int bpp);
+int64_t supersample_clip_items(int w, int h);
+int launch_supersample_combine_clip(const unsigned char *longs, const unsigned char *shorts, unsigned char *out, int w, int h,
+                                    int bpp, int row_stride, int64_t frame_stride, int frames, NativeWorkspace &ws, hipStream_t s,
+                                    std::string *err);
 
 }  // namespace mm

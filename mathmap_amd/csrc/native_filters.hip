@@ -11,6 +11,7 @@
 // Data layout: float maps are float[h][w][4] interleaved in HBM (floatmap.c:30-46), a
 // 16384^2 map is 4.29 GB; all intermediates stay on the device.
 #include "native_filters.h"
+#include "mm_ss_combine.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1274,6 +1275,152 @@ void launch_supersample_combine(const unsigned char *longs, const unsigned char 
                                 int bpp, int out_stride, hipStream_t s) {
     const long n = (long)w * h * bpp;
     k_supersample_combine<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(longs, shorts, out, w, h, bpp, out_stride);
+}
+
+// ---- the combine over the frames of a supersampled clip (mmhip_render_clip_supersampled) ----
+// The same bytes as k_supersample_combine, frame blockIdx.y of a batch per grid row.  A work-item owns SS_CLIP_PIXELS
+// adjacent pixels (a column group) over a strip of SS_CLIP_ROWS rows; blockIdx.x counts the items of one frame, column
+// groups fastest, so that a wave reads and writes runs of adjacent bytes.  The long slices' rows are long_pitch (a
+// multiple of 16) bytes apart, the short slices' rows are packed.
+struct SsClipArgs {
+    const unsigned char *longs, *shorts;
+    unsigned char *out;
+    long long long_frame, short_frame, frame_stride;      // bytes from a frame to the next
+    unsigned long_pitch, short_pitch;
+    int row_stride;
+    int w, h;
+    unsigned groups, items;                               // column groups of a row; work-items of a frame
+};
+
+typedef uint32_t ss_u32x4 __attribute__((ext_vector_type(4)));
+typedef ss_u32x4 ss_u32x4_a4 __attribute__((aligned(4)));      // a short row's group: dword-aligned only
+
+// Pair sums of the group's four pixels from texels 4g .. 4g + 4 of a long row: the aligned 16 bytes and the texel behind them.
+__device__ __forceinline__ void ss_long_sums(const unsigned char *row, bool fifth, mm_ss_halves sums[4]) {
+    const ss_u32x4 v = *(const ss_u32x4 *)row;
+    const uint32_t f = fifth ? *(const uint32_t *)(row + 16) : 0u;
+    sums[0] = mm_ss_pair_sum(v.x, v.y);
+    sums[1] = mm_ss_pair_sum(v.y, v.z);
+    sums[2] = mm_ss_pair_sum(v.z, v.w);
+    sums[3] = mm_ss_pair_sum(v.w, f);
+}
+
+// bpp 4, output dword-aligned (STORE16: 16-byte aligned, one store per row).  A long row is read once per strip (and
+// the strip's first row once more): the pair sums of row r + 1 stay in registers for row r + 1's own turn.
+template <bool STORE16>
+__global__ void __launch_bounds__(256) k_supersample_combine_clip(const SsClipArgs a) {
+    const unsigned item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= a.items) return;
+    const unsigned strip = item / a.groups, g = item - strip * a.groups;
+    const size_t fi = blockIdx.y;
+    const unsigned char *__restrict__ L = a.longs + fi * a.long_frame + (size_t)g * 16;
+    const unsigned char *__restrict__ S = a.shorts + fi * a.short_frame + (size_t)g * 16;
+    unsigned char *__restrict__ O = a.out + fi * a.frame_stride + (size_t)g * 16;
+    const int r0 = (int)strip * SS_CLIP_ROWS;
+    const int real = min(4, a.w - (int)g * 4);            // the last group of a row may hold 1 - 3 pixels
+    mm_ss_halves top[4], bot[4];
+    if (real == 4 && r0 + SS_CLIP_ROWS < a.h) {           // a whole group, and every row has a row below it
+        ss_long_sums(L + (size_t)r0 * a.long_pitch, true, top);
+#pragma unroll
+        for (int i = 0; i < SS_CLIP_ROWS; ++i) {
+            const int r = r0 + i;
+            ss_long_sums(L + (size_t)(r + 1) * a.long_pitch, true, bot);
+            const ss_u32x4 m = *(const ss_u32x4_a4 *)(S + (size_t)r * a.short_pitch);
+            ss_u32x4 o;
+            o.x = mm_ss_combine_word(top[0], bot[0], m.x);
+            o.y = mm_ss_combine_word(top[1], bot[1], m.y);
+            o.z = mm_ss_combine_word(top[2], bot[2], m.z);
+            o.w = mm_ss_combine_word(top[3], bot[3], m.w);
+            unsigned char *dst = O + (long long)r * a.row_stride;
+            if (STORE16) __builtin_nontemporal_store(o, (ss_u32x4 *)dst);
+            else
+                for (int k = 0; k < 4; ++k) __builtin_nontemporal_store(o[k], (uint32_t *)dst + k);
+            for (int k = 0; k < 4; ++k) top[k] = bot[k];
+        }
+        return;
+    }
+    // the frame's last strip and the row's last group: rows end at h (the last row's line3 is its line1, see
+    // k_supersample_combine), only `real` pixels are read from the short row and stored, and the texel behind the
+    // aligned 16 bytes is read only where the fourth pixel is real (the bytes of the 16 that no pixel launch wrote
+    // feed sums of pixels that are not stored)
+    const int r_end = min(r0 + SS_CLIP_ROWS, a.h);
+    ss_long_sums(L + (size_t)r0 * a.long_pitch, real == 4, top);
+    for (int r = r0; r < r_end; ++r) {
+        if (r + 1 < a.h) ss_long_sums(L + (size_t)(r + 1) * a.long_pitch, real == 4, bot);
+        else
+            for (int k = 0; k < 4; ++k) bot[k] = top[k];
+        const uint32_t *mid = (const uint32_t *)(S + (size_t)r * a.short_pitch);
+        uint32_t *dst = (uint32_t *)(O + (long long)r * a.row_stride);
+        for (int k = 0; k < 4; ++k)
+            if (k < real) __builtin_nontemporal_store(mm_ss_combine_word(top[k], bot[k], mid[k]), dst + k);
+        for (int k = 0; k < 4; ++k) top[k] = bot[k];
+    }
+}
+
+// Any bpp and any output alignment, byte by byte over the same grid (the rare path).
+template <int BPP>
+__global__ void __launch_bounds__(256) k_supersample_combine_clip_bytes(const SsClipArgs a) {
+    const unsigned item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= a.items) return;
+    const unsigned strip = item / a.groups, g = item - strip * a.groups;
+    const size_t fi = blockIdx.y;
+    const size_t col0 = (size_t)g * SS_CLIP_PIXELS * BPP;
+    const unsigned char *__restrict__ L = a.longs + fi * a.long_frame + col0;
+    const unsigned char *__restrict__ S = a.shorts + fi * a.short_frame + col0;
+    unsigned char *__restrict__ O = a.out + fi * a.frame_stride + col0;
+    const int r0 = (int)strip * SS_CLIP_ROWS, r_end = min(r0 + SS_CLIP_ROWS, a.h);
+    const int bytes = min(SS_CLIP_PIXELS, a.w - (int)g * SS_CLIP_PIXELS) * BPP;
+    for (int r = r0; r < r_end; ++r) {
+        const unsigned char *l1 = L + (size_t)r * a.long_pitch;
+        const unsigned char *l3 = L + (size_t)(r + 1 < a.h ? r + 1 : r) * a.long_pitch;
+        const unsigned char *l2 = S + (size_t)r * a.short_pitch;
+        unsigned char *dst = O + (long long)r * a.row_stride;
+        for (int b = 0; b < bytes; ++b)
+            dst[b] = (unsigned char)mm_ss_div6((uint32_t)l1[b] + l1[b + BPP] + 2u * l2[b] + l3[b] + l3[b + BPP]);
+    }
+}
+
+size_t supersample_clip_long_pitch(int w, int bpp) { return ((size_t)(w + 1) * bpp + 15) / 16 * 16; }
+
+int64_t supersample_clip_items(int w, int h) {
+    return (int64_t)((w + SS_CLIP_PIXELS - 1) / SS_CLIP_PIXELS) * ((h + SS_CLIP_ROWS - 1) / SS_CLIP_ROWS);
+}
+
+int launch_supersample_combine_clip(const unsigned char *longs, const unsigned char *shorts, unsigned char *out, int w, int h,
+                                    int bpp, int row_stride, int64_t frame_stride, int frames, NativeWorkspace &ws, hipStream_t s,
+                                    std::string *err) {
+    const int64_t items = supersample_clip_items(w, h);
+    const size_t long_pitch = supersample_clip_long_pitch(w, bpp);
+    if (items > 0x7fffffffLL || long_pitch > 0x7fffffffULL || frames < 1 || frames > 65535) {
+        *err = "supersample combine: the batch does not fit one launch";
+        return -1;
+    }
+    SsClipArgs a;
+    a.longs = longs;
+    a.shorts = shorts;
+    a.out = out;
+    a.long_pitch = (unsigned)long_pitch;
+    a.short_pitch = (unsigned)w * bpp;
+    a.long_frame = (long long)h * (long long)long_pitch;
+    a.short_frame = (long long)h * a.short_pitch;
+    a.frame_stride = frame_stride;
+    a.row_stride = row_stride;
+    a.w = w;
+    a.h = h;
+    a.groups = (unsigned)((w + SS_CLIP_PIXELS - 1) / SS_CLIP_PIXELS);
+    a.items = (unsigned)items;
+    const dim3 grid((unsigned)((items + 255) / 256), (unsigned)frames);
+    const uintptr_t align = (uintptr_t)out | (uintptr_t)row_stride | (uintptr_t)frame_stride;
+    ws.timed_launch("supersample_combine_clip", s, [&] {
+        if (bpp == 4 && align % 16 == 0) k_supersample_combine_clip<true><<<grid, 256, 0, s>>>(a);
+        else if (bpp == 4 && align % 4 == 0) k_supersample_combine_clip<false><<<grid, 256, 0, s>>>(a);
+        else if (bpp == 4) k_supersample_combine_clip_bytes<4><<<grid, 256, 0, s>>>(a);
+        else if (bpp == 3) k_supersample_combine_clip_bytes<3><<<grid, 256, 0, s>>>(a);
+        else if (bpp == 2) k_supersample_combine_clip_bytes<2><<<grid, 256, 0, s>>>(a);
+        else k_supersample_combine_clip_bytes<1><<<grid, 256, 0, s>>>(a);
+    });
+    if (hipGetLastError() != hipSuccess) { *err = "supersample combine: kernel launch failed"; return -1; }
+    return 0;
 }
 
 int run_native_filter(const std::string &func, const HNativeRec &rec, const std::vector<HImageDesc> &images,

@@ -1834,6 +1834,107 @@ int mmhip_render_supersampled(mmhip_invocation *inv, int frame, float t, int reg
     return 0;
 }
 
+// ---- supersampled clips ----
+// How mmhip_render_clip_supersampled cuts a clip into batches.  Frames per batch: what both slices' clip launches take
+// in one launch each (clip_plan of the region_w + 1 and the region_w geometry at that many frames), at most 65 535 (the
+// combine's gridDim.y), and what MMHIP_CLIP_SS_BYTES (read once, default 2 GiB) holds of one frame's two slices.
+// per_batch 0: the loop of mmhip_render_supersampled -- filters with native calls or closure images (their nested
+// renders rely on the native memo across the two slices), and frames too large for any of the above.
+struct ClipSsPlan { int per_batch = 0; size_t bytes_per_frame = 0, long_pitch = 0; };
+static ClipSsPlan clip_ss_plan(const mmhip_filter *f, bool host_between, int region_w, int region_h, int bpp, int frames) {
+    static const size_t budget = [] {
+        const char *e = getenv("MMHIP_CLIP_SS_BYTES");
+        const long long v = e ? atoll(e) : 0;
+        return v > 0 ? (size_t)v : (size_t)2 << 30;
+    }();
+    ClipSsPlan p;
+    p.long_pitch = supersample_clip_long_pitch(region_w, bpp);
+    p.bytes_per_frame = (size_t)region_h * (p.long_pitch + (size_t)region_w * bpp);
+    if (host_between || region_w == INT32_MAX || p.long_pitch > (size_t)INT32_MAX || supersample_clip_items(region_w, region_h) > INT32_MAX)
+        return p;
+    long per = (long)std::min<size_t>({(size_t)frames, (size_t)65535, budget / p.bytes_per_frame});
+    // fewer frames in a launch may mean fewer rows per work-item, more workgroups per frame and a lower cap
+    while (per > 0) {
+        const int cap = std::min(clip_plan(clip_launch_geometry(f->ks, region_w + 1, region_h, (int)per)).max_frames,
+                                 clip_plan(clip_launch_geometry(f->ks, region_w, region_h, (int)per)).max_frames);
+        if (cap >= per) break;
+        per = cap;
+    }
+    p.per_batch = (int)per;
+    return p;
+}
+
+int mmhip_filter_clip_supersample_plan(const mmhip_filter *f, int region_w, int region_h, int bpp, int frames, int64_t *out) {
+    if (frames < 1) return fail("clip supersample plan: num_frames must be at least 1");
+    if (bpp < 1 || bpp > 4) return fail("output_bpp must be 1..4");
+    if (region_w < 1 || region_h < 1) return fail("clip supersample plan: empty region");
+    const ClipSsPlan p = clip_ss_plan(f, !f->ks.natives.empty() || !f->closures.empty(), region_w, region_h, bpp, frames);
+    const int64_t v[MMHIP_CLIP_SS_PLAN_FIELDS] = {p.per_batch > 0, p.per_batch, p.per_batch ? (frames + p.per_batch - 1) / p.per_batch : 0,
+                                                  (int64_t)p.bytes_per_frame, (int64_t)p.long_pitch, SS_CLIP_ROWS, SS_CLIP_PIXELS};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+long mmhip_clip_supersampled_batches(mmhip_invocation *inv) { return inv->clip_supersampled_batches; }
+
+// The invocation's sampling offsets for the length of a scope: put back on every way out.
+struct SamplingOffsetGuard {
+    mmhip_invocation *inv;
+    float ox, oy;
+    explicit SamplingOffsetGuard(mmhip_invocation *i) : inv(i), ox(i->sampling_offset_x), oy(i->sampling_offset_y) {}
+    ~SamplingOffsetGuard() { inv->sampling_offset_x = ox; inv->sampling_offset_y = oy; }
+    void set(float v) { inv->sampling_offset_x = inv->sampling_offset_y = v; }
+};
+
+int mmhip_render_clip_supersampled(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int region_x,
+                                   int region_y, int region_w, int region_h, void *out_device, int row_stride,
+                                   int64_t frame_stride, int bpp, void *stream) {
+    if (num_frames < 1) return fail("render_clip_supersampled: num_frames must be at least 1");
+    if (!frames || !ts) return fail("render_clip_supersampled: frames and ts must be arrays of num_frames entries");
+    if (bpp < 1 || bpp > 4) return fail("output_bpp must be 1..4");
+    if (region_w <= 0 || region_h <= 0) return fail("empty region");
+    const int64_t band = (int64_t)(region_h - 1) * row_stride + (int64_t)region_w * bpp;
+    if (frame_stride < band)
+        return fail("render_clip_supersampled: frame_stride " + std::to_string(frame_stride) + " is smaller than one frame's band (" +
+                    std::to_string(band) + " bytes)");
+    const bool host_between = !inv->f->ks.natives.empty() || !inv->f->closures.empty();
+    const ClipSsPlan plan = clip_ss_plan(host_between ? inv->f : active_filter(inv, frames[0], ts[0]), host_between, region_w,
+                                         region_h, bpp, num_frames);
+    if (plan.per_batch < 1) {
+        for (int i = 0; i < num_frames; ++i)
+            if (mmhip_render_supersampled(inv, frames[i], ts[i], region_x, region_y, region_w, region_h,
+                                          (char *)out_device + (int64_t)i * frame_stride, row_stride, bpp, stream) != 0)
+                return -1;
+        return 0;
+    }
+    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
+    const int per_batch = plan.per_batch;
+    const size_t long_frame = (size_t)region_h * plan.long_pitch, short_frame = (size_t)region_h * region_w * bpp;
+    // own allocation, like ss_lines; whatever still reads a smaller one has finished before it is freed
+    if (inv->clip_ss.grow((size_t)per_batch * plan.bytes_per_frame, hipDeviceSynchronize) != hipSuccess)
+        return fail("out of device memory for the supersampling slices of a clip; lower MMHIP_CLIP_SS_BYTES");
+    unsigned char *longs = inv->clip_ss.get<unsigned char>(), *shorts = longs + (size_t)per_batch * long_frame;
+    SamplingOffsetGuard offsets(inv);
+    for (int b0 = 0; b0 < num_frames; b0 += per_batch) {
+        const int n = std::min(per_batch, num_frames - b0);
+        // long slices: region_width + 1 columns at offsets -0.5, then the short ones at 0 (mmhip_render_supersampled)
+        offsets.set(-0.5f);
+        if (mmhip_render_clip(inv, n, frames + b0, ts + b0, region_x, region_y, region_w + 1, region_h, region_y, region_y + region_h,
+                              longs, (int)plan.long_pitch, (int64_t)long_frame, bpp, 0, s) != 0)
+            return -1;
+        offsets.set(0.f);
+        if (mmhip_render_clip(inv, n, frames + b0, ts + b0, region_x, region_y, region_w, region_h, region_y, region_y + region_h,
+                              shorts, region_w * bpp, (int64_t)short_frame, bpp, 0, s) != 0)
+            return -1;
+        std::string err;
+        if (launch_supersample_combine_clip(longs, shorts, (unsigned char *)out_device + (int64_t)b0 * frame_stride, region_w, region_h,
+                                            bpp, row_stride, frame_stride, n, inv->ws, s, &err) != 0)
+            return fail(err);
+        ++inv->clip_supersampled_batches;
+    }
+    return 0;
+}
+
 int mmhip_sync(mmhip_invocation *inv) {
     HIP_TRY(hipStreamSynchronize(inv->stream));
     return 0;

@@ -215,6 +215,9 @@ struct mmhip_invocation {
     long clip_native_batches = 0;          // mmhip_clip_native_batches
     long clip_native_blurs = 0;            // mmhip_clip_native_blurs
     long clip_native_direct_frames = 0;    // mmhip_clip_native_direct_frames
+    DeviceBuffer clip_ss;                  // the slices of a batch of supersampled frames (mmhip_render_clip_supersampled):
+                                           // every frame's long slice, then every frame's short slice
+    long clip_supersampled_batches = 0;    // mmhip_clip_supersampled_batches
     uint32_t edge_color_x = 0, edge_color_y = 0;
     float sampling_offset_x = 0.f, sampling_offset_y = 0.f;
     bool timing = false;
