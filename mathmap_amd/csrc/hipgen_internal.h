@@ -32,6 +32,9 @@ struct Knobs {
     std::optional<int> pair_exit_tail = env_int("MMHIP_PAIR_EXIT_TAIL");
     std::optional<int> pair_pack = env_int("MMHIP_PAIR_PACK");        // 0: pair kernels store through mm_store_pixel, a pixel at a time
     std::optional<int> pair_peel = env_int("MMHIP_PAIR_PEEL");        // 1: peel a first trip that folds off the loops of specialised pair kernels (pair_peel_enabled; default off: not measured yet)
+    // 0: no fused doubling (hipgen_pair.cpp plan_fusion): `d = t + t; r = d + b` of an exit-driven loop stays two additions.
+    // Only with the counted back edge: MMHIP_PAIR_EXIT=0 and MMHIP_PAIR_EXIT_TAIL=0 / 1 keep the earlier arithmetic whatever this says
+    std::optional<int> pair_fma2 = env_int("MMHIP_PAIR_FMA2");
     bool pair_no_uniform = env_int("MMHIP_PAIR_NO_UNIFORM").has_value();   // no wave-uniform scalars in pair-mode loops
     std::optional<int> nt_store = env_int("MMHIP_NT_STORE");          // #define MM_NT_STORE, instead of "the kernel fetches"
     std::optional<int> xcd_order = env_int("MMHIP_XCD_ORDER");        // workgroup -> tile order 0 / 1 / 2 (default 2)

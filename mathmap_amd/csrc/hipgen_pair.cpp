@@ -43,6 +43,13 @@ struct PairGen final : PairMode {
     const bool pack = exit && env.knobs.pair_pack.value_or(1);
     const Stmt *split_def = nullptr;   // the uniform conjunct's defining statement, while its loop body is printed
     bool split_leave = false;          // the value with which it ends the loop
+    // fused doubling (plan_fusion): with the counted back edge, so that every earlier switch gives its earlier text
+    const bool fma2 = exit && env.knobs.pair_fma2.value_or(1) && env.knobs.pair_exit_tail.value_or(2) >= 2;
+    // r = d + b, d = t * k: r = fma(t, k, b) and no statement for d -- unless phis that nothing reads name it (keep_d, count_uses)
+    struct Fuse { const Stmt *r, *d; Primary t, b; float k; bool keep_d; };
+    std::map<const Stmt *, std::vector<Fuse>> fuse_plan;            // loop -> its fused statements
+    std::map<const Stmt *, const Fuse *> fusing;                    // those of the loop copies being printed fused, by r ...
+    std::set<const Stmt *> fused_away;                              // ... and their d
 
     explicit PairGen(const PairEnv &e) : env(e), out(e.out), code(e.code) {}
 
@@ -658,6 +665,180 @@ struct PairGen final : PairMode {
         }
         out << ind << "  " << a << ".x &= ~" << l << ".x; " << a << ".y &= ~" << l << ".y;\n";
     }
+    // ---- fused doubling (MMHIP_PAIR_FMA2) ----
+    // The imaginary part of an escape-time loop is `t = x * y; d = t + t; y' = d + b`.  Doubling is exact, so the sum rounds
+    // once: it is fma(t, 2, b), one instruction for two, except where t + t overflows -- the two-step form then gives an
+    // infinity whatever b is, the fused form the rounded 2t + b, which is finite again only for |b| > 2^103 (the smallest
+    // product that overflows is 2^128, the largest sum that rounds to a finite float lies below 2^128 - 2^103).  The same
+    // holds for every multiplier 2^k, k >= 1: scaling up is exact for denormal t as well (scaling down would not be), a zero
+    // product keeps t's sign and meets b under the same addition rule, and a NaN operand gives NaN either way.
+    // Fused: a float statement `r = d + b` / `r = b + d` of a loop in exit-driven form, where d is defined in the same block of
+    // that loop's body as t + t or t times a literal 2^k, is read by nothing else (not by a live phi either: the exit copies
+    // read those), and b comes from outside the loop: a literal (of at most 2^102: no guard), a frame constant or a pixel value of
+    // an enclosing block.  Where an addend is not a literal the loop is printed twice (fused_loop) under a guard that is
+    // evaluated where the loop is entered.  Nothing else is fused: not x * x + y * y (a product that is not exact), not an
+    // addend that changes from trip to trip, not an int.
+    //
+    // Uses of every value: by assignments, conditions and the results, and by the phis whose own value is live.  A loop nested
+    // in a loop has a phi for every temporary of its body (the value left by the outer loop's last trip meets the new one);
+    // nothing reads those, they form cycles among themselves, and the compiler drops them: `dead` counts what only they read.
+    struct Uses { std::map<const Value *, int> live, dead; };
+    template <class F> static void each_phi(const Block &b, F f) {
+        for (const Stmt *s : b) {
+            for (const Stmt *ph : s->phis) f(ph);
+            each_phi(s->then_, f);
+            each_phi(s->else_, f);
+            each_phi(s->body, f);
+        }
+    }
+    static void count_roots(const Block &b, std::map<const Value *, int> &n) {
+        auto use = [&](const Primary &p) { if (p.kind == Primary::Val) ++n[p.value]; };
+        auto use_rhs = [&](const Rhs &r) { if (r.kind == Rhs::Prim) use(r.prim); for (const Primary &a : r.args) use(a); };
+        for (const Stmt *s : b) {
+            if (s->kind == Stmt::Assign) use_rhs(s->rhs);
+            if (s->kind == Stmt::If || s->kind == Stmt::While) use_rhs(s->cond);
+            count_roots(s->then_, n);
+            count_roots(s->else_, n);
+            count_roots(s->body, n);
+        }
+    }
+    Uses count_uses() const {
+        Uses u;
+        count_roots(code.body, u.live);
+        for (int i = 0; i < 4; ++i) if (code.result[i]) ++u.live[code.result[i]];
+        std::vector<const Stmt *> phis;
+        each_phi(code.body, [&](const Stmt *ph) { phis.push_back(ph); });
+        std::set<const Stmt *> live_phis;
+        auto operands = [](const Stmt *ph, auto f) {
+            for (const Rhs *r : {&ph->rhs, &ph->rhs2}) if (r->kind == Rhs::Prim && r->prim.kind == Primary::Val) f(r->prim.value);
+        };
+        for (bool changed = true; changed;) {
+            changed = false;
+            for (const Stmt *ph : phis)
+                if (!live_phis.count(ph) && u.live.count(ph->lhs)) {
+                    live_phis.insert(ph);
+                    operands(ph, [&](const Value *v) { ++u.live[v]; });
+                    changed = true;
+                }
+        }
+        for (const Stmt *ph : phis)
+            if (!live_phis.count(ph)) operands(ph, [&](const Value *v) { ++u.dead[v]; });
+        return u;
+    }
+    static void defined_in(const Block &b, std::set<const Value *> &d) {
+        for (const Stmt *s : b) {
+            if (s->kind == Stmt::Assign) d.insert(s->lhs);
+            for (const Stmt *ph : s->phis) d.insert(ph->lhs);
+            defined_in(s->then_, d);
+            defined_in(s->else_, d);
+            defined_in(s->body, d);
+        }
+    }
+    static int count_stmts(const Block &b) {      // like the generator's pixel_stats
+        int n = 0;
+        for (const Stmt *s : b)
+            if (s->in_pixel) n += 1 + count_stmts(s->then_) + count_stmts(s->else_) + count_stmts(s->body);
+        return n;
+    }
+    static bool pow2_multiplier(const Primary &p, float &k) {      // a literal 2^k, k >= 1
+        if (p.kind != Primary::IntConst && p.kind != Primary::FloatConst) return false;
+        k = p.kind == Primary::IntConst ? (float)p.i : p.f;
+        if (!(k >= 2.0f) || k > 0x1p127f) return false;
+        unsigned bits;
+        memcpy(&bits, &k, 4);
+        return (bits & 0x7fffffu) == 0;
+    }
+    // d = t + t, 2^k * t or t * 2^k in floats
+    static bool doubling(const Stmt *d, Primary &t, float &k) {
+        if (d->kind != Stmt::Assign || !d->in_pixel || d->lhs->var->type != Ty::Float || d->rhs.kind != Rhs::Op || d->rhs.args.size() != 2) return false;
+        const Primary &a0 = d->rhs.args[0], &a1 = d->rhs.args[1];
+        auto fval = [](const Primary &p) { return p.kind == Primary::Val && p.value->var->type == Ty::Float; };
+        if (!strcmp(d->rhs.op->cname, "ADD") && fval(a0) && fval(a1) && a0.value == a1.value) { t = a0; k = 2.0f; return true; }
+        if (strcmp(d->rhs.op->cname, "MUL")) return false;
+        if (fval(a0) && pow2_multiplier(a1, k)) { t = a0; return true; }
+        if (fval(a1) && pow2_multiplier(a0, k)) { t = a1; return true; }
+        return false;
+    }
+    void plan_block(const Block &b, const std::set<const Value *> &in_loop, const Uses &uses, std::vector<Fuse> &fs) const {
+        for (const Stmt *r : b) {
+            if (!r->in_pixel) continue;
+            if (r->kind == Stmt::If) { plan_block(r->then_, in_loop, uses, fs); plan_block(r->else_, in_loop, uses, fs); }
+            if (r->kind != Stmt::Assign || r->lhs->var->type != Ty::Float || uniform.count(r->lhs)) continue;
+            if (r->rhs.kind != Rhs::Op || strcmp(r->rhs.op->cname, "ADD") || r->rhs.args.size() != 2) continue;
+            for (int i = 0; i < 2; ++i) {
+                const Primary &dp = r->rhs.args[i], &bp = r->rhs.args[1 - i];
+                if (dp.kind != Primary::Val || dp.value->index < 0 || !dp.value->def || dp.value->def->lhs != dp.value) continue;
+                const Stmt *d = dp.value->def;
+                Fuse f{r, d, Primary(), bp, 0.0f, uses.dead.count(d->lhs) > 0};
+                if (std::find(b.begin(), b.end(), d) == b.end() || uniform.count(d->lhs) || !doubling(d, f.t, f.k)) continue;
+                const auto n = uses.live.find(d->lhs);
+                if (n == uses.live.end() || n->second != 1) continue;
+                if (bp.kind == Primary::FloatConst) { if (!(__builtin_fabsf(bp.f) <= 0x1p102f)) continue; }
+                else if (bp.kind == Primary::Val) { if (bp.value->var->type != Ty::Float || in_loop.count(bp.value)) continue; }
+                else if (bp.kind != Primary::IntConst) continue;
+                fs.push_back(f);
+                break;
+            }
+        }
+    }
+    void plan_loops(const Block &b, const Uses &uses) {
+        for (const Stmt *s : b) {
+            if (!s->in_pixel) continue;
+            if (s->kind == Stmt::If) { plan_loops(s->then_, uses); plan_loops(s->else_, uses); }
+            if (s->kind != Stmt::While) continue;
+            const std::vector<const Stmt *> ivs = find_uniform_ivs(s);      // as while_loop will: uniform statements are scalar text
+            std::set<const Value *> in_loop;
+            for (const Stmt *ph : s->phis) in_loop.insert(ph->lhs);
+            defined_in(s->body, in_loop);
+            std::vector<Fuse> fs;
+            plan_block(s->body, in_loop, uses, fs);
+            // two copies of the body must fit the size up to which pair mode is taken at all (eligible)
+            const bool guarded = std::any_of(fs.begin(), fs.end(), [&](const Fuse &f) { return needs_guard(f.b); });
+            if (!fs.empty() && (!guarded || 2 * count_stmts(s->body) <= (env.knobs.pair.has_value() ? 400 : 40))) fuse_plan[s] = fs;
+            plan_loops(s->body, uses);
+            for (const Stmt *ph : ivs) uniform.erase(ph->lhs);
+        }
+    }
+    void plan_fusion() {
+        if (!fma2) return;
+        const Uses uses = count_uses();
+        const std::set<const Value *> keep = uniform;
+        plan_loops(code.body, uses);
+        uniform = keep;
+    }
+    static bool needs_guard(const Primary &b) { return b.kind == Primary::Val && b.value->index >= 0; }
+    // The loop `w` with fused statements.  The guard -- no lane's addend above 2^102, in either pixel; the lanes of columns past the
+    // frame's edge have returned, rows past its end hold the last row's values -- is wave-uniform, and the loop is printed
+    // twice under it: today's text under its own names (mm_l<id>) for a wave in which it fails, the fused text under a
+    // label number of its own.  Both copies read and leave the same phis, mask and exit copies.
+    void fused_loop(const Loop &w, const std::vector<Fuse> &fs, const std::string &id, const std::string &mask) {
+        const std::string &ind = w.ind, I1 = ind + "  ";
+        std::vector<std::string> addends;
+        for (const Fuse &f : fs) {
+            if (!needs_guard(f.b)) continue;
+            const std::string b = pprim(f.b, Ty::Float);
+            if (std::find(addends.begin(), addends.end(), b) == addends.end()) addends.push_back(b);
+        }
+        auto copy = [&](bool fused, const std::string &l, const std::string &I) {
+            Loop c = w;
+            c.ind = I;
+            if (fused) for (const Fuse &f : fs) { fusing[f.r] = &f; if (!f.keep_d) fused_away.insert(f.d); }
+            plan_counted(c, l);
+            out << I << "while (" << c.a << ".x | " << c.a << ".y) {\n";
+            exit_driven_iteration(c, l);
+            out << I << "}\n";
+            if (fused) for (const Fuse &f : fs) { fusing.erase(f.r); fused_away.erase(f.d); }
+        };
+        out << ind << "mm_bb " << w.a << " = mm_andb(" << mask << ", " << pbool(w.s->cond.prim) << ");\n";
+        if (addends.empty()) { copy(true, "mm_l" + id, ind); return; }
+        out << ind << "const bool mm_g" << id << " = ";
+        for (size_t i = 0; i < addends.size(); ++i) out << (i ? " && " : "") << "mm_fma2_ok(" << addends[i] << ")";
+        out << ";\n" << ind << "if (!mm_g" << id << ") {\n";
+        copy(false, "mm_l" + id, I1);
+        out << ind << "} else {\n";
+        copy(true, "mm_l" + std::to_string(ids++), I1);
+        out << ind << "}\n";
+    }
     // A `while` under `mask`: runs while either pixel is in it.  The two shapes share everything but the iteration.
     void while_loop(Stmt *s, const std::string &ind, const std::string &mask) {
         const std::string id = std::to_string(ids++);
@@ -684,12 +865,16 @@ struct PairGen final : PairMode {
             uniform.insert(ph->lhs);
             out << ind << (ph->lhs->var->type == Ty::Float ? "float u" : "int u") << vname(ph->lhs) << " = " << init << ";\n";
         }
-        if (exit) plan_counted(w, "mm_l" + id);
-        out << ind << "mm_bb " << w.a << " = mm_andb(" << mask << ", " << pbool(s->cond.prim) << ");\n";
-        out << ind << "while (" << w.a << ".x | " << w.a << ".y) {\n";
-        if (exit) exit_driven_iteration(w, "mm_l" + id);
-        else selecting_iteration(w);
-        out << ind << "}\n";
+        const auto fp = fuse_plan.find(s);
+        if (fp != fuse_plan.end()) fused_loop(w, fp->second, id, mask);
+        else {
+            if (exit) plan_counted(w, "mm_l" + id);
+            out << ind << "mm_bb " << w.a << " = mm_andb(" << mask << ", " << pbool(s->cond.prim) << ");\n";
+            out << ind << "while (" << w.a << ".x | " << w.a << ".y) {\n";
+            if (exit) exit_driven_iteration(w, "mm_l" + id);
+            else selecting_iteration(w);
+            out << ind << "}\n";
+        }
         for (const auto &e : w.exit_copy) out << ind << vname(e.first->lhs) << " = " << e.second << ";\n";      // read through it from here on
         for (const Stmt *ph : w.ivs) uniform.erase(ph->lhs);
     }
@@ -707,6 +892,14 @@ struct PairGen final : PairMode {
                     if (uniform.count(s->lhs)) {       // scalar statement, the scalar kernel's own expression
                         const char *ty = bools.count(s->lhs) ? "bool" : s->lhs->var->type == Ty::Float ? "float" : "int";
                         out << ind << "const " << ty << " u" << vname(s->lhs) << " = " << env.rhs(s) << ";\n";
+                        break;
+                    }
+                    if (fused_away.count(s)) break;      // its one reader multiplies by itself
+                    if (fusing.count(s)) {
+                        const Fuse &f = *fusing.at(s);
+                        const std::string t = pprim(f.t, Ty::Float), k = float_literal(f.k) + "f", b = pprim(f.b, Ty::Float);
+                        out << ind << vname(s->lhs) << " = mm_pf{__builtin_fmaf(" << t << ".x, " << k << ", " << b << ".x), __builtin_fmaf("
+                            << t << ".y, " << k << ", " << b << ".y)};\n";
                         break;
                     }
                     out << ind << vname(s->lhs) << " = " << prhs(s->rhs, s->lhs) << ";\n";
@@ -740,6 +933,17 @@ MM_DEV mm_bb mm_xbu(bool u) { const unsigned long m = u ? ~0ul : 0ul; return mm_
 // a wave-uniform int for the exit copies, moved from its scalar register where it is wanted (as an ordinary operand it
 // would pull the loop counter, and the loop's bound test, onto the vector unit)
 MM_DEV int mm_s2v(int u) { int r; asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(__builtin_amdgcn_readfirstlane(u))); return r; }
+)";
+        bool guarded = false;      // (a loop whose addends are all literals is fused as it stands)
+        for (const auto &lp : fuse_plan) for (const Fuse &f : lp.second) guarded = guarded || needs_guard(f.b);
+        if (guarded)
+            out << R"(#define MM_PAIR_FMA2 1
+// fused doubling (hipgen_pair.cpp plan_fusion): fl(fl(t * 2^k) + b) is fma(t, 2^k, b) -- the product is exact -- unless the
+// product overflows and the exact sum does not, which takes |b| > 2^103.  True when no lane of the wave holds such an
+// addend in either pixel (NaN fails the comparison): the loop then runs in its fused copy.
+MM_DEV bool mm_fma2_ok(mm_pf b) {
+  return __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(b.x) <= 0x1p102f && __builtin_fabsf(b.y) <= 0x1p102f)) == 0ul;
+}
 )";
         emit_store_pair();
     }
@@ -869,6 +1073,7 @@ std::unique_ptr<PairMode> make_pair_mode(const PairEnv &env) {
     std::unique_ptr<PairGen> g(new PairGen(env));
     if (!g->eligible()) return nullptr;
     g->infer_bools();
+    g->plan_fusion();
     return g;
 }
 

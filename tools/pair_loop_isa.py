@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Instruction counts of a pair-mode kernel's innermost loop, offline (needs hipcc, no GPU).
 
-    python tools/pair_loop_isa.py mandelbrot [-D name=value ...] [--asm]
+    python tools/pair_loop_isa.py mandelbrot [-D name=value ...] [--asm] [--all]
 
 Emits the specialised kernel text of the filter under the current environment (so MMHIP_PAIR_EXIT=0 and the
 other generator switches apply), compiles it to gfx950 assembly with the option list of the JIT (runtime.cpp
 jit_source; hiprtc includes the HIP runtime header by itself, here it is named), finds the innermost loop of
-mm_pixels and prints VALU / SALU / branch counts of
+mm_pixels (with --all: every innermost loop, in program order) and prints VALU / SALU / branch counts of
 
   * its likely path: from the loop header to the first branch back to it, and
   * its exit block: what follows, up to the next branch back to the header or out (for the exit-driven loops:
@@ -103,6 +103,19 @@ def innermost_header(lines):
     return best, depth
 
 
+def innermost_headers(lines):
+    """[(label, depth)] of every innermost loop, in program order"""
+    out, label = [], None
+    for l in lines:
+        m = re.match(r"^(\.LBB\d+_\d+):", l)
+        if m:
+            label = m.group(1)
+        m = re.search(r"This Inner Loop Header: Depth=(\d+)", l)
+        if m and label:
+            out.append((label, int(m.group(1))))
+    return out
+
+
 def count(block):
     c = {"valu": 0, "salu": 0, "branch": 0, "mem": 0, "wait": 0}
     for _, op, _ in block:
@@ -110,12 +123,7 @@ def count(block):
     return c
 
 
-def analyse(asm, show):
-    lines = kernel_lines(asm, "mm_pixels")
-    header, depth = innermost_header(lines)
-    if header is None:
-        sys.exit("mm_pixels has no loop")
-    ins = instructions(lines)
+def analyse_loop(ins, header, depth, show):
     start = next(i for i, (lab, _, _) in enumerate(ins) if lab == header)
     back = next((i for i in range(start, len(ins)) if classify(ins[i][1]) == "branch" and ins[i][2].split()[-1] == header), None)
     if back is None:
@@ -142,7 +150,23 @@ def analyse(asm, show):
     if inner_branches:
         print("note: %d more branch(es) inside the likely path: it is not one basic block" % inner_branches)
     print("innermost loop: %s, depth %d" % (header, depth))
+    res["fma"] = sum(1 for _, op, _ in likely if op.startswith("v_fma"))
     return res
+
+
+def analyse(asm, show):
+    lines = kernel_lines(asm, "mm_pixels")
+    header, depth = innermost_header(lines)
+    if header is None:
+        sys.exit("mm_pixels has no loop")
+    return analyse_loop(instructions(lines), header, depth, show)
+
+
+def analyse_all(asm, show):
+    """every innermost loop of mm_pixels, in program order: [counts as analyse gives them, with "fma": the v_fma_* of the likely path]"""
+    lines = kernel_lines(asm, "mm_pixels")
+    ins = instructions(lines)
+    return [analyse_loop(ins, header, depth, show) for header, depth in innermost_headers(lines)]
 
 
 def main():
@@ -150,6 +174,7 @@ def main():
     ap.add_argument("filter", help="name of a filter of tests/filters.py (mandelbrot, ...)")
     ap.add_argument("-D", dest="defs", action="append", default=[], metavar="name=value", help="user value to specialise on")
     ap.add_argument("--asm", action="store_true", help="print the instructions of both blocks")
+    ap.add_argument("--all", action="store_true", help="every innermost loop of mm_pixels (a fused loop has two copies), not only the last")
     ap.add_argument("--source", metavar="FILE", help="analyse this kernel text instead of the generated one")
     args = ap.parse_args()
     ver = subprocess.run([hipcc(), "--version"], capture_output=True, text=True).stdout.strip().split("\n")
@@ -166,7 +191,7 @@ def main():
             k, v = d.split("=", 1)
             uv[k] = float(v) if "." in v else int(v)
         source = F.load(args.filter).specialized(uv).kernel_source
-    analyse(assembly(source), args.asm)
+    (analyse_all if args.all else analyse)(assembly(source), args.asm)
 
 
 if __name__ == "__main__":
