@@ -101,6 +101,12 @@ const char *mmhip_filter_ir_json_raw(mmhip_filter *f);
 const char *mmhip_filter_kernel_source(mmhip_filter *f);  /* the HIP C++ handed to hiprtc */
 int mmhip_filter_gauss_mode(const mmhip_filter *f);       /* the options' gauss_mode the filter was compiled with */
 int mmhip_filter_num_native_calls(const mmhip_filter *f);
+/* The builtin overloads and macros the parser resolved while it compiled the filter's text, callees included: their
+   unique ids ("mul_quat", "div_s", "macro___origVal", ...), sorted, one per line, as a NUL-terminated string of at
+   most cap bytes in buf (truncated where cap is smaller).  Returns the size that holds all of them, the NUL included;
+   buf may be NULL to ask for it.  Overload resolution takes the first match, so this is how a caller learns which
+   overload an expression reached.  Empty for a filter built from an IR dump.  Not part of the generated code. */
+int mmhip_filter_builtin_ids(const mmhip_filter *f, char *buf, int cap);
 /* The launch geometry of the filter's pixel kernel over rows [0, num_rows) of a region_w-wide region, as
    mmhip_render takes it (MMHIP_PPT included): out[MMHIP_GEOMETRY_FIELDS] receives, in this order,
    tiles_x, tiles_y, wg1 (workgroups at one row per work-item, the rows-per-item choice's input), nwg (workgroups

@@ -44,6 +44,7 @@ SYMBOLS = {
     "mmhip_filter_kernel_source": (C.c_char_p, [C.c_void_p]),
     "mmhip_filter_gauss_mode": (C.c_int, [C.c_void_p]),
     "mmhip_filter_num_native_calls": (C.c_int, [C.c_void_p]),
+    "mmhip_filter_builtin_ids": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "mmhip_filter_launch_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "mmhip_filter_clip_launch_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "mmhip_filter_clip_batch_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),

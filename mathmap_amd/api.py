@@ -162,6 +162,15 @@ class Filter:
     def num_native_calls(self):
         return lib().mmhip_filter_num_native_calls(self._h)
 
+    @property
+    def builtin_ids(self):
+        """The ids of the builtin overloads and macros the parser resolved for this filter's text (a frozenset;
+        empty for a filter built from an IR dump)."""
+        n = lib().mmhip_filter_builtin_ids(self._h, None, 0)
+        buf = C.create_string_buffer(n)
+        lib().mmhip_filter_builtin_ids(self._h, buf, n)
+        return frozenset(buf.value.decode().split())
+
     def launch_geometry(self, region_w, num_rows, closure=None):
         """How the pixel kernel is launched over `num_rows` rows of a `region_w`-wide region (the geometry mmhip_render
         takes, MMHIP_PPT included) -- or, with `closure` = k, how closure image #k is launched over a region_w x

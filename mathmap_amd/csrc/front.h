@@ -10,6 +10,7 @@
 #include <functional>
 #include <map>
 #include <memory>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -108,6 +109,7 @@ struct Module {
     std::map<Filter *, std::unique_ptr<FilterVars>> vars;
     std::vector<std::unique_ptr<AstNode>> nodes;
     std::vector<BuiltinEntry> builtins;
+    std::set<std::string> resolved_ids;   // BuiltinEntry::id of every overload and macro the parser resolved
     Filter *main = nullptr;
 
     Module();

@@ -16,6 +16,11 @@ MM_DEV double mm_noise_int32range(double n) {
     if (n <= -1073741824.0) return (2.0 * fmod(n, 1073741824.0)) + 1073741824.0;
     return n;
 }
+// The library's `x > 0.0 ? (int)x : (int)x - 1` and its `+ 1`, `- 2`, `++` on cell numbers, as the x86-64 build of the
+// library computes them: a double beyond int (or NaN) converts to INT_MIN (mm_d2i), and int arithmetic wraps.  The device's
+// own conversion saturates and its signed overflow is undefined, which matters for voronoiCells: it reduces no range.
+MM_DEV int mm_noise_wrap_add(int a, int b) { return (int)((unsigned)a + (unsigned)b); }
+MM_DEV int mm_noise_cell(double x) { return x > 0.0 ? mm_d2i(x) : mm_noise_wrap_add(mm_d2i(x), -1); }
 MM_DEV double mm_noise_gradient(double fx, double fy, double fz, int ix, int iy, int iz, int seed) {
     int vi = (int)(1619u * (unsigned)ix + 31337u * (unsigned)iy + 6971u * (unsigned)iz + 1013u * (unsigned)seed);
     vi ^= (vi >> 8);
@@ -25,9 +30,9 @@ MM_DEV double mm_noise_gradient(double fx, double fy, double fz, int ix, int iy,
     return ((xg * xp) + (yg * yp) + (zg * zp)) * 2.12;
 }
 MM_DEV double mm_noise_coherent(double x, double y, double z, int seed) {
-    const int x0 = (x > 0.0 ? (int)x : (int)x - 1), x1 = x0 + 1;
-    const int y0 = (y > 0.0 ? (int)y : (int)y - 1), y1 = y0 + 1;
-    const int z0 = (z > 0.0 ? (int)z : (int)z - 1), z1 = z0 + 1;
+    const int x0 = mm_noise_cell(x), x1 = mm_noise_wrap_add(x0, 1);
+    const int y0 = mm_noise_cell(y), y1 = mm_noise_wrap_add(y0, 1);
+    const int z0 = mm_noise_cell(z), z1 = mm_noise_wrap_add(z0, 1);
     const double xs = mm_noise_scurve7(x - (double)x0), ys = mm_noise_scurve7(y - (double)y0), zs = mm_noise_scurve7(z - (double)z0);
     double n0, n1, ix0, ix1, iy0, iy1;
     n0 = mm_noise_gradient(x, y, z, x0, y0, z0, seed);
@@ -97,16 +102,20 @@ MM_DEV int mm_noise_intvalue(int x, int y, int z, int seed) {
 MM_DEV double mm_noise_value(int x, int y, int z, int seed) { return 1.0 - ((double)mm_noise_intvalue(x, y, z, seed) / 1073741824.0); }
 MM_DEV float libnoise_voronoi(float displacement, float fx, float fy, float fz) {
     const double x = fx, y = fy, z = fz;
-    const int xi = (x > 0.0 ? (int)x : (int)x - 1), yi = (y > 0.0 ? (int)y : (int)y - 1), zi = (z > 0.0 ? (int)z : (int)z - 1);
+    const int xi = mm_noise_cell(x), yi = mm_noise_cell(y), zi = mm_noise_cell(z);
+    const int xlo = mm_noise_wrap_add(xi, -2), xhi = mm_noise_wrap_add(xi, 2), ylo = mm_noise_wrap_add(yi, -2), yhi = mm_noise_wrap_add(yi, 2),
+              zlo = mm_noise_wrap_add(zi, -2), zhi = mm_noise_wrap_add(zi, 2);
     double mind = 2147483647.0, xc = 0, yc = 0, zc = 0;
-    for (int zq = zi - 2; zq <= zi + 2; zq++)
-        for (int yq = yi - 2; yq <= yi + 2; yq++)
-            for (int xq = xi - 2; xq <= xi + 2; xq++) {
+    // the library's `for (q = i - 2; q <= i + 2; q++)` with wrapping ints: five cells, or none where i - 2 wrapped past
+    // i + 2 (a coordinate beyond int: the result is then the value of cell 0 0 0); the trip count is what bounds the loop
+    for (int zk = 0, zq = zlo; zk < 5 && zq <= zhi; ++zk, zq = mm_noise_wrap_add(zq, 1))
+        for (int yk = 0, yq = ylo; yk < 5 && yq <= yhi; ++yk, yq = mm_noise_wrap_add(yq, 1))
+            for (int xk = 0, xq = xlo; xk < 5 && xq <= xhi; ++xk, xq = mm_noise_wrap_add(xq, 1)) {
                 const double xp = xq + mm_noise_value(xq, yq, zq, 0), yp = yq + mm_noise_value(xq, yq, zq, 1),
                              zp = zq + mm_noise_value(xq, yq, zq, 2);
                 const double xd = xp - x, yd = yp - y, zd = zp - z;
                 const double dist = xd * xd + yd * yd + zd * zd;
                 if (dist < mind) { mind = dist; xc = xp; yc = yp; zc = zp; }
             }
-    return (float)(0.0 + ((double)displacement * mm_noise_value((int)floor(xc), (int)floor(yc), (int)floor(zc), 0)));
+    return (float)(0.0 + ((double)displacement * mm_noise_value(mm_floor_i(xc), mm_floor_i(yc), mm_floor_i(zc), 0)));
 }

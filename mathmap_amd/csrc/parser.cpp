@@ -465,6 +465,7 @@ AstNode *Parser::make_function(const std::string &name, std::vector<AstNode *> a
     TInfo res;
     if (!args.empty()) {
         if (const BuiltinEntry *e = m_.resolve(name, types, &res)) {
+            m_.resolved_ids.insert(e->id);
             if (e->macro) return e->macro(*this, args, pos);
             AstNode *n = m_.node(AstNode::Func, res, pos);
             n->entry = e;

@@ -224,6 +224,13 @@ const char *mmhip_filter_ir_json_raw(mmhip_filter *f) { return f->ir_json_raw.c_
 const char *mmhip_filter_kernel_source(mmhip_filter *f) { return f->ks.source.c_str(); }
 int mmhip_filter_gauss_mode(const mmhip_filter *f) { return f->opts.gauss_mode; }
 int mmhip_filter_num_native_calls(const mmhip_filter *f) { return f->ks.native_sites; }
+
+int mmhip_filter_builtin_ids(const mmhip_filter *f, char *buf, int cap) {
+    std::string s;
+    for (const std::string &id : f->module.resolved_ids) { s += id; s += '\n'; }
+    if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", s.c_str());
+    return (int)s.size() + 1;
+}
 double mmhip_filter_jit_seconds(const mmhip_filter *f) { return f->jit_seconds; }
 
 // hiprtc-compiles one kernel source (or fetches it from the on-disk cache); 0 on success

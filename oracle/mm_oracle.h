@@ -237,6 +237,7 @@ static inline mmo_tup3 mmo_ell_jac(double u, double m) {
 #define ELL_INT_RJ(x, y, z, p) (mmg_ellint_RJ((x), (y), (z), (p)))
 #define RAND(a, b) \
     (mmg_rand_unit(col + A->region_x, row + A->region_y, A->frame, mm_rand_ctr++) * ((double)(b) - (double)(a)) + (double)(a))
-#define gsl_sf_beta(a, b) (exp(lgamma((a)) + lgamma((b)) - lgamma((a) + (b))))   /* GSL absent: parity unpinned */
+/* gsl_sf_beta takes doubles: the sum of the two float arguments is a double sum */
+#define gsl_sf_beta(a, b) (exp(lgamma((a)) + lgamma((b)) - lgamma((double)(a) + (double)(b))))   /* GSL absent: parity unpinned */
 
 #endif
