@@ -839,13 +839,35 @@ void launch_sweeps(NativeWorkspace &ws, hipStream_t s, bool tol, SweepNames exac
 // `same > 3n/4` switch.  Lines are edge-replicated (gauss.c:333-375).
 struct FirArgs { int w, h, vertical, length; float total; int ctotal; };
 
+// gauss.c:267-280: the half-width of the curve for a deviation of sigma pixels, about 3.33 sigma; -1 where it is not a count
+// (a deviation that is not finite, or taps by the hundred million)
+int rle_curve_length(double sigma) {
+    const double sigma2 = 2 * sigma * sigma;
+    const double l = sqrt(-sigma2 * log(1.0 / 255.0));
+    if (!(l < 1e8)) return -1;
+    int n = (int)(ceil(l) * 2);
+    if ((n % 2) == 0) n += 1;
+    return n / 2;
+}
+
+// what gauss_rle keeps at the start of the workspace: a flag per line and channel of the longer pass, then the taps and
+// the cumulative sums (2 * length + 1 floats each) of the pass with the longer curve; 0 where a curve has no length
+size_t fir_aux_bytes(int w, int h, float hs, float vs) {
+    size_t floats = 0;
+    for (const float sd : {vs, hs}) {
+        if (!(sd > 0.0f)) continue;           // gauss_rle skips the pass
+        const int length = rle_curve_length(sd);
+        if (length < 0) return 0;
+        floats = std::max(floats, 2 * (2 * (size_t)length + 1));
+    }
+    return (size_t)std::max(w, h) * 4 * sizeof(int) + floats * sizeof(float);
+}
+
 // gauss.c:264-306
 void make_rle_curve(double sigma, std::vector<float> &curve, std::vector<float> &sum, int &length, float &total) {
     const double sigma2 = 2 * sigma * sigma;
-    const double l = sqrt(-sigma2 * log(1.0 / 255.0));
-    int n = (int)(ceil(l) * 2);
-    if ((n % 2) == 0) n += 1;
-    length = n / 2;
+    length = rle_curve_length(sigma);
+    const int n = 2 * length + 1;
     curve.assign(n, 0.f);            // curve[length + i], i in [-length, length]
     curve[length] = 1.0f;
     for (int i = 1; i <= length; i++) {
@@ -928,7 +950,7 @@ __global__ void __launch_bounds__(256) k_fir_apply(const float *__restrict__ in,
 
 int gauss_rle(float *map, float *tmp, int w, int h, float hs, float vs, NativeWorkspace &ws, char *aux, hipStream_t s,
               std::string *err) {
-    // aux: device scratch for flags (max(w,h)*4 ints) + curve + csum
+    // aux: device scratch for flags (max(w,h)*4 ints) + curve + csum, fir_aux_bytes(w, h, hs, vs) in all
     float *src = map, *dst = tmp;
     for (int pass = 0; pass < 2; ++pass) {
         const int vertical = pass == 0;
@@ -1009,11 +1031,18 @@ int plan_gaussian_blur(const HNativeRec &rec, const HImageDesc *images, int num_
     p->hs = (float)fabs(hdev * ax);
     p->vs = (float)fabs(vdev * ay);
     // workspace: the scans' checkpoints (4 doubles per line*channel every IIR_U steps, the larger of
-    // the two passes; also covers the FIR path's flags and taps) followed by the intermediate map
+    // the two passes) or the FIR path's flags and taps (below), followed by the intermediate map
     p->ckpt_bytes = checkpoint_bytes(w, h);
     p->scratch_bytes = ((p->ckpt_bytes + (size_t)std::max(w, h) * 64 + (size_t)(w + h) * sizeof(int) + 65536) + 255) & ~(size_t)255;
     p->map_bytes = (size_t)w * h * 4 * sizeof(float);
     p->fir = p->hs < 0.5f || p->vs < 0.5f;     // gauss.c:662-665
+    if (p->fir) {
+        // the FIR path's flags and taps take the checkpoints' place; the taps grow with the deviation, which no range bounds
+        // (one axis below half a pixel, the other as large as the caller likes), so they are counted, not assumed to fit
+        const size_t aux = fir_aux_bytes(w, h, p->hs, p->vs);
+        if (aux == 0) { *err = "gaussian_blur: deviation too large for the FIR path"; return -1; }
+        p->scratch_bytes = std::max(p->scratch_bytes, (aux + 255) & ~(size_t)255);
+    }
     // Does render_image map output pixel (x, y) to texel (x, y)?  Evaluated on the host with the
     // operations of k_render_drawable (IEEE float: same results), once per row and column.
     bool identity = !p->fir && in.kind == IMG_DRAWABLE && in.w == w && in.h == h;

@@ -670,7 +670,8 @@ def test_complex_math_float_ulps(expr, max_ulp, scale):
 @pytest.mark.parametrize("flat", [False, True])
 def test_gauss_fir_path_matches_oracle(hdev, vdev, flat):
     """sigma < 0.5 px on an axis selects the reference's FIR/RLE blur (gauss.c:500-639); a mostly
-    flat image additionally selects its run-length branch (do_encoded_lre) per line."""
+    flat image additionally selects its run-length branch (do_encoded_lre) per line.  The float maps are the
+    oracle's bit for bit (tests/test_gpu_gauss_fir.py), and so are the bytes."""
     w, h = 333, 251
     if flat:
         img = np.full((h, w, 3), 40, np.uint8)
@@ -681,7 +682,7 @@ def test_gauss_fir_path_matches_oracle(hdev, vdev, flat):
     uv = {"hdev": hdev, "vdev": vdev}
     flt, got = hip_render("gauss_direct", w, h, uv, img)
     want = cpu_render(flt, w, h, uv, img)
-    assert stats(got, want)[0] <= 1
+    assert np.array_equal(got, want), stats(got, want)
 
 
 @pytest.mark.parametrize("bpp", [1, 2, 3])
