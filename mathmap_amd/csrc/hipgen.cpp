@@ -824,6 +824,7 @@ struct Generator {
         emit_pixel_kernel();
         ks.source = out.str();
         ks.key = text_key(ks.source);
+        ks.wrapping_ints = opt.edge_x >= 2 || opt.edge_y >= 2;      // REFLECT, ROTATE (KernelSource::wrapping_ints)
     }
 
     // the compile-time options as #defines; decides the workgroup shape, the unroll factor and pair mode

@@ -52,6 +52,12 @@ struct KernelSource {
     std::string rows_name;
     int direct_native = -1;       // index into natives: the pixel is that result sampled at (x, y) and nothing else
     std::string key;              // cache key (hash of source)
+    // Compile with -fwrapv.  apply_edge_behaviour (builtins.c:40-119) negates and mirrors coordinates in ints (`-x % width`,
+    // `(height - 1) - y`), and a coordinate that is NaN, infinite or beyond +-2^31 px arrives there as INT_MIN (mm_f2i): the
+    // reference's x86 ints wrap (-INT_MIN is INT_MIN, INT_MIN % n is negative: the pixel stays outside), while signed overflow
+    // is undefined for the compiler, which turned INT_MIN % 13 into a texel inside the image.  Set for REFLECT and ROTATE edges,
+    // the only code with such arithmetic; every other kernel is compiled as before.
+    bool wrapping_ints = false;
     // The clip variant of the module (mm_prologue_clip, mm_rows_clip, mm_pixels_clip): `source` with these spans
     // replaced, in order -- the kernels' heads; every body is the same text (clip_kernel_source)
     struct Splice { size_t begin, end; std::string text; };

@@ -243,6 +243,7 @@ static int jit_source(const KernelSource &ks, std::vector<char> &code_object) {
         std::istringstream is(e);
         for (std::string w; is >> w;) { extra.push_back(w); extra_key += "_" + std::to_string(std::hash<std::string>()(w) & 0xffff); }
     }
+    if (ks.wrapping_ints) { extra.push_back("-fwrapv"); extra_key += "_wrapv"; }     // (hipgen.h: KernelSource::wrapping_ints)
     std::string path = cache_dir() + "/" + ks.key + "_o2" + extra_key + ".hsaco";   // _o2: option-set version
     std::ifstream in(path, std::ios::binary);
     const char *ov = getenv("MMHIP_SOURCE_OVERRIDE");
@@ -336,6 +337,7 @@ static const mm::KernelSource &clip_source(mmhip_filter *f) {
         f->clip_ks.prologue_name = "mm_prologue_clip";
         f->clip_ks.rows_name = "mm_rows_clip";
         f->clip_ks.pixel_name = "mm_pixels_clip";
+        f->clip_ks.wrapping_ints = f->ks.wrapping_ints;
     }
     return f->clip_ks;
 }

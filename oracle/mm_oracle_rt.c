@@ -94,7 +94,13 @@ mmo_tup4 mmo_tuple_from_color(color_t c) {
 
 /* ---- pixel fetch ------------------------------------------------------------ */
 
-/* builtins.c:40-119 */
+/* builtins.c:40-119.  A coordinate that is NaN, infinite or beyond +-2^31 px arrives as INT_MIN (cvttsd2si).  The reference
+ * negates it (`-x % width`) and mirrors it (`(height - 1) - y`) in ints, which overflows: on x86 both wrap, -INT_MIN is INT_MIN
+ * and INT_MIN % n is negative, so the pixel stays outside.  Written as it stands in the reference that is undefined here too,
+ * and gcc -O2 used it: inlined into get_pixel it dropped the `x < 0` test behind `-x % width` and read the texel 11 places
+ * before a 13-wide row.  So the negation and the mirror are spelt in unsigned arithmetic: the wrapping ints of x86. */
+static int wrap_neg(int x) { return (int)(0u - (unsigned)x); }
+static int wrap_sub(int a, int b) { return (int)((unsigned)a - (unsigned)b); }
 static void apply_edge_behaviour(const mmo_args *A, int *_x, int *_y, int width, int height) {
     int x = *_x, y = *_y;
     switch (A->edge_behaviour_x) {
@@ -103,12 +109,12 @@ static void apply_edge_behaviour(const mmo_args *A, int *_x, int *_y, int width,
             else if (x >= width) x %= width;
             break;
         case 2:
-            if (x < 0) x = -x % width;
+            if (x < 0) x = wrap_neg(x) % width;
             else if (x >= width) x = (width - 1) - (x % width);
             break;
         case 3:
-            if (x < 0) { x = -x % width; y = (height - 1) - y; }
-            else if (x >= width) { x = (width - 1) - (x % width); y = (height - 1) - y; }
+            if (x < 0) { x = wrap_neg(x) % width; y = wrap_sub(height - 1, y); }
+            else if (x >= width) { x = (width - 1) - (x % width); y = wrap_sub(height - 1, y); }
             break;
         default: break;
     }
@@ -118,12 +124,12 @@ static void apply_edge_behaviour(const mmo_args *A, int *_x, int *_y, int width,
             else if (y >= height) y %= height;
             break;
         case 2:
-            if (y < 0) y = -y % height;
+            if (y < 0) y = wrap_neg(y) % height;
             else if (y >= height) y = (height - 1) - (y % height);
             break;
         case 3:
-            if (y < 0) { x = (width - 1) - x; y = -y % height; }
-            else if (y >= height) { x = (width - 1) - x; y = (height - 1) - (y % height); }
+            if (y < 0) { x = wrap_sub(width - 1, x); y = wrap_neg(y) % height; }
+            else if (y >= height) { x = wrap_sub(width - 1, x); y = (height - 1) - (y % height); }
             break;
         default: break;
     }
