@@ -35,6 +35,10 @@ struct Knobs {
     // 0: no fused doubling (hipgen_pair.cpp plan_fusion): `d = t + t; r = d + b` of an exit-driven loop stays two additions.
     // Only with the counted back edge: MMHIP_PAIR_EXIT=0 and MMHIP_PAIR_EXIT_TAIL=0 / 1 keep the earlier arithmetic whatever this says
     std::optional<int> pair_fma2 = env_int("MMHIP_PAIR_FMA2");
+    // 0: the pair step as it was (hipgen_pair.cpp emit_pixel_loop): rows, clamp and 64-bit addresses per lane and step, a frame
+    // constant's truth value through a vector compare.  Only with the fused doubling's conditions and without a peeled trip: every
+    // earlier switch keeps its text whatever this says
+    std::optional<int> pair_step = env_int("MMHIP_PAIR_STEP");
     bool pair_no_uniform = env_int("MMHIP_PAIR_NO_UNIFORM").has_value();   // no wave-uniform scalars in pair-mode loops
     std::optional<int> nt_store = env_int("MMHIP_NT_STORE");          // #define MM_NT_STORE, instead of "the kernel fetches"
     std::optional<int> xcd_order = env_int("MMHIP_XCD_ORDER");        // workgroup -> tile order 0 / 1 / 2 (default 2)

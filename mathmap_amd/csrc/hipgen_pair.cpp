@@ -19,6 +19,7 @@
 #include <cstring>
 #include <map>
 #include <set>
+#include <sstream>
 
 #include "hipgen_internal.h"
 
@@ -50,6 +51,10 @@ struct PairGen final : PairMode {
     std::map<const Stmt *, std::vector<Fuse>> fuse_plan;            // loop -> its fused statements
     std::map<const Stmt *, const Fuse *> fusing;                    // those of the loop copies being printed fused, by r ...
     std::set<const Stmt *> fused_away;                              // ... and their d
+    // the fast step (emit_pixel_loop): with the fused doubling and the kernel's own pack, so that every earlier switch gives its earlier text
+    const bool step = fma2 && pack && !env.knobs.pair_peel.value_or(0) && env.knobs.pair_step.value_or(1);
+    bool fast_step = false;                                         // ... and this kernel has a fused loop and a result pack (make_pair_mode)
+    std::vector<std::string> entry_masks;                           // frame constants read as truth values: mm_ub<k> holds the lane mask of entry k
 
     explicit PairGen(const PairEnv &e) : env(e), out(e.out), code(e.code) {}
 
@@ -189,6 +194,12 @@ struct PairGen final : PairMode {
         // uniform bool is a v_cndmask_b32 pair to this compiler, and the mask would sit in vector registers)
         if (uniform.count(p.value)) return "mm_bu((bool)u" + vname(p.value) + ")";
         if (bools.count(p.value)) return vname(p.value);
+        if (fast_step && !defs.count(p.value)) {      // a frame constant: its mask is made once, in front of the pixel loop (emit_pixel_loop)
+            const std::string c = env.prim(p);
+            size_t k = std::find(entry_masks.begin(), entry_masks.end(), c) - entry_masks.begin();
+            if (k == entry_masks.size()) entry_masks.push_back(c);
+            return "mm_ub" + std::to_string(k);
+        }
         return "mm_tob(" + pprim(p, Ty::Int) + ")";
     }
     std::string pprim(const Primary &p, Ty want) {
@@ -824,6 +835,9 @@ struct PairGen final : PairMode {
             c.ind = I;
             if (fused) for (const Fuse &f : fs) { fusing[f.r] = &f; if (!f.keep_d) fused_away.insert(f.d); }
             plan_counted(c, l);
+            // (the fast step: each copy tests its own scalar copy of the mask -- one test ahead of the guard, read by both copies, is a
+            // truth value that lives across a branch, which this compiler carries in a vector register: v_cndmask_b32, v_cmp_ne_u32)
+            if (fast_step && !addends.empty()) out << I << "asm(\"\" : \"+s\"(" << c.a << ".x), \"+s\"(" << c.a << ".y));\n";
             out << I << "while (" << c.a << ".x | " << c.a << ".y) {\n";
             exit_driven_iteration(c, l);
             out << I << "}\n";
@@ -945,6 +959,26 @@ MM_DEV bool mm_fma2_ok(mm_pf b) {
   return __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(b.x) <= 0x1p102f && __builtin_fabsf(b.y) <= 0x1p102f)) == 0ul;
 }
 )";
+        if (fast_step)
+            out << R"(#define MM_PAIR_STEP 1
+// the fast pair step (hipgen_pair.cpp emit_pixel_loop): a step that lies inside the launch's rows addresses the y table and the
+// output as a wave-uniform 64-bit base -- the tile's first row -- plus a 32-bit lane offset that follows mm_p.  The offset is
+// formed next to the access, so base and offset go into the instruction's own saddr form: no 64-bit vector arithmetic is left.
+MM_DEV mm_pf mm_load_y2(const char *sy, unsigned oy) {      // both rows' y, one 8-byte load (the offset is a multiple of 8)
+  typedef float mm_y2v __attribute__((ext_vector_type(2)));
+  const mm_y2v y = *(const mm_y2v *)(sy + oy);
+  return mm_pf{y.x, y.y};
+}
+// a frame constant read as a truth value: wave-uniform, so its lane mask is all ones or zero and is made on the scalar unit, once,
+// in front of the pixel loop.  Bits outside exec are set: mm_xnotb's argument covers it (selects read their own lane's bit, and
+// the mask a loop tests is ANDed with mm_bu(true), which lies inside exec).  (Through a scalar register by name: a select between
+// 64-bit constants on a uniform bool is a v_cndmask_b32 pair to this compiler.)
+MM_DEV mm_bb mm_xbs(int u) {
+  unsigned long m = (unsigned long)(long)__builtin_amdgcn_readfirstlane(u != 0 ? -1 : 0);
+  asm("" : "+s"(m));
+  return mm_bb{m, m};
+}
+)";
         emit_store_pair();
     }
 
@@ -1010,22 +1044,27 @@ MM_DEV bool mm_fma2_ok(mm_pf b) {
             if (n > 2) w += " | __builtin_amdgcn_perm(" + (n > 3 ? u(3) : u(2)) + ", " + u(2) + ", " + hex(sel(2, n > 3 ? 3 : -1)) + ")";
             return k ? w + " | " + hex(k) : w;
         };
+        // clamp, convert inside one round-toward-zero window: ua<j>, ub<j> hold the bytes of value j
+        auto convert = [&](const char *I) {
+            out << I;
+            for (int j = 0; j < n; ++j) out << " a" << j << " = mm_clamp01(a" << j << "); b" << j << " = mm_clamp01(b" << j << ");";
+            out << "\n" << I << " unsigned";
+            for (int j = 0; j < n; ++j) out << (j ? ", " : " ") << "ua" << j << ", ub" << j;
+            out << ";\n" << I << " asm volatile(\"s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3\\n\\t\"\n";
+            for (int j = 0; j < 2 * n; ++j) out << I << "              \"v_fma_f32 %" << j << ", %" << 2 * n + j << ", %" << 4 * n << ", %" << 4 * n + 1 << "\\n\\t\"\n";
+            out << I << "              \"s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\"\n" << I << "              :";
+            for (int j = 0; j < n; ++j) out << (j ? ", " : " ") << "\"=&v\"(ua" << j << "), \"=&v\"(ub" << j << ")";
+            out << "\n" << I << "              :";
+            for (int j = 0; j < n; ++j) out << " \"v\"(a" << j << "), \"v\"(b" << j << "),";
+            out << " \"s\"(255.0f), \"v\"(8388608.0f));\n";
+        };
         out << "// this kernel's result pack (hipgen_pair.cpp emit_store_pair): both pixels of a step, " << n << " distinct value" << (n > 1 ? "s" : "")
             << " per pixel, literal bytes " << hex(k) << "\n"
             << "MM_DEV void mm_store_pair(const mm_args &A, int row_a, int row_b, int col";
         for (int j = 0; j < n; ++j) out << ", float a" << j << ", float b" << j;
-        out << ") {\n  if (__builtin_expect(!A.floatmap && A.output_bpp == 4, 1)) {\n   ";
-        for (int j = 0; j < n; ++j) out << " a" << j << " = mm_clamp01(a" << j << "); b" << j << " = mm_clamp01(b" << j << ");";
-        out << "\n    unsigned";
-        for (int j = 0; j < n; ++j) out << (j ? ", " : " ") << "ua" << j << ", ub" << j;
-        out << ";\n    asm volatile(\"s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3\\n\\t\"\n";
-        for (int j = 0; j < 2 * n; ++j) out << "                 \"v_fma_f32 %" << j << ", %" << 2 * n + j << ", %" << 4 * n << ", %" << 4 * n + 1 << "\\n\\t\"\n";
-        out << "                 \"s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\"\n                 :";
-        for (int j = 0; j < n; ++j) out << (j ? ", " : " ") << "\"=&v\"(ua" << j << "), \"=&v\"(ub" << j << ")";
-        out << "\n                 :";
-        for (int j = 0; j < n; ++j) out << " \"v\"(a" << j << "), \"v\"(b" << j << "),";
-        out << " \"s\"(255.0f), \"v\"(8388608.0f));\n"
-            << "    MM_STORE_U32((unsigned *)((unsigned char *)A.out + (long)row_a * A.row_stride + (long)col * 4), " << word("a") << ");\n"
+        out << ") {\n  if (__builtin_expect(!A.floatmap && A.output_bpp == 4, 1)) {\n";
+        convert("   ");
+        out << "    MM_STORE_U32((unsigned *)((unsigned char *)A.out + (long)row_a * A.row_stride + (long)col * 4), " << word("a") << ");\n"
             << "    MM_STORE_U32((unsigned *)((unsigned char *)A.out + (long)row_b * A.row_stride + (long)col * 4), " << word("b") << ");\n"
             << "    return;\n  }\n  mm_tup<4> ra, rb;\n";
         for (int i = 0; i < 4; ++i) {
@@ -1033,27 +1072,100 @@ MM_DEV bool mm_fma2_ok(mm_pf b) {
             else out << "  ra.v[" << i << "] = a" << pk.src[i] << "; rb.v[" << i << "] = b" << pk.src[i] << ";\n";
         }
         out << "  mm_store_pixel(A, row_a, col, ra);\n  mm_store_pixel(A, row_b, col, rb);\n}\n";
+        if (!fast_step) return;
+        out << "// the same words from a fast step (mm_load_y2, above): `so` the step's first output row, oa / ob this lane's offsets in its two rows\n"
+            << "MM_DEV void mm_store_step(unsigned char *so, unsigned oa, unsigned ob";
+        for (int j = 0; j < n; ++j) out << ", float a" << j << ", float b" << j;
+        out << ") {\n";
+        convert(" ");
+        out << "  MM_STORE_U32((unsigned *)(so + oa), " << word("a") << ");\n"
+            << "  MM_STORE_U32((unsigned *)(so + ob), " << word("b") << ");\n}\n";
     }
     // two pixels (rows mm_p and mm_p + 1 of this work-item's column) in lockstep
+    //
+    // The fast step (MMHIP_PAIR_STEP unset or 1; 0: the step as it was, byte for byte).  A workgroup's tile is MM_TILE_W columns by
+    // MM_TILE_H * A.ppt rows, a step covers 2 * MM_TILE_H consecutive rows of it, and a work-item's rows are 2 * (threadIdx.x /
+    // MM_TILE_W) and the next one from the step's first row.  So a lane's byte offsets from the tile's first row -- in the output and
+    // in the y table -- are known in front of the pixel loop, that row is wave-uniform (two 64-bit bases, made once), and a step
+    // adds its distance from it, a multiple of mm_p, to the 32-bit offsets: one scalar multiply and three 32-bit vector adds.  The
+    // step as it was computes both rows, clamps them to the launch's last row and forms three 64-bit addresses per lane (two of
+    // them 64-bit multiply-adds), every step.  It is still there, unchanged, for a step whose last row lies past the launch's
+    // rows (the clamp is needed there) and for every launch the fast step is not for: another output format than RGBA8
+    // (mm_store_pair's own branch), a lane offset that does not fit 32 bits, a y table or a tile height that would misalign the
+    // 8-byte load.  All of that is decided once, at kernel entry (mm_fast), and folded into mm_pin, the steps of this tile that lie
+    // inside the launch's rows: the test per step is mm_p < mm_pin, wave-uniform.  No address is truncated: the bases are 64-bit,
+    // and a frame too large for 32-bit lane offsets renders by the other step.  The loops are printed once; only what stands in
+    // front of them and behind them is chosen per step.  Nothing is advanced per step and the test is written as one-sided ifs on
+    // copies of mm_pin because scalar instructions are what this kernel has least room for (a CU's scalar unit serves four SIMDs):
+    // with both bases advanced and one truth value for the test the step was slower than the one it replaces.
     void emit_pixel_loop(const std::string &I) override {
-        out << "#pragma unroll 1\n" << I << "for (; mm_p < A.ppt; mm_p += 2) {\n"
-            << I << "  // vertically adjacent pixels: they mostly take the same path (a wave covers 16 x 8 pixels per step)\n"
-            << I << "  const int rl_a = row0 + (int)(threadIdx.x / MM_TILE_W) + mm_p * MM_TILE_H, rl_b = rl_a + 1;\n"
-            << I << "  const int row_a = rl_a < A.num_rows ? rl_a : A.num_rows - 1, row_b = rl_b < A.num_rows ? rl_b : A.num_rows - 1;\n"
-            << I << "  const mm_pf mm_y2 = {A.ytab[row_a], A.ytab[row_b]};    // CALC_VIRTUAL_Y per row, by the prologue\n";
+        Pack pk;
+        const bool packed = plan_pack(pk);
+        if (fast_step) {      // (only with a pack: make_pair_mode)
+            // the loop's text first: it says which frame constants it reads as truth values (pbool)
+            std::ostringstream body;
+            std::streambuf *const own = out.rdbuf(body.rdbuf());
+            emit_steps(I, pk, packed);
+            out.rdbuf(own);
+            out << I << "// the fast step (hipgen_pair.cpp emit_pixel_loop): decided once; this lane's offsets from the tile's first row, that row's wave-uniform bases\n"
+                << I << "const bool mm_fast = !A.floatmap && A.output_bpp == 4 && A.row_stride >= 0 && ((MM_TILE_H * A.ppt) & 1) == 0 && ((unsigned long)A.ytab & 7ul) == 0ul &&\n"
+                << I << "                     (long)(MM_TILE_H * (A.ppt + 1) - 1) * A.row_stride + (long)A.region_width * 4 <= 0xffffffffl;\n"
+                << I << "const unsigned mm_tr = threadIdx.x / MM_TILE_W;\n"
+                << I << "const unsigned mm_oa = (unsigned)col * 4u + 2u * mm_tr * (unsigned)A.row_stride, mm_ob = mm_oa + (unsigned)A.row_stride, mm_oy = 8u * mm_tr;\n"
+                << I << "const unsigned mm_ss = (unsigned)(MM_TILE_H * A.row_stride);      // mm_p counts rows MM_TILE_H apart\n"
+                << I << "const int mm_sr = __builtin_amdgcn_readfirstlane(tile_y * (MM_TILE_H * A.ppt));\n"
+                << I << "unsigned char *const mm_so = (unsigned char *)A.out + (long)mm_sr * A.row_stride;\n"
+                << I << "const char *const mm_sy = (const char *)(A.ytab + mm_sr);\n"
+                << I << "// the steps, in mm_p, that lie inside the launch's rows (none: not a launch for the fast step): one scalar compare per step\n"
+                << I << "const int mm_pin = mm_fast ? (A.num_rows - mm_sr) / (2 * MM_TILE_H) * 2 : 0;\n"
+                << I << "// (a copy per test: one truth value read in several places would live across branches, which this compiler keeps as a lane\n"
+                << I << "// mask -- s_cselect_b64, s_and_b64 with exec, a branch on vcc -- and an if / else on it goes through a flag block; four one-sided\n"
+                << I << "// tests of scalars the compiler takes for unrelated are s_cmp and a branch on scc each)\n"
+                << I << "int mm_pin_a = mm_pin, mm_pin_b = mm_pin, mm_pin_c = mm_pin;\n"
+                << I << "asm(\"\" : \"+s\"(mm_pin_a), \"+s\"(mm_pin_b), \"+s\"(mm_pin_c));\n";
+            for (size_t k = 0; k < entry_masks.size(); ++k)
+                out << I << "const mm_bb mm_ub" << k << " = mm_xbs(" << entry_masks[k] << ");\n";
+            out << body.str();
+            return;
+        }
+        emit_steps(I, pk, packed);
+    }
+    void emit_steps(const std::string &I, const Pack &pk, bool packed) {
+        const std::string E = fast_step ? I + "  " : I;      // the step as it was: inside an else
+        out << "#pragma unroll 1\n" << I << "for (; mm_p < A.ppt; mm_p += 2) {\n";
+        if (fast_step)
+            out << I << "  const bool mm_in = mm_p < mm_pin;      // wave-uniform: the fast step is for this launch and the whole step lies inside its rows\n"
+                << I << "  mm_pf mm_y2;\n"
+                << I << "  if (__builtin_expect(mm_in, 1)) mm_y2 = mm_load_y2(mm_sy, mm_oy + (unsigned)mm_p * (4u * MM_TILE_H));\n"
+                << I << "  if (__builtin_expect(mm_p >= mm_pin_a, 0)) {      // (!mm_in) the step as it was\n";
+        out << E << "  // vertically adjacent pixels: they mostly take the same path (a wave covers 16 x 8 pixels per step)\n"
+            << E << "  const int rl_a = row0 + (int)(threadIdx.x / MM_TILE_W) + mm_p * MM_TILE_H, rl_b = rl_a + 1;\n"
+            << E << "  const int row_a = rl_a < A.num_rows ? rl_a : A.num_rows - 1, row_b = rl_b < A.num_rows ? rl_b : A.num_rows - 1;\n"
+            << E << (fast_step ? "  mm_y2 = mm_pf{A.ytab[row_a], A.ytab[row_b]};" : "  const mm_pf mm_y2 = {A.ytab[row_a], A.ytab[row_b]};") << "    // CALC_VIRTUAL_Y per row, by the prologue\n";
+        if (fast_step) out << I << "  }\n";
         std::set<Value *> seen;
         for (Value *v : env.pix_defs)
             if (v->index >= 0 && seen.insert(v).second) out << I << "  " << pair_ctype(v) << " " << vname(v) << ";\n";
         stmts(code.body, I + "  ", "mm_bu(true)");
-        Pack pk;
-        if (plan_pack(pk)) {
-            out << I << "  // a row past the end was evaluated as the last row: storing it there again writes the same bytes\n"
-                << I << "  mm_store_pair(A, row_a, row_b, col";
+        if (packed) {
+            std::string vals;
             for (const Value *v : pk.vals) {
                 const std::string e = pprim(Primary::V(const_cast<Value *>(v)), Ty::Float);
-                out << ", " << e << ".x, " << e << ".y";
+                vals += ", " + e + ".x, " + e + ".y";
             }
-            out << ");\n" << I << "}\n";
+            if (fast_step)
+                out << I << "  if (__builtin_expect(mm_p < mm_pin_b, 1)) {      // (mm_in)\n"
+                    << I << "    const unsigned mm_sp = (unsigned)mm_p * mm_ss;\n"
+                    << I << "    mm_store_step(mm_so, mm_oa + mm_sp, mm_ob + mm_sp" << vals << ");\n"
+                    << I << "  }\n"
+                    << I << "  if (__builtin_expect(mm_p >= mm_pin_c, 0)) {      // (!mm_in) the step as it was\n"
+                    << E << "  const int rl_a = row0 + (int)(threadIdx.x / MM_TILE_W) + mm_p * MM_TILE_H, rl_b = rl_a + 1;\n"
+                    << E << "  const int row_a = rl_a < A.num_rows ? rl_a : A.num_rows - 1, row_b = rl_b < A.num_rows ? rl_b : A.num_rows - 1;\n";
+            out << E << "  // a row past the end was evaluated as the last row: storing it there again writes the same bytes\n"
+                << E << "  mm_store_pair(A, row_a, row_b, col" << vals << ");\n";
+            if (fast_step)
+                out << I << "  }\n";
+            out << I << "}\n";
             return;
         }
         out << I << "  mm_tup<4> mm_ra, mm_rb;\n";
@@ -1074,6 +1186,10 @@ std::unique_ptr<PairMode> make_pair_mode(const PairEnv &env) {
     if (!g->eligible()) return nullptr;
     g->infer_bools();
     g->plan_fusion();
+    PairGen::Pack pk;
+    // (with a fused loop only: a kernel in which nothing is fused has one text under either value of MMHIP_PAIR_FMA2, and
+    // MMHIP_PAIR_FMA2=0 is one of the switches that keep their text)
+    g->fast_step = g->step && !g->fuse_plan.empty() && g->plan_pack(pk);
     return g;
 }
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Instruction counts of a pair-mode kernel's innermost loop, offline (needs hipcc, no GPU).
 
-    python tools/pair_loop_isa.py mandelbrot [-D name=value ...] [--asm] [--all]
+    python tools/pair_loop_isa.py mandelbrot [-D name=value ...] [--asm] [--all] [--step]
 
 Emits the specialised kernel text of the filter under the current environment (so MMHIP_PAIR_EXIT=0 and the
 other generator switches apply), compiles it to gfx950 assembly with the option list of the JIT (runtime.cpp
@@ -12,6 +12,9 @@ mm_pixels (with --all: every innermost loop, in program order) and prints VALU /
   * its exit block: what follows, up to the next branch back to the header or out (for the exit-driven loops:
     the block that writes the exit copies; for the per-iteration form there is none, the block shown is
     whatever follows the loop).
+
+With --step it lists one step of the pixel loop instead -- what a pair step costs outside its inner loops (step_listing,
+below).
 
 s_nop and s_waitcnt are listed but not counted.  The counts are those of the compiler that is installed; its
 version is printed first."""
@@ -169,12 +172,124 @@ def analyse_all(asm, show):
     return [analyse_loop(ins, header, depth, show) for header, depth in innermost_headers(lines)]
 
 
+# ---- one step of the pixel loop, outside its inner loops ----
+MUL64 = ("v_mad_i64_i32", "v_mad_u64_u32", "v_mul_hi_u32", "v_mul_hi_i32")
+
+
+def blocks_of(lines):
+    """[{"name", "ins": [(opcode, text)], "header": depth or None, "in": (header label, depth) or None}] in layout order: a
+    block starts at a label or at the compiler's `; %bb.N:` comment, the comments behind it say which loop it lies in"""
+    out, cur = [], None
+    for l in lines:
+        m = re.match(r"^(\.LBB\d+_\d+):", l) or re.match(r"^; %bb\.(\d+):", l)
+        if m:
+            cur = {"name": m.group(1) if m.group(1).startswith(".") else "%bb." + m.group(1), "ins": [], "header": None, "in": None}
+            out.append(cur)
+        if cur is None:
+            continue
+        m = re.search(r"This (?:Inner )?Loop Header: Depth=(\d+)", l)
+        if m and not cur["ins"]:
+            cur["header"] = int(m.group(1))
+        m = re.search(r"in Loop: Header=(BB\d+_\d+) Depth=(\d+)", l)
+        if m and not cur["ins"]:
+            cur["in"] = (".L" + m.group(1), int(m.group(2)))
+        t = l.split(";")[0].strip()
+        if not t or t.startswith(".") or re.match(r"^[\w.$]+:", t):
+            continue
+        cur["ins"].append((t.split()[0], t))
+    return out
+
+
+def step_listing(asm, show=False, quiet=False):
+    """One step of mm_pixels' pixel loop (its outermost loop that has inner loops), the inner loops left out.
+
+    The step's blocks -- those whose innermost loop is the pixel loop -- and the inner loops, each taken as one node, form a
+    graph; every way from the loop header back to it is walked, and among those that pass through the last inner loop in
+    program order and no other (the convention of the loop listing: for a fused loop, its fused copy) the one on which the fewest
+    conditional branches are taken is listed as the likely path: the compiler lays the likely side of a branch out as the
+    fall-through, and both the RGBA8 store and the fast step are marked likely in the text.  Counted: vector, scalar, branch and memory instructions of the step's blocks on
+    that path; named: 64-bit multiplies (v_mad_i64_i32, v_mad_u64_u32, v_mul_hi_*) and vector compares among them."""
+    blocks = blocks_of(kernel_lines(asm, "mm_pixels"))
+    outer = next((b for b in blocks if b["header"] == 1 and any(c["in"] == (b["name"], 1) or (c["header"] or 0) > 1 for c in blocks)), None)
+    if outer is None:
+        sys.exit("mm_pixels has no pixel loop with inner loops")
+    # node of every block: itself (a block of the step), the depth-2 loop it lies in, or None (outside the pixel loop)
+    node, inner, cur2 = {}, [], None
+    started = False
+    for b in blocks:
+        if b is outer:
+            started = True
+        if b is outer or b["in"] == (outer["name"], 1):
+            node[b["name"]] = b["name"]
+        elif started and (b["header"] or 0) == 2:
+            cur2 = b["name"]
+            inner.append(cur2)
+            node[b["name"]] = cur2
+        elif started and ((b["header"] or 0) > 2 or (b["in"] and b["in"][1] >= 2)):
+            node[b["name"]] = cur2
+        else:
+            node[b["name"]] = None
+    # edges, with what they cost: 1 for a conditional branch that is taken, 0 for falling through and for s_branch
+    succ = {}
+    for i, b in enumerate(blocks):
+        n = node[b["name"]]
+        if n is None:
+            continue
+        # (a wave that runs has lanes: s_cbranch_execnz is always taken, s_cbranch_execz never)
+        targets = [(t.split()[-1], 0 if op in ("s_branch", "s_cbranch_execnz") or n in inner else 1) for op, t in b["ins"]
+                   if classify(op) == "branch" and op != "s_cbranch_execz"]
+        last = b["ins"][-1][0] if b["ins"] else None
+        if last not in ("s_branch", "s_endpgm", "s_cbranch_execnz") and i + 1 < len(blocks):
+            targets.append((blocks[i + 1]["name"], 0))
+        for t, cost in targets:
+            tn = node.get(t)
+            if tn is not None and (tn != n or tn == outer["name"]):
+                e = succ.setdefault(n, {})
+                e[tn] = min(cost, e.get(tn, cost))
+    by_name = dict((b["name"], b) for b in blocks)
+    paths, stack = [], [(outer["name"], [outer["name"]], 0)]
+    while stack and len(paths) < 200000:
+        n, path, taken = stack.pop()
+        for t, cost in succ.get(n, {}).items():
+            if t == outer["name"]:
+                paths.append((taken + cost, path))
+            elif t not in path:
+                stack.append((t, path + [t], taken + cost))
+    last_inner = inner[-1] if inner else None
+    through = [p for p in paths if [n for n in p[1] if n in inner] == [last_inner]] or paths
+    if not through:
+        sys.exit("no way through the pixel loop found")
+    best = min(through, key=lambda p: (p[0], len(p[1])))[1]
+    ins = [(n, op, t) for n in best if n not in inner for op, t in by_name[n]["ins"]]
+    c = count([(None, op, t) for _, op, t in ins])
+    res = dict(c)
+    res["mul64"] = [t for _, op, t in ins if op in MUL64]
+    res["vcmp"] = [t for _, op, t in ins if op.startswith("v_cmp")]
+    res["vmem"] = [t for _, op, t in ins if classify(op) == "mem"]
+    res["blocks"] = best
+    res["ways"] = len(through)
+    if not quiet:
+        print("pair step     VALU %2d  SALU %2d  branch %d  memory %d  (outside the inner loops, likely path: %d blocks, %d ways through %s)" % (
+            c["valu"], c["salu"], c["branch"], c["mem"], len([n for n in best if n not in inner]), len(through), last_inner))
+        print("  64-bit multiplies: " + ("; ".join(res["mul64"]) or "none"))
+        print("  vector compares  : " + ("; ".join(res["vcmp"]) or "none"))
+        print("  memory           : " + ("; ".join(res["vmem"]) or "none"))
+        if show:
+            for n in best:
+                print("  " + n + (":  (inner loop)" if n in inner else ":"))
+                if n not in inner:
+                    for op, t in by_name[n]["ins"]:
+                        print("      " + t)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("filter", help="name of a filter of tests/filters.py (mandelbrot, ...)")
     ap.add_argument("-D", dest="defs", action="append", default=[], metavar="name=value", help="user value to specialise on")
     ap.add_argument("--asm", action="store_true", help="print the instructions of both blocks")
     ap.add_argument("--all", action="store_true", help="every innermost loop of mm_pixels (a fused loop has two copies), not only the last")
+    ap.add_argument("--step", action="store_true", help="one step of the pixel loop outside its inner loops, likely path, instead of the loops")
     ap.add_argument("--source", metavar="FILE", help="analyse this kernel text instead of the generated one")
     args = ap.parse_args()
     ver = subprocess.run([hipcc(), "--version"], capture_output=True, text=True).stdout.strip().split("\n")
@@ -191,7 +306,10 @@ def main():
             k, v = d.split("=", 1)
             uv[k] = float(v) if "." in v else int(v)
         source = F.load(args.filter).specialized(uv).kernel_source
-    (analyse_all if args.all else analyse)(assembly(source), args.asm)
+    if args.step:
+        step_listing(assembly(source), args.asm)
+    else:
+        (analyse_all if args.all else analyse)(assembly(source), args.asm)
 
 
 if __name__ == "__main__":
