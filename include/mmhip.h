@@ -287,6 +287,46 @@ long mmhip_clip_supersampled_batches(mmhip_invocation *inv);
    over rows_per_item rows). */
 enum { MMHIP_CLIP_SS_PLAN_FIELDS = 7 };
 int mmhip_filter_clip_supersample_plan(const mmhip_filter *f, int region_w, int region_h, int bpp, int frames, int64_t *out);
+/* A motion-blurred clip (an extension): every output frame is the mean of `samples` = K sub-samples spread over `span`
+   units of t, rendered as float maps in HBM and averaged there by a combine kernel.  frames, ts, the region, the rows,
+   out_device, row_stride, frame_stride, bpp, floatmap and stream are mmhip_render_clip's; asynchronous.
+     - samples is 1 to MMHIP_SHUTTER_MAX_SAMPLES (256); span is any finite float, 0 and negative ones included.
+     - Sub-sample j (0 <= j < K) of output frame i is what mmhip_render produces as a float map at frame number
+       frames[i] -- the same for every j, so in(xy, frame) reads one frame of a sequence -- and at the time
+       t_ij = (float)((double)ts[i] + ((double)span * (double)j) / (double)K): double arithmetic, the product before
+       the quotient, one rounding to float.
+     - Per pixel and channel, in f32, round to nearest, no fma, denormals kept: acc = f_0; acc = acc + f_j for j = 1 ..
+       K - 1 in that order; m = acc * inv_k with inv_k = (float)(1.0 / (double)K).
+     - m is stored as mmhip_render stores a pixel: without floatmap the pixel store's bytes at output_bpp 1 - 4 (CLAMP01,
+       products in double, truncation, grey for bpp 1 and 2, alpha at bpp - 1 for bpp 2 and 4), rows row_stride apart;
+       with floatmap the four floats, rows 16 * render_width bytes apart with the region's columns at the start of each
+       row.  Bytes between rows and between frames are not touched.
+     - samples = 1 is mmhip_render_clip: the call delegates before anything else.
+     - Per batch of B output frames: one nested mmhip_render_clip of B * samples_per_pass float maps (frames[i] repeated,
+       the times above, frame_stride = bytes_per_sample = rows * 16 * render_width) into a temporary of the
+       invocation's, then one launch of the combine on the same stream.  The nested call batches, runs native filters
+       and closures and picks specialised variants as it always does: nothing is refused that mmhip_render_clip takes.
+     - MMHIP_CLIP_SHUTTER_BYTES (read once, default 8 GiB) bounds the temporary.  Where the K sub-samples of one frame
+       fit: frames_per_batch = min(budget / (K * bytes_per_sample), 65 535, num_frames) and one pass.  Otherwise one
+       frame per batch in passes of samples_per_pass = max(1, budget / bytes_per_sample - 1) sub-samples, the running
+       sum carried from pass to pass in one more float map; the order of the sum, and so its bits, are the same.  One
+       sub-sample and the carry map are allocated even where they exceed the budget.
+     - The invocation's state (memo, native maps, sampling offsets, the counters of other paths) is left as the nested
+       clip calls leave it.  mmhip_clip_shutter_batches rises by one per batch; with mmhip_enable_timing the combine is
+       reported by mmhip_drain_native_kernel_ms as shutter_combine_clip, once per pass.
+     - Not combined with supersampling: there is no motion-blurred mmhip_render_clip_supersampled.
+   Errors: samples out of range; a span that is not finite; a sub-sample map beyond 4 GiB; out of device memory (the
+   message names MMHIP_CLIP_SHUTTER_BYTES); mmhip_render_clip's own. */
+enum { MMHIP_SHUTTER_MAX_SAMPLES = 256, MMHIP_CLIP_SHUTTER_PLAN_FIELDS = 6 };
+int mmhip_render_clip_shutter(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
+                              int region_x, int region_y, int region_w, int region_h, int first_row, int last_row,
+                              void *out_device, int row_stride, int64_t frame_stride, int bpp, int floatmap, void *stream);
+long mmhip_clip_shutter_batches(mmhip_invocation *inv);
+/* How mmhip_render_clip_shutter renders `frames` frames of num_rows rows at render width render_w with `samples`
+   sub-samples (needs no GPU).  out[] receives MMHIP_CLIP_SHUTTER_PLAN_FIELDS values: frames_per_batch, batches,
+   samples_per_pass, passes (per frame), bytes_per_sample and carry (1: a carry map joins the passes). */
+int mmhip_filter_clip_shutter_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int samples, int frames,
+                                   int64_t *out);
 /* Convenience: whole frame to a host RGBA8 buffer (width*height*4 bytes); synchronous. */
 int mmhip_render_host(mmhip_invocation *inv, int frame, float t, uint8_t *out_rgba);
 int mmhip_sync(mmhip_invocation *inv);

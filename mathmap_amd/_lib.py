@@ -92,6 +92,11 @@ SYMBOLS = {
                                                  C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
     "mmhip_clip_supersampled_batches": (C.c_long, [C.c_void_p]),
     "mmhip_filter_clip_supersample_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "mmhip_render_clip_shutter": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int, C.c_float, C.c_int,
+                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                            C.c_void_p]),
+    "mmhip_clip_shutter_batches": (C.c_long, [C.c_void_p]),
+    "mmhip_filter_clip_shutter_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "mmhip_render_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "mmhip_sync": (C.c_int, [C.c_void_p]),
     "mmhip_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),
@@ -124,6 +129,8 @@ SELFTEST_SYMBOLS = {
     "mmhip_selftest_eval_binary": (C.c_int, [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_void_p]),
     "mmhip_selftest_gauss_tolerance_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
     "mmhip_selftest_combine_ms": (C.c_long, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "mmhip_selftest_shutter_combine": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                                 C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double)]),
 }
 SELFTEST_PATH = os.path.join(_HERE, "libmathmap_hip_selftest.so")
 _selftest = None

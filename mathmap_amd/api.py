@@ -28,6 +28,9 @@ CLIP_PLAN_FIELDS = ("grid_x", "frames_per_batch", "batches", "shared_slot")
 CLIP_NATIVE_PLAN_FIELDS = ("eligible", "frames_per_batch", "batches", "bytes_per_frame")
 # mmhip_filter_clip_supersample_plan's out[]
 CLIP_SS_PLAN_FIELDS = ("batched", "frames_per_batch", "batches", "bytes_per_frame", "long_pitch", "rows_per_item", "pixels_per_item")
+# mmhip_filter_clip_shutter_plan's out[]
+CLIP_SHUTTER_PLAN_FIELDS = ("frames_per_batch", "batches", "samples_per_pass", "passes", "bytes_per_sample", "carry")
+SHUTTER_MAX_SAMPLES = 256
 
 
 class MathMapError(RuntimeError):
@@ -36,6 +39,17 @@ class MathMapError(RuntimeError):
 
 def _err():
     return lib().mmhip_last_error().decode("utf-8", "replace")
+
+
+def shutter_sample_ts(ts, samples, span):
+    """The times of a motion-blurred clip's sub-samples (mmhip_render_clip_shutter): float32 [N, samples], entry [i, j] =
+    (float)((double)ts[i] + ((double)span * (double)j) / (double)samples), with ts and span taken as float32."""
+    samples = int(samples)
+    if not 1 <= samples <= SHUTTER_MAX_SAMPLES:
+        raise ValueError("shutter_sample_ts: samples must be 1 to %d, not %d" % (SHUTTER_MAX_SAMPLES, samples))
+    ts = np.asarray(ts, dtype=np.float32).reshape(-1).astype(np.float64)
+    j = np.arange(samples, dtype=np.float64)
+    return (ts[:, None] + (np.float64(np.float32(span)) * j)[None, :] / np.float64(samples)).astype(np.float32)
 
 
 class Filter:
@@ -209,6 +223,14 @@ class Filter:
         if lib().mmhip_filter_clip_native_plan(self._h, region_w, num_rows, rw, rh, frames, out) != 0:
             raise MathMapError(_err())
         return dict(zip(CLIP_NATIVE_PLAN_FIELDS, out))
+
+    def clip_shutter_plan(self, region_w, num_rows, render_w, samples, frames):
+        """How render_clip(shutter_samples=samples) renders a `frames`-frame clip of num_rows rows of a region at render
+        width render_w: a dict of the CLIP_SHUTTER_PLAN_FIELDS (carry 1: the sub-samples of a frame take several passes)."""
+        out = (C.c_int64 * len(CLIP_SHUTTER_PLAN_FIELDS))()
+        if lib().mmhip_filter_clip_shutter_plan(self._h, region_w, num_rows, render_w, samples, frames, out) != 0:
+            raise MathMapError(_err())
+        return dict(zip(CLIP_SHUTTER_PLAN_FIELDS, out))
 
     def clip_supersample_plan(self, region_w, region_h, frames, bpp=4):
         """How render_clip(supersample=True) renders a `frames`-frame clip of a region: a dict of the CLIP_SS_PLAN_FIELDS
@@ -411,7 +433,8 @@ class Invocation:
                                        row_stride, bpp, 1 if floatmap else 0, C.c_void_p(stream)))
 
     def render_clip(self, num_frames=None, frames=None, ts=None, out_ptr=None, rows=None, region=None, row_stride=None,
-                    frame_stride=None, bpp=4, floatmap=False, stream=0, supersample=False):
+                    frame_stride=None, bpp=4, floatmap=False, stream=0, supersample=False, shutter_samples=1, shutter_span=None,
+                    shutter=None):
         """Renders a clip in batched launches (mmhip_render_clip): frame i at frame number frames[i] and time ts[i].
         `num_frames`=N alone is the CLI's animation: frame = i, t = (float)i / (float)N.  `rows` = (first_row,
         last_row) and `region`, `row_stride`, `bpp`, `floatmap`, `stream` as in render_rows; frame i lands
@@ -419,10 +442,30 @@ class Invocation:
         uint8 [N,H,W,4] array; with it the call is asynchronous and the frames stay in HBM.
         `supersample`=True renders the CLI's -o frames (mmhip_render_clip_supersampled; compile the filter with
         supersampling=True): whole regions of bytes only, so `rows` or `floatmap` with it is a ValueError; without
-        `out_ptr` it returns a uint8 [N,H,W,bpp] array."""
+        `out_ptr` it returns a uint8 [N,H,W,bpp] array.
+        `shutter_samples`=K > 1 renders a motion-blurred clip (mmhip_render_clip_shutter): every frame is the mean of K
+        sub-samples at frame number frames[i] and the times shutter_sample_ts(ts, K, span).  The span is `shutter_span`
+        in units of t, or `shutter`, a fraction of the frame interval, in the `num_frames`=N form only: span =
+        float32(float64(shutter) / N).  Giving both, `shutter` with explicit ts, K > 1 without either, or K > 1 with
+        `supersample` is a ValueError."""
         from .striping import animation_frame_t
         if supersample and (floatmap or rows is not None):
             raise ValueError("render_clip: supersample=True renders whole regions of bytes: neither floatmap nor rows")
+        shutter_samples = int(shutter_samples)
+        if supersample and shutter_samples > 1:
+            raise ValueError("render_clip: supersample=True is not combined with shutter_samples > 1")
+        if shutter is not None and shutter_span is not None:
+            raise ValueError("render_clip: give shutter or shutter_span, not both")
+        if shutter is not None and (frames is not None or ts is not None or num_frames is None):
+            raise ValueError("render_clip: shutter is a fraction of the frame interval of render_clip(num_frames=N); with frames and ts give shutter_span")
+        if shutter_samples > 1 and shutter is None and shutter_span is None:
+            raise ValueError("render_clip: shutter_samples > 1 needs shutter or shutter_span")
+        if shutter is not None:
+            if num_frames < 1:
+                raise MathMapError("render_clip: num_frames must be at least 1")
+            shutter_span = np.float32(np.float64(shutter) / np.float64(num_frames))
+        shuttered = shutter_samples != 1 or shutter_span is not None
+        span = float(np.float32(shutter_span)) if shutter_span is not None else 0.0
         if frames is None and ts is None:
             if num_frames is None:
                 raise MathMapError("render_clip: give num_frames, or frames and ts")
@@ -447,6 +490,11 @@ class Invocation:
             if frame_stride is None:
                 n_rows = max(min(last_row, ry + rh) - max(first_row, 0), 0)
                 frame_stride = n_rows * (16 * self.render_width if floatmap else row_stride)
+            if shuttered:
+                self._check(lib().mmhip_render_clip_shutter(self._h, num_frames, fp, tp, shutter_samples, span, rx, ry, rw, rh, first_row,
+                                                            last_row, C.c_void_p(out_ptr), row_stride, frame_stride, bpp,
+                                                            1 if floatmap else 0, C.c_void_p(stream)))
+                return None
             self._check(lib().mmhip_render_clip(self._h, num_frames, fp, tp, rx, ry, rw, rh, first_row, last_row,
                                                 C.c_void_p(out_ptr), row_stride, frame_stride, bpp, 1 if floatmap else 0,
                                                 C.c_void_p(stream)))
@@ -460,8 +508,12 @@ class Invocation:
         if not dev:
             raise MathMapError(_err())
         try:
-            self._check(lib().mmhip_render_clip(self._h, num_frames, fp, tp, rx, ry, rw, rh, first_row, last_row,
-                                                C.c_void_p(dev), rw * 4, rw * 4 * rh, 4, 0, None))
+            if shuttered:
+                self._check(lib().mmhip_render_clip_shutter(self._h, num_frames, fp, tp, shutter_samples, span, rx, ry, rw, rh, first_row,
+                                                            last_row, C.c_void_p(dev), rw * 4, rw * 4 * rh, 4, 0, None))
+            else:
+                self._check(lib().mmhip_render_clip(self._h, num_frames, fp, tp, rx, ry, rw, rh, first_row, last_row,
+                                                    C.c_void_p(dev), rw * 4, rw * 4 * rh, 4, 0, None))
             self.sync()
             self._check(lib().mmhip_copy_to_host(out.ctypes.data_as(C.c_void_p), C.c_void_p(dev), out.nbytes))
         finally:
@@ -494,6 +546,10 @@ class Invocation:
         finally:
             lib().mmhip_device_free(C.c_void_p(dev))
         return out
+
+    def clip_shutter_batches(self):
+        """Batches of motion-blurred frames render_clip(shutter_samples > 1) has combined so far."""
+        return lib().mmhip_clip_shutter_batches(self._h)
 
     def clip_supersampled_batches(self):
         """Batches render_clip(supersample=True) ran batched (0 for filters it renders frame by frame)."""

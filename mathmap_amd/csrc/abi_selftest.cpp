@@ -610,4 +610,64 @@ long mmhip_selftest_combine_ms(int w, int h, int bpp, int frames, int rounds, do
     return result;
 }
 
+// The shutter combine alone (tests/test_gpu_clip_shutter.py, tools/clip_shutter_cost.py): launch_shutter_combine_clip on
+// `frames` frames of `samples` sub-sample maps each, `maps` = float[frames][samples][rows][render_w][4] on the host (null:
+// maps of 0.25, for timing at sizes no host array should have).  samples_per_pass below 1 or from `samples` up: one
+// pass; else passes of that many sub-samples joined by a carry map, as mmhip_render_clip_shutter cuts them.  The output
+// buffer of out_bytes bytes is filled with `sentinel` bytes first, frame i is written at out_offset + i * frame_stride,
+// and the whole buffer is copied to `out` (null: not copied).  With rounds > 0 the passes run `rounds` more times with
+// device events around each round: ms[r] receives round r's milliseconds.  Returns 0, or -1 (mmhip_selftest_error).
+int mmhip_selftest_shutter_combine(const float *maps, int frames, int samples, int rows, int region_w, int render_w, int bpp,
+                                   int floatmap, int row_stride, int64_t frame_stride, int samples_per_pass, int out_offset,
+                                   unsigned char *out, int64_t out_bytes, int sentinel, int rounds, double *ms) {
+    const int64_t band = floatmap ? (int64_t)rows * 16 * render_w : (int64_t)(rows - 1) * row_stride + (int64_t)region_w * bpp;
+    if (frames < 1 || frames > 65535 || samples < 1 || samples > MMHIP_SHUTTER_MAX_SAMPLES || rows < 1 || region_w < 1 || render_w < region_w ||
+        bpp < 1 || bpp > 4 || out_offset < 0 || row_stride < 0 || frame_stride < band ||
+        out_bytes < out_offset + (int64_t)(frames - 1) * frame_stride + band || (rounds > 0 && !ms)) {
+        g_selftest_err = "shutter combine: bad arguments";
+        return -1;
+    }
+    if (samples_per_pass < 1 || samples_per_pass > samples) samples_per_pass = samples;
+    const size_t map_bytes = (size_t)rows * render_w * 16, all = map_bytes * samples * frames;
+    DeviceBuffer subs, carry, dst;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto ok = [](hipError_t e) { if (e != hipSuccess) g_selftest_err = std::string("shutter combine: ") + hipGetErrorString(e); return e == hipSuccess; };
+    int result = -1;
+    mm::NativeWorkspace ws;
+    const float inv_k = (float)(1.0 / (double)samples);
+    // every pass of every frame, in the order the runtime launches them
+    auto run = [&]() {
+        std::string err;
+        for (int j0 = 0; j0 < samples; j0 += samples_per_pass) {
+            const int count = std::min(samples_per_pass, samples - j0);
+            const bool last = j0 + count >= samples;
+            if (mm::launch_shutter_combine_clip(subs.get<unsigned char>() + (size_t)j0 * map_bytes, (int64_t)map_bytes, (int64_t)(map_bytes * samples), count,
+                                                j0 > 0 ? carry.get() : nullptr, last ? nullptr : carry.get(), dst.get<unsigned char>() + out_offset,
+                                                region_w, rows, render_w, row_stride, frame_stride, bpp, floatmap, inv_k, frames, ws, nullptr, &err) != 0) {
+                g_selftest_err = err;
+                return false;
+            }
+        }
+        return true;
+    };
+    do {
+        if (!ok(subs.grow(all)) || !ok(dst.grow((size_t)out_bytes)) || (samples_per_pass < samples && !ok(carry.grow(map_bytes * frames)))) break;
+        if (maps ? !ok(hipMemcpy(subs.get(), maps, all, hipMemcpyHostToDevice)) : !ok(hipMemsetD32((hipDeviceptr_t)subs.get(), 0x3e800000, all / 4))) break;
+        if (!ok(hipMemset(dst.get(), sentinel, (size_t)out_bytes))) break;
+        if (!run() || !ok(hipDeviceSynchronize())) break;
+        if (out && !ok(hipMemcpy(out, dst.get(), (size_t)out_bytes, hipMemcpyDeviceToHost))) break;
+        bool timed = true;
+        if (rounds > 0) timed = ok(hipEventCreate(&e0)) && ok(hipEventCreate(&e1));
+        for (int r = 0; r < rounds && timed; ++r) {
+            float t = 0;
+            timed = ok(hipEventRecord(e0, nullptr)) && run() && ok(hipEventRecord(e1, nullptr)) && ok(hipEventSynchronize(e1)) && ok(hipEventElapsedTime(&t, e0, e1));
+            ms[r] = t;
+        }
+        if (timed) result = 0;
+    } while (false);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return result;
+}
+
 }  // extern "C"

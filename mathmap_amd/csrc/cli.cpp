@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -62,6 +63,13 @@ void usage() {
            "      --batch-frames=NUM      with -F, render NUM frames per batched GPU\n"
            "                              launch (default 1: frame by frame); the files\n"
            "                              are the same\n"
+           "      --shutter-samples=K     with -F, motion blur: every frame is the mean of\n"
+           "                              K (1 to 256) renders spread over the shutter\n"
+           "                              time, averaged on the GPU before the bytes are\n"
+           "                              made; not combined with -o\n"
+           "      --shutter=FRACTION      the shutter time as a fraction of the frame\n"
+           "                              interval (default 0.5): sub-sample j is rendered\n"
+           "                              at t = frame/NUM + FRACTION/NUM * j/K\n"
            "\n"
            "Report bugs and suggestions to schani@complang.tuwien.ac.at\n",
            cache_size);
@@ -209,7 +217,7 @@ std::string frame_file(const std::string &pattern, int frame) {
 enum {
     OPT_VERSION = 256, OPT_HELP, OPT_HTMLDOC, OPT_BENCH_NO_OUTPUT, OPT_BENCH_ONLY_COMPILE,
     OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE, OPT_INPUT_FRAMES, OPT_BATCH_FRAMES,
-    OPT_NATIVE_INPUT_FRAME
+    OPT_NATIVE_INPUT_FRAME, OPT_SHUTTER_SAMPLES, OPT_SHUTTER
 };
 
 int main(int argc, char **argv) {
@@ -217,7 +225,8 @@ int main(int argc, char **argv) {
     bool have_script = false, htmldoc = false, bench_no_output = false, bench_no_backend = false;
     int antialiasing = 0, supersampling = 0, img_width = 0, img_height = 0, size_is_set = 0;
     int bench_render_count = 1, num_frames = 1, input_frames = 0, gauss_mode = MMHIP_GAUSS_EXACT, batch_frames = 1;
-    int native_input_frame = MMHIP_NATIVE_FRAME_ZERO;
+    int native_input_frame = MMHIP_NATIVE_FRAME_ZERO, shutter_samples = 1;
+    double shutter = 0.5;
     const char *generator = nullptr;
     std::vector<Define> defines;
     static struct option long_options[] = {
@@ -233,6 +242,7 @@ int main(int argc, char **argv) {
         {"frames", required_argument, 0, 'F'}, {"gauss-mode", required_argument, 0, OPT_GAUSS_MODE},
         {"input-frames", required_argument, 0, OPT_INPUT_FRAMES}, {"batch-frames", required_argument, 0, OPT_BATCH_FRAMES},
         {"native-input-frame", required_argument, 0, OPT_NATIVE_INPUT_FRAME},
+        {"shutter-samples", required_argument, 0, OPT_SHUTTER_SAMPLES}, {"shutter", required_argument, 0, OPT_SHUTTER},
         {0, 0, 0, 0}};
     for (;;) {
         int idx;
@@ -301,8 +311,25 @@ int main(int argc, char **argv) {
                 batch_frames = (int)n;
                 break;
             }
+            case OPT_SHUTTER_SAMPLES: {
+                char *end = nullptr;
+                long n = strtol(optarg, &end, 10);
+                if (end == optarg || *end || n < 1 || n > MMHIP_SHUTTER_MAX_SAMPLES) { fprintf(stderr, "Error: --shutter-samples takes a number of samples, 1 to %d.\n", (int)MMHIP_SHUTTER_MAX_SAMPLES); return 1; }
+                shutter_samples = (int)n;
+                break;
+            }
+            case OPT_SHUTTER: {
+                char *end = nullptr;
+                shutter = strtod(optarg, &end);
+                if (end == optarg || *end || !std::isfinite(shutter)) { fprintf(stderr, "Error: --shutter takes a fraction of the frame interval, like 0.5.\n"); return 1; }
+                break;
+            }
             default: usage(); return 1;
         }
+    }
+    if (supersampling && shutter_samples > 1) {
+        fprintf(stderr, "Error: --shutter-samples is not combined with -o (oversampling).\n");
+        return 1;
     }
     const char *output_filename;
     if (have_script) {
@@ -423,11 +450,15 @@ int main(int argc, char **argv) {
     };
     // --batch-frames=K: K frames per clip render (one batched launch where the filter allows it), then the files one by
     // one; a batch's frames stay under 1 GiB of device memory.  With -o the clip is a supersampled one.
+    // --shutter-samples=K: the frames go through mmhip_render_clip_shutter, --batch-frames of them per call (by default
+    // one, all of its K sub-samples in one nested clip), at the span (float)((double)FRACTION / NUM).
+    const bool shuttered = shutter_samples > 1;
+    const float shutter_span = (float)(shutter / (double)num_frames);
     batch_frames = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch_frames, num_frames), ((size_t)1 << 30) / output.size()));
     void *dev = mmhip_device_alloc(output.size() * batch_frames);
     if (!dev) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
     for (int render_num = 0; render_num < bench_render_count; ++render_num) {
-        for (int first = 0; batch_frames > 1 && first < num_frames; first += batch_frames) {
+        for (int first = 0; (batch_frames > 1 || shuttered) && first < num_frames; first += batch_frames) {
             const int n = std::min(batch_frames, num_frames - first);
             std::vector<int> frames(n);
             std::vector<float> ts(n);
@@ -435,7 +466,10 @@ int main(int argc, char **argv) {
                 frames[i] = first + i;
                 ts[i] = (float)(first + i) / (float)num_frames;       // mathmap_cmdline.c:835
             }
-            const int rc = supersampling
+            const int rc = shuttered
+                               ? mmhip_render_clip_shutter(inv, n, frames.data(), ts.data(), shutter_samples, shutter_span, 0, 0, img_width,
+                                                           img_height, 0, img_height, dev, img_width * 4, (int64_t)output.size(), 4, 0, nullptr)
+                           : supersampling
                                ? mmhip_render_clip_supersampled(inv, n, frames.data(), ts.data(), 0, 0, img_width, img_height, dev,
                                                                 img_width * 4, (int64_t)output.size(), 4, nullptr)
                                : mmhip_render_clip(inv, n, frames.data(), ts.data(), 0, 0, img_width, img_height, 0, img_height, dev,
@@ -449,7 +483,7 @@ int main(int argc, char **argv) {
                 if (!write_frame(first + i)) return 1;
             }
         }
-        for (int frame = 0; batch_frames == 1 && frame < num_frames; ++frame) {
+        for (int frame = 0; batch_frames == 1 && !shuttered && frame < num_frames; ++frame) {
             float t = (float)frame / (float)num_frames;       // mathmap_cmdline.c:835
             int rc = supersampling
                          ? mmhip_render_supersampled(inv, frame, t, 0, 0, img_width, img_height, dev, img_width * 4, 4, nullptr)

@@ -135,5 +135,18 @@ int64_t supersample_clip_items(int w, int h);
 int launch_supersample_combine_clip(const unsigned char *longs, const unsigned char *shorts, unsigned char *out, int w, int h,
                                     int bpp, int row_stride, int64_t frame_stride, int frames, NativeWorkspace &ws, hipStream_t s,
                                     std::string *err);
+// One pass of the temporal combine of a motion-blurred clip (k_shutter_combine_clip; mmhip_render_clip_shutter states the
+// arithmetic, mm_shutter_combine.h holds it) over `frames` frames in one launch.  Sub-sample j of the pass (0 <= j <
+// count) of frame i is a float map of `rows` rows of render_w float4 at samples + i * frame_samples_stride + j *
+// sample_stride, the region's region_w columns at the start of each row.  The sum starts from the first sub-sample
+// where carry_in is null, else from frame i's carry map (rows * render_w float4, the frames packed).  With carry_out
+// the pass writes the running sum there and nothing else (carry_out may be carry_in); without, it scales by inv_k and
+// stores frame i at out + i * frame_stride: float4 rows 16 * render_w bytes apart with `floatmap`, else the pixel
+// store's bytes at output_bpp `bpp`, rows row_stride apart (32-bit stores where bpp is 4 and out, row_stride and
+// frame_stride are multiples of 4).  Refused: maps beyond 2^32 bytes (offsets inside a frame are 32-bit), more than
+// 65 535 frames, float maps that are not 16-byte aligned.  Timed through ws.timed_launch as shutter_combine_clip.
+int launch_shutter_combine_clip(const void *samples, int64_t sample_stride, int64_t frame_samples_stride, int count, const void *carry_in,
+                                void *carry_out, void *out, int region_w, int rows, int render_w, int row_stride, int64_t frame_stride,
+                                int bpp, int floatmap, float inv_k, int frames, NativeWorkspace &ws, hipStream_t s, std::string *err);
 
 }  // namespace mm

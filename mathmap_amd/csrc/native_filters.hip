@@ -11,6 +11,7 @@
 // Data layout: float maps are float[h][w][4] interleaved in HBM (floatmap.c:30-46), a
 // 16384^2 map is 4.29 GB; all intermediates stay on the device.
 #include "native_filters.h"
+#include "mm_shutter_combine.h"
 #include "mm_ss_combine.h"
 
 #include <algorithm>
@@ -1449,6 +1450,128 @@ int launch_supersample_combine_clip(const unsigned char *longs, const unsigned c
         else k_supersample_combine_clip_bytes<1><<<grid, 256, 0, s>>>(a);
     });
     if (hipGetLastError() != hipSuccess) { *err = "supersample combine: kernel launch failed"; return -1; }
+    return 0;
+}
+
+// ---- the temporal combine over the frames of a motion-blurred clip (mmhip_render_clip_shutter) ----
+// Frame blockIdx.y of a batch per grid row, one pixel of the region per lane: blockIdx.x counts the region's pixels row
+// by row, so a wave reads 1 KiB of adjacent float4 from every sub-sample map (but where it crosses a row end of a region
+// narrower than the render width).  The one division is 32-bit and per work-item; a frame's maps are addressed by a
+// 32-bit byte offset from wave-uniform bases that advance by sample_stride, and the sample loop is unrolled by four
+// with the four loads ahead of the four sums.  Everything is read once and written once: non-temporal, but for the
+// store of the carry map, which the next pass reads back.
+struct ShutterArgs {
+    const unsigned char *samples;
+    unsigned char *carry_in, *carry_out, *out;            // (a pass may read and write one carry map: a lane owns its pixel)
+    long long sample_stride, frame_samples_stride, carry_frame_stride, frame_stride;
+    int row_stride, count;
+    unsigned region_w, render_w, items;                   // items: region_w * rows, the work-items of a frame
+    float inv_k;
+};
+
+typedef float sh_f32x4 __attribute__((ext_vector_type(4)));
+typedef sh_f32x4 sh_f32x4_a4 __attribute__((aligned(4)));      // a float-map output: dword-aligned only
+
+enum { SHUTTER_FLOATMAP = 0, SHUTTER_BYTES1 = 1, SHUTTER_BYTES2 = 2, SHUTTER_BYTES3 = 3, SHUTTER_BYTES4 = 4, SHUTTER_WORDS = 5, SHUTTER_CARRY = 6 };
+
+__device__ __forceinline__ sh_f32x4 shutter_add(sh_f32x4 acc, sh_f32x4 f) {
+    sh_f32x4 r;
+    r.x = mm_shutter_add(acc.x, f.x);
+    r.y = mm_shutter_add(acc.y, f.y);
+    r.z = mm_shutter_add(acc.z, f.z);
+    r.w = mm_shutter_add(acc.w, f.w);
+    return r;
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) k_shutter_combine_clip(const ShutterArgs a) {
+    const unsigned item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= a.items) return;
+    const unsigned row = item / a.region_w, col = item - row * a.region_w;
+    const unsigned off = (row * a.render_w + col) * 16u;      // below 2^32: the launcher refuses larger maps
+    const size_t fi = blockIdx.y;
+    const unsigned char *__restrict__ S = a.samples + fi * a.frame_samples_stride;
+    sh_f32x4 acc;
+    int j = 0;
+    if (a.carry_in) acc = __builtin_nontemporal_load((const sh_f32x4 *)(a.carry_in + fi * a.carry_frame_stride + off));
+    else {
+        acc = __builtin_nontemporal_load((const sh_f32x4 *)(S + off));
+        S += a.sample_stride;
+        j = 1;
+    }
+    for (; j + 4 <= a.count; j += 4) {
+        const sh_f32x4 f0 = __builtin_nontemporal_load((const sh_f32x4 *)(S + off));
+        const sh_f32x4 f1 = __builtin_nontemporal_load((const sh_f32x4 *)(S + a.sample_stride + off));
+        const sh_f32x4 f2 = __builtin_nontemporal_load((const sh_f32x4 *)(S + 2 * a.sample_stride + off));
+        const sh_f32x4 f3 = __builtin_nontemporal_load((const sh_f32x4 *)(S + 3 * a.sample_stride + off));
+        acc = shutter_add(shutter_add(shutter_add(shutter_add(acc, f0), f1), f2), f3);
+        S += 4 * a.sample_stride;
+    }
+    for (; j < a.count; ++j) {
+        acc = shutter_add(acc, __builtin_nontemporal_load((const sh_f32x4 *)(S + off)));
+        S += a.sample_stride;
+    }
+    if (MODE == SHUTTER_CARRY) {
+        *(sh_f32x4 *)(a.carry_out + fi * a.carry_frame_stride + off) = acc;
+        return;
+    }
+    sh_f32x4 m;
+    m.x = mm_shutter_scale(acc.x, a.inv_k);
+    m.y = mm_shutter_scale(acc.y, a.inv_k);
+    m.z = mm_shutter_scale(acc.z, a.inv_k);
+    m.w = mm_shutter_scale(acc.w, a.inv_k);
+    unsigned char *__restrict__ O = a.out + fi * a.frame_stride;
+    if (MODE == SHUTTER_FLOATMAP) {
+        __builtin_nontemporal_store(m, (sh_f32x4_a4 *)(O + off));
+        return;
+    }
+    const int bpp = MODE == SHUTTER_WORDS ? 4 : MODE;
+    unsigned char *p = O + (long long)row * a.row_stride + col * (unsigned)bpp;
+    if (MODE == SHUTTER_WORDS) __builtin_nontemporal_store(pack_rgba8(make_float4(m.x, m.y, m.z, m.w)), (unsigned *)p);
+    else mm_shutter_store_bytes(p, m.x, m.y, m.z, m.w, bpp);
+}
+
+int launch_shutter_combine_clip(const void *samples, int64_t sample_stride, int64_t frame_samples_stride, int count, const void *carry_in,
+                                void *carry_out, void *out, int region_w, int rows, int render_w, int row_stride, int64_t frame_stride,
+                                int bpp, int floatmap, float inv_k, int frames, NativeWorkspace &ws, hipStream_t s, std::string *err) {
+    const int64_t map_bytes = (int64_t)rows * render_w * 16;
+    if (region_w < 1 || rows < 1 || render_w < region_w || count < 1 || frames < 1 || frames > 65535 || bpp < 1 || bpp > 4 ||
+        map_bytes > ((int64_t)1 << 32)) {
+        *err = "shutter combine: the batch does not fit one launch";
+        return -1;
+    }
+    if (((uintptr_t)samples | (uintptr_t)sample_stride | (uintptr_t)frame_samples_stride | (uintptr_t)carry_in | (uintptr_t)carry_out) % 16 != 0 ||
+        (!carry_out && floatmap && ((uintptr_t)out | (uintptr_t)frame_stride) % 4 != 0)) {
+        *err = "shutter combine: the float maps are not aligned";
+        return -1;
+    }
+    ShutterArgs a;
+    a.samples = (const unsigned char *)samples;
+    a.carry_in = (unsigned char *)carry_in;
+    a.carry_out = (unsigned char *)carry_out;
+    a.out = (unsigned char *)out;
+    a.sample_stride = sample_stride;
+    a.frame_samples_stride = frame_samples_stride;
+    a.carry_frame_stride = map_bytes;
+    a.frame_stride = frame_stride;
+    a.row_stride = row_stride;
+    a.count = count;
+    a.region_w = (unsigned)region_w;
+    a.render_w = (unsigned)render_w;
+    a.items = (unsigned)region_w * (unsigned)rows;
+    a.inv_k = inv_k;
+    const dim3 grid((a.items + 255u) / 256u, (unsigned)frames);
+    const uintptr_t align = (uintptr_t)out | (uintptr_t)row_stride | (uintptr_t)frame_stride;
+    ws.timed_launch("shutter_combine_clip", s, [&] {
+        if (carry_out) k_shutter_combine_clip<SHUTTER_CARRY><<<grid, 256, 0, s>>>(a);
+        else if (floatmap) k_shutter_combine_clip<SHUTTER_FLOATMAP><<<grid, 256, 0, s>>>(a);
+        else if (bpp == 4 && align % 4 == 0) k_shutter_combine_clip<SHUTTER_WORDS><<<grid, 256, 0, s>>>(a);
+        else if (bpp == 4) k_shutter_combine_clip<SHUTTER_BYTES4><<<grid, 256, 0, s>>>(a);
+        else if (bpp == 3) k_shutter_combine_clip<SHUTTER_BYTES3><<<grid, 256, 0, s>>>(a);
+        else if (bpp == 2) k_shutter_combine_clip<SHUTTER_BYTES2><<<grid, 256, 0, s>>>(a);
+        else k_shutter_combine_clip<SHUTTER_BYTES1><<<grid, 256, 0, s>>>(a);
+    });
+    if (hipGetLastError() != hipSuccess) { *err = "shutter combine: kernel launch failed"; return -1; }
     return 0;
 }
 

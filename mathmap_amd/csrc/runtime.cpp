@@ -27,6 +27,7 @@
 #include "front.h"
 #include "hipgen.h"
 #include "mm_host_abi.h"
+#include "mm_shutter_combine.h"
 #include "native_filters.h"
 #include "passes.h"
 #include "runtime_internal.h"
@@ -1940,6 +1941,111 @@ int mmhip_render_clip_supersampled(mmhip_invocation *inv, int num_frames, const 
                                             bpp, row_stride, frame_stride, n, inv->ws, s, &err) != 0)
             return fail(err);
         ++inv->clip_supersampled_batches;
+    }
+    return 0;
+}
+
+// ---- motion-blurred clips ----
+// How mmhip_render_clip_shutter cuts a clip into batches and a frame's sub-samples into passes (include/mmhip.h has the
+// rules).  MMHIP_CLIP_SHUTTER_BYTES is read once, default 8 GiB.
+struct ClipShutterPlan { int per_batch = 1, batches = 1, samples_per_pass = 1, passes = 1, carry = 0; size_t bytes_per_sample = 0; };
+static ClipShutterPlan clip_shutter_plan(int num_rows, int render_w, int samples, int frames) {
+    static const size_t budget = [] {
+        const char *e = getenv("MMHIP_CLIP_SHUTTER_BYTES");
+        const long long v = e ? atoll(e) : 0;
+        return v > 0 ? (size_t)v : (size_t)8 << 30;
+    }();
+    ClipShutterPlan p;
+    p.bytes_per_sample = (size_t)num_rows * 16 * (size_t)render_w;
+    const size_t frame_bytes = (size_t)samples * p.bytes_per_sample;
+    if (budget >= frame_bytes) {
+        p.per_batch = (int)std::min<size_t>({budget / frame_bytes, (size_t)65535, (size_t)frames});
+        p.samples_per_pass = samples;
+    } else {
+        // not one frame's sub-samples: a frame at a time, in passes over what fits beside the carry map (at least one)
+        p.samples_per_pass = (int)std::max<long long>(1, (long long)(budget / p.bytes_per_sample) - 1);
+        p.passes = (samples + p.samples_per_pass - 1) / p.samples_per_pass;
+        p.carry = p.passes > 1;
+    }
+    p.batches = (frames + p.per_batch - 1) / p.per_batch;
+    return p;
+}
+
+static int clip_shutter_check_samples(const char *who, int samples) {
+    if (samples < 1 || samples > MMHIP_SHUTTER_MAX_SAMPLES)
+        return fail(std::string(who) + ": samples must be 1 to " + std::to_string((int)MMHIP_SHUTTER_MAX_SAMPLES) + ", not " + std::to_string(samples));
+    return 0;
+}
+
+int mmhip_filter_clip_shutter_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int samples, int frames, int64_t *out) {
+    (void)f;
+    if (frames < 1) return fail("clip shutter plan: num_frames must be at least 1");
+    if (clip_shutter_check_samples("clip shutter plan", samples) != 0) return -1;
+    if (region_w < 1 || num_rows < 1 || render_w < region_w) return fail("clip shutter plan: empty region, or one wider than the render width");
+    const ClipShutterPlan p = clip_shutter_plan(num_rows, render_w, samples, frames);
+    const int64_t v[MMHIP_CLIP_SHUTTER_PLAN_FIELDS] = {p.per_batch, p.batches, p.samples_per_pass, p.passes, (int64_t)p.bytes_per_sample, p.carry};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+long mmhip_clip_shutter_batches(mmhip_invocation *inv) { return inv->clip_shutter_batches; }
+
+int mmhip_render_clip_shutter(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
+                              int region_x, int region_y, int region_w, int region_h, int first_row, int last_row, void *out_device,
+                              int row_stride, int64_t frame_stride, int bpp, int floatmap, void *stream) {
+    if (clip_shutter_check_samples("render_clip_shutter", samples) != 0) return -1;
+    if (samples == 1)       // one instant per frame: the plain clip itself
+        return mmhip_render_clip(inv, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
+                                 row_stride, frame_stride, bpp, floatmap, stream);
+    if (!std::isfinite(span)) return fail("render_clip_shutter: span must be finite");
+    if (num_frames < 1) return fail("render_clip_shutter: num_frames must be at least 1");
+    if (!frames || !ts) return fail("render_clip_shutter: frames and ts must be arrays of num_frames entries");
+    if (bpp < 1 || bpp > 4) return fail("output_bpp must be 1..4");
+    if (region_w <= 0 || region_h <= 0) return fail("empty region");
+    if (first_row < 0) first_row = 0;
+    if (last_row > region_y + region_h) last_row = region_y + region_h;
+    if (last_row <= first_row) return 0;
+    const int num_rows = last_row - first_row;
+    const int64_t band = floatmap ? (int64_t)num_rows * 16 * inv->render_w
+                                  : (int64_t)(num_rows - 1) * row_stride + (int64_t)region_w * bpp;
+    if (frame_stride < band)
+        return fail("render_clip_shutter: frame_stride " + std::to_string(frame_stride) + " is smaller than one frame's band (" +
+                    std::to_string(band) + " bytes)");
+    if (region_w > inv->render_w) return fail("render_clip_shutter: the region is wider than the render width");
+    const ClipShutterPlan plan = clip_shutter_plan(num_rows, inv->render_w, samples, num_frames);
+    const size_t bps = plan.bytes_per_sample;
+    if (bps > ((size_t)1 << 32)) return fail("render_clip_shutter: a sub-sample map of more than 4 GiB; render the frame in row bands");
+    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
+    // own allocation, like clip_ss; whatever still reads a smaller one has finished before it is freed
+    const size_t slots = (size_t)plan.per_batch * plan.samples_per_pass;
+    if (inv->clip_shutter.grow((slots + plan.carry) * bps, hipDeviceSynchronize) != hipSuccess)
+        return fail("out of device memory for the sub-samples of a motion-blurred clip; lower MMHIP_CLIP_SHUTTER_BYTES");
+    unsigned char *subs = inv->clip_shutter.get<unsigned char>(), *carry = plan.carry ? subs + slots * bps : nullptr;
+    const float inv_k = mm_shutter_inv_k(samples);
+    std::vector<int> sub_frames;
+    std::vector<float> sub_ts;
+    for (int b0 = 0; b0 < num_frames; b0 += plan.per_batch) {
+        const int n = std::min(plan.per_batch, num_frames - b0);
+        for (int j0 = 0; j0 < samples; j0 += plan.samples_per_pass) {
+            const int count = std::min(plan.samples_per_pass, samples - j0);
+            sub_frames.resize((size_t)n * count);
+            sub_ts.resize((size_t)n * count);
+            for (int i = 0; i < n; ++i)
+                for (int j = 0; j < count; ++j) {
+                    sub_frames[(size_t)i * count + j] = frames[b0 + i];
+                    sub_ts[(size_t)i * count + j] = mm_shutter_sample_t(ts[b0 + i], span, j0 + j, samples);
+                }
+            if (mmhip_render_clip(inv, n * count, sub_frames.data(), sub_ts.data(), region_x, region_y, region_w, region_h, first_row,
+                                  last_row, subs, row_stride, (int64_t)bps, bpp, 1, s) != 0)
+                return -1;
+            const bool last = j0 + count >= samples;
+            std::string err;
+            if (launch_shutter_combine_clip(subs, (int64_t)bps, (int64_t)count * (int64_t)bps, count, j0 > 0 ? carry : nullptr, last ? nullptr : carry,
+                                            (char *)out_device + (int64_t)b0 * frame_stride, region_w, num_rows, inv->render_w, row_stride,
+                                            frame_stride, bpp, floatmap, inv_k, n, inv->ws, s, &err) != 0)
+                return fail(err);
+        }
+        ++inv->clip_shutter_batches;
     }
     return 0;
 }

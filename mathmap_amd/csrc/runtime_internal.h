@@ -218,6 +218,9 @@ struct mmhip_invocation {
     DeviceBuffer clip_ss;                  // the slices of a batch of supersampled frames (mmhip_render_clip_supersampled):
                                            // every frame's long slice, then every frame's short slice
     long clip_supersampled_batches = 0;    // mmhip_clip_supersampled_batches
+    DeviceBuffer clip_shutter;             // the sub-sample float maps of a batch of motion-blurred frames
+                                           // (mmhip_render_clip_shutter), and behind them the carry map where one is needed
+    long clip_shutter_batches = 0;         // mmhip_clip_shutter_batches
     uint32_t edge_color_x = 0, edge_color_y = 0;
     float sampling_offset_x = 0.f, sampling_offset_y = 0.f;
     bool timing = false;
