@@ -5,6 +5,7 @@
 // behaviour.  Rendering a row band = one prologue launch (frame constants, the
 // reference's init_frame, new_template.c.in:314-337) + native-filter kernels if
 // the filter calls any + one pixel-kernel launch (calc_lines, :208-312).
+// Clips of frames are rendered by runtime_clip.cpp.  (The exported functions have C linkage from include/mmhip.h.)
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 #include <sys/stat.h>
@@ -27,7 +28,6 @@
 #include "front.h"
 #include "hipgen.h"
 #include "mm_host_abi.h"
-#include "mm_shutter_combine.h"
 #include "native_filters.h"
 #include "passes.h"
 #include "runtime_internal.h"
@@ -38,17 +38,6 @@ thread_local std::string g_mmhip_err;
 #define g_err g_mmhip_err
 
 namespace {
-
-int fail(const std::string &msg) {
-    g_err = msg;
-    return -1;
-}
-
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 std::string cache_dir() {
     const char *env = getenv("MMHIP_CACHE_DIR");
@@ -66,8 +55,6 @@ bool mmhip_check_options(const mmhip_options *opts) {
     }
     return true;
 }
-
-extern "C" {
 
 const char *mmhip_last_error(void) { return g_err.c_str(); }
 const char *mmhip_version(void) { return "mathmap_amd 0.1 (gfx950)"; }
@@ -143,6 +130,16 @@ mmhip_filter *mmhip_compile(const char *source, const mmhip_options *opts) { ret
 // Compiles with the given scalar user values (index, value) baked in as literals -- the same
 // variant active_filter() builds lazily; exposed so the specialised kernel can be inspected
 // and tested without a GPU.  Values of int/bool user values are truncated to int.
+static bool scalar_constants(const std::vector<UservalInfo> &uvs, int n, const int *indices, const double *values, std::map<int, Primary> *consts) {
+    for (int i = 0; i < n; ++i) {
+        if (indices[i] < 0 || indices[i] >= (int)uvs.size()) { g_err = "user value index out of range"; return false; }
+        const UservalInfo &u = uvs[indices[i]];
+        if (u.kind == UvKind::Float) (*consts)[u.index] = Primary::F((float)values[i]);
+        else if (u.kind == UvKind::Int || u.kind == UvKind::Bool) (*consts)[u.index] = Primary::I((int)values[i]);
+    }
+    return true;
+}
+
 mmhip_filter *mmhip_compile_specialized(const char *source, const mmhip_options *opts, int n, const int *indices,
                                         const double *values) {
     Module probe;
@@ -153,16 +150,9 @@ mmhip_filter *mmhip_compile_specialized(const char *source, const mmhip_options 
         return nullptr;
     }
     std::map<int, Primary> consts;
-    for (int i = 0; i < n; ++i) {
-        if (indices[i] < 0 || indices[i] >= (int)probe.main->uservals.size()) { g_err = "user value index out of range"; return nullptr; }
-        const UservalInfo &u = probe.main->uservals[indices[i]];
-        if (u.kind == UvKind::Float) consts[u.index] = Primary::F((float)values[i]);
-        else if (u.kind == UvKind::Int || u.kind == UvKind::Bool) consts[u.index] = Primary::I((int)values[i]);
-    }
+    if (!scalar_constants(probe.main->uservals, n, indices, values, &consts)) return nullptr;
     return compile_source(source, opts, &consts);
 }
-
-}  // extern "C"
 
 mmhip_filter *mmhip_filter_new_empty() { return new mmhip_filter(); }
 
@@ -190,8 +180,6 @@ bool mmhip_filter_finalize(mmhip_filter *f, const KernelOptions &ko, std::string
     }
     return true;
 }
-
-extern "C" {
 
 void mmhip_filter_free(mmhip_filter *f) {
     if (!f) return;
@@ -298,14 +286,17 @@ static int jit_source(const KernelSource &ks, std::vector<char> &code_object) {
     return 0;
 }
 
+// (f_rows: where the kernels have a per-row slice and the caller launches it)
 static int load_kernels(const KernelSource &ks, const std::vector<char> &code_object, hipModule_t *mod, hipFunction_t *f_pix,
-                        hipFunction_t *f_pro) {
+                        hipFunction_t *f_pro, hipFunction_t *f_rows = nullptr) {
     hipError_t e = hipModuleLoadData(mod, code_object.data());
     if (e != hipSuccess) return fail(std::string("hipModuleLoadData: ") + hipGetErrorString(e));
     e = hipModuleGetFunction(f_pix, *mod, ks.pixel_name.c_str());
     if (e != hipSuccess) return fail(std::string("hipModuleGetFunction(pixels): ") + hipGetErrorString(e));
     e = hipModuleGetFunction(f_pro, *mod, ks.prologue_name.c_str());
     if (e != hipSuccess) return fail(std::string("hipModuleGetFunction(prologue): ") + hipGetErrorString(e));
+    if (f_rows) e = hipModuleGetFunction(f_rows, *mod, ks.rows_name.c_str());
+    if (e != hipSuccess) return fail(std::string("hipModuleGetFunction(rows): ") + hipGetErrorString(e));
     return 0;
 }
 
@@ -315,11 +306,7 @@ long mmhip_filter_jit(mmhip_filter *f, int load_module) {
     for (mmhip_closure_kernel &ck : f->closures)
         if (jit_source(ck.ks, ck.code_object) != 0) return -1;
     if (load_module && !f->loaded) {
-        if (load_kernels(f->ks, f->code_object, &f->mod, &f->f_pix, &f->f_pro) != 0) return -1;
-        if (f->ks.row_values > 0) {
-            hipError_t e = hipModuleGetFunction(&f->f_rows, f->mod, f->ks.rows_name.c_str());
-            if (e != hipSuccess) return fail(std::string("hipModuleGetFunction(rows): ") + hipGetErrorString(e));
-        }
+        if (load_kernels(f->ks, f->code_object, &f->mod, &f->f_pix, &f->f_pro, f->ks.row_values > 0 ? &f->f_rows : nullptr) != 0) return -1;
         for (mmhip_closure_kernel &ck : f->closures)
             if (!ck.loaded) {
                 if (load_kernels(ck.ks, ck.code_object, &ck.mod, &ck.f_pix, &ck.f_pro) != 0) return -1;
@@ -350,11 +337,8 @@ long mmhip_filter_jit_clip(mmhip_filter *f, int load_module) {
     const mm::KernelSource &ks = clip_source(f);
     if (jit_source(ks, f->clip_code_object) != 0) return -1;
     if (load_module && !f->clip_loaded) {
-        if (load_kernels(ks, f->clip_code_object, &f->clip_mod, &f->f_pix_clip, &f->f_pro_clip) != 0) return -1;
-        if (f->ks.row_values > 0) {
-            hipError_t e = hipModuleGetFunction(&f->f_rows_clip, f->clip_mod, ks.rows_name.c_str());
-            if (e != hipSuccess) return fail(std::string("hipModuleGetFunction(rows): ") + hipGetErrorString(e));
-        }
+        if (load_kernels(ks, f->clip_code_object, &f->clip_mod, &f->f_pix_clip, &f->f_pro_clip, f->ks.row_values > 0 ? &f->f_rows_clip : nullptr) != 0)
+            return -1;
         f->clip_loaded = true;
     }
     f->jit_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -514,7 +498,7 @@ static void fill_drawable_desc(HImageDesc &d, const void *data, int w, int h, in
 }
 
 // A native float map (the result of a native filter, or a closure image rendered for one) as the kernels read it.
-static HImageDesc floatmap_desc(const void *data, int w, int h) {
+HImageDesc floatmap_desc(const void *data, int w, int h) {
     HImageDesc d{};
     d.data = data;
     d.w = w;
@@ -561,8 +545,6 @@ int mmhip_set_image_device(mmhip_invocation *inv, int index, const void *device_
     return mmhip_set_image_sequence_device(inv, index, device_rgba32, width, height, 1);
 }
 
-}  // extern "C"
-
 void mmhip_unbind_image(mmhip_invocation *inv, const void *data) {
     for (HImageDesc &img : inv->images)
         if (img.data == data) {
@@ -571,8 +553,6 @@ void mmhip_unbind_image(mmhip_invocation *inv, const void *data) {
             input_changed(inv);
         }
 }
-
-extern "C" {
 
 int mmhip_set_image_sequence_host(mmhip_invocation *inv, int index, const uint8_t *pixels, int width, int height, int channels,
                                   int num_frames) {
@@ -708,6 +688,21 @@ static int next_event_pair(mmhip_invocation *inv) {
     return 0;
 }
 
+// The pixel launch of a render between the event pair of a timed invocation.  f_pix null: a native filter has written
+// the pixels (run_natives) and nothing is launched; the pair is recorded all the same.
+int timed_pixel_launch(mmhip_invocation *inv, hipFunction_t f_pix, unsigned grid_x, unsigned grid_y, void **params, hipStream_t s) {
+    if (inv->timing) {
+        if (next_event_pair(inv) != 0) return -1;
+        HIP_TRY(hipEventRecord(inv->ev0, s));
+    }
+    if (f_pix) HIP_TRY(hipModuleLaunchKernel(f_pix, grid_x, grid_y, 1, 256, 1, 1, 0, s, params, nullptr));
+    if (inv->timing) {
+        HIP_TRY(hipEventRecord(inv->ev1, s));
+        inv->ev_valid = true;
+    }
+    return 0;
+}
+
 // Durations (ms) of the pixel kernel of every timed launch since the last drain, oldest first;
 // waits for the last of them.  Returns how many were written (at most `cap`).
 long mmhip_direct_native_launches(mmhip_invocation *inv) { return inv->direct_native_launches; }
@@ -741,7 +736,7 @@ static int upload_image_table(mmhip_invocation *inv, hipStream_t s) {
     return 0;
 }
 
-static int upload_tables(mmhip_invocation *inv, hipStream_t s) {
+int upload_tables(mmhip_invocation *inv, hipStream_t s) {
     if (!inv->tables_dirty) return 0;
     if (upload_image_table(inv, s) != 0) return -1;
     HIP_TRY(hipMemcpy(inv->d_uv.get(), inv->uv.data(), inv->uv.size() * sizeof(HUserval), hipMemcpyHostToDevice));
@@ -752,24 +747,11 @@ static int upload_tables(mmhip_invocation *inv, hipStream_t s) {
     return 0;
 }
 
-// The launch geometry of a pixel kernel over `num_rows` rows of a `region_w`-wide region: the one place both launch
-// sites (mmhip_render, render_closure) and mmhip_filter_launch_geometry take it from.
-struct LaunchGeometry {
-    int tiles_x = 0, tiles_y = 0;
-    long wg1 = 0;                 // workgroups at one row per work-item: what the rows-per-item choice is made from
-    long nwg = 0;                 // workgroups of the launch
-    int ppt = 1;                  // rows per work-item (mm_args.ppt)
-    uint32_t tiles_magic = 0;     // mm_args.tiles_magic
-};
-
 // rows per work-item for that many workgroups at one row each: enough workgroups must remain to fill 256 CUs several times over
 static int rows_per_item(long wgs) { return wgs >= 262144 ? 16 : wgs >= 131072 ? 8 : wgs >= 32768 ? 4 : wgs >= 8192 ? 2 : 1; }
 
-static LaunchGeometry launch_geometry(const KernelSource &ks, int region_w, int num_rows) {
-    LaunchGeometry g;
-    g.tiles_x = (region_w + ks.tile_w - 1) / ks.tile_w;
-    g.wg1 = (long)g.tiles_x * ((num_rows + ks.tile_h - 1) / ks.tile_h);
-    int ppt = rows_per_item(g.wg1);
+// the launch at `ppt` rows per work-item, or what MMHIP_PPT and the kernel's shape make of them
+static void set_rows_per_item(LaunchGeometry &g, const KernelSource &ks, int num_rows, int ppt) {
     if (const char *e = getenv("MMHIP_PPT")) ppt = std::max(1, atoi(e));
     if (ks.single_pixel) ppt = 1;
     const int u = std::max(1, ks.unroll);          // the kernel steps MM_UNROLL rows at a time
@@ -777,6 +759,13 @@ static LaunchGeometry launch_geometry(const KernelSource &ks, int region_w, int 
     g.tiles_y = (num_rows + ks.tile_h * g.ppt - 1) / (ks.tile_h * g.ppt);
     g.nwg = (long)g.tiles_x * g.tiles_y;
     g.tiles_magic = tile_division_magic(g.tiles_x, g.nwg);
+}
+
+static LaunchGeometry launch_geometry(const KernelSource &ks, int region_w, int num_rows) {
+    LaunchGeometry g;
+    g.tiles_x = (region_w + ks.tile_w - 1) / ks.tile_w;
+    g.wg1 = (long)g.tiles_x * ((num_rows + ks.tile_h - 1) / ks.tile_h);
+    set_rows_per_item(g, ks, num_rows, rows_per_item(g.wg1));
     return g;
 }
 
@@ -784,17 +773,10 @@ static LaunchGeometry launch_geometry(const KernelSource &ks, int region_w, int 
 // made from the workgroups of the whole batch -- a 1920x1080 frame alone is too small to share a work-item's start-up
 // cost between rows, 120 of them are not -- but a work-item's rows stay rows of its own frame: no more of them than the
 // frame has tile rows (or than the frame alone would get).  With frames = 1 this is launch_geometry.
-static LaunchGeometry clip_launch_geometry(const KernelSource &ks, int region_w, int num_rows, int frames) {
+LaunchGeometry clip_launch_geometry(const KernelSource &ks, int region_w, int num_rows, int frames) {
     LaunchGeometry g = launch_geometry(ks, region_w, num_rows);
     const int tile_rows = (num_rows + ks.tile_h - 1) / ks.tile_h;
-    int ppt = std::min(rows_per_item(g.wg1 * std::max(frames, 1)), std::max(rows_per_item(g.wg1), tile_rows));
-    if (const char *e = getenv("MMHIP_PPT")) ppt = std::max(1, atoi(e));
-    if (ks.single_pixel) ppt = 1;
-    const int u = std::max(1, ks.unroll);
-    g.ppt = (ppt + u - 1) / u * u;
-    g.tiles_y = (num_rows + ks.tile_h * g.ppt - 1) / (ks.tile_h * g.ppt);
-    g.nwg = (long)g.tiles_x * g.tiles_y;
-    g.tiles_magic = tile_division_magic(g.tiles_x, g.nwg);
+    set_rows_per_item(g, ks, num_rows, std::min(rows_per_item(g.wg1 * std::max(frames, 1)), std::max(rows_per_item(g.wg1), tile_rows)));
     return g;
 }
 
@@ -802,8 +784,7 @@ static LaunchGeometry clip_launch_geometry(const KernelSource &ks, int region_w,
 // (a workgroup's XCD is then blockIdx.x & 7 in every grid row), gridDim.y at most 65 535 frames, the grid below 2^31
 // work-items, and MMHIP_CLIP_MAX_FRAMES (read once) lowers the frames per launch.  max_frames 0: one frame alone is too
 // large for the grid, and the clip is rendered frame by frame.
-struct ClipPlan { long grid_x = 0; int max_frames = 0; };
-static ClipPlan clip_plan(const LaunchGeometry &g) {
+ClipPlan clip_plan(const LaunchGeometry &g) {
     static const int env_cap = [] {
         const char *e = getenv("MMHIP_CLIP_MAX_FRAMES");
         return e && atoi(e) > 0 ? atoi(e) : 65535;
@@ -857,7 +838,7 @@ int mmhip_filter_closure_launch_geometry(const mmhip_filter *f, int closure, int
 
 // The buffers of a launch of `ks` over `num_rows` rows of a `region_w`-wide region, grown on demand (stream order protects
 // re-use): coordinate tables, with `rows` the per-row values, and the frame constants (zero-filled when new).
-static int grow_launch_buffers(LaunchBuffers &b, const KernelSource &ks, int region_w, int num_rows, bool rows, hipStream_t s) {
+int grow_launch_buffers(LaunchBuffers &b, const KernelSource &ks, int region_w, int num_rows, bool rows, hipStream_t s) {
     auto wait = [s] { return hipStreamSynchronize(s); };
     HIP_TRY(b.xtab.grow((size_t)region_w * sizeof(float), wait));
     HIP_TRY(b.ytab.grow((size_t)num_rows * sizeof(float), wait));
@@ -872,8 +853,7 @@ static int grow_launch_buffers(LaunchBuffers &b, const KernelSource &ks, int reg
 // The native-filter calls the prologue recorded in `host' (a copy of the frame-constant buffer), in the order they
 // were made: entry k of ks.natives (a call site outside loops, or the n-th dynamic entry of the in-loop sites) and its
 // record.  The record's `pad' is the call's number within the frame (mm_native_call in hipgen.cpp).
-struct RecordedCall { size_t k; HNativeRec rec; const std::string *func; };
-static int recorded_calls(const KernelSource &ks, const char *host, std::vector<RecordedCall> *calls) {
+int recorded_calls(const KernelSource &ks, const char *host, std::vector<RecordedCall> *calls) {
     calls->clear();
     if (ks.natives.empty()) return 0;
     int ctr[4];
@@ -1011,13 +991,13 @@ static int render_closure(mmhip_invocation *inv, mmhip_filter *f, int cid, const
 // lrintf(ax x + bx) (builtins.c:247-265) evaluated here for each column and row with the
 // coordinates the prologue just computed -- the native filter may write the RGBA8 pixels itself.
 // Waits for `s', and with it for what the caller queued there before (the frame constants' read-back).
-static bool direct_output_wanted(const mmhip_filter *f, const HArgs &a) {
+bool direct_output_wanted(const mmhip_filter *f, const HArgs &a) {
     return f->ks.direct_native >= 0 && !a.floatmap && a.output_bpp == 4 && (a.row_stride & 3) == 0 && ((uintptr_t)a.out & 3) == 0 &&
            !getenv("MMHIP_NO_DIRECT_NATIVE");
 }
 
 // xt, yt: the launch's coordinate tables as the prologue wrote them
-static bool samples_own_pixels(const HArgs &a, const std::vector<float> &xt, const std::vector<float> &yt) {
+bool samples_own_pixels(const HArgs &a, const std::vector<float> &xt, const std::vector<float> &yt) {
     const HImageDesc m = floatmap_desc(nullptr, a.render_width, a.render_height);
     for (int c = 0; c < a.region_width; ++c)
         if (lrintf(m.ax * xt[c] + m.bx) != (long)a.region_x + c) return false;
@@ -1026,15 +1006,19 @@ static bool samples_own_pixels(const HArgs &a, const std::vector<float> &xt, con
     return true;
 }
 
+// queues the copies; the tables are there once `s' has been waited for
+int read_coordinate_tables(const HArgs &a, hipStream_t s, std::vector<float> *xt, std::vector<float> *yt) {
+    xt->resize(a.region_width);
+    yt->resize(a.num_rows);
+    HIP_TRY(hipMemcpyAsync(xt->data(), a.xtab, xt->size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(yt->data(), a.ytab, yt->size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
 static int direct_output(const mmhip_filter *f, const HArgs &a, hipStream_t s, NativeDirectOut *direct) {
     const bool try_direct = direct_output_wanted(f, a);
     std::vector<float> xt, yt;
-    if (try_direct) {
-        xt.resize(a.region_width);
-        yt.resize(a.num_rows);
-        HIP_TRY(hipMemcpyAsync(xt.data(), a.xtab, xt.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(yt.data(), a.ytab, yt.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
+    if (try_direct && read_coordinate_tables(a, s, &xt, &yt) != 0) return -1;
     HIP_TRY(hipStreamSynchronize(s));
     if (!try_direct) return 0;
     if (!samples_own_pixels(a, xt, yt)) return 0;
@@ -1074,8 +1058,7 @@ static int render_closure_args(mmhip_invocation *inv, mmhip_filter *f, const HAr
 // render's frame number -- the call sees a one-frame view of it, in `images_k' (a copy of the image table, made here if
 // the call has none yet).  `frame_key' becomes that frame number: part of what the memo and the direct output's `seen'
 // record compare, so that one frame's result never answers for another's.  A frame the sequence does not have is an error.
-enum { NO_FRAME_KEY = INT32_MIN };
-static int view_sequence_args(const mmhip_invocation *inv, int frame, const std::string &func, const HNativeRec &rec,
+int view_sequence_args(const mmhip_invocation *inv, int frame, const std::string &func, const HNativeRec &rec,
                               std::vector<HImageDesc> &images_k, int *frame_key) {
     *frame_key = NO_FRAME_KEY;
     if (inv->native_input_frame != MMHIP_NATIVE_FRAME_CURRENT) return 0;
@@ -1120,17 +1103,22 @@ static void drop_native_map(mmhip_invocation *inv, size_t k, bool *table_changed
     *table_changed = true;
 }
 
+// what the native filters of `f' run with (render_closure runs its native filters with these too)
+void set_native_env(mmhip_invocation *inv, const mmhip_filter *f, bool gauss_tolerance) {
+    inv->ws.env.supersampling = f->kopt.supersampling;
+    inv->ws.env.edge_x = f->kopt.edge_x;
+    inv->ws.env.edge_y = f->kopt.edge_y;
+    inv->ws.env.edge_color_x = inv->edge_color_x;
+    inv->ws.env.edge_color_y = inv->edge_color_y;
+    inv->ws.gauss_tolerance = gauss_tolerance;
+}
+
 static int run_natives(mmhip_invocation *inv, mmhip_filter *f, const HArgs &a, hipStream_t s, bool *direct_written) {
     std::vector<char> host(f->ks.xy_bytes);
     HIP_TRY(hipMemcpyAsync(host.data(), inv->launch.xy.get(), host.size(), hipMemcpyDeviceToHost, s));
     NativeDirectOut direct;
     if (direct_output(f, a, s, &direct) != 0) return -1;
-    inv->ws.env.supersampling = f->kopt.supersampling;      // (render_closure runs its native filters with these too)
-    inv->ws.env.edge_x = f->kopt.edge_x;
-    inv->ws.env.edge_y = f->kopt.edge_y;
-    inv->ws.env.edge_color_x = inv->edge_color_x;
-    inv->ws.env.edge_color_y = inv->edge_color_y;
-    inv->ws.gauss_tolerance = f->opts.gauss_mode == MMHIP_GAUSS_TOLERANCE;
+    set_native_env(inv, f, f->opts.gauss_mode == MMHIP_GAUSS_TOLERANCE);
     // rows of the maps this launch may read: everything, or -- opt-in, full-frame regions only --
     // the stripe being rendered (the filter samples the map within its own rows +- margin)
     int want_lo = 0, want_hi = a.render_height;
@@ -1265,24 +1253,22 @@ static mmhip_filter *compile_ir_specialized(const mmhip_filter *f, const std::ma
 
 // The variant of a compiled filter with n scalar user values (index, value) baked in as literals: what
 // active_filter() builds lazily for a value set, for filters of either origin (source text or IR dump).
-extern "C" mmhip_filter *mmhip_filter_specialized(const mmhip_filter *f, int n, const int *indices, const double *values) {
-    std::map<int, Primary> consts;
-    const auto &uvs = f->module.main->uservals;
-    for (int i = 0; i < n; ++i) {
-        if (indices[i] < 0 || indices[i] >= (int)uvs.size()) { g_err = "user value index out of range"; return nullptr; }
-        const UservalInfo &u = uvs[indices[i]];
-        if (u.kind == UvKind::Float) consts[u.index] = Primary::F((float)values[i]);
-        else if (u.kind == UvKind::Int || u.kind == UvKind::Bool) consts[u.index] = Primary::I((int)values[i]);
-    }
+static mmhip_filter *compile_variant(const mmhip_filter *f, const std::map<int, Primary> &consts) {
     mmhip_options o = f->opts;
     o.specialize_uservals = 0;
     return f->source.empty() ? compile_ir_specialized(f, consts) : compile_source(f->source.c_str(), &o, &consts);
 }
 
+mmhip_filter *mmhip_filter_specialized(const mmhip_filter *f, int n, const int *indices, const double *values) {
+    std::map<int, Primary> consts;
+    if (!scalar_constants(f->module.main->uservals, n, indices, values, &consts)) return nullptr;
+    return compile_variant(f, consts);
+}
+
 // The kernel set to launch: the generic filter, or -- with options.specialize_uservals -- a
 // variant with the current scalar user values baked in as literals (built on first use per
 // value set, cached on the filter and on disk through the hiprtc cache).
-static mmhip_filter *active_filter(mmhip_invocation *inv, int frame = 0, float t = 0.0f) {
+mmhip_filter *active_filter(mmhip_invocation *inv, int frame, float t) {
     mmhip_filter *f = inv->f;
     if (!f->specialize || !f->ks.natives.empty() || (f->source.empty() && f->ir_json.empty() && f->ir_json_raw.empty())) return f;
     g_err.clear();
@@ -1314,16 +1300,14 @@ static mmhip_filter *active_filter(mmhip_invocation *inv, int frame = 0, float t
         if (u.count < f->spec_min_uses) return f;
     }
     f->spec_uses.erase(key);
-    mmhip_options o = f->opts;
-    o.specialize_uservals = 0;
-    mmhip_filter *sp = f->source.empty() ? compile_ir_specialized(f, consts) : compile_source(f->source.c_str(), &o, &consts);
+    mmhip_filter *sp = compile_variant(f, consts);
     if (sp && mmhip_filter_jit(sp, 1) < 0) { mmhip_filter_free(sp); sp = nullptr; }
     f->spec_cache[key] = sp;          // nullptr = fall back to the generic kernel for this value set
     return sp ? sp : f;
 }
 
 // mm_args of a render of rows [first_row, last_row) of a region, without the launch's own buffers and geometry
-static HArgs render_args(const mmhip_invocation *inv, int frame, float t, int region_x, int region_y, int region_w, int region_h,
+HArgs render_args(const mmhip_invocation *inv, int frame, float t, int region_x, int region_y, int region_w, int region_h,
                          int first_row, int last_row, void *out_device, int row_stride, int bpp, int floatmap) {
     HArgs a{};
     a.img_width = inv->img_w;
@@ -1358,16 +1342,20 @@ static HArgs render_args(const mmhip_invocation *inv, int frame, float t, int re
     return a;
 }
 
+// new_template.c.in:238-239: the rows of a call, clamped to the region; false where none are left
+bool clamp_rows(int region_y, int region_h, int *first_row, int *last_row) {
+    if (*first_row < 0) *first_row = 0;
+    if (*last_row > region_y + region_h) *last_row = region_y + region_h;
+    return *last_row > *first_row;
+}
+
 int mmhip_render(mmhip_invocation *inv, int frame, float t, int region_x, int region_y, int region_w, int region_h,
                  int first_row, int last_row, void *out_device, int row_stride, int bpp, int floatmap, void *stream) {
     mmhip_filter *f = active_filter(inv, frame, t);
     hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
     if (bpp < 1 || bpp > 4) return fail("output_bpp must be 1..4");
     if (region_w <= 0 || region_h <= 0) return fail("empty region");
-    // new_template.c.in:238-239
-    if (first_row < 0) first_row = 0;
-    if (last_row > region_y + region_h) last_row = region_y + region_h;
-    if (last_row <= first_row) return 0;
+    if (!clamp_rows(region_y, region_h, &first_row, &last_row)) return 0;
     if (upload_tables(inv, s) != 0) return -1;
 
     HArgs a = render_args(inv, frame, t, region_x, region_y, region_w, region_h, first_row, last_row, out_device, row_stride, bpp, floatmap);
@@ -1411,407 +1399,8 @@ int mmhip_render(mmhip_invocation *inv, int frame, float t, int region_x, int re
     if (nwg > 0x7fffffffL) return fail("region too large for one launch");
     a.ppt = geo.ppt;
     a.tiles_magic = geo.tiles_magic;
-    if (inv->timing) {
-        if (next_event_pair(inv) != 0) return -1;
-        HIP_TRY(hipEventRecord(inv->ev0, s));
-    }
     if (direct_written) ++inv->direct_native_launches;
-    if (!direct_written) HIP_TRY(hipModuleLaunchKernel(f->f_pix, (unsigned)nwg, 1, 1, 256, 1, 1, 0, s, params, nullptr));
-    if (inv->timing) {
-        HIP_TRY(hipEventRecord(inv->ev1, s));
-        inv->ev_valid = true;
-    }
-    return 0;
-}
-
-long mmhip_clip_batched_launches(mmhip_invocation *inv) { return inv->clip_batched_launches; }
-long mmhip_clip_prologue_frames(mmhip_invocation *inv) { return inv->clip_prologue_frames; }
-long mmhip_clip_native_batches(mmhip_invocation *inv) { return inv->clip_native_batches; }
-long mmhip_clip_native_blurs(mmhip_invocation *inv) { return inv->clip_native_blurs; }
-long mmhip_clip_native_direct_frames(mmhip_invocation *inv) { return inv->clip_native_direct_frames; }
-
-// mm_clip of the clip kernels (hipgen.cpp clip_prelude; images_stride is `pad' in the text of filters without native calls)
-struct HClipFrame { float t; int frame; };
-struct HClip { const HClipFrame *frames; long long frame_stride; int xy_stride; int rowtab_stride; int nwg; int images_stride; };
-static_assert(sizeof(HClip) == 32, "mm_clip layout");
-
-// ---- clip batches of filters whose native calls are gaussian_blur ----
-// May the native calls of `f' run as batches over the frames of a clip?  Every call site a gaussian_blur outside loops,
-// no closure images, the exact chain with one segment per line, whole maps.
-static bool clip_native_eligible(const mmhip_filter *f, int native_row_margin) {
-    if (f->ks.natives.empty() || f->ks.native_sites != (int)f->ks.natives.size() || !f->closures.empty()) return false;
-    for (const NativeCall &nc : f->ks.natives)
-        if (nc.func != "native_filter_gaussian_blur") return false;
-    const char *seg = getenv("MMHIP_GAUSS_SEGMENTS");
-    return f->opts.gauss_mode == MMHIP_GAUSS_EXACT && !(seg && *seg) && native_row_margin < 0;
-}
-
-// Frames per batch: the clip plan's, at most 65 535 jobs per launch, and what MMHIP_CLIP_NATIVE_BYTES (read once,
-// default 8 GiB) holds of one frame's checkpoints, intermediate and result of every call site.  Below 2 the clip is
-// rendered frame by frame.
-struct ClipNativePlan { bool eligible = false; int per_batch = 0; size_t bytes_per_frame = 0; };
-static ClipNativePlan clip_native_plan(const mmhip_filter *f, int native_row_margin, const ClipPlan &plan, int render_w, int render_h) {
-    static const size_t budget = [] {
-        const char *e = getenv("MMHIP_CLIP_NATIVE_BYTES");
-        const long long v = e ? atoll(e) : 0;
-        return v > 0 ? (size_t)v : (size_t)8 << 30;
-    }();
-    ClipNativePlan p;
-    p.eligible = clip_native_eligible(f, native_row_margin);
-    if (!p.eligible || render_w < 1 || render_h < 1) return p;
-    size_t ck = 0, map = 0;
-    gaussian_blur_batch_job_bytes(render_w, render_h, &ck, &map);
-    p.bytes_per_frame = (size_t)f->ks.native_sites * (ck + 2 * map);
-    const size_t by_bytes = budget / p.bytes_per_frame;
-    const int per = (int)std::min<size_t>(std::min(plan.max_frames, 65535), by_bytes);
-    p.per_batch = per < 2 ? 0 : per;
-    return p;
-}
-
-int mmhip_filter_clip_native_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int render_h, int frames, int64_t *out) {
-    if (frames < 1) return fail("clip native plan: num_frames must be at least 1");
-    if (region_w < 1 || num_rows < 1 || render_w < 1 || render_h < 1) return fail("clip native plan: empty region");
-    const ClipPlan cp = clip_plan(clip_launch_geometry(f->ks, region_w, num_rows, frames));
-    const ClipNativePlan p = clip_native_plan(f, -1, cp, render_w, render_h);
-    const int64_t v[MMHIP_CLIP_NATIVE_PLAN_FIELDS] = {p.eligible, p.per_batch, p.per_batch ? (frames + p.per_batch - 1) / p.per_batch : 0,
-                                                      (int64_t)p.bytes_per_frame};
-    memcpy(out, v, sizeof v);
-    return 0;
-}
-
-// What one call of mmhip_render_clip hands its batches.
-struct ClipCall {
-    mmhip_invocation *inv;
-    mmhip_filter *f;
-    hipStream_t s;
-    HArgs a;                   // out: the first frame of the call
-    HClip c;                   // frames: the call's table
-    char *xy;
-    LaunchGeometry geo;
-    ClipPlan plan;
-    bool per_frame, rows;
-    size_t xy_stride;
-    int64_t frame_stride;
-    const int *frames;
-    const float *ts;
-    void *stream_arg;
-    // native batches: the records of the shared slot (read with the first batch) and whether the launch samples a
-    // native map at every pixel's own centre (decided once per call)
-    std::vector<char> records;
-    int direct_ok = -1;
-};
-
-// Frames [b0, b0 + n) of a clip of a filter whose native calls are all gaussian_blur: one prologue launch, one read-back
-// of all its records, every distinct blur of a call site in one gaussian_blur_batch, one pixel launch over per-frame
-// image tables -- or none, where the blurs pack the frames' bytes themselves.  A batch with a call the batched blur does
-// not take (a FIR deviation, an input of another size, ...) is rendered frame by frame before anything of it is written.
-static int clip_native_batch(ClipCall &cc, int b0, int n) {
-    mmhip_invocation *inv = cc.inv;
-    mmhip_filter *f = cc.f;
-    hipStream_t s = cc.s;
-    const KernelSource &ks = f->ks;
-    HArgs a = cc.a;
-    HClip c = cc.c;
-    char *xy = cc.xy;
-    a.out = (char *)cc.a.out + (int64_t)b0 * cc.frame_stride;
-    c.frames = cc.c.frames + b0;
-    c.images_stride = 0;          // the prologue (and the per-row slice) of every frame reads the invocation's table
-    void *params[] = {&a, &xy, &c};
-    const int num_rows = a.num_rows, region_w = a.region_width;
-    const unsigned pro_x = (unsigned)((std::max(region_w, num_rows) + 255) / 256), rows_x = (unsigned)((num_rows + 255) / 256);
-    const unsigned pro_frames = cc.per_frame ? (unsigned)n : b0 == 0 ? 1u : 0u;
-    if (pro_frames) {
-        HIP_TRY(hipModuleLaunchKernel(f->f_pro_clip, pro_x, pro_frames, 1, 256, 1, 1, 0, s, params, nullptr));
-        if (cc.rows) HIP_TRY(hipModuleLaunchKernel(f->f_rows_clip, rows_x, pro_frames, 1, 256, 1, 1, 0, s, params, nullptr));
-        cc.records.resize(cc.xy_stride * pro_frames);
-        HIP_TRY(hipMemcpyAsync(cc.records.data(), xy, cc.records.size(), hipMemcpyDeviceToHost, s));
-    }
-    std::vector<float> xt, yt;
-    const bool ask_direct = cc.direct_ok < 0 && direct_output_wanted(f, a) && (cc.frame_stride & 3) == 0;
-    if (ask_direct) {
-        xt.resize(region_w);
-        yt.resize(num_rows);
-        HIP_TRY(hipMemcpyAsync(xt.data(), a.xtab, xt.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(yt.data(), a.ytab, yt.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));      // (and with it for the batch before this one: its buffers are free)
-    if (cc.direct_ok < 0) cc.direct_ok = ask_direct && samples_own_pixels(a, xt, yt) ? 1 : 0;
-    auto frame_by_frame = [&]() -> int {
-        for (int i = b0; i < b0 + n; ++i)
-            if (mmhip_render(inv, cc.frames[i], cc.ts[i], a.region_x, a.region_y, a.region_width, a.region_height, a.first_row,
-                             a.first_row + a.num_rows, (char *)cc.a.out + (int64_t)i * cc.frame_stride, a.row_stride, a.output_bpp, a.floatmap,
-                             cc.stream_arg) != 0)
-                return -1;
-        return 0;
-    };
-
-    // Computations: in call order, frames share one where the call site, the record and the computations behind its
-    // native-map arguments are equal -- what the memo does for a loop of single renders.
-    // (view: the image table with the sequence argument's frame in place, MMHIP_NATIVE_FRAME_CURRENT; else empty)
-    struct Comp { size_t k; HNativeRec rec; int frame; std::vector<HImageDesc> view; float *map = nullptr; };
-    const int sites = ks.native_sites, base = inv->native_slot_base;
-    std::vector<Comp> comps;
-    std::vector<int> of_frame((size_t)n * sites, -1);      // [frame][site] -> computation
-    std::map<std::string, int> known;
-    std::vector<char> is_dep;
-    std::vector<RecordedCall> calls;
-    for (int i = 0; i < n; ++i) {
-        if (recorded_calls(ks, cc.records.data() + (cc.per_frame ? (size_t)i * cc.xy_stride : 0), &calls) != 0) return -1;
-        size_t last_k = 0;
-        for (size_t q = 0; q < calls.size(); ++q) {
-            const RecordedCall &call = calls[q];
-            if (q > 0 && call.k <= last_k) return frame_by_frame();      // the sites are not in call order: not expected outside loops
-            last_k = call.k;
-            std::string key((const char *)&call.k, sizeof call.k);
-            key.append((const char *)&call.rec, sizeof call.rec);
-            for (int j = 0; j < call.rec.nargs && j < 4; ++j) {
-                const HNativeArg &arg = call.rec.args[j];
-                if (arg.kind != 2 || arg.img.idx < base || arg.img.idx >= base + sites) continue;
-                const int dep = of_frame[(size_t)i * sites + (arg.img.idx - base)];
-                key.append((const char *)&dep, sizeof dep);
-                if (dep >= 0) is_dep[dep] = 1;
-            }
-            std::vector<HImageDesc> view;
-            int frame_key = NO_FRAME_KEY;
-            if (view_sequence_args(inv, cc.frames[b0 + i], *call.func, call.rec, view, &frame_key) != 0) return -1;
-            key.append((const char *)&frame_key, sizeof frame_key);
-            auto it = known.find(key);
-            if (it == known.end()) {
-                it = known.emplace(key, (int)comps.size()).first;
-                comps.push_back(Comp{call.k, call.rec, i, std::move(view)});
-                is_dep.push_back(0);
-            }
-            of_frame[(size_t)i * sites + call.k] = it->second;
-        }
-    }
-    // direct output: the direct call's blur packs frame i's bytes -- every frame has a blur of its own there, and nothing else reads it
-    bool direct = cc.direct_ok == 1 && ((uintptr_t)a.out & 3) == 0;
-    if (direct) {
-        std::vector<char> taken(comps.size(), 0);
-        for (int i = 0; i < n && direct; ++i) {
-            const int id = of_frame[(size_t)i * sites + ks.direct_native];
-            direct = id >= 0 && !taken[id] && !is_dep[id];
-            if (direct) taken[id] = 1;
-        }
-    }
-    // buffers: checkpoints and intermediate per job of the largest site, a map per computation that is read
-    size_t ck_bytes = 0, map_bytes = 0;
-    gaussian_blur_batch_job_bytes(a.render_width, a.render_height, &ck_bytes, &map_bytes);
-    std::vector<size_t> per_site(sites, 0);
-    size_t kept = 0;
-    for (const Comp &cp : comps) {
-        ++per_site[cp.k];
-        if (!(direct && (int)cp.k == ks.direct_native)) ++kept;
-    }
-    const size_t jobs_max = comps.empty() ? 0 : *std::max_element(per_site.begin(), per_site.end());
-    const size_t images_n = inv->images.size();
-    const size_t images_bytes = ((size_t)n * images_n * sizeof(HImageDesc) + 255) & ~(size_t)255;
-    const size_t tables_bytes = images_bytes + gaussian_blur_batch_table_bytes(comps.size());
-    ClipNativeBuffers &nb = inv->clip_native;
-    auto idle = [] { return hipSuccess; };      // the stream has just been waited for
-    HIP_TRY(nb.work.grow(jobs_max * (ck_bytes + map_bytes), idle));
-    HIP_TRY(nb.maps.grow(kept * map_bytes, idle));
-    HIP_TRY(nb.tables.grow(tables_bytes, idle));
-    if (nb.uploaded_pending) HIP_TRY(hipEventSynchronize(nb.uploaded));
-    nb.uploaded_pending = false;
-    HIP_TRY(nb.host.grow(tables_bytes));
-    {
-        size_t m = 0;
-        for (Comp &cp : comps)
-            if (!(direct && (int)cp.k == ks.direct_native)) cp.map = (float *)(nb.maps.get<char>() + (m++) * map_bytes);
-    }
-    // every frame's image table: the invocation's, the native slots this frame's maps (the null image where a call did not execute)
-    HImageDesc *tables = (HImageDesc *)nb.host.p;
-    HImageDesc null_desc{};
-    null_desc.kind = IMG_NULL;
-    for (int i = 0; i < n; ++i) {
-        HImageDesc *t = tables + (size_t)i * images_n;
-        std::copy(inv->images.begin(), inv->images.end(), t);
-        for (int k = 0; k < sites; ++k) {
-            const int id = of_frame[(size_t)i * sites + k];
-            t[base + k] = id >= 0 && comps[id].map ? floatmap_desc(comps[id].map, a.render_width, a.render_height) : null_desc;
-        }
-    }
-    inv->ws.env.supersampling = f->kopt.supersampling;
-    inv->ws.env.edge_x = f->kopt.edge_x;
-    inv->ws.env.edge_y = f->kopt.edge_y;
-    inv->ws.env.edge_color_x = inv->edge_color_x;
-    inv->ws.env.edge_color_y = inv->edge_color_y;
-    inv->ws.gauss_tolerance = false;
-    // (a computation's own slot is still null in its frame's table while it is planned; a later one finds its map there)
-    for (const Comp &cp : comps) {
-        const int idx = cp.rec.args[0].img.idx;
-        const HImageDesc *t = cp.view.empty() ? tables + (size_t)cp.frame * images_n : cp.view.data();
-        const bool own_result = idx >= base && idx < base + sites && of_frame[(size_t)cp.frame * sites + (idx - base)] >= 0 && (size_t)(idx - base) < cp.k;
-        const bool bound_input = idx >= 0 && idx < base;
-        if (!(own_result || bound_input) ||
-            !gaussian_blur_batchable(cp.rec, t, (int)images_n, a.render_width, a.render_height, inv->ws.env, nullptr, nullptr))
-            return frame_by_frame();
-    }
-    // the job tables of every site, behind the image tables; one copy takes all of them up
-    NativeDirectOut dout;
-    dout.row_stride = a.row_stride;
-    dout.first_row = a.first_row;
-    dout.num_rows = a.num_rows;
-    dout.region_x = a.region_x;
-    dout.region_w = a.region_width;
-    std::vector<std::vector<GaussClipGroup>> groups(sites);
-    std::vector<GaussClipLaunch> launches(sites);
-    size_t at = images_bytes;
-    std::string err;
-    for (int k = 0; k < sites; ++k) {
-        std::vector<GaussClipJob> jobs;
-        const bool packs = direct && k == ks.direct_native;
-        for (size_t id = 0; id < comps.size(); ++id) {
-            const Comp &cp = comps[id];
-            if ((int)cp.k != k) continue;
-            char *w = nb.work.get<char>() + jobs.size() * (ck_bytes + map_bytes);
-            jobs.push_back(GaussClipJob{cp.rec, cp.view.empty() ? tables + (size_t)cp.frame * images_n : cp.view.data(), (int)images_n, (double *)w, (float *)(w + ck_bytes), cp.map,
-                                        packs ? (unsigned char *)a.out + (int64_t)cp.frame * cc.frame_stride : nullptr});
-        }
-        launches[k].render_w = a.render_width;
-        launches[k].render_h = a.render_height;
-        launches[k].direct = packs ? &dout : nullptr;
-        launches[k].write_map = !packs;
-        if (jobs.empty()) continue;
-        if (gaussian_blur_batch_tables(jobs, launches[k], inv->ws.env, (char *)nb.host.p + at, nb.tables.get<char>() + at, &groups[k], &err) != 0)
-            return fail(err);
-        at += gaussian_blur_batch_table_bytes(jobs.size());
-    }
-    if (!nb.uploaded) HIP_TRY(hipEventCreateWithFlags(&nb.uploaded, hipEventDisableTiming));
-    HIP_TRY(hipMemcpyAsync(nb.tables.get(), nb.host.p, tables_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(nb.uploaded, s));
-    nb.uploaded_pending = true;
-    for (int k = 0; k < sites; ++k)
-        if (!groups[k].empty() && gaussian_blur_batch_launch(groups[k], launches[k], inv->ws, s, &err) != 0) return fail(err);
-    ++inv->clip_native_batches;
-    inv->clip_native_blurs += (long)comps.size();
-    if (direct) {
-        inv->clip_native_direct_frames += n;
-        return 0;
-    }
-    a.images = nb.tables.get<HImageDesc>();
-    c.images_stride = (int)images_n;
-    if (inv->timing) {
-        if (next_event_pair(inv) != 0) return -1;
-        HIP_TRY(hipEventRecord(inv->ev0, s));
-    }
-    HIP_TRY(hipModuleLaunchKernel(f->f_pix_clip, (unsigned)cc.plan.grid_x, (unsigned)n, 1, 256, 1, 1, 0, s, params, nullptr));
-    if (inv->timing) {
-        HIP_TRY(hipEventRecord(inv->ev1, s));
-        inv->ev_valid = true;
-    }
-    return 0;
-}
-
-int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int region_x, int region_y,
-                      int region_w, int region_h, int first_row, int last_row, void *out_device, int row_stride,
-                      int64_t frame_stride, int bpp, int floatmap, void *stream) {
-    if (num_frames < 1) return fail("render_clip: num_frames must be at least 1");
-    if (!frames || !ts) return fail("render_clip: frames and ts must be arrays of num_frames entries");
-    if (bpp < 1 || bpp > 4) return fail("output_bpp must be 1..4");
-    if (region_w <= 0 || region_h <= 0) return fail("empty region");
-    if (first_row < 0) first_row = 0;
-    if (last_row > region_y + region_h) last_row = region_y + region_h;
-    if (last_row <= first_row) return 0;
-    const int num_rows = last_row - first_row;
-    // what one frame's band occupies: the next frame must begin behind it
-    const int64_t band = floatmap ? (int64_t)num_rows * 16 * inv->render_w
-                                  : (int64_t)(num_rows - 1) * row_stride + (int64_t)region_w * bpp;
-    if (frame_stride < band)
-        return fail("render_clip: frame_stride " + std::to_string(frame_stride) + " is smaller than one frame's band (" +
-                    std::to_string(band) + " bytes)");
-    mmhip_filter *f = active_filter(inv, frames[0], ts[0]);
-    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
-    const LaunchGeometry geo = clip_launch_geometry(f->ks, region_w, num_rows, num_frames);
-    const ClipPlan plan = clip_plan(geo);
-    const bool natives = !f->ks.natives.empty();
-    const ClipNativePlan nplan = natives ? clip_native_plan(f, inv->native_row_margin, plan, inv->render_w, inv->render_h) : ClipNativePlan();
-    if ((natives && nplan.per_batch < 1) || !f->closures.empty() || plan.max_frames < 1) {
-        // native filters run the host between prologue and pixels of every frame: frame by frame, the same result
-        // (but for gaussian_blur calls the batches below take)
-        for (int i = 0; i < num_frames; ++i)
-            if (mmhip_render(inv, frames[i], ts[i], region_x, region_y, region_w, region_h, first_row, last_row,
-                             (char *)out_device + (int64_t)i * frame_stride, row_stride, bpp, floatmap, stream) != 0)
-                return -1;
-        return 0;
-    }
-    if (mmhip_filter_jit_clip(f, 1) < 0) return -1;
-    if (upload_tables(inv, s) != 0) return -1;
-
-    HArgs a = render_args(inv, frames[0], ts[0], region_x, region_y, region_w, region_h, first_row, last_row, out_device, row_stride, bpp, floatmap);
-    const bool per_frame = f->ks.prologue_uses_time;      // else one frame-constant slot and one row table for all frames
-    const bool rows = f->ks.row_values > 0;
-    const int per_batch = std::min(num_frames, natives ? nplan.per_batch : plan.max_frames);
-    const size_t xy_stride = ((size_t)std::max(f->ks.xy_bytes, 256) + 255) / 256 * 256;
-    const size_t rowtab_stride = (size_t)f->ks.row_values * num_rows;      // floats
-    const int slots = per_frame ? per_batch : 1;
-    if (rowtab_stride * slots > (size_t)INT32_MAX || xy_stride * slots > (size_t)INT32_MAX)
-        return fail("render_clip: the batch's row tables are too large; lower MMHIP_CLIP_MAX_FRAMES");
-    // the coordinate tables are the single-frame path's, rewritten here: its prologue must run again
-    if (grow_launch_buffers(inv->launch, f->ks, region_w, num_rows, false, s) != 0) return -1;
-    inv->pro_filter = nullptr;
-    auto wait = [s] { return hipStreamSynchronize(s); };
-    HIP_TRY(inv->clip.xy.grow(xy_stride * slots, wait, true));
-    if (rows) HIP_TRY(inv->clip.rowtab.grow(rowtab_stride * slots * sizeof(float), wait));
-    // the {t, frame} table of the whole call, copied now: the caller's arrays are free when this returns
-    ClipBuffers::Table &tab = inv->clip.table[inv->clip.next_table++ & 1];
-    if (tab.pending) HIP_TRY(hipEventSynchronize(tab.uploaded));
-    tab.pending = false;
-    const size_t tab_bytes = (size_t)num_frames * sizeof(HClipFrame);
-    HIP_TRY(tab.host.grow(tab_bytes));
-    HIP_TRY(tab.dev.grow(tab_bytes, wait));
-    if (!tab.uploaded) HIP_TRY(hipEventCreateWithFlags(&tab.uploaded, hipEventDisableTiming));
-    HClipFrame *hf = (HClipFrame *)tab.host.p;
-    for (int i = 0; i < num_frames; ++i) hf[i] = HClipFrame{ts[i], frames[i]};
-    HIP_TRY(hipMemcpyAsync(tab.dev.get(), hf, tab_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(tab.uploaded, s));
-    tab.pending = true;
-
-    a.xtab = inv->launch.xtab.get<float>();
-    a.ytab = inv->launch.ytab.get<float>();
-    if (rows) a.rowtab = inv->clip.rowtab.get<float>();
-    a.ppt = geo.ppt;
-    a.tiles_magic = geo.tiles_magic;
-    char *xy = inv->clip.xy.get<char>();
-    HClip c{};
-    c.frame_stride = frame_stride;
-    c.xy_stride = per_frame ? (int)xy_stride : 0;
-    c.rowtab_stride = per_frame ? (int)rowtab_stride : 0;
-    c.nwg = (int)geo.nwg;
-    if (natives) {
-        ClipCall cc{inv, f, s, a, c, xy, geo, plan, per_frame, rows, xy_stride, frame_stride, frames, ts, stream, {}, -1};
-        cc.c.frames = tab.dev.get<HClipFrame>();
-        for (int b0 = 0; b0 < num_frames; b0 += per_batch)
-            if (clip_native_batch(cc, b0, std::min(per_batch, num_frames - b0)) != 0) return -1;
-        return 0;
-    }
-    void *params[] = {&a, &xy, &c};
-    const unsigned pro_x = (unsigned)((std::max(region_w, num_rows) + 255) / 256), rows_x = (unsigned)((num_rows + 255) / 256);
-    for (int b0 = 0; b0 < num_frames; b0 += per_batch) {
-        const int n = std::min(per_batch, num_frames - b0);
-        a.out = (char *)out_device + (int64_t)b0 * frame_stride;
-        c.frames = tab.dev.get<HClipFrame>() + b0;
-        // frame constants (and the per-row slice): one grid row per frame -- or, where they do not depend on t and frame,
-        // frame 0's once for the whole call
-        const unsigned pro_frames = per_frame ? (unsigned)n : b0 == 0 ? 1u : 0u;
-        if (pro_frames) {
-            HIP_TRY(hipModuleLaunchKernel(f->f_pro_clip, pro_x, pro_frames, 1, 256, 1, 1, 0, s, params, nullptr));
-            if (rows) HIP_TRY(hipModuleLaunchKernel(f->f_rows_clip, rows_x, pro_frames, 1, 256, 1, 1, 0, s, params, nullptr));
-            inv->clip_prologue_frames += pro_frames;
-        }
-        if (inv->timing) {
-            if (next_event_pair(inv) != 0) return -1;
-            HIP_TRY(hipEventRecord(inv->ev0, s));
-        }
-        HIP_TRY(hipModuleLaunchKernel(f->f_pix_clip, (unsigned)plan.grid_x, (unsigned)n, 1, 256, 1, 1, 0, s, params, nullptr));
-        ++inv->clip_batched_launches;
-        if (inv->timing) {
-            HIP_TRY(hipEventRecord(inv->ev1, s));
-            inv->ev_valid = true;
-        }
-    }
-    return 0;
+    return timed_pixel_launch(inv, direct_written ? nullptr : f->f_pix, (unsigned)nwg, 1, params, s);
 }
 
 // call_invocation with supersampling (mathmap_common.c:880-927), whole region on the GPU.
@@ -1826,227 +1415,17 @@ int mmhip_render_supersampled(mmhip_invocation *inv, int frame, float t, int reg
     if (inv->ss_lines.grow(long_bytes + short_bytes, hipDeviceSynchronize) != hipSuccess)
         return fail("out of device memory for the supersampling lines");
     unsigned char *tmp = inv->ss_lines.get<unsigned char>();
-    const float ox = inv->sampling_offset_x, oy = inv->sampling_offset_y;
+    SamplingOffsetGuard offsets(inv);
     // long slice: region_width + 1 columns, offsets -0.5 (invocation_init_slice, :892)
-    inv->sampling_offset_x = -0.5f;
-    inv->sampling_offset_y = -0.5f;
+    offsets.set(-0.5f);
     int rc = mmhip_render(inv, frame, t, region_x, region_y, region_w + 1, region_h, region_y, region_y + region_h, tmp,
                           (region_w + 1) * bpp, bpp, 0, s);
-    inv->sampling_offset_x = 0.f;
-    inv->sampling_offset_y = 0.f;
+    offsets.set(0.f);
     if (rc == 0)
         rc = mmhip_render(inv, frame, t, region_x, region_y, region_w, region_h, region_y, region_y + region_h,
                           tmp + long_bytes, region_w * bpp, bpp, 0, s);
-    inv->sampling_offset_x = ox;
-    inv->sampling_offset_y = oy;
     if (rc != 0) return rc;
     launch_supersample_combine(tmp, tmp + long_bytes, (unsigned char *)out_device, region_w, region_h, bpp, row_stride, s);
-    return 0;
-}
-
-// ---- supersampled clips ----
-// How mmhip_render_clip_supersampled cuts a clip into batches.  Frames per batch: what both slices' clip launches take
-// in one launch each (clip_plan of the region_w + 1 and the region_w geometry at that many frames), at most 65 535 (the
-// combine's gridDim.y), and what MMHIP_CLIP_SS_BYTES (read once, default 2 GiB) holds of one frame's two slices.
-// per_batch 0: the loop of mmhip_render_supersampled -- filters with native calls or closure images (their nested
-// renders rely on the native memo across the two slices), and frames too large for any of the above.
-struct ClipSsPlan { int per_batch = 0; size_t bytes_per_frame = 0, long_pitch = 0; };
-static ClipSsPlan clip_ss_plan(const mmhip_filter *f, bool host_between, int region_w, int region_h, int bpp, int frames) {
-    static const size_t budget = [] {
-        const char *e = getenv("MMHIP_CLIP_SS_BYTES");
-        const long long v = e ? atoll(e) : 0;
-        return v > 0 ? (size_t)v : (size_t)2 << 30;
-    }();
-    ClipSsPlan p;
-    p.long_pitch = supersample_clip_long_pitch(region_w, bpp);
-    p.bytes_per_frame = (size_t)region_h * (p.long_pitch + (size_t)region_w * bpp);
-    if (host_between || region_w == INT32_MAX || p.long_pitch > (size_t)INT32_MAX || supersample_clip_items(region_w, region_h) > INT32_MAX)
-        return p;
-    long per = (long)std::min<size_t>({(size_t)frames, (size_t)65535, budget / p.bytes_per_frame});
-    // fewer frames in a launch may mean fewer rows per work-item, more workgroups per frame and a lower cap
-    while (per > 0) {
-        const int cap = std::min(clip_plan(clip_launch_geometry(f->ks, region_w + 1, region_h, (int)per)).max_frames,
-                                 clip_plan(clip_launch_geometry(f->ks, region_w, region_h, (int)per)).max_frames);
-        if (cap >= per) break;
-        per = cap;
-    }
-    p.per_batch = (int)per;
-    return p;
-}
-
-int mmhip_filter_clip_supersample_plan(const mmhip_filter *f, int region_w, int region_h, int bpp, int frames, int64_t *out) {
-    if (frames < 1) return fail("clip supersample plan: num_frames must be at least 1");
-    if (bpp < 1 || bpp > 4) return fail("output_bpp must be 1..4");
-    if (region_w < 1 || region_h < 1) return fail("clip supersample plan: empty region");
-    const ClipSsPlan p = clip_ss_plan(f, !f->ks.natives.empty() || !f->closures.empty(), region_w, region_h, bpp, frames);
-    const int64_t v[MMHIP_CLIP_SS_PLAN_FIELDS] = {p.per_batch > 0, p.per_batch, p.per_batch ? (frames + p.per_batch - 1) / p.per_batch : 0,
-                                                  (int64_t)p.bytes_per_frame, (int64_t)p.long_pitch, SS_CLIP_ROWS, SS_CLIP_PIXELS};
-    memcpy(out, v, sizeof v);
-    return 0;
-}
-
-long mmhip_clip_supersampled_batches(mmhip_invocation *inv) { return inv->clip_supersampled_batches; }
-
-// The invocation's sampling offsets for the length of a scope: put back on every way out.
-struct SamplingOffsetGuard {
-    mmhip_invocation *inv;
-    float ox, oy;
-    explicit SamplingOffsetGuard(mmhip_invocation *i) : inv(i), ox(i->sampling_offset_x), oy(i->sampling_offset_y) {}
-    ~SamplingOffsetGuard() { inv->sampling_offset_x = ox; inv->sampling_offset_y = oy; }
-    void set(float v) { inv->sampling_offset_x = inv->sampling_offset_y = v; }
-};
-
-int mmhip_render_clip_supersampled(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int region_x,
-                                   int region_y, int region_w, int region_h, void *out_device, int row_stride,
-                                   int64_t frame_stride, int bpp, void *stream) {
-    if (num_frames < 1) return fail("render_clip_supersampled: num_frames must be at least 1");
-    if (!frames || !ts) return fail("render_clip_supersampled: frames and ts must be arrays of num_frames entries");
-    if (bpp < 1 || bpp > 4) return fail("output_bpp must be 1..4");
-    if (region_w <= 0 || region_h <= 0) return fail("empty region");
-    const int64_t band = (int64_t)(region_h - 1) * row_stride + (int64_t)region_w * bpp;
-    if (frame_stride < band)
-        return fail("render_clip_supersampled: frame_stride " + std::to_string(frame_stride) + " is smaller than one frame's band (" +
-                    std::to_string(band) + " bytes)");
-    const bool host_between = !inv->f->ks.natives.empty() || !inv->f->closures.empty();
-    const ClipSsPlan plan = clip_ss_plan(host_between ? inv->f : active_filter(inv, frames[0], ts[0]), host_between, region_w,
-                                         region_h, bpp, num_frames);
-    if (plan.per_batch < 1) {
-        for (int i = 0; i < num_frames; ++i)
-            if (mmhip_render_supersampled(inv, frames[i], ts[i], region_x, region_y, region_w, region_h,
-                                          (char *)out_device + (int64_t)i * frame_stride, row_stride, bpp, stream) != 0)
-                return -1;
-        return 0;
-    }
-    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
-    const int per_batch = plan.per_batch;
-    const size_t long_frame = (size_t)region_h * plan.long_pitch, short_frame = (size_t)region_h * region_w * bpp;
-    // own allocation, like ss_lines; whatever still reads a smaller one has finished before it is freed
-    if (inv->clip_ss.grow((size_t)per_batch * plan.bytes_per_frame, hipDeviceSynchronize) != hipSuccess)
-        return fail("out of device memory for the supersampling slices of a clip; lower MMHIP_CLIP_SS_BYTES");
-    unsigned char *longs = inv->clip_ss.get<unsigned char>(), *shorts = longs + (size_t)per_batch * long_frame;
-    SamplingOffsetGuard offsets(inv);
-    for (int b0 = 0; b0 < num_frames; b0 += per_batch) {
-        const int n = std::min(per_batch, num_frames - b0);
-        // long slices: region_width + 1 columns at offsets -0.5, then the short ones at 0 (mmhip_render_supersampled)
-        offsets.set(-0.5f);
-        if (mmhip_render_clip(inv, n, frames + b0, ts + b0, region_x, region_y, region_w + 1, region_h, region_y, region_y + region_h,
-                              longs, (int)plan.long_pitch, (int64_t)long_frame, bpp, 0, s) != 0)
-            return -1;
-        offsets.set(0.f);
-        if (mmhip_render_clip(inv, n, frames + b0, ts + b0, region_x, region_y, region_w, region_h, region_y, region_y + region_h,
-                              shorts, region_w * bpp, (int64_t)short_frame, bpp, 0, s) != 0)
-            return -1;
-        std::string err;
-        if (launch_supersample_combine_clip(longs, shorts, (unsigned char *)out_device + (int64_t)b0 * frame_stride, region_w, region_h,
-                                            bpp, row_stride, frame_stride, n, inv->ws, s, &err) != 0)
-            return fail(err);
-        ++inv->clip_supersampled_batches;
-    }
-    return 0;
-}
-
-// ---- motion-blurred clips ----
-// How mmhip_render_clip_shutter cuts a clip into batches and a frame's sub-samples into passes (include/mmhip.h has the
-// rules).  MMHIP_CLIP_SHUTTER_BYTES is read once, default 8 GiB.
-struct ClipShutterPlan { int per_batch = 1, batches = 1, samples_per_pass = 1, passes = 1, carry = 0; size_t bytes_per_sample = 0; };
-static ClipShutterPlan clip_shutter_plan(int num_rows, int render_w, int samples, int frames) {
-    static const size_t budget = [] {
-        const char *e = getenv("MMHIP_CLIP_SHUTTER_BYTES");
-        const long long v = e ? atoll(e) : 0;
-        return v > 0 ? (size_t)v : (size_t)8 << 30;
-    }();
-    ClipShutterPlan p;
-    p.bytes_per_sample = (size_t)num_rows * 16 * (size_t)render_w;
-    const size_t frame_bytes = (size_t)samples * p.bytes_per_sample;
-    if (budget >= frame_bytes) {
-        p.per_batch = (int)std::min<size_t>({budget / frame_bytes, (size_t)65535, (size_t)frames});
-        p.samples_per_pass = samples;
-    } else {
-        // not one frame's sub-samples: a frame at a time, in passes over what fits beside the carry map (at least one)
-        p.samples_per_pass = (int)std::max<long long>(1, (long long)(budget / p.bytes_per_sample) - 1);
-        p.passes = (samples + p.samples_per_pass - 1) / p.samples_per_pass;
-        p.carry = p.passes > 1;
-    }
-    p.batches = (frames + p.per_batch - 1) / p.per_batch;
-    return p;
-}
-
-static int clip_shutter_check_samples(const char *who, int samples) {
-    if (samples < 1 || samples > MMHIP_SHUTTER_MAX_SAMPLES)
-        return fail(std::string(who) + ": samples must be 1 to " + std::to_string((int)MMHIP_SHUTTER_MAX_SAMPLES) + ", not " + std::to_string(samples));
-    return 0;
-}
-
-int mmhip_filter_clip_shutter_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int samples, int frames, int64_t *out) {
-    (void)f;
-    if (frames < 1) return fail("clip shutter plan: num_frames must be at least 1");
-    if (clip_shutter_check_samples("clip shutter plan", samples) != 0) return -1;
-    if (region_w < 1 || num_rows < 1 || render_w < region_w) return fail("clip shutter plan: empty region, or one wider than the render width");
-    const ClipShutterPlan p = clip_shutter_plan(num_rows, render_w, samples, frames);
-    const int64_t v[MMHIP_CLIP_SHUTTER_PLAN_FIELDS] = {p.per_batch, p.batches, p.samples_per_pass, p.passes, (int64_t)p.bytes_per_sample, p.carry};
-    memcpy(out, v, sizeof v);
-    return 0;
-}
-
-long mmhip_clip_shutter_batches(mmhip_invocation *inv) { return inv->clip_shutter_batches; }
-
-int mmhip_render_clip_shutter(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
-                              int region_x, int region_y, int region_w, int region_h, int first_row, int last_row, void *out_device,
-                              int row_stride, int64_t frame_stride, int bpp, int floatmap, void *stream) {
-    if (clip_shutter_check_samples("render_clip_shutter", samples) != 0) return -1;
-    if (samples == 1)       // one instant per frame: the plain clip itself
-        return mmhip_render_clip(inv, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
-                                 row_stride, frame_stride, bpp, floatmap, stream);
-    if (!std::isfinite(span)) return fail("render_clip_shutter: span must be finite");
-    if (num_frames < 1) return fail("render_clip_shutter: num_frames must be at least 1");
-    if (!frames || !ts) return fail("render_clip_shutter: frames and ts must be arrays of num_frames entries");
-    if (bpp < 1 || bpp > 4) return fail("output_bpp must be 1..4");
-    if (region_w <= 0 || region_h <= 0) return fail("empty region");
-    if (first_row < 0) first_row = 0;
-    if (last_row > region_y + region_h) last_row = region_y + region_h;
-    if (last_row <= first_row) return 0;
-    const int num_rows = last_row - first_row;
-    const int64_t band = floatmap ? (int64_t)num_rows * 16 * inv->render_w
-                                  : (int64_t)(num_rows - 1) * row_stride + (int64_t)region_w * bpp;
-    if (frame_stride < band)
-        return fail("render_clip_shutter: frame_stride " + std::to_string(frame_stride) + " is smaller than one frame's band (" +
-                    std::to_string(band) + " bytes)");
-    if (region_w > inv->render_w) return fail("render_clip_shutter: the region is wider than the render width");
-    const ClipShutterPlan plan = clip_shutter_plan(num_rows, inv->render_w, samples, num_frames);
-    const size_t bps = plan.bytes_per_sample;
-    if (bps > ((size_t)1 << 32)) return fail("render_clip_shutter: a sub-sample map of more than 4 GiB; render the frame in row bands");
-    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
-    // own allocation, like clip_ss; whatever still reads a smaller one has finished before it is freed
-    const size_t slots = (size_t)plan.per_batch * plan.samples_per_pass;
-    if (inv->clip_shutter.grow((slots + plan.carry) * bps, hipDeviceSynchronize) != hipSuccess)
-        return fail("out of device memory for the sub-samples of a motion-blurred clip; lower MMHIP_CLIP_SHUTTER_BYTES");
-    unsigned char *subs = inv->clip_shutter.get<unsigned char>(), *carry = plan.carry ? subs + slots * bps : nullptr;
-    const float inv_k = mm_shutter_inv_k(samples);
-    std::vector<int> sub_frames;
-    std::vector<float> sub_ts;
-    for (int b0 = 0; b0 < num_frames; b0 += plan.per_batch) {
-        const int n = std::min(plan.per_batch, num_frames - b0);
-        for (int j0 = 0; j0 < samples; j0 += plan.samples_per_pass) {
-            const int count = std::min(plan.samples_per_pass, samples - j0);
-            sub_frames.resize((size_t)n * count);
-            sub_ts.resize((size_t)n * count);
-            for (int i = 0; i < n; ++i)
-                for (int j = 0; j < count; ++j) {
-                    sub_frames[(size_t)i * count + j] = frames[b0 + i];
-                    sub_ts[(size_t)i * count + j] = mm_shutter_sample_t(ts[b0 + i], span, j0 + j, samples);
-                }
-            if (mmhip_render_clip(inv, n * count, sub_frames.data(), sub_ts.data(), region_x, region_y, region_w, region_h, first_row,
-                                  last_row, subs, row_stride, (int64_t)bps, bpp, 1, s) != 0)
-                return -1;
-            const bool last = j0 + count >= samples;
-            std::string err;
-            if (launch_shutter_combine_clip(subs, (int64_t)bps, (int64_t)count * (int64_t)bps, count, j0 > 0 ? carry : nullptr, last ? nullptr : carry,
-                                            (char *)out_device + (int64_t)b0 * frame_stride, region_w, num_rows, inv->render_w, row_stride,
-                                            frame_stride, bpp, floatmap, inv_k, n, inv->ws, s, &err) != 0)
-                return fail(err);
-        }
-        ++inv->clip_shutter_batches;
-    }
     return 0;
 }
 
@@ -2093,5 +1472,3 @@ int mmhip_device_count(void) {
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
 }
-
-}  // extern "C"

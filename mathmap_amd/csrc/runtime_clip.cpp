@@ -1,0 +1,564 @@
+// Clip rendering: the frames of an animation in batched launches (mmhip_render_clip), supersampled
+// (mmhip_render_clip_supersampled) and motion-blurred (mmhip_render_clip_shutter), on top of the single-frame path of
+// runtime.cpp.  (The exported functions have C linkage from include/mmhip.h.)
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "mm_shutter_combine.h"
+#include "runtime_internal.h"
+
+using namespace mm;
+
+// A byte budget from the environment: a positive count, or the default.
+static size_t env_bytes(const char *name, size_t fallback) {
+    const char *e = getenv(name);
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (size_t)v : fallback;
+}
+
+// The argument checks of the three entry points, under the name of the one that was called.
+static int check_clip_args(const char *who, int num_frames, const int *frames, const float *ts, int bpp, int region_w, int region_h) {
+    if (num_frames < 1) return fail(std::string(who) + ": num_frames must be at least 1");
+    if (!frames || !ts) return fail(std::string(who) + ": frames and ts must be arrays of num_frames entries");
+    if (bpp < 1 || bpp > 4) return fail("output_bpp must be 1..4");
+    if (region_w <= 0 || region_h <= 0) return fail("empty region");
+    return 0;
+}
+
+// what one frame's band occupies: the next frame must begin behind it (the invocation is looked at for float maps only)
+static int check_frame_stride(const char *who, const mmhip_invocation *inv, int64_t frame_stride, int num_rows, int region_w, int row_stride, int bpp, int floatmap) {
+    const int64_t band = floatmap ? (int64_t)num_rows * 16 * inv->render_w
+                                  : (int64_t)(num_rows - 1) * row_stride + (int64_t)region_w * bpp;
+    if (frame_stride < band)
+        return fail(std::string(who) + ": frame_stride " + std::to_string(frame_stride) + " is smaller than one frame's band (" +
+                    std::to_string(band) + " bytes)");
+    return 0;
+}
+
+long mmhip_clip_batched_launches(mmhip_invocation *inv) { return inv->clip_batched_launches; }
+long mmhip_clip_prologue_frames(mmhip_invocation *inv) { return inv->clip_prologue_frames; }
+long mmhip_clip_native_batches(mmhip_invocation *inv) { return inv->clip_native_batches; }
+long mmhip_clip_native_blurs(mmhip_invocation *inv) { return inv->clip_native_blurs; }
+long mmhip_clip_native_direct_frames(mmhip_invocation *inv) { return inv->clip_native_direct_frames; }
+
+// mm_clip of the clip kernels (hipgen.cpp clip_prelude; images_stride is `pad' in the text of filters without native calls)
+struct HClipFrame { float t; int frame; };
+struct HClip { const HClipFrame *frames; long long frame_stride; int xy_stride; int rowtab_stride; int nwg; int images_stride; };
+static_assert(sizeof(HClip) == 32, "mm_clip layout");
+
+// ---- clip batches of filters whose native calls are gaussian_blur ----
+// May the native calls of `f' run as batches over the frames of a clip?  Every call site a gaussian_blur outside loops,
+// no closure images, the exact chain with one segment per line, whole maps.
+static bool clip_native_eligible(const mmhip_filter *f, int native_row_margin) {
+    if (f->ks.natives.empty() || f->ks.native_sites != (int)f->ks.natives.size() || !f->closures.empty()) return false;
+    for (const NativeCall &nc : f->ks.natives)
+        if (nc.func != "native_filter_gaussian_blur") return false;
+    const char *seg = getenv("MMHIP_GAUSS_SEGMENTS");
+    return f->opts.gauss_mode == MMHIP_GAUSS_EXACT && !(seg && *seg) && native_row_margin < 0;
+}
+
+// Frames per batch: the clip plan's, at most 65 535 jobs per launch, and what MMHIP_CLIP_NATIVE_BYTES (read once,
+// default 8 GiB) holds of one frame's checkpoints, intermediate and result of every call site.  Below 2 the clip is
+// rendered frame by frame.
+struct ClipNativePlan { bool eligible = false; int per_batch = 0; size_t bytes_per_frame = 0; };
+static ClipNativePlan clip_native_plan(const mmhip_filter *f, int native_row_margin, const ClipPlan &plan, int render_w, int render_h) {
+    static const size_t budget = env_bytes("MMHIP_CLIP_NATIVE_BYTES", (size_t)8 << 30);
+    ClipNativePlan p;
+    p.eligible = clip_native_eligible(f, native_row_margin);
+    if (!p.eligible || render_w < 1 || render_h < 1) return p;
+    size_t ck = 0, map = 0;
+    gaussian_blur_batch_job_bytes(render_w, render_h, &ck, &map);
+    p.bytes_per_frame = (size_t)f->ks.native_sites * (ck + 2 * map);
+    const size_t by_bytes = budget / p.bytes_per_frame;
+    const int per = (int)std::min<size_t>(std::min(plan.max_frames, 65535), by_bytes);
+    p.per_batch = per < 2 ? 0 : per;
+    return p;
+}
+
+int mmhip_filter_clip_native_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int render_h, int frames, int64_t *out) {
+    if (frames < 1) return fail("clip native plan: num_frames must be at least 1");
+    if (region_w < 1 || num_rows < 1 || render_w < 1 || render_h < 1) return fail("clip native plan: empty region");
+    const ClipPlan cp = clip_plan(clip_launch_geometry(f->ks, region_w, num_rows, frames));
+    const ClipNativePlan p = clip_native_plan(f, -1, cp, render_w, render_h);
+    const int64_t v[MMHIP_CLIP_NATIVE_PLAN_FIELDS] = {p.eligible, p.per_batch, p.per_batch ? (frames + p.per_batch - 1) / p.per_batch : 0,
+                                                      (int64_t)p.bytes_per_frame};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+// What one call of mmhip_render_clip hands its batches.
+struct ClipCall {
+    mmhip_invocation *inv;
+    mmhip_filter *f;
+    hipStream_t s;
+    HArgs a;                   // out: the first frame of the call
+    HClip c;                   // frames: the call's table
+    char *xy;
+    LaunchGeometry geo;
+    ClipPlan plan;
+    bool per_frame, rows;
+    size_t xy_stride;
+    int64_t frame_stride;
+    const int *frames;
+    const float *ts;
+    void *stream_arg;
+    // native batches: the records of the shared slot (read with the first batch) and whether the launch samples a
+    // native map at every pixel's own centre (decided once per call)
+    std::vector<char> records;
+    int direct_ok = -1;
+};
+
+// Frame constants (and the per-row slice) of frames [b0, b0 + n): one grid row per frame -- or, where they do not depend on
+// t and frame (!per_frame), frame 0's once for the whole call.  Returns the frames they were launched for, or -1.
+static int launch_clip_prologue(const mmhip_filter *f, const HArgs &a, bool per_frame, bool rows, int b0, int n, void **params, hipStream_t s) {
+    const unsigned pro_x = (unsigned)((std::max(a.region_width, a.num_rows) + 255) / 256), rows_x = (unsigned)((a.num_rows + 255) / 256);
+    const unsigned pro_frames = per_frame ? (unsigned)n : b0 == 0 ? 1u : 0u;
+    if (pro_frames) {
+        HIP_TRY(hipModuleLaunchKernel(f->f_pro_clip, pro_x, pro_frames, 1, 256, 1, 1, 0, s, params, nullptr));
+        if (rows) HIP_TRY(hipModuleLaunchKernel(f->f_rows_clip, rows_x, pro_frames, 1, 256, 1, 1, 0, s, params, nullptr));
+    }
+    return (int)pro_frames;
+}
+
+// Frames [b0, b0 + n) of a clip of a filter whose native calls are all gaussian_blur: one prologue launch, one read-back
+// of all its records, every distinct blur of a call site in one gaussian_blur_batch, one pixel launch over per-frame
+// image tables -- or none, where the blurs pack the frames' bytes themselves.  A batch with a call the batched blur does
+// not take (a FIR deviation, an input of another size, ...) is rendered frame by frame before anything of it is written.
+static int clip_native_batch(ClipCall &cc, int b0, int n) {
+    mmhip_invocation *inv = cc.inv;
+    mmhip_filter *f = cc.f;
+    hipStream_t s = cc.s;
+    const KernelSource &ks = f->ks;
+    HArgs a = cc.a;
+    HClip c = cc.c;
+    char *xy = cc.xy;
+    a.out = (char *)cc.a.out + (int64_t)b0 * cc.frame_stride;
+    c.frames = cc.c.frames + b0;
+    c.images_stride = 0;          // the prologue (and the per-row slice) of every frame reads the invocation's table
+    void *params[] = {&a, &xy, &c};
+    const int pro_frames = launch_clip_prologue(f, a, cc.per_frame, cc.rows, b0, n, params, s);
+    if (pro_frames < 0) return -1;
+    if (pro_frames) {
+        cc.records.resize(cc.xy_stride * pro_frames);
+        HIP_TRY(hipMemcpyAsync(cc.records.data(), xy, cc.records.size(), hipMemcpyDeviceToHost, s));
+    }
+    std::vector<float> xt, yt;
+    const bool ask_direct = cc.direct_ok < 0 && direct_output_wanted(f, a) && (cc.frame_stride & 3) == 0;
+    if (ask_direct && read_coordinate_tables(a, s, &xt, &yt) != 0) return -1;
+    HIP_TRY(hipStreamSynchronize(s));      // (and with it for the batch before this one: its buffers are free)
+    if (cc.direct_ok < 0) cc.direct_ok = ask_direct && samples_own_pixels(a, xt, yt) ? 1 : 0;
+    auto frame_by_frame = [&]() -> int {
+        for (int i = b0; i < b0 + n; ++i)
+            if (mmhip_render(inv, cc.frames[i], cc.ts[i], a.region_x, a.region_y, a.region_width, a.region_height, a.first_row,
+                             a.first_row + a.num_rows, (char *)cc.a.out + (int64_t)i * cc.frame_stride, a.row_stride, a.output_bpp, a.floatmap,
+                             cc.stream_arg) != 0)
+                return -1;
+        return 0;
+    };
+
+    // Computations: in call order, frames share one where the call site, the record and the computations behind its
+    // native-map arguments are equal -- what the memo does for a loop of single renders.
+    // (view: the image table with the sequence argument's frame in place, MMHIP_NATIVE_FRAME_CURRENT; else empty)
+    struct Comp { size_t k; HNativeRec rec; int frame; std::vector<HImageDesc> view; float *map = nullptr; };
+    const int sites = ks.native_sites, base = inv->native_slot_base;
+    std::vector<Comp> comps;
+    std::vector<int> of_frame((size_t)n * sites, -1);      // [frame][site] -> computation
+    std::map<std::string, int> known;
+    std::vector<char> is_dep;
+    std::vector<RecordedCall> calls;
+    for (int i = 0; i < n; ++i) {
+        if (recorded_calls(ks, cc.records.data() + (cc.per_frame ? (size_t)i * cc.xy_stride : 0), &calls) != 0) return -1;
+        size_t last_k = 0;
+        for (size_t q = 0; q < calls.size(); ++q) {
+            const RecordedCall &call = calls[q];
+            if (q > 0 && call.k <= last_k) return frame_by_frame();      // the sites are not in call order: not expected outside loops
+            last_k = call.k;
+            std::string key((const char *)&call.k, sizeof call.k);
+            key.append((const char *)&call.rec, sizeof call.rec);
+            for (int j = 0; j < call.rec.nargs && j < 4; ++j) {
+                const HNativeArg &arg = call.rec.args[j];
+                if (arg.kind != 2 || arg.img.idx < base || arg.img.idx >= base + sites) continue;
+                const int dep = of_frame[(size_t)i * sites + (arg.img.idx - base)];
+                key.append((const char *)&dep, sizeof dep);
+                if (dep >= 0) is_dep[dep] = 1;
+            }
+            std::vector<HImageDesc> view;
+            int frame_key = NO_FRAME_KEY;
+            if (view_sequence_args(inv, cc.frames[b0 + i], *call.func, call.rec, view, &frame_key) != 0) return -1;
+            key.append((const char *)&frame_key, sizeof frame_key);
+            auto it = known.find(key);
+            if (it == known.end()) {
+                it = known.emplace(key, (int)comps.size()).first;
+                comps.push_back(Comp{call.k, call.rec, i, std::move(view)});
+                is_dep.push_back(0);
+            }
+            of_frame[(size_t)i * sites + call.k] = it->second;
+        }
+    }
+    // direct output: the direct call's blur packs frame i's bytes -- every frame has a blur of its own there, and nothing else reads it
+    bool direct = cc.direct_ok == 1 && ((uintptr_t)a.out & 3) == 0;
+    if (direct) {
+        std::vector<char> taken(comps.size(), 0);
+        for (int i = 0; i < n && direct; ++i) {
+            const int id = of_frame[(size_t)i * sites + ks.direct_native];
+            direct = id >= 0 && !taken[id] && !is_dep[id];
+            if (direct) taken[id] = 1;
+        }
+    }
+    // buffers: checkpoints and intermediate per job of the largest site, a map per computation that is read
+    size_t ck_bytes = 0, map_bytes = 0;
+    gaussian_blur_batch_job_bytes(a.render_width, a.render_height, &ck_bytes, &map_bytes);
+    std::vector<size_t> per_site(sites, 0);
+    size_t kept = 0;
+    for (const Comp &cp : comps) {
+        ++per_site[cp.k];
+        if (!(direct && (int)cp.k == ks.direct_native)) ++kept;
+    }
+    const size_t jobs_max = comps.empty() ? 0 : *std::max_element(per_site.begin(), per_site.end());
+    const size_t images_n = inv->images.size();
+    const size_t images_bytes = ((size_t)n * images_n * sizeof(HImageDesc) + 255) & ~(size_t)255;
+    const size_t tables_bytes = images_bytes + gaussian_blur_batch_table_bytes(comps.size());
+    ClipNativeBuffers &nb = inv->clip_native;
+    auto idle = [] { return hipSuccess; };      // the stream has just been waited for
+    HIP_TRY(nb.work.grow(jobs_max * (ck_bytes + map_bytes), idle));
+    HIP_TRY(nb.maps.grow(kept * map_bytes, idle));
+    HIP_TRY(nb.tables.grow(tables_bytes, idle));
+    if (nb.uploaded_pending) HIP_TRY(hipEventSynchronize(nb.uploaded));
+    nb.uploaded_pending = false;
+    HIP_TRY(nb.host.grow(tables_bytes));
+    {
+        size_t m = 0;
+        for (Comp &cp : comps)
+            if (!(direct && (int)cp.k == ks.direct_native)) cp.map = (float *)(nb.maps.get<char>() + (m++) * map_bytes);
+    }
+    // every frame's image table: the invocation's, the native slots this frame's maps (the null image where a call did not execute)
+    HImageDesc *tables = (HImageDesc *)nb.host.p;
+    HImageDesc null_desc{};
+    null_desc.kind = IMG_NULL;
+    for (int i = 0; i < n; ++i) {
+        HImageDesc *t = tables + (size_t)i * images_n;
+        std::copy(inv->images.begin(), inv->images.end(), t);
+        for (int k = 0; k < sites; ++k) {
+            const int id = of_frame[(size_t)i * sites + k];
+            t[base + k] = id >= 0 && comps[id].map ? floatmap_desc(comps[id].map, a.render_width, a.render_height) : null_desc;
+        }
+    }
+    set_native_env(inv, f, false);
+    // (a computation's own slot is still null in its frame's table while it is planned; a later one finds its map there)
+    for (const Comp &cp : comps) {
+        const int idx = cp.rec.args[0].img.idx;
+        const HImageDesc *t = cp.view.empty() ? tables + (size_t)cp.frame * images_n : cp.view.data();
+        const bool own_result = idx >= base && idx < base + sites && of_frame[(size_t)cp.frame * sites + (idx - base)] >= 0 && (size_t)(idx - base) < cp.k;
+        const bool bound_input = idx >= 0 && idx < base;
+        if (!(own_result || bound_input) ||
+            !gaussian_blur_batchable(cp.rec, t, (int)images_n, a.render_width, a.render_height, inv->ws.env, nullptr, nullptr))
+            return frame_by_frame();
+    }
+    // the job tables of every site, behind the image tables; one copy takes all of them up
+    NativeDirectOut dout;
+    dout.row_stride = a.row_stride;
+    dout.first_row = a.first_row;
+    dout.num_rows = a.num_rows;
+    dout.region_x = a.region_x;
+    dout.region_w = a.region_width;
+    std::vector<std::vector<GaussClipGroup>> groups(sites);
+    std::vector<GaussClipLaunch> launches(sites);
+    size_t at = images_bytes;
+    std::string err;
+    for (int k = 0; k < sites; ++k) {
+        std::vector<GaussClipJob> jobs;
+        const bool packs = direct && k == ks.direct_native;
+        for (size_t id = 0; id < comps.size(); ++id) {
+            const Comp &cp = comps[id];
+            if ((int)cp.k != k) continue;
+            char *w = nb.work.get<char>() + jobs.size() * (ck_bytes + map_bytes);
+            jobs.push_back(GaussClipJob{cp.rec, cp.view.empty() ? tables + (size_t)cp.frame * images_n : cp.view.data(), (int)images_n, (double *)w, (float *)(w + ck_bytes), cp.map,
+                                        packs ? (unsigned char *)a.out + (int64_t)cp.frame * cc.frame_stride : nullptr});
+        }
+        launches[k].render_w = a.render_width;
+        launches[k].render_h = a.render_height;
+        launches[k].direct = packs ? &dout : nullptr;
+        launches[k].write_map = !packs;
+        if (jobs.empty()) continue;
+        if (gaussian_blur_batch_tables(jobs, launches[k], inv->ws.env, (char *)nb.host.p + at, nb.tables.get<char>() + at, &groups[k], &err) != 0)
+            return fail(err);
+        at += gaussian_blur_batch_table_bytes(jobs.size());
+    }
+    if (!nb.uploaded) HIP_TRY(hipEventCreateWithFlags(&nb.uploaded, hipEventDisableTiming));
+    HIP_TRY(hipMemcpyAsync(nb.tables.get(), nb.host.p, tables_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(nb.uploaded, s));
+    nb.uploaded_pending = true;
+    for (int k = 0; k < sites; ++k)
+        if (!groups[k].empty() && gaussian_blur_batch_launch(groups[k], launches[k], inv->ws, s, &err) != 0) return fail(err);
+    ++inv->clip_native_batches;
+    inv->clip_native_blurs += (long)comps.size();
+    if (direct) {
+        inv->clip_native_direct_frames += n;
+        return 0;
+    }
+    a.images = nb.tables.get<HImageDesc>();
+    c.images_stride = (int)images_n;
+    return timed_pixel_launch(inv, f->f_pix_clip, (unsigned)cc.plan.grid_x, (unsigned)n, params, s);
+}
+
+int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int region_x, int region_y,
+                      int region_w, int region_h, int first_row, int last_row, void *out_device, int row_stride,
+                      int64_t frame_stride, int bpp, int floatmap, void *stream) {
+    if (check_clip_args("render_clip", num_frames, frames, ts, bpp, region_w, region_h) != 0) return -1;
+    if (!clamp_rows(region_y, region_h, &first_row, &last_row)) return 0;
+    const int num_rows = last_row - first_row;
+    if (check_frame_stride("render_clip", inv, frame_stride, num_rows, region_w, row_stride, bpp, floatmap) != 0) return -1;
+    mmhip_filter *f = active_filter(inv, frames[0], ts[0]);
+    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
+    const LaunchGeometry geo = clip_launch_geometry(f->ks, region_w, num_rows, num_frames);
+    const ClipPlan plan = clip_plan(geo);
+    const bool natives = !f->ks.natives.empty();
+    const ClipNativePlan nplan = natives ? clip_native_plan(f, inv->native_row_margin, plan, inv->render_w, inv->render_h) : ClipNativePlan();
+    if ((natives && nplan.per_batch < 1) || !f->closures.empty() || plan.max_frames < 1) {
+        // native filters run the host between prologue and pixels of every frame: frame by frame, the same result
+        // (but for gaussian_blur calls the batches below take)
+        for (int i = 0; i < num_frames; ++i)
+            if (mmhip_render(inv, frames[i], ts[i], region_x, region_y, region_w, region_h, first_row, last_row,
+                             (char *)out_device + (int64_t)i * frame_stride, row_stride, bpp, floatmap, stream) != 0)
+                return -1;
+        return 0;
+    }
+    if (mmhip_filter_jit_clip(f, 1) < 0) return -1;
+    if (upload_tables(inv, s) != 0) return -1;
+
+    HArgs a = render_args(inv, frames[0], ts[0], region_x, region_y, region_w, region_h, first_row, last_row, out_device, row_stride, bpp, floatmap);
+    const bool per_frame = f->ks.prologue_uses_time;      // else one frame-constant slot and one row table for all frames
+    const bool rows = f->ks.row_values > 0;
+    const int per_batch = std::min(num_frames, natives ? nplan.per_batch : plan.max_frames);
+    const size_t xy_stride = ((size_t)std::max(f->ks.xy_bytes, 256) + 255) / 256 * 256;
+    const size_t rowtab_stride = (size_t)f->ks.row_values * num_rows;      // floats
+    const int slots = per_frame ? per_batch : 1;
+    if (rowtab_stride * slots > (size_t)INT32_MAX || xy_stride * slots > (size_t)INT32_MAX)
+        return fail("render_clip: the batch's row tables are too large; lower MMHIP_CLIP_MAX_FRAMES");
+    // the coordinate tables are the single-frame path's, rewritten here: its prologue must run again
+    if (grow_launch_buffers(inv->launch, f->ks, region_w, num_rows, false, s) != 0) return -1;
+    inv->pro_filter = nullptr;
+    auto wait = [s] { return hipStreamSynchronize(s); };
+    HIP_TRY(inv->clip.xy.grow(xy_stride * slots, wait, true));
+    if (rows) HIP_TRY(inv->clip.rowtab.grow(rowtab_stride * slots * sizeof(float), wait));
+    // the {t, frame} table of the whole call, copied now: the caller's arrays are free when this returns
+    ClipBuffers::Table &tab = inv->clip.table[inv->clip.next_table++ & 1];
+    if (tab.pending) HIP_TRY(hipEventSynchronize(tab.uploaded));
+    tab.pending = false;
+    const size_t tab_bytes = (size_t)num_frames * sizeof(HClipFrame);
+    HIP_TRY(tab.host.grow(tab_bytes));
+    HIP_TRY(tab.dev.grow(tab_bytes, wait));
+    if (!tab.uploaded) HIP_TRY(hipEventCreateWithFlags(&tab.uploaded, hipEventDisableTiming));
+    HClipFrame *hf = (HClipFrame *)tab.host.p;
+    for (int i = 0; i < num_frames; ++i) hf[i] = HClipFrame{ts[i], frames[i]};
+    HIP_TRY(hipMemcpyAsync(tab.dev.get(), hf, tab_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(tab.uploaded, s));
+    tab.pending = true;
+
+    a.xtab = inv->launch.xtab.get<float>();
+    a.ytab = inv->launch.ytab.get<float>();
+    if (rows) a.rowtab = inv->clip.rowtab.get<float>();
+    a.ppt = geo.ppt;
+    a.tiles_magic = geo.tiles_magic;
+    char *xy = inv->clip.xy.get<char>();
+    HClip c{};
+    c.frame_stride = frame_stride;
+    c.xy_stride = per_frame ? (int)xy_stride : 0;
+    c.rowtab_stride = per_frame ? (int)rowtab_stride : 0;
+    c.nwg = (int)geo.nwg;
+    if (natives) {
+        ClipCall cc{inv, f, s, a, c, xy, geo, plan, per_frame, rows, xy_stride, frame_stride, frames, ts, stream, {}, -1};
+        cc.c.frames = tab.dev.get<HClipFrame>();
+        for (int b0 = 0; b0 < num_frames; b0 += per_batch)
+            if (clip_native_batch(cc, b0, std::min(per_batch, num_frames - b0)) != 0) return -1;
+        return 0;
+    }
+    void *params[] = {&a, &xy, &c};
+    for (int b0 = 0; b0 < num_frames; b0 += per_batch) {
+        const int n = std::min(per_batch, num_frames - b0);
+        a.out = (char *)out_device + (int64_t)b0 * frame_stride;
+        c.frames = tab.dev.get<HClipFrame>() + b0;
+        const int pro_frames = launch_clip_prologue(f, a, per_frame, rows, b0, n, params, s);
+        if (pro_frames < 0) return -1;
+        inv->clip_prologue_frames += pro_frames;
+        if (timed_pixel_launch(inv, f->f_pix_clip, (unsigned)plan.grid_x, (unsigned)n, params, s) != 0) return -1;
+        ++inv->clip_batched_launches;
+    }
+    return 0;
+}
+
+// ---- supersampled clips ----
+// How mmhip_render_clip_supersampled cuts a clip into batches.  Frames per batch: what both slices' clip launches take
+// in one launch each (clip_plan of the region_w + 1 and the region_w geometry at that many frames), at most 65 535 (the
+// combine's gridDim.y), and what MMHIP_CLIP_SS_BYTES (read once, default 2 GiB) holds of one frame's two slices.
+// per_batch 0: the loop of mmhip_render_supersampled -- filters with native calls or closure images (their nested
+// renders rely on the native memo across the two slices), and frames too large for any of the above.
+struct ClipSsPlan { int per_batch = 0; size_t bytes_per_frame = 0, long_pitch = 0; };
+static ClipSsPlan clip_ss_plan(const mmhip_filter *f, bool host_between, int region_w, int region_h, int bpp, int frames) {
+    static const size_t budget = env_bytes("MMHIP_CLIP_SS_BYTES", (size_t)2 << 30);
+    ClipSsPlan p;
+    p.long_pitch = supersample_clip_long_pitch(region_w, bpp);
+    p.bytes_per_frame = (size_t)region_h * (p.long_pitch + (size_t)region_w * bpp);
+    if (host_between || region_w == INT32_MAX || p.long_pitch > (size_t)INT32_MAX || supersample_clip_items(region_w, region_h) > INT32_MAX)
+        return p;
+    long per = (long)std::min<size_t>({(size_t)frames, (size_t)65535, budget / p.bytes_per_frame});
+    // fewer frames in a launch may mean fewer rows per work-item, more workgroups per frame and a lower cap
+    while (per > 0) {
+        const int cap = std::min(clip_plan(clip_launch_geometry(f->ks, region_w + 1, region_h, (int)per)).max_frames,
+                                 clip_plan(clip_launch_geometry(f->ks, region_w, region_h, (int)per)).max_frames);
+        if (cap >= per) break;
+        per = cap;
+    }
+    p.per_batch = (int)per;
+    return p;
+}
+
+int mmhip_filter_clip_supersample_plan(const mmhip_filter *f, int region_w, int region_h, int bpp, int frames, int64_t *out) {
+    if (frames < 1) return fail("clip supersample plan: num_frames must be at least 1");
+    if (bpp < 1 || bpp > 4) return fail("output_bpp must be 1..4");
+    if (region_w < 1 || region_h < 1) return fail("clip supersample plan: empty region");
+    const ClipSsPlan p = clip_ss_plan(f, !f->ks.natives.empty() || !f->closures.empty(), region_w, region_h, bpp, frames);
+    const int64_t v[MMHIP_CLIP_SS_PLAN_FIELDS] = {p.per_batch > 0, p.per_batch, p.per_batch ? (frames + p.per_batch - 1) / p.per_batch : 0,
+                                                  (int64_t)p.bytes_per_frame, (int64_t)p.long_pitch, SS_CLIP_ROWS, SS_CLIP_PIXELS};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+long mmhip_clip_supersampled_batches(mmhip_invocation *inv) { return inv->clip_supersampled_batches; }
+
+int mmhip_render_clip_supersampled(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int region_x,
+                                   int region_y, int region_w, int region_h, void *out_device, int row_stride,
+                                   int64_t frame_stride, int bpp, void *stream) {
+    if (check_clip_args("render_clip_supersampled", num_frames, frames, ts, bpp, region_w, region_h) != 0) return -1;
+    if (check_frame_stride("render_clip_supersampled", inv, frame_stride, region_h, region_w, row_stride, bpp, 0) != 0) return -1;
+    const bool host_between = !inv->f->ks.natives.empty() || !inv->f->closures.empty();
+    const ClipSsPlan plan = clip_ss_plan(host_between ? inv->f : active_filter(inv, frames[0], ts[0]), host_between, region_w,
+                                         region_h, bpp, num_frames);
+    if (plan.per_batch < 1) {
+        for (int i = 0; i < num_frames; ++i)
+            if (mmhip_render_supersampled(inv, frames[i], ts[i], region_x, region_y, region_w, region_h,
+                                          (char *)out_device + (int64_t)i * frame_stride, row_stride, bpp, stream) != 0)
+                return -1;
+        return 0;
+    }
+    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
+    const int per_batch = plan.per_batch;
+    const size_t long_frame = (size_t)region_h * plan.long_pitch, short_frame = (size_t)region_h * region_w * bpp;
+    // own allocation, like ss_lines; whatever still reads a smaller one has finished before it is freed
+    if (inv->clip_ss.grow((size_t)per_batch * plan.bytes_per_frame, hipDeviceSynchronize) != hipSuccess)
+        return fail("out of device memory for the supersampling slices of a clip; lower MMHIP_CLIP_SS_BYTES");
+    unsigned char *longs = inv->clip_ss.get<unsigned char>(), *shorts = longs + (size_t)per_batch * long_frame;
+    SamplingOffsetGuard offsets(inv);
+    for (int b0 = 0; b0 < num_frames; b0 += per_batch) {
+        const int n = std::min(per_batch, num_frames - b0);
+        // long slices: region_width + 1 columns at offsets -0.5, then the short ones at 0 (mmhip_render_supersampled)
+        offsets.set(-0.5f);
+        if (mmhip_render_clip(inv, n, frames + b0, ts + b0, region_x, region_y, region_w + 1, region_h, region_y, region_y + region_h,
+                              longs, (int)plan.long_pitch, (int64_t)long_frame, bpp, 0, s) != 0)
+            return -1;
+        offsets.set(0.f);
+        if (mmhip_render_clip(inv, n, frames + b0, ts + b0, region_x, region_y, region_w, region_h, region_y, region_y + region_h,
+                              shorts, region_w * bpp, (int64_t)short_frame, bpp, 0, s) != 0)
+            return -1;
+        std::string err;
+        if (launch_supersample_combine_clip(longs, shorts, (unsigned char *)out_device + (int64_t)b0 * frame_stride, region_w, region_h,
+                                            bpp, row_stride, frame_stride, n, inv->ws, s, &err) != 0)
+            return fail(err);
+        ++inv->clip_supersampled_batches;
+    }
+    return 0;
+}
+
+// ---- motion-blurred clips ----
+// How mmhip_render_clip_shutter cuts a clip into batches and a frame's sub-samples into passes (include/mmhip.h has the
+// rules).  MMHIP_CLIP_SHUTTER_BYTES is read once, default 8 GiB.
+struct ClipShutterPlan { int per_batch = 1, batches = 1, samples_per_pass = 1, passes = 1, carry = 0; size_t bytes_per_sample = 0; };
+static ClipShutterPlan clip_shutter_plan(int num_rows, int render_w, int samples, int frames) {
+    static const size_t budget = env_bytes("MMHIP_CLIP_SHUTTER_BYTES", (size_t)8 << 30);
+    ClipShutterPlan p;
+    p.bytes_per_sample = (size_t)num_rows * 16 * (size_t)render_w;
+    const size_t frame_bytes = (size_t)samples * p.bytes_per_sample;
+    if (budget >= frame_bytes) {
+        p.per_batch = (int)std::min<size_t>({budget / frame_bytes, (size_t)65535, (size_t)frames});
+        p.samples_per_pass = samples;
+    } else {
+        // not one frame's sub-samples: a frame at a time, in passes over what fits beside the carry map (at least one)
+        p.samples_per_pass = (int)std::max<long long>(1, (long long)(budget / p.bytes_per_sample) - 1);
+        p.passes = (samples + p.samples_per_pass - 1) / p.samples_per_pass;
+        p.carry = p.passes > 1;
+    }
+    p.batches = (frames + p.per_batch - 1) / p.per_batch;
+    return p;
+}
+
+static int clip_shutter_check_samples(const char *who, int samples) {
+    if (samples < 1 || samples > MMHIP_SHUTTER_MAX_SAMPLES)
+        return fail(std::string(who) + ": samples must be 1 to " + std::to_string((int)MMHIP_SHUTTER_MAX_SAMPLES) + ", not " + std::to_string(samples));
+    return 0;
+}
+
+int mmhip_filter_clip_shutter_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int samples, int frames, int64_t *out) {
+    (void)f;
+    if (frames < 1) return fail("clip shutter plan: num_frames must be at least 1");
+    if (clip_shutter_check_samples("clip shutter plan", samples) != 0) return -1;
+    if (region_w < 1 || num_rows < 1 || render_w < region_w) return fail("clip shutter plan: empty region, or one wider than the render width");
+    const ClipShutterPlan p = clip_shutter_plan(num_rows, render_w, samples, frames);
+    const int64_t v[MMHIP_CLIP_SHUTTER_PLAN_FIELDS] = {p.per_batch, p.batches, p.samples_per_pass, p.passes, (int64_t)p.bytes_per_sample, p.carry};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+long mmhip_clip_shutter_batches(mmhip_invocation *inv) { return inv->clip_shutter_batches; }
+
+int mmhip_render_clip_shutter(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
+                              int region_x, int region_y, int region_w, int region_h, int first_row, int last_row, void *out_device,
+                              int row_stride, int64_t frame_stride, int bpp, int floatmap, void *stream) {
+    if (clip_shutter_check_samples("render_clip_shutter", samples) != 0) return -1;
+    if (samples == 1)       // one instant per frame: the plain clip itself
+        return mmhip_render_clip(inv, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
+                                 row_stride, frame_stride, bpp, floatmap, stream);
+    if (!std::isfinite(span)) return fail("render_clip_shutter: span must be finite");
+    if (check_clip_args("render_clip_shutter", num_frames, frames, ts, bpp, region_w, region_h) != 0) return -1;
+    if (!clamp_rows(region_y, region_h, &first_row, &last_row)) return 0;
+    const int num_rows = last_row - first_row;
+    if (check_frame_stride("render_clip_shutter", inv, frame_stride, num_rows, region_w, row_stride, bpp, floatmap) != 0) return -1;
+    if (region_w > inv->render_w) return fail("render_clip_shutter: the region is wider than the render width");
+    const ClipShutterPlan plan = clip_shutter_plan(num_rows, inv->render_w, samples, num_frames);
+    const size_t bps = plan.bytes_per_sample;
+    if (bps > ((size_t)1 << 32)) return fail("render_clip_shutter: a sub-sample map of more than 4 GiB; render the frame in row bands");
+    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
+    // own allocation, like clip_ss; whatever still reads a smaller one has finished before it is freed
+    const size_t slots = (size_t)plan.per_batch * plan.samples_per_pass;
+    if (inv->clip_shutter.grow((slots + plan.carry) * bps, hipDeviceSynchronize) != hipSuccess)
+        return fail("out of device memory for the sub-samples of a motion-blurred clip; lower MMHIP_CLIP_SHUTTER_BYTES");
+    unsigned char *subs = inv->clip_shutter.get<unsigned char>(), *carry = plan.carry ? subs + slots * bps : nullptr;
+    const float inv_k = mm_shutter_inv_k(samples);
+    std::vector<int> sub_frames;
+    std::vector<float> sub_ts;
+    for (int b0 = 0; b0 < num_frames; b0 += plan.per_batch) {
+        const int n = std::min(plan.per_batch, num_frames - b0);
+        for (int j0 = 0; j0 < samples; j0 += plan.samples_per_pass) {
+            const int count = std::min(plan.samples_per_pass, samples - j0);
+            sub_frames.resize((size_t)n * count);
+            sub_ts.resize((size_t)n * count);
+            for (int i = 0; i < n; ++i)
+                for (int j = 0; j < count; ++j) {
+                    sub_frames[(size_t)i * count + j] = frames[b0 + i];
+                    sub_ts[(size_t)i * count + j] = mm_shutter_sample_t(ts[b0 + i], span, j0 + j, samples);
+                }
+            if (mmhip_render_clip(inv, n * count, sub_frames.data(), sub_ts.data(), region_x, region_y, region_w, region_h, first_row,
+                                  last_row, subs, row_stride, (int64_t)bps, bpp, 1, s) != 0)
+                return -1;
+            const bool last = j0 + count >= samples;
+            std::string err;
+            if (launch_shutter_combine_clip(subs, (int64_t)bps, (int64_t)count * (int64_t)bps, count, j0 > 0 ? carry : nullptr, last ? nullptr : carry,
+                                            (char *)out_device + (int64_t)b0 * frame_stride, region_w, num_rows, inv->render_w, row_stride,
+                                            frame_stride, bpp, floatmap, inv_k, n, inv->ws, s, &err) != 0)
+                return fail(err);
+        }
+        ++inv->clip_shutter_batches;
+    }
+    return 0;
+}

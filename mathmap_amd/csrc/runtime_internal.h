@@ -1,4 +1,4 @@
-// Internal definitions shared by runtime.cpp and abi_backend.cpp.
+// Internal definitions shared by runtime.cpp, runtime_clip.cpp and abi_backend.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -132,7 +132,7 @@ struct ClipBuffers {
     unsigned next_table = 0;
 };
 
-// What the native batches of a clip render keep (clip_native_batch in runtime.cpp), apart from the single-frame path's
+// What the native batches of a clip render keep (clip_native_batch in runtime_clip.cpp), apart from the single-frame path's
 // maps and workspace: checkpoints and intermediates of one call site's jobs, the maps of a batch's blurs, and the tables
 // the kernels index by frame and by job (every frame's image table, then the job tables), which go up from page-locked memory.
 struct ClipNativeBuffers {
@@ -245,3 +245,53 @@ bool mmhip_check_options(const mmhip_options *opts);
 
 // Unbinds every image-table entry that refers to `data` (a device buffer about to be freed).
 void mmhip_unbind_image(mmhip_invocation *inv, const void *data);
+
+// ---- what clip rendering (runtime_clip.cpp) uses of the single-frame path: defined, and described, in runtime.cpp ----
+inline int fail(const std::string &msg) { g_mmhip_err = msg; return -1; }
+
+#define HIP_TRY(expr)                                                                      \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// The launch geometry of a pixel kernel over `num_rows` rows of a `region_w`-wide region: the one place both launch
+// sites (mmhip_render, render_closure) and mmhip_filter_launch_geometry take it from.
+struct LaunchGeometry {
+    int tiles_x = 0, tiles_y = 0;
+    long wg1 = 0;                 // workgroups at one row per work-item: what the rows-per-item choice is made from
+    long nwg = 0;                 // workgroups of the launch
+    int ppt = 1;                  // rows per work-item (mm_args.ppt)
+    uint32_t tiles_magic = 0;     // mm_args.tiles_magic
+};
+LaunchGeometry clip_launch_geometry(const mm::KernelSource &ks, int region_w, int num_rows, int frames);
+struct ClipPlan { long grid_x = 0; int max_frames = 0; };
+ClipPlan clip_plan(const LaunchGeometry &g);
+
+mmhip_filter *active_filter(mmhip_invocation *inv, int frame = 0, float t = 0.0f);
+mm::HArgs render_args(const mmhip_invocation *inv, int frame, float t, int region_x, int region_y, int region_w, int region_h,
+                      int first_row, int last_row, void *out_device, int row_stride, int bpp, int floatmap);
+int upload_tables(mmhip_invocation *inv, hipStream_t s);
+int grow_launch_buffers(LaunchBuffers &b, const mm::KernelSource &ks, int region_w, int num_rows, bool rows, hipStream_t s);
+bool clamp_rows(int region_y, int region_h, int *first_row, int *last_row);
+int timed_pixel_launch(mmhip_invocation *inv, hipFunction_t f_pix, unsigned grid_x, unsigned grid_y, void **params, hipStream_t s);
+
+struct RecordedCall { size_t k; mm::HNativeRec rec; const std::string *func; };
+int recorded_calls(const mm::KernelSource &ks, const char *host, std::vector<RecordedCall> *calls);
+enum { NO_FRAME_KEY = INT32_MIN };
+int view_sequence_args(const mmhip_invocation *inv, int frame, const std::string &func, const mm::HNativeRec &rec,
+                       std::vector<mm::HImageDesc> &images_k, int *frame_key);
+mm::HImageDesc floatmap_desc(const void *data, int w, int h);
+void set_native_env(mmhip_invocation *inv, const mmhip_filter *f, bool gauss_tolerance);
+bool direct_output_wanted(const mmhip_filter *f, const mm::HArgs &a);
+int read_coordinate_tables(const mm::HArgs &a, hipStream_t s, std::vector<float> *xt, std::vector<float> *yt);
+bool samples_own_pixels(const mm::HArgs &a, const std::vector<float> &xt, const std::vector<float> &yt);
+
+// The invocation's sampling offsets for the length of a scope: put back on every way out.
+struct SamplingOffsetGuard {
+    mmhip_invocation *inv;
+    float ox, oy;
+    explicit SamplingOffsetGuard(mmhip_invocation *i) : inv(i), ox(i->sampling_offset_x), oy(i->sampling_offset_y) {}
+    ~SamplingOffsetGuard() { inv->sampling_offset_x = ox; inv->sampling_offset_y = oy; }
+    void set(float v) { inv->sampling_offset_x = inv->sampling_offset_y = v; }
+};

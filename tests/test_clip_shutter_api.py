@@ -311,7 +311,7 @@ def test_the_kernel_includes_the_header_the_test_compiles():
     assert '#include "mm_shutter_combine.h"' in text and "k_shutter_combine_clip" in text
     for fn in ("mm_shutter_add(", "mm_shutter_scale(", "mm_shutter_store_bytes("):
         assert fn in text, fn
-    runtime = open(os.path.join(ROOT, "mathmap_amd", "csrc", "runtime.cpp")).read()
+    runtime = open(os.path.join(ROOT, "mathmap_amd", "csrc", "runtime_clip.cpp")).read()
     assert "mm_shutter_sample_t(" in runtime and "mm_shutter_inv_k(" in runtime
     makefile = open(os.path.join(ROOT, "mathmap_amd", "csrc", "Makefile")).read()
     assert re.search(r"HIPFLAGS\s*=.*-ffp-contract=off", makefile)
