@@ -327,6 +327,48 @@ long mmhip_clip_shutter_batches(mmhip_invocation *inv);
    samples_per_pass, passes (per frame), bytes_per_sample and carry (1: a carry map joins the passes). */
 int mmhip_filter_clip_shutter_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int samples, int frames,
                                    int64_t *out);
+/* The same motion-blurred clip without the sub-sample maps (an extension, opt-in): a variant of the pixel kernel,
+   mm_pixels_shutter, evaluates the K sub-samples of an output pixel one after the other and sums them in registers.
+   The parameters are mmhip_render_clip_shutter's, and so are the bytes: float maps bit for bit, bytes at bpp 1 - 4,
+   nothing touched between rows or frames.  Asynchronous.
+     - The sub-sample times, the order of the sum and the product with inv_k are those stated above (the JIT compiles
+       without fma contraction); RAND's call counter starts at 0 in every sub-sample, as in a render of its own.
+     - samples = 1 is mmhip_render_clip: the call delegates before anything else.  The 4 GiB limit of a sub-sample
+       map does not apply: there is none, and no temporary is allocated.
+     - Fused are filters without native calls and without closure images whose frame fits one launch (a batch of at
+       least one frame, below).  For every other filter the call is mmhip_render_clip_shutter: nothing is refused, and
+       mmhip_clip_shutter_fused_batches stays where it was.  The variant that renders (the filter, or its specialised
+       variant for the current user values) has a shutter module of its own, built on the first such call.
+     - mm_pixels_shutter always has the single-pixel shape (one pixel per work-item, the generic fetch) whatever the
+       shape of the filter's pixel kernel: no pair mode, no unrolled hot fetch.
+     - Per batch of B output frames: the {t, frame} table of all num_frames * K sub-samples goes up once per call; one
+       launch of mm_prologue_clip (and mm_rows_clip) over the batch's B * K slots -- one slot for the whole call where the
+       frame constants read neither t nor frame --, one launch of mm_pixels_shutter over (grid_x, B).
+     - B is the largest value with B * K <= 65 535, B * K <= MMHIP_CLIP_MAX_FRAMES (read once), grid_x * B * 256 < 2^31,
+       B <= num_frames and, where slots are per sub-sample, B * K slots of frame constants (and of row-table floats)
+       within INT32_MAX.  grid_x is the workgroups of the region at one row per work-item, rounded up to a multiple of 8.
+     - mmhip_clip_shutter_fused_batches rises by one per batch and mmhip_clip_prologue_frames by the slots launched;
+       mmhip_clip_batched_launches, mmhip_clip_shutter_batches and the native counters do not move.  With
+       mmhip_enable_timing, mmhip_drain_kernel_ms reports one entry per batch.
+   Errors: those of mmhip_render_clip_shutter but the 4 GiB one, under the name render_clip_shutter_fused. */
+int mmhip_render_clip_shutter_fused(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples,
+                                    float span, int region_x, int region_y, int region_w, int region_h, int first_row,
+                                    int last_row, void *out_device, int row_stride, int64_t frame_stride, int bpp, int floatmap,
+                                    void *stream);
+long mmhip_clip_shutter_fused_batches(mmhip_invocation *inv);
+/* How mmhip_render_clip_shutter_fused renders `frames` frames of num_rows rows of a region_w-wide region with `samples`
+   sub-samples (needs no GPU).  out[] receives MMHIP_CLIP_SHUTTER_FUSED_PLAN_FIELDS values: fused (0: the call is
+   mmhip_render_clip_shutter, and the other fields but grid_x are 0), frames_per_batch (B), batches, slots_per_batch (B * K,
+   or 1 where one slot serves the whole call) and grid_x. */
+enum { MMHIP_CLIP_SHUTTER_FUSED_PLAN_FIELDS = 5 };
+int mmhip_filter_clip_shutter_fused_plan(const mmhip_filter *f, int region_w, int num_rows, int samples, int frames, int64_t *out);
+/* The shutter variant of the module -- mm_prologue_clip and mm_rows_clip as in the clip variant, and mm_pixels_shutter --
+   and its gfx950 compile (like mmhip_filter_jit_clip; load_module = 0 needs no GPU).  Generated from the filter's code
+   when first asked for, cached on the filter and on disk under its own key; the texts of mmhip_filter_kernel_source and
+   mmhip_filter_clip_kernel_source stay what they were.  A filter with native calls or closure images has none: NULL and
+   -1, with a message. */
+const char *mmhip_filter_shutter_kernel_source(mmhip_filter *f);
+long mmhip_filter_jit_shutter(mmhip_filter *f, int load_module);
 /* Convenience: whole frame to a host RGBA8 buffer (width*height*4 bytes); synchronous. */
 int mmhip_render_host(mmhip_invocation *inv, int frame, float t, uint8_t *out_rgba);
 int mmhip_sync(mmhip_invocation *inv);

@@ -31,6 +31,10 @@ CLIP_SS_PLAN_FIELDS = ("batched", "frames_per_batch", "batches", "bytes_per_fram
 # mmhip_filter_clip_shutter_plan's out[]
 CLIP_SHUTTER_PLAN_FIELDS = ("frames_per_batch", "batches", "samples_per_pass", "passes", "bytes_per_sample", "carry")
 SHUTTER_MAX_SAMPLES = 256
+# mmhip_filter_clip_shutter_fused_plan's out[]
+CLIP_SHUTTER_FUSED_PLAN_FIELDS = ("fused", "frames_per_batch", "batches", "slots_per_batch", "grid_x")
+# render_clip's shutter_mode: the sub-sample maps of mmhip_render_clip_shutter, or mmhip_render_clip_shutter_fused
+SHUTTER_MODES = ("maps", "fused")
 
 
 class MathMapError(RuntimeError):
@@ -231,6 +235,30 @@ class Filter:
         if lib().mmhip_filter_clip_shutter_plan(self._h, region_w, num_rows, render_w, samples, frames, out) != 0:
             raise MathMapError(_err())
         return dict(zip(CLIP_SHUTTER_PLAN_FIELDS, out))
+
+    def clip_shutter_fused_plan(self, region_w, num_rows, samples, frames):
+        """How render_clip(shutter_samples=samples, shutter_mode="fused") renders a `frames`-frame clip of num_rows rows of
+        a region_w-wide region: a dict of the CLIP_SHUTTER_FUSED_PLAN_FIELDS (fused 0: the filter takes the maps path)."""
+        out = (C.c_int64 * len(CLIP_SHUTTER_FUSED_PLAN_FIELDS))()
+        if lib().mmhip_filter_clip_shutter_fused_plan(self._h, region_w, num_rows, samples, frames, out) != 0:
+            raise MathMapError(_err())
+        return dict(zip(CLIP_SHUTTER_FUSED_PLAN_FIELDS, out))
+
+    @property
+    def shutter_kernel_source(self):
+        """The shutter variant of kernel_source: kernels mm_prologue_clip, mm_rows_clip, mm_pixels_shutter.  A filter with
+        native calls or closure images has none: MathMapError."""
+        text = lib().mmhip_filter_shutter_kernel_source(self._h)
+        if text is None:
+            raise MathMapError(_err())
+        return text.decode()
+
+    def jit_shutter(self, load=False):
+        """hiprtc-compiles the shutter variant for gfx950; returns the code-object size."""
+        n = lib().mmhip_filter_jit_shutter(self._h, 1 if load else 0)
+        if n < 0:
+            raise MathMapError(_err())
+        return n
 
     def clip_supersample_plan(self, region_w, region_h, frames, bpp=4):
         """How render_clip(supersample=True) renders a `frames`-frame clip of a region: a dict of the CLIP_SS_PLAN_FIELDS
@@ -434,7 +462,7 @@ class Invocation:
 
     def render_clip(self, num_frames=None, frames=None, ts=None, out_ptr=None, rows=None, region=None, row_stride=None,
                     frame_stride=None, bpp=4, floatmap=False, stream=0, supersample=False, shutter_samples=1, shutter_span=None,
-                    shutter=None):
+                    shutter=None, shutter_mode="maps"):
         """Renders a clip in batched launches (mmhip_render_clip): frame i at frame number frames[i] and time ts[i].
         `num_frames`=N alone is the CLI's animation: frame = i, t = (float)i / (float)N.  `rows` = (first_row,
         last_row) and `region`, `row_stride`, `bpp`, `floatmap`, `stream` as in render_rows; frame i lands
@@ -447,8 +475,14 @@ class Invocation:
         sub-samples at frame number frames[i] and the times shutter_sample_ts(ts, K, span).  The span is `shutter_span`
         in units of t, or `shutter`, a fraction of the frame interval, in the `num_frames`=N form only: span =
         float32(float64(shutter) / N).  Giving both, `shutter` with explicit ts, K > 1 without either, or K > 1 with
-        `supersample` is a ValueError."""
+        `supersample` is a ValueError.
+        `shutter_mode`: "maps" (default) renders the sub-samples as float maps and averages them, "fused" sums them in the
+        pixel kernel's registers (mmhip_render_clip_shutter_fused): the same bytes; filters with native calls or closure
+        images take the maps path under either.  Any other value is a ValueError."""
         from .striping import animation_frame_t
+        if shutter_mode not in SHUTTER_MODES:
+            raise ValueError("render_clip: shutter_mode must be one of %s, not %r" % (", ".join(SHUTTER_MODES), shutter_mode))
+        render_shutter = lib().mmhip_render_clip_shutter_fused if shutter_mode == "fused" else lib().mmhip_render_clip_shutter
         if supersample and (floatmap or rows is not None):
             raise ValueError("render_clip: supersample=True renders whole regions of bytes: neither floatmap nor rows")
         shutter_samples = int(shutter_samples)
@@ -491,9 +525,9 @@ class Invocation:
                 n_rows = max(min(last_row, ry + rh) - max(first_row, 0), 0)
                 frame_stride = n_rows * (16 * self.render_width if floatmap else row_stride)
             if shuttered:
-                self._check(lib().mmhip_render_clip_shutter(self._h, num_frames, fp, tp, shutter_samples, span, rx, ry, rw, rh, first_row,
-                                                            last_row, C.c_void_p(out_ptr), row_stride, frame_stride, bpp,
-                                                            1 if floatmap else 0, C.c_void_p(stream)))
+                self._check(render_shutter(self._h, num_frames, fp, tp, shutter_samples, span, rx, ry, rw, rh, first_row,
+                                           last_row, C.c_void_p(out_ptr), row_stride, frame_stride, bpp,
+                                           1 if floatmap else 0, C.c_void_p(stream)))
                 return None
             self._check(lib().mmhip_render_clip(self._h, num_frames, fp, tp, rx, ry, rw, rh, first_row, last_row,
                                                 C.c_void_p(out_ptr), row_stride, frame_stride, bpp, 1 if floatmap else 0,
@@ -509,8 +543,8 @@ class Invocation:
             raise MathMapError(_err())
         try:
             if shuttered:
-                self._check(lib().mmhip_render_clip_shutter(self._h, num_frames, fp, tp, shutter_samples, span, rx, ry, rw, rh, first_row,
-                                                            last_row, C.c_void_p(dev), rw * 4, rw * 4 * rh, 4, 0, None))
+                self._check(render_shutter(self._h, num_frames, fp, tp, shutter_samples, span, rx, ry, rw, rh, first_row,
+                                           last_row, C.c_void_p(dev), rw * 4, rw * 4 * rh, 4, 0, None))
             else:
                 self._check(lib().mmhip_render_clip(self._h, num_frames, fp, tp, rx, ry, rw, rh, first_row, last_row,
                                                     C.c_void_p(dev), rw * 4, rw * 4 * rh, 4, 0, None))
@@ -550,6 +584,10 @@ class Invocation:
     def clip_shutter_batches(self):
         """Batches of motion-blurred frames render_clip(shutter_samples > 1) has combined so far."""
         return lib().mmhip_clip_shutter_batches(self._h)
+
+    def clip_shutter_fused_batches(self):
+        """Batches render_clip(shutter_samples > 1, shutter_mode="fused") rendered fused (0 for filters that take the maps path)."""
+        return lib().mmhip_clip_shutter_fused_batches(self._h)
 
     def clip_supersampled_batches(self):
         """Batches render_clip(supersample=True) ran batched (0 for filters it renders frame by frame)."""

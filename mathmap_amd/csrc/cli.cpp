@@ -70,6 +70,9 @@ void usage() {
            "      --shutter=FRACTION      the shutter time as a fraction of the frame\n"
            "                              interval (default 0.5): sub-sample j is rendered\n"
            "                              at t = frame/NUM + FRACTION/NUM * j/K\n"
+           "      --shutter-mode=MODE     how the K renders are averaged: maps (default,\n"
+           "                              float maps in device memory) or fused (summed in\n"
+           "                              the pixel kernel); the files are the same\n"
            "\n"
            "Report bugs and suggestions to schani@complang.tuwien.ac.at\n",
            cache_size);
@@ -217,7 +220,7 @@ std::string frame_file(const std::string &pattern, int frame) {
 enum {
     OPT_VERSION = 256, OPT_HELP, OPT_HTMLDOC, OPT_BENCH_NO_OUTPUT, OPT_BENCH_ONLY_COMPILE,
     OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE, OPT_INPUT_FRAMES, OPT_BATCH_FRAMES,
-    OPT_NATIVE_INPUT_FRAME, OPT_SHUTTER_SAMPLES, OPT_SHUTTER
+    OPT_NATIVE_INPUT_FRAME, OPT_SHUTTER_SAMPLES, OPT_SHUTTER, OPT_SHUTTER_MODE
 };
 
 int main(int argc, char **argv) {
@@ -227,6 +230,7 @@ int main(int argc, char **argv) {
     int bench_render_count = 1, num_frames = 1, input_frames = 0, gauss_mode = MMHIP_GAUSS_EXACT, batch_frames = 1;
     int native_input_frame = MMHIP_NATIVE_FRAME_ZERO, shutter_samples = 1;
     double shutter = 0.5;
+    bool shutter_fused = false;
     const char *generator = nullptr;
     std::vector<Define> defines;
     static struct option long_options[] = {
@@ -243,6 +247,7 @@ int main(int argc, char **argv) {
         {"input-frames", required_argument, 0, OPT_INPUT_FRAMES}, {"batch-frames", required_argument, 0, OPT_BATCH_FRAMES},
         {"native-input-frame", required_argument, 0, OPT_NATIVE_INPUT_FRAME},
         {"shutter-samples", required_argument, 0, OPT_SHUTTER_SAMPLES}, {"shutter", required_argument, 0, OPT_SHUTTER},
+        {"shutter-mode", required_argument, 0, OPT_SHUTTER_MODE},
         {0, 0, 0, 0}};
     for (;;) {
         int idx;
@@ -318,6 +323,11 @@ int main(int argc, char **argv) {
                 shutter_samples = (int)n;
                 break;
             }
+            case OPT_SHUTTER_MODE:
+                if (!strcmp(optarg, "maps")) shutter_fused = false;
+                else if (!strcmp(optarg, "fused")) shutter_fused = true;
+                else { fprintf(stderr, "Error: --shutter-mode takes maps or fused.\n"); return 1; }
+                break;
             case OPT_SHUTTER: {
                 char *end = nullptr;
                 shutter = strtod(optarg, &end);
@@ -450,7 +460,7 @@ int main(int argc, char **argv) {
     };
     // --batch-frames=K: K frames per clip render (one batched launch where the filter allows it), then the files one by
     // one; a batch's frames stay under 1 GiB of device memory.  With -o the clip is a supersampled one.
-    // --shutter-samples=K: the frames go through mmhip_render_clip_shutter, --batch-frames of them per call (by default
+    // --shutter-samples=K: the frames go through mmhip_render_clip_shutter (--shutter-mode=fused: ..._fused), --batch-frames of them per call (by default
     // one, all of its K sub-samples in one nested clip), at the span (float)((double)FRACTION / NUM).
     const bool shuttered = shutter_samples > 1;
     const float shutter_span = (float)(shutter / (double)num_frames);
@@ -467,8 +477,9 @@ int main(int argc, char **argv) {
                 ts[i] = (float)(first + i) / (float)num_frames;       // mathmap_cmdline.c:835
             }
             const int rc = shuttered
-                               ? mmhip_render_clip_shutter(inv, n, frames.data(), ts.data(), shutter_samples, shutter_span, 0, 0, img_width,
-                                                           img_height, 0, img_height, dev, img_width * 4, (int64_t)output.size(), 4, 0, nullptr)
+                               ? (shutter_fused ? mmhip_render_clip_shutter_fused : mmhip_render_clip_shutter)(
+                                     inv, n, frames.data(), ts.data(), shutter_samples, shutter_span, 0, 0, img_width, img_height, 0, img_height,
+                                     dev, img_width * 4, (int64_t)output.size(), 4, 0, nullptr)
                            : supersampling
                                ? mmhip_render_clip_supersampled(inv, n, frames.data(), ts.data(), 0, 0, img_width, img_height, dev,
                                                                 img_width * 4, (int64_t)output.size(), 4, nullptr)

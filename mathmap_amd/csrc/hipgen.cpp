@@ -16,6 +16,11 @@
 //       pair mode    : loop shape for small arithmetic-only bodies -- two vertically adjacent pixels as
 //                      pairs of values in lockstep (two interleaved instruction streams), hipgen_pair.cpp
 //
+// Two more modules are made of the same statements: the clip variant (mm_*_clip: this text with the kernels' heads
+// replaced, clip_kernel_source) and, generated on demand under KernelOptions::shutter, the shutter variant -- the clip
+// forms of the prologue and the per-row slice, and mm_pixels_shutter: the single shape's body in a loop over a pixel's
+// sub-samples (emit_shutter_pixel_kernel).
+//
 // The environment hooks for experiments that alter this text are the fields of struct Knobs (hipgen_internal.h).
 //
 // Statement printing follows the reference's backends/cc.c:192-397 (one C variable
@@ -682,6 +687,19 @@ struct Generator {
     }
     void find_row_slice() {
         if (fn_root || in_function || knobs.no_row_slice) return;
+        if (opt.shutter) {
+            // the second generation from this code: the slice is what the first run marked (it moved those statements
+            // out of the pixel slice, so the search below would not find them again), its table in the same order
+            std::vector<Value *> defs;
+            std::set<Value *> used;
+            collect_values(code.body, PIXEL, defs, used);
+            for (int i = 0; i < 4; ++i) used.insert(code.result[i]);
+            for (Stmt *s : code.body)
+                if (s->kind == Stmt::Assign && s->in_row && used.count(s->lhs)) row_transfer.push_back(s->lhs);
+            ks.row_values = (int)row_transfer.size();
+            if (ks.row_values > 0) ks.rows_name = "mm_rows";
+            return;
+        }
         std::vector<Stmt *> cand;
         std::set<const Value *> rows;
         auto operand_ok = [&](const Primary &p) {
@@ -740,10 +758,10 @@ struct Generator {
         ks.rows_name = "mm_rows";
     }
     // the frame constants a kernel reads, from where the prologue left them (`only`: those of them that it uses)
-    void transfer_loads(const std::set<Value *> *only) {
+    void transfer_loads(const std::set<Value *> *only, const char *ind = "  ") {
         for (Value *v : transfer_order)
             if (!only || only->count(v))
-                out << "  const " << ctype(v->var) << " " << vname(v) << " = *(const " << ctype(v->var) << " *)(XY + " << transfer_off[v] << ");\n";
+                out << ind << "const " << ctype(v->var) << " " << vname(v) << " = *(const " << ctype(v->var) << " *)(XY + " << transfer_off[v] << ");\n";
     }
     // the row values a pixel of row `row` needs, from the table mm_rows filled
     void row_loads(const std::string &ind, const char *row) {
@@ -821,8 +839,15 @@ struct Generator {
         if (pair) pair->emit_helpers();
         emit_prologue_kernel();
         if (ks.row_values > 0) emit_rows_kernel();
-        emit_pixel_kernel();
+        if (opt.shutter) emit_shutter_pixel_kernel();
+        else emit_pixel_kernel();
         ks.source = out.str();
+        if (opt.shutter) {      // the prologue and the per-row slice in their clip form; the pixel kernel has no other
+            std::string text, key;
+            clip_kernel_source(ks, &text, &key);
+            ks.source = std::move(text);
+            ks.clip_splices.clear();
+        }
         ks.key = text_key(ks.source);
         ks.wrapping_ints = opt.edge_x >= 2 || opt.edge_y >= 2;      // REFLECT, ROTATE (KernelSource::wrapping_ints)
     }
@@ -860,7 +885,8 @@ struct Generator {
         out << "#define MM_TILE_W " << ks.tile_w << "\n#define MM_TILE_H " << ks.tile_h << "\n";
         ks.unroll = opt.unroll > 0 ? opt.unroll : auto_unroll();
         // pair mode (row values are per pixel of a pair; a native call is not arithmetic)
-        if (opt.unroll <= 0 && !knobs.unroll && ks.row_values == 0 && ks.natives.empty())
+        if (opt.shutter) ks.unroll = 1;      // (single-pixel shape, general fetch: emit_shutter_pixel_kernel)
+        else if (opt.unroll <= 0 && !knobs.unroll && ks.row_values == 0 && ks.natives.empty())
             pair = make_pair_mode(PairEnv{out, code, opt, knobs, pix_defs, pixel_stmts, pixel_fetches,
                                           [this](const Primary &p) { return prim(p, PIXEL); },
                                           [this](const Stmt *s) { return rhs(s->rhs, PIXEL, s, s->lhs->var); },
@@ -1046,13 +1072,29 @@ MM_DEV mm_image mm_native_result_in_loop(const mm_args &A, int &n, int sites) {
         emit(KERNEL + "mm_pixels(mm_args A, const char *__restrict__ XY) {\n",
              KERNEL + "mm_pixels_clip(mm_args A, const char *__restrict__ XY, const mm_clip C) {\n"
                       "  if ((int)blockIdx.x >= C.nwg) return;      // padding workgroup\n  MM_CLIP_ENTRY\n");
-        out << R"(  MM_INTERNALS
-  // XCD-aware tile order (MM_XCD_ORDER, above): workgroups are dealt round-robin to the 8 XCDs; give each
+        out << "  MM_INTERNALS\n";
+        emit_tile_order(true);
+        transfer_loads(nullptr);
+        // Large bodies keep the one-pixel-per-work-item shape: a pixel loop makes every frame
+        // constant live across it in SGPRs (after the loop's first store the compiler may not
+        // re-issue scalar loads), and Droste's ~60 of them spilled to VGPR lanes -- 1.7x slower.
+        // Such kernels are compute-bound; the per-workgroup dispatch cost does not show.
+        ks.single_pixel = knobs.single_pixel ? *knobs.single_pixel != 0 : pixel_stmts > 400 || transfer_order.size() > 24;
+        if (ks.single_pixel) emit_single_pixel();
+        else emit_pixel_loops();
+    }
+
+    // from the workgroup to its tile, column and first row (`both`: the text of mm_pixels and, as splices, of mm_pixels_clip;
+    // else the clip form alone)
+    void emit_tile_order(bool both) {
+        out << R"(  // XCD-aware tile order (MM_XCD_ORDER, above): workgroups are dealt round-robin to the 8 XCDs; give each
   // XCD one contiguous band of tiles so neighbouring gathers share its L2 -- or, for a kernel that reads nothing,
   // take the tiles in dispatch order so that cheap and expensive regions of the frame are spread over all XCDs.
   const int tiles_x = (A.region_width + MM_TILE_W - 1) / MM_TILE_W;
 )";
-        emit("  const int nwg = gridDim.x;\n", "  const int nwg = C.nwg;      // the frame's workgroups (gridDim.x is padded)\n");
+        const char *clip_nwg = "  const int nwg = C.nwg;      // the frame's workgroups (gridDim.x is padded)\n";
+        if (both) emit("  const int nwg = gridDim.x;\n", clip_nwg);
+        else out << clip_nwg;
         out << R"(  const int bid = blockIdx.x;
 #if MM_XCD_ORDER == 1
   const int xcd = bid & 7, q = bid >> 3;
@@ -1079,14 +1121,6 @@ MM_DEV mm_image mm_native_result_in_loop(const mm_args &A, int &n, int sites) {
   const float x = A.xtab[col];   // CALC_VIRTUAL_X(col + region_x, ...), once per column
   (void)x;
 )";
-        transfer_loads(nullptr);
-        // Large bodies keep the one-pixel-per-work-item shape: a pixel loop makes every frame
-        // constant live across it in SGPRs (after the loop's first store the compiler may not
-        // re-issue scalar loads), and Droste's ~60 of them spilled to VGPR lanes -- 1.7x slower.
-        // Such kernels are compute-bound; the per-workgroup dispatch cost does not show.
-        ks.single_pixel = knobs.single_pixel ? *knobs.single_pixel != 0 : pixel_stmts > 400 || transfer_order.size() > 24;
-        if (ks.single_pixel) emit_single_pixel();
-        else emit_pixel_loops();
     }
 
     // single shape: one pixel per work-item
@@ -1106,6 +1140,56 @@ MM_DEV mm_image mm_native_result_in_loop(const mm_args &A, int &n, int sites) {
         out << "  mm_tup<4> rt;\n";
         for (int i = 0; i < 4; ++i) out << "  rt.v[" << i << "] = " << prim(Primary::V(code.result[i]), PIXEL) << ";\n";
         out << "  mm_store_pixel(A, rl, col, rt);\n}\n";
+    }
+
+    // ---- the shutter variant's pixel kernel (KernelOptions::shutter) ----
+    // One work-item per output pixel of grid row fi, the single shape's body in a loop over the pixel's S.samples
+    // sub-samples: sub-sample j is slot fi * S.samples + j of the batch -- its {t, frame} entry, its frame constants and
+    // its row table, as mm_prologue_clip and mm_rows_clip left them.  What is summed is what mm_store_pixel would have
+    // been handed for the sub-sample's float map; the sum's order and the product are mmhip_render_clip_shutter's.
+    void emit_shutter_pixel_kernel() {
+        if (!ks.natives.empty()) throw CompileError("the shutter variant is for filters without native calls");
+        ks.single_pixel = true;
+        ks.pair_mode = false;
+        ks.pixel_name = "mm_pixels_shutter";
+        out << shutter_prelude();
+        if (knobs.waves_per_eu) out << "__attribute__((amdgpu_waves_per_eu(" << *knobs.waves_per_eu << "))) ";
+        out << KERNEL
+            << "mm_pixels_shutter(mm_args A, const char *__restrict__ XY, const mm_clip C, const mm_shutter S) {\n"
+               "  if ((int)blockIdx.x >= C.nwg) return;      // padding workgroup\n"
+               "  const int fi = blockIdx.y;                 // the output frame\n"
+               "  A.out = (char *)A.out + (long long)fi * C.frame_stride;\n";
+        emit_tile_order(false);
+        out << "  const int rl = row0;   // A.ppt is 1 for this kernel\n"
+               "  if (rl >= A.num_rows) return;\n"
+               "  const float y = A.ytab[rl];    // CALC_VIRTUAL_Y(first_row + rl, ...), once per row by the prologue\n"
+               "  (void)y;\n"
+               "  const char *const mm_xy0 = XY;\n"
+               "  float *const mm_rowtab0 = A.rowtab;\n"
+               "  mm_tup<4> mm_acc;\n"
+               "  mm_acc.v[0] = mm_acc.v[1] = mm_acc.v[2] = mm_acc.v[3] = 0.0f;\n"
+               "#pragma unroll 1\n"
+               "  for (int mm_j = 0; mm_j < S.samples; ++mm_j) {\n"
+               "    const long long mm_slot = (long long)fi * S.samples + mm_j;\n"
+               "    { const mm_clip_frame mm_cf = C.frames[mm_slot]; A.t = mm_cf.t; A.frame = mm_cf.frame; }\n"
+               "    const char *__restrict__ XY = mm_xy0 + mm_slot * C.xy_stride;\n"
+               "    if (mm_rowtab0) A.rowtab = mm_rowtab0 + mm_slot * C.rowtab_stride;\n"
+               "    MM_INTERNALS\n"
+               "    unsigned mm_rand_ctr = 0;      // RAND call number within this pixel: every sub-sample is a render of its own\n"
+               "    (void)XY; (void)mm_rand_ctr;\n";
+        transfer_loads(nullptr, "    ");
+        row_loads("    ", "rl");
+        decls(pix_defs, "    ");
+        stmts(code.body, PIXEL, "    ");
+        out << "    mm_tup<4> rt;\n";
+        for (int i = 0; i < 4; ++i) out << "    rt.v[" << i << "] = " << prim(Primary::V(code.result[i]), PIXEL) << ";\n";
+        out << "    if (mm_j == 0) mm_acc = rt;\n"
+               "    else\n"
+               "      for (int mm_c = 0; mm_c < 4; ++mm_c) mm_acc.v[mm_c] = mm_acc.v[mm_c] + rt.v[mm_c];\n"
+               "  }\n"
+               "  mm_tup<4> mm_m;\n"
+               "  for (int mm_c = 0; mm_c < 4; ++mm_c) mm_m.v[mm_c] = mm_acc.v[mm_c] * S.inv_k;\n"
+               "  mm_store_pixel(A, rl, col, mm_m);\n}\n";
     }
 
     // loop shape: A.ppt rows per work-item, MM_UNROLL of them per step
@@ -1232,6 +1316,9 @@ const char *clip_prelude_natives() {
            "  if (A.rowtab) A.rowtab += (long long)fi * C.rowtab_stride; \\\n"
            "  A.images += (long long)fi * C.images_stride;\n";
 }
+
+// What mm_pixels_shutter has besides mm_args and mm_clip: the sub-samples of an output pixel and (float)(1.0 / samples).
+const char *shutter_prelude() { return "struct mm_shutter { int samples; float inv_k; };\n"; }
 
 void clip_kernel_source(const KernelSource &ks, std::string *source, std::string *key) {
     source->clear();

@@ -17,6 +17,11 @@ struct KernelOptions {
     int unroll = 0;           // pixels evaluated back to back per work-item step; 0 = choose (hipgen.cpp auto_unroll)
     bool hoist = true;        // evaluate frame-constant code once per frame in a prologue kernel
     bool fast_math_exact = true;   // use f32 paths only where bit-identical to the double path
+    // The shutter variant of the module (fused motion blur): mm_prologue_clip and mm_rows_clip as the clip variant has
+    // them, and mm_pixels_shutter in place of the pixel kernel -- single-pixel shape, the pixel body in a loop over a
+    // pixel's sub-samples, their sum in registers.  Generated a second time from the code `source` was generated from
+    // (the row slice is taken as that run left it); filters without native calls only.
+    bool shutter = false;
 };
 
 // One native-filter (or render) call found in the frame-constant code.
@@ -73,6 +78,7 @@ bool pair_peel_enabled();
 void clip_kernel_source(const KernelSource &ks, std::string *source, std::string *key);
 const char *clip_prelude();
 const char *clip_prelude_natives();   // ... of a filter with native-filter calls: mm_clip.images_stride
+const char *shutter_prelude();        // mm_shutter, behind clip_prelude() in the shutter variant (KernelOptions::shutter)
 const char *device_prelude();
 const char *device_noise_prelude();   // mm_noise_device.h
 const char *device_fastmath_prelude();   // mm_fastmath.h + tables

@@ -187,6 +187,7 @@ void mmhip_filter_free(mmhip_filter *f) {
     for (mmhip_closure_kernel &ck : f->closures) if (ck.mod) (void)hipModuleUnload(ck.mod);
     if (f->mod) (void)hipModuleUnload(f->mod);
     if (f->clip_mod) (void)hipModuleUnload(f->clip_mod);
+    if (f->shutter_mod) (void)hipModuleUnload(f->shutter_mod);
     delete f;
 }
 
@@ -343,6 +344,48 @@ long mmhip_filter_jit_clip(mmhip_filter *f, int load_module) {
     }
     f->jit_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return (long)f->clip_code_object.size();
+}
+
+// The shutter variant's text (hipgen.h KernelOptions::shutter), generated from the retained code when it is first asked
+// for; null, with the message, for a filter that has none.  The main and the clip text are stored strings: not touched.
+static const mm::KernelSource *shutter_source(mmhip_filter *f) {
+    if (!f->shutter_ks.source.empty()) return &f->shutter_ks;
+    if (!f->ks.natives.empty() || !f->closures.empty()) {
+        fail("filter `" + f->module.main->name + "' has no shutter variant: it calls native filters or renders closure images");
+        return nullptr;
+    }
+    if (!f->code) { fail("filter has no shutter variant: its code was not kept"); return nullptr; }
+    try {
+        KernelOptions ko = f->kopt;
+        ko.shutter = true;
+        f->shutter_ks = generate_hip(*f->code, ko);
+    } catch (const std::exception &e) {
+        f->shutter_ks = mm::KernelSource();
+        fail(e.what());
+        return nullptr;
+    }
+    f->shutter_ks.prologue_name = "mm_prologue_clip";
+    f->shutter_ks.rows_name = "mm_rows_clip";
+    return &f->shutter_ks;
+}
+
+const char *mmhip_filter_shutter_kernel_source(mmhip_filter *f) {
+    const mm::KernelSource *ks = shutter_source(f);
+    return ks ? ks->source.c_str() : nullptr;
+}
+
+long mmhip_filter_jit_shutter(mmhip_filter *f, int load_module) {
+    auto t0 = std::chrono::steady_clock::now();
+    const mm::KernelSource *ks = shutter_source(f);
+    if (!ks || jit_source(*ks, f->shutter_code_object) != 0) return -1;
+    if (load_module && !f->shutter_loaded) {
+        if (load_kernels(*ks, f->shutter_code_object, &f->shutter_mod, &f->f_pix_shutter, &f->f_pro_shutter,
+                         ks->row_values > 0 ? &f->f_rows_shutter : nullptr) != 0)
+            return -1;
+        f->shutter_loaded = true;
+    }
+    f->jit_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return (long)f->shutter_code_object.size();
 }
 
 // ---------------------------------------------------------------------------
@@ -792,8 +835,19 @@ ClipPlan clip_plan(const LaunchGeometry &g) {
     ClipPlan p;
     p.grid_x = (g.nwg + 7) / 8 * 8;
     const long by_items = ((1L << 23) - 1) / p.grid_x;      // grid_x * frames * 256 < 2^31
-    p.max_frames = (int)std::min<long>(std::min(65535, env_cap), by_items);
+    p.max_grid_rows = std::min(65535, env_cap);
+    p.max_rows_by_items = by_items;
+    p.max_frames = (int)std::min<long>(p.max_grid_rows, by_items);
     return p;
+}
+
+LaunchGeometry single_pixel_launch_geometry(const KernelSource &ks, int region_w, int num_rows) {
+    KernelSource single;
+    single.tile_w = ks.tile_w;
+    single.tile_h = ks.tile_h;
+    single.unroll = 1;
+    single.single_pixel = true;
+    return launch_geometry(single, region_w, num_rows);
 }
 
 static int geometry_out(const KernelSource &ks, int region_w, int num_rows, int64_t *out, int clip_frames = 0) {

@@ -1,6 +1,7 @@
 // Clip rendering: the frames of an animation in batched launches (mmhip_render_clip), supersampled
-// (mmhip_render_clip_supersampled) and motion-blurred (mmhip_render_clip_shutter), on top of the single-frame path of
-// runtime.cpp.  (The exported functions have C linkage from include/mmhip.h.)
+// (mmhip_render_clip_supersampled) and motion-blurred (mmhip_render_clip_shutter through sub-sample maps,
+// mmhip_render_clip_shutter_fused in the pixel kernel's registers), on top of the single-frame path of runtime.cpp.
+// (The exported functions have C linkage from include/mmhip.h.)
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -112,14 +113,36 @@ struct ClipCall {
 
 // Frame constants (and the per-row slice) of frames [b0, b0 + n): one grid row per frame -- or, where they do not depend on
 // t and frame (!per_frame), frame 0's once for the whole call.  Returns the frames they were launched for, or -1.
-static int launch_clip_prologue(const mmhip_filter *f, const HArgs &a, bool per_frame, bool rows, int b0, int n, void **params, hipStream_t s) {
+// (f_pro, f_rows: mm_prologue_clip and, where the filter has a per-row slice, mm_rows_clip of the module that is launched)
+static int launch_clip_prologue(hipFunction_t f_pro, hipFunction_t f_rows, const HArgs &a, bool per_frame, int b0, int n, void **params, hipStream_t s) {
     const unsigned pro_x = (unsigned)((std::max(a.region_width, a.num_rows) + 255) / 256), rows_x = (unsigned)((a.num_rows + 255) / 256);
     const unsigned pro_frames = per_frame ? (unsigned)n : b0 == 0 ? 1u : 0u;
     if (pro_frames) {
-        HIP_TRY(hipModuleLaunchKernel(f->f_pro_clip, pro_x, pro_frames, 1, 256, 1, 1, 0, s, params, nullptr));
-        if (rows) HIP_TRY(hipModuleLaunchKernel(f->f_rows_clip, rows_x, pro_frames, 1, 256, 1, 1, 0, s, params, nullptr));
+        HIP_TRY(hipModuleLaunchKernel(f_pro, pro_x, pro_frames, 1, 256, 1, 1, 0, s, params, nullptr));
+        if (f_rows) HIP_TRY(hipModuleLaunchKernel(f_rows, rows_x, pro_frames, 1, 256, 1, 1, 0, s, params, nullptr));
     }
     return (int)pro_frames;
+}
+
+// The {t, frame} table of a whole call, `entries` of them: the next of the invocation's two tables, free to be written
+// at its host side when this returns; send_clip_table then copies it up.  The caller's arrays are free after that.
+static int next_clip_table(mmhip_invocation *inv, size_t entries, hipStream_t s, ClipBuffers::Table **out) {
+    ClipBuffers::Table &tab = inv->clip.table[inv->clip.next_table++ & 1];
+    if (tab.pending) HIP_TRY(hipEventSynchronize(tab.uploaded));
+    tab.pending = false;
+    const size_t tab_bytes = entries * sizeof(HClipFrame);
+    HIP_TRY(tab.host.grow(tab_bytes));
+    HIP_TRY(tab.dev.grow(tab_bytes, [s] { return hipStreamSynchronize(s); }));
+    if (!tab.uploaded) HIP_TRY(hipEventCreateWithFlags(&tab.uploaded, hipEventDisableTiming));
+    *out = &tab;
+    return 0;
+}
+
+static int send_clip_table(ClipBuffers::Table &tab, size_t entries, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(tab.dev.get(), tab.host.p, entries * sizeof(HClipFrame), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(tab.uploaded, s));
+    tab.pending = true;
+    return 0;
 }
 
 // Frames [b0, b0 + n) of a clip of a filter whose native calls are all gaussian_blur: one prologue launch, one read-back
@@ -138,7 +161,7 @@ static int clip_native_batch(ClipCall &cc, int b0, int n) {
     c.frames = cc.c.frames + b0;
     c.images_stride = 0;          // the prologue (and the per-row slice) of every frame reads the invocation's table
     void *params[] = {&a, &xy, &c};
-    const int pro_frames = launch_clip_prologue(f, a, cc.per_frame, cc.rows, b0, n, params, s);
+    const int pro_frames = launch_clip_prologue(f->f_pro_clip, cc.rows ? f->f_rows_clip : nullptr, a, cc.per_frame, b0, n, params, s);
     if (pro_frames < 0) return -1;
     if (pro_frames) {
         cc.records.resize(cc.xy_stride * pro_frames);
@@ -344,18 +367,12 @@ int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, 
     HIP_TRY(inv->clip.xy.grow(xy_stride * slots, wait, true));
     if (rows) HIP_TRY(inv->clip.rowtab.grow(rowtab_stride * slots * sizeof(float), wait));
     // the {t, frame} table of the whole call, copied now: the caller's arrays are free when this returns
-    ClipBuffers::Table &tab = inv->clip.table[inv->clip.next_table++ & 1];
-    if (tab.pending) HIP_TRY(hipEventSynchronize(tab.uploaded));
-    tab.pending = false;
-    const size_t tab_bytes = (size_t)num_frames * sizeof(HClipFrame);
-    HIP_TRY(tab.host.grow(tab_bytes));
-    HIP_TRY(tab.dev.grow(tab_bytes, wait));
-    if (!tab.uploaded) HIP_TRY(hipEventCreateWithFlags(&tab.uploaded, hipEventDisableTiming));
+    ClipBuffers::Table *tabp = nullptr;
+    if (next_clip_table(inv, (size_t)num_frames, s, &tabp) != 0) return -1;
+    ClipBuffers::Table &tab = *tabp;
     HClipFrame *hf = (HClipFrame *)tab.host.p;
     for (int i = 0; i < num_frames; ++i) hf[i] = HClipFrame{ts[i], frames[i]};
-    HIP_TRY(hipMemcpyAsync(tab.dev.get(), hf, tab_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(tab.uploaded, s));
-    tab.pending = true;
+    if (send_clip_table(tab, (size_t)num_frames, s) != 0) return -1;
 
     a.xtab = inv->launch.xtab.get<float>();
     a.ytab = inv->launch.ytab.get<float>();
@@ -380,7 +397,7 @@ int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, 
         const int n = std::min(per_batch, num_frames - b0);
         a.out = (char *)out_device + (int64_t)b0 * frame_stride;
         c.frames = tab.dev.get<HClipFrame>() + b0;
-        const int pro_frames = launch_clip_prologue(f, a, per_frame, rows, b0, n, params, s);
+        const int pro_frames = launch_clip_prologue(f->f_pro_clip, rows ? f->f_rows_clip : nullptr, a, per_frame, b0, n, params, s);
         if (pro_frames < 0) return -1;
         inv->clip_prologue_frames += pro_frames;
         if (timed_pixel_launch(inv, f->f_pix_clip, (unsigned)plan.grid_x, (unsigned)n, params, s) != 0) return -1;
@@ -559,6 +576,123 @@ int mmhip_render_clip_shutter(mmhip_invocation *inv, int num_frames, const int *
                 return fail(err);
         }
         ++inv->clip_shutter_batches;
+    }
+    return 0;
+}
+
+// ---- motion-blurred clips, fused ----
+// mm_shutter of mm_pixels_shutter (hipgen.cpp shutter_prelude)
+struct HShutter { int samples; float inv_k; };
+static_assert(sizeof(HShutter) == 8, "mm_shutter layout");
+
+// How mmhip_render_clip_shutter_fused cuts a clip into batches (include/mmhip.h has the rules): a slot is one sub-sample's
+// frame constants and row table, per_batch output frames are one pixel launch.  fused false: the call is
+// mmhip_render_clip_shutter.
+struct ClipShutterFusedPlan {
+    bool fused = false, per_frame = false;
+    int per_batch = 0, batches = 0, slots_per_batch = 0;
+    long grid_x = 0;
+    LaunchGeometry geo;
+    size_t xy_stride = 0, rowtab_stride = 0;      // of one slot: bytes, floats
+};
+static ClipShutterFusedPlan clip_shutter_fused_plan(const mmhip_filter *f, int region_w, int num_rows, int samples, int frames) {
+    ClipShutterFusedPlan p;
+    p.geo = single_pixel_launch_geometry(f->ks, region_w, num_rows);
+    const ClipPlan cp = clip_plan(p.geo);
+    p.grid_x = cp.grid_x;
+    p.per_frame = f->ks.prologue_uses_time;
+    p.xy_stride = ((size_t)std::max(f->ks.xy_bytes, 256) + 255) / 256 * 256;
+    p.rowtab_stride = (size_t)f->ks.row_values * num_rows;
+    if (!f->ks.natives.empty() || !f->closures.empty()) return p;
+    long per = std::min<long>({(long)frames, (long)(cp.max_grid_rows / samples), cp.max_rows_by_items});
+    if (p.per_frame) {
+        per = std::min<long>(per, (long)((size_t)INT32_MAX / (p.xy_stride * samples)));
+        if (p.rowtab_stride) per = std::min<long>(per, (long)((size_t)INT32_MAX / (p.rowtab_stride * samples)));
+    }
+    if (per < 1) return p;
+    p.fused = true;
+    p.per_batch = (int)per;
+    p.batches = (frames + p.per_batch - 1) / p.per_batch;
+    p.slots_per_batch = p.per_frame ? p.per_batch * samples : 1;
+    return p;
+}
+
+int mmhip_filter_clip_shutter_fused_plan(const mmhip_filter *f, int region_w, int num_rows, int samples, int frames, int64_t *out) {
+    if (frames < 1) return fail("clip shutter fused plan: num_frames must be at least 1");
+    if (clip_shutter_check_samples("clip shutter fused plan", samples) != 0) return -1;
+    if (region_w < 1 || num_rows < 1) return fail("clip shutter fused plan: empty region");
+    const ClipShutterFusedPlan p = clip_shutter_fused_plan(f, region_w, num_rows, samples, frames);
+    const int64_t v[MMHIP_CLIP_SHUTTER_FUSED_PLAN_FIELDS] = {p.fused, p.per_batch, p.batches, p.fused ? p.slots_per_batch : 0, p.grid_x};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+long mmhip_clip_shutter_fused_batches(mmhip_invocation *inv) { return inv->clip_shutter_fused_batches; }
+
+int mmhip_render_clip_shutter_fused(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
+                                    int region_x, int region_y, int region_w, int region_h, int first_row, int last_row,
+                                    void *out_device, int row_stride, int64_t frame_stride, int bpp, int floatmap, void *stream) {
+    const char *who = "render_clip_shutter_fused";
+    if (clip_shutter_check_samples(who, samples) != 0) return -1;
+    if (samples == 1)       // one instant per frame: the plain clip itself
+        return mmhip_render_clip(inv, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
+                                 row_stride, frame_stride, bpp, floatmap, stream);
+    if (!std::isfinite(span)) return fail(std::string(who) + ": span must be finite");
+    if (check_clip_args(who, num_frames, frames, ts, bpp, region_w, region_h) != 0) return -1;
+    const int first_arg = first_row, last_arg = last_row;
+    if (!clamp_rows(region_y, region_h, &first_row, &last_row)) return 0;
+    const int num_rows = last_row - first_row;
+    if (check_frame_stride(who, inv, frame_stride, num_rows, region_w, row_stride, bpp, floatmap) != 0) return -1;
+    if (region_w > inv->render_w) return fail(std::string(who) + ": the region is wider than the render width");
+    mmhip_filter *f = active_filter(inv, frames[0], ts[0]);
+    const ClipShutterFusedPlan plan = clip_shutter_fused_plan(f, region_w, num_rows, samples, num_frames);
+    if (!plan.fused)        // native calls, closure images, a frame too large for one launch: the sub-sample maps
+        return mmhip_render_clip_shutter(inv, num_frames, frames, ts, samples, span, region_x, region_y, region_w, region_h, first_arg,
+                                         last_arg, out_device, row_stride, frame_stride, bpp, floatmap, stream);
+    if (mmhip_filter_jit_shutter(f, 1) < 0) return -1;
+    const KernelSource &ks = f->shutter_ks;
+    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
+    if (upload_tables(inv, s) != 0) return -1;
+
+    HArgs a = render_args(inv, frames[0], ts[0], region_x, region_y, region_w, region_h, first_row, last_row, out_device, row_stride, bpp, floatmap);
+    const bool rows = ks.row_values > 0;
+    // the coordinate tables are the single-frame path's, rewritten here: its prologue must run again
+    if (grow_launch_buffers(inv->launch, ks, region_w, num_rows, false, s) != 0) return -1;
+    inv->pro_filter = nullptr;
+    auto wait = [s] { return hipStreamSynchronize(s); };
+    HIP_TRY(inv->clip.xy.grow(plan.xy_stride * plan.slots_per_batch, wait, true));
+    if (rows) HIP_TRY(inv->clip.rowtab.grow(plan.rowtab_stride * plan.slots_per_batch * sizeof(float), wait));
+    // the {t, frame} table of every sub-sample of the call: slot i * samples + j is sub-sample j of output frame i
+    const size_t slots = (size_t)num_frames * samples;
+    ClipBuffers::Table *tab = nullptr;
+    if (next_clip_table(inv, slots, s, &tab) != 0) return -1;
+    HClipFrame *hf = (HClipFrame *)tab->host.p;
+    for (int i = 0; i < num_frames; ++i)
+        for (int j = 0; j < samples; ++j) hf[(size_t)i * samples + j] = HClipFrame{mm_shutter_sample_t(ts[i], span, j, samples), frames[i]};
+    if (send_clip_table(*tab, slots, s) != 0) return -1;
+
+    a.xtab = inv->launch.xtab.get<float>();
+    a.ytab = inv->launch.ytab.get<float>();
+    if (rows) a.rowtab = inv->clip.rowtab.get<float>();
+    a.ppt = plan.geo.ppt;
+    a.tiles_magic = plan.geo.tiles_magic;
+    char *xy = inv->clip.xy.get<char>();
+    HClip c{};
+    c.frame_stride = frame_stride;
+    c.xy_stride = plan.per_frame ? (int)plan.xy_stride : 0;
+    c.rowtab_stride = plan.per_frame ? (int)plan.rowtab_stride : 0;
+    c.nwg = (int)plan.geo.nwg;
+    HShutter sh{samples, mm_shutter_inv_k(samples)};
+    void *params[] = {&a, &xy, &c, &sh};      // (the prologue and the per-row slice take the first three)
+    for (int b0 = 0; b0 < num_frames; b0 += plan.per_batch) {
+        const int n = std::min(plan.per_batch, num_frames - b0);
+        a.out = (char *)out_device + (int64_t)b0 * frame_stride;
+        c.frames = tab->dev.get<HClipFrame>() + (size_t)b0 * samples;
+        const int pro_slots = launch_clip_prologue(f->f_pro_shutter, rows ? f->f_rows_shutter : nullptr, a, plan.per_frame, b0, n * samples, params, s);
+        if (pro_slots < 0) return -1;
+        inv->clip_prologue_frames += pro_slots;
+        if (timed_pixel_launch(inv, f->f_pix_shutter, (unsigned)plan.grid_x, (unsigned)n, params, s) != 0) return -1;
+        ++inv->clip_shutter_fused_batches;
     }
     return 0;
 }

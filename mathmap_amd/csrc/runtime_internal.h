@@ -47,6 +47,13 @@ struct mmhip_filter {
     hipModule_t clip_mod = nullptr;
     hipFunction_t f_pro_clip = nullptr, f_rows_clip = nullptr, f_pix_clip = nullptr;
     bool clip_loaded = false;
+    // the shutter variant of the module (mmhip_render_clip_shutter_fused): generated from `code` when it is first asked
+    // for (KernelOptions::shutter), built and cached like the clip variant; filters without native calls or closure images
+    mm::KernelSource shutter_ks;
+    std::vector<char> shutter_code_object;
+    hipModule_t shutter_mod = nullptr;
+    hipFunction_t f_pro_shutter = nullptr, f_rows_shutter = nullptr, f_pix_shutter = nullptr;
+    bool shutter_loaded = false;
     // user-value specialisation (specialize.cpp): kernels with the scalar user values baked in,
     // keyed by the value bytes; owned by this filter
     std::string source;
@@ -221,6 +228,7 @@ struct mmhip_invocation {
     DeviceBuffer clip_shutter;             // the sub-sample float maps of a batch of motion-blurred frames
                                            // (mmhip_render_clip_shutter), and behind them the carry map where one is needed
     long clip_shutter_batches = 0;         // mmhip_clip_shutter_batches
+    long clip_shutter_fused_batches = 0;   // mmhip_clip_shutter_fused_batches
     uint32_t edge_color_x = 0, edge_color_y = 0;
     float sampling_offset_x = 0.f, sampling_offset_y = 0.f;
     bool timing = false;
@@ -265,7 +273,10 @@ struct LaunchGeometry {
     uint32_t tiles_magic = 0;     // mm_args.tiles_magic
 };
 LaunchGeometry clip_launch_geometry(const mm::KernelSource &ks, int region_w, int num_rows, int frames);
-struct ClipPlan { long grid_x = 0; int max_frames = 0; };
+// ... of a kernel of the single-pixel shape with the tiles of `ks` (mm_pixels_shutter): one row per work-item
+LaunchGeometry single_pixel_launch_geometry(const mm::KernelSource &ks, int region_w, int num_rows);
+// max_frames is the smaller of the two caps it is made of: grid rows (gridDim.y, MMHIP_CLIP_MAX_FRAMES) and work-items
+struct ClipPlan { long grid_x = 0; int max_frames = 0; int max_grid_rows = 0; long max_rows_by_items = 0; };
 ClipPlan clip_plan(const LaunchGeometry &g);
 
 mmhip_filter *active_filter(mmhip_invocation *inv, int frame = 0, float t = 0.0f);
