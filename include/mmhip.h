@@ -369,6 +369,82 @@ int mmhip_filter_clip_shutter_fused_plan(const mmhip_filter *f, int region_w, in
    -1, with a message. */
 const char *mmhip_filter_shutter_kernel_source(mmhip_filter *f);
 long mmhip_filter_jit_shutter(mmhip_filter *f, int load_module);
+/* A grid-supersampled clip (an extension): anti-aliasing in space, alone or together with a shutter.  Every output
+   pixel is the mean of samples * grid_x * grid_y = K * G float sub-samples: K instants of the shutter, and at each of them
+   a regular grid of sx = grid_x by sy = grid_y sampling offsets inside the pixel's footprint.  The parameters before and
+   behind samples, span, grid_x, grid_y are mmhip_render_clip_shutter's; asynchronous.  (The CLI's -o,
+   mmhip_render_clip_supersampled, is something else and stays what it is: the reference's five-tap average of bytes.)
+     - samples = K is 1 to 256 and span any finite float, as for the shutter; grid_x and grid_y are 1 to
+       MMHIP_SAMPLE_GRID_MAX (8) each; K * G is at most MMHIP_SHUTTER_MAX_SAMPLES (256).
+     - The offsets (mathmap_amd/csrc/mm_sample_grid.h), in the units of mmhip_set_sampling_offset (pixels):
+       ox_a = (float)(((double)a + 0.5) / (double)sx - 0.5) for a = 0 .. sx - 1, and oy_b the same with sy.  One point per
+       axis is exactly 0.
+     - Sub-sample (j, b, a) of output frame i is the float map mmhip_render produces at frame number frames[i], at the time
+       t_ij of mmhip_render_clip_shutter (mm_shutter_sample_t(ts[i], span, j, K)) and at sampling offset (ox_a, oy_b).
+       Native filters and closure renders see what they see in any render at that offset (closures render at offset 0).
+     - Order and arithmetic: the sub-samples are numbered s = j * G + b * sx + a, a fastest.  Per pixel and channel, in f32,
+       round to nearest, no fma: acc = f_0; acc = acc + f_s for s = 1 .. K * G - 1 in that order; m = acc * inv_k with
+       inv_k = (float)(1.0 / (double)(K * G)).  m is stored as mmhip_render stores a pixel (bytes at bpp 1 - 4, or the
+       float map).  These are the shutter's rules with K * G in place of K.
+     - The call's grid offsets replace the invocation's sampling offset for the length of the call; the caller's offset is
+       put back on every return, failed calls included.  Bytes between rows and between frames are not touched.
+     - grid_x = grid_y = 1 is mmhip_render_clip_shutter: the call delegates before anything else (and samples = 1 then
+       reaches mmhip_render_clip).
+     - Per batch of B output frames and per pass of `count` time steps: for every grid point g = b * sx + a one nested
+       mmhip_render_clip of the B * count (frame, t) entries at offset (ox_a, oy_b), into the shutter's temporary at
+       g * bytes_per_sample with frame_stride G * bytes_per_sample -- entry e = i * count + j lands at (e * G + g) *
+       bytes_per_sample, the layout [i][j][g] -- and then one launch of the shutter's combine over count * G samples.
+       Nothing is refused that mmhip_render_clip takes.  Known cost: a filter with native calls runs them once per nested
+       call, G times per batch.
+     - MMHIP_CLIP_SHUTTER_BYTES bounds the temporary as it does for the shutter.  Where a frame's K * G maps fit:
+       frames_per_batch = min(budget / (K * G * bytes_per_sample), 65 535, num_frames), one pass.  Otherwise one frame per
+       batch in passes of whole time steps, steps_per_pass = max(1, (budget / bytes_per_sample - 1) / G), the running sum
+       carried in one more map; one time step's G maps and the carry map are allocated even over the budget.
+     - mmhip_clip_sampled_batches rises by one per batch; the shutter's counters do not move.  The combine is timed as
+       shutter_combine_clip.
+   Errors: a grid outside 1 .. 8; samples out of range; K * G > 256; a span that is not finite; a sub-sample map beyond
+   4 GiB; out of device memory; mmhip_render_clip's own. */
+enum { MMHIP_SAMPLE_GRID_MAX = 8, MMHIP_CLIP_SAMPLED_PLAN_FIELDS = 6 };
+int mmhip_render_clip_sampled(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
+                              int grid_x, int grid_y, int region_x, int region_y, int region_w, int region_h, int first_row,
+                              int last_row, void *out_device, int row_stride, int64_t frame_stride, int bpp, int floatmap,
+                              void *stream);
+long mmhip_clip_sampled_batches(mmhip_invocation *inv);
+/* How mmhip_render_clip_sampled renders such a clip (needs no GPU).  out[] receives MMHIP_CLIP_SAMPLED_PLAN_FIELDS
+   values: frames_per_batch, batches, steps_per_pass (time steps, of G maps each), passes (per frame), bytes_per_sample
+   and carry. */
+int mmhip_filter_clip_sampled_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int samples, int grid_x,
+                                   int grid_y, int frames, int64_t *out);
+/* The same clip without the sub-sample maps (opt-in): kernel mm_pixels_sampled of a variant of its own evaluates the
+   K * G sub-samples of an output pixel one after the other and sums them in registers, in the order stated above.  The
+   parameters and the bytes are mmhip_render_clip_sampled's.  Asynchronous.
+     - grid_x = grid_y = 1 is mmhip_render_clip_shutter_fused: the call delegates before anything else.
+     - mm_pixels_sampled has mm_pixels_shutter's shape (one work-item per output pixel, the generic fetch).  The slot
+       i * K + j selects {t, frame} and the frame constants; x and y of grid point (a, b) come from per-offset coordinate
+       tables -- sx * region_w and sy * rows floats -- which the variant's mm_prologue_clip writes with the expressions
+       of every prologue, at the offsets of mm_sample_grid.h uploaded behind the {t, frame} table.
+     - Fused are filters without native calls, without closure images and without a per-row slice (its values follow y;
+       such filters take the maps path) whose frame fits one launch.  For every other filter the call is
+       mmhip_render_clip_sampled: nothing is refused, and mmhip_clip_sampled_fused_batches stays where it was.
+     - Batches are mmhip_render_clip_shutter_fused's: B * K slots per launch.  mmhip_clip_sampled_fused_batches rises by
+       one per batch and mmhip_clip_prologue_frames by the slots launched; no other counter moves.
+   Errors: those of mmhip_render_clip_sampled but the 4 GiB one, under the name render_clip_sampled_fused. */
+int mmhip_render_clip_sampled_fused(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples,
+                                    float span, int grid_x, int grid_y, int region_x, int region_y, int region_w, int region_h,
+                                    int first_row, int last_row, void *out_device, int row_stride, int64_t frame_stride, int bpp,
+                                    int floatmap, void *stream);
+long mmhip_clip_sampled_fused_batches(mmhip_invocation *inv);
+/* How mmhip_render_clip_sampled_fused renders such a clip (needs no GPU): the fields of
+   mmhip_filter_clip_shutter_fused_plan (fused 0: the call is mmhip_render_clip_sampled). */
+enum { MMHIP_CLIP_SAMPLED_FUSED_PLAN_FIELDS = 5 };
+int mmhip_filter_clip_sampled_fused_plan(const mmhip_filter *f, int region_w, int num_rows, int samples, int grid_x, int grid_y,
+                                         int frames, int64_t *out);
+/* The sampled variant of the module -- mm_prologue_clip (with the per-offset tables) and mm_pixels_sampled -- and its gfx950
+   compile, like mmhip_filter_shutter_kernel_source and mmhip_filter_jit_shutter: generated when first asked for, cached
+   under its own key, the other three texts untouched.  A filter with native calls, closure images or a per-row slice has
+   none: NULL and -1, with a message. */
+const char *mmhip_filter_sampled_kernel_source(mmhip_filter *f);
+long mmhip_filter_jit_sampled(mmhip_filter *f, int load_module);
 /* Convenience: whole frame to a host RGBA8 buffer (width*height*4 bytes); synchronous. */
 int mmhip_render_host(mmhip_invocation *inv, int frame, float t, uint8_t *out_rgba);
 int mmhip_sync(mmhip_invocation *inv);

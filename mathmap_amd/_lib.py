@@ -104,6 +104,19 @@ SYMBOLS = {
     "mmhip_filter_clip_shutter_fused_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "mmhip_filter_shutter_kernel_source": (C.c_char_p, [C.c_void_p]),
     "mmhip_filter_jit_shutter": (C.c_long, [C.c_void_p, C.c_int]),
+    "mmhip_render_clip_sampled": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int, C.c_float, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int,
+                                            C.c_int, C.c_void_p]),
+    "mmhip_clip_sampled_batches": (C.c_long, [C.c_void_p]),
+    "mmhip_filter_clip_sampled_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.POINTER(C.c_int64)]),
+    "mmhip_render_clip_sampled_fused": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int, C.c_float, C.c_int,
+                                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64,
+                                                  C.c_int, C.c_int, C.c_void_p]),
+    "mmhip_clip_sampled_fused_batches": (C.c_long, [C.c_void_p]),
+    "mmhip_filter_clip_sampled_fused_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "mmhip_filter_sampled_kernel_source": (C.c_char_p, [C.c_void_p]),
+    "mmhip_filter_jit_sampled": (C.c_long, [C.c_void_p, C.c_int]),
     "mmhip_render_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "mmhip_sync": (C.c_int, [C.c_void_p]),
     "mmhip_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),

@@ -35,6 +35,20 @@ SHUTTER_MAX_SAMPLES = 256
 CLIP_SHUTTER_FUSED_PLAN_FIELDS = ("fused", "frames_per_batch", "batches", "slots_per_batch", "grid_x")
 # render_clip's shutter_mode: the sub-sample maps of mmhip_render_clip_shutter, or mmhip_render_clip_shutter_fused
 SHUTTER_MODES = ("maps", "fused")
+CLIP_SAMPLED_PLAN_FIELDS = ("frames_per_batch", "batches", "steps_per_pass", "passes", "bytes_per_sample", "carry")
+SAMPLE_GRID_MAX = 8
+
+
+def sample_grid(aa):
+    """render_clip's `aa` as the pair (sx, sy): an int n means (n, n).  ValueError outside 1 .. 8."""
+    try:
+        sx, sy = (aa, aa) if isinstance(aa, (int, np.integer)) and not isinstance(aa, bool) else aa
+        ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (sx, sy))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not (1 <= sx <= SAMPLE_GRID_MAX and 1 <= sy <= SAMPLE_GRID_MAX):
+        raise ValueError("render_clip: aa is an int or a pair (sx, sy) of ints from 1 to %d, not %r" % (SAMPLE_GRID_MAX, aa))
+    return int(sx), int(sy)
 
 
 class MathMapError(RuntimeError):
@@ -244,6 +258,40 @@ class Filter:
             raise MathMapError(_err())
         return dict(zip(CLIP_SHUTTER_FUSED_PLAN_FIELDS, out))
 
+    def clip_sampled_plan(self, region_w, num_rows, render_w, samples, aa, frames):
+        """How render_clip(aa=aa, shutter_samples=samples) renders a `frames`-frame clip through sub-sample maps: a dict of
+        the CLIP_SAMPLED_PLAN_FIELDS (steps_per_pass: time steps, of sx * sy maps each)."""
+        sx, sy = sample_grid(aa)
+        out = (C.c_int64 * len(CLIP_SAMPLED_PLAN_FIELDS))()
+        if lib().mmhip_filter_clip_sampled_plan(self._h, region_w, num_rows, render_w, samples, sx, sy, frames, out) != 0:
+            raise MathMapError(_err())
+        return dict(zip(CLIP_SAMPLED_PLAN_FIELDS, out))
+
+    def clip_sampled_fused_plan(self, region_w, num_rows, samples, aa, frames):
+        """How render_clip(aa=aa, shutter_samples=samples, shutter_mode="fused") renders a `frames`-frame clip: a dict of the
+        CLIP_SHUTTER_FUSED_PLAN_FIELDS (fused 0: the filter takes the maps path)."""
+        sx, sy = sample_grid(aa)
+        out = (C.c_int64 * len(CLIP_SHUTTER_FUSED_PLAN_FIELDS))()
+        if lib().mmhip_filter_clip_sampled_fused_plan(self._h, region_w, num_rows, samples, sx, sy, frames, out) != 0:
+            raise MathMapError(_err())
+        return dict(zip(CLIP_SHUTTER_FUSED_PLAN_FIELDS, out))
+
+    @property
+    def sampled_kernel_source(self):
+        """The sampled variant of kernel_source: kernels mm_prologue_clip and mm_pixels_sampled.  A filter with native calls,
+        closure images or a per-row slice has none: MathMapError."""
+        text = lib().mmhip_filter_sampled_kernel_source(self._h)
+        if text is None:
+            raise MathMapError(_err())
+        return text.decode()
+
+    def jit_sampled(self, load=False):
+        """hiprtc-compiles the sampled variant for gfx950; returns the code-object size."""
+        n = lib().mmhip_filter_jit_sampled(self._h, 1 if load else 0)
+        if n < 0:
+            raise MathMapError(_err())
+        return n
+
     @property
     def shutter_kernel_source(self):
         """The shutter variant of kernel_source: kernels mm_prologue_clip, mm_rows_clip, mm_pixels_shutter.  A filter with
@@ -408,6 +456,11 @@ class Invocation:
         self._check(lib().mmhip_set_render_size(self._h, render_width, render_height))
         self.render_width, self.render_height = render_width, render_height
 
+    def set_sampling_offset(self, ox, oy):
+        """The sub-pixel sampling offset of later renders, in pixels (mmhip_set_sampling_offset; the reference's -o renders
+        its second slice at -0.5).  render_clip(aa=...) sets its own for the length of the call and puts this one back."""
+        self._check(lib().mmhip_set_sampling_offset(self._h, float(ox), float(oy)))
+
     def set_edge_colors(self, cx, cy):
         self._check(lib().mmhip_set_edge_colors(self._h, cx, cy))
 
@@ -462,7 +515,7 @@ class Invocation:
 
     def render_clip(self, num_frames=None, frames=None, ts=None, out_ptr=None, rows=None, region=None, row_stride=None,
                     frame_stride=None, bpp=4, floatmap=False, stream=0, supersample=False, shutter_samples=1, shutter_span=None,
-                    shutter=None, shutter_mode="maps"):
+                    shutter=None, shutter_mode="maps", aa=1):
         """Renders a clip in batched launches (mmhip_render_clip): frame i at frame number frames[i] and time ts[i].
         `num_frames`=N alone is the CLI's animation: frame = i, t = (float)i / (float)N.  `rows` = (first_row,
         last_row) and `region`, `row_stride`, `bpp`, `floatmap`, `stream` as in render_rows; frame i lands
@@ -478,11 +531,29 @@ class Invocation:
         `supersample` is a ValueError.
         `shutter_mode`: "maps" (default) renders the sub-samples as float maps and averages them, "fused" sums them in the
         pixel kernel's registers (mmhip_render_clip_shutter_fused): the same bytes; filters with native calls or closure
-        images take the maps path under either.  Any other value is a ValueError."""
+        images take the maps path under either.  Any other value is a ValueError.
+        `aa` = n or (sx, sy), 1 to 8 each, anti-aliases in space (mmhip_render_clip_sampled, with "fused"
+        mmhip_render_clip_sampled_fused): every pixel is the mean, in float, of an sx x sy grid of sub-samples inside its
+        footprint -- times the K shutter sub-samples where shutter_samples > 1, K * sx * sy being at most 256.  Without a
+        shutter it needs no span.  Values outside the range, more than 256 sub-samples, or `aa` != 1 with
+        `supersample` (the -o frames, which stay what they are) are a ValueError; aa=1 changes nothing."""
         from .striping import animation_frame_t
+        grid = sample_grid(aa)
+        if grid != (1, 1):
+            if supersample:
+                raise ValueError("render_clip: aa is not combined with supersample=True")
+            if int(shutter_samples) >= 1 and int(shutter_samples) * grid[0] * grid[1] > 256:
+                raise ValueError("render_clip: shutter_samples * sx * sy must be at most 256, not %d" % (int(shutter_samples) * grid[0] * grid[1]))
+            if int(shutter_samples) == 1 and shutter is None and shutter_span is None:
+                shutter_span = 0.0
         if shutter_mode not in SHUTTER_MODES:
             raise ValueError("render_clip: shutter_mode must be one of %s, not %r" % (", ".join(SHUTTER_MODES), shutter_mode))
         render_shutter = lib().mmhip_render_clip_shutter_fused if shutter_mode == "fused" else lib().mmhip_render_clip_shutter
+        if grid != (1, 1):
+            sampled = lib().mmhip_render_clip_sampled_fused if shutter_mode == "fused" else lib().mmhip_render_clip_sampled
+
+            def render_shutter(h, n, fp, tp, samples, span, *rest):
+                return sampled(h, n, fp, tp, samples, span, grid[0], grid[1], *rest)
         if supersample and (floatmap or rows is not None):
             raise ValueError("render_clip: supersample=True renders whole regions of bytes: neither floatmap nor rows")
         shutter_samples = int(shutter_samples)
@@ -588,6 +659,14 @@ class Invocation:
     def clip_shutter_fused_batches(self):
         """Batches render_clip(shutter_samples > 1, shutter_mode="fused") rendered fused (0 for filters that take the maps path)."""
         return lib().mmhip_clip_shutter_fused_batches(self._h)
+
+    def clip_sampled_batches(self):
+        """Batches of grid-supersampled frames render_clip(aa != 1) has combined from sub-sample maps so far."""
+        return lib().mmhip_clip_sampled_batches(self._h)
+
+    def clip_sampled_fused_batches(self):
+        """Batches render_clip(aa != 1, shutter_mode="fused") rendered fused (0 for filters that take the maps path)."""
+        return lib().mmhip_clip_sampled_fused_batches(self._h)
 
     def clip_supersampled_batches(self):
         """Batches render_clip(supersample=True) ran batched (0 for filters it renders frame by frame)."""

@@ -73,6 +73,12 @@ void usage() {
            "      --shutter-mode=MODE     how the K renders are averaged: maps (default,\n"
            "                              float maps in device memory) or fused (summed in\n"
            "                              the pixel kernel); the files are the same\n"
+           "      --aa=N | SXxSY          anti-aliasing: every pixel is the mean of\n"
+           "                              an N x N (or SX x SY, 1 to 8 each) grid of renders\n"
+           "                              inside its footprint, averaged in float on the\n"
+           "                              GPU; combines with --shutter-samples (K * SX * SY\n"
+           "                              at most 256), --shutter-mode and --batch-frames;\n"
+           "                              not combined with -o\n"
            "\n"
            "Report bugs and suggestions to schani@complang.tuwien.ac.at\n",
            cache_size);
@@ -220,7 +226,7 @@ std::string frame_file(const std::string &pattern, int frame) {
 enum {
     OPT_VERSION = 256, OPT_HELP, OPT_HTMLDOC, OPT_BENCH_NO_OUTPUT, OPT_BENCH_ONLY_COMPILE,
     OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE, OPT_INPUT_FRAMES, OPT_BATCH_FRAMES,
-    OPT_NATIVE_INPUT_FRAME, OPT_SHUTTER_SAMPLES, OPT_SHUTTER, OPT_SHUTTER_MODE
+    OPT_NATIVE_INPUT_FRAME, OPT_SHUTTER_SAMPLES, OPT_SHUTTER, OPT_SHUTTER_MODE, OPT_AA
 };
 
 int main(int argc, char **argv) {
@@ -228,7 +234,7 @@ int main(int argc, char **argv) {
     bool have_script = false, htmldoc = false, bench_no_output = false, bench_no_backend = false;
     int antialiasing = 0, supersampling = 0, img_width = 0, img_height = 0, size_is_set = 0;
     int bench_render_count = 1, num_frames = 1, input_frames = 0, gauss_mode = MMHIP_GAUSS_EXACT, batch_frames = 1;
-    int native_input_frame = MMHIP_NATIVE_FRAME_ZERO, shutter_samples = 1;
+    int native_input_frame = MMHIP_NATIVE_FRAME_ZERO, shutter_samples = 1, aa_x = 1, aa_y = 1;
     double shutter = 0.5;
     bool shutter_fused = false;
     const char *generator = nullptr;
@@ -247,7 +253,7 @@ int main(int argc, char **argv) {
         {"input-frames", required_argument, 0, OPT_INPUT_FRAMES}, {"batch-frames", required_argument, 0, OPT_BATCH_FRAMES},
         {"native-input-frame", required_argument, 0, OPT_NATIVE_INPUT_FRAME},
         {"shutter-samples", required_argument, 0, OPT_SHUTTER_SAMPLES}, {"shutter", required_argument, 0, OPT_SHUTTER},
-        {"shutter-mode", required_argument, 0, OPT_SHUTTER_MODE},
+        {"shutter-mode", required_argument, 0, OPT_SHUTTER_MODE}, {"aa", required_argument, 0, OPT_AA},
         {0, 0, 0, 0}};
     for (;;) {
         int idx;
@@ -328,6 +334,23 @@ int main(int argc, char **argv) {
                 else if (!strcmp(optarg, "fused")) shutter_fused = true;
                 else { fprintf(stderr, "Error: --shutter-mode takes maps or fused.\n"); return 1; }
                 break;
+            case OPT_AA: {
+                char *end = nullptr;
+                long nx = strtol(optarg, &end, 10), ny = nx;
+                bool ok = end != optarg;
+                if (ok && *end == 'x') {
+                    const char *second = end + 1;
+                    ny = strtol(second, &end, 10);
+                    ok = end != second;
+                }
+                if (!ok || *end || nx < 1 || nx > MMHIP_SAMPLE_GRID_MAX || ny < 1 || ny > MMHIP_SAMPLE_GRID_MAX) {
+                    fprintf(stderr, "Error: --aa takes N or SXxSY, 1 to %d each.\n", (int)MMHIP_SAMPLE_GRID_MAX);
+                    return 1;
+                }
+                aa_x = (int)nx;
+                aa_y = (int)ny;
+                break;
+            }
             case OPT_SHUTTER: {
                 char *end = nullptr;
                 shutter = strtod(optarg, &end);
@@ -339,6 +362,15 @@ int main(int argc, char **argv) {
     }
     if (supersampling && shutter_samples > 1) {
         fprintf(stderr, "Error: --shutter-samples is not combined with -o (oversampling).\n");
+        return 1;
+    }
+    const bool sampled = aa_x * aa_y > 1;
+    if (supersampling && sampled) {
+        fprintf(stderr, "Error: --aa is not combined with -o (oversampling).\n");
+        return 1;
+    }
+    if (shutter_samples * aa_x * aa_y > MMHIP_SHUTTER_MAX_SAMPLES) {
+        fprintf(stderr, "Error: --shutter-samples times the --aa grid is at most %d sub-samples.\n", (int)MMHIP_SHUTTER_MAX_SAMPLES);
         return 1;
     }
     const char *output_filename;
@@ -462,7 +494,8 @@ int main(int argc, char **argv) {
     // one; a batch's frames stay under 1 GiB of device memory.  With -o the clip is a supersampled one.
     // --shutter-samples=K: the frames go through mmhip_render_clip_shutter (--shutter-mode=fused: ..._fused), --batch-frames of them per call (by default
     // one, all of its K sub-samples in one nested clip), at the span (float)((double)FRACTION / NUM).
-    const bool shuttered = shutter_samples > 1;
+    // --aa: they go through mmhip_render_clip_sampled (..._fused) instead, with or without a shutter.
+    const bool shuttered = shutter_samples > 1 || sampled;
     const float shutter_span = (float)(shutter / (double)num_frames);
     batch_frames = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch_frames, num_frames), ((size_t)1 << 30) / output.size()));
     void *dev = mmhip_device_alloc(output.size() * batch_frames);
@@ -476,7 +509,11 @@ int main(int argc, char **argv) {
                 frames[i] = first + i;
                 ts[i] = (float)(first + i) / (float)num_frames;       // mathmap_cmdline.c:835
             }
-            const int rc = shuttered
+            const int rc = sampled
+                               ? (shutter_fused ? mmhip_render_clip_sampled_fused : mmhip_render_clip_sampled)(
+                                     inv, n, frames.data(), ts.data(), shutter_samples, shutter_span, aa_x, aa_y, 0, 0, img_width, img_height, 0,
+                                     img_height, dev, img_width * 4, (int64_t)output.size(), 4, 0, nullptr)
+                           : shuttered
                                ? (shutter_fused ? mmhip_render_clip_shutter_fused : mmhip_render_clip_shutter)(
                                      inv, n, frames.data(), ts.data(), shutter_samples, shutter_span, 0, 0, img_width, img_height, 0, img_height,
                                      dev, img_width * 4, (int64_t)output.size(), 4, 0, nullptr)

@@ -19,7 +19,8 @@
 // Two more modules are made of the same statements: the clip variant (mm_*_clip: this text with the kernels' heads
 // replaced, clip_kernel_source) and, generated on demand under KernelOptions::shutter, the shutter variant -- the clip
 // forms of the prologue and the per-row slice, and mm_pixels_shutter: the single shape's body in a loop over a pixel's
-// sub-samples (emit_shutter_pixel_kernel).
+// sub-samples (emit_shutter_pixel_kernel).  KernelOptions::sampled gives the same with mm_pixels_sampled, whose loop also
+// walks a grid of sampling offsets (emit_sampled_pixel_kernel).
 //
 // The environment hooks for experiments that alter this text are the fields of struct Knobs (hipgen_internal.h).
 //
@@ -687,7 +688,7 @@ struct Generator {
     }
     void find_row_slice() {
         if (fn_root || in_function || knobs.no_row_slice) return;
-        if (opt.shutter) {
+        if (opt.variant()) {
             // the second generation from this code: the slice is what the first run marked (it moved those statements
             // out of the pixel slice, so the search below would not find them again), its table in the same order
             std::vector<Value *> defs;
@@ -839,10 +840,11 @@ struct Generator {
         if (pair) pair->emit_helpers();
         emit_prologue_kernel();
         if (ks.row_values > 0) emit_rows_kernel();
-        if (opt.shutter) emit_shutter_pixel_kernel();
+        if (opt.sampled) emit_sampled_pixel_kernel();
+        else if (opt.shutter) emit_shutter_pixel_kernel();
         else emit_pixel_kernel();
         ks.source = out.str();
-        if (opt.shutter) {      // the prologue and the per-row slice in their clip form; the pixel kernel has no other
+        if (opt.variant()) {      // the prologue and the per-row slice in their clip form; the pixel kernel has no other
             std::string text, key;
             clip_kernel_source(ks, &text, &key);
             ks.source = std::move(text);
@@ -885,7 +887,7 @@ struct Generator {
         out << "#define MM_TILE_W " << ks.tile_w << "\n#define MM_TILE_H " << ks.tile_h << "\n";
         ks.unroll = opt.unroll > 0 ? opt.unroll : auto_unroll();
         // pair mode (row values are per pixel of a pair; a native call is not arithmetic)
-        if (opt.shutter) ks.unroll = 1;      // (single-pixel shape, general fetch: emit_shutter_pixel_kernel)
+        if (opt.variant()) ks.unroll = 1;      // (single-pixel shape, general fetch: emit_shutter_pixel_kernel)
         else if (opt.unroll <= 0 && !knobs.unroll && ks.row_values == 0 && ks.natives.empty())
             pair = make_pair_mode(PairEnv{out, code, opt, knobs, pix_defs, pixel_stmts, pixel_fetches,
                                           [this](const Primary &p) { return prim(p, PIXEL); },
@@ -1029,8 +1031,27 @@ MM_DEV mm_image mm_native_result_in_loop(const mm_args &A, int &n, int sites) {
                    "    if (" + first + "gid < A.num_rows) A.ytab[gid] = CALC_VIRTUAL_Y(A.first_row + gid, A.frame_render_height, A.sampling_offset_y);\n"
                    "    if (gid != 0) return;\n  }\n";
         };
-        emit(KERNEL + "mm_prologue(mm_args A, char *XY) {\n" + tables(""),
-             (ks.natives.empty() ? clip_prelude() : clip_prelude_natives()) + KERNEL + "mm_prologue_clip(mm_args A, char *XY, const mm_clip C) {\n  MM_CLIP_ENTRY\n" + tables("fi == 0 && "));
+        // the sampled variant: besides them one x table per grid column and one y table per grid row, the same expressions
+        // at the offsets of S.offs (mm_sample_grid.h on the host) -- the bits a render at that sampling offset computes
+        const std::string sampled_tables =
+            "  {\n    const int gid = blockIdx.x * 256 + threadIdx.x;\n"
+            "    if (fi == 0 && gid < A.region_width) {\n"
+            "      A.xtab[gid] = CALC_VIRTUAL_X(gid + A.region_x, A.frame_render_width, A.sampling_offset_x);\n"
+            "      for (int mm_a = 0; mm_a < S.gx; ++mm_a)\n"
+            "        S.xtabs[mm_a * A.region_width + gid] = CALC_VIRTUAL_X(gid + A.region_x, A.frame_render_width, S.offs[mm_a]);\n"
+            "    }\n"
+            "    if (fi == 0 && gid < A.num_rows) {\n"
+            "      A.ytab[gid] = CALC_VIRTUAL_Y(A.first_row + gid, A.frame_render_height, A.sampling_offset_y);\n"
+            "      for (int mm_b = 0; mm_b < S.gy; ++mm_b)\n"
+            "        S.ytabs[mm_b * A.num_rows + gid] = CALC_VIRTUAL_Y(A.first_row + gid, A.frame_render_height, S.offs[MM_SAMPLE_GRID_MAX + mm_b]);\n"
+            "    }\n"
+            "    if (gid != 0) return;\n  }\n";
+        const std::string clip_head =
+            opt.sampled ? std::string(clip_prelude()) + sampled_prelude() + KERNEL +
+                              "mm_prologue_clip(mm_args A, char *XY, const mm_clip C, const mm_sampled S) {\n  MM_CLIP_ENTRY\n" + sampled_tables
+                        : (ks.natives.empty() ? clip_prelude() : clip_prelude_natives()) + KERNEL +
+                              "mm_prologue_clip(mm_args A, char *XY, const mm_clip C) {\n  MM_CLIP_ENTRY\n" + tables("fi == 0 && ");
+        emit(KERNEL + "mm_prologue(mm_args A, char *XY) {\n" + tables(""), clip_head);
         out << "  MM_INTERNALS\n";
         if (!(fn_root ? fn_root : &code)->functions.empty()) out << "  const int col = 0, rl = 0; unsigned mm_rand_ctr = 0; (void)col; (void)rl; (void)mm_rand_ctr;\n";
         decls(pro_defs, "  ", true);
@@ -1192,6 +1213,64 @@ MM_DEV mm_image mm_native_result_in_loop(const mm_args &A, int &n, int sites) {
                "  mm_store_pixel(A, rl, col, mm_m);\n}\n";
     }
 
+    // ---- the sampled variant's pixel kernel (KernelOptions::sampled) ----
+    // mm_pixels_shutter's shape with a loop over the S.total = K * gx * gy sub-samples of a pixel: sub-sample s is
+    // (j, b, a) with a fastest, decoded by counters.  j alone selects the slot fi * K + j ({t, frame} and the frame
+    // constants); a and b select x and y, read from the per-offset tables mm_prologue_clip wrote -- entry col of table a,
+    // entry rl of table b: a wave-uniform base (mm_xo, mm_yo advance by one table per step) and the lane's own index.
+    // No per-row slice: its values follow y, and such filters take the maps path.
+    void emit_sampled_pixel_kernel() {
+        if (!ks.natives.empty()) throw CompileError("the sampled variant is for filters without native calls");
+        if (ks.row_values > 0) throw CompileError("the sampled variant is for filters without a per-row slice");
+        ks.single_pixel = true;
+        ks.pair_mode = false;
+        ks.pixel_name = "mm_pixels_sampled";
+        if (knobs.waves_per_eu) out << "__attribute__((amdgpu_waves_per_eu(" << *knobs.waves_per_eu << "))) ";
+        out << KERNEL
+            << "mm_pixels_sampled(mm_args A, const char *__restrict__ XY, const mm_clip C, const mm_sampled S) {\n"
+               "  if ((int)blockIdx.x >= C.nwg) return;      // padding workgroup\n"
+               "  const int fi = blockIdx.y;                 // the output frame\n"
+               "  A.out = (char *)A.out + (long long)fi * C.frame_stride;\n";
+        emit_tile_order(false);
+        out << "  const int rl = row0;   // A.ppt is 1 for this kernel\n"
+               "  if (rl >= A.num_rows) return;\n"
+               "  const char *const mm_xy0 = XY;\n"
+               "  const float *const mm_xt = S.xtabs + col;      // this column in the table of grid column 0\n"
+               "  const float *const mm_yt = S.ytabs + rl;       // this row in the table of grid row 0\n"
+               "  const int mm_xend = S.gx * A.region_width, mm_yend = S.gy * A.num_rows;\n"
+               "  long long mm_slot = (long long)fi * S.samples;\n"
+               "  int mm_xo = 0, mm_yo = 0;                      // (wave-uniform) a * region_width, b * num_rows\n"
+               "  mm_tup<4> mm_acc;\n"
+               "  mm_acc.v[0] = mm_acc.v[1] = mm_acc.v[2] = mm_acc.v[3] = 0.0f;\n"
+               "#pragma unroll 1\n"
+               "  for (int mm_s = 0; mm_s < S.total; ++mm_s) {\n"
+               "    { const mm_clip_frame mm_cf = C.frames[mm_slot]; A.t = mm_cf.t; A.frame = mm_cf.frame; }\n"
+               "    const char *__restrict__ XY = mm_xy0 + mm_slot * C.xy_stride;\n"
+               "    const float x = mm_xt[mm_xo];   // CALC_VIRTUAL_X(col + region_x, ..., offset a), by the prologue\n"
+               "    const float y = mm_yt[mm_yo];   // CALC_VIRTUAL_Y(first_row + rl, ..., offset b)\n"
+               "    MM_INTERNALS\n"
+               "    unsigned mm_rand_ctr = 0;      // RAND call number within this pixel: every sub-sample is a render of its own\n"
+               "    (void)XY; (void)x; (void)y; (void)mm_rand_ctr;\n";
+        transfer_loads(nullptr, "    ");
+        decls(pix_defs, "    ");
+        stmts(code.body, PIXEL, "    ");
+        out << "    mm_tup<4> rt;\n";
+        for (int i = 0; i < 4; ++i) out << "    rt.v[" << i << "] = " << prim(Primary::V(code.result[i]), PIXEL) << ";\n";
+        out << "    if (mm_s == 0) mm_acc = rt;\n"
+               "    else\n"
+               "      for (int mm_c = 0; mm_c < 4; ++mm_c) mm_acc.v[mm_c] = mm_acc.v[mm_c] + rt.v[mm_c];\n"
+               "    mm_xo += A.region_width;\n"
+               "    if (mm_xo == mm_xend) {\n"
+               "      mm_xo = 0;\n"
+               "      mm_yo += A.num_rows;\n"
+               "      if (mm_yo == mm_yend) { mm_yo = 0; ++mm_slot; }\n"
+               "    }\n"
+               "  }\n"
+               "  mm_tup<4> mm_m;\n"
+               "  for (int mm_c = 0; mm_c < 4; ++mm_c) mm_m.v[mm_c] = mm_acc.v[mm_c] * S.inv_k;\n"
+               "  mm_store_pixel(A, rl, col, mm_m);\n}\n";
+    }
+
     // loop shape: A.ppt rows per work-item, MM_UNROLL of them per step
     void emit_pixel_loops() {
         // descriptors of frame-constant images, loaded (scalar) once before the pixel loop
@@ -1319,6 +1398,15 @@ const char *clip_prelude_natives() {
 
 // What mm_pixels_shutter has besides mm_args and mm_clip: the sub-samples of an output pixel and (float)(1.0 / samples).
 const char *shutter_prelude() { return "struct mm_shutter { int samples; float inv_k; };\n"; }
+
+// What the sampled variant's kernels have besides mm_args and mm_clip: the grid's offsets (gx along x from offs[0], gy
+// along y from offs[MM_SAMPLE_GRID_MAX], in device memory: a by-value array indexed by a loop counter would be copied
+// to scratch), the per-offset coordinate tables (gx * region_width and gy * num_rows floats), the shutter's sub-samples,
+// total = samples * gx * gy and (float)(1.0 / total).
+const char *sampled_prelude() {
+    return "#define MM_SAMPLE_GRID_MAX 8\n"
+           "struct mm_sampled { const float *offs; float *xtabs; float *ytabs; int samples; int gx; int gy; int total; float inv_k; int pad; };\n";
+}
 
 void clip_kernel_source(const KernelSource &ks, std::string *source, std::string *key) {
     source->clear();

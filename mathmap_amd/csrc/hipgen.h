@@ -22,6 +22,12 @@ struct KernelOptions {
     // pixel's sub-samples, their sum in registers.  Generated a second time from the code `source` was generated from
     // (the row slice is taken as that run left it); filters without native calls only.
     bool shutter = false;
+    // The sampled variant (fused grid supersampling, with or without a shutter): like the shutter variant, with
+    // mm_pixels_sampled in its place -- the loop runs over the K * sx * sy sub-samples of a pixel, x and y of a sub-sample
+    // come from per-offset coordinate tables that this variant's own mm_prologue_clip writes.  Filters without native
+    // calls and without a per-row slice only (the slice's values follow y: such filters take the maps path).
+    bool sampled = false;
+    bool variant() const { return shutter || sampled; }      // a second generation from the code of the main text
 };
 
 // One native-filter (or render) call found in the frame-constant code.
@@ -79,6 +85,7 @@ void clip_kernel_source(const KernelSource &ks, std::string *source, std::string
 const char *clip_prelude();
 const char *clip_prelude_natives();   // ... of a filter with native-filter calls: mm_clip.images_stride
 const char *shutter_prelude();        // mm_shutter, behind clip_prelude() in the shutter variant (KernelOptions::shutter)
+const char *sampled_prelude();        // mm_sampled, behind clip_prelude() in the sampled variant (KernelOptions::sampled)
 const char *device_prelude();
 const char *device_noise_prelude();   // mm_noise_device.h
 const char *device_fastmath_prelude();   // mm_fastmath.h + tables

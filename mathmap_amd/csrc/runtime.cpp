@@ -188,6 +188,7 @@ void mmhip_filter_free(mmhip_filter *f) {
     if (f->mod) (void)hipModuleUnload(f->mod);
     if (f->clip_mod) (void)hipModuleUnload(f->clip_mod);
     if (f->shutter_mod) (void)hipModuleUnload(f->shutter_mod);
+    if (f->sampled_mod) (void)hipModuleUnload(f->sampled_mod);
     delete f;
 }
 
@@ -386,6 +387,45 @@ long mmhip_filter_jit_shutter(mmhip_filter *f, int load_module) {
     }
     f->jit_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return (long)f->shutter_code_object.size();
+}
+
+// The sampled variant's text (hipgen.h KernelOptions::sampled), like the shutter variant's: generated when first asked
+// for, the other three texts not touched.
+static const mm::KernelSource *sampled_source(mmhip_filter *f) {
+    if (!f->sampled_ks.source.empty()) return &f->sampled_ks;
+    if (!f->ks.natives.empty() || !f->closures.empty() || f->ks.row_values > 0) {
+        fail("filter `" + f->module.main->name + "' has no sampled variant: it calls native filters, renders closure images or has a per-row slice");
+        return nullptr;
+    }
+    if (!f->code) { fail("filter has no sampled variant: its code was not kept"); return nullptr; }
+    try {
+        KernelOptions ko = f->kopt;
+        ko.sampled = true;
+        f->sampled_ks = generate_hip(*f->code, ko);
+    } catch (const std::exception &e) {
+        f->sampled_ks = mm::KernelSource();
+        fail(e.what());
+        return nullptr;
+    }
+    f->sampled_ks.prologue_name = "mm_prologue_clip";
+    return &f->sampled_ks;
+}
+
+const char *mmhip_filter_sampled_kernel_source(mmhip_filter *f) {
+    const mm::KernelSource *ks = sampled_source(f);
+    return ks ? ks->source.c_str() : nullptr;
+}
+
+long mmhip_filter_jit_sampled(mmhip_filter *f, int load_module) {
+    auto t0 = std::chrono::steady_clock::now();
+    const mm::KernelSource *ks = sampled_source(f);
+    if (!ks || jit_source(*ks, f->sampled_code_object) != 0) return -1;
+    if (load_module && !f->sampled_loaded) {
+        if (load_kernels(*ks, f->sampled_code_object, &f->sampled_mod, &f->f_pix_sampled, &f->f_pro_sampled) != 0) return -1;
+        f->sampled_loaded = true;
+    }
+    f->jit_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return (long)f->sampled_code_object.size();
 }
 
 // ---------------------------------------------------------------------------

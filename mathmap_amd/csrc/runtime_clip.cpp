@@ -1,12 +1,14 @@
 // Clip rendering: the frames of an animation in batched launches (mmhip_render_clip), supersampled
 // (mmhip_render_clip_supersampled) and motion-blurred (mmhip_render_clip_shutter through sub-sample maps,
-// mmhip_render_clip_shutter_fused in the pixel kernel's registers), on top of the single-frame path of runtime.cpp.
+// mmhip_render_clip_shutter_fused in the pixel kernel's registers) and grid-supersampled (mmhip_render_clip_sampled,
+// mmhip_render_clip_sampled_fused: the same two ways), on top of the single-frame path of runtime.cpp.
 // (The exported functions have C linkage from include/mmhip.h.)
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 
+#include "mm_sample_grid.h"
 #include "mm_shutter_combine.h"
 #include "runtime_internal.h"
 
@@ -491,9 +493,13 @@ int mmhip_render_clip_supersampled(mmhip_invocation *inv, int num_frames, const 
 // ---- motion-blurred clips ----
 // How mmhip_render_clip_shutter cuts a clip into batches and a frame's sub-samples into passes (include/mmhip.h has the
 // rules).  MMHIP_CLIP_SHUTTER_BYTES is read once, default 8 GiB.
+static size_t clip_shutter_budget() {
+    static const size_t budget = env_bytes("MMHIP_CLIP_SHUTTER_BYTES", (size_t)8 << 30);
+    return budget;
+}
 struct ClipShutterPlan { int per_batch = 1, batches = 1, samples_per_pass = 1, passes = 1, carry = 0; size_t bytes_per_sample = 0; };
 static ClipShutterPlan clip_shutter_plan(int num_rows, int render_w, int samples, int frames) {
-    static const size_t budget = env_bytes("MMHIP_CLIP_SHUTTER_BYTES", (size_t)8 << 30);
+    const size_t budget = clip_shutter_budget();
     ClipShutterPlan p;
     p.bytes_per_sample = (size_t)num_rows * 16 * (size_t)render_w;
     const size_t frame_bytes = (size_t)samples * p.bytes_per_sample;
@@ -693,6 +699,227 @@ int mmhip_render_clip_shutter_fused(mmhip_invocation *inv, int num_frames, const
         inv->clip_prologue_frames += pro_slots;
         if (timed_pixel_launch(inv, f->f_pix_shutter, (unsigned)plan.grid_x, (unsigned)n, params, s) != 0) return -1;
         ++inv->clip_shutter_fused_batches;
+    }
+    return 0;
+}
+
+// ---- grid-supersampled clips ----
+// The checks both sampled entry points make of the grid and the sub-sample count, under the name of the one called.
+static int clip_sampled_check(const char *who, int samples, int grid_x, int grid_y) {
+    if (grid_x < 1 || grid_x > MMHIP_SAMPLE_GRID_MAX || grid_y < 1 || grid_y > MMHIP_SAMPLE_GRID_MAX)
+        return fail(std::string(who) + ": grid_x and grid_y must be 1 to " + std::to_string((int)MMHIP_SAMPLE_GRID_MAX) + ", not " +
+                    std::to_string(grid_x) + " x " + std::to_string(grid_y));
+    if (clip_shutter_check_samples(who, samples) != 0) return -1;
+    if (samples * grid_x * grid_y > MMHIP_SHUTTER_MAX_SAMPLES)
+        return fail(std::string(who) + ": samples * grid_x * grid_y must be at most " + std::to_string((int)MMHIP_SHUTTER_MAX_SAMPLES) + ", not " +
+                    std::to_string(samples * grid_x * grid_y));
+    return 0;
+}
+
+// How mmhip_render_clip_sampled cuts a clip into batches and a frame's time steps into passes (include/mmhip.h has the
+// rules): the shutter's plan with G = grid_x * grid_y maps per time step, under the same budget.
+struct ClipSampledPlan { int per_batch = 1, batches = 1, steps_per_pass = 1, passes = 1, carry = 0; size_t bytes_per_sample = 0; };
+static ClipSampledPlan clip_sampled_plan(int num_rows, int render_w, int samples, int grid, int frames) {
+    const size_t budget = clip_shutter_budget();
+    ClipSampledPlan p;
+    p.bytes_per_sample = (size_t)num_rows * 16 * (size_t)render_w;
+    const size_t frame_bytes = (size_t)samples * grid * p.bytes_per_sample;
+    if (budget >= frame_bytes) {
+        p.per_batch = (int)std::min<size_t>({budget / frame_bytes, (size_t)65535, (size_t)frames});
+        p.steps_per_pass = samples;
+    } else {
+        // not one frame's sub-samples: a frame at a time, in passes of whole time steps beside the carry map (at least one step)
+        p.steps_per_pass = (int)std::max<long long>(1, ((long long)(budget / p.bytes_per_sample) - 1) / grid);
+        p.passes = (samples + p.steps_per_pass - 1) / p.steps_per_pass;
+        p.carry = p.passes > 1;
+    }
+    p.batches = (frames + p.per_batch - 1) / p.per_batch;
+    return p;
+}
+
+int mmhip_filter_clip_sampled_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int samples, int grid_x, int grid_y,
+                                   int frames, int64_t *out) {
+    (void)f;
+    if (frames < 1) return fail("clip sampled plan: num_frames must be at least 1");
+    if (clip_sampled_check("clip sampled plan", samples, grid_x, grid_y) != 0) return -1;
+    if (region_w < 1 || num_rows < 1 || render_w < region_w) return fail("clip sampled plan: empty region, or one wider than the render width");
+    const ClipSampledPlan p = clip_sampled_plan(num_rows, render_w, samples, grid_x * grid_y, frames);
+    const int64_t v[MMHIP_CLIP_SAMPLED_PLAN_FIELDS] = {p.per_batch, p.batches, p.steps_per_pass, p.passes, (int64_t)p.bytes_per_sample, p.carry};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+long mmhip_clip_sampled_batches(mmhip_invocation *inv) { return inv->clip_sampled_batches; }
+
+int mmhip_render_clip_sampled(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
+                              int grid_x, int grid_y, int region_x, int region_y, int region_w, int region_h, int first_row,
+                              int last_row, void *out_device, int row_stride, int64_t frame_stride, int bpp, int floatmap, void *stream) {
+    const char *who = "render_clip_sampled";
+    if (grid_x == 1 && grid_y == 1)      // one sample per pixel: the motion-blurred clip itself (and with samples = 1 the plain one)
+        return mmhip_render_clip_shutter(inv, num_frames, frames, ts, samples, span, region_x, region_y, region_w, region_h, first_row,
+                                         last_row, out_device, row_stride, frame_stride, bpp, floatmap, stream);
+    if (clip_sampled_check(who, samples, grid_x, grid_y) != 0) return -1;
+    if (!std::isfinite(span)) return fail(std::string(who) + ": span must be finite");
+    if (check_clip_args(who, num_frames, frames, ts, bpp, region_w, region_h) != 0) return -1;
+    const int first_arg = first_row, last_arg = last_row;
+    if (!clamp_rows(region_y, region_h, &first_row, &last_row)) return 0;
+    const int num_rows = last_row - first_row;
+    if (check_frame_stride(who, inv, frame_stride, num_rows, region_w, row_stride, bpp, floatmap) != 0) return -1;
+    if (region_w > inv->render_w) return fail(std::string(who) + ": the region is wider than the render width");
+    const int grid = grid_x * grid_y;
+    const ClipSampledPlan plan = clip_sampled_plan(num_rows, inv->render_w, samples, grid, num_frames);
+    const size_t bps = plan.bytes_per_sample;
+    if (bps > ((size_t)1 << 32)) return fail(std::string(who) + ": a sub-sample map of more than 4 GiB; render the frame in row bands");
+    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
+    // the shutter's temporary: [frame][time step][grid point] maps, the carry map behind them
+    const size_t slots = (size_t)plan.per_batch * plan.steps_per_pass * grid;
+    if (inv->clip_shutter.grow((slots + plan.carry) * bps, hipDeviceSynchronize) != hipSuccess)
+        return fail("out of device memory for the sub-samples of a grid-supersampled clip; lower MMHIP_CLIP_SHUTTER_BYTES");
+    unsigned char *subs = inv->clip_shutter.get<unsigned char>(), *carry = plan.carry ? subs + slots * bps : nullptr;
+    const float inv_k = mm_shutter_inv_k(samples * grid);
+    SamplingOffsetGuard offsets(inv);
+    std::vector<int> sub_frames;
+    std::vector<float> sub_ts;
+    for (int b0 = 0; b0 < num_frames; b0 += plan.per_batch) {
+        const int n = std::min(plan.per_batch, num_frames - b0);
+        for (int j0 = 0; j0 < samples; j0 += plan.steps_per_pass) {
+            const int count = std::min(plan.steps_per_pass, samples - j0);
+            sub_frames.resize((size_t)n * count);
+            sub_ts.resize((size_t)n * count);
+            for (int i = 0; i < n; ++i)
+                for (int j = 0; j < count; ++j) {
+                    sub_frames[(size_t)i * count + j] = frames[b0 + i];
+                    sub_ts[(size_t)i * count + j] = mm_shutter_sample_t(ts[b0 + i], span, j0 + j, samples);
+                }
+            // grid point g = b * grid_x + a of entry e = i * count + j lands at (e * G + g) * bps: the layout [i][j][g]
+            for (int b = 0; b < grid_y; ++b)
+                for (int a = 0; a < grid_x; ++a) {
+                    offsets.set(mm_sample_grid_offset(a, grid_x), mm_sample_grid_offset(b, grid_y));
+                    if (mmhip_render_clip(inv, n * count, sub_frames.data(), sub_ts.data(), region_x, region_y, region_w, region_h, first_arg,
+                                          last_arg, subs + (size_t)(b * grid_x + a) * bps, row_stride, (int64_t)grid * (int64_t)bps, bpp, 1, s) != 0)
+                        return -1;
+                }
+            const bool last = j0 + count >= samples;
+            std::string err;
+            if (launch_shutter_combine_clip(subs, (int64_t)bps, (int64_t)count * grid * (int64_t)bps, count * grid, j0 > 0 ? carry : nullptr,
+                                            last ? nullptr : carry, (char *)out_device + (int64_t)b0 * frame_stride, region_w, num_rows,
+                                            inv->render_w, row_stride, frame_stride, bpp, floatmap, inv_k, n, inv->ws, s, &err) != 0)
+                return fail(err);
+        }
+        ++inv->clip_sampled_batches;
+    }
+    return 0;
+}
+
+// ---- grid-supersampled clips, fused ----
+// mm_sampled of the sampled variant's kernels (hipgen.cpp sampled_prelude)
+struct HSampled { const float *offs; float *xtabs; float *ytabs; int samples, gx, gy, total; float inv_k; int pad; };
+static_assert(sizeof(HSampled) == 48, "mm_sampled layout");
+
+// How mmhip_render_clip_sampled_fused cuts a clip into batches: the fused shutter's plan with K * G sub-samples per pixel
+// and K slots per frame.  fused false: the call is mmhip_render_clip_sampled.
+static ClipShutterFusedPlan clip_sampled_fused_plan(const mmhip_filter *f, int region_w, int num_rows, int samples, int grid_x, int grid_y, int frames) {
+    ClipShutterFusedPlan p = clip_shutter_fused_plan(f, region_w, num_rows, samples, frames);
+    // the per-row slice's values follow y: such filters take the maps path; so do regions whose tables an int does not index
+    if (p.fused && (f->ks.row_values > 0 || (int64_t)grid_x * region_w > INT32_MAX || (int64_t)grid_y * num_rows > INT32_MAX)) {
+        p.fused = false;
+        p.per_batch = p.batches = p.slots_per_batch = 0;
+    }
+    return p;
+}
+
+int mmhip_filter_clip_sampled_fused_plan(const mmhip_filter *f, int region_w, int num_rows, int samples, int grid_x, int grid_y, int frames,
+                                         int64_t *out) {
+    if (frames < 1) return fail("clip sampled fused plan: num_frames must be at least 1");
+    if (clip_sampled_check("clip sampled fused plan", samples, grid_x, grid_y) != 0) return -1;
+    if (region_w < 1 || num_rows < 1) return fail("clip sampled fused plan: empty region");
+    const ClipShutterFusedPlan p = grid_x * grid_y == 1 ? clip_shutter_fused_plan(f, region_w, num_rows, samples, frames)
+                                                        : clip_sampled_fused_plan(f, region_w, num_rows, samples, grid_x, grid_y, frames);
+    const int64_t v[MMHIP_CLIP_SAMPLED_FUSED_PLAN_FIELDS] = {p.fused, p.per_batch, p.batches, p.fused ? p.slots_per_batch : 0, p.grid_x};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+long mmhip_clip_sampled_fused_batches(mmhip_invocation *inv) { return inv->clip_sampled_fused_batches; }
+
+int mmhip_render_clip_sampled_fused(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
+                                    int grid_x, int grid_y, int region_x, int region_y, int region_w, int region_h, int first_row,
+                                    int last_row, void *out_device, int row_stride, int64_t frame_stride, int bpp, int floatmap,
+                                    void *stream) {
+    const char *who = "render_clip_sampled_fused";
+    if (grid_x == 1 && grid_y == 1)      // one sample per pixel: the fused motion-blurred clip itself
+        return mmhip_render_clip_shutter_fused(inv, num_frames, frames, ts, samples, span, region_x, region_y, region_w, region_h, first_row,
+                                               last_row, out_device, row_stride, frame_stride, bpp, floatmap, stream);
+    if (clip_sampled_check(who, samples, grid_x, grid_y) != 0) return -1;
+    if (!std::isfinite(span)) return fail(std::string(who) + ": span must be finite");
+    if (check_clip_args(who, num_frames, frames, ts, bpp, region_w, region_h) != 0) return -1;
+    const int first_arg = first_row, last_arg = last_row;
+    if (!clamp_rows(region_y, region_h, &first_row, &last_row)) return 0;
+    const int num_rows = last_row - first_row;
+    if (check_frame_stride(who, inv, frame_stride, num_rows, region_w, row_stride, bpp, floatmap) != 0) return -1;
+    if (region_w > inv->render_w) return fail(std::string(who) + ": the region is wider than the render width");
+    mmhip_filter *f = active_filter(inv, frames[0], ts[0]);
+    const ClipShutterFusedPlan plan = clip_sampled_fused_plan(f, region_w, num_rows, samples, grid_x, grid_y, num_frames);
+    if (!plan.fused)        // native calls, closure images, a per-row slice, a frame too large for one launch: the sub-sample maps
+        return mmhip_render_clip_sampled(inv, num_frames, frames, ts, samples, span, grid_x, grid_y, region_x, region_y, region_w, region_h,
+                                         first_arg, last_arg, out_device, row_stride, frame_stride, bpp, floatmap, stream);
+    if (mmhip_filter_jit_sampled(f, 1) < 0) return -1;
+    const KernelSource &ks = f->sampled_ks;
+    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
+    if (upload_tables(inv, s) != 0) return -1;
+
+    HArgs a = render_args(inv, frames[0], ts[0], region_x, region_y, region_w, region_h, first_row, last_row, out_device, row_stride, bpp, floatmap);
+    // the coordinate tables are the single-frame path's, rewritten here: its prologue must run again
+    if (grow_launch_buffers(inv->launch, ks, region_w, num_rows, false, s) != 0) return -1;
+    inv->pro_filter = nullptr;
+    auto wait = [s] { return hipStreamSynchronize(s); };
+    HIP_TRY(inv->clip.xy.grow(plan.xy_stride * plan.slots_per_batch, wait, true));
+    const size_t xtab_floats = (size_t)grid_x * region_w, ytab_floats = (size_t)grid_y * num_rows;
+    HIP_TRY(inv->clip_sampled.grow((xtab_floats + ytab_floats) * sizeof(float), wait));
+    // the {t, frame} table of every time step of the call -- slot i * samples + j is step j of output frame i -- and behind
+    // it, in the same upload, the grid's offsets: those along x from float 0, those along y from float MM_SAMPLE_GRID_MAX
+    const size_t slots = (size_t)num_frames * samples, offs_entries = 2 * MM_SAMPLE_GRID_MAX * sizeof(float) / sizeof(HClipFrame);
+    ClipBuffers::Table *tab = nullptr;
+    if (next_clip_table(inv, slots + offs_entries, s, &tab) != 0) return -1;
+    HClipFrame *hf = (HClipFrame *)tab->host.p;
+    for (int i = 0; i < num_frames; ++i)
+        for (int j = 0; j < samples; ++j) hf[(size_t)i * samples + j] = HClipFrame{mm_shutter_sample_t(ts[i], span, j, samples), frames[i]};
+    float *offs = (float *)(hf + slots);
+    for (int k = 0; k < MM_SAMPLE_GRID_MAX; ++k) {
+        offs[k] = k < grid_x ? mm_sample_grid_offset(k, grid_x) : 0.0f;
+        offs[MM_SAMPLE_GRID_MAX + k] = k < grid_y ? mm_sample_grid_offset(k, grid_y) : 0.0f;
+    }
+    if (send_clip_table(*tab, slots + offs_entries, s) != 0) return -1;
+
+    a.xtab = inv->launch.xtab.get<float>();
+    a.ytab = inv->launch.ytab.get<float>();
+    a.ppt = plan.geo.ppt;
+    a.tiles_magic = plan.geo.tiles_magic;
+    char *xy = inv->clip.xy.get<char>();
+    HClip c{};
+    c.frame_stride = frame_stride;
+    c.xy_stride = plan.per_frame ? (int)plan.xy_stride : 0;
+    c.nwg = (int)plan.geo.nwg;
+    HSampled sm{};
+    sm.offs = (const float *)(tab->dev.get<HClipFrame>() + slots);
+    sm.xtabs = inv->clip_sampled.get<float>();
+    sm.ytabs = sm.xtabs + xtab_floats;
+    sm.samples = samples;
+    sm.gx = grid_x;
+    sm.gy = grid_y;
+    sm.total = samples * grid_x * grid_y;
+    sm.inv_k = mm_shutter_inv_k(sm.total);
+    void *params[] = {&a, &xy, &c, &sm};
+    for (int b0 = 0; b0 < num_frames; b0 += plan.per_batch) {
+        const int n = std::min(plan.per_batch, num_frames - b0);
+        a.out = (char *)out_device + (int64_t)b0 * frame_stride;
+        c.frames = tab->dev.get<HClipFrame>() + (size_t)b0 * samples;
+        // (the coordinate tables are written by the first batch's prologue and stay: they depend on the geometry alone)
+        const int pro_slots = launch_clip_prologue(f->f_pro_sampled, nullptr, a, plan.per_frame, b0, n * samples, params, s);
+        if (pro_slots < 0) return -1;
+        inv->clip_prologue_frames += pro_slots;
+        if (timed_pixel_launch(inv, f->f_pix_sampled, (unsigned)plan.grid_x, (unsigned)n, params, s) != 0) return -1;
+        ++inv->clip_sampled_fused_batches;
     }
     return 0;
 }

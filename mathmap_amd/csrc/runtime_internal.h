@@ -54,6 +54,13 @@ struct mmhip_filter {
     hipModule_t shutter_mod = nullptr;
     hipFunction_t f_pro_shutter = nullptr, f_rows_shutter = nullptr, f_pix_shutter = nullptr;
     bool shutter_loaded = false;
+    // the sampled variant (mmhip_render_clip_sampled_fused, KernelOptions::sampled): the same again, under its own key;
+    // filters without native calls, closure images or a per-row slice
+    mm::KernelSource sampled_ks;
+    std::vector<char> sampled_code_object;
+    hipModule_t sampled_mod = nullptr;
+    hipFunction_t f_pro_sampled = nullptr, f_pix_sampled = nullptr;
+    bool sampled_loaded = false;
     // user-value specialisation (specialize.cpp): kernels with the scalar user values baked in,
     // keyed by the value bytes; owned by this filter
     std::string source;
@@ -229,6 +236,10 @@ struct mmhip_invocation {
                                            // (mmhip_render_clip_shutter), and behind them the carry map where one is needed
     long clip_shutter_batches = 0;         // mmhip_clip_shutter_batches
     long clip_shutter_fused_batches = 0;   // mmhip_clip_shutter_fused_batches
+    long clip_sampled_batches = 0;         // mmhip_clip_sampled_batches
+    long clip_sampled_fused_batches = 0;   // mmhip_clip_sampled_fused_batches
+    DeviceBuffer clip_sampled;             // of a fused grid-supersampled batch: the grid's offsets (16 floats), then the
+                                           // per-offset x tables and y tables (mm_sampled, hipgen.cpp sampled_prelude)
     uint32_t edge_color_x = 0, edge_color_y = 0;
     float sampling_offset_x = 0.f, sampling_offset_y = 0.f;
     bool timing = false;
@@ -305,4 +316,5 @@ struct SamplingOffsetGuard {
     explicit SamplingOffsetGuard(mmhip_invocation *i) : inv(i), ox(i->sampling_offset_x), oy(i->sampling_offset_y) {}
     ~SamplingOffsetGuard() { inv->sampling_offset_x = ox; inv->sampling_offset_y = oy; }
     void set(float v) { inv->sampling_offset_x = inv->sampling_offset_y = v; }
+    void set(float x, float y) { inv->sampling_offset_x = x; inv->sampling_offset_y = y; }
 };
