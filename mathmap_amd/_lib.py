@@ -148,6 +148,7 @@ SELFTEST_SYMBOLS = {
     "mmhip_selftest_eval_unary": (C.c_int, [C.c_int, C.c_uint, C.c_ulonglong, C.c_void_p]),
     "mmhip_selftest_eval_binary": (C.c_int, [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_void_p]),
     "mmhip_selftest_gauss_tolerance_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    "mmhip_selftest_gauss_line_plan": (None, [C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int)]),
     "mmhip_selftest_combine_ms": (C.c_long, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "mmhip_selftest_shutter_combine": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
                                                  C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double)]),

@@ -545,6 +545,12 @@ int mmhip_selftest_gauss_tolerance_map(const uint8_t *rgb, int w, int h, float h
     return mmhip_copy_to_host(map, inv->natives[0].map.get(), (size_t)w * h * 16) == 0 ? 0 : -1;
 }
 
+// {segment length, halo, number of segments} of one pass of gaussian_blur's recursive path (mm::gaussian_blur_line_plan):
+// what a test needs to restate a split pass segment by segment.
+void mmhip_selftest_gauss_line_plan(int n, int lines, float sigma, int tolerance, int *out) {
+    mm::gaussian_blur_line_plan(n, lines, sigma, tolerance, out);
+}
+
 // The two supersampling combines on the same slices (tools/clip_ss_cost.py, tests/test_gpu_clip_supersample.py): `frames`
 // frames of w x h slices of pseudo-random bytes (every frame its own copy, for either kernel), combined frame by frame by launch_supersample_combine (what
 // mmhip_render_supersampled runs) and by one launch_supersample_combine_clip, alternating for `rounds` rounds with device

@@ -77,6 +77,11 @@ int run_native_filter(const std::string &func, const HNativeRec &rec, const std:
                       std::string *err, int *row_lo, int *row_hi,    // in: rows wanted, out: rows filled
                       NativeDirectOut *direct = nullptr);
 
+// How gaussian_blur splits one pass of its recursive path: lines of `n` steps, `lines` of them, a deviation of `sigma`
+// pixels; `tolerance`: the tolerance chain's plan instead of the exact chain's (which reads MMHIP_GAUSS_SEGMENTS per call).
+// out = {segment length, warm-up halo, number of segments}.  Read-only, for tests (abi_selftest.cpp).
+void gaussian_blur_line_plan(int n, int lines, float sigma, int tolerance, int out[3]);
+
 // ---- gaussian_blur over the frames of a clip (mmhip_render_clip) ----
 // One computation of a batch: a gaussian_blur call whose image argument is either a bound drawable of the render size
 // under the identity mapping or an earlier computation's float map, and whose deviations are at least half a pixel

@@ -1173,6 +1173,13 @@ int gaussian_blur(const HNativeRec &rec, const std::vector<HImageDesc> &images, 
 
 }  // namespace
 
+void gaussian_blur_line_plan(int n, int lines, float sigma, int tolerance, int out[3]) {
+    const LineArgs g = tolerance ? plan_tolerance(n, lines, sigma) : plan_segments(n, lines, sigma);
+    out[0] = g.seg;
+    out[1] = g.halo;
+    out[2] = (int)segment_count(g);
+}
+
 void gaussian_blur_batch_job_bytes(int render_w, int render_h, size_t *ckpt_bytes, size_t *map_bytes) {
     *ckpt_bytes = (checkpoint_bytes(render_w, render_h) + 255) & ~(size_t)255;
     *map_bytes = (size_t)render_w * render_h * 4 * sizeof(float);
