@@ -445,6 +445,71 @@ int mmhip_filter_clip_sampled_fused_plan(const mmhip_filter *f, int region_w, in
    none: NULL and -1, with a message. */
 const char *mmhip_filter_sampled_kernel_source(mmhip_filter *f);
 long mmhip_filter_jit_sampled(mmhip_filter *f, int load_module);
+/* An adaptively anti-aliased clip (an extension, opt-in): the grid-supersampled clip of mmhip_render_clip_sampled at
+   samples = 1, refined only where a single-sample render shows contrast.  Every output pixel equals one of two existing
+   renders, chosen by a mask computed from an existing render.  frames, ts, the region, the rows, out_device, row_stride,
+   frame_stride, bpp, floatmap and stream are mmhip_render_clip's; asynchronous.  Spatial only: there is no shutter.
+     - threshold is any float but NaN, which is refused before anything else is looked at.  mode is MMHIP_AA_REFINE_AUTO (0)
+       or MMHIP_AA_REFINE_SELECT (1: force the select path, below).  grid_x and grid_y are mmhip_render_clip_sampled's.
+     - grid_x = grid_y = 1 is mmhip_render_clip: the call delegates right after the threshold check.
+     - For every frame i, F is the float map mmhip_render_clip(floatmap = 1) produces for (frames[i], ts[i]) at sampling
+       offset (0, 0), whatever the invocation's offset, which is put back on every return, failed calls included.  The
+       rendered rectangle is the region's columns by the rows [first_row, last_row) clamped to the region.
+     - Clamp: c(v) = v < 0 ? 0 : (v > 1 ? 1 : v) in f32 -- NaN stays NaN, +inf becomes 1 and -inf 0.
+     - Pixel p is refined iff threshold < 0, or some 8-neighbour q of p inside the rendered rectangle and some channel ch
+       of the four give !(fabsf(c(F[p][ch]) - c(F[q][ch])) <= threshold): one f32 subtraction, no fma; a NaN contrast
+       refines.  Neighbours outside the rectangle are skipped, so a 1 x 1 rectangle is refined by a negative threshold only.
+     - A refined pixel receives exactly the bytes (or floats) mmhip_render_clip_sampled(samples = 1, grid_x, grid_y) gives
+       it: all G = grid_x * grid_y grid points evaluated afresh (F is not reused), summed in the order b * sx + a, scaled by
+       mm_shutter_inv_k(G), stored as mm_store_pixel stores.
+     - Every other pixel receives what the shutter combine stores for the single sample F[p]: acc = f_0, times
+       mm_shutter_inv_k(1), through mm_shutter_store_bytes at bpp 1 - 4 or as the four floats of a float map.
+     - Known property: the mask looks at the rendered rectangle only, so a frame rendered in row bands refines differently
+       at the band seams than a frame rendered whole.
+     - List path (auto mode; filters mmhip_render_clip_sampled_fused takes: no native calls, no closure images, no per-row
+       slice, a frame that fits one launch; region_w and rows at most 65 535), per batch of B frames: the nested
+       mmhip_render_clip of the B base maps at offset 0, one launch of the mask kernel (k_aa_contrast_clip: it stores the
+       pixels that are not refined, counts the refined ones per frame and appends them to the frame's list as
+       col | rl << 16, in no particular order), the refine variant's mm_prologue_clip, and mm_pixels_refine over a grid
+       of refine_grid_x = ceil(region_w * rows / 256) by B workgroups -- sized for the whole rectangle: the host never
+       reads a count while rendering, and work-items beyond a frame's count return.
+     - Select path (every other filter, larger regions, mode 1), per batch: the base maps, the nested
+       mmhip_render_clip_sampled(samples = 1) of the same frames into out_device, and the mask kernel without lists, which
+       overwrites the pixels that are not refined.  It saves no time; it exists so that nothing is refused and so that
+       one filter can be rendered both ways.
+     - Memory: B base maps of rows * 16 * render_width bytes and, on the list path, B lists of 4 bytes per pixel of the
+       rectangle, in a temporary of the invocation's under MMHIP_CLIP_SHUTTER_BYTES: frames_per_batch = min(max(1, budget
+       / bytes_per_frame), 65 535, num_frames) and, on the list path, at most the frames_per_batch of
+       mmhip_filter_clip_sampled_fused_plan at samples = 1.  One frame is allocated even over the budget.  (The nested
+       grid-supersampled clip of the select path has the shutter's temporary besides.)
+     - mmhip_clip_adaptive_batches rises by one per batch.  No other counter moves but those the nested calls move
+       themselves (the refine prologue is not counted in mmhip_clip_prologue_frames).  With mmhip_enable_timing the mask
+       launch is reported by mmhip_drain_native_kernel_ms as aa_contrast_clip and mm_pixels_refine by
+       mmhip_drain_kernel_ms, one entry per batch.
+   Errors: a NaN threshold; a grid outside 1 .. 8 or of more than 256 points; a mode that is neither constant; a base map
+   beyond 4 GiB; out of device memory; mmhip_render_clip's own. */
+enum { MMHIP_AA_REFINE_AUTO = 0, MMHIP_AA_REFINE_SELECT = 1, MMHIP_CLIP_ADAPTIVE_PLAN_FIELDS = 5 };
+int mmhip_render_clip_adaptive(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int grid_x, int grid_y,
+                               float threshold, int mode, int region_x, int region_y, int region_w, int region_h, int first_row,
+                               int last_row, void *out_device, int row_stride, int64_t frame_stride, int bpp, int floatmap,
+                               void *stream);
+long mmhip_clip_adaptive_batches(mmhip_invocation *inv);
+/* The refined pixels of every frame of the last mmhip_render_clip_adaptive call of this invocation: counts[i] for
+   i < min(n, frames of that call).  Waits for that call's stream.  Returns the frames of that call (0 after a call that
+   delegated to mmhip_render_clip), or -1. */
+int mmhip_clip_adaptive_refined(mmhip_invocation *inv, int64_t *counts, int n);
+/* How mmhip_render_clip_adaptive renders `frames` frames in auto mode (needs no GPU).  out[] receives
+   MMHIP_CLIP_ADAPTIVE_PLAN_FIELDS values: list_path (0: the select path), frames_per_batch, batches, bytes_per_frame (the
+   base map and, on the list path, the list) and refine_grid_x (0 on the select path). */
+int mmhip_filter_clip_adaptive_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int grid_x, int grid_y,
+                                    int frames, int64_t *out);
+/* The refine variant of the module -- the sampled variant's mm_prologue_clip, text unchanged, and mm_pixels_refine, which
+   is mm_pixels_sampled with the tile order replaced by a read of the frame's list -- and its gfx950 compile, like
+   mmhip_filter_sampled_kernel_source and mmhip_filter_jit_sampled: generated when first asked for, cached under its own
+   key, the other four texts untouched.  A filter with native calls, closure images or a per-row slice has none: NULL and
+   -1, with a message. */
+const char *mmhip_filter_refine_kernel_source(mmhip_filter *f);
+long mmhip_filter_jit_refine(mmhip_filter *f, int load_module);
 /* Convenience: whole frame to a host RGBA8 buffer (width*height*4 bytes); synchronous. */
 int mmhip_render_host(mmhip_invocation *inv, int frame, float t, uint8_t *out_rgba);
 int mmhip_sync(mmhip_invocation *inv);

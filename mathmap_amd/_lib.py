@@ -117,6 +117,14 @@ SYMBOLS = {
     "mmhip_filter_clip_sampled_fused_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "mmhip_filter_sampled_kernel_source": (C.c_char_p, [C.c_void_p]),
     "mmhip_filter_jit_sampled": (C.c_long, [C.c_void_p, C.c_int]),
+    "mmhip_render_clip_adaptive": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.c_int,
+                                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int,
+                                             C.c_int, C.c_void_p]),
+    "mmhip_clip_adaptive_batches": (C.c_long, [C.c_void_p]),
+    "mmhip_clip_adaptive_refined": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "mmhip_filter_clip_adaptive_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "mmhip_filter_refine_kernel_source": (C.c_char_p, [C.c_void_p]),
+    "mmhip_filter_jit_refine": (C.c_long, [C.c_void_p, C.c_int]),
     "mmhip_render_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "mmhip_sync": (C.c_int, [C.c_void_p]),
     "mmhip_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),

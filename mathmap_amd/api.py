@@ -35,6 +35,8 @@ SHUTTER_MAX_SAMPLES = 256
 CLIP_SHUTTER_FUSED_PLAN_FIELDS = ("fused", "frames_per_batch", "batches", "slots_per_batch", "grid_x")
 # render_clip's shutter_mode: the sub-sample maps of mmhip_render_clip_shutter, or mmhip_render_clip_shutter_fused
 SHUTTER_MODES = ("maps", "fused")
+AA_REFINE_MODES = ("list", "select")      # mmhip_render_clip_adaptive's mode 0 (auto) and 1
+CLIP_ADAPTIVE_PLAN_FIELDS = ("list_path", "frames_per_batch", "batches", "bytes_per_frame", "refine_grid_x")
 CLIP_SAMPLED_PLAN_FIELDS = ("frames_per_batch", "batches", "steps_per_pass", "passes", "bytes_per_sample", "carry")
 SAMPLE_GRID_MAX = 8
 
@@ -276,6 +278,31 @@ class Filter:
             raise MathMapError(_err())
         return dict(zip(CLIP_SHUTTER_FUSED_PLAN_FIELDS, out))
 
+    def clip_adaptive_plan(self, region_w, num_rows, render_w, aa, frames):
+        """How render_clip(aa=aa, aa_threshold=T) renders a `frames`-frame clip: a dict of the CLIP_ADAPTIVE_PLAN_FIELDS
+        (list_path 0: the filter or the region takes the select path)."""
+        sx, sy = sample_grid(aa)
+        out = (C.c_int64 * len(CLIP_ADAPTIVE_PLAN_FIELDS))()
+        if lib().mmhip_filter_clip_adaptive_plan(self._h, region_w, num_rows, render_w, sx, sy, frames, out) != 0:
+            raise MathMapError(_err())
+        return dict(zip(CLIP_ADAPTIVE_PLAN_FIELDS, out))
+
+    @property
+    def refine_kernel_source(self):
+        """The refine variant of kernel_source: kernels mm_prologue_clip (the sampled variant's) and mm_pixels_refine.  A
+        filter without a sampled variant has none: MathMapError."""
+        text = lib().mmhip_filter_refine_kernel_source(self._h)
+        if text is None:
+            raise MathMapError(_err())
+        return text.decode()
+
+    def jit_refine(self, load=False):
+        """hiprtc-compiles the refine variant for gfx950; returns the code-object size."""
+        n = lib().mmhip_filter_jit_refine(self._h, 1 if load else 0)
+        if n < 0:
+            raise MathMapError(_err())
+        return n
+
     @property
     def sampled_kernel_source(self):
         """The sampled variant of kernel_source: kernels mm_prologue_clip and mm_pixels_sampled.  A filter with native calls,
@@ -515,7 +542,7 @@ class Invocation:
 
     def render_clip(self, num_frames=None, frames=None, ts=None, out_ptr=None, rows=None, region=None, row_stride=None,
                     frame_stride=None, bpp=4, floatmap=False, stream=0, supersample=False, shutter_samples=1, shutter_span=None,
-                    shutter=None, shutter_mode="maps", aa=1):
+                    shutter=None, shutter_mode="maps", aa=1, aa_threshold=None, aa_refine="list"):
         """Renders a clip in batched launches (mmhip_render_clip): frame i at frame number frames[i] and time ts[i].
         `num_frames`=N alone is the CLI's animation: frame = i, t = (float)i / (float)N.  `rows` = (first_row,
         last_row) and `region`, `row_stride`, `bpp`, `floatmap`, `stream` as in render_rows; frame i lands
@@ -536,9 +563,26 @@ class Invocation:
         mmhip_render_clip_sampled_fused): every pixel is the mean, in float, of an sx x sy grid of sub-samples inside its
         footprint -- times the K shutter sub-samples where shutter_samples > 1, K * sx * sy being at most 256.  Without a
         shutter it needs no span.  Values outside the range, more than 256 sub-samples, or `aa` != 1 with
-        `supersample` (the -o frames, which stay what they are) are a ValueError; aa=1 changes nothing."""
+        `supersample` (the -o frames, which stay what they are) are a ValueError; aa=1 changes nothing.
+        `aa_threshold` = T (default None: not adaptive, and `aa_refine` is not looked at) renders the adaptively
+        anti-aliased clip (mmhip_render_clip_adaptive): a pixel gets the grid's mean only where a single-sample render,
+        clamped to 0..1, differs by more than T from one of its 8 neighbours in some channel (T < 0: everywhere), and
+        that render's value elsewhere.  `aa_refine`: "list" (default: the refined pixels alone are rendered, where the
+        filter allows it) or "select" (the whole grid render, then the choice): the same bytes.  Spatial only:
+        `aa_threshold` with `supersample` or shutter_samples > 1, a NaN, or another `aa_refine` is a ValueError."""
         from .striping import animation_frame_t
         grid = sample_grid(aa)
+        adaptive = aa_threshold is not None
+        if adaptive:
+            if supersample:
+                raise ValueError("render_clip: aa_threshold is not combined with supersample=True")
+            if int(shutter_samples) > 1:
+                raise ValueError("render_clip: aa_threshold is not combined with shutter_samples")
+            if aa_refine not in AA_REFINE_MODES:
+                raise ValueError("render_clip: aa_refine must be one of %s, not %r" % (", ".join(AA_REFINE_MODES), aa_refine))
+            aa_threshold = float(aa_threshold)
+            if aa_threshold != aa_threshold:
+                raise ValueError("render_clip: aa_threshold must not be NaN")
         if grid != (1, 1):
             if supersample:
                 raise ValueError("render_clip: aa is not combined with supersample=True")
@@ -554,6 +598,9 @@ class Invocation:
 
             def render_shutter(h, n, fp, tp, samples, span, *rest):
                 return sampled(h, n, fp, tp, samples, span, grid[0], grid[1], *rest)
+        if adaptive:
+            def render_shutter(h, n, fp, tp, samples, span, *rest):
+                return lib().mmhip_render_clip_adaptive(h, n, fp, tp, grid[0], grid[1], aa_threshold, AA_REFINE_MODES.index(aa_refine), *rest)
         if supersample and (floatmap or rows is not None):
             raise ValueError("render_clip: supersample=True renders whole regions of bytes: neither floatmap nor rows")
         shutter_samples = int(shutter_samples)
@@ -569,7 +616,7 @@ class Invocation:
             if num_frames < 1:
                 raise MathMapError("render_clip: num_frames must be at least 1")
             shutter_span = np.float32(np.float64(shutter) / np.float64(num_frames))
-        shuttered = shutter_samples != 1 or shutter_span is not None
+        shuttered = shutter_samples != 1 or shutter_span is not None or adaptive
         span = float(np.float32(shutter_span)) if shutter_span is not None else 0.0
         if frames is None and ts is None:
             if num_frames is None:
@@ -667,6 +714,21 @@ class Invocation:
     def clip_sampled_fused_batches(self):
         """Batches render_clip(aa != 1, shutter_mode="fused") rendered fused (0 for filters that take the maps path)."""
         return lib().mmhip_clip_sampled_fused_batches(self._h)
+
+    def clip_adaptive_batches(self):
+        """Batches render_clip(aa_threshold=T) has rendered so far, on either path."""
+        return lib().mmhip_clip_adaptive_batches(self._h)
+
+    def clip_adaptive_refined(self):
+        """The refined pixels of every frame of the last render_clip(aa_threshold=T) call: an int64 array (empty after a
+        call with aa=1).  Waits for that call."""
+        n = lib().mmhip_clip_adaptive_refined(self._h, None, 0)
+        if n < 0:
+            raise MathMapError(_err())
+        out = np.zeros(n, dtype=np.int64)
+        if n and lib().mmhip_clip_adaptive_refined(self._h, out.ctypes.data_as(C.POINTER(C.c_int64)), n) < 0:
+            raise MathMapError(_err())
+        return out
 
     def clip_supersampled_batches(self):
         """Batches render_clip(supersample=True) ran batched (0 for filters it renders frame by frame)."""

@@ -79,6 +79,16 @@ void usage() {
            "                              GPU; combines with --shutter-samples (K * SX * SY\n"
            "                              at most 256), --shutter-mode and --batch-frames;\n"
            "                              not combined with -o\n"
+           "      --aa-threshold=T        with --aa, adaptive anti-aliasing: only pixels\n"
+           "                              whose clamped value differs by more than T from\n"
+           "                              one of their 8 neighbours in a single-sample\n"
+           "                              render get the grid; the others keep that\n"
+           "                              render's value; not combined with -o or\n"
+           "                              --shutter-samples\n"
+           "      --aa-refine=MODE        with --aa-threshold, how the refined pixels are\n"
+           "                              rendered: list (default: they alone, where the\n"
+           "                              filter allows it) or select (the whole grid\n"
+           "                              render, then the choice); the files are the same\n"
            "\n"
            "Report bugs and suggestions to schani@complang.tuwien.ac.at\n",
            cache_size);
@@ -226,7 +236,7 @@ std::string frame_file(const std::string &pattern, int frame) {
 enum {
     OPT_VERSION = 256, OPT_HELP, OPT_HTMLDOC, OPT_BENCH_NO_OUTPUT, OPT_BENCH_ONLY_COMPILE,
     OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE, OPT_INPUT_FRAMES, OPT_BATCH_FRAMES,
-    OPT_NATIVE_INPUT_FRAME, OPT_SHUTTER_SAMPLES, OPT_SHUTTER, OPT_SHUTTER_MODE, OPT_AA
+    OPT_NATIVE_INPUT_FRAME, OPT_SHUTTER_SAMPLES, OPT_SHUTTER, OPT_SHUTTER_MODE, OPT_AA, OPT_AA_THRESHOLD, OPT_AA_REFINE
 };
 
 int main(int argc, char **argv) {
@@ -236,7 +246,9 @@ int main(int argc, char **argv) {
     int bench_render_count = 1, num_frames = 1, input_frames = 0, gauss_mode = MMHIP_GAUSS_EXACT, batch_frames = 1;
     int native_input_frame = MMHIP_NATIVE_FRAME_ZERO, shutter_samples = 1, aa_x = 1, aa_y = 1;
     double shutter = 0.5;
-    bool shutter_fused = false;
+    bool shutter_fused = false, adaptive = false, aa_refine_set = false;
+    float aa_threshold = 0.0f;
+    int aa_refine = MMHIP_AA_REFINE_AUTO;
     const char *generator = nullptr;
     std::vector<Define> defines;
     static struct option long_options[] = {
@@ -254,6 +266,7 @@ int main(int argc, char **argv) {
         {"native-input-frame", required_argument, 0, OPT_NATIVE_INPUT_FRAME},
         {"shutter-samples", required_argument, 0, OPT_SHUTTER_SAMPLES}, {"shutter", required_argument, 0, OPT_SHUTTER},
         {"shutter-mode", required_argument, 0, OPT_SHUTTER_MODE}, {"aa", required_argument, 0, OPT_AA},
+        {"aa-threshold", required_argument, 0, OPT_AA_THRESHOLD}, {"aa-refine", required_argument, 0, OPT_AA_REFINE},
         {0, 0, 0, 0}};
     for (;;) {
         int idx;
@@ -351,6 +364,19 @@ int main(int argc, char **argv) {
                 aa_y = (int)ny;
                 break;
             }
+            case OPT_AA_THRESHOLD: {
+                char *end = nullptr;
+                aa_threshold = strtof(optarg, &end);
+                if (end == optarg || *end || std::isnan(aa_threshold)) { fprintf(stderr, "Error: --aa-threshold takes a number, like 0.05.\n"); return 1; }
+                adaptive = true;
+                break;
+            }
+            case OPT_AA_REFINE:
+                if (!strcmp(optarg, "list")) aa_refine = MMHIP_AA_REFINE_AUTO;
+                else if (!strcmp(optarg, "select")) aa_refine = MMHIP_AA_REFINE_SELECT;
+                else { fprintf(stderr, "Error: --aa-refine takes list or select.\n"); return 1; }
+                aa_refine_set = true;
+                break;
             case OPT_SHUTTER: {
                 char *end = nullptr;
                 shutter = strtod(optarg, &end);
@@ -359,6 +385,22 @@ int main(int argc, char **argv) {
             }
             default: usage(); return 1;
         }
+    }
+    if (aa_refine_set && !adaptive) {
+        fprintf(stderr, "Error: --aa-refine goes with --aa-threshold.\n");
+        return 1;
+    }
+    if (adaptive && supersampling) {
+        fprintf(stderr, "Error: --aa-threshold is not combined with -o (oversampling).\n");
+        return 1;
+    }
+    if (adaptive && shutter_samples > 1) {
+        fprintf(stderr, "Error: --aa-threshold is not combined with --shutter-samples.\n");
+        return 1;
+    }
+    if (adaptive && aa_x * aa_y == 1) {
+        fprintf(stderr, "Error: --aa-threshold goes with --aa.\n");
+        return 1;
     }
     if (supersampling && shutter_samples > 1) {
         fprintf(stderr, "Error: --shutter-samples is not combined with -o (oversampling).\n");
@@ -495,6 +537,7 @@ int main(int argc, char **argv) {
     // --shutter-samples=K: the frames go through mmhip_render_clip_shutter (--shutter-mode=fused: ..._fused), --batch-frames of them per call (by default
     // one, all of its K sub-samples in one nested clip), at the span (float)((double)FRACTION / NUM).
     // --aa: they go through mmhip_render_clip_sampled (..._fused) instead, with or without a shutter.
+    // --aa-threshold: through mmhip_render_clip_adaptive.
     const bool shuttered = shutter_samples > 1 || sampled;
     const float shutter_span = (float)(shutter / (double)num_frames);
     batch_frames = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch_frames, num_frames), ((size_t)1 << 30) / output.size()));
@@ -509,7 +552,10 @@ int main(int argc, char **argv) {
                 frames[i] = first + i;
                 ts[i] = (float)(first + i) / (float)num_frames;       // mathmap_cmdline.c:835
             }
-            const int rc = sampled
+            const int rc = adaptive
+                               ? mmhip_render_clip_adaptive(inv, n, frames.data(), ts.data(), aa_x, aa_y, aa_threshold, aa_refine, 0, 0, img_width,
+                                                            img_height, 0, img_height, dev, img_width * 4, (int64_t)output.size(), 4, 0, nullptr)
+                           : sampled
                                ? (shutter_fused ? mmhip_render_clip_sampled_fused : mmhip_render_clip_sampled)(
                                      inv, n, frames.data(), ts.data(), shutter_samples, shutter_span, aa_x, aa_y, 0, 0, img_width, img_height, 0,
                                      img_height, dev, img_width * 4, (int64_t)output.size(), 4, 0, nullptr)

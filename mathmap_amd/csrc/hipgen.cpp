@@ -20,7 +20,8 @@
 // replaced, clip_kernel_source) and, generated on demand under KernelOptions::shutter, the shutter variant -- the clip
 // forms of the prologue and the per-row slice, and mm_pixels_shutter: the single shape's body in a loop over a pixel's
 // sub-samples (emit_shutter_pixel_kernel).  KernelOptions::sampled gives the same with mm_pixels_sampled, whose loop also
-// walks a grid of sampling offsets (emit_sampled_pixel_kernel).
+// walks a grid of sampling offsets (emit_sampled_pixel_kernel); with KernelOptions::refine the same kernel takes its pixels
+// from a list (mm_pixels_refine).
 //
 // The environment hooks for experiments that alter this text are the fields of struct Knobs (hipgen_internal.h).
 //
@@ -1224,17 +1225,30 @@ MM_DEV mm_image mm_native_result_in_loop(const mm_args &A, int &n, int sites) {
         if (ks.row_values > 0) throw CompileError("the sampled variant is for filters without a per-row slice");
         ks.single_pixel = true;
         ks.pair_mode = false;
-        ks.pixel_name = "mm_pixels_sampled";
+        ks.pixel_name = opt.refine ? "mm_pixels_refine" : "mm_pixels_sampled";
+        if (opt.refine) out << refine_prelude();
         if (knobs.waves_per_eu) out << "__attribute__((amdgpu_waves_per_eu(" << *knobs.waves_per_eu << "))) ";
-        out << KERNEL
-            << "mm_pixels_sampled(mm_args A, const char *__restrict__ XY, const mm_clip C, const mm_sampled S) {\n"
-               "  if ((int)blockIdx.x >= C.nwg) return;      // padding workgroup\n"
-               "  const int fi = blockIdx.y;                 // the output frame\n"
-               "  A.out = (char *)A.out + (long long)fi * C.frame_stride;\n";
-        emit_tile_order(false);
-        out << "  const int rl = row0;   // A.ppt is 1 for this kernel\n"
-               "  if (rl >= A.num_rows) return;\n"
-               "  const char *const mm_xy0 = XY;\n"
+        if (opt.refine) {
+            // the refine variant: work-item i of grid row fi renders entry i of frame fi's list, whatever the tile order
+            out << KERNEL
+                << "mm_pixels_refine(mm_args A, const char *__restrict__ XY, const mm_clip C, const mm_sampled S, const mm_refine R) {\n"
+                   "  const int fi = blockIdx.y;                 // the output frame\n"
+                   "  const unsigned mm_i = blockIdx.x * 256u + threadIdx.x;\n"
+                   "  if (mm_i >= R.counts[fi]) return;          // the launch covers the whole rectangle: the list may be shorter\n"
+                   "  A.out = (char *)A.out + (long long)fi * C.frame_stride;\n"
+                   "  const unsigned mm_e = R.list[(long long)fi * R.list_stride + mm_i];\n"
+                   "  const int col = (int)(mm_e & 0xffffu), rl = (int)(mm_e >> 16);      // col | rl << 16, by the mask kernel\n";
+        } else {
+            out << KERNEL
+                << "mm_pixels_sampled(mm_args A, const char *__restrict__ XY, const mm_clip C, const mm_sampled S) {\n"
+                   "  if ((int)blockIdx.x >= C.nwg) return;      // padding workgroup\n"
+                   "  const int fi = blockIdx.y;                 // the output frame\n"
+                   "  A.out = (char *)A.out + (long long)fi * C.frame_stride;\n";
+            emit_tile_order(false);
+            out << "  const int rl = row0;   // A.ppt is 1 for this kernel\n"
+                   "  if (rl >= A.num_rows) return;\n";
+        }
+        out << "  const char *const mm_xy0 = XY;\n"
                "  const float *const mm_xt = S.xtabs + col;      // this column in the table of grid column 0\n"
                "  const float *const mm_yt = S.ytabs + rl;       // this row in the table of grid row 0\n"
                "  const int mm_xend = S.gx * A.region_width, mm_yend = S.gy * A.num_rows;\n"
@@ -1406,6 +1420,12 @@ const char *shutter_prelude() { return "struct mm_shutter { int samples; float i
 const char *sampled_prelude() {
     return "#define MM_SAMPLE_GRID_MAX 8\n"
            "struct mm_sampled { const float *offs; float *xtabs; float *ytabs; int samples; int gx; int gy; int total; float inv_k; int pad; };\n";
+}
+
+// What mm_pixels_refine has besides those: every frame's list of the pixels to refine (col | rl << 16, list_stride entries
+// per frame) and the lists' lengths, as the mask kernel (k_aa_contrast_clip, native_filters.hip) left them.
+const char *refine_prelude() {
+    return "struct mm_refine { const unsigned *list; const unsigned *counts; long long list_stride; };\n";
 }
 
 void clip_kernel_source(const KernelSource &ks, std::string *source, std::string *key) {

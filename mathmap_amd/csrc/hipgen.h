@@ -27,6 +27,10 @@ struct KernelOptions {
     // come from per-offset coordinate tables that this variant's own mm_prologue_clip writes.  Filters without native
     // calls and without a per-row slice only (the slice's values follow y: such filters take the maps path).
     bool sampled = false;
+    // The refine variant (adaptive anti-aliasing, mmhip_render_clip_adaptive): the sampled variant's mm_prologue_clip,
+    // text unchanged, and mm_pixels_refine in place of mm_pixels_sampled -- the same loop over a pixel's sub-samples, the
+    // pixel taken from a per-frame list (mm_refine) instead of the tile order.  Set together with `sampled`.
+    bool refine = false;
     bool variant() const { return shutter || sampled; }      // a second generation from the code of the main text
 };
 
@@ -86,6 +90,7 @@ const char *clip_prelude();
 const char *clip_prelude_natives();   // ... of a filter with native-filter calls: mm_clip.images_stride
 const char *shutter_prelude();        // mm_shutter, behind clip_prelude() in the shutter variant (KernelOptions::shutter)
 const char *sampled_prelude();        // mm_sampled, behind clip_prelude() in the sampled variant (KernelOptions::sampled)
+const char *refine_prelude();         // mm_refine, in front of mm_pixels_refine in the refine variant (KernelOptions::refine)
 const char *device_prelude();
 const char *device_noise_prelude();   // mm_noise_device.h
 const char *device_fastmath_prelude();   // mm_fastmath.h + tables

@@ -153,5 +153,15 @@ int launch_supersample_combine_clip(const unsigned char *longs, const unsigned c
 int launch_shutter_combine_clip(const void *samples, int64_t sample_stride, int64_t frame_samples_stride, int count, const void *carry_in,
                                 void *carry_out, void *out, int region_w, int rows, int render_w, int row_stride, int64_t frame_stride,
                                 int bpp, int floatmap, float inv_k, int frames, NativeWorkspace &ws, hipStream_t s, std::string *err);
+// The contrast mask of an adaptively anti-aliased clip (k_aa_contrast_clip; mmhip_render_clip_adaptive states the rule)
+// over `frames` frames in one launch.  Frame i's base map is `rows` rows of render_w float4 at base + i *
+// base_frame_stride, the region's region_w columns at the start of each row.  A pixel that is not refined is stored at
+// out + i * frame_stride as the shutter combine stores a single sample (the same store modes); a refined one is left
+// alone, counted in counts[i] (which the caller has zeroed) and, where `list` is not null, appended to frame i's list at
+// list + i * list_stride as col | rl << 16, in no particular order.  Refused: what the shutter combine refuses, and with
+// a list a region beyond 65 535 columns or rows.  Timed through ws.timed_launch as aa_contrast_clip.
+int launch_aa_contrast_clip(const void *base, int64_t base_frame_stride, void *out, unsigned *counts, unsigned *list, int64_t list_stride,
+                            int region_w, int rows, int render_w, int row_stride, int64_t frame_stride, int bpp, int floatmap,
+                            float threshold, int frames, NativeWorkspace &ws, hipStream_t s, std::string *err);
 
 }  // namespace mm

@@ -1582,6 +1582,167 @@ int launch_shutter_combine_clip(const void *samples, int64_t sample_stride, int6
     return 0;
 }
 
+// ---- the contrast mask of an adaptively anti-aliased clip (mmhip_render_clip_adaptive states the rule) ----
+// Frame blockIdx.y of a batch per grid row, one tile of AA_TILE_W x AA_TILE_H pixels of the rendered rectangle per
+// workgroup, one pixel per lane.  A lane loads its own texel of the base map (kept as loaded for the store, clamped into
+// LDS), the first 84 lanes the tile's one-pixel halo; texels outside the rectangle are neither loaded nor compared.  A
+// pixel that is not refined is stored as the shutter combine stores a single sample; a refined one is counted -- one
+// atomicAdd per workgroup -- and, with LIST, appended to the frame's list as col | rl << 16 at the place its rank among
+// the workgroup's refined lanes (ballot, popcount) gives it in the range that atomicAdd reserved.
+struct AaArgs {
+    const unsigned char *base;
+    unsigned char *out;
+    unsigned *counts, *list;
+    long long base_frame_stride, frame_stride, list_stride;
+    int row_stride;
+    unsigned region_w, rows, render_w, tiles_x;
+    float threshold, inv_k;
+};
+
+constexpr int AA_TILE_W = 32, AA_TILE_H = 8, AA_HALO = 2 * (AA_TILE_W + 2) + 2 * AA_TILE_H;
+static_assert(AA_TILE_W * AA_TILE_H == 256 && AA_HALO <= 256, "one lane per pixel of the tile, the halo by the first lanes");
+
+__device__ __forceinline__ float aa_clamp(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
+__device__ __forceinline__ sh_f32x4 aa_clamp4(sh_f32x4 f) {
+    sh_f32x4 r;
+    r.x = aa_clamp(f.x);
+    r.y = aa_clamp(f.y);
+    r.z = aa_clamp(f.z);
+    r.w = aa_clamp(f.w);
+    return r;
+}
+// one f32 subtraction per channel; a NaN contrast refines
+__device__ __forceinline__ bool aa_contrast(sh_f32x4 p, sh_f32x4 q, float threshold) {
+    return !(fabsf(p.x - q.x) <= threshold) || !(fabsf(p.y - q.y) <= threshold) || !(fabsf(p.z - q.z) <= threshold) ||
+           !(fabsf(p.w - q.w) <= threshold);
+}
+
+template <int MODE, bool LIST>
+__global__ void __launch_bounds__(256) k_aa_contrast_clip(const AaArgs a) {
+    __shared__ sh_f32x4 tile[AA_TILE_H + 2][AA_TILE_W + 2];
+    __shared__ unsigned wave_n[4], wg_base;
+    const unsigned ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
+    const int x0 = (int)tx * AA_TILE_W, y0 = (int)ty * AA_TILE_H, w = (int)a.region_w, h = (int)a.rows;
+    const size_t fi = blockIdx.y;
+    const unsigned char *__restrict__ F = a.base + fi * a.base_frame_stride;
+    const int lx = threadIdx.x % AA_TILE_W, ly = threadIdx.x / AA_TILE_W;
+    const int col = x0 + lx, rl = y0 + ly;
+    const bool inside = col < w && rl < h;
+    const unsigned off = ((unsigned)rl * a.render_w + (unsigned)col) * 16u;      // below 2^32: the launcher refuses larger maps
+    sh_f32x4 raw = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (inside) {
+        raw = *(const sh_f32x4 *)(F + off);
+        tile[ly + 1][lx + 1] = aa_clamp4(raw);
+    }
+    if (threadIdx.x < AA_HALO) {
+        const int k = threadIdx.x;
+        int hx, hy;
+        if (k < AA_TILE_W + 2) { hx = k - 1; hy = -1; }
+        else if (k < 2 * (AA_TILE_W + 2)) { hx = k - (AA_TILE_W + 2) - 1; hy = AA_TILE_H; }
+        else if (k < 2 * (AA_TILE_W + 2) + AA_TILE_H) { hx = -1; hy = k - 2 * (AA_TILE_W + 2); }
+        else { hx = AA_TILE_W; hy = k - 2 * (AA_TILE_W + 2) - AA_TILE_H; }
+        const int gx = x0 + hx, gy = y0 + hy;
+        if (gx >= 0 && gx < w && gy >= 0 && gy < h)
+            tile[hy + 1][hx + 1] = aa_clamp4(*(const sh_f32x4 *)(F + ((unsigned)gy * a.render_w + (unsigned)gx) * 16u));
+    }
+    __syncthreads();
+    bool refine = false;
+    if (inside) {
+        refine = a.threshold < 0.0f;
+        const sh_f32x4 p = tile[ly + 1][lx + 1];
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                if (dx == 0 && dy == 0) continue;
+                const int qx = col + dx, qy = rl + dy;
+                if (qx >= 0 && qx < w && qy >= 0 && qy < h && aa_contrast(p, tile[ly + 1 + dy][lx + 1 + dx], a.threshold)) refine = true;
+            }
+    }
+    if (inside && !refine) {
+        sh_f32x4 m;
+        m.x = mm_shutter_scale(raw.x, a.inv_k);
+        m.y = mm_shutter_scale(raw.y, a.inv_k);
+        m.z = mm_shutter_scale(raw.z, a.inv_k);
+        m.w = mm_shutter_scale(raw.w, a.inv_k);
+        unsigned char *__restrict__ O = a.out + fi * a.frame_stride;
+        if (MODE == SHUTTER_FLOATMAP) *(sh_f32x4_a4 *)(O + off) = m;
+        else {
+            const int bpp = MODE == SHUTTER_WORDS ? 4 : MODE;
+            unsigned char *p = O + (long long)rl * a.row_stride + (unsigned)col * (unsigned)bpp;
+            if (MODE == SHUTTER_WORDS) *(unsigned *)p = pack_rgba8(make_float4(m.x, m.y, m.z, m.w));
+            else mm_shutter_store_bytes(p, m.x, m.y, m.z, m.w, bpp);
+        }
+    }
+    const unsigned long long ballot = __ballot(refine);
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_n[wave] = (unsigned)__popcll(ballot);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned total = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+        wg_base = total ? atomicAdd(a.counts + fi, total) : 0u;
+    }
+    if (LIST) {
+        __syncthreads();
+        if (refine) {
+            unsigned at = wg_base + (unsigned)__popcll(ballot & ((1ull << lane) - 1ull));
+            for (unsigned k = 0; k < wave; ++k) at += wave_n[k];
+            a.list[fi * a.list_stride + at] = (unsigned)col | ((unsigned)rl << 16);
+        }
+    }
+}
+
+int launch_aa_contrast_clip(const void *base, int64_t base_frame_stride, void *out, unsigned *counts, unsigned *list, int64_t list_stride,
+                            int region_w, int rows, int render_w, int row_stride, int64_t frame_stride, int bpp, int floatmap,
+                            float threshold, int frames, NativeWorkspace &ws, hipStream_t s, std::string *err) {
+    const int64_t map_bytes = (int64_t)rows * render_w * 16;
+    if (region_w < 1 || rows < 1 || render_w < region_w || frames < 1 || frames > 65535 || bpp < 1 || bpp > 4 || map_bytes > ((int64_t)1 << 32) ||
+        (list && (region_w > 65535 || rows > 65535 || list_stride < (int64_t)region_w * rows))) {
+        *err = "aa contrast: the batch does not fit one launch";
+        return -1;
+    }
+    if (((uintptr_t)base | (uintptr_t)base_frame_stride) % 16 != 0 || (floatmap && ((uintptr_t)out | (uintptr_t)frame_stride) % 4 != 0)) {
+        *err = "aa contrast: the float maps are not aligned";
+        return -1;
+    }
+    AaArgs a;
+    a.base = (const unsigned char *)base;
+    a.out = (unsigned char *)out;
+    a.counts = counts;
+    a.list = list;
+    a.base_frame_stride = base_frame_stride;
+    a.frame_stride = frame_stride;
+    a.list_stride = list_stride;
+    a.row_stride = row_stride;
+    a.region_w = (unsigned)region_w;
+    a.rows = (unsigned)rows;
+    a.render_w = (unsigned)render_w;
+    a.tiles_x = ((unsigned)region_w + AA_TILE_W - 1) / AA_TILE_W;
+    a.threshold = threshold;
+    a.inv_k = mm_shutter_inv_k(1);
+    const dim3 grid(a.tiles_x * (((unsigned)rows + AA_TILE_H - 1) / AA_TILE_H), (unsigned)frames);
+    const uintptr_t align = (uintptr_t)out | (uintptr_t)row_stride | (uintptr_t)frame_stride;
+    const int mode = floatmap ? SHUTTER_FLOATMAP : bpp == 4 && align % 4 == 0 ? SHUTTER_WORDS : bpp;
+    ws.timed_launch("aa_contrast_clip", s, [&] {
+#define MM_AA_LAUNCH(M)                                                       \
+    case M:                                                                   \
+        if (list) k_aa_contrast_clip<M, true><<<grid, 256, 0, s>>>(a);        \
+        else k_aa_contrast_clip<M, false><<<grid, 256, 0, s>>>(a);            \
+        break;
+        switch (mode) {
+            MM_AA_LAUNCH(SHUTTER_FLOATMAP)
+            MM_AA_LAUNCH(SHUTTER_BYTES1)
+            MM_AA_LAUNCH(SHUTTER_BYTES2)
+            MM_AA_LAUNCH(SHUTTER_BYTES3)
+            MM_AA_LAUNCH(SHUTTER_BYTES4)
+            MM_AA_LAUNCH(SHUTTER_WORDS)
+        }
+#undef MM_AA_LAUNCH
+    });
+    if (hipGetLastError() != hipSuccess) { *err = "aa contrast: kernel launch failed"; return -1; }
+    return 0;
+}
+
 int run_native_filter(const std::string &func, const HNativeRec &rec, const std::vector<HImageDesc> &images,
                       int render_w, int render_h, float *out_map, NativeWorkspace &ws, hipStream_t stream,
                       std::string *err, int *row_lo, int *row_hi, NativeDirectOut *direct) {

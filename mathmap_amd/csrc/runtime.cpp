@@ -189,6 +189,7 @@ void mmhip_filter_free(mmhip_filter *f) {
     if (f->clip_mod) (void)hipModuleUnload(f->clip_mod);
     if (f->shutter_mod) (void)hipModuleUnload(f->shutter_mod);
     if (f->sampled_mod) (void)hipModuleUnload(f->sampled_mod);
+    if (f->refine_mod) (void)hipModuleUnload(f->refine_mod);
     delete f;
 }
 
@@ -426,6 +427,45 @@ long mmhip_filter_jit_sampled(mmhip_filter *f, int load_module) {
     }
     f->jit_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return (long)f->sampled_code_object.size();
+}
+
+// The refine variant's text (hipgen.h KernelOptions::refine), like the sampled variant's and for the same filters:
+// generated when first asked for, the other four texts not touched.
+static const mm::KernelSource *refine_source(mmhip_filter *f) {
+    if (!f->refine_ks.source.empty()) return &f->refine_ks;
+    if (!f->ks.natives.empty() || !f->closures.empty() || f->ks.row_values > 0) {
+        fail("filter `" + f->module.main->name + "' has no refine variant: it calls native filters, renders closure images or has a per-row slice");
+        return nullptr;
+    }
+    if (!f->code) { fail("filter has no refine variant: its code was not kept"); return nullptr; }
+    try {
+        KernelOptions ko = f->kopt;
+        ko.sampled = ko.refine = true;
+        f->refine_ks = generate_hip(*f->code, ko);
+    } catch (const std::exception &e) {
+        f->refine_ks = mm::KernelSource();
+        fail(e.what());
+        return nullptr;
+    }
+    f->refine_ks.prologue_name = "mm_prologue_clip";
+    return &f->refine_ks;
+}
+
+const char *mmhip_filter_refine_kernel_source(mmhip_filter *f) {
+    const mm::KernelSource *ks = refine_source(f);
+    return ks ? ks->source.c_str() : nullptr;
+}
+
+long mmhip_filter_jit_refine(mmhip_filter *f, int load_module) {
+    auto t0 = std::chrono::steady_clock::now();
+    const mm::KernelSource *ks = refine_source(f);
+    if (!ks || jit_source(*ks, f->refine_code_object) != 0) return -1;
+    if (load_module && !f->refine_loaded) {
+        if (load_kernels(*ks, f->refine_code_object, &f->refine_mod, &f->f_pix_refine, &f->f_pro_refine) != 0) return -1;
+        f->refine_loaded = true;
+    }
+    f->jit_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return (long)f->refine_code_object.size();
 }
 
 // ---------------------------------------------------------------------------

@@ -923,3 +923,183 @@ int mmhip_render_clip_sampled_fused(mmhip_invocation *inv, int num_frames, const
     }
     return 0;
 }
+
+// ---- adaptively anti-aliased clips ----
+// mm_refine of mm_pixels_refine (hipgen.cpp refine_prelude)
+struct HRefine { const unsigned *list; const unsigned *counts; long long list_stride; };
+static_assert(sizeof(HRefine) == 24, "mm_refine layout");
+
+// How mmhip_render_clip_adaptive cuts a clip into batches (include/mmhip.h has the rules).  list_path: the refine variant
+// renders the refined pixels from lists; else the full grid-supersampled clip is rendered and the mask kernel puts the
+// plain pixels back (the select path).  `fused` is the sampled variant's plan at one time step: its eligibility and caps
+// are the refine variant's.
+struct ClipAdaptivePlan {
+    bool list_path = false;
+    int per_batch = 1, batches = 1;
+    size_t bytes_per_map = 0, bytes_per_frame = 0, list_entries = 0;
+    long refine_grid_x = 0;
+    ClipShutterFusedPlan fused;
+};
+static ClipAdaptivePlan clip_adaptive_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int grid_x, int grid_y, int frames,
+                                           int mode) {
+    const size_t budget = clip_shutter_budget();
+    ClipAdaptivePlan p;
+    p.bytes_per_map = (size_t)num_rows * 16 * (size_t)render_w;
+    p.list_entries = (size_t)region_w * (size_t)num_rows;
+    p.fused = clip_sampled_fused_plan(f, region_w, num_rows, 1, grid_x, grid_y, frames);
+    // a list entry is col | rl << 16
+    p.list_path = mode == MMHIP_AA_REFINE_AUTO && p.fused.fused && region_w <= 65535 && num_rows <= 65535;
+    p.bytes_per_frame = p.bytes_per_map + (p.list_path ? p.list_entries * sizeof(unsigned) : 0);
+    // one frame per batch even over the budget
+    size_t per = std::min<size_t>({std::max<size_t>(budget / p.bytes_per_frame, 1), (size_t)65535, (size_t)frames});
+    if (p.list_path) {
+        // (the sampled plan's grid_x * 256 covers the rectangle, so its cap on the work-items of a launch holds for this grid too)
+        p.refine_grid_x = (long)((p.list_entries + 255) / 256);
+        per = std::min<size_t>(per, (size_t)p.fused.per_batch);
+    }
+    p.per_batch = (int)per;
+    p.batches = (frames + p.per_batch - 1) / p.per_batch;
+    return p;
+}
+
+int mmhip_filter_clip_adaptive_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int grid_x, int grid_y, int frames,
+                                    int64_t *out) {
+    if (frames < 1) return fail("clip adaptive plan: num_frames must be at least 1");
+    if (clip_sampled_check("clip adaptive plan", 1, grid_x, grid_y) != 0) return -1;
+    if (region_w < 1 || num_rows < 1 || render_w < region_w) return fail("clip adaptive plan: empty region, or one wider than the render width");
+    const ClipAdaptivePlan p = clip_adaptive_plan(f, region_w, num_rows, render_w, grid_x, grid_y, frames, MMHIP_AA_REFINE_AUTO);
+    const int64_t v[MMHIP_CLIP_ADAPTIVE_PLAN_FIELDS] = {p.list_path, p.per_batch, p.batches, (int64_t)p.bytes_per_frame, p.refine_grid_x};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+long mmhip_clip_adaptive_batches(mmhip_invocation *inv) { return inv->clip_adaptive_batches; }
+
+int mmhip_clip_adaptive_refined(mmhip_invocation *inv, int64_t *counts, int n) {
+    if (n < 0 || (n > 0 && !counts)) return fail("clip_adaptive_refined: counts must be an array of n entries");
+    const int m = std::min(n, inv->clip_adaptive_frames);
+    if (m > 0) {
+        std::vector<unsigned> host((size_t)m);
+        HIP_TRY(hipStreamSynchronize(inv->clip_adaptive_stream));
+        HIP_TRY(hipMemcpy(host.data(), inv->clip_adaptive_counts.get(), (size_t)m * sizeof(unsigned), hipMemcpyDeviceToHost));
+        for (int i = 0; i < m; ++i) counts[i] = host[i];
+    }
+    return inv->clip_adaptive_frames;
+}
+
+// The refined pixels of frames [b0, b0 + n) from their lists: the refine variant's prologue over the batch's slots -- every
+// batch's, since the nested render of the base maps has rewritten the frame constants and the coordinate tables -- and
+// mm_pixels_refine over a grid that covers the whole rectangle (the counts stay on the device).
+static int clip_adaptive_refine_batch(mmhip_invocation *inv, mmhip_filter *f, const ClipAdaptivePlan &plan, const int *frames, const float *ts, int b0,
+                                      int n, int grid_x, int grid_y, int region_x, int region_y, int region_w, int region_h, int first_row,
+                                      int last_row, void *out, int row_stride, int64_t frame_stride, int bpp, int floatmap, const unsigned *lists,
+                                      const unsigned *counts, hipStream_t s) {
+    const KernelSource &ks = f->refine_ks;
+    const int num_rows = last_row - first_row;
+    if (upload_tables(inv, s) != 0) return -1;
+    HArgs a = render_args(inv, frames[b0], ts[b0], region_x, region_y, region_w, region_h, first_row, last_row, out, row_stride, bpp, floatmap);
+    if (grow_launch_buffers(inv->launch, ks, region_w, num_rows, false, s) != 0) return -1;
+    inv->pro_filter = nullptr;
+    auto wait = [s] { return hipStreamSynchronize(s); };
+    const bool per_frame = plan.fused.per_frame;
+    HIP_TRY(inv->clip.xy.grow(plan.fused.xy_stride * (per_frame ? plan.per_batch : 1), wait, true));
+    const size_t xtab_floats = (size_t)grid_x * region_w, ytab_floats = (size_t)grid_y * num_rows;
+    HIP_TRY(inv->clip_sampled.grow((xtab_floats + ytab_floats) * sizeof(float), wait));
+    // the batch's {t, frame} table and behind it the grid's offsets, as mmhip_render_clip_sampled_fused lays them out
+    const size_t slots = (size_t)n, offs_entries = 2 * MM_SAMPLE_GRID_MAX * sizeof(float) / sizeof(HClipFrame);
+    ClipBuffers::Table *tab = nullptr;
+    if (next_clip_table(inv, slots + offs_entries, s, &tab) != 0) return -1;
+    HClipFrame *hf = (HClipFrame *)tab->host.p;
+    for (int i = 0; i < n; ++i) hf[i] = HClipFrame{ts[b0 + i], frames[b0 + i]};
+    float *offs = (float *)(hf + slots);
+    for (int k = 0; k < MM_SAMPLE_GRID_MAX; ++k) {
+        offs[k] = k < grid_x ? mm_sample_grid_offset(k, grid_x) : 0.0f;
+        offs[MM_SAMPLE_GRID_MAX + k] = k < grid_y ? mm_sample_grid_offset(k, grid_y) : 0.0f;
+    }
+    if (send_clip_table(*tab, slots + offs_entries, s) != 0) return -1;
+
+    a.xtab = inv->launch.xtab.get<float>();
+    a.ytab = inv->launch.ytab.get<float>();
+    a.ppt = plan.fused.geo.ppt;
+    a.tiles_magic = plan.fused.geo.tiles_magic;
+    char *xy = inv->clip.xy.get<char>();
+    HClip c{};
+    c.frames = tab->dev.get<HClipFrame>();
+    c.frame_stride = frame_stride;
+    c.xy_stride = per_frame ? (int)plan.fused.xy_stride : 0;
+    c.nwg = (int)plan.fused.geo.nwg;
+    HSampled sm{};
+    sm.offs = (const float *)(tab->dev.get<HClipFrame>() + slots);
+    sm.xtabs = inv->clip_sampled.get<float>();
+    sm.ytabs = sm.xtabs + xtab_floats;
+    sm.samples = 1;
+    sm.gx = grid_x;
+    sm.gy = grid_y;
+    sm.total = grid_x * grid_y;
+    sm.inv_k = mm_shutter_inv_k(sm.total);
+    HRefine r{lists, counts, (long long)plan.list_entries};
+    void *params[] = {&a, &xy, &c, &sm, &r};      // (the prologue takes the first four)
+    if (launch_clip_prologue(f->f_pro_refine, nullptr, a, per_frame, 0, n, params, s) < 0) return -1;
+    return timed_pixel_launch(inv, f->f_pix_refine, (unsigned)plan.refine_grid_x, (unsigned)n, params, s);
+}
+
+int mmhip_render_clip_adaptive(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int grid_x, int grid_y, float threshold,
+                               int mode, int region_x, int region_y, int region_w, int region_h, int first_row, int last_row, void *out_device,
+                               int row_stride, int64_t frame_stride, int bpp, int floatmap, void *stream) {
+    const char *who = "render_clip_adaptive";
+    if (std::isnan(threshold)) return fail(std::string(who) + ": threshold must not be NaN");
+    if (grid_x == 1 && grid_y == 1) {      // one sample per pixel, refined or not: the plain clip itself
+        const int rc = mmhip_render_clip(inv, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
+                                         row_stride, frame_stride, bpp, floatmap, stream);
+        if (rc == 0 && inv) inv->clip_adaptive_frames = 0;      // no mask, no counts
+        return rc;
+    }
+    if (clip_sampled_check(who, 1, grid_x, grid_y) != 0) return -1;
+    if (mode != MMHIP_AA_REFINE_AUTO && mode != MMHIP_AA_REFINE_SELECT)
+        return fail(std::string(who) + ": mode must be 0 (auto) or 1 (select), not " + std::to_string(mode));
+    if (check_clip_args(who, num_frames, frames, ts, bpp, region_w, region_h) != 0) return -1;
+    const int first_arg = first_row, last_arg = last_row;
+    if (!clamp_rows(region_y, region_h, &first_row, &last_row)) return 0;
+    const int num_rows = last_row - first_row;
+    if (check_frame_stride(who, inv, frame_stride, num_rows, region_w, row_stride, bpp, floatmap) != 0) return -1;
+    if (region_w > inv->render_w) return fail(std::string(who) + ": the region is wider than the render width");
+    mmhip_filter *f = active_filter(inv, frames[0], ts[0]);
+    const ClipAdaptivePlan plan = clip_adaptive_plan(f, region_w, num_rows, inv->render_w, grid_x, grid_y, num_frames, mode);
+    const size_t bps = plan.bytes_per_map;
+    if (bps > ((size_t)1 << 32)) return fail(std::string(who) + ": a base map of more than 4 GiB; render the frame in row bands");
+    if (plan.list_path && mmhip_filter_jit_refine(f, 1) < 0) return -1;
+    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
+    // own allocations (the nested grid-supersampled clip of the select path fills the shutter's temporary); whatever still
+    // reads a smaller one has finished before it is freed
+    if (inv->clip_adaptive.grow((size_t)plan.per_batch * plan.bytes_per_frame, hipDeviceSynchronize) != hipSuccess ||
+        inv->clip_adaptive_counts.grow((size_t)num_frames * sizeof(unsigned), hipDeviceSynchronize) != hipSuccess)
+        return fail("out of device memory for the base maps of an adaptively anti-aliased clip; lower MMHIP_CLIP_SHUTTER_BYTES");
+    unsigned char *base = inv->clip_adaptive.get<unsigned char>();
+    unsigned *lists = plan.list_path ? (unsigned *)(base + (size_t)plan.per_batch * bps) : nullptr;
+    unsigned *counts = inv->clip_adaptive_counts.get<unsigned>();
+    inv->clip_adaptive_frames = num_frames;
+    inv->clip_adaptive_stream = s;
+    SamplingOffsetGuard offsets(inv);
+    offsets.set(0.f);      // the base maps are rendered at offset 0, whatever the caller's
+    for (int b0 = 0; b0 < num_frames; b0 += plan.per_batch) {
+        const int n = std::min(plan.per_batch, num_frames - b0);
+        char *out = (char *)out_device + (int64_t)b0 * frame_stride;
+        if (mmhip_render_clip(inv, n, frames + b0, ts + b0, region_x, region_y, region_w, region_h, first_arg, last_arg, base, row_stride,
+                              (int64_t)bps, bpp, 1, s) != 0)
+            return -1;
+        // select path: every pixel refined, then the mask kernel puts back those that are not
+        if (!plan.list_path && mmhip_render_clip_sampled(inv, n, frames + b0, ts + b0, 1, 0.0f, grid_x, grid_y, region_x, region_y, region_w,
+                                                         region_h, first_arg, last_arg, out, row_stride, frame_stride, bpp, floatmap, s) != 0)
+            return -1;
+        HIP_TRY(hipMemsetAsync(counts + b0, 0, (size_t)n * sizeof(unsigned), s));
+        std::string err;
+        if (launch_aa_contrast_clip(base, (int64_t)bps, out, counts + b0, lists, (int64_t)plan.list_entries, region_w, num_rows, inv->render_w,
+                                    row_stride, frame_stride, bpp, floatmap, threshold, n, inv->ws, s, &err) != 0)
+            return fail(err);
+        if (plan.list_path && clip_adaptive_refine_batch(inv, f, plan, frames, ts, b0, n, grid_x, grid_y, region_x, region_y, region_w, region_h,
+                                                         first_row, last_row, out, row_stride, frame_stride, bpp, floatmap, lists, counts + b0, s) != 0)
+            return -1;
+        ++inv->clip_adaptive_batches;
+    }
+    return 0;
+}

@@ -61,6 +61,13 @@ struct mmhip_filter {
     hipModule_t sampled_mod = nullptr;
     hipFunction_t f_pro_sampled = nullptr, f_pix_sampled = nullptr;
     bool sampled_loaded = false;
+    // the refine variant (mmhip_render_clip_adaptive, KernelOptions::refine): the fifth module, under its own key; the
+    // filters that have a sampled variant
+    mm::KernelSource refine_ks;
+    std::vector<char> refine_code_object;
+    hipModule_t refine_mod = nullptr;
+    hipFunction_t f_pro_refine = nullptr, f_pix_refine = nullptr;
+    bool refine_loaded = false;
     // user-value specialisation (specialize.cpp): kernels with the scalar user values baked in,
     // keyed by the value bytes; owned by this filter
     std::string source;
@@ -240,6 +247,12 @@ struct mmhip_invocation {
     long clip_sampled_fused_batches = 0;   // mmhip_clip_sampled_fused_batches
     DeviceBuffer clip_sampled;             // of a fused grid-supersampled batch: the grid's offsets (16 floats), then the
                                            // per-offset x tables and y tables (mm_sampled, hipgen.cpp sampled_prelude)
+    // adaptive anti-aliasing (mmhip_render_clip_adaptive): a batch's base maps and, behind them, its lists of the pixels to
+    // refine; the refined-pixel counts of every frame of the last call, and the stream that call ran on
+    DeviceBuffer clip_adaptive, clip_adaptive_counts;
+    int clip_adaptive_frames = 0;
+    hipStream_t clip_adaptive_stream = nullptr;
+    long clip_adaptive_batches = 0;        // mmhip_clip_adaptive_batches
     uint32_t edge_color_x = 0, edge_color_y = 0;
     float sampling_offset_x = 0.f, sampling_offset_y = 0.f;
     bool timing = false;
