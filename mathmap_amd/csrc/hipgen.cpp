@@ -358,8 +358,11 @@ struct Generator {
                 if (lhs && lhs->type == Ty::Int && (!strcmp(cn, "floor") || !strcmp(cn, "ceil")))
                     name = !strcmp(cn, "floor") ? "mm_floor_i" : "mm_ceil_i";      // x86 double -> int conversion
                 if (floats && !strcmp(cn, "hypot") && !(lhs && lhs->type == Ty::Float)) name = "mm_hypot_ff";      // a double-typed result keeps the earlier form
+                // a table read multiplies its argument before it truncates: a float where the argument is a variable's content
+                const bool table_read = !strcmp(cn, "APPLY_CURVE") || !strcmp(cn, "APPLY_GRADIENT");
                 std::string s = name + "(";
-                for (size_t i = 0; i < r.args.size(); ++i) s += (i ? "," : "") + prim(r.args[i], sl);
+                for (size_t i = 0; i < r.args.size(); ++i)
+                    s += (i ? "," : "") + std::string(table_read && r.args[i].kind == Primary::FloatConst && r.args[i].of_variable ? "(float)" : "") + prim(r.args[i], sl);
                 return s + ")";
             }
             default: return "0";

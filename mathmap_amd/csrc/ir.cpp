@@ -331,7 +331,7 @@ void js_prim(std::ostringstream &o, const Primary &p) {
         case Primary::FloatConst: {
             uint32_t bits;
             std::memcpy(&bits, &p.f, 4);
-            o << "[\"f\"," << bits << "]";
+            o << "[\"f\"," << bits << (p.of_variable ? ",1]" : "]");
             break;
         }
         case Primary::ComplexConst: {

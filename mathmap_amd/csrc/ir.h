@@ -81,6 +81,10 @@ struct Primary {
     int i = 0;
     float f = 0.f, f2 = 0.f;
     unsigned color = 0;
+    // IntConst / FloatConst: the content of a variable -- a user value baked in, or folded from one -- and not a literal of the
+    // source.  Generated C reads a float variable as a float and a float literal as a double (ops.lisp:348), and the two differ
+    // where an operator macro does arithmetic on its argument before it truncates (APPLY_CURVE, APPLY_GRADIENT).
+    bool of_variable = false;
     static Primary V(Value *v) { Primary p; p.kind = Val; p.value = v; return p; }
     static Primary I(int v) { Primary p; p.kind = IntConst; p.i = v; return p; }
     static Primary F(float v) { Primary p; p.kind = FloatConst; p.f = v; return p; }

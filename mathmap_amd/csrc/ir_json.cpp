@@ -123,7 +123,7 @@ struct Loader {
         Primary p;
         if (k == "v") return Primary::V(value(j[1].i(), j[2].i()));
         if (k == "i") return Primary::I((int)j[1].i());
-        if (k == "f") { uint32_t b = (uint32_t)j[1].num; float f; memcpy(&f, &b, 4); return Primary::F(f); }
+        if (k == "f") { uint32_t b = (uint32_t)j[1].num; float f; memcpy(&f, &b, 4); p = Primary::F(f); p.of_variable = j.arr.size() > 2 && j[2].i() != 0; return p; }
         if (k == "c") { uint32_t a = (uint32_t)j[1].num, b = (uint32_t)j[2].num; p.kind = Primary::ComplexConst; memcpy(&p.f, &a, 4); memcpy(&p.f2, &b, 4); return p; }
         if (k == "k") { p.kind = Primary::ColorConst; p.color = (unsigned)j[1].num; return p; }
         throw CompileError("IR JSON: bad primary");

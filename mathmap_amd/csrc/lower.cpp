@@ -261,7 +261,11 @@ void Lowerer::gen_filter(Filter *f, const std::vector<Primary> *args, CompVar *r
                 CompVar *bv = g_.temp(ty);
                 auto cit = uv_consts_ ? uv_consts_->find(u.index) : std::map<int, Primary>::const_iterator();
                 if (uv_consts_ && cit != uv_consts_->end() && (u.kind == UvKind::Int || u.kind == UvKind::Float || u.kind == UvKind::Bool))
-                    env.uservals[u.index] = g_.assign(bv, Rhs::P(cit->second));
+                {
+                    Primary c = cit->second;
+                    c.of_variable = true;
+                    env.uservals[u.index] = g_.assign(bv, Rhs::P(c));
+                }
                 else
                     env.uservals[u.index] = g_.assign_op(bv, getters[(int)u.kind], {Primary::I(u.index)});
             }

@@ -1349,7 +1349,10 @@ static void bake_uservals(Block &b, const std::map<int, Primary> &consts) {
             const char *n = st->rhs.op->cname;
             if (!strcmp(n, "USERVAL_INT_ACCESS") || !strcmp(n, "USERVAL_FLOAT_ACCESS") || !strcmp(n, "USERVAL_BOOL_ACCESS")) {
                 auto it = consts.find(st->rhs.args[0].i);
-                if (it != consts.end()) st->rhs = Rhs::P(it->second);
+                if (it != consts.end()) {
+                    st->rhs = Rhs::P(it->second);
+                    st->rhs.prim.of_variable = true;
+                }
             }
         }
         if (st->kind == Stmt::If) { bake_uservals(st->then_, consts); bake_uservals(st->else_, consts); }

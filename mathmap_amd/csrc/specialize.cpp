@@ -45,15 +45,20 @@ double as_double(const Primary &p) { return p.kind == Primary::IntConst ? (doubl
 
 // C assignment conversion of a constant to the type of the variable it is stored in
 bool convert_to(Ty t, Primary &p) {
+    const bool of_variable = p.of_variable;
     if (t == Ty::Int) {
         if (p.kind == Primary::FloatConst) {
             if (!(std::fabs(p.f) < 2e9f)) return false;
             p = Primary::I((int)p.f);
+            p.of_variable = of_variable;
         }
         return p.kind == Primary::IntConst;
     }
     if (t == Ty::Float) {
-        if (p.kind == Primary::IntConst) p = Primary::F((float)p.i);
+        if (p.kind == Primary::IntConst) {
+            p = Primary::F((float)p.i);
+            p.of_variable = of_variable;
+        }
         return p.kind == Primary::FloatConst;
     }
     return false;
@@ -62,7 +67,7 @@ bool convert_to(Ty t, Primary &p) {
 bool both_int(const Primary &a, const Primary &b) { return a.kind == Primary::IntConst && b.kind == Primary::IntConst; }
 
 // folds an operator on constants with the C semantics of its macro (opmacros.h)
-bool fold_impl(const OpInfo *op, const std::vector<Primary> &a, Primary &out) {
+bool fold_values(const OpInfo *op, const std::vector<Primary> &a, Primary &out) {
     const char *n = op->cname;
     auto bin = [&](auto fi, auto fd) {
         if (both_int(a[0], a[1])) out = Primary::I(fi(a[0].i, a[1].i));
@@ -90,6 +95,14 @@ bool fold_impl(const OpInfo *op, const std::vector<Primary> &a, Primary &out) {
     }
     if (!strcmp(n, "INT2FLOAT") && a[0].kind == Primary::IntConst) { out = Primary::F((float)a[0].i); return true; }
     return false;   // libm and everything else stays in the kernel / prologue
+}
+
+// fold_values, and the result is the content of a variable where an operand is (Primary::of_variable)
+bool fold_impl(const OpInfo *op, const std::vector<Primary> &a, Primary &out) {
+    if (!fold_values(op, a, out)) return false;
+    out.of_variable = false;
+    for (const Primary &p : a) out.of_variable |= p.of_variable;
+    return true;
 }
 
 struct Sccp {

@@ -181,6 +181,10 @@ class Gen:
                     n, self.prim(a[1]), self.prim(a[0]), n, self.prim(a[2]))
             if op == "RENDER":
                 return "mmo_render(A, %d, %s)" % (self.natives[id(stmt)], ", ".join(self.prim(a) for a in r["args"]))
+            if op in ("APPLY_CURVE", "APPLY_GRADIENT"):
+                # ["f", bits, 1]: a baked user value, or a fold of one -- the content of a float variable, which C reads as a
+                # float; the macro multiplies its argument before it truncates, so a double there can give another entry
+                return "%s(%s)" % (op, ",".join(("(float)" if a[0] == "f" and len(a) > 2 and a[2] else "") + self.prim(a) for a in r["args"]))
             return "%s(%s)" % (op, ",".join(self.prim(a) for a in r["args"]))
         raise OracleUnsupported("rhs kind %s" % k)
 
