@@ -209,151 +209,113 @@ class Filter:
         """How the pixel kernel is launched over `num_rows` rows of a `region_w`-wide region (the geometry mmhip_render
         takes, MMHIP_PPT included) -- or, with `closure` = k, how closure image #k is launched over a region_w x
         num_rows frame.  A dict of the GEOMETRY_FIELDS."""
-        out = (C.c_int64 * len(GEOMETRY_FIELDS))()
         if closure is None:
-            rc = lib().mmhip_filter_launch_geometry(self._h, region_w, num_rows, out)
-        else:
-            rc = lib().mmhip_filter_closure_launch_geometry(self._h, closure, region_w, num_rows, out)
-        if rc != 0:
+            return self._plan("mmhip_filter_launch_geometry", GEOMETRY_FIELDS, region_w, num_rows)
+        return self._plan("mmhip_filter_closure_launch_geometry", GEOMETRY_FIELDS, closure, region_w, num_rows)
+
+    def _plan(self, symbol, fields, *args):
+        """What the library's plan function `symbol` writes for `args`: a dict of `fields`."""
+        out = (C.c_int64 * len(fields))()
+        if getattr(lib(), symbol)(self._h, *args, out) != 0:
             raise MathMapError(_err())
-        return dict(zip(GEOMETRY_FIELDS, out))
+        return dict(zip(fields, out))
+
+    def _variant(self, symbol, *args):
+        """A module variant's text (decoded) or code-object size from the library function `symbol`; no text, or a
+        negative size, is the library's refusal: MathMapError."""
+        got = getattr(lib(), symbol)(self._h, *args)
+        if got is None or (not isinstance(got, bytes) and got < 0):
+            raise MathMapError(_err())
+        return got.decode() if isinstance(got, bytes) else got
 
     def clip_launch_geometry(self, region_w, num_rows, frames):
         """The geometry of one frame of a `frames`-frame clip render (render_clip): GEOMETRY_FIELDS, with the
         rows per work-item chosen from the workgroups of all frames together; frames=1 is launch_geometry."""
-        out = (C.c_int64 * len(GEOMETRY_FIELDS))()
-        if lib().mmhip_filter_clip_launch_geometry(self._h, region_w, num_rows, frames, out) != 0:
-            raise MathMapError(_err())
-        return dict(zip(GEOMETRY_FIELDS, out))
+        return self._plan("mmhip_filter_clip_launch_geometry", GEOMETRY_FIELDS, region_w, num_rows, frames)
 
     def clip_batch_plan(self, region_w, num_rows, frames):
         """How render_clip cuts a `frames`-frame clip into launches: a dict of the CLIP_PLAN_FIELDS
         (frames_per_batch 0: the filter is rendered frame by frame)."""
-        out = (C.c_int64 * len(CLIP_PLAN_FIELDS))()
-        if lib().mmhip_filter_clip_batch_plan(self._h, region_w, num_rows, frames, out) != 0:
-            raise MathMapError(_err())
-        return dict(zip(CLIP_PLAN_FIELDS, out))
+        return self._plan("mmhip_filter_clip_batch_plan", CLIP_PLAN_FIELDS, region_w, num_rows, frames)
 
     def clip_native_plan(self, region_w, num_rows, frames, render_w=None, render_h=None):
         """How render_clip batches the gaussian_blur calls of a `frames`-frame clip at render size render_w x render_h
         (default: the region's): a dict of the CLIP_NATIVE_PLAN_FIELDS (eligible 0: the filter's native calls are not
         batched; frames_per_batch 0: rendered frame by frame)."""
-        out = (C.c_int64 * len(CLIP_NATIVE_PLAN_FIELDS))()
         rw, rh = region_w if render_w is None else render_w, num_rows if render_h is None else render_h
-        if lib().mmhip_filter_clip_native_plan(self._h, region_w, num_rows, rw, rh, frames, out) != 0:
-            raise MathMapError(_err())
-        return dict(zip(CLIP_NATIVE_PLAN_FIELDS, out))
+        return self._plan("mmhip_filter_clip_native_plan", CLIP_NATIVE_PLAN_FIELDS, region_w, num_rows, rw, rh, frames)
 
     def clip_shutter_plan(self, region_w, num_rows, render_w, samples, frames):
         """How render_clip(shutter_samples=samples) renders a `frames`-frame clip of num_rows rows of a region at render
         width render_w: a dict of the CLIP_SHUTTER_PLAN_FIELDS (carry 1: the sub-samples of a frame take several passes)."""
-        out = (C.c_int64 * len(CLIP_SHUTTER_PLAN_FIELDS))()
-        if lib().mmhip_filter_clip_shutter_plan(self._h, region_w, num_rows, render_w, samples, frames, out) != 0:
-            raise MathMapError(_err())
-        return dict(zip(CLIP_SHUTTER_PLAN_FIELDS, out))
+        return self._plan("mmhip_filter_clip_shutter_plan", CLIP_SHUTTER_PLAN_FIELDS, region_w, num_rows, render_w, samples, frames)
 
     def clip_shutter_fused_plan(self, region_w, num_rows, samples, frames):
         """How render_clip(shutter_samples=samples, shutter_mode="fused") renders a `frames`-frame clip of num_rows rows of
         a region_w-wide region: a dict of the CLIP_SHUTTER_FUSED_PLAN_FIELDS (fused 0: the filter takes the maps path)."""
-        out = (C.c_int64 * len(CLIP_SHUTTER_FUSED_PLAN_FIELDS))()
-        if lib().mmhip_filter_clip_shutter_fused_plan(self._h, region_w, num_rows, samples, frames, out) != 0:
-            raise MathMapError(_err())
-        return dict(zip(CLIP_SHUTTER_FUSED_PLAN_FIELDS, out))
+        return self._plan("mmhip_filter_clip_shutter_fused_plan", CLIP_SHUTTER_FUSED_PLAN_FIELDS, region_w, num_rows, samples, frames)
 
     def clip_sampled_plan(self, region_w, num_rows, render_w, samples, aa, frames):
         """How render_clip(aa=aa, shutter_samples=samples) renders a `frames`-frame clip through sub-sample maps: a dict of
         the CLIP_SAMPLED_PLAN_FIELDS (steps_per_pass: time steps, of sx * sy maps each)."""
         sx, sy = sample_grid(aa)
-        out = (C.c_int64 * len(CLIP_SAMPLED_PLAN_FIELDS))()
-        if lib().mmhip_filter_clip_sampled_plan(self._h, region_w, num_rows, render_w, samples, sx, sy, frames, out) != 0:
-            raise MathMapError(_err())
-        return dict(zip(CLIP_SAMPLED_PLAN_FIELDS, out))
+        return self._plan("mmhip_filter_clip_sampled_plan", CLIP_SAMPLED_PLAN_FIELDS, region_w, num_rows, render_w, samples, sx, sy, frames)
 
     def clip_sampled_fused_plan(self, region_w, num_rows, samples, aa, frames):
         """How render_clip(aa=aa, shutter_samples=samples, shutter_mode="fused") renders a `frames`-frame clip: a dict of the
         CLIP_SHUTTER_FUSED_PLAN_FIELDS (fused 0: the filter takes the maps path)."""
         sx, sy = sample_grid(aa)
-        out = (C.c_int64 * len(CLIP_SHUTTER_FUSED_PLAN_FIELDS))()
-        if lib().mmhip_filter_clip_sampled_fused_plan(self._h, region_w, num_rows, samples, sx, sy, frames, out) != 0:
-            raise MathMapError(_err())
-        return dict(zip(CLIP_SHUTTER_FUSED_PLAN_FIELDS, out))
+        return self._plan("mmhip_filter_clip_sampled_fused_plan", CLIP_SHUTTER_FUSED_PLAN_FIELDS, region_w, num_rows, samples, sx, sy, frames)
 
     def clip_adaptive_plan(self, region_w, num_rows, render_w, aa, frames):
         """How render_clip(aa=aa, aa_threshold=T) renders a `frames`-frame clip: a dict of the CLIP_ADAPTIVE_PLAN_FIELDS
         (list_path 0: the filter or the region takes the select path)."""
         sx, sy = sample_grid(aa)
-        out = (C.c_int64 * len(CLIP_ADAPTIVE_PLAN_FIELDS))()
-        if lib().mmhip_filter_clip_adaptive_plan(self._h, region_w, num_rows, render_w, sx, sy, frames, out) != 0:
-            raise MathMapError(_err())
-        return dict(zip(CLIP_ADAPTIVE_PLAN_FIELDS, out))
+        return self._plan("mmhip_filter_clip_adaptive_plan", CLIP_ADAPTIVE_PLAN_FIELDS, region_w, num_rows, render_w, sx, sy, frames)
 
     @property
     def refine_kernel_source(self):
         """The refine variant of kernel_source: kernels mm_prologue_clip (the sampled variant's) and mm_pixels_refine.  A
         filter without a sampled variant has none: MathMapError."""
-        text = lib().mmhip_filter_refine_kernel_source(self._h)
-        if text is None:
-            raise MathMapError(_err())
-        return text.decode()
+        return self._variant("mmhip_filter_refine_kernel_source")
 
     def jit_refine(self, load=False):
         """hiprtc-compiles the refine variant for gfx950; returns the code-object size."""
-        n = lib().mmhip_filter_jit_refine(self._h, 1 if load else 0)
-        if n < 0:
-            raise MathMapError(_err())
-        return n
+        return self._variant("mmhip_filter_jit_refine", 1 if load else 0)
 
     @property
     def sampled_kernel_source(self):
         """The sampled variant of kernel_source: kernels mm_prologue_clip and mm_pixels_sampled.  A filter with native calls,
         closure images or a per-row slice has none: MathMapError."""
-        text = lib().mmhip_filter_sampled_kernel_source(self._h)
-        if text is None:
-            raise MathMapError(_err())
-        return text.decode()
+        return self._variant("mmhip_filter_sampled_kernel_source")
 
     def jit_sampled(self, load=False):
         """hiprtc-compiles the sampled variant for gfx950; returns the code-object size."""
-        n = lib().mmhip_filter_jit_sampled(self._h, 1 if load else 0)
-        if n < 0:
-            raise MathMapError(_err())
-        return n
+        return self._variant("mmhip_filter_jit_sampled", 1 if load else 0)
 
     @property
     def shutter_kernel_source(self):
         """The shutter variant of kernel_source: kernels mm_prologue_clip, mm_rows_clip, mm_pixels_shutter.  A filter with
         native calls or closure images has none: MathMapError."""
-        text = lib().mmhip_filter_shutter_kernel_source(self._h)
-        if text is None:
-            raise MathMapError(_err())
-        return text.decode()
+        return self._variant("mmhip_filter_shutter_kernel_source")
 
     def jit_shutter(self, load=False):
         """hiprtc-compiles the shutter variant for gfx950; returns the code-object size."""
-        n = lib().mmhip_filter_jit_shutter(self._h, 1 if load else 0)
-        if n < 0:
-            raise MathMapError(_err())
-        return n
+        return self._variant("mmhip_filter_jit_shutter", 1 if load else 0)
 
     def clip_supersample_plan(self, region_w, region_h, frames, bpp=4):
         """How render_clip(supersample=True) renders a `frames`-frame clip of a region: a dict of the CLIP_SS_PLAN_FIELDS
         (batched 0: the loop of single supersampled renders)."""
-        out = (C.c_int64 * len(CLIP_SS_PLAN_FIELDS))()
-        if lib().mmhip_filter_clip_supersample_plan(self._h, region_w, region_h, bpp, frames, out) != 0:
-            raise MathMapError(_err())
-        return dict(zip(CLIP_SS_PLAN_FIELDS, out))
+        return self._plan("mmhip_filter_clip_supersample_plan", CLIP_SS_PLAN_FIELDS, region_w, region_h, bpp, frames)
 
     @property
     def clip_kernel_source(self):
         """The clip variant of kernel_source: kernels mm_prologue_clip, mm_rows_clip, mm_pixels_clip."""
-        return lib().mmhip_filter_clip_kernel_source(self._h).decode()
+        return self._variant("mmhip_filter_clip_kernel_source")
 
     def jit_clip(self, load=False):
         """hiprtc-compiles the clip variant for gfx950; returns the code-object size."""
-        n = lib().mmhip_filter_jit_clip(self._h, 1 if load else 0)
-        if n < 0:
-            raise MathMapError(_err())
-        return n
+        return self._variant("mmhip_filter_jit_clip", 1 if load else 0)
 
     @property
     def num_closures(self):
@@ -361,10 +323,7 @@ class Filter:
 
     def jit(self, load=False):
         """hiprtc-compiles the kernel string for gfx950; returns the code-object size."""
-        n = lib().mmhip_filter_jit(self._h, 1 if load else 0)
-        if n < 0:
-            raise MathMapError(_err())
-        return n
+        return self._variant("mmhip_filter_jit", 1 if load else 0)
 
     @property
     def jit_seconds(self):
@@ -636,20 +595,19 @@ class Invocation:
         fp, tp = frames.ctypes.data_as(C.POINTER(C.c_int)), ts.ctypes.data_as(C.POINTER(C.c_float))
         if supersample:
             return self._render_clip_supersampled(num_frames, fp, tp, out_ptr, (rx, ry, rw, rh), row_stride, frame_stride, bpp, stream)
+
+        def render(*landing):
+            """The native call of this clip; landing: out, row_stride, frame_stride, bpp, floatmap, stream."""
+            if shuttered:
+                return render_shutter(self._h, num_frames, fp, tp, shutter_samples, span, rx, ry, rw, rh, first_row, last_row, *landing)
+            return lib().mmhip_render_clip(self._h, num_frames, fp, tp, rx, ry, rw, rh, first_row, last_row, *landing)
         if out_ptr is not None:
             if row_stride is None:
                 row_stride = rw * bpp
             if frame_stride is None:
                 n_rows = max(min(last_row, ry + rh) - max(first_row, 0), 0)
                 frame_stride = n_rows * (16 * self.render_width if floatmap else row_stride)
-            if shuttered:
-                self._check(render_shutter(self._h, num_frames, fp, tp, shutter_samples, span, rx, ry, rw, rh, first_row,
-                                           last_row, C.c_void_p(out_ptr), row_stride, frame_stride, bpp,
-                                           1 if floatmap else 0, C.c_void_p(stream)))
-                return None
-            self._check(lib().mmhip_render_clip(self._h, num_frames, fp, tp, rx, ry, rw, rh, first_row, last_row,
-                                                C.c_void_p(out_ptr), row_stride, frame_stride, bpp, 1 if floatmap else 0,
-                                                C.c_void_p(stream)))
+            self._check(render(C.c_void_p(out_ptr), row_stride, frame_stride, bpp, 1 if floatmap else 0, C.c_void_p(stream)))
             return None
         if rows is not None or region is not None or floatmap or bpp != 4 or row_stride is not None or frame_stride is not None:
             raise MathMapError("render_clip without out_ptr returns whole RGBA frames: pass out_ptr for bands, regions and other formats")
@@ -660,12 +618,7 @@ class Invocation:
         if not dev:
             raise MathMapError(_err())
         try:
-            if shuttered:
-                self._check(render_shutter(self._h, num_frames, fp, tp, shutter_samples, span, rx, ry, rw, rh, first_row,
-                                           last_row, C.c_void_p(dev), rw * 4, rw * 4 * rh, 4, 0, None))
-            else:
-                self._check(lib().mmhip_render_clip(self._h, num_frames, fp, tp, rx, ry, rw, rh, first_row, last_row,
-                                                    C.c_void_p(dev), rw * 4, rw * 4 * rh, 4, 0, None))
+            self._check(render(C.c_void_p(dev), rw * 4, rw * 4 * rh, 4, 0, None))
             self.sync()
             self._check(lib().mmhip_copy_to_host(out.ctypes.data_as(C.c_void_p), C.c_void_p(dev), out.nbytes))
         finally:

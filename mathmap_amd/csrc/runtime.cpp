@@ -186,10 +186,7 @@ void mmhip_filter_free(mmhip_filter *f) {
     for (auto &p : f->spec_cache) mmhip_filter_free(p.second);
     for (mmhip_closure_kernel &ck : f->closures) if (ck.mod) (void)hipModuleUnload(ck.mod);
     if (f->mod) (void)hipModuleUnload(f->mod);
-    if (f->clip_mod) (void)hipModuleUnload(f->clip_mod);
-    if (f->shutter_mod) (void)hipModuleUnload(f->shutter_mod);
-    if (f->sampled_mod) (void)hipModuleUnload(f->sampled_mod);
-    if (f->refine_mod) (void)hipModuleUnload(f->refine_mod);
+    for (ModuleVariant &v : f->variants) if (v.mod) (void)hipModuleUnload(v.mod);
     delete f;
 }
 
@@ -321,152 +318,87 @@ long mmhip_filter_jit(mmhip_filter *f, int load_module) {
     return (long)f->code_object.size();
 }
 
-// The clip variant's text (hipgen.cpp clip_kernel_source), made when it is first asked for.
-static const mm::KernelSource &clip_source(mmhip_filter *f) {
-    if (f->clip_ks.source.empty()) {
-        clip_kernel_source(f->ks, &f->clip_ks.source, &f->clip_ks.key);
-        f->clip_ks.prologue_name = "mm_prologue_clip";
-        f->clip_ks.rows_name = "mm_rows_clip";
-        f->clip_ks.pixel_name = "mm_pixels_clip";
-        f->clip_ks.wrapping_ints = f->ks.wrapping_ints;
+// The variants generated from the retained code (hipgen.h KernelOptions): the option that makes each one, and which
+// filters have it.  None is for filters that call native filters or render closure images; `rows`: a per-row slice does
+// not rule the variant out, and its kernel is mm_rows_clip.
+struct GeneratedVariant {
+    const char *name;
+    void (*set)(KernelOptions &);
+    bool rows;
+    const char *refused;
+};
+static const GeneratedVariant generated_variants[VARIANT_COUNT] = {
+    {nullptr, nullptr, true, nullptr},      // VARIANT_CLIP is not generated
+    {"shutter", [](KernelOptions &ko) { ko.shutter = true; }, true, "it calls native filters or renders closure images"},
+    {"sampled", [](KernelOptions &ko) { ko.sampled = true; }, false,
+     "it calls native filters, renders closure images or has a per-row slice"},
+    {"refine", [](KernelOptions &ko) { ko.sampled = ko.refine = true; }, false,
+     "it calls native filters, renders closure images or has a per-row slice"},
+};
+
+// The text of one variant, made when it is first asked for: whatever else the filter has of text is a stored string and
+// is not touched.  The clip variant is made from the main text (hipgen.cpp clip_kernel_source) and every filter has it;
+// the others are generated from the retained code: null, with the message, for a filter that has none.  A variant whose
+// generation failed stays empty, and is generated again when it is next asked for.
+static const KernelSource *variant_source(mmhip_filter *f, int which) {
+    KernelSource &ks = f->variants[which].ks;
+    if (!ks.source.empty()) return &ks;
+    const GeneratedVariant *g = &generated_variants[which];
+    if (!g->set) {
+        clip_kernel_source(f->ks, &ks.source, &ks.key);
+        ks.prologue_name = "mm_prologue_clip";
+        ks.rows_name = "mm_rows_clip";
+        ks.pixel_name = "mm_pixels_clip";
+        ks.wrapping_ints = f->ks.wrapping_ints;
+        ks.row_values = f->ks.row_values;      // (of what the record describes this and the names alone are filled in)
+        return &ks;
     }
-    return f->clip_ks;
-}
-
-const char *mmhip_filter_clip_kernel_source(mmhip_filter *f) { return clip_source(f).source.c_str(); }
-
-long mmhip_filter_jit_clip(mmhip_filter *f, int load_module) {
-    auto t0 = std::chrono::steady_clock::now();
-    const mm::KernelSource &ks = clip_source(f);
-    if (jit_source(ks, f->clip_code_object) != 0) return -1;
-    if (load_module && !f->clip_loaded) {
-        if (load_kernels(ks, f->clip_code_object, &f->clip_mod, &f->f_pix_clip, &f->f_pro_clip, f->ks.row_values > 0 ? &f->f_rows_clip : nullptr) != 0)
-            return -1;
-        f->clip_loaded = true;
-    }
-    f->jit_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return (long)f->clip_code_object.size();
-}
-
-// The shutter variant's text (hipgen.h KernelOptions::shutter), generated from the retained code when it is first asked
-// for; null, with the message, for a filter that has none.  The main and the clip text are stored strings: not touched.
-static const mm::KernelSource *shutter_source(mmhip_filter *f) {
-    if (!f->shutter_ks.source.empty()) return &f->shutter_ks;
-    if (!f->ks.natives.empty() || !f->closures.empty()) {
-        fail("filter `" + f->module.main->name + "' has no shutter variant: it calls native filters or renders closure images");
+    if (!f->ks.natives.empty() || !f->closures.empty() || (!g->rows && f->ks.row_values > 0)) {
+        fail("filter `" + f->module.main->name + "' has no " + g->name + " variant: " + g->refused);
         return nullptr;
     }
-    if (!f->code) { fail("filter has no shutter variant: its code was not kept"); return nullptr; }
+    if (!f->code) { fail(std::string("filter has no ") + g->name + " variant: its code was not kept"); return nullptr; }
     try {
         KernelOptions ko = f->kopt;
-        ko.shutter = true;
-        f->shutter_ks = generate_hip(*f->code, ko);
+        g->set(ko);
+        ks = generate_hip(*f->code, ko);
     } catch (const std::exception &e) {
-        f->shutter_ks = mm::KernelSource();
+        ks = KernelSource();
         fail(e.what());
         return nullptr;
     }
-    f->shutter_ks.prologue_name = "mm_prologue_clip";
-    f->shutter_ks.rows_name = "mm_rows_clip";
-    return &f->shutter_ks;
+    ks.prologue_name = "mm_prologue_clip";
+    if (g->rows) ks.rows_name = "mm_rows_clip";
+    return &ks;
 }
 
-const char *mmhip_filter_shutter_kernel_source(mmhip_filter *f) {
-    const mm::KernelSource *ks = shutter_source(f);
+static const char *variant_text(mmhip_filter *f, int which) {
+    const KernelSource *ks = variant_source(f, which);
     return ks ? ks->source.c_str() : nullptr;
 }
 
-long mmhip_filter_jit_shutter(mmhip_filter *f, int load_module) {
+// hiprtc-compiles a variant and, where asked, loads its kernels: the code object's size, or -1.
+static long jit_variant(mmhip_filter *f, int which, int load_module) {
     auto t0 = std::chrono::steady_clock::now();
-    const mm::KernelSource *ks = shutter_source(f);
-    if (!ks || jit_source(*ks, f->shutter_code_object) != 0) return -1;
-    if (load_module && !f->shutter_loaded) {
-        if (load_kernels(*ks, f->shutter_code_object, &f->shutter_mod, &f->f_pix_shutter, &f->f_pro_shutter,
-                         ks->row_values > 0 ? &f->f_rows_shutter : nullptr) != 0)
-            return -1;
-        f->shutter_loaded = true;
+    const KernelSource *ks = variant_source(f, which);
+    ModuleVariant &v = f->variants[which];
+    if (!ks || jit_source(*ks, v.code_object) != 0) return -1;
+    if (load_module && !v.loaded) {
+        if (load_kernels(*ks, v.code_object, &v.mod, &v.f_pix, &v.f_pro, ks->row_values > 0 ? &v.f_rows : nullptr) != 0) return -1;
+        v.loaded = true;
     }
     f->jit_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return (long)f->shutter_code_object.size();
+    return (long)v.code_object.size();
 }
 
-// The sampled variant's text (hipgen.h KernelOptions::sampled), like the shutter variant's: generated when first asked
-// for, the other three texts not touched.
-static const mm::KernelSource *sampled_source(mmhip_filter *f) {
-    if (!f->sampled_ks.source.empty()) return &f->sampled_ks;
-    if (!f->ks.natives.empty() || !f->closures.empty() || f->ks.row_values > 0) {
-        fail("filter `" + f->module.main->name + "' has no sampled variant: it calls native filters, renders closure images or has a per-row slice");
-        return nullptr;
-    }
-    if (!f->code) { fail("filter has no sampled variant: its code was not kept"); return nullptr; }
-    try {
-        KernelOptions ko = f->kopt;
-        ko.sampled = true;
-        f->sampled_ks = generate_hip(*f->code, ko);
-    } catch (const std::exception &e) {
-        f->sampled_ks = mm::KernelSource();
-        fail(e.what());
-        return nullptr;
-    }
-    f->sampled_ks.prologue_name = "mm_prologue_clip";
-    return &f->sampled_ks;
-}
-
-const char *mmhip_filter_sampled_kernel_source(mmhip_filter *f) {
-    const mm::KernelSource *ks = sampled_source(f);
-    return ks ? ks->source.c_str() : nullptr;
-}
-
-long mmhip_filter_jit_sampled(mmhip_filter *f, int load_module) {
-    auto t0 = std::chrono::steady_clock::now();
-    const mm::KernelSource *ks = sampled_source(f);
-    if (!ks || jit_source(*ks, f->sampled_code_object) != 0) return -1;
-    if (load_module && !f->sampled_loaded) {
-        if (load_kernels(*ks, f->sampled_code_object, &f->sampled_mod, &f->f_pix_sampled, &f->f_pro_sampled) != 0) return -1;
-        f->sampled_loaded = true;
-    }
-    f->jit_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return (long)f->sampled_code_object.size();
-}
-
-// The refine variant's text (hipgen.h KernelOptions::refine), like the sampled variant's and for the same filters:
-// generated when first asked for, the other four texts not touched.
-static const mm::KernelSource *refine_source(mmhip_filter *f) {
-    if (!f->refine_ks.source.empty()) return &f->refine_ks;
-    if (!f->ks.natives.empty() || !f->closures.empty() || f->ks.row_values > 0) {
-        fail("filter `" + f->module.main->name + "' has no refine variant: it calls native filters, renders closure images or has a per-row slice");
-        return nullptr;
-    }
-    if (!f->code) { fail("filter has no refine variant: its code was not kept"); return nullptr; }
-    try {
-        KernelOptions ko = f->kopt;
-        ko.sampled = ko.refine = true;
-        f->refine_ks = generate_hip(*f->code, ko);
-    } catch (const std::exception &e) {
-        f->refine_ks = mm::KernelSource();
-        fail(e.what());
-        return nullptr;
-    }
-    f->refine_ks.prologue_name = "mm_prologue_clip";
-    return &f->refine_ks;
-}
-
-const char *mmhip_filter_refine_kernel_source(mmhip_filter *f) {
-    const mm::KernelSource *ks = refine_source(f);
-    return ks ? ks->source.c_str() : nullptr;
-}
-
-long mmhip_filter_jit_refine(mmhip_filter *f, int load_module) {
-    auto t0 = std::chrono::steady_clock::now();
-    const mm::KernelSource *ks = refine_source(f);
-    if (!ks || jit_source(*ks, f->refine_code_object) != 0) return -1;
-    if (load_module && !f->refine_loaded) {
-        if (load_kernels(*ks, f->refine_code_object, &f->refine_mod, &f->f_pix_refine, &f->f_pro_refine) != 0) return -1;
-        f->refine_loaded = true;
-    }
-    f->jit_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return (long)f->refine_code_object.size();
-}
+const char *mmhip_filter_clip_kernel_source(mmhip_filter *f) { return variant_text(f, VARIANT_CLIP); }
+long mmhip_filter_jit_clip(mmhip_filter *f, int load_module) { return jit_variant(f, VARIANT_CLIP, load_module); }
+const char *mmhip_filter_shutter_kernel_source(mmhip_filter *f) { return variant_text(f, VARIANT_SHUTTER); }
+long mmhip_filter_jit_shutter(mmhip_filter *f, int load_module) { return jit_variant(f, VARIANT_SHUTTER, load_module); }
+const char *mmhip_filter_sampled_kernel_source(mmhip_filter *f) { return variant_text(f, VARIANT_SAMPLED); }
+long mmhip_filter_jit_sampled(mmhip_filter *f, int load_module) { return jit_variant(f, VARIANT_SAMPLED, load_module); }
+const char *mmhip_filter_refine_kernel_source(mmhip_filter *f) { return variant_text(f, VARIANT_REFINE); }
+long mmhip_filter_jit_refine(mmhip_filter *f, int load_module) { return jit_variant(f, VARIANT_REFINE, load_module); }
 
 // ---------------------------------------------------------------------------
 // invocation

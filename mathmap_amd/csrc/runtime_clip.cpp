@@ -1,7 +1,10 @@
 // Clip rendering: the frames of an animation in batched launches (mmhip_render_clip), supersampled
 // (mmhip_render_clip_supersampled) and motion-blurred (mmhip_render_clip_shutter through sub-sample maps,
-// mmhip_render_clip_shutter_fused in the pixel kernel's registers) and grid-supersampled (mmhip_render_clip_sampled,
-// mmhip_render_clip_sampled_fused: the same two ways), on top of the single-frame path of runtime.cpp.
+// mmhip_render_clip_shutter_fused in the pixel kernel's registers), grid-supersampled (mmhip_render_clip_sampled,
+// mmhip_render_clip_sampled_fused: the same two ways) and adaptively so (mmhip_render_clip_adaptive), on top of the
+// single-frame path of runtime.cpp.  Every entry point checks its arguments into a ClipTarget (clip_target), the paths
+// hand that to each other (render_clip_to, render_clip_maps), and whatever launches a variant's kernels over batches of
+// frames does so through clip_call_begin and clip_call_run.
 // (The exported functions have C linkage from include/mmhip.h.)
 #include <algorithm>
 #include <cmath>
@@ -21,7 +24,7 @@ static size_t env_bytes(const char *name, size_t fallback) {
     return v > 0 ? (size_t)v : fallback;
 }
 
-// The argument checks of the three entry points, under the name of the one that was called.
+// The argument checks every entry point makes, under the name of the one that was called.
 static int check_clip_args(const char *who, int num_frames, const int *frames, const float *ts, int bpp, int region_w, int region_h) {
     if (num_frames < 1) return fail(std::string(who) + ": num_frames must be at least 1");
     if (!frames || !ts) return fail(std::string(who) + ": frames and ts must be arrays of num_frames entries");
@@ -91,22 +94,70 @@ int mmhip_filter_clip_native_plan(const mmhip_filter *f, int region_w, int num_r
     return 0;
 }
 
-// What one call of mmhip_render_clip hands its batches.
+// Where a clip call lands: the region, its rows clamped to the region, the output and its layout, the stream.  Every
+// entry point fills one (clip_target) and the paths hand it to each other.
+struct ClipTarget {
+    int region_x, region_y, region_w, region_h;
+    int first_row, last_row, num_rows;
+    void *out;
+    int row_stride;
+    int64_t frame_stride;
+    int bpp, floatmap;
+    hipStream_t s;
+    // the same rows of the same region as float maps at `maps`, a frame every `stride` bytes: what a path renders its
+    // intermediates to
+    ClipTarget as_floatmaps(void *maps, int64_t stride) const {
+        ClipTarget t = *this;
+        t.out = maps;
+        t.frame_stride = stride;
+        t.floatmap = 1;
+        return t;
+    }
+    // frame b0 of the call as the first one
+    ClipTarget from_frame(int b0) const {
+        ClipTarget t = *this;
+        t.out = (char *)out + (int64_t)b0 * frame_stride;
+        return t;
+    }
+};
+
+// Fills `tg` from an entry point's arguments and makes the checks all of them share, under the name of the one that was
+// called: -1 refused, 0 nothing to render (no row of the region is asked for), 1 filled.  `span`: the shutter's, 0 for a
+// call without one.  `in_render_width`: the paths that go through float maps of the render width want the region inside
+// it.  The invocation is not looked at before a check needs it.
+static int clip_target(const char *who, const mmhip_invocation *inv, float span, int num_frames, const int *frames, const float *ts,
+                       int region_x, int region_y, int region_w, int region_h, int first_row, int last_row, void *out_device, int row_stride,
+                       int64_t frame_stride, int bpp, int floatmap, void *stream, bool in_render_width, ClipTarget *tg) {
+    if (!std::isfinite(span)) return fail(std::string(who) + ": span must be finite");
+    if (check_clip_args(who, num_frames, frames, ts, bpp, region_w, region_h) != 0) return -1;
+    if (!clamp_rows(region_y, region_h, &first_row, &last_row)) return 0;
+    const int num_rows = last_row - first_row;
+    if (check_frame_stride(who, inv, frame_stride, num_rows, region_w, row_stride, bpp, floatmap) != 0) return -1;
+    if (in_render_width && region_w > inv->render_w) return fail(std::string(who) + ": the region is wider than the render width");
+    *tg = ClipTarget{region_x, region_y, region_w, region_h, first_row, last_row, num_rows, out_device, row_stride, frame_stride,
+                     bpp, floatmap, stream ? (hipStream_t)stream : (hipStream_t)inv->stream};
+    return 1;
+}
+
+// What one batched clip call hands its batches: the module that is launched and how, as the caller's plan has it, and
+// what clip_call_begin makes of that.
 struct ClipCall {
     mmhip_invocation *inv;
     mmhip_filter *f;
+    const ModuleVariant *v;    // the variant whose kernels are launched
     hipStream_t s;
-    HArgs a;                   // out: the first frame of the call
-    HClip c;                   // frames: the call's table
-    char *xy;
     LaunchGeometry geo;
-    ClipPlan plan;
-    bool per_frame, rows;
-    size_t xy_stride;
-    int64_t frame_stride;
+    long grid_x;               // of the pixel launch
+    bool per_frame;            // else one frame-constant slot and one row table for all frames
+    size_t xy_stride, rowtab_stride;      // of one slot: bytes, floats
     const int *frames;
     const float *ts;
-    void *stream_arg;
+    // from clip_call_begin
+    HArgs a{};                 // out: the first frame of the call
+    HClip c{};                 // frames: the call's table
+    char *xy = nullptr;
+    bool rows = false;
+    ClipBuffers::Table *tab = nullptr;
     // native batches: the records of the shared slot (read with the first batch) and whether the launch samples a
     // native map at every pixel's own centre (decided once per call)
     std::vector<char> records;
@@ -159,26 +210,26 @@ static int clip_native_batch(ClipCall &cc, int b0, int n) {
     HArgs a = cc.a;
     HClip c = cc.c;
     char *xy = cc.xy;
-    a.out = (char *)cc.a.out + (int64_t)b0 * cc.frame_stride;
+    a.out = (char *)cc.a.out + (int64_t)b0 * cc.c.frame_stride;
     c.frames = cc.c.frames + b0;
     c.images_stride = 0;          // the prologue (and the per-row slice) of every frame reads the invocation's table
     void *params[] = {&a, &xy, &c};
-    const int pro_frames = launch_clip_prologue(f->f_pro_clip, cc.rows ? f->f_rows_clip : nullptr, a, cc.per_frame, b0, n, params, s);
+    const int pro_frames = launch_clip_prologue(cc.v->f_pro, cc.rows ? cc.v->f_rows : nullptr, a, cc.per_frame, b0, n, params, s);
     if (pro_frames < 0) return -1;
     if (pro_frames) {
         cc.records.resize(cc.xy_stride * pro_frames);
         HIP_TRY(hipMemcpyAsync(cc.records.data(), xy, cc.records.size(), hipMemcpyDeviceToHost, s));
     }
     std::vector<float> xt, yt;
-    const bool ask_direct = cc.direct_ok < 0 && direct_output_wanted(f, a) && (cc.frame_stride & 3) == 0;
+    const bool ask_direct = cc.direct_ok < 0 && direct_output_wanted(f, a) && (cc.c.frame_stride & 3) == 0;
     if (ask_direct && read_coordinate_tables(a, s, &xt, &yt) != 0) return -1;
     HIP_TRY(hipStreamSynchronize(s));      // (and with it for the batch before this one: its buffers are free)
     if (cc.direct_ok < 0) cc.direct_ok = ask_direct && samples_own_pixels(a, xt, yt) ? 1 : 0;
     auto frame_by_frame = [&]() -> int {
         for (int i = b0; i < b0 + n; ++i)
             if (mmhip_render(inv, cc.frames[i], cc.ts[i], a.region_x, a.region_y, a.region_width, a.region_height, a.first_row,
-                             a.first_row + a.num_rows, (char *)cc.a.out + (int64_t)i * cc.frame_stride, a.row_stride, a.output_bpp, a.floatmap,
-                             cc.stream_arg) != 0)
+                             a.first_row + a.num_rows, (char *)cc.a.out + (int64_t)i * cc.c.frame_stride, a.row_stride, a.output_bpp, a.floatmap,
+                             cc.s) != 0)
                 return -1;
         return 0;
     };
@@ -300,7 +351,7 @@ static int clip_native_batch(ClipCall &cc, int b0, int n) {
             if ((int)cp.k != k) continue;
             char *w = nb.work.get<char>() + jobs.size() * (ck_bytes + map_bytes);
             jobs.push_back(GaussClipJob{cp.rec, cp.view.empty() ? tables + (size_t)cp.frame * images_n : cp.view.data(), (int)images_n, (double *)w, (float *)(w + ck_bytes), cp.map,
-                                        packs ? (unsigned char *)a.out + (int64_t)cp.frame * cc.frame_stride : nullptr});
+                                        packs ? (unsigned char *)a.out + (int64_t)cp.frame * cc.c.frame_stride : nullptr});
         }
         launches[k].render_w = a.render_width;
         launches[k].render_h = a.render_height;
@@ -325,19 +376,81 @@ static int clip_native_batch(ClipCall &cc, int b0, int n) {
     }
     a.images = nb.tables.get<HImageDesc>();
     c.images_stride = (int)images_n;
-    return timed_pixel_launch(inv, f->f_pix_clip, (unsigned)cc.plan.grid_x, (unsigned)n, params, s);
+    return timed_pixel_launch(inv, cc.v->f_pix, (unsigned)cc.grid_x, (unsigned)n, params, s);
 }
 
-int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int region_x, int region_y,
-                      int region_w, int region_h, int first_row, int last_row, void *out_device, int row_stride,
-                      int64_t frame_stride, int bpp, int floatmap, void *stream) {
-    if (check_clip_args("render_clip", num_frames, frames, ts, bpp, region_w, region_h) != 0) return -1;
-    if (!clamp_rows(region_y, region_h, &first_row, &last_row)) return 0;
-    const int num_rows = last_row - first_row;
-    if (check_frame_stride("render_clip", inv, frame_stride, num_rows, region_w, row_stride, bpp, floatmap) != 0) return -1;
+// ---- the batched launch every path without native calls ends in ----
+// What a batched call sets up before its first launch, for the kernels of `ks` (the text cc.v was made from) over the
+// rows of `tg`: the invocation's tables, the launch arguments of frame frame0 at t0, room for `slots` frame-constant
+// slots and row tables, and the next {t, frame} table with `entries` entries.  The caller writes the table's host side
+// and sends it up (send_clip_table).
+static int clip_call_begin(ClipCall &cc, const ClipTarget &tg, const KernelSource &ks, int frame0, float t0, size_t slots, size_t entries) {
+    mmhip_invocation *inv = cc.inv;
+    hipStream_t s = cc.s;
+    if (upload_tables(inv, s) != 0) return -1;
+    HArgs &a = cc.a;
+    a = render_args(inv, frame0, t0, tg.region_x, tg.region_y, tg.region_w, tg.region_h, tg.first_row, tg.last_row, tg.out, tg.row_stride,
+                    tg.bpp, tg.floatmap);
+    cc.rows = ks.row_values > 0;
+    // the coordinate tables are the single-frame path's, rewritten here: its prologue must run again
+    if (grow_launch_buffers(inv->launch, ks, tg.region_w, tg.num_rows, false, s) != 0) return -1;
+    inv->pro_filter = nullptr;
+    auto wait = [s] { return hipStreamSynchronize(s); };
+    HIP_TRY(inv->clip.xy.grow(cc.xy_stride * slots, wait, true));
+    if (cc.rows) HIP_TRY(inv->clip.rowtab.grow(cc.rowtab_stride * slots * sizeof(float), wait));
+    if (next_clip_table(inv, entries, s, &cc.tab) != 0) return -1;
+
+    a.xtab = inv->launch.xtab.get<float>();
+    a.ytab = inv->launch.ytab.get<float>();
+    if (cc.rows) a.rowtab = inv->clip.rowtab.get<float>();
+    a.ppt = cc.geo.ppt;
+    a.tiles_magic = cc.geo.tiles_magic;
+    cc.xy = inv->clip.xy.get<char>();
+    cc.c = HClip{};
+    cc.c.frames = cc.tab->dev.get<HClipFrame>();
+    cc.c.frame_stride = tg.frame_stride;
+    cc.c.xy_stride = cc.per_frame ? (int)cc.xy_stride : 0;
+    cc.c.rowtab_stride = cc.per_frame ? (int)cc.rowtab_stride : 0;
+    cc.c.nwg = (int)cc.geo.nwg;
+    return 0;
+}
+
+// The launches of a call that clip_call_begin has set up: `num_frames` output frames, `per_batch` of them to a pixel
+// launch, each with `per_frame_slots` entries of the table (1, or the sub-samples in time of a fused frame); the prologue
+// (and the per-row slice) runs over a batch's slots.  params: &cc.a, &cc.xy, &cc.c and what the variant's kernels take
+// behind them.  `launches` is the caller's counter of batches; without one the caller counts for itself, and the
+// prologue's slots are not counted either.
+static int clip_call_run(ClipCall &cc, int num_frames, int per_batch, int per_frame_slots, void **params, long *launches) {
+    const ClipBuffers::Table &tab = *cc.tab;
+    char *out = (char *)cc.a.out;
+    for (int b0 = 0; b0 < num_frames; b0 += per_batch) {
+        const int n = std::min(per_batch, num_frames - b0);
+        cc.a.out = out + (int64_t)b0 * cc.c.frame_stride;
+        cc.c.frames = tab.dev.get<HClipFrame>() + (size_t)b0 * per_frame_slots;
+        const int pro_slots = launch_clip_prologue(cc.v->f_pro, cc.rows ? cc.v->f_rows : nullptr, cc.a, cc.per_frame, b0, n * per_frame_slots,
+                                                   params, cc.s);
+        if (pro_slots < 0) return -1;
+        if (timed_pixel_launch(cc.inv, cc.v->f_pix, (unsigned)cc.grid_x, (unsigned)n, params, cc.s) != 0) return -1;
+        if (launches) {
+            cc.inv->clip_prologue_frames += pro_slots;
+            ++*launches;
+        }
+    }
+    return 0;
+}
+
+// The {t, frame} entries of `num_frames` frames with `samples` instants each (mm_shutter_sample_t; one instant is the
+// frame's own t): slot i * samples + j is instant j of frame i.
+static void fill_clip_table(HClipFrame *hf, int num_frames, const int *frames, const float *ts, int samples, float span) {
+    for (int i = 0; i < num_frames; ++i)
+        for (int j = 0; j < samples; ++j)
+            hf[(size_t)i * samples + j] = HClipFrame{samples == 1 ? ts[i] : mm_shutter_sample_t(ts[i], span, j, samples), frames[i]};
+}
+
+// mmhip_render_clip behind its argument checks: what the other paths render their float maps with.
+static int render_clip_to(mmhip_invocation *inv, const ClipTarget &tg, int num_frames, const int *frames, const float *ts) {
     mmhip_filter *f = active_filter(inv, frames[0], ts[0]);
-    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
-    const LaunchGeometry geo = clip_launch_geometry(f->ks, region_w, num_rows, num_frames);
+    const LaunchGeometry geo = clip_launch_geometry(f->ks, tg.region_w, tg.num_rows, num_frames);
     const ClipPlan plan = clip_plan(geo);
     const bool natives = !f->ks.natives.empty();
     const ClipNativePlan nplan = natives ? clip_native_plan(f, inv->native_row_margin, plan, inv->render_w, inv->render_h) : ClipNativePlan();
@@ -345,67 +458,40 @@ int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, 
         // native filters run the host between prologue and pixels of every frame: frame by frame, the same result
         // (but for gaussian_blur calls the batches below take)
         for (int i = 0; i < num_frames; ++i)
-            if (mmhip_render(inv, frames[i], ts[i], region_x, region_y, region_w, region_h, first_row, last_row,
-                             (char *)out_device + (int64_t)i * frame_stride, row_stride, bpp, floatmap, stream) != 0)
+            if (mmhip_render(inv, frames[i], ts[i], tg.region_x, tg.region_y, tg.region_w, tg.region_h, tg.first_row, tg.last_row,
+                             (char *)tg.out + (int64_t)i * tg.frame_stride, tg.row_stride, tg.bpp, tg.floatmap, tg.s) != 0)
                 return -1;
         return 0;
     }
     if (mmhip_filter_jit_clip(f, 1) < 0) return -1;
-    if (upload_tables(inv, s) != 0) return -1;
-
-    HArgs a = render_args(inv, frames[0], ts[0], region_x, region_y, region_w, region_h, first_row, last_row, out_device, row_stride, bpp, floatmap);
-    const bool per_frame = f->ks.prologue_uses_time;      // else one frame-constant slot and one row table for all frames
-    const bool rows = f->ks.row_values > 0;
+    const bool per_frame = f->ks.prologue_uses_time;
     const int per_batch = std::min(num_frames, natives ? nplan.per_batch : plan.max_frames);
     const size_t xy_stride = ((size_t)std::max(f->ks.xy_bytes, 256) + 255) / 256 * 256;
-    const size_t rowtab_stride = (size_t)f->ks.row_values * num_rows;      // floats
+    const size_t rowtab_stride = (size_t)f->ks.row_values * tg.num_rows;
     const int slots = per_frame ? per_batch : 1;
     if (rowtab_stride * slots > (size_t)INT32_MAX || xy_stride * slots > (size_t)INT32_MAX)
         return fail("render_clip: the batch's row tables are too large; lower MMHIP_CLIP_MAX_FRAMES");
-    // the coordinate tables are the single-frame path's, rewritten here: its prologue must run again
-    if (grow_launch_buffers(inv->launch, f->ks, region_w, num_rows, false, s) != 0) return -1;
-    inv->pro_filter = nullptr;
-    auto wait = [s] { return hipStreamSynchronize(s); };
-    HIP_TRY(inv->clip.xy.grow(xy_stride * slots, wait, true));
-    if (rows) HIP_TRY(inv->clip.rowtab.grow(rowtab_stride * slots * sizeof(float), wait));
+    ClipCall cc{inv, f, &f->variants[VARIANT_CLIP], tg.s, geo, plan.grid_x, per_frame, xy_stride, rowtab_stride, frames, ts};
     // the {t, frame} table of the whole call, copied now: the caller's arrays are free when this returns
-    ClipBuffers::Table *tabp = nullptr;
-    if (next_clip_table(inv, (size_t)num_frames, s, &tabp) != 0) return -1;
-    ClipBuffers::Table &tab = *tabp;
-    HClipFrame *hf = (HClipFrame *)tab.host.p;
-    for (int i = 0; i < num_frames; ++i) hf[i] = HClipFrame{ts[i], frames[i]};
-    if (send_clip_table(tab, (size_t)num_frames, s) != 0) return -1;
-
-    a.xtab = inv->launch.xtab.get<float>();
-    a.ytab = inv->launch.ytab.get<float>();
-    if (rows) a.rowtab = inv->clip.rowtab.get<float>();
-    a.ppt = geo.ppt;
-    a.tiles_magic = geo.tiles_magic;
-    char *xy = inv->clip.xy.get<char>();
-    HClip c{};
-    c.frame_stride = frame_stride;
-    c.xy_stride = per_frame ? (int)xy_stride : 0;
-    c.rowtab_stride = per_frame ? (int)rowtab_stride : 0;
-    c.nwg = (int)geo.nwg;
+    if (clip_call_begin(cc, tg, f->ks, frames[0], ts[0], (size_t)slots, (size_t)num_frames) != 0) return -1;
+    fill_clip_table((HClipFrame *)cc.tab->host.p, num_frames, frames, ts, 1, 0.0f);
+    if (send_clip_table(*cc.tab, (size_t)num_frames, tg.s) != 0) return -1;
     if (natives) {
-        ClipCall cc{inv, f, s, a, c, xy, geo, plan, per_frame, rows, xy_stride, frame_stride, frames, ts, stream, {}, -1};
-        cc.c.frames = tab.dev.get<HClipFrame>();
         for (int b0 = 0; b0 < num_frames; b0 += per_batch)
             if (clip_native_batch(cc, b0, std::min(per_batch, num_frames - b0)) != 0) return -1;
         return 0;
     }
-    void *params[] = {&a, &xy, &c};
-    for (int b0 = 0; b0 < num_frames; b0 += per_batch) {
-        const int n = std::min(per_batch, num_frames - b0);
-        a.out = (char *)out_device + (int64_t)b0 * frame_stride;
-        c.frames = tab.dev.get<HClipFrame>() + b0;
-        const int pro_frames = launch_clip_prologue(f->f_pro_clip, rows ? f->f_rows_clip : nullptr, a, per_frame, b0, n, params, s);
-        if (pro_frames < 0) return -1;
-        inv->clip_prologue_frames += pro_frames;
-        if (timed_pixel_launch(inv, f->f_pix_clip, (unsigned)plan.grid_x, (unsigned)n, params, s) != 0) return -1;
-        ++inv->clip_batched_launches;
-    }
-    return 0;
+    void *params[] = {&cc.a, &cc.xy, &cc.c};
+    return clip_call_run(cc, num_frames, per_batch, 1, params, &inv->clip_batched_launches);
+}
+
+int mmhip_render_clip(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int region_x, int region_y,
+                      int region_w, int region_h, int first_row, int last_row, void *out_device, int row_stride,
+                      int64_t frame_stride, int bpp, int floatmap, void *stream) {
+    ClipTarget tg;
+    const int go = clip_target("render_clip", inv, 0.0f, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row,
+                               out_device, row_stride, frame_stride, bpp, floatmap, stream, false, &tg);
+    return go == 1 ? render_clip_to(inv, tg, num_frames, frames, ts) : go;
 }
 
 // ---- supersampled clips ----
@@ -490,26 +576,28 @@ int mmhip_render_clip_supersampled(mmhip_invocation *inv, int num_frames, const 
     return 0;
 }
 
-// ---- motion-blurred clips ----
-// How mmhip_render_clip_shutter cuts a clip into batches and a frame's sub-samples into passes (include/mmhip.h has the
-// rules).  MMHIP_CLIP_SHUTTER_BYTES is read once, default 8 GiB.
+// ---- clips through sub-sample maps: motion-blurred (mmhip_render_clip_shutter), grid-supersampled (mmhip_render_clip_sampled) ----
+// MMHIP_CLIP_SHUTTER_BYTES is read once, default 8 GiB.
 static size_t clip_shutter_budget() {
     static const size_t budget = env_bytes("MMHIP_CLIP_SHUTTER_BYTES", (size_t)8 << 30);
     return budget;
 }
-struct ClipShutterPlan { int per_batch = 1, batches = 1, samples_per_pass = 1, passes = 1, carry = 0; size_t bytes_per_sample = 0; };
-static ClipShutterPlan clip_shutter_plan(int num_rows, int render_w, int samples, int frames) {
+
+// How the maps path cuts a clip into batches and a frame's time steps into passes (include/mmhip.h has the rules of both
+// entry points): `samples` time steps of `grid` maps each -- one for the shutter alone -- under the one budget.
+struct ClipMapsPlan { int per_batch = 1, batches = 1, steps_per_pass = 1, passes = 1, carry = 0; size_t bytes_per_sample = 0; };
+static ClipMapsPlan clip_maps_plan(int num_rows, int render_w, int samples, int grid, int frames) {
     const size_t budget = clip_shutter_budget();
-    ClipShutterPlan p;
+    ClipMapsPlan p;
     p.bytes_per_sample = (size_t)num_rows * 16 * (size_t)render_w;
-    const size_t frame_bytes = (size_t)samples * p.bytes_per_sample;
+    const size_t frame_bytes = (size_t)samples * grid * p.bytes_per_sample;
     if (budget >= frame_bytes) {
         p.per_batch = (int)std::min<size_t>({budget / frame_bytes, (size_t)65535, (size_t)frames});
-        p.samples_per_pass = samples;
+        p.steps_per_pass = samples;
     } else {
-        // not one frame's sub-samples: a frame at a time, in passes over what fits beside the carry map (at least one)
-        p.samples_per_pass = (int)std::max<long long>(1, (long long)(budget / p.bytes_per_sample) - 1);
-        p.passes = (samples + p.samples_per_pass - 1) / p.samples_per_pass;
+        // not one frame's sub-samples: a frame at a time, in passes of whole time steps beside the carry map (at least one step)
+        p.steps_per_pass = (int)std::max<long long>(1, ((long long)(budget / p.bytes_per_sample) - 1) / grid);
+        p.passes = (samples + p.steps_per_pass - 1) / p.steps_per_pass;
         p.carry = p.passes > 1;
     }
     p.batches = (frames + p.per_batch - 1) / p.per_batch;
@@ -522,48 +610,75 @@ static int clip_shutter_check_samples(const char *who, int samples) {
     return 0;
 }
 
+// The checks the sampled entry points make of the grid and the sub-sample count, under the name of the one called.
+static int clip_sampled_check(const char *who, int samples, int grid_x, int grid_y) {
+    if (grid_x < 1 || grid_x > MMHIP_SAMPLE_GRID_MAX || grid_y < 1 || grid_y > MMHIP_SAMPLE_GRID_MAX)
+        return fail(std::string(who) + ": grid_x and grid_y must be 1 to " + std::to_string((int)MMHIP_SAMPLE_GRID_MAX) + ", not " +
+                    std::to_string(grid_x) + " x " + std::to_string(grid_y));
+    if (clip_shutter_check_samples(who, samples) != 0) return -1;
+    if (samples * grid_x * grid_y > MMHIP_SHUTTER_MAX_SAMPLES)
+        return fail(std::string(who) + ": samples * grid_x * grid_y must be at most " + std::to_string((int)MMHIP_SHUTTER_MAX_SAMPLES) + ", not " +
+                    std::to_string(samples * grid_x * grid_y));
+    return 0;
+}
+
+// The fields both maps plans report (MMHIP_CLIP_SHUTTER_PLAN_FIELDS, MMHIP_CLIP_SAMPLED_PLAN_FIELDS: the same six).
+static int put_maps_plan(const ClipMapsPlan &p, int64_t *out) {
+    static_assert(MMHIP_CLIP_SHUTTER_PLAN_FIELDS == 6 && MMHIP_CLIP_SAMPLED_PLAN_FIELDS == 6, "the maps plans' fields");
+    const int64_t v[6] = {p.per_batch, p.batches, p.steps_per_pass, p.passes, (int64_t)p.bytes_per_sample, p.carry};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
 int mmhip_filter_clip_shutter_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int samples, int frames, int64_t *out) {
     (void)f;
     if (frames < 1) return fail("clip shutter plan: num_frames must be at least 1");
     if (clip_shutter_check_samples("clip shutter plan", samples) != 0) return -1;
     if (region_w < 1 || num_rows < 1 || render_w < region_w) return fail("clip shutter plan: empty region, or one wider than the render width");
-    const ClipShutterPlan p = clip_shutter_plan(num_rows, render_w, samples, frames);
-    const int64_t v[MMHIP_CLIP_SHUTTER_PLAN_FIELDS] = {p.per_batch, p.batches, p.samples_per_pass, p.passes, (int64_t)p.bytes_per_sample, p.carry};
-    memcpy(out, v, sizeof v);
-    return 0;
+    return put_maps_plan(clip_maps_plan(num_rows, render_w, samples, 1, frames), out);
+}
+
+int mmhip_filter_clip_sampled_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int samples, int grid_x, int grid_y,
+                                   int frames, int64_t *out) {
+    (void)f;
+    if (frames < 1) return fail("clip sampled plan: num_frames must be at least 1");
+    if (clip_sampled_check("clip sampled plan", samples, grid_x, grid_y) != 0) return -1;
+    if (region_w < 1 || num_rows < 1 || render_w < region_w) return fail("clip sampled plan: empty region, or one wider than the render width");
+    return put_maps_plan(clip_maps_plan(num_rows, render_w, samples, grid_x * grid_y, frames), out);
 }
 
 long mmhip_clip_shutter_batches(mmhip_invocation *inv) { return inv->clip_shutter_batches; }
+long mmhip_clip_sampled_batches(mmhip_invocation *inv) { return inv->clip_sampled_batches; }
 
-int mmhip_render_clip_shutter(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
-                              int region_x, int region_y, int region_w, int region_h, int first_row, int last_row, void *out_device,
-                              int row_stride, int64_t frame_stride, int bpp, int floatmap, void *stream) {
-    if (clip_shutter_check_samples("render_clip_shutter", samples) != 0) return -1;
-    if (samples == 1)       // one instant per frame: the plain clip itself
-        return mmhip_render_clip(inv, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
-                                 row_stride, frame_stride, bpp, floatmap, stream);
-    if (!std::isfinite(span)) return fail("render_clip_shutter: span must be finite");
-    if (check_clip_args("render_clip_shutter", num_frames, frames, ts, bpp, region_w, region_h) != 0) return -1;
-    if (!clamp_rows(region_y, region_h, &first_row, &last_row)) return 0;
-    const int num_rows = last_row - first_row;
-    if (check_frame_stride("render_clip_shutter", inv, frame_stride, num_rows, region_w, row_stride, bpp, floatmap) != 0) return -1;
-    if (region_w > inv->render_w) return fail("render_clip_shutter: the region is wider than the render width");
-    const ClipShutterPlan plan = clip_shutter_plan(num_rows, inv->render_w, samples, num_frames);
+// A clip of frames that are each the mean of samples * grid_x * grid_y float maps: `samples` instants of the shutter, at
+// every one a grid_x x grid_y grid of sampling offsets inside the pixel.  A 1 x 1 grid is the motion-blurred clip and
+// renders at the caller's sampling offset, which it does not touch; a grid replaces that offset with its own and puts it
+// back on every way out.  The two speak and count as the entry points they are.
+static int render_clip_maps(mmhip_invocation *inv, const ClipTarget &tg, int num_frames, const int *frames, const float *ts, int samples,
+                            float span, int grid_x, int grid_y) {
+    const int grid = grid_x * grid_y;
+    const bool gridded = grid > 1;
+    const std::string who = gridded ? "render_clip_sampled" : "render_clip_shutter";
+    long &batches = gridded ? inv->clip_sampled_batches : inv->clip_shutter_batches;
+    const ClipMapsPlan plan = clip_maps_plan(tg.num_rows, inv->render_w, samples, grid, num_frames);
     const size_t bps = plan.bytes_per_sample;
-    if (bps > ((size_t)1 << 32)) return fail("render_clip_shutter: a sub-sample map of more than 4 GiB; render the frame in row bands");
-    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
-    // own allocation, like clip_ss; whatever still reads a smaller one has finished before it is freed
-    const size_t slots = (size_t)plan.per_batch * plan.samples_per_pass;
+    if (bps > ((size_t)1 << 32)) return fail(who + ": a sub-sample map of more than 4 GiB; render the frame in row bands");
+    hipStream_t s = tg.s;
+    // own allocation, like clip_ss: [frame][time step][grid point] maps, the carry map behind them; whatever still reads a
+    // smaller one has finished before it is freed
+    const size_t slots = (size_t)plan.per_batch * plan.steps_per_pass * grid;
     if (inv->clip_shutter.grow((slots + plan.carry) * bps, hipDeviceSynchronize) != hipSuccess)
-        return fail("out of device memory for the sub-samples of a motion-blurred clip; lower MMHIP_CLIP_SHUTTER_BYTES");
+        return fail(std::string("out of device memory for the sub-samples of a ") + (gridded ? "grid-supersampled" : "motion-blurred") +
+                    " clip; lower MMHIP_CLIP_SHUTTER_BYTES");
     unsigned char *subs = inv->clip_shutter.get<unsigned char>(), *carry = plan.carry ? subs + slots * bps : nullptr;
-    const float inv_k = mm_shutter_inv_k(samples);
+    const float inv_k = mm_shutter_inv_k(samples * grid);
+    SamplingOffsetGuard offsets(inv);
     std::vector<int> sub_frames;
     std::vector<float> sub_ts;
     for (int b0 = 0; b0 < num_frames; b0 += plan.per_batch) {
         const int n = std::min(plan.per_batch, num_frames - b0);
-        for (int j0 = 0; j0 < samples; j0 += plan.samples_per_pass) {
-            const int count = std::min(plan.samples_per_pass, samples - j0);
+        for (int j0 = 0; j0 < samples; j0 += plan.steps_per_pass) {
+            const int count = std::min(plan.steps_per_pass, samples - j0);
             sub_frames.resize((size_t)n * count);
             sub_ts.resize((size_t)n * count);
             for (int i = 0; i < n; ++i)
@@ -571,25 +686,61 @@ int mmhip_render_clip_shutter(mmhip_invocation *inv, int num_frames, const int *
                     sub_frames[(size_t)i * count + j] = frames[b0 + i];
                     sub_ts[(size_t)i * count + j] = mm_shutter_sample_t(ts[b0 + i], span, j0 + j, samples);
                 }
-            if (mmhip_render_clip(inv, n * count, sub_frames.data(), sub_ts.data(), region_x, region_y, region_w, region_h, first_row,
-                                  last_row, subs, row_stride, (int64_t)bps, bpp, 1, s) != 0)
-                return -1;
+            // grid point g = b * grid_x + a of entry e = i * count + j lands at (e * G + g) * bps: the layout [i][j][g]
+            for (int b = 0; b < grid_y; ++b)
+                for (int a = 0; a < grid_x; ++a) {
+                    if (gridded) offsets.set(mm_sample_grid_offset(a, grid_x), mm_sample_grid_offset(b, grid_y));
+                    if (render_clip_to(inv, tg.as_floatmaps(subs + (size_t)(b * grid_x + a) * bps, (int64_t)grid * (int64_t)bps), n * count,
+                                       sub_frames.data(), sub_ts.data()) != 0)
+                        return -1;
+                }
             const bool last = j0 + count >= samples;
             std::string err;
-            if (launch_shutter_combine_clip(subs, (int64_t)bps, (int64_t)count * (int64_t)bps, count, j0 > 0 ? carry : nullptr, last ? nullptr : carry,
-                                            (char *)out_device + (int64_t)b0 * frame_stride, region_w, num_rows, inv->render_w, row_stride,
-                                            frame_stride, bpp, floatmap, inv_k, n, inv->ws, s, &err) != 0)
+            if (launch_shutter_combine_clip(subs, (int64_t)bps, (int64_t)count * grid * (int64_t)bps, count * grid, j0 > 0 ? carry : nullptr,
+                                            last ? nullptr : carry, (char *)tg.out + (int64_t)b0 * tg.frame_stride, tg.region_w, tg.num_rows,
+                                            inv->render_w, tg.row_stride, tg.frame_stride, tg.bpp, tg.floatmap, inv_k, n, inv->ws, s, &err) != 0)
                 return fail(err);
         }
-        ++inv->clip_shutter_batches;
+        ++batches;
     }
     return 0;
 }
 
-// ---- motion-blurred clips, fused ----
+int mmhip_render_clip_shutter(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
+                              int region_x, int region_y, int region_w, int region_h, int first_row, int last_row, void *out_device,
+                              int row_stride, int64_t frame_stride, int bpp, int floatmap, void *stream) {
+    const char *who = "render_clip_shutter";
+    if (clip_shutter_check_samples(who, samples) != 0) return -1;
+    if (samples == 1)       // one instant per frame: the plain clip itself
+        return mmhip_render_clip(inv, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
+                                 row_stride, frame_stride, bpp, floatmap, stream);
+    ClipTarget tg;
+    const int go = clip_target(who, inv, span, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
+                               row_stride, frame_stride, bpp, floatmap, stream, true, &tg);
+    return go == 1 ? render_clip_maps(inv, tg, num_frames, frames, ts, samples, span, 1, 1) : go;
+}
+
+int mmhip_render_clip_sampled(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
+                              int grid_x, int grid_y, int region_x, int region_y, int region_w, int region_h, int first_row,
+                              int last_row, void *out_device, int row_stride, int64_t frame_stride, int bpp, int floatmap, void *stream) {
+    const char *who = "render_clip_sampled";
+    if (grid_x == 1 && grid_y == 1)      // one sample per pixel: the motion-blurred clip itself (and with samples = 1 the plain one)
+        return mmhip_render_clip_shutter(inv, num_frames, frames, ts, samples, span, region_x, region_y, region_w, region_h, first_row,
+                                         last_row, out_device, row_stride, frame_stride, bpp, floatmap, stream);
+    if (clip_sampled_check(who, samples, grid_x, grid_y) != 0) return -1;
+    ClipTarget tg;
+    const int go = clip_target(who, inv, span, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
+                               row_stride, frame_stride, bpp, floatmap, stream, true, &tg);
+    return go == 1 ? render_clip_maps(inv, tg, num_frames, frames, ts, samples, span, grid_x, grid_y) : go;
+}
+
+// ---- the same clips, fused: a pixel's sub-samples summed in the pixel kernel's registers ----
 // mm_shutter of mm_pixels_shutter (hipgen.cpp shutter_prelude)
 struct HShutter { int samples; float inv_k; };
 static_assert(sizeof(HShutter) == 8, "mm_shutter layout");
+// mm_sampled of the sampled variant's kernels (hipgen.cpp sampled_prelude)
+struct HSampled { const float *offs; float *xtabs; float *ytabs; int samples, gx, gy, total; float inv_k; int pad; };
+static_assert(sizeof(HSampled) == 48, "mm_sampled layout");
 
 // How mmhip_render_clip_shutter_fused cuts a clip into batches (include/mmhip.h has the rules): a slot is one sub-sample's
 // frame constants and row table, per_batch output frames are one pixel launch.  fused false: the call is
@@ -623,199 +774,6 @@ static ClipShutterFusedPlan clip_shutter_fused_plan(const mmhip_filter *f, int r
     return p;
 }
 
-int mmhip_filter_clip_shutter_fused_plan(const mmhip_filter *f, int region_w, int num_rows, int samples, int frames, int64_t *out) {
-    if (frames < 1) return fail("clip shutter fused plan: num_frames must be at least 1");
-    if (clip_shutter_check_samples("clip shutter fused plan", samples) != 0) return -1;
-    if (region_w < 1 || num_rows < 1) return fail("clip shutter fused plan: empty region");
-    const ClipShutterFusedPlan p = clip_shutter_fused_plan(f, region_w, num_rows, samples, frames);
-    const int64_t v[MMHIP_CLIP_SHUTTER_FUSED_PLAN_FIELDS] = {p.fused, p.per_batch, p.batches, p.fused ? p.slots_per_batch : 0, p.grid_x};
-    memcpy(out, v, sizeof v);
-    return 0;
-}
-
-long mmhip_clip_shutter_fused_batches(mmhip_invocation *inv) { return inv->clip_shutter_fused_batches; }
-
-int mmhip_render_clip_shutter_fused(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
-                                    int region_x, int region_y, int region_w, int region_h, int first_row, int last_row,
-                                    void *out_device, int row_stride, int64_t frame_stride, int bpp, int floatmap, void *stream) {
-    const char *who = "render_clip_shutter_fused";
-    if (clip_shutter_check_samples(who, samples) != 0) return -1;
-    if (samples == 1)       // one instant per frame: the plain clip itself
-        return mmhip_render_clip(inv, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
-                                 row_stride, frame_stride, bpp, floatmap, stream);
-    if (!std::isfinite(span)) return fail(std::string(who) + ": span must be finite");
-    if (check_clip_args(who, num_frames, frames, ts, bpp, region_w, region_h) != 0) return -1;
-    const int first_arg = first_row, last_arg = last_row;
-    if (!clamp_rows(region_y, region_h, &first_row, &last_row)) return 0;
-    const int num_rows = last_row - first_row;
-    if (check_frame_stride(who, inv, frame_stride, num_rows, region_w, row_stride, bpp, floatmap) != 0) return -1;
-    if (region_w > inv->render_w) return fail(std::string(who) + ": the region is wider than the render width");
-    mmhip_filter *f = active_filter(inv, frames[0], ts[0]);
-    const ClipShutterFusedPlan plan = clip_shutter_fused_plan(f, region_w, num_rows, samples, num_frames);
-    if (!plan.fused)        // native calls, closure images, a frame too large for one launch: the sub-sample maps
-        return mmhip_render_clip_shutter(inv, num_frames, frames, ts, samples, span, region_x, region_y, region_w, region_h, first_arg,
-                                         last_arg, out_device, row_stride, frame_stride, bpp, floatmap, stream);
-    if (mmhip_filter_jit_shutter(f, 1) < 0) return -1;
-    const KernelSource &ks = f->shutter_ks;
-    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
-    if (upload_tables(inv, s) != 0) return -1;
-
-    HArgs a = render_args(inv, frames[0], ts[0], region_x, region_y, region_w, region_h, first_row, last_row, out_device, row_stride, bpp, floatmap);
-    const bool rows = ks.row_values > 0;
-    // the coordinate tables are the single-frame path's, rewritten here: its prologue must run again
-    if (grow_launch_buffers(inv->launch, ks, region_w, num_rows, false, s) != 0) return -1;
-    inv->pro_filter = nullptr;
-    auto wait = [s] { return hipStreamSynchronize(s); };
-    HIP_TRY(inv->clip.xy.grow(plan.xy_stride * plan.slots_per_batch, wait, true));
-    if (rows) HIP_TRY(inv->clip.rowtab.grow(plan.rowtab_stride * plan.slots_per_batch * sizeof(float), wait));
-    // the {t, frame} table of every sub-sample of the call: slot i * samples + j is sub-sample j of output frame i
-    const size_t slots = (size_t)num_frames * samples;
-    ClipBuffers::Table *tab = nullptr;
-    if (next_clip_table(inv, slots, s, &tab) != 0) return -1;
-    HClipFrame *hf = (HClipFrame *)tab->host.p;
-    for (int i = 0; i < num_frames; ++i)
-        for (int j = 0; j < samples; ++j) hf[(size_t)i * samples + j] = HClipFrame{mm_shutter_sample_t(ts[i], span, j, samples), frames[i]};
-    if (send_clip_table(*tab, slots, s) != 0) return -1;
-
-    a.xtab = inv->launch.xtab.get<float>();
-    a.ytab = inv->launch.ytab.get<float>();
-    if (rows) a.rowtab = inv->clip.rowtab.get<float>();
-    a.ppt = plan.geo.ppt;
-    a.tiles_magic = plan.geo.tiles_magic;
-    char *xy = inv->clip.xy.get<char>();
-    HClip c{};
-    c.frame_stride = frame_stride;
-    c.xy_stride = plan.per_frame ? (int)plan.xy_stride : 0;
-    c.rowtab_stride = plan.per_frame ? (int)plan.rowtab_stride : 0;
-    c.nwg = (int)plan.geo.nwg;
-    HShutter sh{samples, mm_shutter_inv_k(samples)};
-    void *params[] = {&a, &xy, &c, &sh};      // (the prologue and the per-row slice take the first three)
-    for (int b0 = 0; b0 < num_frames; b0 += plan.per_batch) {
-        const int n = std::min(plan.per_batch, num_frames - b0);
-        a.out = (char *)out_device + (int64_t)b0 * frame_stride;
-        c.frames = tab->dev.get<HClipFrame>() + (size_t)b0 * samples;
-        const int pro_slots = launch_clip_prologue(f->f_pro_shutter, rows ? f->f_rows_shutter : nullptr, a, plan.per_frame, b0, n * samples, params, s);
-        if (pro_slots < 0) return -1;
-        inv->clip_prologue_frames += pro_slots;
-        if (timed_pixel_launch(inv, f->f_pix_shutter, (unsigned)plan.grid_x, (unsigned)n, params, s) != 0) return -1;
-        ++inv->clip_shutter_fused_batches;
-    }
-    return 0;
-}
-
-// ---- grid-supersampled clips ----
-// The checks both sampled entry points make of the grid and the sub-sample count, under the name of the one called.
-static int clip_sampled_check(const char *who, int samples, int grid_x, int grid_y) {
-    if (grid_x < 1 || grid_x > MMHIP_SAMPLE_GRID_MAX || grid_y < 1 || grid_y > MMHIP_SAMPLE_GRID_MAX)
-        return fail(std::string(who) + ": grid_x and grid_y must be 1 to " + std::to_string((int)MMHIP_SAMPLE_GRID_MAX) + ", not " +
-                    std::to_string(grid_x) + " x " + std::to_string(grid_y));
-    if (clip_shutter_check_samples(who, samples) != 0) return -1;
-    if (samples * grid_x * grid_y > MMHIP_SHUTTER_MAX_SAMPLES)
-        return fail(std::string(who) + ": samples * grid_x * grid_y must be at most " + std::to_string((int)MMHIP_SHUTTER_MAX_SAMPLES) + ", not " +
-                    std::to_string(samples * grid_x * grid_y));
-    return 0;
-}
-
-// How mmhip_render_clip_sampled cuts a clip into batches and a frame's time steps into passes (include/mmhip.h has the
-// rules): the shutter's plan with G = grid_x * grid_y maps per time step, under the same budget.
-struct ClipSampledPlan { int per_batch = 1, batches = 1, steps_per_pass = 1, passes = 1, carry = 0; size_t bytes_per_sample = 0; };
-static ClipSampledPlan clip_sampled_plan(int num_rows, int render_w, int samples, int grid, int frames) {
-    const size_t budget = clip_shutter_budget();
-    ClipSampledPlan p;
-    p.bytes_per_sample = (size_t)num_rows * 16 * (size_t)render_w;
-    const size_t frame_bytes = (size_t)samples * grid * p.bytes_per_sample;
-    if (budget >= frame_bytes) {
-        p.per_batch = (int)std::min<size_t>({budget / frame_bytes, (size_t)65535, (size_t)frames});
-        p.steps_per_pass = samples;
-    } else {
-        // not one frame's sub-samples: a frame at a time, in passes of whole time steps beside the carry map (at least one step)
-        p.steps_per_pass = (int)std::max<long long>(1, ((long long)(budget / p.bytes_per_sample) - 1) / grid);
-        p.passes = (samples + p.steps_per_pass - 1) / p.steps_per_pass;
-        p.carry = p.passes > 1;
-    }
-    p.batches = (frames + p.per_batch - 1) / p.per_batch;
-    return p;
-}
-
-int mmhip_filter_clip_sampled_plan(const mmhip_filter *f, int region_w, int num_rows, int render_w, int samples, int grid_x, int grid_y,
-                                   int frames, int64_t *out) {
-    (void)f;
-    if (frames < 1) return fail("clip sampled plan: num_frames must be at least 1");
-    if (clip_sampled_check("clip sampled plan", samples, grid_x, grid_y) != 0) return -1;
-    if (region_w < 1 || num_rows < 1 || render_w < region_w) return fail("clip sampled plan: empty region, or one wider than the render width");
-    const ClipSampledPlan p = clip_sampled_plan(num_rows, render_w, samples, grid_x * grid_y, frames);
-    const int64_t v[MMHIP_CLIP_SAMPLED_PLAN_FIELDS] = {p.per_batch, p.batches, p.steps_per_pass, p.passes, (int64_t)p.bytes_per_sample, p.carry};
-    memcpy(out, v, sizeof v);
-    return 0;
-}
-
-long mmhip_clip_sampled_batches(mmhip_invocation *inv) { return inv->clip_sampled_batches; }
-
-int mmhip_render_clip_sampled(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
-                              int grid_x, int grid_y, int region_x, int region_y, int region_w, int region_h, int first_row,
-                              int last_row, void *out_device, int row_stride, int64_t frame_stride, int bpp, int floatmap, void *stream) {
-    const char *who = "render_clip_sampled";
-    if (grid_x == 1 && grid_y == 1)      // one sample per pixel: the motion-blurred clip itself (and with samples = 1 the plain one)
-        return mmhip_render_clip_shutter(inv, num_frames, frames, ts, samples, span, region_x, region_y, region_w, region_h, first_row,
-                                         last_row, out_device, row_stride, frame_stride, bpp, floatmap, stream);
-    if (clip_sampled_check(who, samples, grid_x, grid_y) != 0) return -1;
-    if (!std::isfinite(span)) return fail(std::string(who) + ": span must be finite");
-    if (check_clip_args(who, num_frames, frames, ts, bpp, region_w, region_h) != 0) return -1;
-    const int first_arg = first_row, last_arg = last_row;
-    if (!clamp_rows(region_y, region_h, &first_row, &last_row)) return 0;
-    const int num_rows = last_row - first_row;
-    if (check_frame_stride(who, inv, frame_stride, num_rows, region_w, row_stride, bpp, floatmap) != 0) return -1;
-    if (region_w > inv->render_w) return fail(std::string(who) + ": the region is wider than the render width");
-    const int grid = grid_x * grid_y;
-    const ClipSampledPlan plan = clip_sampled_plan(num_rows, inv->render_w, samples, grid, num_frames);
-    const size_t bps = plan.bytes_per_sample;
-    if (bps > ((size_t)1 << 32)) return fail(std::string(who) + ": a sub-sample map of more than 4 GiB; render the frame in row bands");
-    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
-    // the shutter's temporary: [frame][time step][grid point] maps, the carry map behind them
-    const size_t slots = (size_t)plan.per_batch * plan.steps_per_pass * grid;
-    if (inv->clip_shutter.grow((slots + plan.carry) * bps, hipDeviceSynchronize) != hipSuccess)
-        return fail("out of device memory for the sub-samples of a grid-supersampled clip; lower MMHIP_CLIP_SHUTTER_BYTES");
-    unsigned char *subs = inv->clip_shutter.get<unsigned char>(), *carry = plan.carry ? subs + slots * bps : nullptr;
-    const float inv_k = mm_shutter_inv_k(samples * grid);
-    SamplingOffsetGuard offsets(inv);
-    std::vector<int> sub_frames;
-    std::vector<float> sub_ts;
-    for (int b0 = 0; b0 < num_frames; b0 += plan.per_batch) {
-        const int n = std::min(plan.per_batch, num_frames - b0);
-        for (int j0 = 0; j0 < samples; j0 += plan.steps_per_pass) {
-            const int count = std::min(plan.steps_per_pass, samples - j0);
-            sub_frames.resize((size_t)n * count);
-            sub_ts.resize((size_t)n * count);
-            for (int i = 0; i < n; ++i)
-                for (int j = 0; j < count; ++j) {
-                    sub_frames[(size_t)i * count + j] = frames[b0 + i];
-                    sub_ts[(size_t)i * count + j] = mm_shutter_sample_t(ts[b0 + i], span, j0 + j, samples);
-                }
-            // grid point g = b * grid_x + a of entry e = i * count + j lands at (e * G + g) * bps: the layout [i][j][g]
-            for (int b = 0; b < grid_y; ++b)
-                for (int a = 0; a < grid_x; ++a) {
-                    offsets.set(mm_sample_grid_offset(a, grid_x), mm_sample_grid_offset(b, grid_y));
-                    if (mmhip_render_clip(inv, n * count, sub_frames.data(), sub_ts.data(), region_x, region_y, region_w, region_h, first_arg,
-                                          last_arg, subs + (size_t)(b * grid_x + a) * bps, row_stride, (int64_t)grid * (int64_t)bps, bpp, 1, s) != 0)
-                        return -1;
-                }
-            const bool last = j0 + count >= samples;
-            std::string err;
-            if (launch_shutter_combine_clip(subs, (int64_t)bps, (int64_t)count * grid * (int64_t)bps, count * grid, j0 > 0 ? carry : nullptr,
-                                            last ? nullptr : carry, (char *)out_device + (int64_t)b0 * frame_stride, region_w, num_rows,
-                                            inv->render_w, row_stride, frame_stride, bpp, floatmap, inv_k, n, inv->ws, s, &err) != 0)
-                return fail(err);
-        }
-        ++inv->clip_sampled_batches;
-    }
-    return 0;
-}
-
-// ---- grid-supersampled clips, fused ----
-// mm_sampled of the sampled variant's kernels (hipgen.cpp sampled_prelude)
-struct HSampled { const float *offs; float *xtabs; float *ytabs; int samples, gx, gy, total; float inv_k; int pad; };
-static_assert(sizeof(HSampled) == 48, "mm_sampled layout");
-
 // How mmhip_render_clip_sampled_fused cuts a clip into batches: the fused shutter's plan with K * G sub-samples per pixel
 // and K slots per frame.  fused false: the call is mmhip_render_clip_sampled.
 static ClipShutterFusedPlan clip_sampled_fused_plan(const mmhip_filter *f, int region_w, int num_rows, int samples, int grid_x, int grid_y, int frames) {
@@ -828,19 +786,93 @@ static ClipShutterFusedPlan clip_sampled_fused_plan(const mmhip_filter *f, int r
     return p;
 }
 
+// The fields both fused plans report (MMHIP_CLIP_SHUTTER_FUSED_PLAN_FIELDS, MMHIP_CLIP_SAMPLED_FUSED_PLAN_FIELDS: the same five).
+static int put_fused_plan(const ClipShutterFusedPlan &p, int64_t *out) {
+    static_assert(MMHIP_CLIP_SHUTTER_FUSED_PLAN_FIELDS == 5 && MMHIP_CLIP_SAMPLED_FUSED_PLAN_FIELDS == 5, "the fused plans' fields");
+    const int64_t v[5] = {p.fused, p.per_batch, p.batches, p.fused ? p.slots_per_batch : 0, p.grid_x};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+int mmhip_filter_clip_shutter_fused_plan(const mmhip_filter *f, int region_w, int num_rows, int samples, int frames, int64_t *out) {
+    if (frames < 1) return fail("clip shutter fused plan: num_frames must be at least 1");
+    if (clip_shutter_check_samples("clip shutter fused plan", samples) != 0) return -1;
+    if (region_w < 1 || num_rows < 1) return fail("clip shutter fused plan: empty region");
+    return put_fused_plan(clip_shutter_fused_plan(f, region_w, num_rows, samples, frames), out);
+}
+
 int mmhip_filter_clip_sampled_fused_plan(const mmhip_filter *f, int region_w, int num_rows, int samples, int grid_x, int grid_y, int frames,
                                          int64_t *out) {
     if (frames < 1) return fail("clip sampled fused plan: num_frames must be at least 1");
     if (clip_sampled_check("clip sampled fused plan", samples, grid_x, grid_y) != 0) return -1;
     if (region_w < 1 || num_rows < 1) return fail("clip sampled fused plan: empty region");
-    const ClipShutterFusedPlan p = grid_x * grid_y == 1 ? clip_shutter_fused_plan(f, region_w, num_rows, samples, frames)
-                                                        : clip_sampled_fused_plan(f, region_w, num_rows, samples, grid_x, grid_y, frames);
-    const int64_t v[MMHIP_CLIP_SAMPLED_FUSED_PLAN_FIELDS] = {p.fused, p.per_batch, p.batches, p.fused ? p.slots_per_batch : 0, p.grid_x};
-    memcpy(out, v, sizeof v);
+    return put_fused_plan(grid_x * grid_y == 1 ? clip_shutter_fused_plan(f, region_w, num_rows, samples, frames)
+                                               : clip_sampled_fused_plan(f, region_w, num_rows, samples, grid_x, grid_y, frames), out);
+}
+
+long mmhip_clip_shutter_fused_batches(mmhip_invocation *inv) { return inv->clip_shutter_fused_batches; }
+long mmhip_clip_sampled_fused_batches(mmhip_invocation *inv) { return inv->clip_sampled_fused_batches; }
+
+// A fused call of the variant `which`, as its plan has it (grid_x: of the pixel launch).
+static ClipCall fused_clip_call(mmhip_invocation *inv, mmhip_filter *f, int which, const ClipShutterFusedPlan &plan, long grid_x,
+                                const ClipTarget &tg, const int *frames, const float *ts) {
+    return ClipCall{inv, f, &f->variants[which], tg.s, plan.geo, grid_x, plan.per_frame, plan.xy_stride, plan.rowtab_stride, frames, ts};
+}
+
+// The sample grid of a call of the sampled or the refine variant: room for the per-offset x and y tables (the prologue
+// fills them), and behind the `slots` {t, frame} entries of the call's table, in the same upload, the grid's offsets --
+// those along x from float 0, those along y from float MM_SAMPLE_GRID_MAX.  Between clip_call_begin, which has made room
+// for GRID_OFFSET_ENTRIES more entries, and send_clip_table.
+static const size_t GRID_OFFSET_ENTRIES = 2 * MM_SAMPLE_GRID_MAX * sizeof(float) / sizeof(HClipFrame);
+static int clip_sample_grid(ClipCall &cc, const ClipTarget &tg, size_t slots, int samples, int grid_x, int grid_y, HSampled *sm) {
+    mmhip_invocation *inv = cc.inv;
+    hipStream_t s = cc.s;
+    const size_t xtab_floats = (size_t)grid_x * tg.region_w, ytab_floats = (size_t)grid_y * tg.num_rows;
+    HIP_TRY(inv->clip_sampled.grow((xtab_floats + ytab_floats) * sizeof(float), [s] { return hipStreamSynchronize(s); }));
+    float *offs = (float *)((HClipFrame *)cc.tab->host.p + slots);
+    for (int k = 0; k < MM_SAMPLE_GRID_MAX; ++k) {
+        offs[k] = k < grid_x ? mm_sample_grid_offset(k, grid_x) : 0.0f;
+        offs[MM_SAMPLE_GRID_MAX + k] = k < grid_y ? mm_sample_grid_offset(k, grid_y) : 0.0f;
+    }
+    *sm = HSampled{};
+    sm->offs = (const float *)(cc.tab->dev.get<HClipFrame>() + slots);
+    sm->xtabs = inv->clip_sampled.get<float>();
+    sm->ytabs = sm->xtabs + xtab_floats;
+    sm->samples = samples;
+    sm->gx = grid_x;
+    sm->gy = grid_y;
+    sm->total = samples * grid_x * grid_y;
+    sm->inv_k = mm_shutter_inv_k(sm->total);
     return 0;
 }
 
-long mmhip_clip_sampled_fused_batches(mmhip_invocation *inv) { return inv->clip_sampled_fused_batches; }
+int mmhip_render_clip_shutter_fused(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
+                                    int region_x, int region_y, int region_w, int region_h, int first_row, int last_row,
+                                    void *out_device, int row_stride, int64_t frame_stride, int bpp, int floatmap, void *stream) {
+    const char *who = "render_clip_shutter_fused";
+    if (clip_shutter_check_samples(who, samples) != 0) return -1;
+    if (samples == 1)       // one instant per frame: the plain clip itself
+        return mmhip_render_clip(inv, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
+                                 row_stride, frame_stride, bpp, floatmap, stream);
+    ClipTarget tg;
+    const int go = clip_target(who, inv, span, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
+                               row_stride, frame_stride, bpp, floatmap, stream, true, &tg);
+    if (go != 1) return go;
+    mmhip_filter *f = active_filter(inv, frames[0], ts[0]);
+    const ClipShutterFusedPlan plan = clip_shutter_fused_plan(f, tg.region_w, tg.num_rows, samples, num_frames);
+    if (!plan.fused)        // native calls, closure images, a frame too large for one launch: the sub-sample maps
+        return render_clip_maps(inv, tg, num_frames, frames, ts, samples, span, 1, 1);
+    if (mmhip_filter_jit_shutter(f, 1) < 0) return -1;
+    ClipCall cc = fused_clip_call(inv, f, VARIANT_SHUTTER, plan, plan.grid_x, tg, frames, ts);
+    // the {t, frame} table of every sub-sample of the call: slot i * samples + j is sub-sample j of output frame i
+    const size_t slots = (size_t)num_frames * samples;
+    if (clip_call_begin(cc, tg, cc.v->ks, frames[0], ts[0], (size_t)plan.slots_per_batch, slots) != 0) return -1;
+    fill_clip_table((HClipFrame *)cc.tab->host.p, num_frames, frames, ts, samples, span);
+    if (send_clip_table(*cc.tab, slots, tg.s) != 0) return -1;
+    HShutter sh{samples, mm_shutter_inv_k(samples)};
+    void *params[] = {&cc.a, &cc.xy, &cc.c, &sh};      // (the prologue and the per-row slice take the first three)
+    return clip_call_run(cc, num_frames, plan.per_batch, samples, params, &inv->clip_shutter_fused_batches);
+}
 
 int mmhip_render_clip_sampled_fused(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
                                     int grid_x, int grid_y, int region_x, int region_y, int region_w, int region_h, int first_row,
@@ -851,77 +883,26 @@ int mmhip_render_clip_sampled_fused(mmhip_invocation *inv, int num_frames, const
         return mmhip_render_clip_shutter_fused(inv, num_frames, frames, ts, samples, span, region_x, region_y, region_w, region_h, first_row,
                                                last_row, out_device, row_stride, frame_stride, bpp, floatmap, stream);
     if (clip_sampled_check(who, samples, grid_x, grid_y) != 0) return -1;
-    if (!std::isfinite(span)) return fail(std::string(who) + ": span must be finite");
-    if (check_clip_args(who, num_frames, frames, ts, bpp, region_w, region_h) != 0) return -1;
-    const int first_arg = first_row, last_arg = last_row;
-    if (!clamp_rows(region_y, region_h, &first_row, &last_row)) return 0;
-    const int num_rows = last_row - first_row;
-    if (check_frame_stride(who, inv, frame_stride, num_rows, region_w, row_stride, bpp, floatmap) != 0) return -1;
-    if (region_w > inv->render_w) return fail(std::string(who) + ": the region is wider than the render width");
+    ClipTarget tg;
+    const int go = clip_target(who, inv, span, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
+                               row_stride, frame_stride, bpp, floatmap, stream, true, &tg);
+    if (go != 1) return go;
     mmhip_filter *f = active_filter(inv, frames[0], ts[0]);
-    const ClipShutterFusedPlan plan = clip_sampled_fused_plan(f, region_w, num_rows, samples, grid_x, grid_y, num_frames);
+    const ClipShutterFusedPlan plan = clip_sampled_fused_plan(f, tg.region_w, tg.num_rows, samples, grid_x, grid_y, num_frames);
     if (!plan.fused)        // native calls, closure images, a per-row slice, a frame too large for one launch: the sub-sample maps
-        return mmhip_render_clip_sampled(inv, num_frames, frames, ts, samples, span, grid_x, grid_y, region_x, region_y, region_w, region_h,
-                                         first_arg, last_arg, out_device, row_stride, frame_stride, bpp, floatmap, stream);
+        return render_clip_maps(inv, tg, num_frames, frames, ts, samples, span, grid_x, grid_y);
     if (mmhip_filter_jit_sampled(f, 1) < 0) return -1;
-    const KernelSource &ks = f->sampled_ks;
-    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
-    if (upload_tables(inv, s) != 0) return -1;
-
-    HArgs a = render_args(inv, frames[0], ts[0], region_x, region_y, region_w, region_h, first_row, last_row, out_device, row_stride, bpp, floatmap);
-    // the coordinate tables are the single-frame path's, rewritten here: its prologue must run again
-    if (grow_launch_buffers(inv->launch, ks, region_w, num_rows, false, s) != 0) return -1;
-    inv->pro_filter = nullptr;
-    auto wait = [s] { return hipStreamSynchronize(s); };
-    HIP_TRY(inv->clip.xy.grow(plan.xy_stride * plan.slots_per_batch, wait, true));
-    const size_t xtab_floats = (size_t)grid_x * region_w, ytab_floats = (size_t)grid_y * num_rows;
-    HIP_TRY(inv->clip_sampled.grow((xtab_floats + ytab_floats) * sizeof(float), wait));
-    // the {t, frame} table of every time step of the call -- slot i * samples + j is step j of output frame i -- and behind
-    // it, in the same upload, the grid's offsets: those along x from float 0, those along y from float MM_SAMPLE_GRID_MAX
-    const size_t slots = (size_t)num_frames * samples, offs_entries = 2 * MM_SAMPLE_GRID_MAX * sizeof(float) / sizeof(HClipFrame);
-    ClipBuffers::Table *tab = nullptr;
-    if (next_clip_table(inv, slots + offs_entries, s, &tab) != 0) return -1;
-    HClipFrame *hf = (HClipFrame *)tab->host.p;
-    for (int i = 0; i < num_frames; ++i)
-        for (int j = 0; j < samples; ++j) hf[(size_t)i * samples + j] = HClipFrame{mm_shutter_sample_t(ts[i], span, j, samples), frames[i]};
-    float *offs = (float *)(hf + slots);
-    for (int k = 0; k < MM_SAMPLE_GRID_MAX; ++k) {
-        offs[k] = k < grid_x ? mm_sample_grid_offset(k, grid_x) : 0.0f;
-        offs[MM_SAMPLE_GRID_MAX + k] = k < grid_y ? mm_sample_grid_offset(k, grid_y) : 0.0f;
-    }
-    if (send_clip_table(*tab, slots + offs_entries, s) != 0) return -1;
-
-    a.xtab = inv->launch.xtab.get<float>();
-    a.ytab = inv->launch.ytab.get<float>();
-    a.ppt = plan.geo.ppt;
-    a.tiles_magic = plan.geo.tiles_magic;
-    char *xy = inv->clip.xy.get<char>();
-    HClip c{};
-    c.frame_stride = frame_stride;
-    c.xy_stride = plan.per_frame ? (int)plan.xy_stride : 0;
-    c.nwg = (int)plan.geo.nwg;
-    HSampled sm{};
-    sm.offs = (const float *)(tab->dev.get<HClipFrame>() + slots);
-    sm.xtabs = inv->clip_sampled.get<float>();
-    sm.ytabs = sm.xtabs + xtab_floats;
-    sm.samples = samples;
-    sm.gx = grid_x;
-    sm.gy = grid_y;
-    sm.total = samples * grid_x * grid_y;
-    sm.inv_k = mm_shutter_inv_k(sm.total);
-    void *params[] = {&a, &xy, &c, &sm};
-    for (int b0 = 0; b0 < num_frames; b0 += plan.per_batch) {
-        const int n = std::min(plan.per_batch, num_frames - b0);
-        a.out = (char *)out_device + (int64_t)b0 * frame_stride;
-        c.frames = tab->dev.get<HClipFrame>() + (size_t)b0 * samples;
-        // (the coordinate tables are written by the first batch's prologue and stay: they depend on the geometry alone)
-        const int pro_slots = launch_clip_prologue(f->f_pro_sampled, nullptr, a, plan.per_frame, b0, n * samples, params, s);
-        if (pro_slots < 0) return -1;
-        inv->clip_prologue_frames += pro_slots;
-        if (timed_pixel_launch(inv, f->f_pix_sampled, (unsigned)plan.grid_x, (unsigned)n, params, s) != 0) return -1;
-        ++inv->clip_sampled_fused_batches;
-    }
-    return 0;
+    ClipCall cc = fused_clip_call(inv, f, VARIANT_SAMPLED, plan, plan.grid_x, tg, frames, ts);
+    // the {t, frame} table of every time step of the call -- slot i * samples + j is step j of output frame i -- and the grid
+    const size_t slots = (size_t)num_frames * samples;
+    if (clip_call_begin(cc, tg, cc.v->ks, frames[0], ts[0], (size_t)plan.slots_per_batch, slots + GRID_OFFSET_ENTRIES) != 0) return -1;
+    fill_clip_table((HClipFrame *)cc.tab->host.p, num_frames, frames, ts, samples, span);
+    HSampled sm;
+    if (clip_sample_grid(cc, tg, slots, samples, grid_x, grid_y, &sm) != 0) return -1;
+    if (send_clip_table(*cc.tab, slots + GRID_OFFSET_ENTRIES, tg.s) != 0) return -1;
+    // (the coordinate tables are written by the first batch's prologue and stay: they depend on the geometry alone)
+    void *params[] = {&cc.a, &cc.xy, &cc.c, &sm};
+    return clip_call_run(cc, num_frames, plan.per_batch, samples, params, &inv->clip_sampled_fused_batches);
 }
 
 // ---- adaptively anti-aliased clips ----
@@ -987,60 +968,24 @@ int mmhip_clip_adaptive_refined(mmhip_invocation *inv, int64_t *counts, int n) {
     return inv->clip_adaptive_frames;
 }
 
-// The refined pixels of frames [b0, b0 + n) from their lists: the refine variant's prologue over the batch's slots -- every
-// batch's, since the nested render of the base maps has rewritten the frame constants and the coordinate tables -- and
-// mm_pixels_refine over a grid that covers the whole rectangle (the counts stay on the device).
-static int clip_adaptive_refine_batch(mmhip_invocation *inv, mmhip_filter *f, const ClipAdaptivePlan &plan, const int *frames, const float *ts, int b0,
-                                      int n, int grid_x, int grid_y, int region_x, int region_y, int region_w, int region_h, int first_row,
-                                      int last_row, void *out, int row_stride, int64_t frame_stride, int bpp, int floatmap, const unsigned *lists,
-                                      const unsigned *counts, hipStream_t s) {
-    const KernelSource &ks = f->refine_ks;
-    const int num_rows = last_row - first_row;
-    if (upload_tables(inv, s) != 0) return -1;
-    HArgs a = render_args(inv, frames[b0], ts[b0], region_x, region_y, region_w, region_h, first_row, last_row, out, row_stride, bpp, floatmap);
-    if (grow_launch_buffers(inv->launch, ks, region_w, num_rows, false, s) != 0) return -1;
-    inv->pro_filter = nullptr;
-    auto wait = [s] { return hipStreamSynchronize(s); };
-    const bool per_frame = plan.fused.per_frame;
-    HIP_TRY(inv->clip.xy.grow(plan.fused.xy_stride * (per_frame ? plan.per_batch : 1), wait, true));
-    const size_t xtab_floats = (size_t)grid_x * region_w, ytab_floats = (size_t)grid_y * num_rows;
-    HIP_TRY(inv->clip_sampled.grow((xtab_floats + ytab_floats) * sizeof(float), wait));
+// The refined pixels of the `n` frames of a batch, which `tg` begins at, from their lists: the whole set-up, table and
+// prologue over the batch's slots -- every batch's, since the nested render of the base maps has rewritten the frame
+// constants and the coordinate tables -- and mm_pixels_refine over a grid that covers the whole rectangle (the counts
+// stay on the device).  The batch is counted by the caller, its prologue slots are not.
+static int clip_adaptive_refine_batch(mmhip_invocation *inv, mmhip_filter *f, const ClipAdaptivePlan &plan, const ClipTarget &tg, int n,
+                                      const int *frames, const float *ts, int grid_x, int grid_y, const unsigned *lists,
+                                      const unsigned *counts) {
+    ClipCall cc = fused_clip_call(inv, f, VARIANT_REFINE, plan.fused, plan.refine_grid_x, tg, frames, ts);
     // the batch's {t, frame} table and behind it the grid's offsets, as mmhip_render_clip_sampled_fused lays them out
-    const size_t slots = (size_t)n, offs_entries = 2 * MM_SAMPLE_GRID_MAX * sizeof(float) / sizeof(HClipFrame);
-    ClipBuffers::Table *tab = nullptr;
-    if (next_clip_table(inv, slots + offs_entries, s, &tab) != 0) return -1;
-    HClipFrame *hf = (HClipFrame *)tab->host.p;
-    for (int i = 0; i < n; ++i) hf[i] = HClipFrame{ts[b0 + i], frames[b0 + i]};
-    float *offs = (float *)(hf + slots);
-    for (int k = 0; k < MM_SAMPLE_GRID_MAX; ++k) {
-        offs[k] = k < grid_x ? mm_sample_grid_offset(k, grid_x) : 0.0f;
-        offs[MM_SAMPLE_GRID_MAX + k] = k < grid_y ? mm_sample_grid_offset(k, grid_y) : 0.0f;
-    }
-    if (send_clip_table(*tab, slots + offs_entries, s) != 0) return -1;
-
-    a.xtab = inv->launch.xtab.get<float>();
-    a.ytab = inv->launch.ytab.get<float>();
-    a.ppt = plan.fused.geo.ppt;
-    a.tiles_magic = plan.fused.geo.tiles_magic;
-    char *xy = inv->clip.xy.get<char>();
-    HClip c{};
-    c.frames = tab->dev.get<HClipFrame>();
-    c.frame_stride = frame_stride;
-    c.xy_stride = per_frame ? (int)plan.fused.xy_stride : 0;
-    c.nwg = (int)plan.fused.geo.nwg;
-    HSampled sm{};
-    sm.offs = (const float *)(tab->dev.get<HClipFrame>() + slots);
-    sm.xtabs = inv->clip_sampled.get<float>();
-    sm.ytabs = sm.xtabs + xtab_floats;
-    sm.samples = 1;
-    sm.gx = grid_x;
-    sm.gy = grid_y;
-    sm.total = grid_x * grid_y;
-    sm.inv_k = mm_shutter_inv_k(sm.total);
+    if (clip_call_begin(cc, tg, cc.v->ks, frames[0], ts[0], (size_t)(cc.per_frame ? plan.per_batch : 1), (size_t)n + GRID_OFFSET_ENTRIES) != 0)
+        return -1;
+    fill_clip_table((HClipFrame *)cc.tab->host.p, n, frames, ts, 1, 0.0f);
+    HSampled sm;
+    if (clip_sample_grid(cc, tg, (size_t)n, 1, grid_x, grid_y, &sm) != 0) return -1;
+    if (send_clip_table(*cc.tab, (size_t)n + GRID_OFFSET_ENTRIES, tg.s) != 0) return -1;
     HRefine r{lists, counts, (long long)plan.list_entries};
-    void *params[] = {&a, &xy, &c, &sm, &r};      // (the prologue takes the first four)
-    if (launch_clip_prologue(f->f_pro_refine, nullptr, a, per_frame, 0, n, params, s) < 0) return -1;
-    return timed_pixel_launch(inv, f->f_pix_refine, (unsigned)plan.refine_grid_x, (unsigned)n, params, s);
+    void *params[] = {&cc.a, &cc.xy, &cc.c, &sm, &r};      // (the prologue takes the first four)
+    return clip_call_run(cc, n, n, 1, params, nullptr);
 }
 
 int mmhip_render_clip_adaptive(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int grid_x, int grid_y, float threshold,
@@ -1057,18 +1002,16 @@ int mmhip_render_clip_adaptive(mmhip_invocation *inv, int num_frames, const int 
     if (clip_sampled_check(who, 1, grid_x, grid_y) != 0) return -1;
     if (mode != MMHIP_AA_REFINE_AUTO && mode != MMHIP_AA_REFINE_SELECT)
         return fail(std::string(who) + ": mode must be 0 (auto) or 1 (select), not " + std::to_string(mode));
-    if (check_clip_args(who, num_frames, frames, ts, bpp, region_w, region_h) != 0) return -1;
-    const int first_arg = first_row, last_arg = last_row;
-    if (!clamp_rows(region_y, region_h, &first_row, &last_row)) return 0;
-    const int num_rows = last_row - first_row;
-    if (check_frame_stride(who, inv, frame_stride, num_rows, region_w, row_stride, bpp, floatmap) != 0) return -1;
-    if (region_w > inv->render_w) return fail(std::string(who) + ": the region is wider than the render width");
+    ClipTarget tg;
+    const int go = clip_target(who, inv, 0.0f, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
+                               row_stride, frame_stride, bpp, floatmap, stream, true, &tg);
+    if (go != 1) return go;
     mmhip_filter *f = active_filter(inv, frames[0], ts[0]);
-    const ClipAdaptivePlan plan = clip_adaptive_plan(f, region_w, num_rows, inv->render_w, grid_x, grid_y, num_frames, mode);
+    const ClipAdaptivePlan plan = clip_adaptive_plan(f, tg.region_w, tg.num_rows, inv->render_w, grid_x, grid_y, num_frames, mode);
     const size_t bps = plan.bytes_per_map;
     if (bps > ((size_t)1 << 32)) return fail(std::string(who) + ": a base map of more than 4 GiB; render the frame in row bands");
     if (plan.list_path && mmhip_filter_jit_refine(f, 1) < 0) return -1;
-    hipStream_t s = stream ? (hipStream_t)stream : inv->stream;
+    hipStream_t s = tg.s;
     // own allocations (the nested grid-supersampled clip of the select path fills the shutter's temporary); whatever still
     // reads a smaller one has finished before it is freed
     if (inv->clip_adaptive.grow((size_t)plan.per_batch * plan.bytes_per_frame, hipDeviceSynchronize) != hipSuccess ||
@@ -1083,21 +1026,16 @@ int mmhip_render_clip_adaptive(mmhip_invocation *inv, int num_frames, const int 
     offsets.set(0.f);      // the base maps are rendered at offset 0, whatever the caller's
     for (int b0 = 0; b0 < num_frames; b0 += plan.per_batch) {
         const int n = std::min(plan.per_batch, num_frames - b0);
-        char *out = (char *)out_device + (int64_t)b0 * frame_stride;
-        if (mmhip_render_clip(inv, n, frames + b0, ts + b0, region_x, region_y, region_w, region_h, first_arg, last_arg, base, row_stride,
-                              (int64_t)bps, bpp, 1, s) != 0)
-            return -1;
+        const ClipTarget batch = tg.from_frame(b0);
+        if (render_clip_to(inv, tg.as_floatmaps(base, (int64_t)bps), n, frames + b0, ts + b0) != 0) return -1;
         // select path: every pixel refined, then the mask kernel puts back those that are not
-        if (!plan.list_path && mmhip_render_clip_sampled(inv, n, frames + b0, ts + b0, 1, 0.0f, grid_x, grid_y, region_x, region_y, region_w,
-                                                         region_h, first_arg, last_arg, out, row_stride, frame_stride, bpp, floatmap, s) != 0)
-            return -1;
+        if (!plan.list_path && render_clip_maps(inv, batch, n, frames + b0, ts + b0, 1, 0.0f, grid_x, grid_y) != 0) return -1;
         HIP_TRY(hipMemsetAsync(counts + b0, 0, (size_t)n * sizeof(unsigned), s));
         std::string err;
-        if (launch_aa_contrast_clip(base, (int64_t)bps, out, counts + b0, lists, (int64_t)plan.list_entries, region_w, num_rows, inv->render_w,
-                                    row_stride, frame_stride, bpp, floatmap, threshold, n, inv->ws, s, &err) != 0)
+        if (launch_aa_contrast_clip(base, (int64_t)bps, batch.out, counts + b0, lists, (int64_t)plan.list_entries, tg.region_w, tg.num_rows,
+                                    inv->render_w, tg.row_stride, tg.frame_stride, tg.bpp, tg.floatmap, threshold, n, inv->ws, s, &err) != 0)
             return fail(err);
-        if (plan.list_path && clip_adaptive_refine_batch(inv, f, plan, frames, ts, b0, n, grid_x, grid_y, region_x, region_y, region_w, region_h,
-                                                         first_row, last_row, out, row_stride, frame_stride, bpp, floatmap, lists, counts + b0, s) != 0)
+        if (plan.list_path && clip_adaptive_refine_batch(inv, f, plan, batch, n, frames + b0, ts + b0, grid_x, grid_y, lists, counts + b0) != 0)
             return -1;
         ++inv->clip_adaptive_batches;
     }

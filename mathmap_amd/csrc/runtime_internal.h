@@ -16,15 +16,20 @@
 
 namespace mm { void load_ir_json(Module &mod, FilterCode &code, const char *json); }   // ir_json.cpp
 
-// The kernels that render closure image #k of a filter into a float map (FilterCode::closure_renders[k]):
-// same user values and images as the owning filter, own code object.
-struct mmhip_closure_kernel {
+// One module of a filter: its text (with key and kernel names), its code object, and the loaded module with its kernels
+// (f_rows: where the text has a per-row slice, ks.row_values > 0, and the owner launches it).
+struct ModuleVariant {
     mm::KernelSource ks;
     std::vector<char> code_object;
     hipModule_t mod = nullptr;
-    hipFunction_t f_pro = nullptr, f_pix = nullptr;
+    hipFunction_t f_pro = nullptr, f_rows = nullptr, f_pix = nullptr;
     bool loaded = false;
 };
+enum { VARIANT_CLIP, VARIANT_SHUTTER, VARIANT_SAMPLED, VARIANT_REFINE, VARIANT_COUNT };
+
+// The kernels that render closure image #k of a filter into a float map (FilterCode::closure_renders[k]):
+// same user values and images as the owning filter, own code object.
+using mmhip_closure_kernel = ModuleVariant;
 
 struct mmhip_filter {
     std::vector<mmhip_closure_kernel> closures;
@@ -41,33 +46,13 @@ struct mmhip_filter {
     hipFunction_t f_rows = nullptr;           // the per-row slice's kernel (KernelSource::row_values > 0)
     bool loaded = false;
     double jit_seconds = 0;
-    // the clip variant of the module (mmhip_render_clip): text, code object and kernels, built on the first clip render
-    mm::KernelSource clip_ks;                 // source, key and kernel names only
-    std::vector<char> clip_code_object;
-    hipModule_t clip_mod = nullptr;
-    hipFunction_t f_pro_clip = nullptr, f_rows_clip = nullptr, f_pix_clip = nullptr;
-    bool clip_loaded = false;
-    // the shutter variant of the module (mmhip_render_clip_shutter_fused): generated from `code` when it is first asked
-    // for (KernelOptions::shutter), built and cached like the clip variant; filters without native calls or closure images
-    mm::KernelSource shutter_ks;
-    std::vector<char> shutter_code_object;
-    hipModule_t shutter_mod = nullptr;
-    hipFunction_t f_pro_shutter = nullptr, f_rows_shutter = nullptr, f_pix_shutter = nullptr;
-    bool shutter_loaded = false;
-    // the sampled variant (mmhip_render_clip_sampled_fused, KernelOptions::sampled): the same again, under its own key;
-    // filters without native calls, closure images or a per-row slice
-    mm::KernelSource sampled_ks;
-    std::vector<char> sampled_code_object;
-    hipModule_t sampled_mod = nullptr;
-    hipFunction_t f_pro_sampled = nullptr, f_pix_sampled = nullptr;
-    bool sampled_loaded = false;
-    // the refine variant (mmhip_render_clip_adaptive, KernelOptions::refine): the fifth module, under its own key; the
-    // filters that have a sampled variant
-    mm::KernelSource refine_ks;
-    std::vector<char> refine_code_object;
-    hipModule_t refine_mod = nullptr;
-    hipFunction_t f_pro_refine = nullptr, f_pix_refine = nullptr;
-    bool refine_loaded = false;
+    // the variants of the module that clip rendering launches, each built when it is first asked for (runtime.cpp
+    // variant_source, jit_variant).  clip (mmhip_render_clip): made from the main text, for every filter.  shutter
+    // (mmhip_render_clip_shutter_fused, KernelOptions::shutter): generated from `code`; filters without native calls or
+    // closure images.  sampled (mmhip_render_clip_sampled_fused, KernelOptions::sampled): the same under its own key;
+    // filters that have no per-row slice either.  refine (mmhip_render_clip_adaptive, KernelOptions::refine): the fifth
+    // module, under its own key; the filters that have a sampled variant.
+    ModuleVariant variants[VARIANT_COUNT];
     // user-value specialisation (specialize.cpp): kernels with the scalar user values baked in,
     // keyed by the value bytes; owned by this filter
     std::string source;

@@ -344,6 +344,26 @@ def test_the_callers_sampling_offset_is_put_back(mode):
     assert np.array_equal(inv.render(t=0.3, frame=1), want)
 
 
+@pytest.mark.parametrize("mode", MODES)
+def test_the_grid_replaces_the_callers_sampling_offset(mode):
+    """On an invocation with a sampling offset a motion-blurred clip renders at that offset (its bytes:
+    tests/test_gpu_clip_shutter.py), the grid clip behind it at the grid's own offsets -- the restatement's, which knows
+    nothing of the caller's -- and a single render after both at the caller's offset again."""
+    w = h = 17
+    frames, ts, offset = [2, 0], [0.9, 0.1], (-0.5, 0.25)
+    flt, image = compiled("rotate")
+    inv, other, fresh = (invoke(flt, image, w, h) for _ in range(3))
+    inv.set_sampling_offset(*offset)
+    fresh.set_sampling_offset(*offset)
+    inv.render_clip(frames=frames, ts=ts, shutter_samples=3, shutter_span=SPAN, shutter_mode=mode)
+    got = inv.render_clip(frames=frames, ts=ts, aa=2, shutter_mode=mode)
+    subs = sub_sample_maps(other, frames, ts, 1, 0.0, 2)
+    for i in range(len(frames)):
+        assert np.array_equal(got[i], G.combine(subs[i], bpp=4, floatmap=False)), (mode, i)
+    assert np.array_equal(inv.render(t=0.3, frame=1), fresh.render(t=0.3, frame=1))
+    assert not np.array_equal(inv.render(t=0.3, frame=1), other.render(t=0.3, frame=1))      # (left at offset 0)
+
+
 def test_the_callers_sampling_offset_is_put_back_after_a_failed_call():
     """The nested clip fails behind the first change of the offset: a blur told to read the render's own frame of a
     sequence, at a frame number the sequence does not have."""

@@ -379,6 +379,27 @@ def test_renders_around_a_shutter_clip(name):
     assert np.array_equal(inv.render_clip(frames=FRAMES, ts=TS, shutter_samples=K, shutter_span=SPAN), blurred)
 
 
+@pytest.mark.parametrize("mode", ["maps", "fused"])
+def test_the_shutter_clip_renders_at_the_callers_sampling_offset(mode):
+    """A motion-blurred clip has one sample per pixel and instant: it is taken at the invocation's sampling offset, as
+    every single render is, and the offset is still there afterwards.  (The grid of render_clip(aa=...) replaces it:
+    tests/test_gpu_clip_sampled.py.)"""
+    w = h = 17
+    frames, ts, k, offset = [2, 0], [0.9, 0.1], 3, (-0.5, 0.25)
+    flt, image = compiled("rotate")
+    inv, other, fresh, centred = (invoke(flt, image, w, h) for _ in range(4))
+    for i in (inv, other, fresh):
+        i.set_sampling_offset(*offset)
+    got = inv.render_clip(frames=frames, ts=ts, shutter_samples=k, shutter_span=SPAN, shutter_mode=mode)
+    subs = sub_sample_maps(other, frames, ts, k, SPAN)          # six single renders at the offset
+    for i in range(len(frames)):
+        assert np.array_equal(got[i], R.combine(subs[i], bpp=4)), (mode, i)
+    assert not np.array_equal(got, centred.render_clip(frames=frames, ts=ts, shutter_samples=k, shutter_span=SPAN, shutter_mode=mode))
+    assert (inv.clip_shutter_fused_batches(), inv.clip_shutter_batches()) == ((1, 0) if mode == "fused" else (0, 1))
+    assert np.array_equal(inv.render(t=0.3, frame=1), fresh.render(t=0.3, frame=1))
+    assert not np.array_equal(inv.render(t=0.3, frame=1), centred.render(t=0.3, frame=1))
+
+
 # ---- 6. the command line ----
 
 def read_png(path):
