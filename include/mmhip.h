@@ -510,6 +510,77 @@ int mmhip_filter_clip_adaptive_plan(const mmhip_filter *f, int region_w, int num
    -1, with a message. */
 const char *mmhip_filter_refine_kernel_source(mmhip_filter *f);
 long mmhip_filter_jit_refine(mmhip_filter *f, int load_module);
+/* A grid-supersampled clip under a reconstruction filter wider than a pixel (an extension, opt-in): every output pixel
+   is a weighted sum of the sub-samples of its own grid and of the grids of its neighbour pixels, the weights a separable
+   box, tent, Gaussian or Mitchell-Netravali kernel.  Every parameter except `kernel` and `radius` means what it means
+   for mmhip_render_clip_sampled; asynchronous.  This statement is the specification: tests/clip_filter_reference.py
+   restates it, mathmap_amd/csrc/mm_clip_filter.h holds it.
+     - kernel is MMHIP_AA_BOX, MMHIP_AA_TENT, MMHIP_AA_GAUSSIAN or MMHIP_AA_MITCHELL.  radius is in pixels, finite, and
+       0.5 <= radius <= 4.  The Python and CLI layers use these radii when none is given: box 0.5, tent 1.0, Gaussian 1.5,
+       Mitchell 2.0.  D = (int)ceil(radius - 0.5) is the number of neighbour pixels reached on each side: 0 <= D <= 4.
+     - samples, span, grid_x = sx, grid_y = sy, the offsets ox_a and oy_b, the sub-sample (j, b, a) of a pixel and its time
+       t_ij are mmhip_render_clip_sampled's: sx and sy are 1 to 8, samples * sx * sy is at most 256.  A 1 x 1 grid is allowed:
+       a post-filter of single samples.  Nothing delegates to another entry point.
+     - Sample position: offsets add to the pixel index in both axes, so sub-sample (b, a) of the pixel at column c + dx, row
+       r + dy lies, in double, at d_x = (double)dx + (double)ox_a and d_y = (double)dy + (double)oy_b from the centre of
+       pixel (c, r).
+     - The weight of one axis, k(d), in double, with ad = fabs(d) and R = (double)radius: 0 where ad >= R; else
+         box: 1.0
+         tent: 1.0 - ad / R
+         Gaussian: exp(-2.0 * (d * d)) - exp(-2.0 * (R * R)), exp being the host libm's double function
+         Mitchell (B = C = 1/3), with u = (2.0 * ad) / R:
+           u < 1: (((7.0 * u - 12.0) * u) * u + 16.0 / 3.0) / 6.0
+           else:  ((((-7.0 / 3.0) * u + 12.0) * u - 20.0) * u + 32.0 / 3.0) / 6.0
+       each evaluated in the order written, without fma.
+     - Taps: a tap of the x axis is a pair (dx, a) with dx = -D .. D and a = 0 .. sx - 1, in the order dx ascending, then a
+       ascending.  It exists only where the neighbour pixel lies inside the frame: 0 <= region_x + c + dx < render_width;
+       likewise (dy, b) and rows against render_height.  The frame counts, not the region and not the rows asked for: row
+       bands and sub-regions of a call equal the same pixels of a whole-frame call.
+     - Normalisation is per axis and per column (or row) of the frame: n is the double sum of k over the existing taps in
+       tap order (n = 0.0; n = n + k), and the tap's weight is w = (float)(k / n).  A tap with w == 0 is dropped: it is
+       never read, whatever it holds.  An n that is not a positive finite number refuses the call.  Only the first and last D
+       columns and rows differ from the interior: a pixel with lo = min(D, index) neighbours before it and hi = min(D, size -
+       1 - index) after it has the table of class (lo, hi), at most (D + 1)^2 tables per axis; they are built on the host
+       and uploaded.  mmhip_clip_filter_taps returns one.
+     - Arithmetic, per channel, in f32, round to nearest, no fma, denormals kept.  With f[g] the float map of grid point g
+       = b * sx + a of a time step: h_b(c, r') is the sum over the taps (dx ascending, then a ascending) of wx * f[b * sx +
+       a](c + dx, r') -- each product rounded on its own; the first product starts the sum, every later product is added to
+       it in order.  s_j(c, r) is the same sum over (dy ascending, then b ascending) of wy * h_b(c, r + dy).  Over the K =
+       samples time steps: acc = s_0; acc = acc + s_j for j = 1 .. K - 1; m = acc * (float)(1.0 / (double)K).
+     - m is stored as every clip path stores a pixel: mm_shutter_store_bytes at bpp 1 - 4, or the float map.  Bytes
+       between rows and between frames are not touched.  Box at radius 0.5 is not bit-identical to
+       mmhip_render_clip_sampled in general: the association of the sum differs.
+     - The sub-sample maps hold the haloed rectangle: columns [max(0, region_x - D), min(render_width, region_x + region_w
+       + D)) by rows [max(0, first_row - D), min(render_height, last_row + D)).  Per batch and pass, for every grid point
+       one nested mmhip_render_clip of that rectangle as float maps at the grid point's sampling offset, in the layout
+       [i][j][g] of mmhip_render_clip_sampled, then one launch of the combine (k_filter_combine_clip).  Native filters and
+       closures run as they do there; nothing that mmhip_render_clip accepts is refused.
+     - Batches and passes are mmhip_render_clip_sampled's with the haloed row count in place of the rows:
+       MMHIP_CLIP_SHUTTER_BYTES bounds the temporary, passes are whole time steps, and the carry map holds the running acc of
+       the output rectangle.
+     - The caller's sampling offset is put back on every return, failed calls included.  One upload of the tap tables per
+       call, one combine launch per pass.  mmhip_clip_filtered_batches rises by one per batch; the sampled, shutter and
+       adaptive counters do not move.  The combine is timed as filter_combine_clip.
+   Errors: what mmhip_render_clip_sampled refuses, under the name render_clip_filtered; an unknown kernel; a radius
+   outside the range; a region that does not lie inside the render size (0 <= region_x, region_x + region_w <=
+   render_width, the rows inside [0, render_height) after the usual clamp); a sub-sample map of the haloed rectangle
+   beyond 4 GiB; out of device memory. */
+enum { MMHIP_AA_BOX = 0, MMHIP_AA_TENT = 1, MMHIP_AA_GAUSSIAN = 2, MMHIP_AA_MITCHELL = 3, MMHIP_CLIP_FILTERED_PLAN_FIELDS = 8 };
+int mmhip_render_clip_filtered(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span,
+                               int grid_x, int grid_y, int kernel, float radius, int region_x, int region_y, int region_w,
+                               int region_h, int first_row, int last_row, void *out_device, int row_stride, int64_t frame_stride,
+                               int bpp, int floatmap, void *stream);
+long mmhip_clip_filtered_batches(mmhip_invocation *inv);
+/* How mmhip_render_clip_filtered renders the rows [first_row, last_row) of the columns [region_x, region_x + region_w) of
+   a render_w x render_h frame (needs no GPU; the kernel does not matter, the radius does).  out[] receives
+   MMHIP_CLIP_FILTERED_PLAN_FIELDS values: the six of mmhip_filter_clip_sampled_plan -- bytes_per_sample being a map of the
+   haloed rectangle -- then halo_columns and halo_rows, the rectangle's size. */
+int mmhip_filter_clip_filtered_plan(const mmhip_filter *f, int region_x, int region_w, int first_row, int last_row, int render_w,
+                                    int render_h, int samples, int grid_x, int grid_y, float radius, int frames, int64_t *out);
+/* The normalised float taps of one axis with n grid points, for a pixel with lo neighbours before it and hi after it
+   inside the frame (0 <= lo, hi <= D; needs no GPU): out[(dx + D) * n + a] is the weight of tap (dx, a), 0 for a tap that
+   does not exist.  Returns the number of floats written, (2 D + 1) * n, or -1. */
+int mmhip_clip_filter_taps(int kernel, float radius, int n, int lo, int hi, float *out);
 /* Convenience: whole frame to a host RGBA8 buffer (width*height*4 bytes); synchronous. */
 int mmhip_render_host(mmhip_invocation *inv, int frame, float t, uint8_t *out_rgba);
 int mmhip_sync(mmhip_invocation *inv);

@@ -125,6 +125,13 @@ SYMBOLS = {
     "mmhip_filter_clip_adaptive_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "mmhip_filter_refine_kernel_source": (C.c_char_p, [C.c_void_p]),
     "mmhip_filter_jit_refine": (C.c_long, [C.c_void_p, C.c_int]),
+    "mmhip_render_clip_filtered": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int, C.c_float, C.c_int, C.c_int,
+                                             C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "mmhip_clip_filtered_batches": (C.c_long, [C.c_void_p]),
+    "mmhip_filter_clip_filtered_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.c_float, C.c_int, C.POINTER(C.c_int64)]),
+    "mmhip_clip_filter_taps": (C.c_int, [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "mmhip_render_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "mmhip_sync": (C.c_int, [C.c_void_p]),
     "mmhip_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),
@@ -160,6 +167,9 @@ SELFTEST_SYMBOLS = {
     "mmhip_selftest_combine_ms": (C.c_long, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "mmhip_selftest_shutter_combine": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
                                                  C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "mmhip_selftest_filter_combine": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
+                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double)]),
 }
 SELFTEST_PATH = os.path.join(_HERE, "libmathmap_hip_selftest.so")
 _selftest = None

@@ -39,6 +39,12 @@ AA_REFINE_MODES = ("list", "select")      # mmhip_render_clip_adaptive's mode 0 
 CLIP_ADAPTIVE_PLAN_FIELDS = ("list_path", "frames_per_batch", "batches", "bytes_per_frame", "refine_grid_x")
 CLIP_SAMPLED_PLAN_FIELDS = ("frames_per_batch", "batches", "steps_per_pass", "passes", "bytes_per_sample", "carry")
 SAMPLE_GRID_MAX = 8
+# render_clip's aa_filter: mmhip_render_clip_filtered's kernels, and the radius (pixels) each has when none is given
+AA_FILTERS = {"box": 0, "tent": 1, "gaussian": 2, "mitchell": 3}
+AA_FILTER_RADII = {"box": 0.5, "tent": 1.0, "gaussian": 1.5, "mitchell": 2.0}
+AA_RADIUS_MIN, AA_RADIUS_MAX = 0.5, 4.0
+# mmhip_filter_clip_filtered_plan's out[]
+CLIP_FILTERED_PLAN_FIELDS = CLIP_SAMPLED_PLAN_FIELDS + ("halo_columns", "halo_rows")
 
 
 def sample_grid(aa):
@@ -55,6 +61,33 @@ def sample_grid(aa):
 
 class MathMapError(RuntimeError):
     pass
+
+
+def aa_filter_kernel(aa_filter, aa_radius=None):
+    """render_clip's `aa_filter` and `aa_radius` as mmhip_render_clip_filtered's (kernel, radius): the name's constant and
+    the given radius, or the name's default.  ValueError for an unknown name and a radius outside 0.5 .. 4."""
+    if not isinstance(aa_filter, str) or aa_filter not in AA_FILTERS:
+        raise ValueError("render_clip: aa_filter must be one of %s, not %r" % (", ".join(AA_FILTERS), aa_filter))
+    radius = AA_FILTER_RADII[aa_filter] if aa_radius is None else aa_radius
+    try:
+        radius = float(np.float32(radius))
+    except (TypeError, ValueError):
+        radius = float("nan")
+    if not AA_RADIUS_MIN <= radius <= AA_RADIUS_MAX:
+        raise ValueError("render_clip: aa_radius must be %g to %g pixels, not %r" % (AA_RADIUS_MIN, AA_RADIUS_MAX, aa_radius))
+    return AA_FILTERS[aa_filter], radius
+
+
+def clip_filter_taps(aa_filter, n, lo, hi, aa_radius=None):
+    """The normalised float32 taps of one axis of render_clip(aa_filter=...) with n grid points, for a pixel with `lo`
+    neighbours before it and `hi` after it inside the frame (mmhip_clip_filter_taps): an array [2 D + 1, n], entry [dx + D,
+    a] the weight of tap (dx, a), 0 where the tap does not exist.  Needs no GPU."""
+    kernel, radius = aa_filter_kernel(aa_filter, aa_radius)
+    out = np.zeros(9 * SAMPLE_GRID_MAX, dtype=np.float32)
+    got = lib().mmhip_clip_filter_taps(kernel, radius, int(n), int(lo), int(hi), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if got < 0:
+        raise MathMapError(_err())
+    return out[:got].reshape(-1, int(n)).copy()
 
 
 def _err():
@@ -272,6 +305,16 @@ class Filter:
         (list_path 0: the filter or the region takes the select path)."""
         sx, sy = sample_grid(aa)
         return self._plan("mmhip_filter_clip_adaptive_plan", CLIP_ADAPTIVE_PLAN_FIELDS, region_w, num_rows, render_w, sx, sy, frames)
+
+    def clip_filtered_plan(self, region_w, num_rows, render_w, render_h, samples, aa, aa_filter, frames, aa_radius=None, region_x=0,
+                           first_row=0):
+        """How render_clip(aa=aa, aa_filter=aa_filter, aa_radius=aa_radius, shutter_samples=samples) renders a `frames`-frame
+        clip of num_rows rows from first_row of the region_w columns from region_x of a render_w x render_h frame: a dict of
+        the CLIP_FILTERED_PLAN_FIELDS (the sampled plan's over maps of the haloed rectangle, and that rectangle's size)."""
+        sx, sy = sample_grid(aa)
+        _, radius = aa_filter_kernel(aa_filter, aa_radius)
+        return self._plan("mmhip_filter_clip_filtered_plan", CLIP_FILTERED_PLAN_FIELDS, region_x, region_w, first_row, first_row + num_rows,
+                          render_w, render_h, samples, sx, sy, radius, frames)
 
     @property
     def refine_kernel_source(self):
@@ -501,7 +544,7 @@ class Invocation:
 
     def render_clip(self, num_frames=None, frames=None, ts=None, out_ptr=None, rows=None, region=None, row_stride=None,
                     frame_stride=None, bpp=4, floatmap=False, stream=0, supersample=False, shutter_samples=1, shutter_span=None,
-                    shutter=None, shutter_mode="maps", aa=1, aa_threshold=None, aa_refine="list"):
+                    shutter=None, shutter_mode="maps", aa=1, aa_threshold=None, aa_refine="list", aa_filter=None, aa_radius=None):
         """Renders a clip in batched launches (mmhip_render_clip): frame i at frame number frames[i] and time ts[i].
         `num_frames`=N alone is the CLI's animation: frame = i, t = (float)i / (float)N.  `rows` = (first_row,
         last_row) and `region`, `row_stride`, `bpp`, `floatmap`, `stream` as in render_rows; frame i lands
@@ -528,9 +571,29 @@ class Invocation:
         clamped to 0..1, differs by more than T from one of its 8 neighbours in some channel (T < 0: everywhere), and
         that render's value elsewhere.  `aa_refine`: "list" (default: the refined pixels alone are rendered, where the
         filter allows it) or "select" (the whole grid render, then the choice): the same bytes.  Spatial only:
-        `aa_threshold` with `supersample` or shutter_samples > 1, a NaN, or another `aa_refine` is a ValueError."""
+        `aa_threshold` with `supersample` or shutter_samples > 1, a NaN, or another `aa_refine` is a ValueError.
+        `aa_filter` = "box", "tent", "gaussian" or "mitchell" (default None: every path above exactly as it is) weights the
+        grid's sub-samples with a reconstruction filter of `aa_radius` pixels, 0.5 to 4 (default: AA_FILTER_RADII), which
+        reaches into the neighbour pixels (mmhip_render_clip_filtered); `aa` may be 1, and a shutter goes with it.  An
+        unknown name, a radius out of range, `aa_radius` without `aa_filter`, or `aa_filter` with `aa_threshold`,
+        `supersample` or shutter_mode="fused" is a ValueError."""
         from .striping import animation_frame_t
         grid = sample_grid(aa)
+        filtered = aa_filter is not None
+        if aa_radius is not None and not filtered:
+            raise ValueError("render_clip: aa_radius needs aa_filter")
+        if filtered:
+            kernel, radius = aa_filter_kernel(aa_filter, aa_radius)
+            if aa_threshold is not None:
+                raise ValueError("render_clip: aa_filter is not combined with aa_threshold")
+            if supersample:
+                raise ValueError("render_clip: aa_filter is not combined with supersample=True")
+            if shutter_mode == "fused":
+                raise ValueError("render_clip: aa_filter is not combined with shutter_mode=\"fused\"")
+            if int(shutter_samples) >= 1 and int(shutter_samples) * grid[0] * grid[1] > 256:
+                raise ValueError("render_clip: shutter_samples * sx * sy must be at most 256, not %d" % (int(shutter_samples) * grid[0] * grid[1]))
+            if int(shutter_samples) == 1 and shutter is None and shutter_span is None:
+                shutter_span = 0.0
         adaptive = aa_threshold is not None
         if adaptive:
             if supersample:
@@ -560,6 +623,9 @@ class Invocation:
         if adaptive:
             def render_shutter(h, n, fp, tp, samples, span, *rest):
                 return lib().mmhip_render_clip_adaptive(h, n, fp, tp, grid[0], grid[1], aa_threshold, AA_REFINE_MODES.index(aa_refine), *rest)
+        if filtered:
+            def render_shutter(h, n, fp, tp, samples, span, *rest):
+                return lib().mmhip_render_clip_filtered(h, n, fp, tp, samples, span, grid[0], grid[1], kernel, radius, *rest)
         if supersample and (floatmap or rows is not None):
             raise ValueError("render_clip: supersample=True renders whole regions of bytes: neither floatmap nor rows")
         shutter_samples = int(shutter_samples)
@@ -667,6 +733,10 @@ class Invocation:
     def clip_sampled_fused_batches(self):
         """Batches render_clip(aa != 1, shutter_mode="fused") rendered fused (0 for filters that take the maps path)."""
         return lib().mmhip_clip_sampled_fused_batches(self._h)
+
+    def clip_filtered_batches(self):
+        """Batches render_clip(aa_filter=...) has combined so far."""
+        return lib().mmhip_clip_filtered_batches(self._h)
 
     def clip_adaptive_batches(self):
         """Batches render_clip(aa_threshold=T) has rendered so far, on either path."""

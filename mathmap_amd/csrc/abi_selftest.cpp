@@ -15,6 +15,8 @@
 #include "../../include/mathmap_hip_backend.h"
 #include "../../include/mmhip.h"
 #include "front.h"
+#include "mm_clip_filter.h"
+#include "mm_sample_grid.h"
 #include "runtime_internal.h"
 
 namespace mm { void load_ir_json(Module &mod, FilterCode &code, const char *json); }   // ir_json.cpp
@@ -658,6 +660,91 @@ int mmhip_selftest_shutter_combine(const float *maps, int frames, int samples, i
     };
     do {
         if (!ok(subs.grow(all)) || !ok(dst.grow((size_t)out_bytes)) || (samples_per_pass < samples && !ok(carry.grow(map_bytes * frames)))) break;
+        if (maps ? !ok(hipMemcpy(subs.get(), maps, all, hipMemcpyHostToDevice)) : !ok(hipMemsetD32((hipDeviceptr_t)subs.get(), 0x3e800000, all / 4))) break;
+        if (!ok(hipMemset(dst.get(), sentinel, (size_t)out_bytes))) break;
+        if (!run() || !ok(hipDeviceSynchronize())) break;
+        if (out && !ok(hipMemcpy(out, dst.get(), (size_t)out_bytes, hipMemcpyDeviceToHost))) break;
+        bool timed = true;
+        if (rounds > 0) timed = ok(hipEventCreate(&e0)) && ok(hipEventCreate(&e1));
+        for (int r = 0; r < rounds && timed; ++r) {
+            float t = 0;
+            timed = ok(hipEventRecord(e0, nullptr)) && run() && ok(hipEventRecord(e1, nullptr)) && ok(hipEventSynchronize(e1)) && ok(hipEventElapsedTime(&t, e0, e1));
+            ms[r] = t;
+        }
+        if (timed) result = 0;
+    } while (false);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return result;
+}
+
+// The filter combine alone (tests/test_gpu_clip_filtered.py, tools/clip_filter_cost.py): launch_filter_combine_clip over
+// `frames` frames of `steps` time steps of an sx x sy grid, for the output rectangle of region_w columns from region_x by
+// `rows` rows from first_row of a render_w x render_h frame.  `maps` = float[frames][steps][sy * sx][halo_rows][render_w][4]
+// on the host, the haloed rectangle of mmhip_render_clip_filtered with its columns at the start of each row (null: maps
+// of 0.25, for timing).  The tap blocks are built from mm_clip_filter.h as the runtime builds them.  steps_per_pass,
+// the output buffer, `sentinel`, `rounds` and `ms` are mmhip_selftest_shutter_combine's.  Returns 0, or -1.
+int mmhip_selftest_filter_combine(const float *maps, int frames, int steps, int sx, int sy, int kernel, float radius, int render_w,
+                                  int render_h, int region_x, int first_row, int region_w, int rows, int bpp, int floatmap,
+                                  int row_stride, int64_t frame_stride, int steps_per_pass, int out_offset, unsigned char *out,
+                                  int64_t out_bytes, int sentinel, int rounds, double *ms) {
+    const int64_t band = floatmap ? (int64_t)rows * 16 * render_w : (int64_t)(rows - 1) * row_stride + (int64_t)region_w * bpp;
+    if (frames < 1 || frames > 65535 || steps < 1 || sx < 1 || sx > MM_SAMPLE_GRID_MAX || sy < 1 || sy > MM_SAMPLE_GRID_MAX ||
+        steps * sx * sy > MMHIP_SHUTTER_MAX_SAMPLES || kernel < 0 || kernel >= MM_CLIP_FILTER_KERNELS || !(radius >= 0.5f && radius <= 4.0f) ||
+        render_w < 1 || render_h < 1 || region_x < 0 || first_row < 0 || region_w < 1 || rows < 1 || (int64_t)region_x + region_w > render_w ||
+        (int64_t)first_row + rows > render_h || bpp < 1 || bpp > 4 || out_offset < 0 || row_stride < 0 || frame_stride < band ||
+        out_bytes < out_offset + (int64_t)(frames - 1) * frame_stride + band || (rounds > 0 && !ms)) {
+        g_selftest_err = "filter combine: bad arguments";
+        return -1;
+    }
+    if (steps_per_pass < 1 || steps_per_pass > steps) steps_per_pass = steps;
+    const int reach = mm_clip_filter_reach((double)radius), grid = sx * sy;
+    const int hx0 = std::max(0, region_x - reach), hy0 = std::max(0, first_row - reach);
+    const int hw = std::min(render_w, region_x + region_w + reach) - hx0, hrows = std::min(render_h, first_row + rows + reach) - hy0;
+    const size_t map_bytes = (size_t)hrows * render_w * 16, all = map_bytes * grid * steps * frames;
+    // the blocks of both axes, x first
+    std::vector<unsigned> tables;
+    size_t y_tables = 0;
+    for (int axis = 0; axis < 2; ++axis) {
+        const int n = axis ? sy : sx;
+        float offs[MM_SAMPLE_GRID_MAX];
+        for (int a = 0; a < n; ++a) offs[a] = mm_sample_grid_offset(a, n);
+        if (axis) y_tables = tables.size();
+        const size_t at = tables.size();
+        tables.resize(at + (size_t)(reach + 1) * (reach + 1) * mm_clip_filter_block_words(mm_clip_filter_tap_count(reach, n)));
+        if (mm_clip_filter_axis_blocks(kernel, (double)radius, n, offs, axis ? render_h : render_w, tables.data() + at) != 0) {
+            g_selftest_err = "filter combine: the weights do not sum to a positive finite number";
+            return -1;
+        }
+    }
+    DeviceBuffer subs, carry, dst, taps_dev;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto ok = [](hipError_t e) { if (e != hipSuccess) g_selftest_err = std::string("filter combine: ") + hipGetErrorString(e); return e == hipSuccess; };
+    int result = -1;
+    mm::NativeWorkspace ws;
+    const float inv_k = (float)(1.0 / (double)steps);
+    auto run = [&]() {
+        std::string err;
+        const unsigned *wx = taps_dev.get<unsigned>(), *wy = wx + y_tables;
+        for (int j0 = 0; j0 < steps; j0 += steps_per_pass) {
+            const int count = std::min(steps_per_pass, steps - j0);
+            const bool last = j0 + count >= steps;
+            if (mm::launch_filter_combine_clip(subs.get<unsigned char>() + (size_t)j0 * grid * map_bytes, (int64_t)map_bytes,
+                                               (int64_t)(map_bytes * grid * steps), count, sx, sy, reach, wx, wy, j0 > 0 ? carry.get() : nullptr,
+                                               last ? nullptr : carry.get(), dst.get<unsigned char>() + out_offset, region_x, first_row, region_w,
+                                               rows, hx0, hy0, hw, hrows, render_w, render_h, row_stride, frame_stride, bpp, floatmap, inv_k, frames,
+                                               ws, nullptr, &err) != 0) {
+                g_selftest_err = err;
+                return false;
+            }
+        }
+        return true;
+    };
+    do {
+        if (!ok(subs.grow(all)) || !ok(dst.grow((size_t)out_bytes)) || !ok(taps_dev.grow(tables.size() * sizeof(unsigned))) ||
+            (steps_per_pass < steps && !ok(carry.grow((size_t)rows * region_w * 16 * frames))))
+            break;
+        if (!ok(hipMemcpy(taps_dev.get(), tables.data(), tables.size() * sizeof(unsigned), hipMemcpyHostToDevice))) break;
         if (maps ? !ok(hipMemcpy(subs.get(), maps, all, hipMemcpyHostToDevice)) : !ok(hipMemsetD32((hipDeviceptr_t)subs.get(), 0x3e800000, all / 4))) break;
         if (!ok(hipMemset(dst.get(), sentinel, (size_t)out_bytes))) break;
         if (!run() || !ok(hipDeviceSynchronize())) break;

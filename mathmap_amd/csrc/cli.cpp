@@ -89,6 +89,13 @@ void usage() {
            "                              rendered: list (default: they alone, where the\n"
            "                              filter allows it) or select (the whole grid\n"
            "                              render, then the choice); the files are the same\n"
+           "      --aa-filter=NAME[:RADIUS]\n"
+           "                              with --aa (which may be --aa=1), weight the\n"
+           "                              grid's renders with a reconstruction filter that\n"
+           "                              reaches into the neighbour pixels: box, tent,\n"
+           "                              gaussian or mitchell, RADIUS in pixels from 0.5\n"
+           "                              to 4 (default 0.5, 1, 1.5 and 2); not combined\n"
+           "                              with -o, --aa-threshold or --shutter-mode=fused\n"
            "\n"
            "Report bugs and suggestions to schani@complang.tuwien.ac.at\n",
            cache_size);
@@ -236,7 +243,7 @@ std::string frame_file(const std::string &pattern, int frame) {
 enum {
     OPT_VERSION = 256, OPT_HELP, OPT_HTMLDOC, OPT_BENCH_NO_OUTPUT, OPT_BENCH_ONLY_COMPILE,
     OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE, OPT_INPUT_FRAMES, OPT_BATCH_FRAMES,
-    OPT_NATIVE_INPUT_FRAME, OPT_SHUTTER_SAMPLES, OPT_SHUTTER, OPT_SHUTTER_MODE, OPT_AA, OPT_AA_THRESHOLD, OPT_AA_REFINE
+    OPT_NATIVE_INPUT_FRAME, OPT_SHUTTER_SAMPLES, OPT_SHUTTER, OPT_SHUTTER_MODE, OPT_AA, OPT_AA_THRESHOLD, OPT_AA_REFINE, OPT_AA_FILTER
 };
 
 int main(int argc, char **argv) {
@@ -249,6 +256,9 @@ int main(int argc, char **argv) {
     bool shutter_fused = false, adaptive = false, aa_refine_set = false;
     float aa_threshold = 0.0f;
     int aa_refine = MMHIP_AA_REFINE_AUTO;
+    bool aa_set = false, filtered = false;
+    int aa_kernel = MMHIP_AA_BOX;
+    float aa_radius = 0.5f;
     const char *generator = nullptr;
     std::vector<Define> defines;
     static struct option long_options[] = {
@@ -267,6 +277,7 @@ int main(int argc, char **argv) {
         {"shutter-samples", required_argument, 0, OPT_SHUTTER_SAMPLES}, {"shutter", required_argument, 0, OPT_SHUTTER},
         {"shutter-mode", required_argument, 0, OPT_SHUTTER_MODE}, {"aa", required_argument, 0, OPT_AA},
         {"aa-threshold", required_argument, 0, OPT_AA_THRESHOLD}, {"aa-refine", required_argument, 0, OPT_AA_REFINE},
+        {"aa-filter", required_argument, 0, OPT_AA_FILTER},
         {0, 0, 0, 0}};
     for (;;) {
         int idx;
@@ -362,6 +373,31 @@ int main(int argc, char **argv) {
                 }
                 aa_x = (int)nx;
                 aa_y = (int)ny;
+                aa_set = true;
+                break;
+            }
+            case OPT_AA_FILTER: {
+                static const struct { const char *name; int kernel; float radius; } kernels[] = {
+                    {"box", MMHIP_AA_BOX, 0.5f}, {"tent", MMHIP_AA_TENT, 1.0f}, {"gaussian", MMHIP_AA_GAUSSIAN, 1.5f}, {"mitchell", MMHIP_AA_MITCHELL, 2.0f}};
+                const char *colon = strchr(optarg, ':');
+                const std::string name = colon ? std::string(optarg, colon - optarg) : std::string(optarg);
+                bool ok = false;
+                for (const auto &k : kernels)
+                    if (name == k.name) {
+                        aa_kernel = k.kernel;
+                        aa_radius = k.radius;
+                        ok = true;
+                    }
+                if (ok && colon) {
+                    char *end = nullptr;
+                    aa_radius = strtof(colon + 1, &end);
+                    ok = end != colon + 1 && !*end && std::isfinite(aa_radius) && aa_radius >= 0.5f && aa_radius <= 4.0f;
+                }
+                if (!ok) {
+                    fprintf(stderr, "Error: --aa-filter takes box, tent, gaussian or mitchell, and behind a colon a radius from 0.5 to 4.\n");
+                    return 1;
+                }
+                filtered = true;
                 break;
             }
             case OPT_AA_THRESHOLD: {
@@ -400,6 +436,22 @@ int main(int argc, char **argv) {
     }
     if (adaptive && aa_x * aa_y == 1) {
         fprintf(stderr, "Error: --aa-threshold goes with --aa.\n");
+        return 1;
+    }
+    if (filtered && !aa_set) {
+        fprintf(stderr, "Error: --aa-filter goes with --aa (which may be --aa=1).\n");
+        return 1;
+    }
+    if (filtered && supersampling) {
+        fprintf(stderr, "Error: --aa-filter is not combined with -o (oversampling).\n");
+        return 1;
+    }
+    if (filtered && adaptive) {
+        fprintf(stderr, "Error: --aa-filter is not combined with --aa-threshold.\n");
+        return 1;
+    }
+    if (filtered && shutter_fused) {
+        fprintf(stderr, "Error: --aa-filter is not combined with --shutter-mode=fused.\n");
         return 1;
     }
     if (supersampling && shutter_samples > 1) {
@@ -537,8 +589,8 @@ int main(int argc, char **argv) {
     // --shutter-samples=K: the frames go through mmhip_render_clip_shutter (--shutter-mode=fused: ..._fused), --batch-frames of them per call (by default
     // one, all of its K sub-samples in one nested clip), at the span (float)((double)FRACTION / NUM).
     // --aa: they go through mmhip_render_clip_sampled (..._fused) instead, with or without a shutter.
-    // --aa-threshold: through mmhip_render_clip_adaptive.
-    const bool shuttered = shutter_samples > 1 || sampled;
+    // --aa-threshold: through mmhip_render_clip_adaptive.  --aa-filter: through mmhip_render_clip_filtered.
+    const bool shuttered = shutter_samples > 1 || sampled || filtered;
     const float shutter_span = (float)(shutter / (double)num_frames);
     batch_frames = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch_frames, num_frames), ((size_t)1 << 30) / output.size()));
     void *dev = mmhip_device_alloc(output.size() * batch_frames);
@@ -552,7 +604,11 @@ int main(int argc, char **argv) {
                 frames[i] = first + i;
                 ts[i] = (float)(first + i) / (float)num_frames;       // mathmap_cmdline.c:835
             }
-            const int rc = adaptive
+            const int rc = filtered
+                               ? mmhip_render_clip_filtered(inv, n, frames.data(), ts.data(), shutter_samples, shutter_span, aa_x, aa_y, aa_kernel,
+                                                            aa_radius, 0, 0, img_width, img_height, 0, img_height, dev, img_width * 4,
+                                                            (int64_t)output.size(), 4, 0, nullptr)
+                           : adaptive
                                ? mmhip_render_clip_adaptive(inv, n, frames.data(), ts.data(), aa_x, aa_y, aa_threshold, aa_refine, 0, 0, img_width,
                                                             img_height, 0, img_height, dev, img_width * 4, (int64_t)output.size(), 4, 0, nullptr)
                            : sampled

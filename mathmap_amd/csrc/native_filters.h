@@ -163,5 +163,23 @@ int launch_shutter_combine_clip(const void *samples, int64_t sample_stride, int6
 int launch_aa_contrast_clip(const void *base, int64_t base_frame_stride, void *out, unsigned *counts, unsigned *list, int64_t list_stride,
                             int region_w, int rows, int render_w, int row_stride, int64_t frame_stride, int bpp, int floatmap,
                             float threshold, int frames, NativeWorkspace &ws, hipStream_t s, std::string *err);
+// One pass of the reconstruction filter of an anti-aliased clip (k_filter_combine_clip; mmhip_render_clip_filtered states
+// the arithmetic, mm_clip_filter.h holds it) over `frames` frames in one launch.  The maps hold the haloed rectangle:
+// columns [halo_x, halo_x + halo_w) by rows [halo_y, halo_y + halo_rows) of the render_w x render_h frame, as halo_rows
+// rows of render_w float4 with the rectangle's columns at the start of each row.  Grid point g = b * sx + a of time step
+// j of the pass (0 <= j < count) of frame i is at samples + i * frame_samples_stride + (j * sx * sy + g) * sample_stride.
+// wx and wy, in device memory, are the (D + 1)^2 tap blocks of each axis by edge class (mm_clip_filter_axis_blocks), D = reach.
+// The output is the rectangle of region_w columns from frame column region_x by `rows` rows from frame row first_row.
+// The time sum starts from the first step where carry_in is null, else from frame i's carry map (rows * region_w
+// float4, packed, the frames packed).  With carry_out the pass writes the running sum there and nothing else (carry_out
+// may be carry_in); without, it scales by inv_k and stores frame i at out + i * frame_stride as
+// launch_shutter_combine_clip does.  Refused: maps beyond 2^32 bytes, more than 65 535 frames, maps that do not hold
+// every neighbour of the output rectangle that lies inside the frame, float maps that are not 16-byte aligned.  Timed
+// through ws.timed_launch as filter_combine_clip.
+int launch_filter_combine_clip(const void *samples, int64_t sample_stride, int64_t frame_samples_stride, int count, int sx, int sy, int reach,
+                               const unsigned *wx, const unsigned *wy, const void *carry_in, void *carry_out, void *out, int region_x,
+                               int first_row, int region_w, int rows, int halo_x, int halo_y, int halo_w, int halo_rows, int render_w,
+                               int render_h, int row_stride, int64_t frame_stride, int bpp, int floatmap, float inv_k, int frames,
+                               NativeWorkspace &ws, hipStream_t s, std::string *err);
 
 }  // namespace mm

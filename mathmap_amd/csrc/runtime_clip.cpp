@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "mm_clip_filter.h"
 #include "mm_sample_grid.h"
 #include "mm_shutter_combine.h"
 #include "runtime_internal.h"
@@ -732,6 +733,164 @@ int mmhip_render_clip_sampled(mmhip_invocation *inv, int num_frames, const int *
     const int go = clip_target(who, inv, span, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
                                row_stride, frame_stride, bpp, floatmap, stream, true, &tg);
     return go == 1 ? render_clip_maps(inv, tg, num_frames, frames, ts, samples, span, grid_x, grid_y) : go;
+}
+
+// ---- grid-supersampled clips under a reconstruction filter wider than a pixel (mmhip_render_clip_filtered) ----
+static int clip_filter_check(const char *who, int kernel, float radius) {
+    if (kernel < 0 || kernel >= MM_CLIP_FILTER_KERNELS)
+        return fail(std::string(who) + ": kernel must be MMHIP_AA_BOX, MMHIP_AA_TENT, MMHIP_AA_GAUSSIAN or MMHIP_AA_MITCHELL (0 to 3), not " +
+                    std::to_string(kernel));
+    if (!std::isfinite(radius) || radius < 0.5f || radius > 4.0f)
+        return fail(std::string(who) + ": radius must be 0.5 to 4 pixels, not " + std::to_string(radius));
+    return 0;
+}
+
+// The rectangle the sub-sample maps of a filtered clip hold: the output's columns and rows and the D neighbours either
+// side of them that lie inside the frame.
+struct ClipHalo { int x0, y0, w, rows; };
+static ClipHalo clip_halo(int region_x, int region_w, int first_row, int last_row, int render_w, int render_h, int reach) {
+    ClipHalo h;
+    h.x0 = std::max(0, region_x - reach);
+    h.y0 = std::max(0, first_row - reach);
+    h.w = (int)std::min<int64_t>(render_w, (int64_t)region_x + region_w + reach) - h.x0;
+    h.rows = (int)std::min<int64_t>(render_h, (int64_t)last_row + reach) - h.y0;
+    return h;
+}
+
+// The rectangle of a filtered call inside the frame?  (the rows are clamped to the region already)
+static int clip_filtered_check_rect(const char *who, int region_x, int region_w, int first_row, int last_row, int render_w, int render_h) {
+    if (region_x < 0 || (int64_t)region_x + region_w > render_w)
+        return fail(std::string(who) + ": the region's columns [" + std::to_string(region_x) + ", " + std::to_string((int64_t)region_x + region_w) +
+                    ") must lie inside the render width " + std::to_string(render_w));
+    if (first_row < 0 || last_row > render_h)
+        return fail(std::string(who) + ": the rows [" + std::to_string(first_row) + ", " + std::to_string(last_row) +
+                    ") must lie inside the render height " + std::to_string(render_h));
+    return 0;
+}
+
+int mmhip_clip_filter_taps(int kernel, float radius, int n, int lo, int hi, float *out) {
+    const char *who = "clip_filter_taps";
+    if (clip_filter_check(who, kernel, radius) != 0) return -1;
+    const int reach = mm_clip_filter_reach((double)radius);
+    if (n < 1 || n > MMHIP_SAMPLE_GRID_MAX) return fail(std::string(who) + ": n must be 1 to " + std::to_string((int)MMHIP_SAMPLE_GRID_MAX) + ", not " + std::to_string(n));
+    if (lo < 0 || lo > reach || hi < 0 || hi > reach)
+        return fail(std::string(who) + ": lo and hi must be 0 to D = " + std::to_string(reach) + ", not " + std::to_string(lo) + " and " + std::to_string(hi));
+    if (!out) return fail(std::string(who) + ": out must hold (2 D + 1) * n floats");
+    float offs[MM_SAMPLE_GRID_MAX];
+    for (int a = 0; a < n; ++a) offs[a] = mm_sample_grid_offset(a, n);
+    if (mm_clip_filter_taps(kernel, (double)radius, n, offs, lo, hi, out) != 0)
+        return fail(std::string(who) + ": the weights do not sum to a positive finite number");
+    return mm_clip_filter_tap_count(reach, n);
+}
+
+int mmhip_filter_clip_filtered_plan(const mmhip_filter *f, int region_x, int region_w, int first_row, int last_row, int render_w, int render_h,
+                                    int samples, int grid_x, int grid_y, float radius, int frames, int64_t *out) {
+    (void)f;
+    const char *who = "clip filtered plan";
+    if (frames < 1) return fail("clip filtered plan: num_frames must be at least 1");
+    if (clip_sampled_check(who, samples, grid_x, grid_y) != 0) return -1;
+    if (clip_filter_check(who, MM_CLIP_FILTER_BOX, radius) != 0) return -1;
+    if (region_w < 1 || last_row <= first_row || render_w < 1 || render_h < 1) return fail("clip filtered plan: empty region");
+    if (clip_filtered_check_rect(who, region_x, region_w, first_row, last_row, render_w, render_h) != 0) return -1;
+    const ClipHalo h = clip_halo(region_x, region_w, first_row, last_row, render_w, render_h, mm_clip_filter_reach((double)radius));
+    const ClipMapsPlan p = clip_maps_plan(h.rows, render_w, samples, grid_x * grid_y, frames);
+    static_assert(MMHIP_CLIP_FILTERED_PLAN_FIELDS == 8, "the filtered plan's fields");
+    const int64_t v[8] = {p.per_batch, p.batches, p.steps_per_pass, p.passes, (int64_t)p.bytes_per_sample, p.carry, h.w, h.rows};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+long mmhip_clip_filtered_batches(mmhip_invocation *inv) { return inv->clip_filtered_batches; }
+
+// The tap blocks of one axis of `size` pixels with n grid points, for every edge class, appended to `out`.
+static int clip_filter_blocks(const char *who, int kernel, float radius, int n, int size, std::vector<unsigned> *out) {
+    const int reach = mm_clip_filter_reach((double)radius);
+    const size_t at = out->size();
+    out->resize(at + (size_t)(reach + 1) * (reach + 1) * mm_clip_filter_block_words(mm_clip_filter_tap_count(reach, n)));
+    float offs[MM_SAMPLE_GRID_MAX];
+    for (int a = 0; a < n; ++a) offs[a] = mm_sample_grid_offset(a, n);
+    if (mm_clip_filter_axis_blocks(kernel, (double)radius, n, offs, size, out->data() + at) != 0)
+        return fail(std::string(who) + ": the filter's weights do not sum to a positive finite number");
+    return 0;
+}
+
+int mmhip_render_clip_filtered(mmhip_invocation *inv, int num_frames, const int *frames, const float *ts, int samples, float span, int grid_x,
+                               int grid_y, int kernel, float radius, int region_x, int region_y, int region_w, int region_h, int first_row,
+                               int last_row, void *out_device, int row_stride, int64_t frame_stride, int bpp, int floatmap, void *stream) {
+    const char *who = "render_clip_filtered";
+    if (clip_sampled_check(who, samples, grid_x, grid_y) != 0) return -1;
+    if (clip_filter_check(who, kernel, radius) != 0) return -1;
+    ClipTarget tg;
+    const int go = clip_target(who, inv, span, num_frames, frames, ts, region_x, region_y, region_w, region_h, first_row, last_row, out_device,
+                               row_stride, frame_stride, bpp, floatmap, stream, true, &tg);
+    if (go != 1) return go;
+    const int render_w = inv->render_w, render_h = inv->render_h;
+    if (clip_filtered_check_rect(who, tg.region_x, tg.region_w, tg.first_row, tg.last_row, render_w, render_h) != 0) return -1;
+    const int grid = grid_x * grid_y, reach = mm_clip_filter_reach((double)radius);
+    const ClipHalo halo = clip_halo(tg.region_x, tg.region_w, tg.first_row, tg.last_row, render_w, render_h, reach);
+    const ClipMapsPlan plan = clip_maps_plan(halo.rows, render_w, samples, grid, num_frames);
+    const size_t bps = plan.bytes_per_sample;
+    if (bps > ((size_t)1 << 32))
+        return fail(std::string(who) + ": a sub-sample map of the haloed rectangle of more than 4 GiB; render the frame in row bands");
+    hipStream_t s = tg.s;
+    // the tap tables of both axes: built here, one upload per call
+    std::vector<unsigned> &tables = inv->clip_filter_host;
+    tables.clear();
+    if (clip_filter_blocks(who, kernel, radius, grid_x, render_w, &tables) != 0) return -1;
+    const size_t y_tables = tables.size();
+    if (clip_filter_blocks(who, kernel, radius, grid_y, render_h, &tables) != 0) return -1;
+    HIP_TRY(inv->clip_filter_taps.grow(tables.size() * sizeof(unsigned), [s] { return hipStreamSynchronize(s); }));
+    HIP_TRY(hipMemcpyAsync(inv->clip_filter_taps.get(), tables.data(), tables.size() * sizeof(unsigned), hipMemcpyHostToDevice, s));
+    const unsigned *wx = inv->clip_filter_taps.get<unsigned>(), *wy = wx + y_tables;
+    // the shutter's temporary: [frame][time step][grid point] maps of the haloed rectangle, the carry map of the output
+    // rectangle (smaller than a map) behind them; whatever still reads a smaller one has finished before it is freed
+    const size_t slots = (size_t)plan.per_batch * plan.steps_per_pass * grid;
+    if (inv->clip_shutter.grow((slots + plan.carry) * bps, hipDeviceSynchronize) != hipSuccess)
+        return fail("out of device memory for the sub-samples of a filtered clip; lower MMHIP_CLIP_SHUTTER_BYTES");
+    unsigned char *subs = inv->clip_shutter.get<unsigned char>(), *carry = plan.carry ? subs + slots * bps : nullptr;
+    const float inv_k = mm_shutter_inv_k(samples);
+    // what the nested renders land in: the haloed rectangle as float maps
+    ClipTarget maps = tg;
+    maps.region_x = halo.x0;
+    maps.region_y = halo.y0;
+    maps.region_w = halo.w;
+    maps.region_h = halo.rows;
+    maps.first_row = halo.y0;
+    maps.last_row = halo.y0 + halo.rows;
+    maps.num_rows = halo.rows;
+    SamplingOffsetGuard offsets(inv);
+    std::vector<int> sub_frames;
+    std::vector<float> sub_ts;
+    for (int b0 = 0; b0 < num_frames; b0 += plan.per_batch) {
+        const int n = std::min(plan.per_batch, num_frames - b0);
+        for (int j0 = 0; j0 < samples; j0 += plan.steps_per_pass) {
+            const int count = std::min(plan.steps_per_pass, samples - j0);
+            sub_frames.resize((size_t)n * count);
+            sub_ts.resize((size_t)n * count);
+            for (int i = 0; i < n; ++i)
+                for (int j = 0; j < count; ++j) {
+                    sub_frames[(size_t)i * count + j] = frames[b0 + i];
+                    sub_ts[(size_t)i * count + j] = mm_shutter_sample_t(ts[b0 + i], span, j0 + j, samples);
+                }
+            // the layout [i][j][g] of render_clip_maps
+            for (int b = 0; b < grid_y; ++b)
+                for (int a = 0; a < grid_x; ++a) {
+                    offsets.set(mm_sample_grid_offset(a, grid_x), mm_sample_grid_offset(b, grid_y));
+                    if (render_clip_to(inv, maps.as_floatmaps(subs + (size_t)(b * grid_x + a) * bps, (int64_t)grid * (int64_t)bps), n * count,
+                                       sub_frames.data(), sub_ts.data()) != 0)
+                        return -1;
+                }
+            const bool last = j0 + count >= samples;
+            std::string err;
+            if (launch_filter_combine_clip(subs, (int64_t)bps, (int64_t)count * grid * (int64_t)bps, count, grid_x, grid_y, reach, wx, wy,
+                                           j0 > 0 ? carry : nullptr, last ? nullptr : carry, (char *)tg.out + (int64_t)b0 * tg.frame_stride,
+                                           tg.region_x, tg.first_row, tg.region_w, tg.num_rows, halo.x0, halo.y0, halo.w, halo.rows, render_w,
+                                           render_h, tg.row_stride, tg.frame_stride, tg.bpp, tg.floatmap, inv_k, n, inv->ws, s, &err) != 0)
+                return fail(err);
+        }
+        ++inv->clip_filtered_batches;
+    }
+    return 0;
 }
 
 // ---- the same clips, fused: a pixel's sub-samples summed in the pixel kernel's registers ----

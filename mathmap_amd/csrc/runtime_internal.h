@@ -238,6 +238,11 @@ struct mmhip_invocation {
     int clip_adaptive_frames = 0;
     hipStream_t clip_adaptive_stream = nullptr;
     long clip_adaptive_batches = 0;        // mmhip_clip_adaptive_batches
+    // filtered clips (mmhip_render_clip_filtered): the tap blocks of both axes by edge class, as built on the host and
+    // as the combine reads them; the maps are the shutter's temporary
+    std::vector<unsigned> clip_filter_host;
+    DeviceBuffer clip_filter_taps;
+    long clip_filtered_batches = 0;        // mmhip_clip_filtered_batches
     uint32_t edge_color_x = 0, edge_color_y = 0;
     float sampling_offset_x = 0.f, sampling_offset_y = 0.f;
     bool timing = false;
