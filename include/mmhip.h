@@ -581,6 +581,53 @@ int mmhip_filter_clip_filtered_plan(const mmhip_filter *f, int region_x, int reg
    inside the frame (0 <= lo, hi <= D; needs no GPU): out[(dx + D) * n + a] is the weight of tap (dx, a), 0 for a tap that
    does not exist.  Returns the number of floats written, (2 D + 1) * n, or -1. */
 int mmhip_clip_filter_taps(int kernel, float radius, int n, int lo, int hi, float *out);
+/* A clip as planar Y'CbCr 4:2:0: converts num_frames RGBA8 frames in device memory -- what every clip entry point above
+   leaves at output_bpp 4 -- to the payloads of a YUV4MPEG2 file, on the GPU (k_rgba8_to_yuv420_clip, one launch).
+   Asynchronous on `stream` (0: the invocation's), like mmhip_render_clip with out_device.  This statement is the
+   specification: tests/yuv_reference.py restates it, mathmap_amd/csrc/mm_yuv.h holds it.
+     - Source: frames of width x height RGBA8 pixels (4 bytes per pixel only), of which the rows [first_row, last_row) are
+       converted.  src_rgba points at row first_row of frame 0; rows are src_row_stride bytes apart (at least 4 * width),
+       frames src_frame_stride.  The alpha byte is not read, as the PNG writer drops it.
+     - Destination: every frame is one contiguous Y4M payload: the Y plane, width * height bytes with rows `width` apart,
+       then Cb, then Cr, each cw * ch bytes with cw = (width + 1) >> 1 and ch = (height + 1) >> 1, rows cw apart.  Frames
+       are dst_frame_stride bytes apart, at least width * height + 2 * cw * ch (mmhip_yuv420_frame_bytes).  dst is the
+       base of frame 0's whole-frame layout, for a row band too.
+     - A band writes the Y rows [first_row, last_row) and the chroma rows [first_row / 2, (last_row + 1) / 2) and nothing
+       else: no byte between frames, of other rows or behind the planes.  first_row must be even and last_row even or
+       equal to height; under these two rules bands converted separately give the bytes of a whole-frame call.
+     - Arithmetic: all int32, every / a floor division (an arithmetic shift of a signed value).  Per pixel
+         Y = ((yr * R + yg * G + yb * B + 2^15) >> 16) + off
+       Per chroma sample (cx, cy), with Rs, Gs, Bs the sums over the four pixels (min(2 cx + i, width - 1), min(2 cy + j,
+       height - 1)), i, j in {0, 1} -- an odd last column or row is replicated; chroma is sited at the centre of the
+       block, hence C420jpeg --
+         Cb = clamp(((cbr * Rs + cbg * Gs + cbb * Bs + 2^17) >> 18) + 128, 0, 255)
+         Cr likewise with crr, crg, crb.
+       The clamp matters at full range only, where pure blue and pure red give 256.
+     - Coefficients: floor(k * 2^16 + 0.5) of the standard's constants, the green luma coefficient and one chroma
+       coefficient per row set so that each row sums exactly (white is Y 235 or 255, grey has chroma 128):
+         matrix, range    off   yr, yg, yb            cbr, cbg, cbb            crr, crg, crb
+         bt601 limited    16    16829, 33039, 6416    -9714, -19071, 28785     28784, -24103, -4681
+         bt601 full       0     19595, 38470, 7471    -11058, -21710, 32768    32768, -27439, -5329
+         bt709 limited    16    11966, 40254, 4064    -6596, -22189, 28785     28784, -26145, -2639
+         bt709 full       0     13933, 46871, 4732    -7509, -25259, 32768     32768, -29763, -3005
+       The Python and CLI layers use bt709 limited when nothing is given.
+     - The kernel has a path of aligned wide accesses (width a multiple of 8, src_rgba and both source strides multiples
+       of 16, dst and dst_frame_stride multiples of 8) and a path of byte accesses for everything else; the launcher
+       chooses, the bytes are the same.  Timed as yuv420_clip (mmhip_drain_native_kernel_ms).
+   Errors, by name: width or height below 1; num_frames below 1 or above 65 535; an unknown matrix or range; rows that
+   are not rows of the frame; an odd first_row; an odd last_row that is not height; a src_row_stride below one row; a
+   dst_frame_stride below one frame; a Y plane or a source band of more than 4 GiB (offsets inside a frame are 32-bit). */
+enum { MMHIP_YUV_BT601 = 0, MMHIP_YUV_BT709 = 1 };
+enum { MMHIP_YUV_LIMITED = 0, MMHIP_YUV_FULL = 1 };
+int mmhip_clip_to_yuv420(mmhip_invocation *inv, const void *src_rgba, int64_t src_row_stride, int64_t src_frame_stride, int width,
+                         int height, int first_row, int last_row, int num_frames, int matrix, int range, void *dst,
+                         int64_t dst_frame_stride, void *stream);
+/* width * height + 2 * cw * ch: the bytes of one frame's payload (needs no GPU).  -1 for a size below 1 x 1. */
+int64_t mmhip_yuv420_frame_bytes(int width, int height);
+/* The stream header of a YUV4MPEG2 file of such frames (needs no GPU):
+   "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=LIMITED\n" (or FULL), NUL-terminated, into buf of `cap` bytes.
+   A frame in the file is "FRAME\n" followed by one frame's payload.  Returns the header's length without the NUL, or -1. */
+int mmhip_y4m_header(char *buf, int cap, int width, int height, int fps_num, int fps_den, int range);
 /* Convenience: whole frame to a host RGBA8 buffer (width*height*4 bytes); synchronous. */
 int mmhip_render_host(mmhip_invocation *inv, int frame, float t, uint8_t *out_rgba);
 int mmhip_sync(mmhip_invocation *inv);

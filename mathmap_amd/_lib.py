@@ -25,6 +25,10 @@ class UservalInfo(C.Structure):
                 ("bool_default", C.c_int), ("image_flags", C.c_uint)]
 
 
+# mmhip_clip_to_yuv420's matrix and range (include/mmhip.h)
+MMHIP_YUV_BT601, MMHIP_YUV_BT709 = 0, 1
+MMHIP_YUV_LIMITED, MMHIP_YUV_FULL = 0, 1
+
 # every symbol include/mmhip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mmhip_last_error": (C.c_char_p, []),
@@ -132,6 +136,10 @@ SYMBOLS = {
     "mmhip_filter_clip_filtered_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                   C.c_float, C.c_int, C.POINTER(C.c_int64)]),
     "mmhip_clip_filter_taps": (C.c_int, [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "mmhip_clip_to_yuv420": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mmhip_yuv420_frame_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "mmhip_y4m_header": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mmhip_render_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "mmhip_sync": (C.c_int, [C.c_void_p]),
     "mmhip_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),

@@ -45,6 +45,12 @@ AA_FILTER_RADII = {"box": 0.5, "tent": 1.0, "gaussian": 1.5, "mitchell": 2.0}
 AA_RADIUS_MIN, AA_RADIUS_MAX = 0.5, 4.0
 # mmhip_filter_clip_filtered_plan's out[]
 CLIP_FILTERED_PLAN_FIELDS = CLIP_SAMPLED_PLAN_FIELDS + ("halo_columns", "halo_rows")
+# render_clip's pixel_format, yuv_matrix and yuv_range: mmhip_clip_to_yuv420's modes
+PIXEL_FORMATS = ("yuv420p",)
+YUV_MATRICES = {"bt601": 0, "bt709": 1}
+YUV_RANGES = {"limited": 0, "full": 1}
+# the RGBA8 staging buffer of render_clip(pixel_format=...) unless MMHIP_CLIP_YUV_BYTES says otherwise
+CLIP_YUV_BYTES = 1 << 30
 
 
 def sample_grid(aa):
@@ -92,6 +98,73 @@ def clip_filter_taps(aa_filter, n, lo, hi, aa_radius=None):
 
 def _err():
     return lib().mmhip_last_error().decode("utf-8", "replace")
+
+
+def yuv_mode(yuv_matrix, yuv_range):
+    """render_clip's `yuv_matrix` and `yuv_range` as mmhip_clip_to_yuv420's (matrix, range).  ValueError for an unknown name."""
+    if not isinstance(yuv_matrix, str) or yuv_matrix not in YUV_MATRICES:
+        raise ValueError("yuv_matrix must be one of %s, not %r" % (", ".join(YUV_MATRICES), yuv_matrix))
+    if not isinstance(yuv_range, str) or yuv_range not in YUV_RANGES:
+        raise ValueError("yuv_range must be one of %s, not %r" % (", ".join(YUV_RANGES), yuv_range))
+    return YUV_MATRICES[yuv_matrix], YUV_RANGES[yuv_range]
+
+
+def yuv420_frame_bytes(w, h):
+    """The bytes of one w x h frame as planar 4:2:0 (mmhip_yuv420_frame_bytes): w * h + 2 * cw * ch.  Needs no GPU."""
+    n = lib().mmhip_yuv420_frame_bytes(int(w), int(h))
+    if n < 0:
+        raise MathMapError(_err())
+    return n
+
+
+def yuv420_planes(buf, w, h):
+    """The planes of frames as render_clip(pixel_format="yuv420p") returns them: `buf` is uint8 [N, frame_bytes] (or one
+    frame, [frame_bytes]); returns the views (Y [N, h, w], Cb [N, ch, cw], Cr [N, ch, cw])."""
+    buf = np.asarray(buf)
+    if buf.ndim == 1:
+        buf = buf[None]
+    cw, ch = (w + 1) >> 1, (h + 1) >> 1
+    if buf.dtype != np.uint8 or buf.ndim != 2 or buf.shape[1] < w * h + 2 * cw * ch:
+        raise ValueError("yuv420_planes: uint8 [N, %d] for frames of %d x %d, not %s %r" % (w * h + 2 * cw * ch, w, h, buf.dtype, buf.shape))
+    n = buf.shape[0]
+    y = buf[:, :w * h].reshape(n, h, w)
+    cb = buf[:, w * h:w * h + cw * ch].reshape(n, ch, cw)
+    cr = buf[:, w * h + cw * ch:w * h + 2 * cw * ch].reshape(n, ch, cw)
+    return y, cb, cr
+
+
+def y4m_header(w, h, fps=(25, 1), yuv_range="limited"):
+    """The stream header of a YUV4MPEG2 file (mmhip_y4m_header) as bytes.  Needs no GPU."""
+    if yuv_range not in YUV_RANGES:
+        raise ValueError("yuv_range must be one of %s, not %r" % (", ".join(YUV_RANGES), yuv_range))
+    num, den = (fps, 1) if isinstance(fps, (int, np.integer)) else fps
+    line = C.create_string_buffer(160)
+    n = lib().mmhip_y4m_header(line, 160, int(w), int(h), int(num), int(den), YUV_RANGES[yuv_range])
+    if n < 0:
+        raise MathMapError(_err())
+    return line.raw[:n]
+
+
+def write_y4m(path_or_file, buf, w, h, fps=(25, 1), yuv_range="limited"):
+    """Writes frames as render_clip(pixel_format="yuv420p") returns them (uint8 [N, frame_bytes]) as one YUV4MPEG2 file:
+    the header, then "FRAME\\n" and the payload per frame.  `path_or_file`: a file name, or a binary file object (which
+    stays open).  `fps` = n or (n, d).  The colour matrix has no place in the format: tell the encoder."""
+    frame_bytes = yuv420_frame_bytes(w, h)
+    buf = np.asarray(buf)
+    if buf.ndim == 1:
+        buf = buf[None]
+    if buf.dtype != np.uint8 or buf.ndim != 2 or buf.shape[1] != frame_bytes:
+        raise ValueError("write_y4m: uint8 [N, %d] for frames of %d x %d, not %s %r" % (frame_bytes, w, h, buf.dtype, buf.shape))
+    header = y4m_header(w, h, fps, yuv_range)
+    f = open(path_or_file, "wb") if isinstance(path_or_file, (str, bytes)) or hasattr(path_or_file, "__fspath__") else path_or_file
+    try:
+        f.write(header)
+        for frame in buf:
+            f.write(b"FRAME\n")
+            f.write(np.ascontiguousarray(frame).tobytes())
+    finally:
+        if f is not path_or_file:
+            f.close()
 
 
 def shutter_sample_ts(ts, samples, span):
@@ -544,7 +617,8 @@ class Invocation:
 
     def render_clip(self, num_frames=None, frames=None, ts=None, out_ptr=None, rows=None, region=None, row_stride=None,
                     frame_stride=None, bpp=4, floatmap=False, stream=0, supersample=False, shutter_samples=1, shutter_span=None,
-                    shutter=None, shutter_mode="maps", aa=1, aa_threshold=None, aa_refine="list", aa_filter=None, aa_radius=None):
+                    shutter=None, shutter_mode="maps", aa=1, aa_threshold=None, aa_refine="list", aa_filter=None, aa_radius=None,
+                    pixel_format=None, yuv_matrix="bt709", yuv_range="limited"):
         """Renders a clip in batched launches (mmhip_render_clip): frame i at frame number frames[i] and time ts[i].
         `num_frames`=N alone is the CLI's animation: frame = i, t = (float)i / (float)N.  `rows` = (first_row,
         last_row) and `region`, `row_stride`, `bpp`, `floatmap`, `stream` as in render_rows; frame i lands
@@ -576,8 +650,28 @@ class Invocation:
         grid's sub-samples with a reconstruction filter of `aa_radius` pixels, 0.5 to 4 (default: AA_FILTER_RADII), which
         reaches into the neighbour pixels (mmhip_render_clip_filtered); `aa` may be 1, and a shutter goes with it.  An
         unknown name, a radius out of range, `aa_radius` without `aa_filter`, or `aa_filter` with `aa_threshold`,
-        `supersample` or shutter_mode="fused" is a ValueError."""
+        `supersample` or shutter_mode="fused" is a ValueError.
+        `pixel_format`="yuv420p" (default None: every call above exactly as it is) delivers the clip as planar Y'CbCr
+        4:2:0 (mmhip_clip_to_yuv420) in the mode `yuv_matrix` ("bt709", "bt601") and `yuv_range` ("limited", "full"): the
+        frames are rendered as above, in groups, into an RGBA8 staging buffer on the device -- at most
+        MMHIP_CLIP_YUV_BYTES of it (default 1 GiB, read once per call) -- and every group is converted there; frame numbers
+        and times are those of the ungrouped call.  Without `out_ptr` returns uint8 [N, frame_bytes], one Y4M payload per
+        frame (yuv420_planes, write_y4m); with it the payloads land there, yuv420_frame_bytes apart, and nothing is
+        copied to the host (the staging buffer's release waits for the device).  `rows` must begin on an even row and end
+        on an even row or the last.  `floatmap`, another `bpp`, `region`, `row_stride` or `frame_stride` with it, or an
+        unknown format, matrix or range, is a ValueError."""
         from .striping import animation_frame_t
+        if pixel_format is not None:
+            keywords = dict(num_frames=num_frames, frames=frames, ts=ts, supersample=supersample, shutter_samples=shutter_samples,
+                            shutter_span=shutter_span, shutter=shutter, shutter_mode=shutter_mode, aa=aa, aa_threshold=aa_threshold,
+                            aa_refine=aa_refine, aa_filter=aa_filter, aa_radius=aa_radius)
+            if pixel_format not in PIXEL_FORMATS:
+                raise ValueError("render_clip: pixel_format must be one of %s, not %r" % (", ".join(PIXEL_FORMATS), pixel_format))
+            for name, given in (("floatmap", floatmap), ("bpp", bpp != 4), ("region", region is not None), ("row_stride", row_stride is not None),
+                                ("frame_stride", frame_stride is not None)):
+                if given:
+                    raise ValueError("render_clip: pixel_format is not combined with %s: whole RGBA8 frames are converted" % name)
+            return self._render_clip_yuv420(yuv_mode(yuv_matrix, yuv_range), out_ptr, rows, stream, keywords)
         grid = sample_grid(aa)
         filtered = aa_filter is not None
         if aa_radius is not None and not filtered:
@@ -689,6 +783,103 @@ class Invocation:
             self._check(lib().mmhip_copy_to_host(out.ctypes.data_as(C.c_void_p), C.c_void_p(dev), out.nbytes))
         finally:
             lib().mmhip_device_free(C.c_void_p(dev))
+        return out
+
+    def clip_to_yuv420(self, src_ptr, dst_ptr, num_frames, width=None, height=None, rows=None, src_row_stride=None, src_frame_stride=None,
+                       dst_frame_stride=None, yuv_matrix="bt709", yuv_range="limited", stream=0):
+        """Converts RGBA8 frames in device memory to planar Y'CbCr 4:2:0 payloads in device memory (mmhip_clip_to_yuv420),
+        asynchronously.  `src_ptr` is the first converted row of frame 0 -- row rows[0] of the `rows` = (first_row,
+        last_row) band, default the whole frame -- rows `src_row_stride` bytes apart (default 4 * width) and frames
+        `src_frame_stride` (default: the band's rows); `dst_ptr` is the base of frame 0's payload, frames
+        `dst_frame_stride` apart (default yuv420_frame_bytes).  The size defaults to the render size."""
+        matrix, rng = yuv_mode(yuv_matrix, yuv_range)
+        w = self.render_width if width is None else int(width)
+        h = self.render_height if height is None else int(height)
+        first_row, last_row = rows if rows is not None else (0, h)
+        if src_row_stride is None:
+            src_row_stride = 4 * w
+        if src_frame_stride is None:
+            src_frame_stride = max(last_row - first_row, 0) * src_row_stride
+        if dst_frame_stride is None:
+            dst_frame_stride = w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1)
+        self._check(lib().mmhip_clip_to_yuv420(self._h, C.c_void_p(src_ptr), src_row_stride, src_frame_stride, w, h, first_row, last_row,
+                                               int(num_frames), matrix, rng, C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
+
+    def _render_clip_yuv420(self, mode, out_ptr, rows, stream, keywords):
+        """render_clip(pixel_format="yuv420p"): the clip of `keywords` in groups of frames through an RGBA8 staging buffer."""
+        import os
+        from .striping import animation_frame_t
+        matrix, rng = mode
+        num_frames, frames, ts = keywords.pop("num_frames"), keywords.pop("frames"), keywords.pop("ts")
+        shutter, shutter_span = keywords.pop("shutter"), keywords.pop("shutter_span")
+        # what the ungrouped call would make of its arguments: every group gets its frames, its ts and the span
+        if shutter is not None:
+            if shutter_span is not None:
+                raise ValueError("render_clip: give shutter or shutter_span, not both")
+            if frames is not None or ts is not None or num_frames is None:
+                raise ValueError("render_clip: shutter is a fraction of the frame interval of render_clip(num_frames=N); with frames and ts give shutter_span")
+            if num_frames < 1:
+                raise MathMapError("render_clip: num_frames must be at least 1")
+            shutter_span = np.float32(np.float64(shutter) / np.float64(num_frames))
+        if frames is None and ts is None:
+            if num_frames is None:
+                raise MathMapError("render_clip: give num_frames, or frames and ts")
+            frames = list(range(num_frames))
+            ts = [animation_frame_t(i, num_frames) for i in frames]
+        elif frames is None or ts is None:
+            raise MathMapError("render_clip: frames and ts go together")
+        frames = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        ts = np.ascontiguousarray(ts, dtype=np.float32).reshape(-1)
+        if num_frames is None:
+            num_frames = len(frames)
+        if len(frames) != num_frames or len(ts) != num_frames:
+            raise MathMapError("render_clip: frames and ts must have num_frames = %d entries" % num_frames)
+        if num_frames < 1:
+            raise MathMapError("render_clip: num_frames must be at least 1")
+        w, h = self.render_width, self.render_height
+        first_row, last_row = (int(rows[0]), int(rows[1])) if rows is not None else (0, h)
+        if not 0 <= first_row < last_row <= h:
+            raise ValueError("render_clip: rows (%d, %d) are not rows of a frame of %d" % (first_row, last_row, h))
+        if first_row % 2 or (last_row % 2 and last_row != h):
+            raise ValueError("render_clip: with pixel_format, rows begin on an even row and end on an even row or the last, not (%d, %d) of %d"
+                             % (first_row, last_row, h))
+        if out_ptr is None:
+            if rows is not None:
+                raise MathMapError("render_clip without out_ptr returns whole frames: pass out_ptr for bands")
+            stream = 0      # the invocation's, which the copy waits for
+        frame_bytes = yuv420_frame_bytes(w, h)
+        band_bytes = (last_row - first_row) * w * 4
+        try:
+            budget = int(os.environ.get("MMHIP_CLIP_YUV_BYTES", "") or 0)
+        except ValueError:
+            budget = 0
+        if budget <= 0:
+            budget = CLIP_YUV_BYTES
+        per_group = max(1, min(num_frames, 65535, budget // band_bytes))
+        out = dst = None
+        staging = lib().mmhip_device_alloc(per_group * band_bytes)
+        if not staging:
+            raise MathMapError(_err())
+        try:
+            if out_ptr is None:
+                out = np.empty((num_frames, frame_bytes), dtype=np.uint8)
+                dst = lib().mmhip_device_alloc(out.nbytes)
+                if not dst:
+                    raise MathMapError(_err())
+            for g0 in range(0, num_frames, per_group):
+                n = min(per_group, num_frames - g0)
+                self.render_clip(frames=frames[g0:g0 + n], ts=ts[g0:g0 + n], out_ptr=staging, rows=rows, stream=stream,
+                                 shutter_span=shutter_span, **keywords)
+                self._check(lib().mmhip_clip_to_yuv420(self._h, C.c_void_p(staging), w * 4, band_bytes, w, h, first_row, last_row, n, matrix, rng,
+                                                       C.c_void_p((dst if out_ptr is None else out_ptr) + g0 * frame_bytes), frame_bytes,
+                                                       C.c_void_p(stream)))
+            if out_ptr is None:
+                self.sync()
+                self._check(lib().mmhip_copy_to_host(out.ctypes.data_as(C.c_void_p), C.c_void_p(dst), out.nbytes))
+        finally:
+            lib().mmhip_device_free(C.c_void_p(staging))
+            if dst:
+                lib().mmhip_device_free(C.c_void_p(dst))
         return out
 
     def _render_clip_supersampled(self, num_frames, fp, tp, out_ptr, region, row_stride, frame_stride, bpp, stream):

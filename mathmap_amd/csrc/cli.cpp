@@ -96,6 +96,17 @@ void usage() {
            "                              gaussian or mitchell, RADIUS in pixels from 0.5\n"
            "                              to 4 (default 0.5, 1, 1.5 and 2); not combined\n"
            "                              with -o, --aa-threshold or --shutter-mode=fused\n"
+           "  <outfile> ending in .y4m    write all -F frames (-F 1 too) to one YUV4MPEG2\n"
+           "                              file, planar Y'CbCr 4:2:0 converted on the GPU\n"
+           "                              (C420jpeg chroma siting), which video encoders\n"
+           "                              read; an <outfile> of - writes that stream to\n"
+           "                              standard output, for a pipe; --batch-frames is then\n"
+           "                              by default what fits in 1 GiB of device memory\n"
+           "      --yuv-matrix=MATRIX     with a .y4m output: bt709 (default) or bt601\n"
+           "      --yuv-range=RANGE       with a .y4m output: limited (default, Y 16-235)\n"
+           "                              or full (0-255)\n"
+           "      --fps=N[:D]             with a .y4m output: the frame rate N/D written\n"
+           "                              to the header (default 25)\n"
            "\n"
            "Report bugs and suggestions to schani@complang.tuwien.ac.at\n",
            cache_size);
@@ -243,7 +254,8 @@ std::string frame_file(const std::string &pattern, int frame) {
 enum {
     OPT_VERSION = 256, OPT_HELP, OPT_HTMLDOC, OPT_BENCH_NO_OUTPUT, OPT_BENCH_ONLY_COMPILE,
     OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE, OPT_INPUT_FRAMES, OPT_BATCH_FRAMES,
-    OPT_NATIVE_INPUT_FRAME, OPT_SHUTTER_SAMPLES, OPT_SHUTTER, OPT_SHUTTER_MODE, OPT_AA, OPT_AA_THRESHOLD, OPT_AA_REFINE, OPT_AA_FILTER
+    OPT_NATIVE_INPUT_FRAME, OPT_SHUTTER_SAMPLES, OPT_SHUTTER, OPT_SHUTTER_MODE, OPT_AA, OPT_AA_THRESHOLD, OPT_AA_REFINE, OPT_AA_FILTER,
+    OPT_YUV_MATRIX, OPT_YUV_RANGE, OPT_FPS
 };
 
 int main(int argc, char **argv) {
@@ -259,6 +271,8 @@ int main(int argc, char **argv) {
     bool aa_set = false, filtered = false;
     int aa_kernel = MMHIP_AA_BOX;
     float aa_radius = 0.5f;
+    int yuv_matrix = MMHIP_YUV_BT709, yuv_range = MMHIP_YUV_LIMITED, fps_num = 25, fps_den = 1;      // quicktime_set_video(..., 25, ...), mathmap_cmdline.c:817-863
+    bool yuv_options = false, batch_frames_set = false;
     const char *generator = nullptr;
     std::vector<Define> defines;
     static struct option long_options[] = {
@@ -277,7 +291,8 @@ int main(int argc, char **argv) {
         {"shutter-samples", required_argument, 0, OPT_SHUTTER_SAMPLES}, {"shutter", required_argument, 0, OPT_SHUTTER},
         {"shutter-mode", required_argument, 0, OPT_SHUTTER_MODE}, {"aa", required_argument, 0, OPT_AA},
         {"aa-threshold", required_argument, 0, OPT_AA_THRESHOLD}, {"aa-refine", required_argument, 0, OPT_AA_REFINE},
-        {"aa-filter", required_argument, 0, OPT_AA_FILTER},
+        {"aa-filter", required_argument, 0, OPT_AA_FILTER}, {"yuv-matrix", required_argument, 0, OPT_YUV_MATRIX},
+        {"yuv-range", required_argument, 0, OPT_YUV_RANGE}, {"fps", required_argument, 0, OPT_FPS},
         {0, 0, 0, 0}};
     for (;;) {
         int idx;
@@ -344,6 +359,37 @@ int main(int argc, char **argv) {
                 long n = strtol(optarg, &end, 10);
                 if (end == optarg || *end || n < 1 || n > 65535) { fprintf(stderr, "Error: --batch-frames takes a number of frames, 1 to 65535.\n"); return 1; }
                 batch_frames = (int)n;
+                batch_frames_set = true;
+                break;
+            }
+            case OPT_YUV_MATRIX:
+                if (!strcmp(optarg, "bt601")) yuv_matrix = MMHIP_YUV_BT601;
+                else if (!strcmp(optarg, "bt709")) yuv_matrix = MMHIP_YUV_BT709;
+                else { fprintf(stderr, "Error: --yuv-matrix takes bt601 or bt709.\n"); return 1; }
+                yuv_options = true;
+                break;
+            case OPT_YUV_RANGE:
+                if (!strcmp(optarg, "limited")) yuv_range = MMHIP_YUV_LIMITED;
+                else if (!strcmp(optarg, "full")) yuv_range = MMHIP_YUV_FULL;
+                else { fprintf(stderr, "Error: --yuv-range takes limited or full.\n"); return 1; }
+                yuv_options = true;
+                break;
+            case OPT_FPS: {
+                char *end = nullptr;
+                long n = strtol(optarg, &end, 10), d = 1;
+                bool ok = end != optarg;
+                if (ok && *end == ':') {
+                    const char *second = end + 1;
+                    d = strtol(second, &end, 10);
+                    ok = end != second;
+                }
+                if (!ok || *end || n < 1 || n > 1000000000 || d < 1 || d > 1000000000) {
+                    fprintf(stderr, "Error: --fps takes a frame rate N or N:D of positive integers, like 25 or 30000:1001.\n");
+                    return 1;
+                }
+                fps_num = (int)n;
+                fps_den = (int)d;
+                yuv_options = true;
                 break;
             }
             case OPT_SHUTTER_SAMPLES: {
@@ -476,6 +522,14 @@ int main(int argc, char **argv) {
         script = argv[optind];
         output_filename = argv[optind + 1];
     }
+    // an output name ending in .y4m, or - for standard output: all frames as one YUV4MPEG2 stream
+    const size_t name_len = strlen(output_filename);
+    const bool to_stdout = !strcmp(output_filename, "-");
+    const bool y4m = to_stdout || (name_len >= 4 && !strcmp(output_filename + name_len - 4, ".y4m"));
+    if (yuv_options && !y4m) {
+        fprintf(stderr, "Error: --yuv-matrix, --yuv-range and --fps go with an output file name ending in .y4m (or -).\n");
+        return 1;
+    }
     if (htmldoc) { fprintf(stderr, "Error: --htmldoc is not supported by the HIP command line.\n"); return 1; }
     if (generator) { fprintf(stderr, "Unknown generator `%s'\n", generator); return 1; }
     // the file of frame `frame` of an image define: the name itself unless --input-frames makes it a pattern
@@ -592,11 +646,35 @@ int main(int argc, char **argv) {
     // --aa-threshold: through mmhip_render_clip_adaptive.  --aa-filter: through mmhip_render_clip_filtered.
     const bool shuttered = shutter_samples > 1 || sampled || filtered;
     const float shutter_span = (float)(shutter / (double)num_frames);
+    // A .y4m output: every batch is converted to planar 4:2:0 on the device (mmhip_clip_to_yuv420), its payloads come
+    // over in one copy, and each goes to the file behind "FRAME\n".  Without --batch-frames a batch is what fits in the
+    // 1 GiB of RGBA8 staging.
+    if (y4m && !batch_frames_set) batch_frames = 65535;
     batch_frames = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch_frames, num_frames), ((size_t)1 << 30) / output.size()));
     void *dev = mmhip_device_alloc(output.size() * batch_frames);
     if (!dev) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
+    const size_t yuv_frame = y4m ? (size_t)mmhip_yuv420_frame_bytes(img_width, img_height) : 0;
+    void *yuv_dev = nullptr;
+    std::vector<unsigned char> yuv_host;
+    FILE *movie = nullptr;
+    if (y4m) {
+        yuv_dev = mmhip_device_alloc(yuv_frame * batch_frames);
+        if (!yuv_dev) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
+        yuv_host.resize(yuv_frame * batch_frames);
+        char header[160];
+        const int header_len = mmhip_y4m_header(header, sizeof header, img_width, img_height, fps_num, fps_den, yuv_range);
+        if (header_len < 0) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
+        if (!bench_no_output) {
+            movie = to_stdout ? stdout : fopen(output_filename, "wb");
+            if (!movie || fwrite(header, 1, (size_t)header_len, movie) != (size_t)header_len) {
+                fprintf(stderr, "Error: Cannot open file `%s' for writing: %s\n", output_filename, strerror(errno));
+                return 1;
+            }
+        }
+    }
     for (int render_num = 0; render_num < bench_render_count; ++render_num) {
-        for (int first = 0; (batch_frames > 1 || shuttered) && first < num_frames; first += batch_frames) {
+        const bool last_render = render_num == bench_render_count - 1;      // (the movie holds the frames once)
+        for (int first = 0; (batch_frames > 1 || shuttered || y4m) && first < num_frames; first += batch_frames) {
             const int n = std::min(batch_frames, num_frames - first);
             std::vector<int> frames(n);
             std::vector<float> ts(n);
@@ -624,16 +702,29 @@ int main(int argc, char **argv) {
                                                                 img_width * 4, (int64_t)output.size(), 4, nullptr)
                                : mmhip_render_clip(inv, n, frames.data(), ts.data(), 0, 0, img_width, img_height, 0, img_height, dev,
                                                    img_width * 4, (int64_t)output.size(), 4, 0, nullptr);
-            if (rc != 0 || mmhip_sync(inv) != 0) {
+            if (rc != 0 ||
+                (y4m && mmhip_clip_to_yuv420(inv, dev, (int64_t)img_width * 4, (int64_t)output.size(), img_width, img_height, 0, img_height, n,
+                                             yuv_matrix, yuv_range, yuv_dev, (int64_t)yuv_frame, nullptr) != 0) ||
+                mmhip_sync(inv) != 0) {
                 fprintf(stderr, "Error: %s\n", mmhip_last_error());
                 return 1;
+            }
+            if (y4m) {
+                if (!movie || !last_render) continue;
+                if (mmhip_copy_to_host(yuv_host.data(), yuv_dev, yuv_frame * n) != 0) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
+                for (int i = 0; i < n; ++i)
+                    if (fwrite("FRAME\n", 1, 6, movie) != 6 || fwrite(yuv_host.data() + (size_t)i * yuv_frame, 1, yuv_frame, movie) != yuv_frame) {
+                        fprintf(stderr, "Error: Cannot write to file `%s': %s\n", output_filename, strerror(errno));
+                        return 1;
+                    }
+                continue;
             }
             for (int i = 0; i < n && !bench_no_output; ++i) {
                 if (mmhip_copy_to_host(output.data(), (char *)dev + (size_t)i * output.size(), output.size()) != 0) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
                 if (!write_frame(first + i)) return 1;
             }
         }
-        for (int frame = 0; batch_frames == 1 && !shuttered && frame < num_frames; ++frame) {
+        for (int frame = 0; batch_frames == 1 && !shuttered && !y4m && frame < num_frames; ++frame) {
             float t = (float)frame / (float)num_frames;       // mathmap_cmdline.c:835
             int rc = supersampling
                          ? mmhip_render_supersampled(inv, frame, t, 0, 0, img_width, img_height, dev, img_width * 4, 4, nullptr)
@@ -644,6 +735,11 @@ int main(int argc, char **argv) {
             if (!write_frame(frame)) return 1;
         }
     }
+    if (movie && (to_stdout ? fflush(movie) : fclose(movie)) != 0) {
+        fprintf(stderr, "Error: Cannot write to file `%s': %s\n", output_filename, strerror(errno));
+        return 1;
+    }
+    mmhip_device_free(yuv_dev);
     mmhip_device_free(dev);
     mmhip_invocation_free(inv);
     mmhip_filter_free(flt);

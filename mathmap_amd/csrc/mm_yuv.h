@@ -1,0 +1,85 @@
+// The arithmetic and the layout of a clip's planar Y'CbCr 4:2:0 output (k_rgba8_to_yuv420_clip, clip_yuv.hip; the
+// semantics are stated at mmhip_clip_to_yuv420 in include/mmhip.h): the coefficient tables of the four modes, the luma of
+// a pixel, the chroma of a 2 x 2 block, and where the planes of a frame lie.  Plain C++, so that the host compiles the
+// same text: the launcher takes a mode's coefficients from the table, both paths of the kernel convert with the two
+// formulas, and a stand-alone test program (tests/test_clip_yuv_api.py) runs all of it on a frame worked out by hand.
+// All of it is int32; every shift is an arithmetic shift of a signed value (floor division).
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIP__)
+#define MM_YUV_FN __attribute__((host)) __attribute__((device)) inline
+#else
+#define MM_YUV_FN inline
+#endif
+
+enum { MM_YUV_BT601 = 0, MM_YUV_BT709 = 1, MM_YUV_MATRICES = 2 };
+enum { MM_YUV_LIMITED = 0, MM_YUV_FULL = 1, MM_YUV_RANGES = 2 };
+
+// One mode: Y = ((yr R + yg G + yb B + 2^15) >> 16) + off; the chroma rows take the sums of a 2 x 2 block.  Each
+// coefficient is floor(k * 2^16 + 0.5) of the standard's constant, but for the green luma coefficient and one chroma
+// coefficient per row, which make the row sum exactly: white is 235 or 255, grey has chroma 128.
+struct mm_yuv_mode {
+    int off;
+    int yr, yg, yb;
+    int cbr, cbg, cbb;
+    int crr, crg, crb;
+};
+
+// [matrix][range]
+static const mm_yuv_mode MM_YUV_MODES[MM_YUV_MATRICES][MM_YUV_RANGES] = {
+    {{16, 16829, 33039, 6416, -9714, -19071, 28785, 28784, -24103, -4681},      // bt601 limited
+     {0, 19595, 38470, 7471, -11058, -21710, 32768, 32768, -27439, -5329}},     // bt601 full
+    {{16, 11966, 40254, 4064, -6596, -22189, 28785, 28784, -26145, -2639},      // bt709 limited
+     {0, 13933, 46871, 4732, -7509, -25259, 32768, 32768, -29763, -3005}},      // bt709 full
+};
+
+inline bool mm_yuv_mode_known(int matrix, int range) {
+    return matrix >= 0 && matrix < MM_YUV_MATRICES && range >= 0 && range < MM_YUV_RANGES;
+}
+
+// The luma of one pixel: 16 .. 235 or 0 .. 255 by construction, no clamp.
+MM_YUV_FN int mm_yuv_luma(const mm_yuv_mode &m, int r, int g, int b) { return ((m.yr * r + m.yg * g + m.yb * b + (1 << 15)) >> 16) + m.off; }
+
+// One chroma sample from the sums of its block's four pixels and the row's coefficients.  The clamp matters at full
+// range only, where pure blue and pure red give 256.
+MM_YUV_FN int mm_yuv_chroma(int kr, int kg, int kb, int rs, int gs, int bs) {
+    const int c = ((kr * rs + kg * gs + kb * bs + (1 << 17)) >> 18) + 128;
+    return c < 0 ? 0 : c > 255 ? 255 : c;
+}
+MM_YUV_FN int mm_yuv_cb(const mm_yuv_mode &m, int rs, int gs, int bs) { return mm_yuv_chroma(m.cbr, m.cbg, m.cbb, rs, gs, bs); }
+MM_YUV_FN int mm_yuv_cr(const mm_yuv_mode &m, int rs, int gs, int bs) { return mm_yuv_chroma(m.crr, m.crg, m.crb, rs, gs, bs); }
+
+// A frame: the Y plane, width * height bytes with rows `width` apart, then Cb, then Cr, each cw * ch bytes with rows cw
+// apart.
+MM_YUV_FN int mm_yuv_cw(int width) { return (width + 1) >> 1; }
+MM_YUV_FN int mm_yuv_ch(int height) { return (height + 1) >> 1; }
+MM_YUV_FN int64_t mm_yuv_cb_offset(int width, int height) { return (int64_t)width * height; }
+MM_YUV_FN int64_t mm_yuv_cr_offset(int width, int height) { return (int64_t)width * height + (int64_t)mm_yuv_cw(width) * mm_yuv_ch(height); }
+MM_YUV_FN int64_t mm_yuv_frame_bytes(int width, int height) { return (int64_t)width * height + 2 * (int64_t)mm_yuv_cw(width) * mm_yuv_ch(height); }
+
+// A whole frame on the host, as the kernel converts it: rgba is height rows of width RGBA8 pixels row_stride bytes apart
+// (the alpha byte is not read), dst one frame of mm_yuv_frame_bytes.  An odd last column or row is replicated.
+inline void mm_yuv_frame_host(const mm_yuv_mode &m, const unsigned char *rgba, int64_t row_stride, int width, int height, unsigned char *dst) {
+    const int cw = mm_yuv_cw(width), ch = mm_yuv_ch(height);
+    unsigned char *cb = dst + mm_yuv_cb_offset(width, height), *cr = dst + mm_yuv_cr_offset(width, height);
+    for (int r = 0; r < height; ++r)
+        for (int c = 0; c < width; ++c) {
+            const unsigned char *p = rgba + r * row_stride + (int64_t)c * 4;
+            dst[(int64_t)r * width + c] = (unsigned char)mm_yuv_luma(m, p[0], p[1], p[2]);
+        }
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            int rs = 0, gs = 0, bs = 0;
+            for (int j = 0; j < 2; ++j)
+                for (int i = 0; i < 2; ++i) {
+                    const int c = 2 * cx + i < width ? 2 * cx + i : width - 1, r = 2 * cy + j < height ? 2 * cy + j : height - 1;
+                    const unsigned char *p = rgba + r * row_stride + (int64_t)c * 4;
+                    rs += p[0];
+                    gs += p[1];
+                    bs += p[2];
+                }
+            cb[(int64_t)cy * cw + cx] = (unsigned char)mm_yuv_cb(m, rs, gs, bs);
+            cr[(int64_t)cy * cw + cx] = (unsigned char)mm_yuv_cr(m, rs, gs, bs);
+        }
+}

@@ -181,5 +181,17 @@ int launch_filter_combine_clip(const void *samples, int64_t sample_stride, int64
                                int first_row, int region_w, int rows, int halo_x, int halo_y, int halo_w, int halo_rows, int render_w,
                                int render_h, int row_stride, int64_t frame_stride, int bpp, int floatmap, float inv_k, int frames,
                                NativeWorkspace &ws, hipStream_t s, std::string *err);
+// RGBA8 frames of a clip to planar Y'CbCr 4:2:0 in one launch (k_rgba8_to_yuv420_clip, clip_yuv.hip; mmhip_clip_to_yuv420
+// states the semantics and its parameters are these, mm_yuv.h holds the arithmetic).  The launcher takes the path of
+// aligned wide accesses where the width is a multiple of 8, src and both source strides are multiples of 16 and dst and
+// dst_frame_stride multiples of 8, else the path of byte accesses: the same bytes.  Refused, by name, in `err` (the
+// check alone needs no GPU): a size below 1 x 1, no frame or more than 65 535, an unknown matrix or range, rows outside
+// the frame, an odd first_row, an odd last_row that is not the height, a src_row_stride below one row, a
+// dst_frame_stride below one frame, a Y plane or a source band beyond 4 GiB.  Timed through ws.timed_launch as yuv420_clip.
+int check_rgba8_to_yuv420_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
+                               int last_row, int frames, int matrix, int range, const void *dst, int64_t dst_frame_stride, std::string *err);
+int launch_rgba8_to_yuv420_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
+                                int last_row, int frames, int matrix, int range, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws,
+                                hipStream_t s, std::string *err);
 
 }  // namespace mm

@@ -8,12 +8,14 @@
 // (The exported functions have C linkage from include/mmhip.h.)
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
 #include "mm_clip_filter.h"
 #include "mm_sample_grid.h"
 #include "mm_shutter_combine.h"
+#include "mm_yuv.h"
 #include "runtime_internal.h"
 
 using namespace mm;
@@ -1198,5 +1200,41 @@ int mmhip_render_clip_adaptive(mmhip_invocation *inv, int num_frames, const int 
             return -1;
         ++inv->clip_adaptive_batches;
     }
+    return 0;
+}
+
+// ---- clips as planar Y'CbCr 4:2:0 (mmhip_clip_to_yuv420): RGBA8 frames in HBM to Y4M payloads in HBM ----
+static_assert(MMHIP_YUV_BT601 == MM_YUV_BT601 && MMHIP_YUV_BT709 == MM_YUV_BT709 && MMHIP_YUV_LIMITED == MM_YUV_LIMITED &&
+                  MMHIP_YUV_FULL == MM_YUV_FULL,
+              "the modes of mm_yuv.h");
+int64_t mmhip_yuv420_frame_bytes(int width, int height) {
+    if (width < 1 || height < 1) return fail("yuv420_frame_bytes: width and height must be at least 1");
+    return mm_yuv_frame_bytes(width, height);
+}
+
+int mmhip_y4m_header(char *buf, int cap, int width, int height, int fps_num, int fps_den, int range) {
+    if (width < 1 || height < 1) return fail("y4m_header: width and height must be at least 1");
+    if (fps_num < 1 || fps_den < 1) return fail("y4m_header: fps_num and fps_den must be at least 1");
+    if (range != MMHIP_YUV_LIMITED && range != MMHIP_YUV_FULL)
+        return fail("y4m_header: range must be MMHIP_YUV_LIMITED or MMHIP_YUV_FULL (0 or 1), not " + std::to_string(range));
+    char line[160];
+    const int n = snprintf(line, sizeof line, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=%s\n", width, height, fps_num, fps_den,
+                           range == MMHIP_YUV_FULL ? "FULL" : "LIMITED");
+    if (!buf || cap < n + 1) return fail("y4m_header: the buffer holds " + std::to_string(buf ? cap : 0) + " bytes, the header needs " + std::to_string(n + 1));
+    memcpy(buf, line, (size_t)n + 1);
+    return n;
+}
+
+int mmhip_clip_to_yuv420(mmhip_invocation *inv, const void *src_rgba, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
+                         int first_row, int last_row, int num_frames, int matrix, int range, void *dst, int64_t dst_frame_stride, void *stream) {
+    std::string err;
+    if (check_rgba8_to_yuv420_clip(src_rgba, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix, range, dst,
+                                   dst_frame_stride, &err) != 0)
+        return fail(err);
+    if (!inv) return fail("clip_to_yuv420: no invocation");
+    hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)inv->stream;
+    if (launch_rgba8_to_yuv420_clip(src_rgba, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix, range, dst,
+                                    dst_frame_stride, inv->ws, s, &err) != 0)
+        return fail(err);
     return 0;
 }
