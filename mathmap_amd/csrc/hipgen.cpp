@@ -896,7 +896,8 @@ struct Generator {
             pair = make_pair_mode(PairEnv{out, code, opt, knobs, pix_defs, pixel_stmts, pixel_fetches,
                                           [this](const Primary &p) { return prim(p, PIXEL); },
                                           [this](const Stmt *s) { return rhs(s->rhs, PIXEL, s, s->lhs->var); },
-                                          [this](const Value *v) { return value_visible(v, PIXEL); }});
+                                          [this](const Value *v) { return value_visible(v, PIXEL); },
+                                          [this](const std::string &text, const std::string &clip_text) { emit(text, clip_text); }});
         if (pair) ks.unroll = 2;
         ks.pair_mode = pair != nullptr;
         ks.pair_exit = pair && pair->exit_driven();

@@ -39,6 +39,9 @@ struct Knobs {
     // constant's truth value through a vector compare.  Only with the fused doubling's conditions and without a peeled trip: every
     // earlier switch keeps its text whatever this says
     std::optional<int> pair_step = env_int("MMHIP_PAIR_STEP");
+    // 0: a workgroup's steps are consecutive rows, as they were (hipgen_pair.cpp emit_pixel_loop): the single-frame kernel's text
+    // as it was.  Only where the fast step is taken: MMHIP_PAIR_STEP=0 and every earlier switch keep their text whatever this says
+    std::optional<int> pair_spread = env_int("MMHIP_PAIR_SPREAD");
     bool pair_no_uniform = env_int("MMHIP_PAIR_NO_UNIFORM").has_value();   // no wave-uniform scalars in pair-mode loops
     std::optional<int> nt_store = env_int("MMHIP_NT_STORE");          // #define MM_NT_STORE, instead of "the kernel fetches"
     std::optional<int> xcd_order = env_int("MMHIP_XCD_ORDER");        // workgroup -> tile order 0 / 1 / 2 (default 2)
@@ -75,6 +78,7 @@ struct PairEnv {
     std::function<std::string(const Primary &)> prim;     // the scalar generator's text of an operand in the pixel slice ...
     std::function<std::string(const Stmt *)> rhs;         // ... and of an assignment's right-hand side
     std::function<bool(const Value *)> value_visible;     // can the pixel slice name the value?
+    std::function<void(const std::string &, const std::string &)> emit_both;   // a text, and what stands in its place in the clip variant
 };
 struct PairMode {
     virtual ~PairMode() {}

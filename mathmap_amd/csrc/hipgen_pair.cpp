@@ -54,7 +54,8 @@ struct PairGen final : PairMode {
     // the fast step (emit_pixel_loop): with the fused doubling and the kernel's own pack, so that every earlier switch gives its earlier text
     const bool step = fma2 && pack && !env.knobs.pair_peel.value_or(0) && env.knobs.pair_step.value_or(1);
     bool fast_step = false;                                         // ... and this kernel has a fused loop and a result pack (make_pair_mode)
-    std::vector<std::string> entry_masks;                           // frame constants read as truth values: mm_ub<k> holds the lane mask of entry k
+    bool spread = false;                                            // ... whose steps the single-frame kernel deals across the launch's rows (MMHIP_PAIR_SPREAD)
+    std::vector<std::string> entry_masks;                         // frame constants read as truth values: mm_ub<k> holds the lane mask of entry k
 
     explicit PairGen(const PairEnv &e) : env(e), out(e.out), code(e.code) {}
 
@@ -1107,25 +1108,93 @@ MM_DEV mm_bb mm_xbs(int u) {
             std::streambuf *const own = out.rdbuf(body.rdbuf());
             emit_steps(I, pk, packed);
             out.rdbuf(own);
-            out << I << "// the fast step (hipgen_pair.cpp emit_pixel_loop): decided once; this lane's offsets from the tile's first row, that row's wave-uniform bases\n"
-                << I << "const bool mm_fast = !A.floatmap && A.output_bpp == 4 && A.row_stride >= 0 && ((MM_TILE_H * A.ppt) & 1) == 0 && ((unsigned long)A.ytab & 7ul) == 0ul &&\n"
-                << I << "                     (long)(MM_TILE_H * (A.ppt + 1) - 1) * A.row_stride + (long)A.region_width * 4 <= 0xffffffffl;\n"
-                << I << "const unsigned mm_tr = threadIdx.x / MM_TILE_W;\n"
-                << I << "const unsigned mm_oa = (unsigned)col * 4u + 2u * mm_tr * (unsigned)A.row_stride, mm_ob = mm_oa + (unsigned)A.row_stride, mm_oy = 8u * mm_tr;\n"
-                << I << "const unsigned mm_ss = (unsigned)(MM_TILE_H * A.row_stride);      // mm_p counts rows MM_TILE_H apart\n"
-                << I << "const int mm_sr = __builtin_amdgcn_readfirstlane(tile_y * (MM_TILE_H * A.ppt));\n"
-                << I << "unsigned char *const mm_so = (unsigned char *)A.out + (long)mm_sr * A.row_stride;\n"
-                << I << "const char *const mm_sy = (const char *)(A.ytab + mm_sr);\n"
-                << I << "// the steps, in mm_p, that lie inside the launch's rows (none: not a launch for the fast step): one scalar compare per step\n"
-                << I << "const int mm_pin = mm_fast ? (A.num_rows - mm_sr) / (2 * MM_TILE_H) * 2 : 0;\n"
-                << I << "// (a copy per test: one truth value read in several places would live across branches, which this compiler keeps as a lane\n"
-                << I << "// mask -- s_cselect_b64, s_and_b64 with exec, a branch on vcc -- and an if / else on it goes through a flag block; four one-sided\n"
-                << I << "// tests of scalars the compiler takes for unrelated are s_cmp and a branch on scc each)\n"
-                << I << "int mm_pin_a = mm_pin, mm_pin_b = mm_pin, mm_pin_c = mm_pin;\n"
-                << I << "asm(\"\" : \"+s\"(mm_pin_a), \"+s\"(mm_pin_b), \"+s\"(mm_pin_c));\n";
+            // what depends on the lane and the column alone; the first row `sr` the steps start from and what follows from it
+            auto lane_head = [](const std::string &I, const char *offsets) {
+                return I + "// the fast step (hipgen_pair.cpp emit_pixel_loop): decided once; this lane's offsets from the tile's first row, that row's wave-uniform bases\n" +
+                       I + "const bool mm_fast = !A.floatmap && A.output_bpp == 4 && A.row_stride >= 0 && ((MM_TILE_H * A.ppt) & 1) == 0 && ((unsigned long)A.ytab & 7ul) == 0ul &&\n" +
+                       I + "                     (long)(MM_TILE_H * (A.ppt + 1) - 1) * A.row_stride + (long)A.region_width * 4 <= 0xffffffffl;\n" +
+                       I + "const unsigned mm_tr = threadIdx.x / MM_TILE_W;\n" +
+                       I + offsets + " mm_oa = (unsigned)col * 4u + 2u * mm_tr * (unsigned)A.row_stride, mm_ob = mm_oa + (unsigned)A.row_stride, mm_oy = 8u * mm_tr;\n" +
+                       I + "const unsigned mm_ss = (unsigned)(MM_TILE_H * A.row_stride);      // mm_p counts rows MM_TILE_H apart\n";
+            };
+            auto row_head = [](const std::string &I, const std::string &sr) {
+                return I + "const int mm_sr = __builtin_amdgcn_readfirstlane(" + sr + ");\n" +
+                       I + "unsigned char *const mm_so = (unsigned char *)A.out + (long)mm_sr * A.row_stride;\n" +
+                       I + "const char *const mm_sy = (const char *)(A.ytab + mm_sr);\n" +
+                       I + "// the steps, in mm_p, that lie inside the launch's rows (none: not a launch for the fast step): one scalar compare per step\n" +
+                       I + "const int mm_pin = mm_fast ? (A.num_rows - mm_sr) / (2 * MM_TILE_H) * 2 : 0;\n";
+            };
+            auto pin_copies = [](const std::string &I) {
+                return I + "// (a copy per test: one truth value read in several places would live across branches, which this compiler keeps as a lane\n" +
+                       I + "// mask -- s_cselect_b64, s_and_b64 with exec, a branch on vcc -- and an if / else on it goes through a flag block; four one-sided\n" +
+                       I + "// tests of scalars the compiler takes for unrelated are s_cmp and a branch on scc each)\n" +
+                       I + "int mm_pin_a = mm_pin, mm_pin_b = mm_pin, mm_pin_c = mm_pin;\n" +
+                       I + "asm(\"\" : \"+s\"(mm_pin_a), \"+s\"(mm_pin_b), \"+s\"(mm_pin_c));\n";
+            };
+            std::string masks;
             for (size_t k = 0; k < entry_masks.size(); ++k)
-                out << I << "const mm_bb mm_ub" << k << " = mm_xbs(" << entry_masks[k] << ");\n";
-            out << body.str();
+                masks += I + "const mm_bb mm_ub" + std::to_string(k) + " = mm_xbs(" + entry_masks[k] + ");\n";
+            const std::string steps = body.str();
+            const std::string tile = lane_head(I, "const unsigned") + row_head(I, "tile_y * (MM_TILE_H * A.ppt)") + pin_copies(I) + masks + steps;      // consecutive steps
+            if (!spread) {
+                out << tile;
+                return;
+            }
+            // Spread steps (MMHIP_PAIR_SPREAD unset or 1; 0: the text as it was), the single-frame kernel only.  A workgroup's cost
+            // follows where its tile lies -- inside the set every pixel runs to the iteration limit -- and only a few workgroups
+            // pass through a wave slot per launch, so the heavy ones that were handed out late finish alone while the other slots
+            // stand empty.  The workgroup keeps its columns and its A.ppt / 2 steps, but the steps are no longer consecutive:
+            // step k (a segment) starts mm_nty steps behind step k - 1, mm_nty the launch's tile rows, so every workgroup takes its
+            // rows from all over the frame's height and costs about what its column costs.  The segments of all workgroups tile
+            // the launch's step rows exactly once ((k, tile_y) -> k * mm_nty + tile_y is one to one onto [0, mm_nty * A.ppt / 2));
+            // one that starts at or past the last row has nothing to do, and neither has any later one.  The step loop below is
+            // the text as it was with one trip per segment (mm_p stays 0); a clip launch has workgroups enough and keeps its text.
+            //   What a segment needs -- its first row, the two bases, mm_pin -- is computed for the first one by the statements the
+            // text had and advanced from there by scalar additions: recomputed per segment (a 64-bit multiply, a division, the
+            // select on mm_fast) the step had 40 scalar instructions where the consecutive one has 15, and rendered 4 % slower.
+            //   The step as it was counts its rows from `row0`: each of its two blocks gets one of its own, the segment's first row
+            // plus the lane's, behind an empty asm -- a segment's rows no longer follow mm_p, and the compiler would compute them,
+            // clamps and all, in front of the branch for every step (five vector instructions for blocks that run once per frame).
+            const std::string J = I + "  ", E = I + "    ";
+            auto replace_all = [](std::string s, const std::string &was, const std::string &is) {
+                for (size_t at = s.find(was); at != std::string::npos; at = s.find(was, at + is.size())) s.replace(at, was.size(), is);
+                return s;
+            };
+            const std::string rows_was = E + "const int rl_a = row0 + ";
+            const std::string seg = replace_all(replace_all(steps, "for (; mm_p < A.ppt; mm_p += 2) {\n", "for (mm_p = 0; mm_p < 2; mm_p += 2) {      // one step per segment\n"), rows_was,
+                                                E + "int row0 = mm_sr;      // the segment's first row, not the tile's\n" +
+                                                E + "asm volatile(\"\" : \"+s\"(row0));\n" +
+                                                E + "row0 += (int)(threadIdx.x / MM_TILE_W);\n" + rows_was);
+            std::string body_in;
+            for (size_t b = 0, e; b < seg.size(); b = e + 1) {      // one level deeper (preprocessor lines stay where they are)
+                e = seg.find('\n', b);
+                if (e == std::string::npos) e = seg.size() - 1;
+                body_in += (seg[b] == '#' || seg[b] == '\n' ? "" : "  ") + seg.substr(b, e + 1 - b);
+            }
+            env.emit_both(lane_head(I, "unsigned") + masks +
+                              I + "// spread steps (hipgen_pair.cpp emit_pixel_loop): segment k of this workgroup is step k * mm_nty + tile_y of the launch's rows\n" +
+                              I + "const int mm_nty = (A.tiles_magic ? (int)__umulhi((unsigned)(nwg - 1), A.tiles_magic) : (nwg - 1) / tiles_x) + 1;      // the launch's tile rows\n" +
+                              I + "// the first segment: its first row, the bases there, the whole steps (times two) from that row to the launch's last\n" +
+                              row_head(I, "tile_y * (2 * MM_TILE_H)") +
+                              I + "// from segment to segment all of them move by mm_nty steps -- one scalar addition each, nothing is multiplied or divided per\n" +
+                              I + "// step -- up to the workgroup's last segment or the launch's last row: a segment that starts at or past it has nothing to do\n" +
+                              I + "const int mm_ds = mm_nty * (2 * MM_TILE_H), mm_last = mm_sr + (A.ppt >> 1) * mm_ds, mm_end = mm_last < A.num_rows ? mm_last : A.num_rows;\n" +
+                              I + "const long mm_dso = (long)mm_ds * A.row_stride;\n" +
+                              I + "int mm_srk = mm_sr, mm_pink = mm_pin;\n" +
+                              I + "unsigned char *mm_sok = mm_so;\n" +
+                              I + "const char *mm_syk = mm_sy;\n" +
+                              "#pragma nounroll\n" +
+                              I + "for (; mm_srk < mm_end; mm_srk += mm_ds, mm_sok += mm_dso, mm_syk += 4 * mm_ds, mm_pink -= 2 * mm_nty) {\n" +
+                              J + "const int mm_sr = mm_srk, mm_pin = mm_pink;      // this segment's, under the names the step knows\n" +
+                              J + "unsigned char *const mm_so = mm_sok;\n" +
+                              J + "const char *const mm_sy = mm_syk;\n" +
+                              pin_copies(J) +
+                              J + "// (the lane offsets no longer change from step to step: left to itself the compiler adds them to the frame's base once, as\n" +
+                              J + "// 64-bit vector addresses, and adds the segment's distance to those per step -- the saddr form, a scalar base and these\n" +
+                              J + "// 32-bit offsets, needs no vector instruction at all)\n" +
+                              J + "asm volatile(\"\" : \"+v\"(mm_oa), \"+v\"(mm_ob), \"+v\"(mm_oy));\n" +
+                              body_in + I + "}\n",
+                          tile);
             return;
         }
         emit_steps(I, pk, packed);
@@ -1190,6 +1259,7 @@ std::unique_ptr<PairMode> make_pair_mode(const PairEnv &env) {
     // (with a fused loop only: a kernel in which nothing is fused has one text under either value of MMHIP_PAIR_FMA2, and
     // MMHIP_PAIR_FMA2=0 is one of the switches that keep their text)
     g->fast_step = g->step && !g->fuse_plan.empty() && g->plan_pack(pk);
+    g->spread = g->fast_step && env.knobs.pair_spread.value_or(1);
     return g;
 }
 

@@ -36,11 +36,11 @@ EXIT_MARK = "#define MM_PAIR_EXIT 1"    # ... with exit-driven loops
 ENVIRONMENTS = [{}] + [{k: v} for k, vs in [
     ("MMHIP_UNROLL", "124"), ("MMHIP_TILE_W", ["8", "64"]), ("MMHIP_SINGLE_PIXEL", "01"), ("MMHIP_PAIR", "01"),
     ("MMHIP_PAIR_MASKS", "0"), ("MMHIP_PAIR_EXIT", "0"), ("MMHIP_PAIR_EXIT_TAIL", "0"), ("MMHIP_PAIR_NO_UNIFORM", "1"),
-    ("MMHIP_NT_STORE", "01"), ("MMHIP_XCD_ORDER", "01"), ("MMHIP_WAVES_PER_EU", "2"), ("MMHIP_NO_FETCHED_RESULT", "1"),
+    ("MMHIP_PAIR_SPREAD", "0"), ("MMHIP_NT_STORE", "01"), ("MMHIP_XCD_ORDER", "01"), ("MMHIP_WAVES_PER_EU", "2"), ("MMHIP_NO_FETCHED_RESULT", "1"),
     ("MMHIP_NO_SAME_TAPS", "1"), ("MMHIP_NO_OUTSIDE_SHORTCUT", "1"), ("MMHIP_FRAME_HOT", "01"), ("MMHIP_NO_ROW_SLICE", "1"),
     ("MMHIP_MAX_CALL_DEPTH", "4")] for v in vs] + [
     {"MMHIP_PAIR": "1", k: v} for k, v in [("MMHIP_PAIR_EXIT", "0"), ("MMHIP_PAIR_EXIT_TAIL", "0"), ("MMHIP_PAIR_MASKS", "0"),
-                                           ("MMHIP_PAIR_NO_UNIFORM", "1")]]
+                                           ("MMHIP_PAIR_NO_UNIFORM", "1"), ("MMHIP_PAIR_SPREAD", "0")]]
 
 
 # the clip plans: byte budgets (read once per process), filters, (region_w, num_rows, render_w, frames), samples, aa
