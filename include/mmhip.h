@@ -628,6 +628,80 @@ int64_t mmhip_yuv420_frame_bytes(int width, int height);
    "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=LIMITED\n" (or FULL), NUL-terminated, into buf of `cap` bytes.
    A frame in the file is "FRAME\n" followed by one frame's payload.  Returns the header's length without the NUL, or -1. */
 int mmhip_y4m_header(char *buf, int cap, int width, int height, int fps_num, int fps_den, int range);
+/* The other direction: planar Y'CbCr 4:2:0 frames as an input drawable.  Converts num_frames payloads in device memory
+   -- the layout mmhip_clip_to_yuv420 writes and a YUV4MPEG2 file holds -- to the packed words of a drawable, on the GPU
+   (k_yuv420_to_rgba_clip, one launch).  Device to device, asynchronous on `stream` (0: the invocation's).  This statement
+   is the specification: tests/yuv_input_reference.py restates it, mathmap_amd/csrc/mm_yuv.h holds it.
+     - Source: every frame is one contiguous payload: the Y plane, width * height bytes with rows `width` apart, then Cb,
+       then Cr, each cw * ch bytes with cw = (width + 1) >> 1 and ch = (height + 1) >> 1, rows cw apart.  Frames are
+       src_frame_stride bytes apart, at least mmhip_yuv420_frame_bytes.  An odd last column or row has its own chroma
+       sample.
+     - Destination: packed frames of width * height uint32 words, rows `width` words apart, frames dst_frame_stride bytes
+       apart: a multiple of 4 and at least 4 * width * height.  With dst_frame_stride = 4 * width * height this is what
+       mmhip_set_image_sequence_device takes.  Nothing is written between or behind frames.
+     - Arithmetic: all int32, every >> an arithmetic shift of a signed value (a floor division).  Per pixel, with Cb' and
+       Cr' the chroma the pixel sees (below),
+         y = Y - off, u = Cb' - 128, v = Cr' - 128
+         R = clamp((ky * y + rcr * v + 2^15) >> 16, 0, 255)
+         G = clamp((ky * y + gcb * u + gcr * v + 2^15) >> 16, 0, 255)
+         B = clamp((ky * y + bcb * u + 2^15) >> 16, 0, 255)
+       and the word is R << 24 | G << 16 | B << 8 | 255, the layout of mmhip_set_image_device; alpha is 255, as the RGB8
+       upload forces it.  Out-of-range input (Y below 16 at limited range, chroma beyond 240) is legal and clamped:
+       nothing is refused per sample.  No intermediate leaves int32 for any byte triple.
+     - Coefficients: from the standard's constants Kr, Kb (0.299, 0.114 for bt601; 0.2126, 0.0722 for bt709) and Kg = 1 -
+       Kr - Kb, the magnitude rounded as floor(|k| * 2^16 + 0.5) and the sign kept.  At limited range the luma scale is
+       255/219, the chroma scale 255/224 and off 16; at full range both scales are 1 and off is 0.  ky = luma scale; rcr =
+       2 (1 - Kr) * chroma scale; bcb = 2 (1 - Kb) * chroma scale; gcb = -2 (1 - Kb) Kb / Kg * chroma scale; gcr = -2 (1 -
+       Kr) Kr / Kg * chroma scale:
+         matrix, range    off   ky      rcr      gcb      gcr      bcb
+         bt601 limited    16    76309   104597   -25675   -53279   132201
+         bt601 full       0     65536   91881    -22553   -46802   116130
+         bt709 limited    16    76309   117489   -13975   -34925   138438
+         bt709 full       0     65536   103206   -12276   -30679   121609
+       (235, 128, 128) at limited and (255, 128, 128) at full range give white, (16, 128, 128) and (0, 128, 128) black; at
+       full range (v, 128, 128) gives v, v, v.
+     - Chroma is sited at the centre of its 2 x 2 block (C420jpeg, what the writer emits).  chroma is
+         MMHIP_YUV_CHROMA_REPLICATE: pixel (x, y) takes sample (x >> 1, y >> 1);
+         MMHIP_YUV_CHROMA_BILINEAR (the Python and CLI default): cx = x >> 1, nx = clamp(cx + (x & 1 ? 1 : -1), 0, cw - 1),
+           cy and ny likewise from y and ch, and
+           C' = (9 * C[cy][cx] + 3 * C[cy][nx] + 3 * C[ny][cx] + C[ny][nx] + 8) >> 4
+           for Cb and Cr alike: an 8-bit value before the matrix is applied.
+     - The kernel has a path of aligned wide accesses (width a multiple of 8, src_yuv and src_frame_stride multiples of 8,
+       dst_rgba32 and dst_frame_stride multiples of 16) and a path of byte loads and 4-byte stores for everything else;
+       the launcher chooses, the words are the same.  mmhip_clip_from_yuv420_launches counts the launches of each.
+       MMHIP_YUV_IN_STORES=cached|nt (read per call, default cached) selects plain or non-temporal stores.  Timed as
+       yuv420_to_rgba_clip (mmhip_drain_native_kernel_ms).
+   Errors, by name: width or height below 1; num_frames below 1 or above 65 535; an unknown matrix, range or chroma mode;
+   null pointers; a src_frame_stride below one frame; a dst_frame_stride that is not a multiple of 4 or below one frame; a
+   destination frame of more than 4 GiB (offsets inside a frame are 32-bit). */
+enum { MMHIP_YUV_CHROMA_BILINEAR = 0, MMHIP_YUV_CHROMA_REPLICATE = 1 };
+enum { MMHIP_YUV_IN_PATH_ALIGNED = 0, MMHIP_YUV_IN_PATH_BYTES = 1 };
+int mmhip_clip_from_yuv420(mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height, int num_frames,
+                           int matrix, int range, int chroma, void *dst_rgba32, int64_t dst_frame_stride, void *stream);
+/* The converter's launches of this invocation on path MMHIP_YUV_IN_PATH_ALIGNED or MMHIP_YUV_IN_PATH_BYTES; -1 for
+   another path. */
+long mmhip_clip_from_yuv420_launches(mmhip_invocation *inv, int path);
+/* Binds num_frames host payloads, frame_stride bytes apart (at least mmhip_yuv420_frame_bytes), as the sequence of image
+   user value `index`: allocates the owned sequence as mmhip_set_image_sequence_host does (the same refusals of sizes,
+   the same release of the upload it replaces), uploads the payloads as they are -- 1.5 bytes per pixel -- in groups
+   through a device staging buffer of at most MMHIP_CLIP_YUV_IN_BYTES (default 256 MiB, read per call, always at least one
+   frame), converts every group with one mmhip_clip_from_yuv420 launch and binds the result through
+   mmhip_set_image_sequence_device.  Everything documented for sequences holds unchanged: in(xy, n), white for a missing
+   frame, native filters and mmhip_set_native_input_frame.  Synchronous.  mmhip_clip_yuv_input_groups returns the groups
+   of the last such call of the invocation. */
+int mmhip_set_image_sequence_yuv420_host(mmhip_invocation *inv, int index, const uint8_t *yuv, int64_t frame_stride, int width,
+                                         int height, int num_frames, int matrix, int range, int chroma);
+int mmhip_clip_yuv_input_groups(mmhip_invocation *inv);
+/* Reads the stream header of a YUV4MPEG2 file from the first `len` bytes of buf (needs no GPU).  Accepted tags: the magic
+   word YUV4MPEG2, W and H, an optional F (default 25:1), A (ignored), I of p or ?, no C tag or C420jpeg, C420mpeg2,
+   C420paldv or C420 -- all read as 8-bit 4:2:0 with centre siting: the co-sited variants (C420mpeg2, C420paldv) are read
+   as centre-sited, a shift of a quarter pixel that is not corrected -- XCOLORRANGE=FULL or LIMITED, and other X tags
+   (ignored).  *range receives MMHIP_YUV_FULL or MMHIP_YUV_LIMITED, or -1 where the header does not state it;
+   *header_len the bytes up to and including the newline.  A frame follows as a line beginning with FRAME (parameters
+   may follow the word) and one payload.  Refuses by name: another magic word; a missing or non-positive W or H; an
+   interlaced stream; every other colour space (C422, C444, C420p10, Cmono, ...); a malformed F; a header without a
+   newline within len.  Returns 0, or -1. */
+int mmhip_y4m_parse_header(const char *buf, int len, int *width, int *height, int *fps_num, int *fps_den, int *range, int *header_len);
 /* Convenience: whole frame to a host RGBA8 buffer (width*height*4 bytes); synchronous. */
 int mmhip_render_host(mmhip_invocation *inv, int frame, float t, uint8_t *out_rgba);
 int mmhip_sync(mmhip_invocation *inv);

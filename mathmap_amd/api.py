@@ -49,6 +49,8 @@ CLIP_FILTERED_PLAN_FIELDS = CLIP_SAMPLED_PLAN_FIELDS + ("halo_columns", "halo_ro
 PIXEL_FORMATS = ("yuv420p",)
 YUV_MATRICES = {"bt601": 0, "bt709": 1}
 YUV_RANGES = {"limited": 0, "full": 1}
+# set_image_yuv420's and clip_from_yuv420's chroma: mmhip_clip_from_yuv420's modes
+YUV_CHROMAS = {"bilinear": 0, "replicate": 1}
 # the RGBA8 staging buffer of render_clip(pixel_format=...) unless MMHIP_CLIP_YUV_BYTES says otherwise
 CLIP_YUV_BYTES = 1 << 30
 
@@ -109,6 +111,13 @@ def yuv_mode(yuv_matrix, yuv_range):
     return YUV_MATRICES[yuv_matrix], YUV_RANGES[yuv_range]
 
 
+def yuv_chroma(chroma):
+    """set_image_yuv420's `chroma` as mmhip_clip_from_yuv420's mode.  ValueError for an unknown name."""
+    if not isinstance(chroma, str) or chroma not in YUV_CHROMAS:
+        raise ValueError("chroma must be one of %s, not %r" % (", ".join(YUV_CHROMAS), chroma))
+    return YUV_CHROMAS[chroma]
+
+
 def yuv420_frame_bytes(w, h):
     """The bytes of one w x h frame as planar 4:2:0 (mmhip_yuv420_frame_bytes): w * h + 2 * cw * ch.  Needs no GPU."""
     n = lib().mmhip_yuv420_frame_bytes(int(w), int(h))
@@ -162,6 +171,56 @@ def write_y4m(path_or_file, buf, w, h, fps=(25, 1), yuv_range="limited"):
         for frame in buf:
             f.write(b"FRAME\n")
             f.write(np.ascontiguousarray(frame).tobytes())
+    finally:
+        if f is not path_or_file:
+            f.close()
+
+
+def y4m_parse_header(data):
+    """The stream header at the start of `data` (bytes) of a YUV4MPEG2 file (mmhip_y4m_parse_header): (w, h, (fps_num,
+    fps_den), yuv_range or None, header_len).  Needs no GPU.  ValueError, by name, for what the reader does not take."""
+    data = bytes(data)
+    out = [C.c_int(0) for _ in range(6)]
+    if lib().mmhip_y4m_parse_header(data, len(data), *[C.byref(v) for v in out]) != 0:
+        raise ValueError(_err())
+    w, h, num, den, rng, header_len = [v.value for v in out]
+    names = {v: k for k, v in YUV_RANGES.items()}
+    return w, h, (num, den), names.get(rng), header_len
+
+
+def read_y4m(path_or_file, max_frames=None):
+    """Reads a YUV4MPEG2 file of 8-bit 4:2:0 frames -- what write_y4m writes, and what video decoders emit: returns (yuv
+    uint8 [N, frame_bytes], w, h, fps (num, den), yuv_range or None), the first value being what set_image_yuv420 takes
+    and yuv_range "limited" or "full" where the header states XCOLORRANGE.  `path_or_file`: a file name, or a binary
+    file object (which stays open; a pipe will do).  `max_frames` caps the frames read.  A FRAME line may carry
+    parameters.  ValueError, by name: a header the reader does not take, a line that is not FRAME where a frame should
+    begin, a truncated last frame, a file with no frames."""
+    if max_frames is not None and int(max_frames) < 1:
+        raise ValueError("read_y4m: max_frames must be at least 1, not %r" % (max_frames,))
+    f = open(path_or_file, "rb") if isinstance(path_or_file, (str, bytes)) or hasattr(path_or_file, "__fspath__") else path_or_file
+    try:
+        header = f.readline(4096)
+        w, h, fps, yuv_range, _ = y4m_parse_header(header)
+        frame_bytes = yuv420_frame_bytes(w, h)
+        frames = []
+        while max_frames is None or len(frames) < int(max_frames):
+            line = f.readline(4096)
+            if not line:
+                break
+            if not (line.startswith(b"FRAME") and line.endswith(b"\n") and line[5:6] in (b" ", b"\n")):
+                raise ValueError("read_y4m: frame %d does not begin with a FRAME line but with %r" % (len(frames), line[:16]))
+            payload = bytearray()
+            while len(payload) < frame_bytes:          # (a pipe may deliver less than asked for)
+                piece = f.read(frame_bytes - len(payload))
+                if not piece:
+                    break
+                payload += piece
+            if len(payload) != frame_bytes:
+                raise ValueError("read_y4m: frame %d is truncated: %d of %d bytes" % (len(frames), len(payload), frame_bytes))
+            frames.append(np.frombuffer(bytes(payload), np.uint8))
+        if not frames:
+            raise ValueError("read_y4m: the file has no frames")
+        return np.stack(frames), w, h, fps, yuv_range
     finally:
         if f is not path_or_file:
             f.close()
@@ -531,6 +590,38 @@ class Invocation:
         n, h, w, c = a.shape
         self._check(lib().mmhip_set_image_sequence_host(self._h, u["index"], a.ctypes.data_as(C.c_void_p), w, h, c, n))
 
+    def set_image_yuv420(self, name, yuv, w, h, yuv_matrix="bt709", yuv_range="limited", chroma="bilinear"):
+        """Binds planar Y'CbCr 4:2:0 frames as input drawable: `yuv` is uint8 [N, frame_bytes] -- what read_y4m and
+        render_clip(pixel_format="yuv420p") return -- or one frame, [frame_bytes], of `w` x `h` pixels.  The payloads go
+        up as they are (1.5 bytes per pixel) and are expanded to the drawable's words on the GPU
+        (mmhip_set_image_sequence_yuv420_host) in the mode `yuv_matrix`, `yuv_range`, with `chroma` "bilinear" (default)
+        or "replicate"; alpha is 255.  From there on the sequence is what set_image binds."""
+        matrix, rng = yuv_mode(yuv_matrix, yuv_range)
+        mode = yuv_chroma(chroma)
+        w, h = int(w), int(h)
+        if w < 1 or h < 1:
+            raise ValueError("set_image_yuv420: w and h must be at least 1, not %d x %d" % (w, h))
+        frame_bytes = w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1)
+        a = np.asarray(yuv)
+        if a.ndim == 1:
+            a = a[None]
+        if a.dtype != np.uint8 or a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != frame_bytes:
+            raise ValueError("set_image_yuv420: uint8 [N, %d] for frames of %d x %d, not %s %r" % (frame_bytes, w, h, a.dtype, a.shape))
+        a = np.ascontiguousarray(a)
+        u = self._index(name)
+        self._check(lib().mmhip_set_image_sequence_yuv420_host(self._h, u["index"], a.ctypes.data_as(C.c_void_p), frame_bytes, w, h, a.shape[0],
+                                                               matrix, rng, mode))
+
+    def clip_yuv_input_groups(self):
+        """The upload groups of the last set_image_yuv420 (mmhip_clip_yuv_input_groups)."""
+        return lib().mmhip_clip_yuv_input_groups(self._h)
+
+    def clip_from_yuv420_launches(self, path):
+        """The launches of clip_from_yuv420's kernel on `path`: "aligned" or "bytes" (mmhip_clip_from_yuv420_launches)."""
+        if path not in ("aligned", "bytes"):
+            raise ValueError("path must be aligned or bytes, not %r" % (path,))
+        return lib().mmhip_clip_from_yuv420_launches(self._h, 0 if path == "aligned" else 1)
+
     def set_image_device(self, name, device_ptr, width, height, keepalive=None, num_frames=1):
         """Binds a packed 0xRRGGBBAA uint32 image already resident in HBM; with num_frames > 1, that
         many frames of width x height one after the other ([N,H,W] uint32)."""
@@ -804,6 +895,23 @@ class Invocation:
             dst_frame_stride = w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1)
         self._check(lib().mmhip_clip_to_yuv420(self._h, C.c_void_p(src_ptr), src_row_stride, src_frame_stride, w, h, first_row, last_row,
                                                int(num_frames), matrix, rng, C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
+
+    def clip_from_yuv420(self, src_ptr, dst_ptr, num_frames, width=None, height=None, src_frame_stride=None, dst_frame_stride=None,
+                         yuv_matrix="bt709", yuv_range="limited", chroma="bilinear", stream=0):
+        """Converts planar Y'CbCr 4:2:0 payloads in device memory to drawable words (0xRRGGBBAA, alpha 255) in device
+        memory (mmhip_clip_from_yuv420), asynchronously: what set_image_device takes.  Payloads are `src_frame_stride`
+        bytes apart (default yuv420_frame_bytes), frames of words `dst_frame_stride` (default 4 * width * height).  The
+        size defaults to the render size."""
+        matrix, rng = yuv_mode(yuv_matrix, yuv_range)
+        mode = yuv_chroma(chroma)
+        w = self.render_width if width is None else int(width)
+        h = self.render_height if height is None else int(height)
+        if src_frame_stride is None:
+            src_frame_stride = w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1)
+        if dst_frame_stride is None:
+            dst_frame_stride = 4 * w * h
+        self._check(lib().mmhip_clip_from_yuv420(self._h, C.c_void_p(src_ptr), src_frame_stride, w, h, int(num_frames), matrix, rng, mode,
+                                                 C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
 
     def _render_clip_yuv420(self, mode, out_ptr, rows, stream, keywords):
         """render_clip(pixel_format="yuv420p"): the clip of `keywords` in groups of frames through an RGBA8 staging buffer."""

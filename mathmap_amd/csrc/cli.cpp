@@ -107,6 +107,21 @@ void usage() {
            "                              or full (0-255)\n"
            "      --fps=N[:D]             with a .y4m output: the frame rate N/D written\n"
            "                              to the header (default 25)\n"
+           "  -D<name>=FILE.y4m           an input image whose file name ends in .y4m, or is -\n"
+           "                              (standard input, for one image at most), is a\n"
+           "                              YUV4MPEG2 stream of 8-bit 4:2:0 frames: all its\n"
+           "                              frames (--input-frames=NUM: the first NUM) are bound\n"
+           "                              as a sequence and expanded to RGB on the GPU; without\n"
+           "                              -s the size is the stream's, without -F every input\n"
+           "                              frame is rendered, and a .y4m output without --fps\n"
+           "                              takes the stream's frame rate; in(xy, frame)\n"
+           "                              processes the video frame by frame\n"
+           "      --input-yuv-matrix=MATRIX  with a .y4m input: bt709 (default) or bt601\n"
+           "      --input-yuv-range=RANGE with a .y4m input: limited or full (default: the\n"
+           "                              stream's XCOLORRANGE, else limited)\n"
+           "      --input-chroma=MODE     with a .y4m input: bilinear (default, chroma\n"
+           "                              interpolated between the 2 x 2 blocks' centres) or\n"
+           "                              replicate (a block's four pixels share its chroma)\n"
            "\n"
            "Report bugs and suggestions to schani@complang.tuwien.ac.at\n",
            cache_size);
@@ -228,6 +243,58 @@ bool write_png_rgb(const char *path, const unsigned char *rgba, int w, int h) {
 
 struct Define { std::string name, value; };
 
+// A YUV4MPEG2 stream of 8-bit 4:2:0 frames (mmhip_y4m_parse_header states what a header may hold): its payloads one after
+// the other, as mmhip_set_image_sequence_yuv420_host takes them.
+struct Y4mStream {
+    int uv = -1;      // the image user value it is bound to
+    int width = 0, height = 0, fps_num = 25, fps_den = 1, range = -1, frames = 0;
+    std::vector<unsigned char> payloads;
+};
+bool is_y4m_name(const std::string &v) { return v == "-" || (v.size() >= 4 && v.compare(v.size() - 4, 4, ".y4m") == 0); }
+// One line of at most `cap` bytes, the newline included; false at the end of the file before any byte.
+bool read_line(FILE *f, std::string &line, size_t cap) {
+    line.clear();
+    for (int c; line.size() < cap && (c = fgetc(f)) != EOF;) {
+        line.push_back((char)c);
+        if (c == '\n') break;
+    }
+    return !line.empty();
+}
+// Reads the stream `name` (- is standard input), at most max_frames frames of it (0: all).  On failure `err` says why.
+bool read_y4m(const std::string &name, int max_frames, Y4mStream &out, std::string &err) {
+    FILE *f = name == "-" ? stdin : fopen(name.c_str(), "rb");
+    if (!f) { err = "Could not read input stream `" + name + "': " + strerror(errno); return false; }
+    auto done = [&](bool ok) {
+        if (f != stdin) fclose(f);
+        return ok;
+    };
+    std::string line;
+    read_line(f, line, 4096);
+    int header_len = 0;
+    if (mmhip_y4m_parse_header(line.data(), (int)line.size(), &out.width, &out.height, &out.fps_num, &out.fps_den, &out.range, &header_len) != 0) {
+        err = "`" + name + "': " + mmhip_last_error();
+        return done(false);
+    }
+    const size_t frame_bytes = (size_t)mmhip_yuv420_frame_bytes(out.width, out.height);
+    while (!max_frames || out.frames < max_frames) {
+        if (!read_line(f, line, 4096)) break;
+        if (line.compare(0, 5, "FRAME") != 0 || line.back() != '\n' || (line[5] != ' ' && line[5] != '\n')) {
+            err = "`" + name + "': frame " + std::to_string(out.frames) + " does not begin with a FRAME line";
+            return done(false);
+        }
+        const size_t at = out.payloads.size();
+        out.payloads.resize(at + frame_bytes);
+        const size_t got = fread(out.payloads.data() + at, 1, frame_bytes, f);
+        if (got != frame_bytes) {
+            err = "`" + name + "': frame " + std::to_string(out.frames) + " is truncated: " + std::to_string(got) + " of " + std::to_string(frame_bytes) + " bytes";
+            return done(false);
+        }
+        ++out.frames;
+    }
+    if (!out.frames) { err = "`" + name + "': the stream has no frames"; return done(false); }
+    return done(true);
+}
+
 // --input-frames: a define's value with exactly one %d-style conversion (%d, %04d, ...; %% is a literal percent sign)
 // names one file per frame.  0: no conversion, 1: such a pattern, -1: anything else snprintf must not be handed.
 int frame_pattern(const std::string &v) {
@@ -255,7 +322,7 @@ enum {
     OPT_VERSION = 256, OPT_HELP, OPT_HTMLDOC, OPT_BENCH_NO_OUTPUT, OPT_BENCH_ONLY_COMPILE,
     OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE, OPT_INPUT_FRAMES, OPT_BATCH_FRAMES,
     OPT_NATIVE_INPUT_FRAME, OPT_SHUTTER_SAMPLES, OPT_SHUTTER, OPT_SHUTTER_MODE, OPT_AA, OPT_AA_THRESHOLD, OPT_AA_REFINE, OPT_AA_FILTER,
-    OPT_YUV_MATRIX, OPT_YUV_RANGE, OPT_FPS
+    OPT_YUV_MATRIX, OPT_YUV_RANGE, OPT_FPS, OPT_INPUT_YUV_MATRIX, OPT_INPUT_YUV_RANGE, OPT_INPUT_CHROMA
 };
 
 int main(int argc, char **argv) {
@@ -273,6 +340,8 @@ int main(int argc, char **argv) {
     float aa_radius = 0.5f;
     int yuv_matrix = MMHIP_YUV_BT709, yuv_range = MMHIP_YUV_LIMITED, fps_num = 25, fps_den = 1;      // quicktime_set_video(..., 25, ...), mathmap_cmdline.c:817-863
     bool yuv_options = false, batch_frames_set = false;
+    int input_yuv_matrix = MMHIP_YUV_BT709, input_yuv_range = -1, input_chroma = MMHIP_YUV_CHROMA_BILINEAR;      // -1: the stream's, else limited
+    bool input_yuv_options = false, frames_set = false, fps_set = false;
     const char *generator = nullptr;
     std::vector<Define> defines;
     static struct option long_options[] = {
@@ -293,6 +362,8 @@ int main(int argc, char **argv) {
         {"aa-threshold", required_argument, 0, OPT_AA_THRESHOLD}, {"aa-refine", required_argument, 0, OPT_AA_REFINE},
         {"aa-filter", required_argument, 0, OPT_AA_FILTER}, {"yuv-matrix", required_argument, 0, OPT_YUV_MATRIX},
         {"yuv-range", required_argument, 0, OPT_YUV_RANGE}, {"fps", required_argument, 0, OPT_FPS},
+        {"input-yuv-matrix", required_argument, 0, OPT_INPUT_YUV_MATRIX}, {"input-yuv-range", required_argument, 0, OPT_INPUT_YUV_RANGE},
+        {"input-chroma", required_argument, 0, OPT_INPUT_CHROMA},
         {0, 0, 0, 0}};
     for (;;) {
         int idx;
@@ -331,7 +402,7 @@ int main(int argc, char **argv) {
                 }
                 size_is_set = 1;
                 break;
-            case 'F': num_frames = atoi(optarg); if (num_frames < 1) num_frames = 1; break;
+            case 'F': num_frames = atoi(optarg); if (num_frames < 1) num_frames = 1; frames_set = true; break;
             case OPT_BENCH_RENDER_COUNT: bench_render_count = atoi(optarg); break;
             case OPT_BENCH_ONLY_COMPILE: bench_render_count = 0; break;
             case OPT_BENCH_NO_OUTPUT: bench_no_output = true; break;
@@ -390,8 +461,27 @@ int main(int argc, char **argv) {
                 fps_num = (int)n;
                 fps_den = (int)d;
                 yuv_options = true;
+                fps_set = true;
                 break;
             }
+            case OPT_INPUT_YUV_MATRIX:
+                if (!strcmp(optarg, "bt601")) input_yuv_matrix = MMHIP_YUV_BT601;
+                else if (!strcmp(optarg, "bt709")) input_yuv_matrix = MMHIP_YUV_BT709;
+                else { fprintf(stderr, "Error: --input-yuv-matrix takes bt601 or bt709.\n"); return 1; }
+                input_yuv_options = true;
+                break;
+            case OPT_INPUT_YUV_RANGE:
+                if (!strcmp(optarg, "limited")) input_yuv_range = MMHIP_YUV_LIMITED;
+                else if (!strcmp(optarg, "full")) input_yuv_range = MMHIP_YUV_FULL;
+                else { fprintf(stderr, "Error: --input-yuv-range takes limited or full.\n"); return 1; }
+                input_yuv_options = true;
+                break;
+            case OPT_INPUT_CHROMA:
+                if (!strcmp(optarg, "bilinear")) input_chroma = MMHIP_YUV_CHROMA_BILINEAR;
+                else if (!strcmp(optarg, "replicate")) input_chroma = MMHIP_YUV_CHROMA_REPLICATE;
+                else { fprintf(stderr, "Error: --input-chroma takes bilinear or replicate.\n"); return 1; }
+                input_yuv_options = true;
+                break;
             case OPT_SHUTTER_SAMPLES: {
                 char *end = nullptr;
                 long n = strtol(optarg, &end, 10);
@@ -566,6 +656,41 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    // image defines that name a YUV4MPEG2 stream (a name ending in .y4m, or - for standard input): read whole, or up to
+    // --input-frames frames, before the size and the number of frames are settled, which the first of them may give
+    std::vector<Y4mStream> streams;
+    int from_stdin = 0;
+    for (int i = 0; i < nuv; ++i) {
+        mmhip_userval_info info;
+        mmhip_filter_userval_info(flt, i, &info);
+        const Define *d = info.kind == MMHIP_UV_IMAGE ? lookup(info.name) : nullptr;
+        if (!d || !is_y4m_name(d->value)) continue;
+        from_stdin += d->value == "-";
+        streams.emplace_back();
+        streams.back().uv = i;
+    }
+    if (input_yuv_options && streams.empty()) {
+        fprintf(stderr, "Error: --input-yuv-matrix, --input-yuv-range and --input-chroma go with an input image whose file name ends in .y4m (or is -).\n");
+        return 1;
+    }
+    if (from_stdin > 1) {
+        fprintf(stderr, "Error: At most one input image can be read from standard input (-).\n");
+        return 1;
+    }
+    for (Y4mStream &st : streams) {
+        mmhip_userval_info info;
+        mmhip_filter_userval_info(flt, st.uv, &info);
+        std::string err;
+        if (!read_y4m(lookup(info.name)->value, input_frames, st, err)) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
+    }
+    auto stream_of = [&](int uv) -> const Y4mStream * {
+        for (const Y4mStream &st : streams) if (st.uv == uv) return &st;
+        return nullptr;
+    };
+    if (!streams.empty()) {
+        if (!frames_set) num_frames = streams[0].frames;
+        if (y4m && !fps_set) { fps_num = streams[0].fps_num; fps_den = streams[0].fps_den; }
+    }
     std::vector<unsigned char> pixels;
     if (!size_is_set)
         for (int i = 0; i < nuv; ++i) {
@@ -574,6 +699,12 @@ int main(int argc, char **argv) {
             if (info.kind != MMHIP_UV_IMAGE) continue;
             const Define *d = lookup(info.name);
             if (!d) { fprintf(stderr, "Error: No value defined for input image `%s'.\n", info.name); return 1; }
+            if (const Y4mStream *st = stream_of(i)) {
+                img_width = st->width;
+                img_height = st->height;
+                size_is_set = 1;
+                break;
+            }
             if (!read_png(file_of(*d, 0).c_str(), pixels, img_width, img_height)) {
                 fprintf(stderr, "Error: Could not read input image `%s'.\n", file_of(*d, 0).c_str());
                 return 1;
@@ -599,6 +730,15 @@ int main(int argc, char **argv) {
             case MMHIP_UV_FLOAT: mmhip_set_float(inv, i, (float)strtod(d->value.c_str(), nullptr)); break;
             case MMHIP_UV_BOOL: mmhip_set_bool(inv, i, (int)(float)atoi(d->value.c_str())); break;
             case MMHIP_UV_IMAGE: {
+                if (const Y4mStream *st = stream_of(i)) {
+                    const int range = input_yuv_range >= 0 ? input_yuv_range : st->range >= 0 ? st->range : MMHIP_YUV_LIMITED;
+                    if (mmhip_set_image_sequence_yuv420_host(inv, i, st->payloads.data(), mmhip_yuv420_frame_bytes(st->width, st->height), st->width,
+                                                             st->height, st->frames, input_yuv_matrix, range, input_chroma) != 0) {
+                        fprintf(stderr, "Error: %s\n", mmhip_last_error());
+                        return 1;
+                    }
+                    break;
+                }
                 // one file, or with --input-frames and a %d in the name one file per frame, all of one size
                 const int n = sequence_of(*d);
                 std::vector<unsigned char> frames;

@@ -83,3 +83,75 @@ inline void mm_yuv_frame_host(const mm_yuv_mode &m, const unsigned char *rgba, i
             cr[(int64_t)cy * cw + cx] = (unsigned char)mm_yuv_cr(m, rs, gs, bs);
         }
 }
+
+// ---- the other direction: planar Y'CbCr 4:2:0 frames to the drawable's words (k_yuv420_to_rgba_clip, clip_yuv_in.hip;
+// the semantics are stated at mmhip_clip_from_yuv420 in include/mmhip.h) ----
+enum { MM_YUV_CHROMA_BILINEAR = 0, MM_YUV_CHROMA_REPLICATE = 1, MM_YUV_CHROMAS = 2 };
+
+// One mode: with y = Y - off, u = Cb' - 128, v = Cr' - 128,
+//   R = clamp((ky y + rcr v + 2^15) >> 16), G = clamp((ky y + gcb u + gcr v + 2^15) >> 16), B = clamp((ky y + bcb u + 2^15) >> 16).
+// Each coefficient is the standard's constant with its magnitude rounded as floor(|k| * 2^16 + 0.5), the sign kept.
+struct mm_yuv_rgba_mode {
+    int off;
+    int ky, rcr, gcb, gcr, bcb;
+};
+
+// [matrix][range]
+static const mm_yuv_rgba_mode MM_YUV_RGBA_MODES[MM_YUV_MATRICES][MM_YUV_RANGES] = {
+    {{16, 76309, 104597, -25675, -53279, 132201},      // bt601 limited
+     {0, 65536, 91881, -22553, -46802, 116130}},       // bt601 full
+    {{16, 76309, 117489, -13975, -34925, 138438},      // bt709 limited
+     {0, 65536, 103206, -12276, -30679, 121609}},      // bt709 full
+};
+
+inline bool mm_yuv_chroma_known(int chroma) { return chroma >= 0 && chroma < MM_YUV_CHROMAS; }
+
+MM_YUV_FN int mm_yuv_clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+
+// One pixel's drawable word, R << 24 | G << 16 | B << 8 | 255, from its luma and the chroma it sees (any byte values:
+// what leaves 0 .. 255 is clamped).  The largest intermediate is below 2^26.
+MM_YUV_FN uint32_t mm_yuv_to_rgba(const mm_yuv_rgba_mode &m, int luma, int cb, int cr) {
+    const int y = m.ky * (luma - m.off) + (1 << 15), u = cb - 128, v = cr - 128;
+    const int r = mm_yuv_clamp255((y + m.rcr * v) >> 16);
+    const int g = mm_yuv_clamp255((y + m.gcb * u + m.gcr * v) >> 16);
+    const int b = mm_yuv_clamp255((y + m.bcb * u) >> 16);
+    return (uint32_t)r << 24 | (uint32_t)g << 16 | (uint32_t)b << 8 | 255u;
+}
+
+// The chroma a pixel sees in bilinear mode, in two exact steps: the column sum of the pixel's own chroma row (3) and its
+// neighbour row (1), then the pixel's own column (3) and its neighbour column (1), rounded once:
+// (9 C[cy][cx] + 3 C[cy][nx] + 3 C[ny][cx] + C[ny][nx] + 8) >> 4.
+MM_YUV_FN int mm_yuv_chroma_column(int own_row, int neighbour_row) { return 3 * own_row + neighbour_row; }
+MM_YUV_FN int mm_yuv_chroma_blend(int own_column, int neighbour_column) { return (3 * own_column + neighbour_column + 8) >> 4; }
+
+// Chroma sample index of the neighbour of pixel coordinate p along an axis with n chroma samples: towards the odd
+// pixel's right (lower) sample, the even pixel's left (upper) one, clamped to the plane.
+MM_YUV_FN int mm_yuv_chroma_neighbour(int p, int n) {
+    const int c = (p >> 1) + ((p & 1) ? 1 : -1);
+    return c < 0 ? 0 : c > n - 1 ? n - 1 : c;
+}
+
+// The chroma pixel (x, y) sees in a plane of cw x ch samples with rows cw apart.
+MM_YUV_FN int mm_yuv_chroma_replicate(const unsigned char *plane, int cw, int ch, int x, int y) {
+    (void)ch;
+    return plane[(int64_t)(y >> 1) * cw + (x >> 1)];
+}
+MM_YUV_FN int mm_yuv_chroma_bilinear(const unsigned char *plane, int cw, int ch, int x, int y) {
+    const int cx = x >> 1, cy = y >> 1, nx = mm_yuv_chroma_neighbour(x, cw), ny = mm_yuv_chroma_neighbour(y, ch);
+    const unsigned char *own = plane + (int64_t)cy * cw, *nb = plane + (int64_t)ny * cw;
+    return mm_yuv_chroma_blend(mm_yuv_chroma_column(own[cx], nb[cx]), mm_yuv_chroma_column(own[nx], nb[nx]));
+}
+
+// A whole frame on the host, as the kernel converts it: src is one frame's payload (mm_yuv_frame_bytes), dst width *
+// height words.
+inline void mm_yuv_to_rgba_frame_host(const mm_yuv_rgba_mode &m, int chroma, const unsigned char *src, int width, int height, uint32_t *dst) {
+    const int cw = mm_yuv_cw(width), ch = mm_yuv_ch(height);
+    const unsigned char *cb = src + mm_yuv_cb_offset(width, height), *cr = src + mm_yuv_cr_offset(width, height);
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            const bool rep = chroma == MM_YUV_CHROMA_REPLICATE;
+            const int u = rep ? mm_yuv_chroma_replicate(cb, cw, ch, x, y) : mm_yuv_chroma_bilinear(cb, cw, ch, x, y);
+            const int v = rep ? mm_yuv_chroma_replicate(cr, cw, ch, x, y) : mm_yuv_chroma_bilinear(cr, cw, ch, x, y);
+            dst[(int64_t)y * width + x] = mm_yuv_to_rgba(m, src[(int64_t)y * width + x], u, v);
+        }
+}

@@ -193,5 +193,16 @@ int check_rgba8_to_yuv420_clip(const void *src, int64_t src_row_stride, int64_t 
 int launch_rgba8_to_yuv420_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
                                 int last_row, int frames, int matrix, int range, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws,
                                 hipStream_t s, std::string *err);
+// Planar Y'CbCr 4:2:0 frames of a clip to drawable words in one launch (k_yuv420_to_rgba_clip, clip_yuv_in.hip;
+// mmhip_clip_from_yuv420 states the semantics and its parameters are these, mm_yuv.h holds the arithmetic).  The launcher
+// takes the path of aligned wide accesses (*path = 0) where the width is a multiple of 8, src and src_frame_stride are
+// multiples of 8 and dst and dst_frame_stride multiples of 16, else the path of byte accesses (*path = 1): the same
+// words.  Refused, by name, in `err` (the check alone needs no GPU): a size below 1 x 1, no frame or more than 65 535, an
+// unknown matrix, range or chroma mode, null pointers, a stride below one frame, a dst_frame_stride that is no multiple
+// of 4, a destination frame beyond 4 GiB.  Timed through ws.timed_launch as yuv420_to_rgba_clip.
+int check_yuv420_to_rgba_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
+                              const void *dst, int64_t dst_frame_stride, std::string *err);
+int launch_yuv420_to_rgba_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
+                               void *dst, int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err);
 
 }  // namespace mm

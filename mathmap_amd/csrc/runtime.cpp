@@ -644,6 +644,60 @@ int mmhip_set_image_sequence_host(mmhip_invocation *inv, int index, const uint8_
     return mmhip_set_image_sequence_device(inv, index, dev, width, height, num_frames);
 }
 
+// Planar Y'CbCr 4:2:0 payloads as a sequence: they go up as they are, in groups through a staging buffer of at most
+// MMHIP_CLIP_YUV_IN_BYTES, and k_yuv420_to_rgba_clip expands every group into the owned sequence.
+int mmhip_set_image_sequence_yuv420_host(mmhip_invocation *inv, int index, const uint8_t *yuv, int64_t frame_stride, int width, int height,
+                                         int num_frames, int matrix, int range, int chroma) {
+    const std::string who = "set_image_sequence_yuv420_host: ";
+    if (width < 1 || height < 1) return fail(who + "width and height must be at least 1, not " + std::to_string(width) + " x " + std::to_string(height));
+    if (num_frames < 1) return fail("num_frames must be at least 1");
+    size_t bytes = 0;
+    if (!sequence_bytes(width, height, num_frames, bytes)) return fail("image sequence: the size overflows (fewer than 2^31 rows in all, and a byte count that fits)");
+    if (!yuv) return fail(who + "no payloads");
+    const int64_t frame_bytes = mmhip_yuv420_frame_bytes(width, height), words_bytes = (int64_t)width * height * 4;
+    if (frame_stride < frame_bytes)
+        return fail(who + "frame_stride " + std::to_string(frame_stride) + " is smaller than one frame (" + std::to_string(frame_bytes) + " bytes)");
+    std::string err;
+    // (the converter's own refusals before anything is allocated: the pointers are placeholders)
+    if (check_yuv420_to_rgba_clip(yuv, frame_bytes, width, height, 1, matrix, range, chroma, yuv, words_bytes, &err) != 0) return fail(err);
+    if (!uv_info(inv, index, UvKind::Image)) return -1;
+    const char *text = getenv("MMHIP_CLIP_YUV_IN_BYTES");
+    long long budget = text ? atoll(text) : 0;
+    if (budget <= 0) budget = (long long)256 << 20;
+    const int per_group = (int)std::max<long long>(1, std::min<long long>(std::min(num_frames, 65535), budget / frame_bytes));
+    DeviceBuffer d, staging;
+    HIP_TRY(d.grow(bytes));
+    HIP_TRY(staging.grow((size_t)per_group * (size_t)frame_bytes));
+    hipStream_t s = (hipStream_t)inv->stream;
+    inv->clip_yuv_input_groups = 0;
+    for (int g0 = 0; g0 < num_frames; g0 += per_group) {
+        const int n = std::min(per_group, num_frames - g0);
+        if (g0) HIP_TRY(hipStreamSynchronize(s));      // the launch before this one reads the staging buffer
+        const uint8_t *from = yuv + (size_t)g0 * (size_t)frame_stride;
+        if (frame_stride == frame_bytes) HIP_TRY(hipMemcpy(staging.get(), from, (size_t)n * (size_t)frame_bytes, hipMemcpyHostToDevice));
+        else
+            for (int k = 0; k < n; ++k)
+                HIP_TRY(hipMemcpy(staging.get<char>() + (size_t)k * (size_t)frame_bytes, from + (size_t)k * (size_t)frame_stride, (size_t)frame_bytes,
+                                  hipMemcpyHostToDevice));
+        if (mmhip_clip_from_yuv420(inv, staging.get(), frame_bytes, width, height, n, matrix, range, chroma, d.get<char>() + (size_t)g0 * (size_t)words_bytes,
+                                   words_bytes, s) != 0)
+            return -1;
+        ++inv->clip_yuv_input_groups;
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    // the upload this one replaces (if it was ours) is freed once nothing in flight reads it
+    const void *old = inv->images[inv->image_slot_of_uv[index]].data;
+    for (auto it = inv->owned.begin(); it != inv->owned.end(); ++it)
+        if (it->get() == old) {
+            (void)hipDeviceSynchronize();     // renders may have been queued on caller streams
+            inv->owned.erase(it);
+            break;
+        }
+    const void *dev = d.get();
+    inv->owned.push_back(std::move(d));
+    return mmhip_set_image_sequence_device(inv, index, dev, width, height, num_frames);
+}
+
 int mmhip_set_image_host(mmhip_invocation *inv, int index, const uint8_t *pixels, int width, int height, int channels) {
     return mmhip_set_image_sequence_host(inv, index, pixels, width, height, channels, 1);
 }

@@ -1238,3 +1238,85 @@ int mmhip_clip_to_yuv420(mmhip_invocation *inv, const void *src_rgba, int64_t sr
         return fail(err);
     return 0;
 }
+
+// ---- planar Y'CbCr 4:2:0 as input (mmhip_clip_from_yuv420): Y4M payloads in HBM to drawable words in HBM ----
+static_assert(MMHIP_YUV_CHROMA_BILINEAR == MM_YUV_CHROMA_BILINEAR && MMHIP_YUV_CHROMA_REPLICATE == MM_YUV_CHROMA_REPLICATE,
+              "the chroma modes of mm_yuv.h");
+int mmhip_clip_from_yuv420(mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height, int num_frames, int matrix,
+                           int range, int chroma, void *dst_rgba32, int64_t dst_frame_stride, void *stream) {
+    std::string err;
+    if (check_yuv420_to_rgba_clip(src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, dst_rgba32, dst_frame_stride, &err) != 0)
+        return fail(err);
+    if (!inv) return fail("clip_from_yuv420: no invocation");
+    hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)inv->stream;
+    int path = 0;
+    if (launch_yuv420_to_rgba_clip(src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, dst_rgba32, dst_frame_stride, inv->ws,
+                                   s, &path, &err) != 0)
+        return fail(err);
+    ++inv->clip_yuv_input_launches[path];
+    return 0;
+}
+
+long mmhip_clip_from_yuv420_launches(mmhip_invocation *inv, int path) {
+    if (path != MMHIP_YUV_IN_PATH_ALIGNED && path != MMHIP_YUV_IN_PATH_BYTES)
+        return fail("clip_from_yuv420_launches: path must be MMHIP_YUV_IN_PATH_ALIGNED or MMHIP_YUV_IN_PATH_BYTES (0 or 1), not " + std::to_string(path));
+    return inv->clip_yuv_input_launches[path];
+}
+
+int mmhip_clip_yuv_input_groups(mmhip_invocation *inv) { return inv->clip_yuv_input_groups; }
+
+int mmhip_y4m_parse_header(const char *buf, int len, int *width, int *height, int *fps_num, int *fps_den, int *range, int *header_len) {
+    const std::string who = "y4m_parse_header: ";
+    if (!buf || len < 0) return fail(who + "no buffer");
+    const char *nl = (const char *)memchr(buf, '\n', (size_t)len);
+    if (len < 9 || memcmp(buf, "YUV4MPEG2", 9) != 0 || (len > 9 && buf[9] != ' ' && buf[9] != '\n'))
+        return fail(who + "the stream does not begin with the magic word YUV4MPEG2");
+    if (!nl) return fail(who + "no newline within the first " + std::to_string(len) + " bytes: not a stream header");
+    int w = 0, h = 0, num = 25, den = 1, rng = -1;
+    // a positive int that fills the whole text, or 0
+    auto number = [](const std::string &text) {
+        if (text.empty() || text.size() > 9) return 0;
+        for (char c : text)
+            if (c < '0' || c > '9') return 0;
+        return atoi(text.c_str());
+    };
+    const std::string line(buf + 9, nl);
+    for (size_t at = 0; at < line.size();) {
+        if (line[at] == ' ') { ++at; continue; }
+        const size_t end = std::min(line.find(' ', at), line.size());
+        const std::string tag = line.substr(at, end - at), value = tag.substr(1);
+        at = end;
+        switch (tag[0]) {
+            case 'W': w = number(value); break;
+            case 'H': h = number(value); break;
+            case 'F': {
+                const size_t colon = value.find(':');
+                num = colon == std::string::npos ? 0 : number(value.substr(0, colon));
+                den = colon == std::string::npos ? 0 : number(value.substr(colon + 1));
+                if (num < 1 || den < 1) return fail(who + "the frame rate `" + tag + "' is not F<num>:<den> of positive integers");
+                break;
+            }
+            case 'A': break;
+            case 'I':
+                if (value != "p" && value != "?") return fail(who + "an interlaced stream (`" + tag + "'): only progressive frames are read");
+                break;
+            case 'C':
+                if (value != "420jpeg" && value != "420mpeg2" && value != "420paldv" && value != "420")
+                    return fail(who + "the colour space `" + tag + "' is not 8-bit 4:2:0 (C420jpeg, C420mpeg2, C420paldv or C420)");
+                break;
+            case 'X':
+                if (value == "COLORRANGE=FULL") rng = MMHIP_YUV_FULL;
+                else if (value == "COLORRANGE=LIMITED") rng = MMHIP_YUV_LIMITED;
+                break;
+            default: return fail(who + "the header tag `" + tag + "' is not known");
+        }
+    }
+    if (w < 1 || h < 1) return fail(who + "W and H must be given and positive");
+    if (width) *width = w;
+    if (height) *height = h;
+    if (fps_num) *fps_num = num;
+    if (fps_den) *fps_den = den;
+    if (range) *range = rng;
+    if (header_len) *header_len = (int)(nl - buf) + 1;
+    return 0;
+}

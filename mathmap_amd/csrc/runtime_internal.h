@@ -243,6 +243,10 @@ struct mmhip_invocation {
     std::vector<unsigned> clip_filter_host;
     DeviceBuffer clip_filter_taps;
     long clip_filtered_batches = 0;        // mmhip_clip_filtered_batches
+    // YUV 4:2:0 input (mmhip_clip_from_yuv420, mmhip_set_image_sequence_yuv420_host): the converter's launches by the
+    // path the launcher took (aligned, byte), and the upload groups of the last host call
+    long clip_yuv_input_launches[2] = {0, 0};
+    int clip_yuv_input_groups = 0;
     uint32_t edge_color_x = 0, edge_color_y = 0;
     float sampling_offset_x = 0.f, sampling_offset_y = 0.f;
     bool timing = false;
