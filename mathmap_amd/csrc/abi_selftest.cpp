@@ -14,6 +14,7 @@
 
 #include "../../include/mathmap_hip_backend.h"
 #include "../../include/mmhip.h"
+#include "clip_kernels.h"
 #include "front.h"
 #include "mm_clip_filter.h"
 #include "mm_sample_grid.h"
@@ -649,9 +650,10 @@ int mmhip_selftest_shutter_combine(const float *maps, int frames, int samples, i
         for (int j0 = 0; j0 < samples; j0 += samples_per_pass) {
             const int count = std::min(samples_per_pass, samples - j0);
             const bool last = j0 + count >= samples;
-            if (mm::launch_shutter_combine_clip(subs.get<unsigned char>() + (size_t)j0 * map_bytes, (int64_t)map_bytes, (int64_t)(map_bytes * samples), count,
-                                                j0 > 0 ? carry.get() : nullptr, last ? nullptr : carry.get(), dst.get<unsigned char>() + out_offset,
-                                                region_w, rows, render_w, row_stride, frame_stride, bpp, floatmap, inv_k, frames, ws, nullptr, &err) != 0) {
+            const mm::ClipSamples in{subs.get<unsigned char>() + (size_t)j0 * map_bytes, (int64_t)map_bytes, (int64_t)(map_bytes * samples), count,
+                                     j0 > 0 ? carry.get() : nullptr, last ? nullptr : carry.get()};
+            const mm::ClipStore to{dst.get<unsigned char>() + out_offset, row_stride, frame_stride, bpp, floatmap};
+            if (mm::launch_shutter_combine_clip(in, to, region_w, rows, render_w, inv_k, frames, ws, nullptr, &err) != 0) {
                 g_selftest_err = err;
                 return false;
             }
@@ -726,14 +728,15 @@ int mmhip_selftest_filter_combine(const float *maps, int frames, int steps, int 
     auto run = [&]() {
         std::string err;
         const unsigned *wx = taps_dev.get<unsigned>(), *wy = wx + y_tables;
+        const mm::ClipFilterTaps taps{sx, sy, reach, wx, wy};
+        const mm::ClipStore to{dst.get<unsigned char>() + out_offset, row_stride, frame_stride, bpp, floatmap};
+        const mm::ClipRect rect{region_x, first_row, region_w, rows, hx0, hy0, hw, hrows, render_w, render_h};
         for (int j0 = 0; j0 < steps; j0 += steps_per_pass) {
             const int count = std::min(steps_per_pass, steps - j0);
             const bool last = j0 + count >= steps;
-            if (mm::launch_filter_combine_clip(subs.get<unsigned char>() + (size_t)j0 * grid * map_bytes, (int64_t)map_bytes,
-                                               (int64_t)(map_bytes * grid * steps), count, sx, sy, reach, wx, wy, j0 > 0 ? carry.get() : nullptr,
-                                               last ? nullptr : carry.get(), dst.get<unsigned char>() + out_offset, region_x, first_row, region_w,
-                                               rows, hx0, hy0, hw, hrows, render_w, render_h, row_stride, frame_stride, bpp, floatmap, inv_k, frames,
-                                               ws, nullptr, &err) != 0) {
+            const mm::ClipSamples in{subs.get<unsigned char>() + (size_t)j0 * grid * map_bytes, (int64_t)map_bytes, (int64_t)(map_bytes * grid * steps),
+                                     count, j0 > 0 ? carry.get() : nullptr, last ? nullptr : carry.get()};
+            if (mm::launch_filter_combine_clip(in, taps, to, rect, inv_k, frames, ws, nullptr, &err) != 0) {
                 g_selftest_err = err;
                 return false;
             }

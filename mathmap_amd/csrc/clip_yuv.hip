@@ -8,7 +8,7 @@
 #include <string>
 
 #include "mm_yuv.h"
-#include "native_filters.h"
+#include "clip_kernels.h"
 
 namespace mm {
 

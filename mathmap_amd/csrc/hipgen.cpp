@@ -1427,7 +1427,7 @@ const char *sampled_prelude() {
 }
 
 // What mm_pixels_refine has besides those: every frame's list of the pixels to refine (col | rl << 16, list_stride entries
-// per frame) and the lists' lengths, as the mask kernel (k_aa_contrast_clip, native_filters.hip) left them.
+// per frame) and the lists' lengths, as the mask kernel (k_aa_contrast_clip, clip_combine.hip) left them.
 const char *refine_prelude() {
     return "struct mm_refine { const unsigned *list; const unsigned *counts; long long list_stride; };\n";
 }

@@ -1,4 +1,4 @@
-// The arithmetic of a clip's reconstruction filter (k_filter_combine_clip, native_filters.hip; the semantics are stated
+// The arithmetic of a clip's reconstruction filter (k_filter_combine_clip, clip_combine.hip; the semantics are stated
 // at mmhip_render_clip_filtered in include/mmhip.h): the kernel functions of one axis in double, the normalised float
 // taps of a pixel's edge class, and the two sequential f32 sums -- along the row into h_b, down the column into s_j.
 // Plain C++, so that the host compiles the same text: the runtime builds the tap tables with it, the combine kernel sums

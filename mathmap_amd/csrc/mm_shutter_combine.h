@@ -1,4 +1,4 @@
-// The per-pixel arithmetic of the shutter combine (k_shutter_combine_clip, native_filters.hip; the semantics are stated
+// The per-pixel arithmetic of the shutter combine (k_shutter_combine_clip, clip_combine.hip; the semantics are stated
 // at mmhip_render_clip_shutter in include/mmhip.h): the time of a sub-sample, the sequential f32 sum of a pixel's
 // sub-samples, its scale by 1 / K, and the pixel store's byte conversions for output_bpp 1 - 4 (mm_store_pixel in
 // mm_device.h: CLAMP01, products in double, truncation).  Plain C++, so that the host compiles the same text

@@ -1,4 +1,4 @@
-// The per-word arithmetic of the clip's supersampling combine (k_supersample_combine_clip, native_filters.hip): one
+// The per-word arithmetic of the clip's supersampling combine (k_supersample_combine_clip, clip_combine.hip): one
 // RGBA8 pixel is one 32-bit word, and the combine's per-byte (l1[c] + l1[c+1] + 2*l2[c] + l3[c] + l3[c+1]) / 6 is done on
 // the word's even and odd bytes spread into the 16-bit halves of two words.  Plain C++, so that the host compiles the
 // same text (tests/test_clip_supersample_api.py runs it against the per-byte formula).

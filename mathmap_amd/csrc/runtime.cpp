@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/mmhip.h"
+#include "clip_kernels.h"
 #include "front.h"
 #include "hipgen.h"
 #include "mm_host_abi.h"

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "clip_kernels.h"
 #include "mm_clip_filter.h"
 #include "mm_sample_grid.h"
 #include "mm_shutter_combine.h"
@@ -122,6 +123,8 @@ struct ClipTarget {
         t.out = (char *)out + (int64_t)b0 * frame_stride;
         return t;
     }
+    // where a combine kernel stores the frames (clip_kernels.h)
+    ClipStore store() const { return ClipStore{out, row_stride, frame_stride, bpp, floatmap}; }
 };
 
 // Fills `tg` from an entry point's arguments and makes the checks all of them share, under the name of the one that was
@@ -699,9 +702,8 @@ static int render_clip_maps(mmhip_invocation *inv, const ClipTarget &tg, int num
                 }
             const bool last = j0 + count >= samples;
             std::string err;
-            if (launch_shutter_combine_clip(subs, (int64_t)bps, (int64_t)count * grid * (int64_t)bps, count * grid, j0 > 0 ? carry : nullptr,
-                                            last ? nullptr : carry, (char *)tg.out + (int64_t)b0 * tg.frame_stride, tg.region_w, tg.num_rows,
-                                            inv->render_w, tg.row_stride, tg.frame_stride, tg.bpp, tg.floatmap, inv_k, n, inv->ws, s, &err) != 0)
+            const ClipSamples in{subs, (int64_t)bps, (int64_t)count * grid * (int64_t)bps, count * grid, j0 > 0 ? carry : nullptr, last ? nullptr : carry};
+            if (launch_shutter_combine_clip(in, tg.from_frame(b0).store(), tg.region_w, tg.num_rows, inv->render_w, inv_k, n, inv->ws, s, &err) != 0)
                 return fail(err);
         }
         ++batches;
@@ -844,6 +846,8 @@ int mmhip_render_clip_filtered(mmhip_invocation *inv, int num_frames, const int 
     HIP_TRY(inv->clip_filter_taps.grow(tables.size() * sizeof(unsigned), [s] { return hipStreamSynchronize(s); }));
     HIP_TRY(hipMemcpyAsync(inv->clip_filter_taps.get(), tables.data(), tables.size() * sizeof(unsigned), hipMemcpyHostToDevice, s));
     const unsigned *wx = inv->clip_filter_taps.get<unsigned>(), *wy = wx + y_tables;
+    const ClipFilterTaps taps{grid_x, grid_y, reach, wx, wy};
+    const ClipRect rect{tg.region_x, tg.first_row, tg.region_w, tg.num_rows, halo.x0, halo.y0, halo.w, halo.rows, render_w, render_h};
     // the shutter's temporary: [frame][time step][grid point] maps of the haloed rectangle, the carry map of the output
     // rectangle (smaller than a map) behind them; whatever still reads a smaller one has finished before it is freed
     const size_t slots = (size_t)plan.per_batch * plan.steps_per_pass * grid;
@@ -884,11 +888,8 @@ int mmhip_render_clip_filtered(mmhip_invocation *inv, int num_frames, const int 
                 }
             const bool last = j0 + count >= samples;
             std::string err;
-            if (launch_filter_combine_clip(subs, (int64_t)bps, (int64_t)count * grid * (int64_t)bps, count, grid_x, grid_y, reach, wx, wy,
-                                           j0 > 0 ? carry : nullptr, last ? nullptr : carry, (char *)tg.out + (int64_t)b0 * tg.frame_stride,
-                                           tg.region_x, tg.first_row, tg.region_w, tg.num_rows, halo.x0, halo.y0, halo.w, halo.rows, render_w,
-                                           render_h, tg.row_stride, tg.frame_stride, tg.bpp, tg.floatmap, inv_k, n, inv->ws, s, &err) != 0)
-                return fail(err);
+            const ClipSamples in{subs, (int64_t)bps, (int64_t)count * grid * (int64_t)bps, count, j0 > 0 ? carry : nullptr, last ? nullptr : carry};
+            if (launch_filter_combine_clip(in, taps, tg.from_frame(b0).store(), rect, inv_k, n, inv->ws, s, &err) != 0) return fail(err);
         }
         ++inv->clip_filtered_batches;
     }
@@ -1193,8 +1194,8 @@ int mmhip_render_clip_adaptive(mmhip_invocation *inv, int num_frames, const int 
         if (!plan.list_path && render_clip_maps(inv, batch, n, frames + b0, ts + b0, 1, 0.0f, grid_x, grid_y) != 0) return -1;
         HIP_TRY(hipMemsetAsync(counts + b0, 0, (size_t)n * sizeof(unsigned), s));
         std::string err;
-        if (launch_aa_contrast_clip(base, (int64_t)bps, batch.out, counts + b0, lists, (int64_t)plan.list_entries, tg.region_w, tg.num_rows,
-                                    inv->render_w, tg.row_stride, tg.frame_stride, tg.bpp, tg.floatmap, threshold, n, inv->ws, s, &err) != 0)
+        if (launch_aa_contrast_clip(base, (int64_t)bps, batch.store(), ClipRefined{counts + b0, lists, (int64_t)plan.list_entries}, tg.region_w,
+                                    tg.num_rows, inv->render_w, threshold, n, inv->ws, s, &err) != 0)
             return fail(err);
         if (plan.list_path && clip_adaptive_refine_batch(inv, f, plan, batch, n, frames + b0, ts + b0, grid_x, grid_y, lists, counts + b0) != 0)
             return -1;

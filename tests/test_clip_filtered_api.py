@@ -54,9 +54,9 @@ def test_entry_points_exist_and_are_declared():
     from mathmap_amd._lib import SELFTEST_SYMBOLS
     assert "mmhip_selftest_filter_combine" in SELFTEST_SYMBOLS
     csrc = os.path.join(ROOT, "mathmap_amd", "csrc")
-    assert "k_filter_combine_clip" in open(os.path.join(csrc, "native_filters.hip")).read()
-    assert "launch_filter_combine_clip" in open(os.path.join(csrc, "native_filters.h")).read()
-    for text in (open(os.path.join(csrc, "native_filters.hip")).read(), open(os.path.join(csrc, "runtime_clip.cpp")).read()):
+    assert "k_filter_combine_clip" in open(os.path.join(csrc, "clip_combine.hip")).read()
+    assert "launch_filter_combine_clip" in open(os.path.join(csrc, "clip_kernels.h")).read()
+    for text in (open(os.path.join(csrc, "clip_combine.hip")).read(), open(os.path.join(csrc, "runtime_clip.cpp")).read()):
         assert '#include "mm_clip_filter.h"' in text
 
 

@@ -307,7 +307,7 @@ def test_the_restatement_on_values_worked_out_by_hand():
 
 
 def test_the_kernel_includes_the_header_the_test_compiles():
-    text = open(os.path.join(ROOT, "mathmap_amd", "csrc", "native_filters.hip")).read()
+    text = open(os.path.join(ROOT, "mathmap_amd", "csrc", "clip_combine.hip")).read()
     assert '#include "mm_shutter_combine.h"' in text and "k_shutter_combine_clip" in text
     for fn in ("mm_shutter_add(", "mm_shutter_scale(", "mm_shutter_store_bytes("):
         assert fn in text, fn

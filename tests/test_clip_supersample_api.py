@@ -231,7 +231,7 @@ def test_word_arithmetic_is_the_per_byte_formula(sanitize):
 
 
 def test_the_kernel_includes_the_header_the_test_compiles():
-    text = open(os.path.join(ROOT, "mathmap_amd", "csrc", "native_filters.hip")).read()
+    text = open(os.path.join(ROOT, "mathmap_amd", "csrc", "clip_combine.hip")).read()
     assert '#include "mm_ss_combine.h"' in text and "mm_ss_combine_word(" in text and "k_supersample_combine_clip" in text
 
 

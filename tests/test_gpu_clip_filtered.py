@@ -290,6 +290,26 @@ def test_the_kernel_alone_on_maps_with_special_values(case):
         assert same_buffer(got, want, floatmap), (case, floatmap, bpp, row_pad, gap)
 
 
+def test_one_tap_of_weight_one_stores_what_the_shutter_combine_stores():
+    """The two kernels share one pixel store: the box at half a pixel over a 1 x 1 grid and one step is one tap of weight
+    1.0f and inv_k 1, the shutter combine of one sample is the sample times 1, so the buffers are equal byte for byte --
+    sentinels and the bits of a float map's NaNs included -- at every layout."""
+    maps = synthetic(2, 1, 1, 1, 13, 37, seed=7)
+    assert np.isnan(maps).any() and np.isinf(maps).any() and X.reach(0.5) == 0
+    frames, h, w = 2, 13, 37
+    samples = np.ascontiguousarray(maps.reshape(frames, 1, h, w, 4))
+    for floatmap, bpp, row_pad, gap in ((True, 4, 0, 32), (False, 4, 0, 0), (False, 4, 3, 7), (False, 3, 5, 11), (False, 2, 0, 1), (False, 1, 7, 0)):
+        filtered, lay = run_kernel(maps, "box", 0.5, None, bpp, floatmap, 0, row_pad, gap)
+        assert lay.lead % 2 == (1 if not floatmap and (bpp != 4 or row_pad) else 0)      # bpp 4 once aligned, once from an odd offset
+        combined = np.empty(lay.total, np.uint8)
+        rc = selftest_lib().mmhip_selftest_shutter_combine(samples.ctypes.data_as(C.c_void_p), frames, 1, h, w, w, bpp, 1 if floatmap else 0,
+                                                           lay.stride or 0, lay.fstride, 0, lay.lead, combined.ctypes.data_as(C.c_void_p),
+                                                           lay.total, SENTINEL, 0, None)
+        assert rc == 0, selftest_lib().mmhip_selftest_error().decode()
+        assert (filtered != SENTINEL).any() and (filtered[:lay.lead] == SENTINEL).all() and (filtered[-9:] == SENTINEL).all()
+        assert np.array_equal(filtered, combined), (floatmap, bpp, row_pad, gap)
+
+
 # ---- 6. call hygiene ----
 
 def test_the_callers_sampling_offset_is_put_back():

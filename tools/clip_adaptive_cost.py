@@ -14,7 +14,7 @@ Parts, each merged into the record at --out (stamped with --commit):
   --part registers  no GPU needed: per filter the VGPR and SGPR counts and .private_segment_fixed_size of
                     mm_pixels_refine beside those of mm_pixels_sampled, from the gfx950 assembly of both texts under the
                     JIT's options; and the same, with the LDS bytes, for every instance of k_aa_contrast_clip, from the
-                    assembly of csrc/native_filters.hip under the library's options.
+                    assembly of csrc/clip_combine.hip under the library's options.
 
     python tools/clip_adaptive_cost.py --part clip --out profiles/r15_clip_adaptive_cost.json --commit <sha>
     python tools/clip_adaptive_cost.py --part registers --out profiles/r15_clip_adaptive_cost.json --commit <sha>
@@ -126,13 +126,13 @@ def measure_registers(which):
 
 
 def mask_kernel_registers():
-    """Every instance of k_aa_contrast_clip in the assembly of native_filters.hip, compiled as the library compiles it."""
+    """Every instance of k_aa_contrast_clip in the assembly of clip_combine.hip, compiled as the library compiles it."""
     from pair_loop_isa import hipcc
     csrc = os.path.join(ROOT, "mathmap_amd", "csrc")
     with tempfile.TemporaryDirectory() as d:
-        asm = os.path.join(d, "native_filters.s")
+        asm = os.path.join(d, "clip_combine.s")
         cmd = [hipcc(), "-std=c++17", "-O2", "-I", csrc, "-I", os.path.join(ROOT, "include"), "--offload-arch=gfx950", "-ffp-contract=off",
-               "--cuda-device-only", "-S", "-o", asm, os.path.join(csrc, "native_filters.hip")]
+               "--cuda-device-only", "-S", "-o", asm, os.path.join(csrc, "clip_combine.hip")]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             sys.exit("compilation failed:\n" + r.stderr[-4000:])
@@ -175,7 +175,7 @@ def main():
             f.write("\n")
     if args.part == "registers":
         part = record.setdefault("registers", {})
-        part["taken"] = "without a GPU, from the gfx950 assembly of the generated texts under the JIT's options and of native_filters.hip under the library's"
+        part["taken"] = "without a GPU, from the gfx950 assembly of the generated texts under the JIT's options and of clip_combine.hip under the library's"
         part.setdefault("filters", {})
         for which in (args.cases.split(",") if args.cases else FILTERS):
             part["filters"][which.rstrip("+")] = measure_registers(which)
