@@ -702,6 +702,73 @@ int mmhip_clip_yuv_input_groups(mmhip_invocation *inv);
    interlaced stream; every other colour space (C422, C444, C420p10, Cmono, ...); a malformed F; a header without a
    newline within len.  Returns 0, or -1. */
 int mmhip_y4m_parse_header(const char *buf, int len, int *width, int *height, int *fps_num, int *fps_den, int *range, int *header_len);
+/* A clip as 10-bit planar Y'CbCr 4:2:0 (yuv420p10): converts num_frames float frames in device memory -- what every clip
+   entry point above but the supersampled one leaves with floatmap = 1 -- to the payloads of a YUV4MPEG2 file of colour
+   space C420p10, on the GPU (k_float_to_yuv420p10_clip, one launch), so that nothing the clip computed in float is lost to
+   an 8-bit store first.  Asynchronous on `stream` (0: the invocation's).  This statement is the specification:
+   tests/yuv10_reference.py restates it, mathmap_amd/csrc/mm_yuv.h holds it.
+     - Source: frames of width x height float4 RGBA pixels (16 bytes per pixel), of which the rows [first_row, last_row)
+       are converted.  src points at row first_row of frame 0; rows are src_row_stride bytes apart (at least 16 * width),
+       frames src_frame_stride; src and both strides are multiples of 4.  Alpha is not read.
+     - Per channel: c = CLAMP01(v) as the pixel store clamps (NaN and -0 give 0, +inf gives 1), then
+         q = (int)rintf(c * 65535.0f)
+       one float32 product rounded to nearest with ties to even: 0 .. 65535.  NumPy:
+       np.rint(np.float32(c) * np.float32(65535)).astype(np.int32).
+     - Arithmetic: from here on all int32, every >> an arithmetic shift of a signed value (a floor division).  Per pixel
+         Y = ((yr * R + yg * G + yb * B + 2^19) >> 20) + off
+       Per chroma sample (cx, cy), with Rs, Gs, Bs the sums of q over the four pixels (min(2 cx + i, width - 1), min(2 cy +
+       j, height - 1)), i, j in {0, 1} -- an odd last column or row is replicated; chroma is sited at the centre of the
+       block (the siting of C420jpeg) --
+         Cb = clamp(((cbr * Rs + cbg * Gs + cbb * Bs + 2^20) >> 21) + 512, 0, 1023)
+         Cr likewise with crr, crg, crb.
+     - Coefficients: from the standard's constants Kr, Kb (0.299, 0.114 for bt601; 0.2126, 0.0722 for bt709) and Kg = 1 -
+       Kr - Kb.  The luma row is k = (Kr, Kg, Kb); the Cb row (-Kr, -Kg, 1 - Kb) / (2 (1 - Kb)), the Cr row (1 - Kr, -Kg,
+       -Kb) / (2 (1 - Kr)).  With the channel in 0 .. 65535 the luma excursion E is 876 (limited, off 64) or 1023 (full, off
+       0) and the chroma excursion 896 or 1023.  A luma coefficient is floor(k * E / 65535 * 2^20 + 0.5), a chroma
+       coefficient sign(k) * floor(|k| * E / 65535 * 2^19 + 0.5).  The green coefficient of every row is not rounded by
+       itself: it makes the luma row sum to the rounded coefficient of k = 1 and each chroma row sum to 0 (white is Y 940
+       or 1023 exactly, black 64 or 0, every grey has chroma 512):
+         matrix, range    off   yr, yg, yb            cbr, cbg, cbb          crr, crg, crb
+         bt601 limited    64    4191, 8227, 1598      -1210, -2374, 3584     3584, -3001, -583
+         bt601 full       0     4894, 9608, 1866      -1381, -2711, 4092     4092, -3427, -665
+         bt709 limited    64    2980, 10024, 1012     -821, -2763, 3584      3584, -3255, -329
+         bt709 full       0     3480, 11706, 1182     -938, -3154, 4092      4092, -3717, -375
+       The largest luma intermediate is 1 073 201 168 and the chroma intermediates lie in [-1 072 676 880, 1 073 725 456]:
+       inside int32 with room to spare (at scale 2^20 the full-range chroma would end 32 736 below 2^31, hence 2^19).  Limited-range chroma stays in 64 ..
+       960 and full-range chroma in 1 .. 1023 without the clamp: pure blue and pure red, 1023.5 in the real formula,
+       give 1023 (4092 is rounded down), so the clamp is a guard no colour reaches.
+     - Destination: every frame is one contiguous payload of 16-bit little-endian samples with the value in the low 10
+       bits: the Y plane, width * height samples with rows `width` samples apart, then Cb, then Cr, each cw * ch samples
+       with cw = (width + 1) >> 1 and ch = (height + 1) >> 1, rows cw samples apart: 2 * (width * height + 2 * cw * ch)
+       bytes (mmhip_yuv420p10_frame_bytes).  Frames are dst_frame_stride bytes apart, even and at least the payload.  dst
+       (even) is the base of frame 0's whole-frame layout, for a row band too.
+     - A band writes the Y rows [first_row, last_row) and the chroma rows [first_row / 2, (last_row + 1) / 2) and nothing
+       else: no byte between frames, of other rows or behind the planes.  first_row must be even and last_row even or
+       equal to height; under these two rules bands converted separately give the bytes of a whole-frame call.
+     - The kernel has a path of aligned wide accesses (width a multiple of 8; src, both source strides, dst and
+       dst_frame_stride multiples of 16) and a path of per-pixel loads and 2-byte stores for everything else; the launcher
+       chooses, the bytes are the same.  mmhip_clip_float_to_yuv420p10_launches counts the launches of each.
+       MMHIP_YUV10_COLUMNS=4|8 (read per call, default 4) sets the columns a work-item of the aligned path converts,
+       MMHIP_YUV10_LOADS=cached|nt (read per call, default cached) plain or non-temporal loads.  Timed as yuv420p10_clip
+       (mmhip_drain_native_kernel_ms).
+   Errors, by name, in the wording of mmhip_clip_to_yuv420 where the condition is the same: width or height below 1;
+   num_frames below 1 or above 65 535; an unknown matrix or range; rows that are not rows of the frame; an odd first_row;
+   an odd last_row that is not height; null pointers; a src_row_stride below one row; a source pointer or stride that is
+   not a multiple of 4; a dst_frame_stride below one frame; an odd dst or dst_frame_stride; a Y plane or a source band of
+   more than 4 GiB (offsets inside a frame are 32-bit). */
+enum { MMHIP_YUV10_PATH_ALIGNED = 0, MMHIP_YUV10_PATH_BYTES = 1 };
+int mmhip_clip_float_to_yuv420p10(mmhip_invocation *inv, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width,
+                                  int height, int first_row, int last_row, int num_frames, int matrix, int range, void *dst,
+                                  int64_t dst_frame_stride, void *stream);
+/* 2 * (width * height + 2 * cw * ch): the bytes of one frame's 10-bit payload (needs no GPU).  -1 for a size below 1 x 1. */
+int64_t mmhip_yuv420p10_frame_bytes(int width, int height);
+/* The stream header of a YUV4MPEG2 file of such frames (needs no GPU): the line of mmhip_y4m_header with C420p10 in
+   place of C420jpeg, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420p10 XCOLORRANGE=LIMITED\n" (or FULL).  A frame in the file is
+   "FRAME\n" followed by one frame's payload.  Returns the header's length without the NUL, or -1. */
+int mmhip_y4m_header_p10(char *buf, int cap, int width, int height, int fps_num, int fps_den, int range);
+/* The converter's launches of this invocation on path MMHIP_YUV10_PATH_ALIGNED or MMHIP_YUV10_PATH_BYTES; -1 for another
+   path. */
+long mmhip_clip_float_to_yuv420p10_launches(mmhip_invocation *inv, int path);
 /* Convenience: whole frame to a host RGBA8 buffer (width*height*4 bytes); synchronous. */
 int mmhip_render_host(mmhip_invocation *inv, int frame, float t, uint8_t *out_rgba);
 int mmhip_sync(mmhip_invocation *inv);

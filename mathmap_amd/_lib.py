@@ -31,6 +31,8 @@ MMHIP_YUV_LIMITED, MMHIP_YUV_FULL = 0, 1
 # mmhip_clip_from_yuv420's chroma mode, and the paths mmhip_clip_from_yuv420_launches counts
 MMHIP_YUV_CHROMA_BILINEAR, MMHIP_YUV_CHROMA_REPLICATE = 0, 1
 MMHIP_YUV_IN_PATH_ALIGNED, MMHIP_YUV_IN_PATH_BYTES = 0, 1
+# the paths mmhip_clip_float_to_yuv420p10_launches counts
+MMHIP_YUV10_PATH_ALIGNED, MMHIP_YUV10_PATH_BYTES = 0, 1
 
 # every symbol include/mmhip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -150,6 +152,11 @@ SYMBOLS = {
                                                        C.c_int]),
     "mmhip_clip_yuv_input_groups": (C.c_int, [C.c_void_p]),
     "mmhip_y4m_parse_header": (C.c_int, [C.c_char_p, C.c_int] + [C.POINTER(C.c_int)] * 6),
+    "mmhip_clip_float_to_yuv420p10": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mmhip_yuv420p10_frame_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "mmhip_y4m_header_p10": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mmhip_clip_float_to_yuv420p10_launches": (C.c_long, [C.c_void_p, C.c_int]),
     "mmhip_render_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "mmhip_sync": (C.c_int, [C.c_void_p]),
     "mmhip_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),

@@ -45,8 +45,9 @@ AA_FILTER_RADII = {"box": 0.5, "tent": 1.0, "gaussian": 1.5, "mitchell": 2.0}
 AA_RADIUS_MIN, AA_RADIUS_MAX = 0.5, 4.0
 # mmhip_filter_clip_filtered_plan's out[]
 CLIP_FILTERED_PLAN_FIELDS = CLIP_SAMPLED_PLAN_FIELDS + ("halo_columns", "halo_rows")
-# render_clip's pixel_format, yuv_matrix and yuv_range: mmhip_clip_to_yuv420's modes
-PIXEL_FORMATS = ("yuv420p",)
+# render_clip's pixel_format, yuv_matrix and yuv_range: mmhip_clip_to_yuv420's modes; "yuv420p10" is
+# mmhip_clip_float_to_yuv420p10's 10-bit form, one uint16 per sample
+PIXEL_FORMATS = ("yuv420p", "yuv420p10")
 YUV_MATRICES = {"bt601": 0, "bt709": 1}
 YUV_RANGES = {"limited": 0, "full": 1}
 # set_image_yuv420's and clip_from_yuv420's chroma: mmhip_clip_from_yuv420's modes
@@ -118,23 +119,39 @@ def yuv_chroma(chroma):
     return YUV_CHROMAS[chroma]
 
 
-def yuv420_frame_bytes(w, h):
-    """The bytes of one w x h frame as planar 4:2:0 (mmhip_yuv420_frame_bytes): w * h + 2 * cw * ch.  Needs no GPU."""
-    n = lib().mmhip_yuv420_frame_bytes(int(w), int(h))
+def _pixel_format_of(who, buf, pixel_format):
+    """The format of the frames `buf`: `pixel_format` where given, else by the dtype (uint16: "yuv420p10").  ValueError for an
+    unknown name or a dtype the format does not have."""
+    if pixel_format is None:
+        pixel_format = "yuv420p10" if buf.dtype.kind == "u" and buf.dtype.itemsize == 2 else "yuv420p"
+    if pixel_format not in PIXEL_FORMATS:
+        raise ValueError("%s: pixel_format must be one of %s, not %r" % (who, ", ".join(PIXEL_FORMATS), pixel_format))
+    return pixel_format
+
+
+def yuv420_frame_bytes(w, h, pixel_format="yuv420p"):
+    """The bytes of one w x h frame as planar 4:2:0 (mmhip_yuv420_frame_bytes): w * h + 2 * cw * ch, and twice that for
+    `pixel_format`="yuv420p10" (mmhip_yuv420p10_frame_bytes).  Needs no GPU."""
+    if pixel_format not in PIXEL_FORMATS:
+        raise ValueError("yuv420_frame_bytes: pixel_format must be one of %s, not %r" % (", ".join(PIXEL_FORMATS), pixel_format))
+    n = (lib().mmhip_yuv420p10_frame_bytes if pixel_format == "yuv420p10" else lib().mmhip_yuv420_frame_bytes)(int(w), int(h))
     if n < 0:
         raise MathMapError(_err())
     return n
 
 
-def yuv420_planes(buf, w, h):
+def yuv420_planes(buf, w, h, pixel_format=None):
     """The planes of frames as render_clip(pixel_format="yuv420p") returns them: `buf` is uint8 [N, frame_bytes] (or one
-    frame, [frame_bytes]); returns the views (Y [N, h, w], Cb [N, ch, cw], Cr [N, ch, cw])."""
+    frame, [frame_bytes]); returns the views (Y [N, h, w], Cb [N, ch, cw], Cr [N, ch, cw]).  The frames of "yuv420p10" are
+    uint16 [N, frame_bytes / 2]: told by the dtype, or by `pixel_format`, which the dtype must then agree with."""
     buf = np.asarray(buf)
     if buf.ndim == 1:
         buf = buf[None]
     cw, ch = (w + 1) >> 1, (h + 1) >> 1
-    if buf.dtype != np.uint8 or buf.ndim != 2 or buf.shape[1] < w * h + 2 * cw * ch:
-        raise ValueError("yuv420_planes: uint8 [N, %d] for frames of %d x %d, not %s %r" % (w * h + 2 * cw * ch, w, h, buf.dtype, buf.shape))
+    dtype = np.uint16 if _pixel_format_of("yuv420_planes", buf, pixel_format) == "yuv420p10" else np.uint8
+    if buf.dtype.kind != "u" or buf.dtype.itemsize != np.dtype(dtype).itemsize or buf.ndim != 2 or buf.shape[1] < w * h + 2 * cw * ch:
+        raise ValueError("yuv420_planes: %s [N, %d] for frames of %d x %d, not %s %r"
+                         % (np.dtype(dtype).name, w * h + 2 * cw * ch, w, h, buf.dtype, buf.shape))
     n = buf.shape[0]
     y = buf[:, :w * h].reshape(n, h, w)
     cb = buf[:, w * h:w * h + cw * ch].reshape(n, ch, cw)
@@ -142,29 +159,39 @@ def yuv420_planes(buf, w, h):
     return y, cb, cr
 
 
-def y4m_header(w, h, fps=(25, 1), yuv_range="limited"):
-    """The stream header of a YUV4MPEG2 file (mmhip_y4m_header) as bytes.  Needs no GPU."""
+def y4m_header(w, h, fps=(25, 1), yuv_range="limited", pixel_format="yuv420p"):
+    """The stream header of a YUV4MPEG2 file (mmhip_y4m_header; for `pixel_format`="yuv420p10" mmhip_y4m_header_p10) as
+    bytes.  Needs no GPU."""
     if yuv_range not in YUV_RANGES:
         raise ValueError("yuv_range must be one of %s, not %r" % (", ".join(YUV_RANGES), yuv_range))
+    if pixel_format not in PIXEL_FORMATS:
+        raise ValueError("y4m_header: pixel_format must be one of %s, not %r" % (", ".join(PIXEL_FORMATS), pixel_format))
     num, den = (fps, 1) if isinstance(fps, (int, np.integer)) else fps
     line = C.create_string_buffer(160)
-    n = lib().mmhip_y4m_header(line, 160, int(w), int(h), int(num), int(den), YUV_RANGES[yuv_range])
+    header = lib().mmhip_y4m_header_p10 if pixel_format == "yuv420p10" else lib().mmhip_y4m_header
+    n = header(line, 160, int(w), int(h), int(num), int(den), YUV_RANGES[yuv_range])
     if n < 0:
         raise MathMapError(_err())
     return line.raw[:n]
 
 
-def write_y4m(path_or_file, buf, w, h, fps=(25, 1), yuv_range="limited"):
+def write_y4m(path_or_file, buf, w, h, fps=(25, 1), yuv_range="limited", pixel_format=None):
     """Writes frames as render_clip(pixel_format="yuv420p") returns them (uint8 [N, frame_bytes]) as one YUV4MPEG2 file:
     the header, then "FRAME\\n" and the payload per frame.  `path_or_file`: a file name, or a binary file object (which
-    stays open).  `fps` = n or (n, d).  The colour matrix has no place in the format: tell the encoder."""
-    frame_bytes = yuv420_frame_bytes(w, h)
+    stays open).  `fps` = n or (n, d).  The colour matrix has no place in the format: tell the encoder.  The frames of
+    "yuv420p10" (uint16 [N, frame_bytes / 2], told by the dtype or by `pixel_format`) go out as C420p10, every sample as
+    two bytes, the low one first."""
     buf = np.asarray(buf)
     if buf.ndim == 1:
         buf = buf[None]
-    if buf.dtype != np.uint8 or buf.ndim != 2 or buf.shape[1] != frame_bytes:
-        raise ValueError("write_y4m: uint8 [N, %d] for frames of %d x %d, not %s %r" % (frame_bytes, w, h, buf.dtype, buf.shape))
-    header = y4m_header(w, h, fps, yuv_range)
+    pixel_format = _pixel_format_of("write_y4m", buf, pixel_format)
+    dtype = np.uint16 if pixel_format == "yuv420p10" else np.uint8
+    samples = yuv420_frame_bytes(w, h)
+    if buf.dtype.kind != "u" or buf.dtype.itemsize != np.dtype(dtype).itemsize or buf.ndim != 2 or buf.shape[1] != samples:
+        raise ValueError("write_y4m: %s [N, %d] for frames of %d x %d, not %s %r" % (np.dtype(dtype).name, samples, w, h, buf.dtype, buf.shape))
+    if dtype == np.uint16:
+        buf = buf.astype("<u2", copy=False)
+    header = y4m_header(w, h, fps, yuv_range, pixel_format)
     f = open(path_or_file, "wb") if isinstance(path_or_file, (str, bytes)) or hasattr(path_or_file, "__fspath__") else path_or_file
     try:
         f.write(header)
@@ -750,7 +777,12 @@ class Invocation:
         frame (yuv420_planes, write_y4m); with it the payloads land there, yuv420_frame_bytes apart, and nothing is
         copied to the host (the staging buffer's release waits for the device).  `rows` must begin on an even row and end
         on an even row or the last.  `floatmap`, another `bpp`, `region`, `row_stride` or `frame_stride` with it, or an
-        unknown format, matrix or range, is a ValueError."""
+        unknown format, matrix or range, is a ValueError.
+        `pixel_format`="yuv420p10" delivers 10-bit samples converted from the float pixels, before any 8-bit store
+        (mmhip_clip_float_to_yuv420p10): the groups are rendered with floatmap=True into a float staging buffer, 16 bytes
+        per pixel under the same budget, and converted there.  Without `out_ptr` returns uint16 [N, frame_bytes / 2]
+        (little-endian, the value in the low 10 bits); with it the payloads land yuv420_frame_bytes(w, h, "yuv420p10")
+        apart.  Everything else as with "yuv420p"; `supersample`=True with it is a ValueError (that path lands bytes)."""
         from .striping import animation_frame_t
         if pixel_format is not None:
             keywords = dict(num_frames=num_frames, frames=frames, ts=ts, supersample=supersample, shutter_samples=shutter_samples,
@@ -762,7 +794,9 @@ class Invocation:
                                 ("frame_stride", frame_stride is not None)):
                 if given:
                     raise ValueError("render_clip: pixel_format is not combined with %s: whole RGBA8 frames are converted" % name)
-            return self._render_clip_yuv420(yuv_mode(yuv_matrix, yuv_range), out_ptr, rows, stream, keywords)
+            if pixel_format == "yuv420p10" and supersample:
+                raise ValueError("render_clip: pixel_format=\"yuv420p10\" is not combined with supersample=True: that path lands bytes only")
+            return self._render_clip_yuv420(yuv_mode(yuv_matrix, yuv_range), out_ptr, rows, stream, keywords, pixel_format)
         grid = sample_grid(aa)
         filtered = aa_filter is not None
         if aa_radius is not None and not filtered:
@@ -913,8 +947,35 @@ class Invocation:
         self._check(lib().mmhip_clip_from_yuv420(self._h, C.c_void_p(src_ptr), src_frame_stride, w, h, int(num_frames), matrix, rng, mode,
                                                  C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
 
-    def _render_clip_yuv420(self, mode, out_ptr, rows, stream, keywords):
-        """render_clip(pixel_format="yuv420p"): the clip of `keywords` in groups of frames through an RGBA8 staging buffer."""
+    def clip_float_to_yuv420p10(self, src_ptr, dst_ptr, num_frames, width=None, height=None, rows=None, src_row_stride=None,
+                                src_frame_stride=None, dst_frame_stride=None, yuv_matrix="bt709", yuv_range="limited", stream=0):
+        """Converts float frames in device memory (float4 RGBA, what floatmap=True lands) to 10-bit planar Y'CbCr 4:2:0
+        payloads in device memory (mmhip_clip_float_to_yuv420p10), asynchronously.  The arguments are clip_to_yuv420's:
+        rows are `src_row_stride` bytes apart (default 16 * width), frames `src_frame_stride` (default: the band's rows),
+        payloads `dst_frame_stride` (default yuv420_frame_bytes(w, h, "yuv420p10")).  The size defaults to the render
+        size."""
+        matrix, rng = yuv_mode(yuv_matrix, yuv_range)
+        w = self.render_width if width is None else int(width)
+        h = self.render_height if height is None else int(height)
+        first_row, last_row = rows if rows is not None else (0, h)
+        if src_row_stride is None:
+            src_row_stride = 16 * w
+        if src_frame_stride is None:
+            src_frame_stride = max(last_row - first_row, 0) * src_row_stride
+        if dst_frame_stride is None:
+            dst_frame_stride = 2 * (w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1))
+        self._check(lib().mmhip_clip_float_to_yuv420p10(self._h, C.c_void_p(src_ptr), src_row_stride, src_frame_stride, w, h, first_row, last_row,
+                                                        int(num_frames), matrix, rng, C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
+
+    def clip_float_to_yuv420p10_launches(self, path):
+        """The launches of clip_float_to_yuv420p10's kernel on `path`: "aligned" or "bytes" (mmhip_clip_float_to_yuv420p10_launches)."""
+        if path not in ("aligned", "bytes"):
+            raise ValueError("clip_float_to_yuv420p10_launches: path must be \"aligned\" or \"bytes\", not %r" % (path,))
+        return lib().mmhip_clip_float_to_yuv420p10_launches(self._h, 0 if path == "aligned" else 1)
+
+    def _render_clip_yuv420(self, mode, out_ptr, rows, stream, keywords, pixel_format="yuv420p"):
+        """render_clip(pixel_format="yuv420p"): the clip of `keywords` in groups of frames through an RGBA8 staging buffer;
+        with "yuv420p10" through a staging buffer of float maps."""
         import os
         from .striping import animation_frame_t
         matrix, rng = mode
@@ -955,8 +1016,11 @@ class Invocation:
             if rows is not None:
                 raise MathMapError("render_clip without out_ptr returns whole frames: pass out_ptr for bands")
             stream = 0      # the invocation's, which the copy waits for
-        frame_bytes = yuv420_frame_bytes(w, h)
-        band_bytes = (last_row - first_row) * w * 4
+        deep = pixel_format == "yuv420p10"
+        frame_bytes = yuv420_frame_bytes(w, h, pixel_format)
+        pixel_bytes = 16 if deep else 4
+        band_bytes = (last_row - first_row) * w * pixel_bytes
+        convert = lib().mmhip_clip_float_to_yuv420p10 if deep else lib().mmhip_clip_to_yuv420
         try:
             budget = int(os.environ.get("MMHIP_CLIP_YUV_BYTES", "") or 0)
         except ValueError:
@@ -970,17 +1034,16 @@ class Invocation:
             raise MathMapError(_err())
         try:
             if out_ptr is None:
-                out = np.empty((num_frames, frame_bytes), dtype=np.uint8)
+                out = np.empty((num_frames, frame_bytes // 2), dtype="<u2") if deep else np.empty((num_frames, frame_bytes), dtype=np.uint8)
                 dst = lib().mmhip_device_alloc(out.nbytes)
                 if not dst:
                     raise MathMapError(_err())
             for g0 in range(0, num_frames, per_group):
                 n = min(per_group, num_frames - g0)
                 self.render_clip(frames=frames[g0:g0 + n], ts=ts[g0:g0 + n], out_ptr=staging, rows=rows, stream=stream,
-                                 shutter_span=shutter_span, **keywords)
-                self._check(lib().mmhip_clip_to_yuv420(self._h, C.c_void_p(staging), w * 4, band_bytes, w, h, first_row, last_row, n, matrix, rng,
-                                                       C.c_void_p((dst if out_ptr is None else out_ptr) + g0 * frame_bytes), frame_bytes,
-                                                       C.c_void_p(stream)))
+                                 shutter_span=shutter_span, floatmap=deep, **keywords)
+                self._check(convert(self._h, C.c_void_p(staging), w * pixel_bytes, band_bytes, w, h, first_row, last_row, n, matrix, rng,
+                                    C.c_void_p((dst if out_ptr is None else out_ptr) + g0 * frame_bytes), frame_bytes, C.c_void_p(stream)))
             if out_ptr is None:
                 self.sync()
                 self._check(lib().mmhip_copy_to_host(out.ctypes.data_as(C.c_void_p), C.c_void_p(dst), out.nbytes))

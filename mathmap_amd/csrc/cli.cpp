@@ -107,6 +107,12 @@ void usage() {
            "                              or full (0-255)\n"
            "      --fps=N[:D]             with a .y4m output: the frame rate N/D written\n"
            "                              to the header (default 25)\n"
+           "      --pixel-format=FORMAT   with a .y4m output: yuv420p (default, 8-bit\n"
+           "                              samples converted from the RGBA8 frames) or\n"
+           "                              yuv420p10 (C420p10: 10-bit samples in 16-bit\n"
+           "                              little-endian words, converted from the float\n"
+           "                              pixels before any 8-bit store; Y 64-940 at\n"
+           "                              limited range); yuv420p10 is not combined with -o\n"
            "  -D<name>=FILE.y4m           an input image whose file name ends in .y4m, or is -\n"
            "                              (standard input, for one image at most), is a\n"
            "                              YUV4MPEG2 stream of 8-bit 4:2:0 frames: all its\n"
@@ -322,7 +328,7 @@ enum {
     OPT_VERSION = 256, OPT_HELP, OPT_HTMLDOC, OPT_BENCH_NO_OUTPUT, OPT_BENCH_ONLY_COMPILE,
     OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE, OPT_INPUT_FRAMES, OPT_BATCH_FRAMES,
     OPT_NATIVE_INPUT_FRAME, OPT_SHUTTER_SAMPLES, OPT_SHUTTER, OPT_SHUTTER_MODE, OPT_AA, OPT_AA_THRESHOLD, OPT_AA_REFINE, OPT_AA_FILTER,
-    OPT_YUV_MATRIX, OPT_YUV_RANGE, OPT_FPS, OPT_INPUT_YUV_MATRIX, OPT_INPUT_YUV_RANGE, OPT_INPUT_CHROMA
+    OPT_YUV_MATRIX, OPT_YUV_RANGE, OPT_FPS, OPT_INPUT_YUV_MATRIX, OPT_INPUT_YUV_RANGE, OPT_INPUT_CHROMA, OPT_PIXEL_FORMAT
 };
 
 int main(int argc, char **argv) {
@@ -340,6 +346,7 @@ int main(int argc, char **argv) {
     float aa_radius = 0.5f;
     int yuv_matrix = MMHIP_YUV_BT709, yuv_range = MMHIP_YUV_LIMITED, fps_num = 25, fps_den = 1;      // quicktime_set_video(..., 25, ...), mathmap_cmdline.c:817-863
     bool yuv_options = false, batch_frames_set = false;
+    bool pixel_format_set = false, deep = false;      // --pixel-format, and whether it is yuv420p10
     int input_yuv_matrix = MMHIP_YUV_BT709, input_yuv_range = -1, input_chroma = MMHIP_YUV_CHROMA_BILINEAR;      // -1: the stream's, else limited
     bool input_yuv_options = false, frames_set = false, fps_set = false;
     const char *generator = nullptr;
@@ -363,7 +370,7 @@ int main(int argc, char **argv) {
         {"aa-filter", required_argument, 0, OPT_AA_FILTER}, {"yuv-matrix", required_argument, 0, OPT_YUV_MATRIX},
         {"yuv-range", required_argument, 0, OPT_YUV_RANGE}, {"fps", required_argument, 0, OPT_FPS},
         {"input-yuv-matrix", required_argument, 0, OPT_INPUT_YUV_MATRIX}, {"input-yuv-range", required_argument, 0, OPT_INPUT_YUV_RANGE},
-        {"input-chroma", required_argument, 0, OPT_INPUT_CHROMA},
+        {"input-chroma", required_argument, 0, OPT_INPUT_CHROMA}, {"pixel-format", required_argument, 0, OPT_PIXEL_FORMAT},
         {0, 0, 0, 0}};
     for (;;) {
         int idx;
@@ -464,6 +471,12 @@ int main(int argc, char **argv) {
                 fps_set = true;
                 break;
             }
+            case OPT_PIXEL_FORMAT:
+                if (!strcmp(optarg, "yuv420p")) deep = false;
+                else if (!strcmp(optarg, "yuv420p10")) deep = true;
+                else { fprintf(stderr, "Error: --pixel-format takes yuv420p or yuv420p10.\n"); return 1; }
+                pixel_format_set = true;
+                break;
             case OPT_INPUT_YUV_MATRIX:
                 if (!strcmp(optarg, "bt601")) input_yuv_matrix = MMHIP_YUV_BT601;
                 else if (!strcmp(optarg, "bt709")) input_yuv_matrix = MMHIP_YUV_BT709;
@@ -618,6 +631,14 @@ int main(int argc, char **argv) {
     const bool y4m = to_stdout || (name_len >= 4 && !strcmp(output_filename + name_len - 4, ".y4m"));
     if (yuv_options && !y4m) {
         fprintf(stderr, "Error: --yuv-matrix, --yuv-range and --fps go with an output file name ending in .y4m (or -).\n");
+        return 1;
+    }
+    if (pixel_format_set && !y4m) {
+        fprintf(stderr, "Error: --pixel-format goes with an output file name ending in .y4m (or -).\n");
+        return 1;
+    }
+    if (deep && supersampling) {
+        fprintf(stderr, "Error: --pixel-format=yuv420p10 is not combined with -o: supersampled frames are bytes.\n");
         return 1;
     }
     if (htmldoc) { fprintf(stderr, "Error: --htmldoc is not supported by the HIP command line.\n"); return 1; }
@@ -790,10 +811,14 @@ int main(int argc, char **argv) {
     // over in one copy, and each goes to the file behind "FRAME\n".  Without --batch-frames a batch is what fits in the
     // 1 GiB of RGBA8 staging.
     if (y4m && !batch_frames_set) batch_frames = 65535;
-    batch_frames = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch_frames, num_frames), ((size_t)1 << 30) / output.size()));
-    void *dev = mmhip_device_alloc(output.size() * batch_frames);
+    // --pixel-format=yuv420p10: the batches land as float maps, 16 bytes per pixel, and mmhip_clip_float_to_yuv420p10
+    // converts those.
+    const size_t landed_frame = deep ? output.size() * 4 : output.size();
+    const int landed_floatmap = deep ? 1 : 0;
+    batch_frames = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch_frames, num_frames), ((size_t)1 << 30) / landed_frame));
+    void *dev = mmhip_device_alloc(landed_frame * batch_frames);
     if (!dev) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
-    const size_t yuv_frame = y4m ? (size_t)mmhip_yuv420_frame_bytes(img_width, img_height) : 0;
+    const size_t yuv_frame = !y4m ? 0 : (size_t)(deep ? mmhip_yuv420p10_frame_bytes(img_width, img_height) : mmhip_yuv420_frame_bytes(img_width, img_height));
     void *yuv_dev = nullptr;
     std::vector<unsigned char> yuv_host;
     FILE *movie = nullptr;
@@ -802,7 +827,7 @@ int main(int argc, char **argv) {
         if (!yuv_dev) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
         yuv_host.resize(yuv_frame * batch_frames);
         char header[160];
-        const int header_len = mmhip_y4m_header(header, sizeof header, img_width, img_height, fps_num, fps_den, yuv_range);
+        const int header_len = (deep ? mmhip_y4m_header_p10 : mmhip_y4m_header)(header, sizeof header, img_width, img_height, fps_num, fps_den, yuv_range);
         if (header_len < 0) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
         if (!bench_no_output) {
             movie = to_stdout ? stdout : fopen(output_filename, "wb");
@@ -825,26 +850,28 @@ int main(int argc, char **argv) {
             const int rc = filtered
                                ? mmhip_render_clip_filtered(inv, n, frames.data(), ts.data(), shutter_samples, shutter_span, aa_x, aa_y, aa_kernel,
                                                             aa_radius, 0, 0, img_width, img_height, 0, img_height, dev, img_width * 4,
-                                                            (int64_t)output.size(), 4, 0, nullptr)
+                                                            (int64_t)landed_frame, 4, landed_floatmap, nullptr)
                            : adaptive
                                ? mmhip_render_clip_adaptive(inv, n, frames.data(), ts.data(), aa_x, aa_y, aa_threshold, aa_refine, 0, 0, img_width,
-                                                            img_height, 0, img_height, dev, img_width * 4, (int64_t)output.size(), 4, 0, nullptr)
+                                                            img_height, 0, img_height, dev, img_width * 4, (int64_t)landed_frame, 4, landed_floatmap, nullptr)
                            : sampled
                                ? (shutter_fused ? mmhip_render_clip_sampled_fused : mmhip_render_clip_sampled)(
                                      inv, n, frames.data(), ts.data(), shutter_samples, shutter_span, aa_x, aa_y, 0, 0, img_width, img_height, 0,
-                                     img_height, dev, img_width * 4, (int64_t)output.size(), 4, 0, nullptr)
+                                     img_height, dev, img_width * 4, (int64_t)landed_frame, 4, landed_floatmap, nullptr)
                            : shuttered
                                ? (shutter_fused ? mmhip_render_clip_shutter_fused : mmhip_render_clip_shutter)(
                                      inv, n, frames.data(), ts.data(), shutter_samples, shutter_span, 0, 0, img_width, img_height, 0, img_height,
-                                     dev, img_width * 4, (int64_t)output.size(), 4, 0, nullptr)
+                                     dev, img_width * 4, (int64_t)landed_frame, 4, landed_floatmap, nullptr)
                            : supersampling
                                ? mmhip_render_clip_supersampled(inv, n, frames.data(), ts.data(), 0, 0, img_width, img_height, dev,
                                                                 img_width * 4, (int64_t)output.size(), 4, nullptr)
                                : mmhip_render_clip(inv, n, frames.data(), ts.data(), 0, 0, img_width, img_height, 0, img_height, dev,
-                                                   img_width * 4, (int64_t)output.size(), 4, 0, nullptr);
+                                                   img_width * 4, (int64_t)landed_frame, 4, landed_floatmap, nullptr);
             if (rc != 0 ||
-                (y4m && mmhip_clip_to_yuv420(inv, dev, (int64_t)img_width * 4, (int64_t)output.size(), img_width, img_height, 0, img_height, n,
-                                             yuv_matrix, yuv_range, yuv_dev, (int64_t)yuv_frame, nullptr) != 0) ||
+                (y4m && !deep && mmhip_clip_to_yuv420(inv, dev, (int64_t)img_width * 4, (int64_t)output.size(), img_width, img_height, 0, img_height, n,
+                                                      yuv_matrix, yuv_range, yuv_dev, (int64_t)yuv_frame, nullptr) != 0) ||
+                (deep && mmhip_clip_float_to_yuv420p10(inv, dev, (int64_t)img_width * 16, (int64_t)landed_frame, img_width, img_height, 0, img_height, n,
+                                                       yuv_matrix, yuv_range, yuv_dev, (int64_t)yuv_frame, nullptr) != 0) ||
                 mmhip_sync(inv) != 0) {
                 fprintf(stderr, "Error: %s\n", mmhip_last_error());
                 return 1;

@@ -1,5 +1,5 @@
 // Launchers of the hand-written kernels that finish a clip or convert its frames: the combines, the contrast mask and the
-// reconstruction filter (clip_combine.hip), Y'CbCr 4:2:0 out (clip_yuv.hip) and in (clip_yuv_in.hip).
+// reconstruction filter (clip_combine.hip), Y'CbCr 4:2:0 out (clip_yuv.hip, 10-bit from float frames: clip_yuv10.hip) and in (clip_yuv_in.hip).
 #pragma once
 #include "native_filters.h"      // NativeWorkspace
 
@@ -100,5 +100,17 @@ int check_yuv420_to_rgba_clip(const void *src, int64_t src_frame_stride, int wid
                               const void *dst, int64_t dst_frame_stride, std::string *err);
 int launch_yuv420_to_rgba_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
                                void *dst, int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err);
+// Float frames of a clip (float4 RGBA, what floatmap = 1 lands) to planar Y'CbCr 4:2:0 with 10-bit samples in 16-bit
+// words in one launch (k_float_to_yuv420p10_clip, clip_yuv10.hip; mmhip_clip_float_to_yuv420p10 states the semantics and
+// its parameters are these, mm_yuv.h holds the arithmetic).  The launcher takes the path of aligned wide accesses (*path =
+// 0) where the width is a multiple of 8 and src, both source strides, dst and dst_frame_stride are multiples of 16, else
+// the path of per-pixel loads and 2-byte stores (*path = 1): the same samples.  Refused, by name, in `err` (the check
+// alone needs no GPU): what check_rgba8_to_yuv420_clip refuses, a source pointer or stride that is no multiple of 4, an
+// odd dst or dst_frame_stride.  Timed through ws.timed_launch as yuv420p10_clip.
+int check_float_to_yuv420p10_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
+                                  int last_row, int frames, int matrix, int range, const void *dst, int64_t dst_frame_stride, std::string *err);
+int launch_float_to_yuv420p10_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
+                                   int last_row, int frames, int matrix, int range, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws,
+                                   hipStream_t s, int *path, std::string *err);
 
 }  // namespace mm

@@ -155,3 +155,78 @@ inline void mm_yuv_to_rgba_frame_host(const mm_yuv_rgba_mode &m, int chroma, con
             dst[(int64_t)y * width + x] = mm_yuv_to_rgba(m, src[(int64_t)y * width + x], u, v);
         }
 }
+
+// ---- 10-bit output from float frames: float4 RGBA pixels to planar Y'CbCr 4:2:0 with 16-bit little-endian samples, the
+// value in the low 10 bits (k_float_to_yuv420p10_clip, clip_yuv10.hip; the semantics are stated at
+// mmhip_clip_float_to_yuv420p10 in include/mmhip.h) ----
+
+// One mode over channels quantised to 0 .. 65535: Y = ((yr R + yg G + yb B + 2^19) >> 20) + off; a chroma sample is
+// clamp(((k . sums of the 2 x 2 block) + 2^20) >> 21) + 512.  A luma coefficient is floor(k * E / 65535 * 2^20 + 0.5) with
+// the excursion E = 876 (limited) or 1023 (full), a chroma coefficient sign(k) floor(|k| * E / 65535 * 2^19 + 0.5) with
+// E = 896 or 1023; the green coefficient of every row makes the row sum exactly (luma: the coefficient of k = 1, chroma:
+// 0), so white is 940 or 1023 and grey has chroma 512.  Chroma is at scale 2^19 because at 2^20 the full-range sums of four
+// pixels would end 32 736 below 2^31.
+static const mm_yuv_mode MM_YUV10_MODES[MM_YUV_MATRICES][MM_YUV_RANGES] = {
+    {{64, 4191, 8227, 1598, -1210, -2374, 3584, 3584, -3001, -583},      // bt601 limited
+     {0, 4894, 9608, 1866, -1381, -2711, 4092, 4092, -3427, -665}},      // bt601 full
+    {{64, 2980, 10024, 1012, -821, -2763, 3584, 3584, -3255, -329},      // bt709 limited
+     {0, 3480, 11706, 1182, -938, -3154, 4092, 4092, -3717, -375}},      // bt709 full
+};
+
+// One channel: CLAMP01 as the pixel store sees it (NaN and -0 give 0), one float32 product, rounded to nearest with ties
+// to even: 0 .. 65535.  The device spells the two operations with intrinsics the compiler neither contracts nor
+// reassociates; the host's product is a single float32 multiplication and rintf rounds in the default mode.
+MM_YUV_FN int mm_yuv10_quant(float v) {
+    const float c = !(v > 0.0f) ? 0.0f : (v > 1.0f ? 1.0f : v);
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __float2int_rn(__fmul_rn(c, 65535.0f));
+#else
+    volatile float p = c * 65535.0f;
+    return (int)__builtin_rintf(p);
+#endif
+}
+
+// The luma of one pixel: 64 .. 940 or 0 .. 1023 by construction, no clamp.  The largest intermediate is 1 073 201 168.
+MM_YUV_FN int mm_yuv10_luma(const mm_yuv_mode &m, int r, int g, int b) { return ((m.yr * r + m.yg * g + m.yb * b + (1 << 19)) >> 20) + m.off; }
+
+// One chroma sample from the sums of its block's four pixels.  The intermediates lie in [-1 072 676 880, 1 073 725 456],
+// so the sample lies in 1 .. 1023 before the clamp (pure blue and pure red at full range, 1023.5 in the real formula, give
+// 1023): the clamp is a guard no colour reaches.
+MM_YUV_FN int mm_yuv10_chroma(int kr, int kg, int kb, int rs, int gs, int bs) {
+    const int c = ((kr * rs + kg * gs + kb * bs + (1 << 20)) >> 21) + 512;
+    return c < 0 ? 0 : c > 1023 ? 1023 : c;
+}
+MM_YUV_FN int mm_yuv10_cb(const mm_yuv_mode &m, int rs, int gs, int bs) { return mm_yuv10_chroma(m.cbr, m.cbg, m.cbb, rs, gs, bs); }
+MM_YUV_FN int mm_yuv10_cr(const mm_yuv_mode &m, int rs, int gs, int bs) { return mm_yuv10_chroma(m.crr, m.crg, m.crb, rs, gs, bs); }
+
+// A frame: the planes of mm_yuv_frame_bytes with two bytes per sample; the plane offsets of mm_yuv_cb_offset and
+// mm_yuv_cr_offset count samples.
+MM_YUV_FN int64_t mm_yuv10_frame_bytes(int width, int height) { return 2 * mm_yuv_frame_bytes(width, height); }
+
+// A whole frame on the host, as the kernel converts it: src is height rows of width float4 RGBA pixels row_stride bytes
+// apart (alpha is not read), dst one frame of mm_yuv10_frame_bytes / 2 samples.  An odd last column or row is
+// replicated.
+inline void mm_yuv10_frame_host(const mm_yuv_mode &m, const float *src, int64_t row_stride, int width, int height, uint16_t *dst) {
+    const int cw = mm_yuv_cw(width), ch = mm_yuv_ch(height);
+    uint16_t *cb = dst + mm_yuv_cb_offset(width, height), *cr = dst + mm_yuv_cr_offset(width, height);
+    auto pixel = [&](int r, int c) { return (const float *)((const char *)src + r * row_stride) + (int64_t)c * 4; };
+    for (int r = 0; r < height; ++r)
+        for (int c = 0; c < width; ++c) {
+            const float *p = pixel(r, c);
+            dst[(int64_t)r * width + c] = (uint16_t)mm_yuv10_luma(m, mm_yuv10_quant(p[0]), mm_yuv10_quant(p[1]), mm_yuv10_quant(p[2]));
+        }
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            int rs = 0, gs = 0, bs = 0;
+            for (int j = 0; j < 2; ++j)
+                for (int i = 0; i < 2; ++i) {
+                    const int c = 2 * cx + i < width ? 2 * cx + i : width - 1, r = 2 * cy + j < height ? 2 * cy + j : height - 1;
+                    const float *p = pixel(r, c);
+                    rs += mm_yuv10_quant(p[0]);
+                    gs += mm_yuv10_quant(p[1]);
+                    bs += mm_yuv10_quant(p[2]);
+                }
+            cb[(int64_t)cy * cw + cx] = (uint16_t)mm_yuv10_cb(m, rs, gs, bs);
+            cr[(int64_t)cy * cw + cx] = (uint16_t)mm_yuv10_cr(m, rs, gs, bs);
+        }
+}

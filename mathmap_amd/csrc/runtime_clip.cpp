@@ -1240,6 +1240,50 @@ int mmhip_clip_to_yuv420(mmhip_invocation *inv, const void *src_rgba, int64_t sr
     return 0;
 }
 
+// ---- clips as 10-bit planar Y'CbCr 4:2:0 (mmhip_clip_float_to_yuv420p10): float frames in HBM to Y4M payloads in HBM ----
+int64_t mmhip_yuv420p10_frame_bytes(int width, int height) {
+    if (width < 1 || height < 1) return fail("yuv420p10_frame_bytes: width and height must be at least 1");
+    return mm_yuv10_frame_bytes(width, height);
+}
+
+int mmhip_y4m_header_p10(char *buf, int cap, int width, int height, int fps_num, int fps_den, int range) {
+    if (width < 1 || height < 1) return fail("y4m_header_p10: width and height must be at least 1");
+    if (fps_num < 1 || fps_den < 1) return fail("y4m_header_p10: fps_num and fps_den must be at least 1");
+    if (range != MMHIP_YUV_LIMITED && range != MMHIP_YUV_FULL)
+        return fail("y4m_header_p10: range must be MMHIP_YUV_LIMITED or MMHIP_YUV_FULL (0 or 1), not " + std::to_string(range));
+    char line[160];
+    const int n = snprintf(line, sizeof line, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420p10 XCOLORRANGE=%s\n", width, height, fps_num, fps_den,
+                           range == MMHIP_YUV_FULL ? "FULL" : "LIMITED");
+    if (!buf || cap < n + 1)
+        return fail("y4m_header_p10: the buffer holds " + std::to_string(buf ? cap : 0) + " bytes, the header needs " + std::to_string(n + 1));
+    memcpy(buf, line, (size_t)n + 1);
+    return n;
+}
+
+int mmhip_clip_float_to_yuv420p10(mmhip_invocation *inv, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
+                                  int first_row, int last_row, int num_frames, int matrix, int range, void *dst, int64_t dst_frame_stride,
+                                  void *stream) {
+    std::string err;
+    if (check_float_to_yuv420p10_clip(src, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix, range, dst,
+                                      dst_frame_stride, &err) != 0)
+        return fail(err);
+    if (!inv) return fail("clip_float_to_yuv420p10: no invocation");
+    hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)inv->stream;
+    int path = 0;
+    if (launch_float_to_yuv420p10_clip(src, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix, range, dst,
+                                       dst_frame_stride, inv->ws, s, &path, &err) != 0)
+        return fail(err);
+    ++inv->clip_yuv10_launches[path];
+    return 0;
+}
+
+long mmhip_clip_float_to_yuv420p10_launches(mmhip_invocation *inv, int path) {
+    if (path != MMHIP_YUV10_PATH_ALIGNED && path != MMHIP_YUV10_PATH_BYTES)
+        return fail("clip_float_to_yuv420p10_launches: path must be MMHIP_YUV10_PATH_ALIGNED or MMHIP_YUV10_PATH_BYTES (0 or 1), not " +
+                    std::to_string(path));
+    return inv->clip_yuv10_launches[path];
+}
+
 // ---- planar Y'CbCr 4:2:0 as input (mmhip_clip_from_yuv420): Y4M payloads in HBM to drawable words in HBM ----
 static_assert(MMHIP_YUV_CHROMA_BILINEAR == MM_YUV_CHROMA_BILINEAR && MMHIP_YUV_CHROMA_REPLICATE == MM_YUV_CHROMA_REPLICATE,
               "the chroma modes of mm_yuv.h");

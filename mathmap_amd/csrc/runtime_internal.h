@@ -247,6 +247,8 @@ struct mmhip_invocation {
     // path the launcher took (aligned, byte), and the upload groups of the last host call
     long clip_yuv_input_launches[2] = {0, 0};
     int clip_yuv_input_groups = 0;
+    // 10-bit YUV 4:2:0 output from float frames (mmhip_clip_float_to_yuv420p10): the converter's launches by path
+    long clip_yuv10_launches[2] = {0, 0};
     uint32_t edge_color_x = 0, edge_color_y = 0;
     float sampling_offset_x = 0.f, sampling_offset_y = 0.f;
     bool timing = false;
