@@ -62,7 +62,13 @@ typedef struct mmhip_options {
                              closure or another native result), and both deviations are at least 0.5 px.  Everything else
                              -- float-map output, row bands, stripes, supersampling, memoised maps -- runs the exact chain.
                              Not part of the kernel source.  Other values: mmhip_compile* fails. */
-    int reserved[5];
+    int deep_inputs;      /* 1 (an extension): the filter's kernels can fetch float32 input drawables -- MM_IMG_DEEP images,
+                             bound by mmhip_set_image_sequence_float_host / _device, where the semantics are stated.  Part of
+                             the kernel source (#define MM_DEEP_INPUTS 1): with 0, the default, the generated text is what it
+                             is without the option and the two setters refuse the filter.  Every other kind of image is
+                             fetched as before either way.  Not together with pixel_inc > 1 (the preview's stride has no
+                             meaning for these images).  Values other than 0 and 1: mmhip_compile* fails. */
+    int reserved[4];
 } mmhip_options;
 
 typedef struct mmhip_userval_info {
@@ -100,6 +106,7 @@ const char *mmhip_filter_ir_json(mmhip_filter *f);        /* IR dump after the o
 const char *mmhip_filter_ir_json_raw(mmhip_filter *f);
 const char *mmhip_filter_kernel_source(mmhip_filter *f);  /* the HIP C++ handed to hiprtc */
 int mmhip_filter_gauss_mode(const mmhip_filter *f);       /* the options' gauss_mode the filter was compiled with */
+int mmhip_filter_deep_inputs(const mmhip_filter *f);      /* the options' deep_inputs the filter was compiled with */
 int mmhip_filter_num_native_calls(const mmhip_filter *f);
 /* The builtin overloads and macros the parser resolved while it compiled the filter's text, callees included: their
    unique ids ("mul_quat", "div_s", "macro___origVal", ...), sorted, one per line, as a NUL-terminated string of at
@@ -188,6 +195,45 @@ int mmhip_set_image_sequence_host(mmhip_invocation *inv, int index, const uint8_
                                   int num_frames);
 int mmhip_set_image_sequence_device(mmhip_invocation *inv, int index, const void *device_rgba32, int width, int height,
                                     int num_frames);
+/* Float32 input drawables ("deep" images; an extension): texels are four floats, float4[num_frames][height][width] in HBM,
+   frames one after the other -- the layout a whole-frame floatmap = 1 clip render writes with frame_stride = 16 * width *
+   height, so that one filter's float frames are the next one's input without an 8-bit step.  Only for invocations of a
+   filter compiled with mmhip_options.deep_inputs = 1.  Width, height, num_frames, scale and middle are those of an 8-bit
+   drawable of the same size, and so is everything else of the invocation: clip paths, shutter, aa, reconstruction filters
+   and pixel formats do not know the kind of an input.
+   The fetch is the drawable fetch with the byte step taken out:
+     - Coordinates exactly as for an 8-bit drawable: the resize factors, (x + middle_x) * scale_x and -((y - middle_y) *
+       scale_y), + 0.5 unless supersampling, floor and the x86 conversion to int; for the bilinear fetch x1 = floor(x),
+       x2 = x1 + 1, x2fact = x - (float)x1, x1fact = 1 - x2fact (y alike) and the weights p1fact = x1fact * y1fact,
+       p2fact = x1fact * y2fact, p3fact = x2fact * y1fact, p4fact = x2fact * y2fact of taps (x1, y1), (x1, y2), (x2, y1),
+       (x2, y2).
+     - One tap, in the order of the 8-bit tap: an unbound image gives (1, 1, 1, 1); the edge behaviour is applied; x outside
+       gives edge colour x; y outside edge colour y; then a frame outside [0, num_frames) gives (1, 1, 1, 1); otherwise
+       the texel's four floats as stored.  Edge colours become floats as TUPLE_FROM_COLOR makes them (byte / 255).
+     - No clamp and no rounding: NaN, +-inf, negative values, values above 1 and denormals pass through.
+     - No texel is loaded before its bounds and frame tests have passed: no coordinate forms an address outside the
+       sequence.
+     - Nearest: the result is the tap.  Bilinear: per channel ((p1 * p1fact + p2 * p2fact) + p3 * p3fact) + p4 * p4fact,
+       every product and sum one float32 operation rounded to nearest, in that order, none contracted to an fma; no rintf
+       and no division by 255.  On texels that are bytes / 255 the result is therefore within 0.5 / 255 (the byte rounding
+       the 8-bit fetch applies) plus a few float32 ulps of the 8-bit fetch's, not equal to it.
+     - A coordinate that is NaN, infinite or at or beyond 2^31 px gives what the same formulas give (not pinned); the
+       fetch stays inside the buffer.
+   _host: `pixels` is float[num_frames][height][width][channels], channels 3 (alpha becomes 1.0f) or 4; uploaded once, owned
+   by the invocation.  _device: `device_float4` is already in HBM, 16-byte aligned, not copied and not owned.
+   Either replaces whatever was bound to the index, 8-bit or deep (an upload the invocation owned is freed), and an 8-bit
+   setter replaces a deep image likewise.  Rebinding makes native results stale.
+   Native filters (gaussian_blur, convolve, half_convolve, visualize_fft, render()) read their image argument as bytes: a
+   call whose argument is a deep image fails that render with a message that names the filter and says that float inputs are
+   not supported there; the invocation stays usable.  A closure image whose body fetches a deep image is generated code and
+   works.
+   Errors, before anything is allocated or bound: width or height < 1; num_frames < 1; channels neither 3 nor 4; a null
+   pointer, or a device pointer that is not 16-byte aligned; a byte count that overflows; height * num_frames of 2^31 rows
+   or more (as for 8-bit sequences); a filter compiled without deep_inputs. */
+int mmhip_set_image_sequence_float_host(mmhip_invocation *inv, int index, const float *pixels, int width, int height, int channels,
+                                        int num_frames);
+int mmhip_set_image_sequence_float_device(mmhip_invocation *inv, int index, const void *device_float4, int width, int height,
+                                          int num_frames);
 /* Which frame of a bound sequence native filters read (gaussian_blur, render(), convolve, half_convolve,
    visualize_fft; an extension).  The reference's render_image samples its argument at frame 0 (ORIG_VAL(fx, fy, image,
    0.0), builtins/builtins.c:334), so gaussian_blur(in, ...) on a sequence blurs frame 0 in every output frame:

@@ -15,7 +15,7 @@ class Options(C.Structure):
     _fields_ = [("intersample", C.c_int), ("supersampling", C.c_int),
                 ("edge_behaviour_x", C.c_int), ("edge_behaviour_y", C.c_int),
                 ("tile_w", C.c_int), ("specialize_uservals", C.c_int), ("pixel_inc", C.c_int),
-                ("gauss_mode", C.c_int), ("reserved", C.c_int * 5)]
+                ("gauss_mode", C.c_int), ("deep_inputs", C.c_int), ("reserved", C.c_int * 4)]
 
 
 class UservalInfo(C.Structure):
@@ -52,6 +52,7 @@ SYMBOLS = {
     "mmhip_filter_ir_json_raw": (C.c_char_p, [C.c_void_p]),
     "mmhip_filter_kernel_source": (C.c_char_p, [C.c_void_p]),
     "mmhip_filter_gauss_mode": (C.c_int, [C.c_void_p]),
+    "mmhip_filter_deep_inputs": (C.c_int, [C.c_void_p]),
     "mmhip_filter_num_native_calls": (C.c_int, [C.c_void_p]),
     "mmhip_filter_builtin_ids": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "mmhip_filter_launch_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
@@ -83,6 +84,8 @@ SYMBOLS = {
     "mmhip_set_image_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "mmhip_set_image_sequence_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mmhip_set_image_sequence_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "mmhip_set_image_sequence_float_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mmhip_set_image_sequence_float_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "mmhip_set_edge_colors": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "mmhip_set_render_size": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mmhip_set_sampling_offset": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),

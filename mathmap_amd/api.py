@@ -268,18 +268,21 @@ class Filter:
     """A compiled .mm filter (front-end + IR + generated HIP kernel string)."""
 
     def __init__(self, source="", intersample=True, supersampling=False, edge_x=EDGE_COLOR, edge_y=EDGE_COLOR,
-                 tile_w=0, specialize=False, constants=None, ir_json=None, _handle=None, pixel_inc=1, gauss_mode="exact"):
+                 tile_w=0, specialize=False, constants=None, ir_json=None, _handle=None, pixel_inc=1, gauss_mode="exact",
+                 deep_inputs=False):
         """`source`: .mm text; or `ir_json`: an IR dump (mmhip_filter_ir_json_raw / the reference-ABI importer's
         form) -- the IR-level entry point.  `constants` (name -> number) bakes scalar user values in as literals.
         `pixel_inc` > 1: the bilinear fetch interpolates over a source sampled at that stride (the GIMP preview's
         fast image source, builtins.c:186-216).  `gauss_mode`: "exact" (default), or "tolerance" -- gaussian_blur's
         faster chain, within 1 per RGBA8 channel of exact, where the render writes the blur's bytes directly (the
-        conditions are stated at mmhip_options.gauss_mode in include/mmhip.h)."""
+        conditions are stated at mmhip_options.gauss_mode in include/mmhip.h).  `deep_inputs`: the kernels can fetch
+        float32 input drawables (Invocation.set_image with a float32 array, set_image_device_float); off by default,
+        and then the generated text is what it is without the option."""
         if gauss_mode not in GAUSS_MODES:
             raise MathMapError("gauss_mode must be one of %s, not %r" % (", ".join(sorted(GAUSS_MODES)), gauss_mode))
         self._source = source
         self._kwargs = dict(intersample=intersample, supersampling=supersampling, edge_x=edge_x, edge_y=edge_y,
-                            tile_w=tile_w, pixel_inc=pixel_inc, gauss_mode=gauss_mode)
+                            tile_w=tile_w, pixel_inc=pixel_inc, gauss_mode=gauss_mode, deep_inputs=deep_inputs)
         if _handle is not None:
             self._h = _handle
             return
@@ -292,6 +295,7 @@ class Filter:
         o.pixel_inc = pixel_inc
         o.specialize_uservals = 1 if specialize else 0
         o.gauss_mode = GAUSS_MODES[gauss_mode]
+        o.deep_inputs = 1 if deep_inputs else 0
         if ir_json is not None:
             self._h = lib().mmhip_compile_ir_json(ir_json.encode(), C.byref(o))
         else:
@@ -383,6 +387,11 @@ class Filter:
         """The gauss_mode the library compiled this filter with: "exact" or "tolerance"."""
         mode = lib().mmhip_filter_gauss_mode(self._h)
         return {v: k for k, v in GAUSS_MODES.items()}[mode]
+
+    @property
+    def deep_inputs(self):
+        """Whether the library compiled this filter's kernels with the float32 drawable fetch (mmhip_options.deep_inputs)."""
+        return bool(lib().mmhip_filter_deep_inputs(self._h))
 
     @property
     def num_native_calls(self):
@@ -546,6 +555,20 @@ def as_image_sequence(array):
     return a
 
 
+IMAGE_DTYPES = "uint8 (an 8-bit drawable) or float32 (a float drawable; Filter(..., deep_inputs=True))"
+
+
+def as_float_image_sequence(array):
+    """A float32 host image ([H,W,3|4]) or sequence ([N,H,W,3|4]) as the contiguous [N,H,W,C] array that
+    mmhip_set_image_sequence_float_host takes."""
+    a = np.ascontiguousarray(array, dtype=np.float32)
+    if a.ndim == 3:
+        a = a[None]
+    if a.ndim != 4 or a.shape[0] < 1:
+        raise MathMapError("an image is [H,W,3|4], an image sequence [N,H,W,3|4] with N >= 1; got shape %s" % (tuple(np.shape(array)),))
+    return a
+
+
 class Invocation:
     """A filter bound to a canvas size, user values and input images (all in HBM)."""
 
@@ -611,8 +634,20 @@ class Invocation:
         """Binds a host uint8 array as input drawable (uploaded once to HBM): [H,W,3|4] is one image,
         [N,H,W,3|4] a sequence of N frames of one size.  in(xy, n) reads frame (int)n of it (plain
         in(xy): frame (int)t), and opaque white where there is no such frame; gaussian_blur, convolve
-        and render() read frame 0 (set_native_input_frame("current"): the render's own frame)."""
+        and render() read frame 0 (set_native_input_frame("current"): the render's own frame).
+        A float32 array of the same shapes is bound as a float drawable (mmhip_set_image_sequence_float_host: the
+        texels are fetched as they are, unquantised; 3 channels get alpha 1.0) -- the filter must have been compiled
+        with deep_inputs=True.  An array of any other dtype is a ValueError; what has no dtype (nested lists) is
+        converted to uint8, as before."""
         u = self._index(name)
+        dtype = getattr(array, "dtype", None)
+        if dtype is not None and dtype == np.float32:
+            a = as_float_image_sequence(array)
+            n, h, w, c = a.shape
+            self._check(lib().mmhip_set_image_sequence_float_host(self._h, u["index"], a.ctypes.data_as(C.c_void_p), w, h, c, n))
+            return
+        if dtype is not None and dtype != np.uint8:
+            raise ValueError("set_image: the array's dtype must be %s, not %s" % (IMAGE_DTYPES, dtype))
         a = as_image_sequence(array)
         n, h, w, c = a.shape
         self._check(lib().mmhip_set_image_sequence_host(self._h, u["index"], a.ctypes.data_as(C.c_void_p), w, h, c, n))
@@ -654,6 +689,15 @@ class Invocation:
         many frames of width x height one after the other ([N,H,W] uint32)."""
         u = self._index(name)
         self._check(lib().mmhip_set_image_sequence_device(self._h, u["index"], C.c_void_p(device_ptr), width, height, num_frames))
+        if keepalive is not None:
+            self._keep.append(keepalive)
+
+    def set_image_device_float(self, name, device_ptr, width, height, num_frames=1, keepalive=None):
+        """Binds float4 texels already resident in HBM as a float drawable: [num_frames, height, width] float4, 16-byte
+        aligned, not copied (mmhip_set_image_sequence_float_device) -- the layout render_clip(floatmap=True, out_ptr=p)
+        writes for whole frames.  The filter must have been compiled with deep_inputs=True."""
+        u = self._index(name)
+        self._check(lib().mmhip_set_image_sequence_float_device(self._h, u["index"], C.c_void_p(device_ptr), width, height, num_frames))
         if keepalive is not None:
             self._keep.append(keepalive)
 

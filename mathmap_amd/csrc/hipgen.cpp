@@ -169,6 +169,23 @@ std::string text_key(const std::string &s) {
 
 const std::string KERNEL = "extern \"C\" __global__ void __launch_bounds__(256) ";
 
+// The device prelude of a kernel generated without KernelOptions::deep_inputs: mm_device.h less its MM_DEEP_INPUTS
+// regions, each cut from its `#if MM_DEEP_INPUTS` line to its `#endif  // MM_DEEP_INPUTS` line.  That is the text the
+// prelude had before the option existed, so such a kernel keeps its text, its key and its cached code object.
+const std::string &plain_device_prelude() {
+    static const std::string text = [] {
+        const std::string open = "#if MM_DEEP_INPUTS\n", close = "#endif  // MM_DEEP_INPUTS\n";
+        std::string s = device_prelude();
+        for (size_t at; (at = s.find(open)) != std::string::npos;) {
+            const size_t end = s.find(close, at);
+            if (end == std::string::npos) throw CompileError("internal: mm_device.h: an MM_DEEP_INPUTS region without its #endif line");
+            s.erase(at, end + close.size() - at);
+        }
+        return s;
+    }();
+    return text;
+}
+
 struct Generator {
     FilterCode &code;
     const KernelOptions &opt;
@@ -888,6 +905,7 @@ struct Generator {
         out << "#define MM_SUPERSAMPLING " << opt.supersampling << "\n";
         out << "#define MM_EDGE_X " << opt.edge_x << "\n#define MM_EDGE_Y " << opt.edge_y << "\n";
         if (opt.pixel_inc > 1) out << "#define MM_PIXEL_INC " << opt.pixel_inc << "\n";
+        if (opt.deep_inputs) out << "#define MM_DEEP_INPUTS 1\n";
         out << "#define MM_TILE_W " << ks.tile_w << "\n#define MM_TILE_H " << ks.tile_h << "\n";
         ks.unroll = opt.unroll > 0 ? opt.unroll : auto_unroll();
         // pair mode (row values are per pixel of a pair; a native call is not arithmetic)
@@ -924,7 +942,7 @@ struct Generator {
                "#define MMQ_FMA(a, b, c) __builtin_fma((a), (b), (c))\n#define MMQ_SQRT(a) sqrt((a))\n"
                "#define MMQ_SQRTF(a) sqrtf((a))\n"
             << device_fastmath_prelude() << "\n";
-        out << device_prelude() << "\n";
+        out << (opt.deep_inputs ? device_prelude() : plain_device_prelude().c_str()) << "\n";
         bool noise = uses_noise(code.body);
         for (auto &fn : (fn_root ? fn_root : &code)->functions) noise = noise || uses_noise(fn->body);
         if (noise) {

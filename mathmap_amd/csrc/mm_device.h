@@ -649,12 +649,81 @@ MM_DEV mm_image_desc mm_load_desc(const mm_args &A, mm_image img) {
     return d;
 }
 
+#if MM_DEEP_INPUTS
+// (Kernels generated without the option do not carry the two MM_DEEP_INPUTS regions of this file at all: hipgen.cpp
+// plain_device_prelude cuts them, from the `#if` line to the `#endif` line with the macro's name behind it, so their
+// text -- and with it every cache key -- is what it was before the option existed.)
+// ---- float32 drawables (an extension, include/mmhip.h mmhip_set_image_sequence_float_*; MM_DEEP_INPUTS 1 is
+// mmhip_options.deep_inputs) ------------------------------------------------------------------------------------------
+// data is float4[num_frames][h][w], frames contiguous; w, h, num_frames, scale and middle as for a drawable.  The fetch
+// is the drawable's generic fetch with the byte step taken out: same coordinates, same order of tests per tap, the
+// texel's four floats as stored -- no clamp, no rintf, no division by 255.  Such an image is never hot
+// (mm_fetch_is_hot_any asks for MM_IMG_DRAWABLE), so mm_orig_val_d below is the one place that reaches this.
+enum { MM_IMG_DEEP = 3 };
+struct mm_deep_edges { mm_tup<4> x, y; };      // the edge colours as TUPLE_FROM_COLOR makes them: once per fetch, not per tap
+MM_DEV mm_deep_edges mm_deep_edge_colours(const mm_args &A) {
+    mm_deep_edges e;
+    e.x = mm_tuple_from_color(A.edge_color_x);
+    e.y = mm_tuple_from_color(A.edge_color_y);
+    return e;
+}
+// One tap, in get_pixel's order (mm_get_pixel_cold): edge behaviour, x outside, y outside, bad frame, texel.  The load
+// is the only conditional code -- one 16-byte global_load_dwordx4 under the lanes that passed all three tests, so no
+// coordinate forms an address outside the sequence and a wave with no lane inside issues no load -- and the outcomes
+// are selects behind it: the four taps of a bilinear fetch stay one region each instead of three early exits.
+// Row `frame * h + y` fits an int (the runtime binds no sequence of 2^31 rows or more) and is not negative.
+MM_DEV mm_tup<4> mm_get_pixel_deep(const mm_image_desc &d, const mm_deep_edges &e, int x, int y, int frame) {
+    mm_apply_edge_behaviour(x, y, d.w, d.h);
+    const bool out_x = x < 0 || x >= d.w, out_y = y < 0 || y >= d.h;
+    const bool bad_frame = (unsigned)frame >= (unsigned)d.num_frames;
+    mm_tup<4> t;
+    t.v[0] = t.v[1] = t.v[2] = t.v[3] = 1.0f;
+    if (!(out_x || out_y || bad_frame)) {
+        const float4 p = ((mm_gmap)d.data)[(long)(unsigned)(frame * d.h + y) * d.w + x];
+        t.v[0] = p.x; t.v[1] = p.y; t.v[2] = p.z; t.v[3] = p.w;
+    }
+    if (out_y) t = e.y;
+    if (out_x) t = e.x;
+    return t;
+}
+MM_DEV mm_tup<4> mm_orig_val_deep(const mm_args &A, const mm_image_desc &d, float x, float y, int frame) {
+    const mm_deep_edges e = mm_deep_edge_colours(A);
+    x = (x + d.middle_x) * d.scale_x;
+    y = -((y - d.middle_y) * d.scale_y);
+#if MM_INTERSAMPLE
+    // get_orig_val_intersample_pixel's taps and weights (mm_intersample_tuple_cold, mm_bilinear_sums), then per channel
+    // ((p1 f1 + p2 f2) + p3 f3) + p4 f4: every product and sum its own correctly rounded float32 operation.  Neither of
+    // the 8-bit path's wave-uniform shortcuts is kept: four equal float taps do not sum to the tap bit for bit.
+    const int x1 = mm_f2i(floorf(x)), x2 = x1 + 1;
+    const int y1 = mm_f2i(floorf(y)), y2 = y1 + 1;
+    const float x2fact = __fsub_rn(x, (float)x1), y2fact = __fsub_rn(y, (float)y1);
+    const float x1fact = __fsub_rn(1.0f, x2fact), y1fact = __fsub_rn(1.0f, y2fact);
+    const float f1 = __fmul_rn(x1fact, y1fact), f2 = __fmul_rn(x1fact, y2fact), f3 = __fmul_rn(x2fact, y1fact), f4 = __fmul_rn(x2fact, y2fact);
+    const mm_tup<4> p1 = mm_get_pixel_deep(d, e, x1, y1, frame), p2 = mm_get_pixel_deep(d, e, x1, y2, frame);
+    const mm_tup<4> p3 = mm_get_pixel_deep(d, e, x2, y1, frame), p4 = mm_get_pixel_deep(d, e, x2, y2, frame);
+    mm_tup<4> t;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        t.v[c] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(p1.v[c], f1), __fmul_rn(p2.v[c], f2)), __fmul_rn(p3.v[c], f3)), __fmul_rn(p4.v[c], f4));
+    return t;
+#else
+#if !MM_SUPERSAMPLING
+    x = __fadd_rn(x, 0.5f);      // (mm_orig_val_pixel: the reference's double add, rounded back, is this float add)
+    y = __fadd_rn(y, 0.5f);
+#endif
+    return mm_get_pixel_deep(d, e, mm_f2i(floorf(x)), mm_f2i(floorf(y)), frame);
+#endif
+}
+#endif  // MM_DEEP_INPUTS
 MM_DEV mm_tup<4> mm_intersample_tuple_cold(const mm_args &A, const mm_image_desc &d, float x, float y, int frame);
 // opmacros.h:199-216 (closure images are applied at compile time and never reach here)
 MM_DEV mm_tup<4> mm_orig_val_d(const mm_args &A, float x, float y, mm_image img, float f, const mm_image_desc &d) {
     if (img.resized) { x *= img.xf; y *= img.yf; }
     if (img.idx < 0) { mm_tup<4> t; t.v[0] = t.v[1] = t.v[2] = t.v[3] = 1.0f; return t; }
     if (d.kind == MM_IMG_FLOATMAP) return mm_floatmap_pixel(d, x, y);
+#if MM_DEEP_INPUTS
+    if (d.kind == MM_IMG_DEEP) return mm_orig_val_deep(A, d, x, y, mm_f2i(f));
+#endif  // MM_DEEP_INPUTS
 #if MM_INTERSAMPLE
     return mm_intersample_tuple_cold(A, d, x, y, mm_f2i(f));
 #else

@@ -9,10 +9,10 @@ namespace mm {
 
 struct HImage { int idx; int pw; int ph; float xf; float yf; int resized; };
 
-enum { IMG_DRAWABLE = 0, IMG_FLOATMAP = 1, IMG_NULL = 2 };
+enum { IMG_DRAWABLE = 0, IMG_FLOATMAP = 1, IMG_NULL = 2, IMG_DEEP = 3 };      // IMG_DEEP: float4 texels (mmhip_options.deep_inputs)
 
 struct HImageDesc {          // mm_image_entry
-    const void *data;        // drawable: num_frames frames of w x h packed texels, one after the other
+    const void *data;        // drawable: num_frames frames of w x h packed texels, one after the other (deep: float4 texels)
     int w, h;
     int kind;
     int num_frames;

@@ -985,6 +985,12 @@ size_t checkpoint_bytes(int w, int h) {
 // the scan kernels index a block of rows with 32-bit element offsets (MapSrc::at)
 bool scan_offsets_fit(int w, int hn) { return (long)std::max(w, hn) * 4 * 20 * 8 < (1L << 32); }
 
+// render_image reads a drawable's texels as packed bytes: a float32 drawable (IMG_DEEP, mmhip_options.deep_inputs) is
+// refused by name instead -- its floats are never read as words.
+static std::string deep_input_refusal(const char *who) {
+    return std::string(who) + ": float inputs are not supported by native filters (the image argument is a float32 drawable; fetch it in filter code instead)";
+}
+
 int plan_gaussian_blur(const HNativeRec &rec, const HImageDesc *images, int num_images, int rw, int rh, const NativeEnv &env,
                        GaussPlan *p, std::string *err) {
     const HImage &img = rec.args[0].img;
@@ -997,6 +1003,9 @@ int plan_gaussian_blur(const HNativeRec &rec, const HImageDesc *images, int num_
         w = in.w;
         h = in.h;
         if (w != rw || h != rh) { *err = "gaussian_blur: float-map input of a different size is not supported"; return -1; }
+    } else if (in.kind == IMG_DEEP) {
+        *err = deep_input_refusal("gaussian_blur");
+        return -1;
     } else if (in.kind != IMG_DRAWABLE) {
         *err = "gaussian_blur: input image is not bound";
         return -1;
@@ -1257,6 +1266,7 @@ int native_input_map(const char *who, const HImage &img, const std::vector<HImag
     if (img.idx < 0 || img.idx >= (int)images.size()) { *err = std::string(who) + ": input is not a bitmap image"; return -1; }
     const HImageDesc &in = images[img.idx];
     if (in.kind == IMG_FLOATMAP && in.w == w && in.h == h) { *map = (const float *)in.data; return 0; }
+    if (in.kind == IMG_DEEP) { *err = deep_input_refusal(who); return -1; }
     if (in.kind != IMG_DRAWABLE) { *err = std::string(who) + ": input image is not bound (or a float map of another size)"; return -1; }
     launch_render_drawable(in, img, env, dst, w, h, s);
     *map = dst;
@@ -1289,6 +1299,7 @@ int run_native_filter(const std::string &func, const HNativeRec &rec, const std:
                                                                             img.xf, img.yf, (float4 *)out_map, w, h);
             return 0;
         }
+        if (in.kind == IMG_DEEP) { *err = deep_input_refusal("render()"); return -1; }
         if (in.kind != IMG_DRAWABLE) { *err = "render(): input image is not bound"; return -1; }
         launch_render_drawable(in, img, ws.env, out_map, w, h, stream);
         return 0;

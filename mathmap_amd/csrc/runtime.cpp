@@ -54,6 +54,14 @@ bool mmhip_check_options(const mmhip_options *opts) {
         g_err = "options: gauss_mode " + std::to_string(opts->gauss_mode) + " is neither MMHIP_GAUSS_EXACT (0) nor MMHIP_GAUSS_TOLERANCE (1)";
         return false;
     }
+    if (opts && opts->deep_inputs != 0 && opts->deep_inputs != 1) {
+        g_err = "options: deep_inputs " + std::to_string(opts->deep_inputs) + " is neither 0 nor 1";
+        return false;
+    }
+    if (opts && opts->deep_inputs == 1 && opts->pixel_inc > 1) {
+        g_err = "options: deep_inputs with pixel_inc " + std::to_string(opts->pixel_inc) + ": the preview's stride has no meaning for float32 drawables";
+        return false;
+    }
     return true;
 }
 
@@ -105,6 +113,7 @@ static mmhip_filter *compile_source(const char *source, const mmhip_options *opt
             ko.edge_x = opts->edge_behaviour_x;
             ko.edge_y = opts->edge_behaviour_y;
             ko.pixel_inc = opts->pixel_inc > 1 ? opts->pixel_inc : 1;
+            ko.deep_inputs = opts->deep_inputs;
             if (opts->tile_w) ko.tile_w = opts->tile_w;
             f->opts = *opts;
             f->specialize = opts->specialize_uservals != 0;
@@ -213,6 +222,7 @@ const char *mmhip_filter_ir_json(mmhip_filter *f) { return f->ir_json.c_str(); }
 const char *mmhip_filter_ir_json_raw(mmhip_filter *f) { return f->ir_json_raw.c_str(); }
 const char *mmhip_filter_kernel_source(mmhip_filter *f) { return f->ks.source.c_str(); }
 int mmhip_filter_gauss_mode(const mmhip_filter *f) { return f->opts.gauss_mode; }
+int mmhip_filter_deep_inputs(const mmhip_filter *f) { return f->kopt.deep_inputs; }      // (what the kernels were generated with)
 int mmhip_filter_num_native_calls(const mmhip_filter *f) { return f->ks.native_sites; }
 
 int mmhip_filter_builtin_ids(const mmhip_filter *f, char *buf, int cap) {
@@ -584,6 +594,17 @@ static bool sequence_bytes(int width, int height, int num_frames, size_t &bytes)
            !__builtin_mul_overflow(texels, (size_t)4, &bytes) && bytes <= (size_t)PTRDIFF_MAX;
 }
 
+// The upload bound to `slot`, if it was ours, goes once nothing in flight reads it.
+static void release_owned_image(mmhip_invocation *inv, int slot) {
+    const void *old = inv->images[slot].data;
+    for (auto it = inv->owned.begin(); it != inv->owned.end(); ++it)
+        if (it->get() == old) {
+            (void)hipDeviceSynchronize();     // renders may have been queued on caller streams
+            inv->owned.erase(it);
+            return;
+        }
+}
+
 int mmhip_set_image_sequence_device(mmhip_invocation *inv, int index, const void *device_rgba32, int width, int height, int num_frames) {
     // (the arguments first: what is wrong with them does not depend on the invocation)
     if (num_frames < 1) return fail("num_frames must be at least 1");
@@ -592,6 +613,7 @@ int mmhip_set_image_sequence_device(mmhip_invocation *inv, int index, const void
     const UservalInfo *u = uv_info(inv, index, UvKind::Image);
     if (!u) return -1;
     int slot = inv->image_slot_of_uv[index];
+    if (inv->images[slot].kind == IMG_DEEP && inv->images[slot].data != device_rgba32) release_owned_image(inv, slot);      // a float32 upload of ours
     fill_drawable_desc(inv->images[slot], device_rgba32, width, height, num_frames);
     input_changed(inv);
     return 0;
@@ -643,6 +665,80 @@ int mmhip_set_image_sequence_host(mmhip_invocation *inv, int index, const uint8_
     const void *dev = d.get();
     inv->owned.push_back(std::move(d));
     return mmhip_set_image_sequence_device(inv, index, dev, width, height, num_frames);
+}
+
+// ---- float32 drawables (mmhip_options.deep_inputs; the semantics are stated in include/mmhip.h) ----
+
+// What is wrong with the arguments of a deep-image setter, checked before the invocation is looked at and before anything
+// is allocated or bound; `bytes` becomes the size of the sequence (16 bytes a texel).
+static int check_deep_sequence(const std::string &who, const void *p, bool device, int width, int height, int num_frames, size_t *bytes) {
+    if (width < 1 || height < 1) return fail(who + "width and height must be at least 1, not " + std::to_string(width) + " x " + std::to_string(height));
+    if (num_frames < 1) return fail(who + "num_frames must be at least 1");
+    if (!p) return fail(who + "the pixels are a null pointer");
+    if (device && ((uintptr_t)p & 15u) != 0) return fail(who + "the device pointer is not 16-byte aligned (float4 texels)");
+    size_t words = 0;
+    // (sequence_bytes counts 4 bytes a texel and applies the row rule of the generic fetch, which mm_get_pixel_deep shares)
+    if (!sequence_bytes(width, height, num_frames, words) || __builtin_mul_overflow(words, (size_t)4, bytes) || *bytes > (size_t)PTRDIFF_MAX)
+        return fail(who + "the size overflows (fewer than 2^31 rows in all, and a byte count that fits)");
+    return 0;
+}
+
+// ... and with the invocation: its filter's kernels must know the kind
+static int check_deep_filter(const std::string &who, const mmhip_invocation *inv) {
+    if (!inv) return fail(who + "no invocation");
+    if (!inv->f->kopt.deep_inputs)
+        return fail(who + "filter `" + inv->f->module.main->name + "' was not compiled with deep_inputs (mmhip_options.deep_inputs = 1)");
+    return 0;
+}
+
+static void bind_deep_image(mmhip_invocation *inv, int slot, const void *data, int width, int height, int num_frames) {
+    fill_drawable_desc(inv->images[slot], data, width, height, num_frames);
+    inv->images[slot].kind = IMG_DEEP;
+    input_changed(inv);
+}
+
+int mmhip_set_image_sequence_float_device(mmhip_invocation *inv, int index, const void *device_float4, int width, int height, int num_frames) {
+    const std::string who = "set_image_sequence_float_device: ";
+    size_t bytes = 0;
+    if (check_deep_sequence(who, device_float4, true, width, height, num_frames, &bytes) != 0 || check_deep_filter(who, inv) != 0) return -1;
+    if (!uv_info(inv, index, UvKind::Image)) return -1;
+    const int slot = inv->image_slot_of_uv[index];
+    if (inv->images[slot].data != device_float4) release_owned_image(inv, slot);
+    bind_deep_image(inv, slot, device_float4, width, height, num_frames);
+    return 0;
+}
+
+int mmhip_set_image_sequence_float_host(mmhip_invocation *inv, int index, const float *pixels, int width, int height, int channels, int num_frames) {
+    const std::string who = "set_image_sequence_float_host: ";
+    if (channels != 3 && channels != 4) return fail(who + "channels must be 3 or 4, not " + std::to_string(channels));
+    size_t bytes = 0;
+    if (check_deep_sequence(who, pixels, false, width, height, num_frames, &bytes) != 0 || check_deep_filter(who, inv) != 0) return -1;
+    if (!uv_info(inv, index, UvKind::Image)) return -1;
+    const size_t n = (size_t)width * height;
+    DeviceBuffer d;
+    HIP_TRY(d.grow(bytes));
+    if (channels == 4) HIP_TRY(hipMemcpy(d.get(), pixels, bytes, hipMemcpyHostToDevice));
+    else {
+        // one frame at a time through one staging buffer, alpha 1.0f: the frames land one after the other
+        std::vector<float> texels;
+        try { texels.resize(n * 4); } catch (const std::bad_alloc &) { return fail(who + "out of host memory"); }
+        for (int k = 0; k < num_frames; ++k) {
+            const float *frame = pixels + (size_t)k * n * 3;
+            for (size_t i = 0; i < n; ++i) {
+                texels[i * 4 + 0] = frame[i * 3 + 0];
+                texels[i * 4 + 1] = frame[i * 3 + 1];
+                texels[i * 4 + 2] = frame[i * 3 + 2];
+                texels[i * 4 + 3] = 1.0f;
+            }
+            HIP_TRY(hipMemcpy(d.get<char>() + (size_t)k * n * 16, texels.data(), n * 16, hipMemcpyHostToDevice));
+        }
+    }
+    const int slot = inv->image_slot_of_uv[index];
+    release_owned_image(inv, slot);
+    const void *dev = d.get();
+    inv->owned.push_back(std::move(d));
+    bind_deep_image(inv, slot, dev, width, height, num_frames);
+    return 0;
 }
 
 // Planar Y'CbCr 4:2:0 payloads as a sequence: they go up as they are, in groups through a staging buffer of at most
