@@ -815,6 +815,81 @@ int mmhip_y4m_header_p10(char *buf, int cap, int width, int height, int fps_num,
 /* The converter's launches of this invocation on path MMHIP_YUV10_PATH_ALIGNED or MMHIP_YUV10_PATH_BYTES; -1 for another
    path. */
 long mmhip_clip_float_to_yuv420p10_launches(mmhip_invocation *inv, int path);
+/* The other direction at 10 bits: planar Y'CbCr 4:2:0 frames of 16-bit samples as a float32 input drawable.  Converts
+   num_frames payloads in device memory -- the layout mmhip_clip_float_to_yuv420p10 writes and a YUV4MPEG2 file of colour
+   space C420p10 holds -- to the float4 texels a filter compiled with deep_inputs = 1 binds, on the GPU
+   (k_yuv420p10_to_float_clip, one launch), so that no 8-bit step stands between a 10-bit stream and the filter.  Device to
+   device, asynchronous on `stream` (0: the invocation's).  This statement is the specification:
+   tests/yuv10_input_reference.py restates it, mathmap_amd/csrc/mm_yuv.h holds it.
+     - Source: every frame is one contiguous payload of 16-bit little-endian samples: the Y plane, width * height samples
+       with rows `width` samples apart, then Cb, then Cr, each cw * ch samples with cw = (width + 1) >> 1 and ch = (height
+       + 1) >> 1, rows cw samples apart: mmhip_yuv420p10_frame_bytes in all.  src_yuv and src_frame_stride are even; the
+       stride is at least one payload.  A sample s is read as min(s, 1023): nothing is refused per sample.
+     - Chroma the pixel sees, at scale 16, an exact integer that is not rounded back to 10 bits (centre siting, as in
+       mmhip_clip_from_yuv420).  chroma is
+         MMHIP_YUV_CHROMA_REPLICATE: S = 16 * C[y >> 1][x >> 1];
+         MMHIP_YUV_CHROMA_BILINEAR (the Python and CLI default): cx = x >> 1, nx = clamp(cx + (x & 1 ? 1 : -1), 0, cw - 1),
+           cy and ny likewise from y and ch, and
+           S = 9 * C[cy][cx] + 3 * C[cy][nx] + 3 * C[ny][cx] + C[ny][nx]
+       for Cb and Cr alike; u = S_cb - 8192, v = S_cr - 8192.
+     - To float: yf = (float)(Y - off), uf = (float)u, vf = (float)v, all three exact; off and the luma excursion E are 64
+       and 876 (limited) or 0 and 1023 (full).  L = yf / (float)E is one IEEE float32 division; every * and + below is one
+       float32 operation rounded to nearest, none contracted to an fma (the device uses __fdiv_rn, __fmul_rn, __fadd_rn):
+         R = L + vf * rcr
+         G = (L + uf * gcb) + vf * gcr
+         B = L + uf * bcb
+         A = 1.0f
+       There is no clamp: below-black and super-white samples become values below 0 and above 1, as a deep drawable
+       allows; a filter that wants them gone clamps them itself.
+     - Coefficients: from the standard's constants Kr, Kb (0.299, 0.114 for bt601; 0.2126, 0.0722 for bt709), Kg = 1 - Kr -
+       Kb and the chroma excursion Ec = 896 (limited) or 1023 (full), per 1/16 chroma unit: rcr = 2 (1 - Kr) / (16 Ec); bcb
+       = 2 (1 - Kb) / (16 Ec); gcb = -2 (1 - Kb) Kb / (Kg * 16 Ec); gcr = -2 (1 - Kr) Kr / (Kg * 16 Ec); each the float32
+       nearest to the exact rational value:
+         matrix, range    off   E      rcr               gcb                gcr                bcb
+         bt601 limited    64    876    0x1.9a2f66p-14f   -0x1.92bce0p-16f   -0x1.a1df2ap-15f   0x1.0337e2p-13f
+         bt601 full       0     1023   0x1.67434ap-14f   -0x1.60bd72p-16f   -0x1.6dfec6p-15f   0x1.c61350p-14f
+         bt709 limited    64    876    0x1.ccbdd2p-14f   -0x1.b67222p-17f   -0x1.11eb6ap-15f   0x1.0f72a2p-13f
+         bt709 full       0     1023   0x1.938afap-14f   -0x1.8003e0p-17f   -0x1.dfd3eep-16f   0x1.db7f7ap-14f
+       With chroma 512 R == G == B for every Y; Y = off gives 0.0f and Y = off + E 1.0f exactly; at limited range Y = 0
+       gives -0.07305936f and Y = 1023 1.0947489f.  A grey frame that goes on through mmhip_clip_float_to_yuv420p10 in
+       the same mode returns every legal Y code unchanged.
+     - Destination: frames of width * height float4 texels, rows 16 * width bytes apart, frames dst_frame_stride bytes
+       apart; dst_float4 and dst_frame_stride are multiples of 16 and the stride is at least 16 * width * height.  With
+       dst_frame_stride = 16 * width * height this is what mmhip_set_image_sequence_float_device takes.  Nothing is
+       written between or behind frames.
+     - The kernel has a path of aligned wide accesses (width a multiple of 8, src_yuv and src_frame_stride multiples of
+       16; the destination is aligned by the rule above) and a path of 2-byte loads and per-pixel stores for everything
+       else; the launcher chooses, the floats are the same.  mmhip_clip_from_yuv420p10_launches counts the launches of
+       each.  MMHIP_YUV10_IN_COLUMNS=2|4|8 (read per call, default 2) sets the columns a work-item of the aligned path
+       converts, MMHIP_YUV10_IN_STORES=cached|nt (read per call, default cached) plain or non-temporal stores; the
+       defaults are the fastest of the six measured.  Timed as yuv420p10_to_float_clip
+       (mmhip_drain_native_kernel_ms).
+   Errors, by name, in the wording of mmhip_clip_from_yuv420 where the condition is the same: width or height below 1;
+   num_frames below 1 or above 65 535; an unknown matrix, range or chroma mode; null pointers; an odd src_yuv or
+   src_frame_stride; a src_frame_stride below one payload; a dst_float4 or dst_frame_stride that is not a multiple of 16;
+   a dst_frame_stride below one frame; a destination frame of more than 4 GiB (offsets inside a frame are 32-bit). */
+enum { MMHIP_YUV10_IN_PATH_ALIGNED = 0, MMHIP_YUV10_IN_PATH_SAMPLES = 1 };
+int mmhip_clip_from_yuv420p10(mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height, int num_frames,
+                              int matrix, int range, int chroma, void *dst_float4, int64_t dst_frame_stride, void *stream);
+/* The converter's launches of this invocation on path MMHIP_YUV10_IN_PATH_ALIGNED or MMHIP_YUV10_IN_PATH_SAMPLES; -1 for
+   another path. */
+long mmhip_clip_from_yuv420p10_launches(mmhip_invocation *inv, int path);
+/* Binds num_frames host payloads of 16-bit samples (in the host's byte order), frame_stride bytes apart (even, at least
+   mmhip_yuv420p10_frame_bytes), as the float32 sequence of image user value `index`, as
+   mmhip_set_image_sequence_float_host binds float frames: the same refusals, before anything is allocated (sizes, a null
+   pointer, a filter compiled without deep_inputs), then the converter's own.  The payloads go up as they are -- 3 bytes
+   per pixel instead of 16 -- in groups through a device staging buffer of at most MMHIP_CLIP_YUV_IN_BYTES (default 256
+   MiB, read per call, always at least one frame); every group takes one mmhip_clip_from_yuv420p10 launch into the owned
+   sequence, which is bound as a deep image; the upload it replaces is released.  Synchronous.
+   mmhip_clip_yuv10_input_groups returns the groups of the last such call of the invocation. */
+int mmhip_set_image_sequence_yuv420p10_host(mmhip_invocation *inv, int index, const uint16_t *yuv, int64_t frame_stride, int width,
+                                            int height, int num_frames, int matrix, int range, int chroma);
+int mmhip_clip_yuv10_input_groups(mmhip_invocation *inv);
+/* mmhip_y4m_parse_header for streams of either depth: accepts everything that function accepts, with *bits = 8, and the
+   colour space C420p10 with *bits = 10 (a frame's payload is then mmhip_yuv420p10_frame_bytes of little-endian 16-bit
+   samples).  Every other refusal is that function's.  Needs no GPU.  Returns 0, or -1. */
+int mmhip_y4m_parse_stream_header(const char *buf, int len, int *width, int *height, int *fps_num, int *fps_den, int *range, int *bits,
+                                  int *header_len);
 /* Convenience: whole frame to a host RGBA8 buffer (width*height*4 bytes); synchronous. */
 int mmhip_render_host(mmhip_invocation *inv, int frame, float t, uint8_t *out_rgba);
 int mmhip_sync(mmhip_invocation *inv);

@@ -33,6 +33,8 @@ MMHIP_YUV_CHROMA_BILINEAR, MMHIP_YUV_CHROMA_REPLICATE = 0, 1
 MMHIP_YUV_IN_PATH_ALIGNED, MMHIP_YUV_IN_PATH_BYTES = 0, 1
 # the paths mmhip_clip_float_to_yuv420p10_launches counts
 MMHIP_YUV10_PATH_ALIGNED, MMHIP_YUV10_PATH_BYTES = 0, 1
+# the paths mmhip_clip_from_yuv420p10_launches counts
+MMHIP_YUV10_IN_PATH_ALIGNED, MMHIP_YUV10_IN_PATH_SAMPLES = 0, 1
 
 # every symbol include/mmhip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -160,6 +162,13 @@ SYMBOLS = {
     "mmhip_yuv420p10_frame_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "mmhip_y4m_header_p10": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mmhip_clip_float_to_yuv420p10_launches": (C.c_long, [C.c_void_p, C.c_int]),
+    "mmhip_clip_from_yuv420p10": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_int64, C.c_void_p]),
+    "mmhip_clip_from_yuv420p10_launches": (C.c_long, [C.c_void_p, C.c_int]),
+    "mmhip_set_image_sequence_yuv420p10_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                          C.c_int]),
+    "mmhip_clip_yuv10_input_groups": (C.c_int, [C.c_void_p]),
+    "mmhip_y4m_parse_stream_header": (C.c_int, [C.c_char_p, C.c_int] + [C.POINTER(C.c_int)] * 7),
     "mmhip_render_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "mmhip_sync": (C.c_int, [C.c_void_p]),
     "mmhip_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),

@@ -215,20 +215,44 @@ def y4m_parse_header(data):
     return w, h, (num, den), names.get(rng), header_len
 
 
-def read_y4m(path_or_file, max_frames=None):
+def y4m_parse_stream_header(data):
+    """y4m_parse_header for streams of either depth (mmhip_y4m_parse_stream_header): (w, h, (fps_num, fps_den), yuv_range or
+    None, header_len, pixel_format), the last "yuv420p" or, for the colour space C420p10, "yuv420p10".  Needs no GPU.
+    ValueError, by name, for what the reader does not take."""
+    data = bytes(data)
+    out = [C.c_int(0) for _ in range(7)]
+    if lib().mmhip_y4m_parse_stream_header(data, len(data), *[C.byref(v) for v in out]) != 0:
+        raise ValueError(_err())
+    w, h, num, den, rng, bits, header_len = [v.value for v in out]
+    names = {v: k for k, v in YUV_RANGES.items()}
+    return w, h, (num, den), names.get(rng), header_len, "yuv420p10" if bits == 10 else "yuv420p"
+
+
+def read_y4m(path_or_file, max_frames=None, pixel_format="yuv420p"):
     """Reads a YUV4MPEG2 file of 8-bit 4:2:0 frames -- what write_y4m writes, and what video decoders emit: returns (yuv
     uint8 [N, frame_bytes], w, h, fps (num, den), yuv_range or None), the first value being what set_image_yuv420 takes
     and yuv_range "limited" or "full" where the header states XCOLORRANGE.  `path_or_file`: a file name, or a binary
     file object (which stays open; a pipe will do).  `max_frames` caps the frames read.  A FRAME line may carry
     parameters.  ValueError, by name: a header the reader does not take, a line that is not FRAME where a frame should
-    begin, a truncated last frame, a file with no frames."""
+    begin, a truncated last frame, a file with no frames.
+    `pixel_format`="yuv420p10" reads streams of colour space C420p10 only and returns uint16 [N, frame_bytes / 2], what
+    set_image_yuv420p10 takes (the file's samples are little-endian whatever the host); an 8-bit stream is a ValueError
+    then.  "any" reads either depth: the array's dtype tells which."""
     if max_frames is not None and int(max_frames) < 1:
         raise ValueError("read_y4m: max_frames must be at least 1, not %r" % (max_frames,))
+    if pixel_format not in PIXEL_FORMATS + ("any",):
+        raise ValueError("read_y4m: pixel_format must be one of %s, not %r" % (", ".join(PIXEL_FORMATS + ("any",)), pixel_format))
     f = open(path_or_file, "rb") if isinstance(path_or_file, (str, bytes)) or hasattr(path_or_file, "__fspath__") else path_or_file
     try:
         header = f.readline(4096)
-        w, h, fps, yuv_range, _ = y4m_parse_header(header)
-        frame_bytes = yuv420_frame_bytes(w, h)
+        if pixel_format == "yuv420p":
+            w, h, fps, yuv_range, _ = y4m_parse_header(header)
+            found = "yuv420p"
+        else:
+            w, h, fps, yuv_range, _, found = y4m_parse_stream_header(header)
+            if pixel_format == "yuv420p10" and found != "yuv420p10":
+                raise ValueError("read_y4m: pixel_format=\"yuv420p10\" reads streams of colour space C420p10, and this one holds 8-bit samples")
+        frame_bytes = yuv420_frame_bytes(w, h, found)
         frames = []
         while max_frames is None or len(frames) < int(max_frames):
             line = f.readline(4096)
@@ -244,7 +268,7 @@ def read_y4m(path_or_file, max_frames=None):
                 payload += piece
             if len(payload) != frame_bytes:
                 raise ValueError("read_y4m: frame %d is truncated: %d of %d bytes" % (len(frames), len(payload), frame_bytes))
-            frames.append(np.frombuffer(bytes(payload), np.uint8))
+            frames.append(np.frombuffer(bytes(payload), "<u2").astype(np.uint16) if found == "yuv420p10" else np.frombuffer(bytes(payload), np.uint8))
         if not frames:
             raise ValueError("read_y4m: the file has no frames")
         return np.stack(frames), w, h, fps, yuv_range
@@ -674,6 +698,39 @@ class Invocation:
         self._check(lib().mmhip_set_image_sequence_yuv420_host(self._h, u["index"], a.ctypes.data_as(C.c_void_p), frame_bytes, w, h, a.shape[0],
                                                                matrix, rng, mode))
 
+    def set_image_yuv420p10(self, name, yuv, w, h, yuv_matrix="bt709", yuv_range="limited", chroma="bilinear"):
+        """Binds 10-bit planar Y'CbCr 4:2:0 frames as float32 input drawable: `yuv` is uint16 [N, frame_bytes / 2] -- what
+        read_y4m(pixel_format="yuv420p10") and render_clip(pixel_format="yuv420p10") return -- or one frame, of `w` x `h`
+        pixels.  The payloads go up as they are (3 bytes per pixel) and are expanded to float4 texels on the GPU
+        (mmhip_set_image_sequence_yuv420p10_host) in the mode `yuv_matrix`, `yuv_range`, with `chroma` "bilinear"
+        (default) or "replicate": unclamped, alpha 1.0, no 8-bit step.  From there on the sequence is what set_image
+        binds for a float32 array; the filter must have been compiled with deep_inputs=True."""
+        matrix, rng = yuv_mode(yuv_matrix, yuv_range)
+        mode = yuv_chroma(chroma)
+        w, h = int(w), int(h)
+        if w < 1 or h < 1:
+            raise ValueError("set_image_yuv420p10: w and h must be at least 1, not %d x %d" % (w, h))
+        samples = w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1)
+        a = np.asarray(yuv)
+        if a.ndim == 1:
+            a = a[None]
+        if a.dtype.kind != "u" or a.dtype.itemsize != 2 or a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != samples:
+            raise ValueError("set_image_yuv420p10: uint16 [N, %d] for frames of %d x %d, not %s %r" % (samples, w, h, a.dtype, a.shape))
+        a = np.ascontiguousarray(a, np.uint16)      # (the host's byte order, which the library reads)
+        u = self._index(name)
+        self._check(lib().mmhip_set_image_sequence_yuv420p10_host(self._h, u["index"], a.ctypes.data_as(C.c_void_p), 2 * samples, w, h, a.shape[0],
+                                                                  matrix, rng, mode))
+
+    def clip_yuv10_input_groups(self):
+        """The upload groups of the last set_image_yuv420p10 (mmhip_clip_yuv10_input_groups)."""
+        return lib().mmhip_clip_yuv10_input_groups(self._h)
+
+    def clip_from_yuv420p10_launches(self, path):
+        """The launches of clip_from_yuv420p10's kernel on `path`: "aligned" or "samples" (mmhip_clip_from_yuv420p10_launches)."""
+        if path not in ("aligned", "samples"):
+            raise ValueError("clip_from_yuv420p10_launches: path must be \"aligned\" or \"samples\", not %r" % (path,))
+        return lib().mmhip_clip_from_yuv420p10_launches(self._h, 0 if path == "aligned" else 1)
+
     def clip_yuv_input_groups(self):
         """The upload groups of the last set_image_yuv420 (mmhip_clip_yuv_input_groups)."""
         return lib().mmhip_clip_yuv_input_groups(self._h)
@@ -990,6 +1047,23 @@ class Invocation:
             dst_frame_stride = 4 * w * h
         self._check(lib().mmhip_clip_from_yuv420(self._h, C.c_void_p(src_ptr), src_frame_stride, w, h, int(num_frames), matrix, rng, mode,
                                                  C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
+
+    def clip_from_yuv420p10(self, src_ptr, dst_ptr, num_frames, width=None, height=None, src_frame_stride=None, dst_frame_stride=None,
+                            yuv_matrix="bt709", yuv_range="limited", chroma="bilinear", stream=0):
+        """Converts 10-bit planar Y'CbCr 4:2:0 payloads in device memory (16-bit samples) to float4 texels in device
+        memory (mmhip_clip_from_yuv420p10), asynchronously: what set_image_device_float takes.  Payloads are
+        `src_frame_stride` bytes apart (default yuv420_frame_bytes(w, h, "yuv420p10")), frames of texels
+        `dst_frame_stride` (default 16 * width * height).  The size defaults to the render size."""
+        matrix, rng = yuv_mode(yuv_matrix, yuv_range)
+        mode = yuv_chroma(chroma)
+        w = self.render_width if width is None else int(width)
+        h = self.render_height if height is None else int(height)
+        if src_frame_stride is None:
+            src_frame_stride = 2 * (w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1))
+        if dst_frame_stride is None:
+            dst_frame_stride = 16 * w * h
+        self._check(lib().mmhip_clip_from_yuv420p10(self._h, C.c_void_p(src_ptr), src_frame_stride, w, h, int(num_frames), matrix, rng, mode,
+                                                    C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
 
     def clip_float_to_yuv420p10(self, src_ptr, dst_ptr, num_frames, width=None, height=None, rows=None, src_row_stride=None,
                                 src_frame_stride=None, dst_frame_stride=None, yuv_matrix="bt709", yuv_range="limited", stream=0):

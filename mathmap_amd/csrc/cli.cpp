@@ -117,7 +117,13 @@ void usage() {
            "                              (standard input, for one image at most), is a\n"
            "                              YUV4MPEG2 stream of 8-bit 4:2:0 frames: all its\n"
            "                              frames (--input-frames=NUM: the first NUM) are bound\n"
-           "                              as a sequence and expanded to RGB on the GPU; without\n"
+           "                              as a sequence and expanded to RGB on the GPU; a\n"
+           "                              stream whose header says C420p10 (10-bit samples in\n"
+           "                              16-bit little-endian words) is expanded to float32\n"
+           "                              pixels instead, unclamped and with no 8-bit step,\n"
+           "                              and the filter is compiled for float32 inputs\n"
+           "                              (native filters like gaussian_blur do not read\n"
+           "                              such an image); without\n"
            "                              -s the size is the stream's, without -F every input\n"
            "                              frame is rendered, and a .y4m output without --fps\n"
            "                              takes the stream's frame rate; in(xy, frame)\n"
@@ -249,11 +255,12 @@ bool write_png_rgb(const char *path, const unsigned char *rgba, int w, int h) {
 
 struct Define { std::string name, value; };
 
-// A YUV4MPEG2 stream of 8-bit 4:2:0 frames (mmhip_y4m_parse_header states what a header may hold): its payloads one after
-// the other, as mmhip_set_image_sequence_yuv420_host takes them.
+// A YUV4MPEG2 stream of 4:2:0 frames of 8 or 10 bits (mmhip_y4m_parse_stream_header states what a header may hold): its
+// payloads one after the other, as mmhip_set_image_sequence_yuv420_host (bits 8) or ..._yuv420p10_host (bits 10) takes
+// them.
 struct Y4mStream {
     int uv = -1;      // the image user value it is bound to
-    int width = 0, height = 0, fps_num = 25, fps_den = 1, range = -1, frames = 0;
+    int width = 0, height = 0, fps_num = 25, fps_den = 1, range = -1, bits = 8, frames = 0;
     std::vector<unsigned char> payloads;
 };
 bool is_y4m_name(const std::string &v) { return v == "-" || (v.size() >= 4 && v.compare(v.size() - 4, 4, ".y4m") == 0); }
@@ -277,11 +284,12 @@ bool read_y4m(const std::string &name, int max_frames, Y4mStream &out, std::stri
     std::string line;
     read_line(f, line, 4096);
     int header_len = 0;
-    if (mmhip_y4m_parse_header(line.data(), (int)line.size(), &out.width, &out.height, &out.fps_num, &out.fps_den, &out.range, &header_len) != 0) {
+    if (mmhip_y4m_parse_stream_header(line.data(), (int)line.size(), &out.width, &out.height, &out.fps_num, &out.fps_den, &out.range, &out.bits,
+                                      &header_len) != 0) {
         err = "`" + name + "': " + mmhip_last_error();
         return done(false);
     }
-    const size_t frame_bytes = (size_t)mmhip_yuv420_frame_bytes(out.width, out.height);
+    const size_t frame_bytes = (size_t)(out.bits == 10 ? mmhip_yuv420p10_frame_bytes(out.width, out.height) : mmhip_yuv420_frame_bytes(out.width, out.height));
     while (!max_frames || out.frames < max_frames) {
         if (!read_line(f, line, 4096)) break;
         if (line.compare(0, 5, "FRAME") != 0 || line.back() != '\n' || (line[5] != ' ' && line[5] != '\n')) {
@@ -657,8 +665,8 @@ int main(int argc, char **argv) {
     // start with) is a compiled filter in the IR dump form of mmhip_filter_ir_json_raw, e.g. the output of another
     // front-end; everything after compilation is the same
     size_t first = script.find_first_not_of(" \t\r\n");
-    mmhip_filter *flt = (first != std::string::npos && script[first] == '{') ? mmhip_compile_ir_json(script.c_str(), &opts)
-                                                                             : mmhip_compile(script.c_str(), &opts);
+    const bool is_ir = first != std::string::npos && script[first] == '{';
+    mmhip_filter *flt = is_ir ? mmhip_compile_ir_json(script.c_str(), &opts) : mmhip_compile(script.c_str(), &opts);
     if (bench_no_backend) return 0;
     if (!flt) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
     if (bench_render_count == 0) return mmhip_filter_jit(flt, 0) < 0 ? 1 : 0;
@@ -703,6 +711,16 @@ int main(int argc, char **argv) {
         mmhip_filter_userval_info(flt, st.uv, &info);
         std::string err;
         if (!read_y4m(lookup(info.name)->value, input_frames, st, err)) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
+    }
+    // a 10-bit stream is bound as a float32 drawable: the filter is compiled once more, for such inputs (its user values
+    // are the same)
+    bool deep_input = false;
+    for (const Y4mStream &st : streams) deep_input = deep_input || st.bits == 10;
+    if (deep_input) {
+        mmhip_filter_free(flt);
+        opts.deep_inputs = 1;
+        flt = is_ir ? mmhip_compile_ir_json(script.c_str(), &opts) : mmhip_compile(script.c_str(), &opts);
+        if (!flt) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
     }
     auto stream_of = [&](int uv) -> const Y4mStream * {
         for (const Y4mStream &st : streams) if (st.uv == uv) return &st;
@@ -753,6 +771,16 @@ int main(int argc, char **argv) {
             case MMHIP_UV_IMAGE: {
                 if (const Y4mStream *st = stream_of(i)) {
                     const int range = input_yuv_range >= 0 ? input_yuv_range : st->range >= 0 ? st->range : MMHIP_YUV_LIMITED;
+                    if (st->bits == 10) {
+                        // (the bytes of a file are little-endian samples, which is this host's order)
+                        if (mmhip_set_image_sequence_yuv420p10_host(inv, i, (const uint16_t *)st->payloads.data(),
+                                                                    mmhip_yuv420p10_frame_bytes(st->width, st->height), st->width, st->height, st->frames,
+                                                                    input_yuv_matrix, range, input_chroma) != 0) {
+                            fprintf(stderr, "Error: %s\n", mmhip_last_error());
+                            return 1;
+                        }
+                        break;
+                    }
                     if (mmhip_set_image_sequence_yuv420_host(inv, i, st->payloads.data(), mmhip_yuv420_frame_bytes(st->width, st->height), st->width,
                                                              st->height, st->frames, input_yuv_matrix, range, input_chroma) != 0) {
                         fprintf(stderr, "Error: %s\n", mmhip_last_error());

@@ -1,5 +1,6 @@
 // Launchers of the hand-written kernels that finish a clip or convert its frames: the combines, the contrast mask and the
-// reconstruction filter (clip_combine.hip), Y'CbCr 4:2:0 out (clip_yuv.hip, 10-bit from float frames: clip_yuv10.hip) and in (clip_yuv_in.hip).
+// reconstruction filter (clip_combine.hip), Y'CbCr 4:2:0 out (clip_yuv.hip, 10-bit from float frames: clip_yuv10.hip) and in (clip_yuv_in.hip,
+// 10-bit to float frames: clip_yuv10_in.hip).
 #pragma once
 #include "native_filters.h"      // NativeWorkspace
 
@@ -112,5 +113,16 @@ int check_float_to_yuv420p10_clip(const void *src, int64_t src_row_stride, int64
 int launch_float_to_yuv420p10_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
                                    int last_row, int frames, int matrix, int range, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws,
                                    hipStream_t s, int *path, std::string *err);
+// Planar Y'CbCr 4:2:0 frames of 16-bit samples (10 bits used) to the float4 texels of a deep drawable in one launch
+// (k_yuv420p10_to_float_clip, clip_yuv10_in.hip; mmhip_clip_from_yuv420p10 states the semantics and its parameters are
+// these, mm_yuv.h holds the arithmetic).  The launcher takes the path of aligned wide accesses (*path = 0) where the width
+// is a multiple of 8 and src and src_frame_stride are multiples of 16, else the path of 2-byte loads and per-pixel
+// stores (*path = 1): the same floats.  Refused, by name, in `err` (the check alone needs no GPU): what
+// check_yuv420_to_rgba_clip refuses, an odd src or src_frame_stride, a dst or dst_frame_stride that is no multiple of
+// 16.  Timed through ws.timed_launch as yuv420p10_to_float_clip.
+int check_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
+                                  const void *dst, int64_t dst_frame_stride, std::string *err);
+int launch_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
+                                   void *dst, int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err);
 
 }  // namespace mm

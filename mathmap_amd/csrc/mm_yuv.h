@@ -3,7 +3,8 @@
 // a pixel, the chroma of a 2 x 2 block, and where the planes of a frame lie.  Plain C++, so that the host compiles the
 // same text: the launcher takes a mode's coefficients from the table, both paths of the kernel convert with the two
 // formulas, and a stand-alone test program (tests/test_clip_yuv_api.py) runs all of it on a frame worked out by hand.
-// All of it is int32; every shift is an arithmetic shift of a signed value (floor division).
+// All of it is int32; every shift is an arithmetic shift of a signed value (floor division) -- but for the quantiser of the
+// 10-bit output and the matrix of the 10-bit input at the end, which are float32 and say so.
 #pragma once
 #include <stdint.h>
 
@@ -229,4 +230,78 @@ inline void mm_yuv10_frame_host(const mm_yuv_mode &m, const float *src, int64_t 
             cb[(int64_t)cy * cw + cx] = (uint16_t)mm_yuv10_cb(m, rs, gs, bs);
             cr[(int64_t)cy * cw + cx] = (uint16_t)mm_yuv10_cr(m, rs, gs, bs);
         }
+}
+
+// ---- 10-bit input to float frames: planar Y'CbCr 4:2:0 payloads of 16-bit samples to float4 RGBA texels, what a deep
+// drawable binds (k_yuv420p10_to_float_clip, clip_yuv10_in.hip; the semantics are stated at mmhip_clip_from_yuv420p10 in
+// include/mmhip.h) ----
+
+// One mode: with yf = (float)(Y - off), uf = (float)(S_cb - 8192), vf = (float)(S_cr - 8192) -- S the chroma the pixel sees
+// at scale 16 -- and L = yf / e,
+//   R = L + vf * rcr, G = (L + uf * gcb) + vf * gcr, B = L + uf * bcb,
+// every operation one float32 operation rounded to nearest.  Each coefficient is the float32 nearest to the exact
+// rational 2 (1 - Kr) / (16 Ec) and so on, Ec = 896 (limited) or 1023 (full).
+struct mm_yuv10_float_mode {
+    int off;
+    float e, rcr, gcb, gcr, bcb;
+};
+
+// [matrix][range]
+static const mm_yuv10_float_mode MM_YUV10_FLOAT_MODES[MM_YUV_MATRICES][MM_YUV_RANGES] = {
+    {{64, 876.0f, 0x1.9a2f66p-14f, -0x1.92bce0p-16f, -0x1.a1df2ap-15f, 0x1.0337e2p-13f},      // bt601 limited
+     {0, 1023.0f, 0x1.67434ap-14f, -0x1.60bd72p-16f, -0x1.6dfec6p-15f, 0x1.c61350p-14f}},     // bt601 full
+    {{64, 876.0f, 0x1.ccbdd2p-14f, -0x1.b67222p-17f, -0x1.11eb6ap-15f, 0x1.0f72a2p-13f},      // bt709 limited
+     {0, 1023.0f, 0x1.938afap-14f, -0x1.8003e0p-17f, -0x1.dfd3eep-16f, 0x1.db7f7ap-14f}},     // bt709 full
+};
+
+// The three float32 operations.  The device spells them with intrinsics the compiler neither contracts nor
+// reassociates; the host forms each result in a volatile, so that no product meets a sum in an fma.
+#if defined(__HIP_DEVICE_COMPILE__)
+MM_YUV_FN float mm_yuv_fmul(float a, float b) { return __fmul_rn(a, b); }
+MM_YUV_FN float mm_yuv_fadd(float a, float b) { return __fadd_rn(a, b); }
+MM_YUV_FN float mm_yuv_fdiv(float a, float b) { return __fdiv_rn(a, b); }
+#else
+MM_YUV_FN float mm_yuv_fmul(float a, float b) { volatile float r = a * b; return r; }
+MM_YUV_FN float mm_yuv_fadd(float a, float b) { volatile float r = a + b; return r; }
+MM_YUV_FN float mm_yuv_fdiv(float a, float b) { volatile float r = a / b; return r; }
+#endif
+
+// A sample as it is read: nothing is refused, what lies above 10 bits is 1023.
+MM_YUV_FN int mm_yuv10_sample(unsigned s) { return (int)(s < 1023u ? s : 1023u); }
+
+// The chroma a pixel sees at scale 16, an exact integer in 0 .. 16 368: mm_yuv_chroma_column's sums of the own and the
+// neighbour column weighed 3 and 1 without the rounding of mm_yuv_chroma_blend; replicate mode is 16 times the sample.
+MM_YUV_FN int mm_yuv10_chroma_blend16(int own_column, int neighbour_column) { return 3 * own_column + neighbour_column; }
+MM_YUV_FN int mm_yuv10_chroma_replicate16(int sample) { return 16 * sample; }
+
+// One pixel's texel from its luma (0 .. 1023) and the chroma it sees at scale 16.  Nothing is clamped.
+MM_YUV_FN void mm_yuv10_to_float(const mm_yuv10_float_mode &m, int luma, int s_cb, int s_cr, float rgba[4]) {
+    const float yf = (float)(luma - m.off), uf = (float)(s_cb - 8192), vf = (float)(s_cr - 8192);
+    const float l = mm_yuv_fdiv(yf, m.e);
+    rgba[0] = mm_yuv_fadd(l, mm_yuv_fmul(vf, m.rcr));
+    rgba[1] = mm_yuv_fadd(mm_yuv_fadd(l, mm_yuv_fmul(uf, m.gcb)), mm_yuv_fmul(vf, m.gcr));
+    rgba[2] = mm_yuv_fadd(l, mm_yuv_fmul(uf, m.bcb));
+    rgba[3] = 1.0f;
+}
+
+// The chroma at scale 16 pixel (x, y) sees in a plane of cw x ch samples with rows cw apart.
+MM_YUV_FN int mm_yuv10_chroma16(int chroma, const uint16_t *plane, int cw, int ch, int x, int y) {
+    const int cx = x >> 1, cy = y >> 1;
+    const uint16_t *own = plane + (int64_t)cy * cw;
+    if (chroma == MM_YUV_CHROMA_REPLICATE) return mm_yuv10_chroma_replicate16(mm_yuv10_sample(own[cx]));
+    const int nx = mm_yuv_chroma_neighbour(x, cw), ny = mm_yuv_chroma_neighbour(y, ch);
+    const uint16_t *nb = plane + (int64_t)ny * cw;
+    return mm_yuv10_chroma_blend16(mm_yuv_chroma_column(mm_yuv10_sample(own[cx]), mm_yuv10_sample(nb[cx])),
+                                   mm_yuv_chroma_column(mm_yuv10_sample(own[nx]), mm_yuv10_sample(nb[nx])));
+}
+
+// A whole frame on the host, as the kernel converts it: src is one frame's payload (mm_yuv10_frame_bytes / 2 samples in
+// the host's byte order), dst width * height float4 texels.
+inline void mm_yuv10_to_float_frame_host(const mm_yuv10_float_mode &m, int chroma, const uint16_t *src, int width, int height, float *dst) {
+    const int cw = mm_yuv_cw(width), ch = mm_yuv_ch(height);
+    const uint16_t *cb = src + mm_yuv_cb_offset(width, height), *cr = src + mm_yuv_cr_offset(width, height);
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x)
+            mm_yuv10_to_float(m, mm_yuv10_sample(src[(int64_t)y * width + x]), mm_yuv10_chroma16(chroma, cb, cw, ch, x, y),
+                              mm_yuv10_chroma16(chroma, cr, cw, ch, x, y), dst + ((int64_t)y * width + x) * 4);
 }

@@ -795,6 +795,54 @@ int mmhip_set_image_sequence_yuv420_host(mmhip_invocation *inv, int index, const
     return mmhip_set_image_sequence_device(inv, index, dev, width, height, num_frames);
 }
 
+// The same for payloads of 16-bit samples and a deep drawable: 3 bytes a pixel go up, k_yuv420p10_to_float_clip expands
+// every group into the owned sequence of float4 texels.
+int mmhip_set_image_sequence_yuv420p10_host(mmhip_invocation *inv, int index, const uint16_t *yuv, int64_t frame_stride, int width, int height,
+                                            int num_frames, int matrix, int range, int chroma) {
+    const std::string who = "set_image_sequence_yuv420p10_host: ";
+    size_t bytes = 0;
+    if (check_deep_sequence(who, yuv, false, width, height, num_frames, &bytes) != 0 || check_deep_filter(who, inv) != 0) return -1;
+    const int64_t frame_bytes = mmhip_yuv420p10_frame_bytes(width, height), texel_bytes = (int64_t)width * height * 16;
+    if (frame_stride % 2 != 0) return fail(who + "frame_stride " + std::to_string(frame_stride) + " is odd (the samples are 16-bit)");
+    if (frame_stride < frame_bytes)
+        return fail(who + "frame_stride " + std::to_string(frame_stride) + " is smaller than one frame (" + std::to_string(frame_bytes) + " bytes)");
+    std::string err;
+    // (the converter's own refusals before anything is allocated: the pointers are placeholders)
+    if (check_yuv420p10_to_float_clip((const void *)16, frame_bytes, width, height, 1, matrix, range, chroma, (const void *)16, texel_bytes, &err) != 0)
+        return fail(err);
+    if (!uv_info(inv, index, UvKind::Image)) return -1;
+    const char *text = getenv("MMHIP_CLIP_YUV_IN_BYTES");
+    long long budget = text ? atoll(text) : 0;
+    if (budget <= 0) budget = (long long)256 << 20;
+    const int per_group = (int)std::max<long long>(1, std::min<long long>(std::min(num_frames, 65535), budget / frame_bytes));
+    DeviceBuffer d, staging;
+    HIP_TRY(d.grow(bytes));
+    HIP_TRY(staging.grow((size_t)per_group * (size_t)frame_bytes));
+    hipStream_t s = (hipStream_t)inv->stream;
+    inv->clip_yuv10_input_groups = 0;
+    for (int g0 = 0; g0 < num_frames; g0 += per_group) {
+        const int n = std::min(per_group, num_frames - g0);
+        if (g0) HIP_TRY(hipStreamSynchronize(s));      // the launch before this one reads the staging buffer
+        const char *from = (const char *)yuv + (size_t)g0 * (size_t)frame_stride;
+        if (frame_stride == frame_bytes) HIP_TRY(hipMemcpy(staging.get(), from, (size_t)n * (size_t)frame_bytes, hipMemcpyHostToDevice));
+        else
+            for (int k = 0; k < n; ++k)
+                HIP_TRY(hipMemcpy(staging.get<char>() + (size_t)k * (size_t)frame_bytes, from + (size_t)k * (size_t)frame_stride, (size_t)frame_bytes,
+                                  hipMemcpyHostToDevice));
+        if (mmhip_clip_from_yuv420p10(inv, staging.get(), frame_bytes, width, height, n, matrix, range, chroma,
+                                      d.get<char>() + (size_t)g0 * (size_t)texel_bytes, texel_bytes, s) != 0)
+            return -1;
+        ++inv->clip_yuv10_input_groups;
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    const int slot = inv->image_slot_of_uv[index];
+    release_owned_image(inv, slot);
+    const void *dev = d.get();
+    inv->owned.push_back(std::move(d));
+    bind_deep_image(inv, slot, dev, width, height, num_frames);
+    return 0;
+}
+
 int mmhip_set_image_host(mmhip_invocation *inv, int index, const uint8_t *pixels, int width, int height, int channels) {
     return mmhip_set_image_sequence_host(inv, index, pixels, width, height, channels, 1);
 }

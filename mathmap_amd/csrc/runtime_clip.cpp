@@ -1310,14 +1310,15 @@ long mmhip_clip_from_yuv420_launches(mmhip_invocation *inv, int path) {
 
 int mmhip_clip_yuv_input_groups(mmhip_invocation *inv) { return inv->clip_yuv_input_groups; }
 
-int mmhip_y4m_parse_header(const char *buf, int len, int *width, int *height, int *fps_num, int *fps_den, int *range, int *header_len) {
-    const std::string who = "y4m_parse_header: ";
+// The header of either depth: `bits` null refuses C420p10 with the 8-bit reader's words.
+static int y4m_parse(const std::string &who, const char *buf, int len, int *width, int *height, int *fps_num, int *fps_den, int *range, int *bits,
+                     int *header_len) {
     if (!buf || len < 0) return fail(who + "no buffer");
     const char *nl = (const char *)memchr(buf, '\n', (size_t)len);
     if (len < 9 || memcmp(buf, "YUV4MPEG2", 9) != 0 || (len > 9 && buf[9] != ' ' && buf[9] != '\n'))
         return fail(who + "the stream does not begin with the magic word YUV4MPEG2");
     if (!nl) return fail(who + "no newline within the first " + std::to_string(len) + " bytes: not a stream header");
-    int w = 0, h = 0, num = 25, den = 1, rng = -1;
+    int w = 0, h = 0, num = 25, den = 1, rng = -1, depth = 8;
     // a positive int that fills the whole text, or 0
     auto number = [](const std::string &text) {
         if (text.empty() || text.size() > 9) return 0;
@@ -1346,8 +1347,12 @@ int mmhip_y4m_parse_header(const char *buf, int len, int *width, int *height, in
                 if (value != "p" && value != "?") return fail(who + "an interlaced stream (`" + tag + "'): only progressive frames are read");
                 break;
             case 'C':
+                if (bits && value == "420p10") { depth = 10; break; }
                 if (value != "420jpeg" && value != "420mpeg2" && value != "420paldv" && value != "420")
-                    return fail(who + "the colour space `" + tag + "' is not 8-bit 4:2:0 (C420jpeg, C420mpeg2, C420paldv or C420)");
+                    return fail(who + "the colour space `" + tag + "' is not " +
+                                (bits ? "4:2:0 of 8 or 10 bits (C420jpeg, C420mpeg2, C420paldv, C420 or C420p10)"
+                                      : "8-bit 4:2:0 (C420jpeg, C420mpeg2, C420paldv or C420)"));
+                depth = 8;
                 break;
             case 'X':
                 if (value == "COLORRANGE=FULL") rng = MMHIP_YUV_FULL;
@@ -1362,6 +1367,43 @@ int mmhip_y4m_parse_header(const char *buf, int len, int *width, int *height, in
     if (fps_num) *fps_num = num;
     if (fps_den) *fps_den = den;
     if (range) *range = rng;
+    if (bits) *bits = depth;
     if (header_len) *header_len = (int)(nl - buf) + 1;
     return 0;
 }
+
+int mmhip_y4m_parse_header(const char *buf, int len, int *width, int *height, int *fps_num, int *fps_den, int *range, int *header_len) {
+    return y4m_parse("y4m_parse_header: ", buf, len, width, height, fps_num, fps_den, range, nullptr, header_len);
+}
+
+int mmhip_y4m_parse_stream_header(const char *buf, int len, int *width, int *height, int *fps_num, int *fps_den, int *range, int *bits,
+                                  int *header_len) {
+    int depth = 8;
+    return y4m_parse("y4m_parse_stream_header: ", buf, len, width, height, fps_num, fps_den, range, bits ? bits : &depth, header_len);
+}
+
+// ---- 10-bit planar Y'CbCr 4:2:0 as input (mmhip_clip_from_yuv420p10): Y4M payloads in HBM to float4 texels in HBM ----
+int mmhip_clip_from_yuv420p10(mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height, int num_frames, int matrix,
+                              int range, int chroma, void *dst_float4, int64_t dst_frame_stride, void *stream) {
+    std::string err;
+    if (check_yuv420p10_to_float_clip(src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, dst_float4, dst_frame_stride,
+                                      &err) != 0)
+        return fail(err);
+    if (!inv) return fail("clip_from_yuv420p10: no invocation");
+    hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)inv->stream;
+    int path = 0;
+    if (launch_yuv420p10_to_float_clip(src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, dst_float4, dst_frame_stride,
+                                       inv->ws, s, &path, &err) != 0)
+        return fail(err);
+    ++inv->clip_yuv10_input_launches[path];
+    return 0;
+}
+
+long mmhip_clip_from_yuv420p10_launches(mmhip_invocation *inv, int path) {
+    if (path != MMHIP_YUV10_IN_PATH_ALIGNED && path != MMHIP_YUV10_IN_PATH_SAMPLES)
+        return fail("clip_from_yuv420p10_launches: path must be MMHIP_YUV10_IN_PATH_ALIGNED or MMHIP_YUV10_IN_PATH_SAMPLES (0 or 1), not " +
+                    std::to_string(path));
+    return inv->clip_yuv10_input_launches[path];
+}
+
+int mmhip_clip_yuv10_input_groups(mmhip_invocation *inv) { return inv->clip_yuv10_input_groups; }

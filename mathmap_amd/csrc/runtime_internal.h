@@ -249,6 +249,10 @@ struct mmhip_invocation {
     int clip_yuv_input_groups = 0;
     // 10-bit YUV 4:2:0 output from float frames (mmhip_clip_float_to_yuv420p10): the converter's launches by path
     long clip_yuv10_launches[2] = {0, 0};
+    // 10-bit YUV 4:2:0 input to float frames (mmhip_clip_from_yuv420p10, mmhip_set_image_sequence_yuv420p10_host): the
+    // converter's launches by path, and the upload groups of the last host call
+    long clip_yuv10_input_launches[2] = {0, 0};
+    int clip_yuv10_input_groups = 0;
     uint32_t edge_color_x = 0, edge_color_y = 0;
     float sampling_offset_x = 0.f, sampling_offset_y = 0.f;
     bool timing = false;
