@@ -173,7 +173,13 @@ int mmhip_set_by_name(mmhip_invocation *inv, const char *name, const char *value
 /* Input image from host memory: channels = 3 (RGB8, alpha forced to 255 as
    mathmap_cmdline.c:183 does) or 4 (RGBA8).  Uploaded once, stays in HBM. */
 int mmhip_set_image_host(mmhip_invocation *inv, int index, const uint8_t *pixels, int width, int height, int channels);
-/* Input image already resident in HBM as packed 0xRRGGBBAA uint32 per pixel. */
+/* Input image already resident in HBM as packed 0xRRGGBBAA uint32 per pixel.  Not copied and not owned.
+   Contents rewritten in place: the invocation keeps what it has read from a bound pointer -- frame constants such as
+   in(xy:[0.1, 0.2]) while the prologue is skipped, native results while their memo answers -- and may go on using it
+   for as long as the pointer stays bound.  Calling this setter (or the _sequence_ one) again, with the same pointer, once
+   the writer's work has been waited for or ordered in front of the next render's stream, publishes the new contents to
+   frame constants and native results alike; without that call a later render may show the old contents, the new ones,
+   or both. */
 int mmhip_set_image_device(mmhip_invocation *inv, int index, const void *device_rgba32, int width, int height);
 /* Multi-frame input (an extension; the reference's drawables carry num_frames cache entries, mathmap_cmdline.c:131-184):
    num_frames frames of width x height, packed one after the other -- color_t[num_frames][height][width] in HBM, host
@@ -223,6 +229,9 @@ int mmhip_set_image_sequence_device(mmhip_invocation *inv, int index, const void
    by the invocation.  _device: `device_float4` is already in HBM, 16-byte aligned, not copied and not owned.
    Either replaces whatever was bound to the index, 8-bit or deep (an upload the invocation owned is freed), and an 8-bit
    setter replaces a deep image likewise.  Rebinding makes native results stale.
+   Contents rewritten in place behind a bound _device pointer ("chain in HBM": one filter's float maps are the next one's
+   drawable) follow the rule stated at mmhip_set_image_device: call the setter again with the same pointer to publish
+   them to frame constants and native results; without that call the invocation may keep what it read.
    Native filters (gaussian_blur, convolve, half_convolve, visualize_fft, render()) read their image argument as bytes: a
    call whose argument is a deep image fails that render with a message that names the filter and says that float inputs are
    not supported there; the invocation stays usable.  A closure image whose body fetches a deep image is generated code and
@@ -247,6 +256,11 @@ int mmhip_set_image_sequence_float_device(mmhip_invocation *inv, int index, cons
    number is part of what the native results' memo compares.  Errors: a mode that is neither constant. */
 enum { MMHIP_NATIVE_FRAME_ZERO = 0, MMHIP_NATIVE_FRAME_CURRENT = 1 };
 int mmhip_set_native_input_frame(mmhip_invocation *inv, int mode);
+/* The colours (0xRRGGBBAA) a fetch beyond the left / right and the upper / lower edge returns under edge behaviour
+   "colour".  Frame constants follow a change (the colours are part of what the prologue skip compares), and so do
+   native results: render(in) keeps the drawable's resize wrapper and samples a non-square drawable beyond its edges
+   with these colours, so a change of either colour makes every native result stale.  Setting the colours they
+   already have changes nothing and keeps the results. */
 int mmhip_set_edge_colors(mmhip_invocation *inv, uint32_t color_x, uint32_t color_y);
 int mmhip_set_render_size(mmhip_invocation *inv, int render_width, int render_height);
 /* sub-pixel sampling offset of the slice (mathmap.h:219; -0.5 for the second supersampling pass) */
@@ -910,6 +924,12 @@ long mmhip_direct_native_launches(mmhip_invocation *inv);
 /* Launches of this invocation whose pixels gaussian_blur's tolerance chain wrote (gauss_mode MMHIP_GAUSS_TOLERANCE and the
    conditions stated at mmhip_options.gauss_mode). */
 long mmhip_tolerance_blur_launches(mmhip_invocation *inv);
+/* Launches of the prologue kernel (mm_prologue) that mmhip_render made for this invocation, one per launch, the nested
+   renders of mmhip_render_supersampled included; a render that found its frame constants standing adds nothing. */
+long mmhip_prologue_launches(mmhip_invocation *inv);
+/* Native filter calls of this invocation's single-frame renders that were answered from the memo: same arguments on
+   unchanged inputs, so the map of the earlier call was kept and no native kernel ran for the call. */
+long mmhip_native_memo_hits(mmhip_invocation *inv);
 
 /* device memory helpers for callers without their own allocator */
 void *mmhip_device_alloc(size_t bytes);

@@ -78,6 +78,8 @@ SYMBOLS = {
     "mmhip_drain_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "mmhip_direct_native_launches": (C.c_long, [C.c_void_p]),
     "mmhip_tolerance_blur_launches": (C.c_long, [C.c_void_p]),
+    "mmhip_prologue_launches": (C.c_long, [C.c_void_p]),
+    "mmhip_native_memo_hits": (C.c_long, [C.c_void_p]),
     "mmhip_drain_native_kernel_ms": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int]),
     "mmhip_set_curve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mmhip_set_gradient": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

@@ -817,6 +817,14 @@ class Invocation:
         """Launches whose pixels gaussian_blur's tolerance chain wrote (Filter(gauss_mode="tolerance"))."""
         return lib().mmhip_tolerance_blur_launches(self._h)
 
+    def prologue_launches(self):
+        """Launches of the prologue kernel by render calls (a render whose frame constants stand adds none)."""
+        return lib().mmhip_prologue_launches(self._h)
+
+    def native_memo_hits(self):
+        """Native filter calls of single-frame renders that were answered from the memo."""
+        return lib().mmhip_native_memo_hits(self._h)
+
     def render(self, t=0.0, frame=0):
         """Renders the whole frame and returns it as a uint8 [H,W,4] array (RGBA)."""
         out = np.empty((self.render_height, self.render_width, 4), dtype=np.uint8)

@@ -884,6 +884,9 @@ int mmhip_set_native_input_frame(mmhip_invocation *inv, int mode) {
 }
 
 int mmhip_set_edge_colors(mmhip_invocation *inv, uint32_t cx, uint32_t cy) {
+    // render(in) keeps the drawable's resize wrapper, so k_render_drawable samples beyond the edges with these colours
+    // (set_native_env): a change of either makes the native results stale; the values they have leave the memo alone
+    if (inv->edge_color_x != cx || inv->edge_color_y != cy) ++inv->input_generation;
     inv->edge_color_x = cx;
     inv->edge_color_y = cy;
     return 0;
@@ -961,6 +964,8 @@ int timed_pixel_launch(mmhip_invocation *inv, hipFunction_t f_pix, unsigned grid
 // waits for the last of them.  Returns how many were written (at most `cap`).
 long mmhip_direct_native_launches(mmhip_invocation *inv) { return inv->direct_native_launches; }
 long mmhip_tolerance_blur_launches(mmhip_invocation *inv) { return inv->tolerance_blur_launches; }
+long mmhip_prologue_launches(mmhip_invocation *inv) { return inv->prologue_launches; }
+long mmhip_native_memo_hits(mmhip_invocation *inv) { return inv->native_memo_hits; }
 
 int mmhip_drain_kernel_ms(mmhip_invocation *inv, double *out_ms, int cap) {
     int n = 0;
@@ -1419,6 +1424,7 @@ static int run_natives(mmhip_invocation *inv, mmhip_filter *f, const HArgs &a, h
         if (view_sequence_args(inv, a.frame, *call.func, rec, images_k, &frame_key) != 0) return -1;
         std::vector<unsigned long long> deps;
         if (memo_hit(inv, e, rec, frame_key, want_lo, want_hi, &deps) && !closure_args) {
+            ++inv->native_memo_hits;
             done.push_back(call);
             continue;
         }
@@ -1652,6 +1658,7 @@ int mmhip_render(mmhip_invocation *inv, int frame, float t, int region_x, int re
         if (!fresh) {
             int n = std::max(region_w, a.num_rows);
             HIP_TRY(hipModuleLaunchKernel(f->f_pro, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, s, params, nullptr));
+            ++inv->prologue_launches;
             // the per-row slice (x-const code): once per row of the launch, after the frame constants it reads
             if (f->ks.row_values > 0)
                 HIP_TRY(hipModuleLaunchKernel(f->f_rows, (unsigned)((a.num_rows + 255) / 256), 1, 1, 256, 1, 1, 0, s, params, nullptr));

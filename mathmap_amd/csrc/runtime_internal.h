@@ -207,6 +207,8 @@ struct mmhip_invocation {
     int native_input_frame = 0;                     // mmhip_set_native_input_frame
     long direct_native_launches = 0;                // mmhip_direct_native_launches
     long tolerance_blur_launches = 0;               // mmhip_tolerance_blur_launches
+    long prologue_launches = 0;                     // mmhip_prologue_launches
+    long native_memo_hits = 0;                      // mmhip_native_memo_hits
     // the prologue kernel is skipped while nothing it reads has changed (mmhip_render)
     mm::HArgs pro_args{};
     const mmhip_filter *pro_filter = nullptr;
