@@ -942,6 +942,79 @@ int mmhip_device_count(void);
    current when they are created.  Returns 0, or -1 with mmhip_last_error(). */
 int mmhip_set_device(int ordinal);
 
+/* Chroma siting for the four 4:2:0 converters above.  Everything stated there places a chroma sample at the centre of its
+   2 x 2 luma block (MMHIP_YUV_SITING_CENTER: JPEG siting, C420jpeg), and every function above keeps doing exactly that.
+   H.264, HEVC and AV1 streams under BT.709 and BT.601 carry chroma co-sited with the even luma column of the block and
+   centred between its two rows (MMHIP_YUV_SITING_LEFT: MPEG-2 or "left" siting, C420mpeg2): it is what a decoder writes
+   into a Y4M pipe and what an encoder assumes on the way in.  Read with the wrong siting, the colour planes shift
+   against luma by a quarter of a luma pixel in each direction of the conversion.  The _sited functions below are the
+   functions above with an `int siting` argument after `range` (out) or `chroma` (in): the same parameters, layouts,
+   paths, counters, timing labels and environment variables; the same refusals in the same order under their own names
+   (clip_to_yuv420_sited: ...), and one more, made after the matrix, range and chroma checks and before anything is
+   allocated, launched or bound: "siting must be MMHIP_YUV_SITING_CENTER or MMHIP_YUV_SITING_LEFT (0 or 1), not N".  With
+   MMHIP_YUV_SITING_CENTER each is the function above: the same kernel instantiation, the same bytes.  This statement is
+   the specification of MMHIP_YUV_SITING_LEFT: tests/yuv_sited_reference.py restates it, mathmap_amd/csrc/mm_yuv.h holds
+   it.  Top-left siting (BT.2020) and the siting of C420paldv are not modelled.
+     - Out, left siting (mmhip_clip_to_yuv420_sited, mmhip_clip_float_to_yuv420p10_sited).  Luma is unchanged.  Chroma
+       sample (cx, cy) is computed from six pixels: the columns 2 cx - 1, 2 cx, 2 cx + 1 with the weights 1, 2, 1 -- a
+       column below 0 is column 0, a column at or above width is width - 1 -- and the rows 2 cy and 2 cy + 1 with weight 1
+       each -- a row at or above height is height - 1.  Rs, Gs, Bs are the weighted sums of the bytes at 8 bits, of the
+       quantised channels q (mmhip_clip_float_to_yuv420p10) at 10 bits; the weights sum to 8.  With the mode's
+       coefficients as they stand in the tables above, every / a floor division,
+         8 bits:   Cb = clamp(((cbr * Rs + cbg * Gs + cbb * Bs + 2^18) >> 19) + 128, 0, 255)
+         10 bits:  Cb = clamp(floor((cbr * Rs + cbg * Gs + cbb * Bs + 2^21) / 2^22) + 512, 0, 1023)
+       and Cr likewise.  At 8 bits the sums are at most 2040 and a row's absolute coefficients sum to at most 65 536: the
+       intermediate stays below 2^27, all int32.  At 10 bits the sums reach 524 280; a row's coefficients have both signs,
+       so k . sums and each of its partial sums lies within +-4092 * 524 280 = +-2 145 353 760 and the intermediate with
+       its rounding term in [-2 143 256 608, 2 147 450 912]: twice the centre form's, the upper end 32 736 below 2^31.
+       An int32 would hold that by a margin the centre form changes its scale to avoid, so this one expression is
+       computed in int64, where nothing depends on the margin; the shift leaves -511 .. 511, a sample in 1 .. 1023 before
+       the clamp (pure blue and pure red at full range give 1023).  A chroma row of coefficients sums to 0: grey
+       gives 128 and 512 exactly, as at centre siting.  On a frame whose columns 2 cx - 1, 2 cx, 2 cx + 1 are equal the
+       sample is the centre-sited one (sums of 8 against 4, one more bit of shift).
+     - In, left siting, chroma MMHIP_YUV_CHROMA_BILINEAR (mmhip_clip_from_yuv420_sited, mmhip_clip_from_yuv420p10_sited).
+       Vertically unchanged: with cy = y >> 1 and ny = clamp(cy + (y & 1 ? 1 : -1), 0, ch - 1), the column sum at chroma
+       column i is col(i) = 3 * C[cy][i] + C[ny][i] (at 10 bits of samples read as min(s, 1023)).  Horizontally an even
+       pixel column lies on its chroma column and an odd one half way to the next: with cx = x >> 1 and r = min(cx + 1,
+       cw - 1),
+                   even x                       odd x
+         8 bits:   C' = (4 * col(cx) + 8) >> 4  C' = (2 * col(cx) + 2 * col(r) + 8) >> 4
+         10 bits:  S = 4 * col(cx)              S = 2 * col(cx) + 2 * col(r)
+       the weights sum to 16; the 10-bit S stays at scale 16 and is not rounded.  Everything after the chroma the pixel
+       sees is unchanged: the matrix and the clamps at 8 bits, u = S_cb - 8192, v = S_cr - 8192 and the explicit float32
+       operations at 10.  A work-item reads its own and the right chroma column only, one column fewer than centre
+       siting.
+     - chroma MMHIP_YUV_CHROMA_REPLICATE ignores the siting: either value is accepted and gives the bytes of centre.
+     - The host setters upload and group as the functions above and convert every group with the _sited converter; what
+       the converter refuses is refused under its _sited name before anything is allocated or bound. */
+enum { MMHIP_YUV_SITING_CENTER = 0, MMHIP_YUV_SITING_LEFT = 1 };
+int mmhip_clip_to_yuv420_sited(mmhip_invocation *inv, const void *src_rgba, int64_t src_row_stride, int64_t src_frame_stride, int width,
+                               int height, int first_row, int last_row, int num_frames, int matrix, int range, int siting, void *dst,
+                               int64_t dst_frame_stride, void *stream);
+int mmhip_clip_float_to_yuv420p10_sited(mmhip_invocation *inv, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width,
+                                        int height, int first_row, int last_row, int num_frames, int matrix, int range, int siting, void *dst,
+                                        int64_t dst_frame_stride, void *stream);
+int mmhip_clip_from_yuv420_sited(mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height, int num_frames,
+                                 int matrix, int range, int chroma, int siting, void *dst_rgba32, int64_t dst_frame_stride, void *stream);
+int mmhip_clip_from_yuv420p10_sited(mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height, int num_frames,
+                                    int matrix, int range, int chroma, int siting, void *dst_float4, int64_t dst_frame_stride, void *stream);
+int mmhip_set_image_sequence_yuv420_host_sited(mmhip_invocation *inv, int index, const uint8_t *yuv, int64_t frame_stride, int width,
+                                               int height, int num_frames, int matrix, int range, int chroma, int siting);
+int mmhip_set_image_sequence_yuv420p10_host_sited(mmhip_invocation *inv, int index, const uint16_t *yuv, int64_t frame_stride, int width,
+                                                  int height, int num_frames, int matrix, int range, int chroma, int siting);
+/* The stream header of a YUV4MPEG2 file for frames of `bits` 8 or 10 with a siting (needs no GPU).  With
+   MMHIP_YUV_SITING_CENTER the line of mmhip_y4m_header (bits 8) or mmhip_y4m_header_p10 (bits 10), byte for byte.  With
+   MMHIP_YUV_SITING_LEFT at 8 bits the same line with C420mpeg2 in place of C420jpeg:
+   "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420mpeg2 XCOLORRANGE=LIMITED\n" (or FULL).  At 10 bits the C420p10 line unchanged:
+   Y4M has no tag for the siting of a 10-bit stream, so tell the encoder.  Refuses, by name, bits that are neither, an
+   unknown siting, and what mmhip_y4m_header refuses.  Returns the header's length without the NUL, or -1. */
+int mmhip_y4m_header_sited(char *buf, int cap, int width, int height, int fps_num, int fps_den, int range, int bits, int siting);
+/* The chroma siting a stream header states (needs no GPU): *siting receives MMHIP_YUV_SITING_LEFT for C420mpeg2 and
+   MMHIP_YUV_SITING_CENTER for no C tag, C420, C420jpeg, C420paldv and C420p10.  C420paldv (co-sited columns, Cb and Cr on
+   alternating rows) is not modelled and is read as centre, as mmhip_y4m_parse_header reads it; C420p10 cannot say.
+   Refuses what mmhip_y4m_parse_stream_header refuses, in its words, under the name y4m_stream_siting.  Returns 0, or -1. */
+int mmhip_y4m_stream_siting(const char *buf, int len, int *siting);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,8 @@ MMHIP_YUV_IN_PATH_ALIGNED, MMHIP_YUV_IN_PATH_BYTES = 0, 1
 MMHIP_YUV10_PATH_ALIGNED, MMHIP_YUV10_PATH_BYTES = 0, 1
 # the paths mmhip_clip_from_yuv420p10_launches counts
 MMHIP_YUV10_IN_PATH_ALIGNED, MMHIP_YUV10_IN_PATH_SAMPLES = 0, 1
+# the chroma siting of the mmhip_..._sited converters
+MMHIP_YUV_SITING_CENTER, MMHIP_YUV_SITING_LEFT = 0, 1
 
 # every symbol include/mmhip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -181,6 +183,20 @@ SYMBOLS = {
     "mmhip_copy_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "mmhip_device_count": (C.c_int, []),
     "mmhip_set_device": (C.c_int, [C.c_int]),
+    "mmhip_clip_to_yuv420_sited": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mmhip_clip_float_to_yuv420p10_sited": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mmhip_clip_from_yuv420_sited": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.c_void_p, C.c_int64, C.c_void_p]),
+    "mmhip_clip_from_yuv420p10_sited": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mmhip_set_image_sequence_yuv420_host_sited": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                             C.c_int, C.c_int, C.c_int]),
+    "mmhip_set_image_sequence_yuv420p10_host_sited": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                                C.c_int, C.c_int, C.c_int]),
+    "mmhip_y4m_header_sited": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mmhip_y4m_stream_siting": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
 }
 
 # reference-ABI tier (include/mathmap_hip_backend.h) and its self-test driver

@@ -52,6 +52,8 @@ YUV_MATRICES = {"bt601": 0, "bt709": 1}
 YUV_RANGES = {"limited": 0, "full": 1}
 # set_image_yuv420's and clip_from_yuv420's chroma: mmhip_clip_from_yuv420's modes
 YUV_CHROMAS = {"bilinear": 0, "replicate": 1}
+# the `chroma_siting` keyword: where a chroma sample lies in its 2 x 2 block (the mmhip_..._sited entry points)
+YUV_SITINGS = {"center": 0, "left": 1}
 # the RGBA8 staging buffer of render_clip(pixel_format=...) unless MMHIP_CLIP_YUV_BYTES says otherwise
 CLIP_YUV_BYTES = 1 << 30
 
@@ -119,6 +121,16 @@ def yuv_chroma(chroma):
     return YUV_CHROMAS[chroma]
 
 
+def yuv_siting(chroma_siting):
+    """The `chroma_siting` keyword as the mmhip_..._sited entry points' siting: "center" (C420jpeg, the default everywhere) or
+    "left" (C420mpeg2, what video streams carry).  ValueError for another value.
+    Callers take the _sited entry point only for "left": with "center" they make the call they always made, so that its
+    refusals keep speaking with the unsited function's name (the bytes are the same either way)."""
+    if not isinstance(chroma_siting, str) or chroma_siting not in YUV_SITINGS:
+        raise ValueError("chroma_siting must be one of %s, not %r" % (", ".join(YUV_SITINGS), chroma_siting))
+    return YUV_SITINGS[chroma_siting]
+
+
 def _pixel_format_of(who, buf, pixel_format):
     """The format of the frames `buf`: `pixel_format` where given, else by the dtype (uint16: "yuv420p10").  ValueError for an
     unknown name or a dtype the format does not have."""
@@ -159,9 +171,11 @@ def yuv420_planes(buf, w, h, pixel_format=None):
     return y, cb, cr
 
 
-def y4m_header(w, h, fps=(25, 1), yuv_range="limited", pixel_format="yuv420p"):
+def y4m_header(w, h, fps=(25, 1), yuv_range="limited", pixel_format="yuv420p", chroma_siting="center"):
     """The stream header of a YUV4MPEG2 file (mmhip_y4m_header; for `pixel_format`="yuv420p10" mmhip_y4m_header_p10) as
-    bytes.  Needs no GPU."""
+    bytes.  Needs no GPU.  `chroma_siting`="left" tags an 8-bit stream C420mpeg2 (mmhip_y4m_header_sited); C420p10 has no
+    tag for it and stays as it is."""
+    siting = yuv_siting(chroma_siting)
     if yuv_range not in YUV_RANGES:
         raise ValueError("yuv_range must be one of %s, not %r" % (", ".join(YUV_RANGES), yuv_range))
     if pixel_format not in PIXEL_FORMATS:
@@ -169,18 +183,24 @@ def y4m_header(w, h, fps=(25, 1), yuv_range="limited", pixel_format="yuv420p"):
     num, den = (fps, 1) if isinstance(fps, (int, np.integer)) else fps
     line = C.create_string_buffer(160)
     header = lib().mmhip_y4m_header_p10 if pixel_format == "yuv420p10" else lib().mmhip_y4m_header
-    n = header(line, 160, int(w), int(h), int(num), int(den), YUV_RANGES[yuv_range])
+    if siting:
+        n = lib().mmhip_y4m_header_sited(line, 160, int(w), int(h), int(num), int(den), YUV_RANGES[yuv_range], 10 if pixel_format == "yuv420p10" else 8,
+                                         siting)
+    else:
+        n = header(line, 160, int(w), int(h), int(num), int(den), YUV_RANGES[yuv_range])
     if n < 0:
         raise MathMapError(_err())
     return line.raw[:n]
 
 
-def write_y4m(path_or_file, buf, w, h, fps=(25, 1), yuv_range="limited", pixel_format=None):
+def write_y4m(path_or_file, buf, w, h, fps=(25, 1), yuv_range="limited", pixel_format=None, chroma_siting="center"):
     """Writes frames as render_clip(pixel_format="yuv420p") returns them (uint8 [N, frame_bytes]) as one YUV4MPEG2 file:
     the header, then "FRAME\\n" and the payload per frame.  `path_or_file`: a file name, or a binary file object (which
     stays open).  `fps` = n or (n, d).  The colour matrix has no place in the format: tell the encoder.  The frames of
     "yuv420p10" (uint16 [N, frame_bytes / 2], told by the dtype or by `pixel_format`) go out as C420p10, every sample as
-    two bytes, the low one first."""
+    two bytes, the low one first.  `chroma_siting` names the siting the frames were converted with: "left" writes the tag
+    C420mpeg2 for 8-bit frames (y4m_header); the payloads are written as they are."""
+    yuv_siting(chroma_siting)
     buf = np.asarray(buf)
     if buf.ndim == 1:
         buf = buf[None]
@@ -191,7 +211,7 @@ def write_y4m(path_or_file, buf, w, h, fps=(25, 1), yuv_range="limited", pixel_f
         raise ValueError("write_y4m: %s [N, %d] for frames of %d x %d, not %s %r" % (np.dtype(dtype).name, samples, w, h, buf.dtype, buf.shape))
     if dtype == np.uint16:
         buf = buf.astype("<u2", copy=False)
-    header = y4m_header(w, h, fps, yuv_range, pixel_format)
+    header = y4m_header(w, h, fps, yuv_range, pixel_format, chroma_siting)
     f = open(path_or_file, "wb") if isinstance(path_or_file, (str, bytes)) or hasattr(path_or_file, "__fspath__") else path_or_file
     try:
         f.write(header)
@@ -226,6 +246,22 @@ def y4m_parse_stream_header(data):
     w, h, num, den, rng, bits, header_len = [v.value for v in out]
     names = {v: k for k, v in YUV_RANGES.items()}
     return w, h, (num, den), names.get(rng), header_len, "yuv420p10" if bits == 10 else "yuv420p"
+
+
+def y4m_chroma_siting(data_or_path):
+    """The chroma siting a YUV4MPEG2 stream header states (mmhip_y4m_stream_siting): "left" for C420mpeg2, "center" for no C
+    tag, C420, C420jpeg, C420paldv (not modelled) and C420p10 (which cannot say).  `data_or_path`: the stream's first bytes
+    (bytes, bytearray or memoryview), or a file name, whose first line is read.  Needs no GPU.  ValueError, by name, for what
+    y4m_parse_stream_header refuses."""
+    if isinstance(data_or_path, (bytes, bytearray, memoryview)):
+        data = bytes(data_or_path)
+    else:
+        with open(data_or_path, "rb") as f:
+            data = f.readline(4096)
+    siting = C.c_int(0)
+    if lib().mmhip_y4m_stream_siting(data, len(data), C.byref(siting)) != 0:
+        raise ValueError(_err())
+    return {v: k for k, v in YUV_SITINGS.items()}[siting.value]
 
 
 def read_y4m(path_or_file, max_frames=None, pixel_format="yuv420p"):
@@ -676,14 +712,17 @@ class Invocation:
         n, h, w, c = a.shape
         self._check(lib().mmhip_set_image_sequence_host(self._h, u["index"], a.ctypes.data_as(C.c_void_p), w, h, c, n))
 
-    def set_image_yuv420(self, name, yuv, w, h, yuv_matrix="bt709", yuv_range="limited", chroma="bilinear"):
+    def set_image_yuv420(self, name, yuv, w, h, yuv_matrix="bt709", yuv_range="limited", chroma="bilinear", chroma_siting="center"):
         """Binds planar Y'CbCr 4:2:0 frames as input drawable: `yuv` is uint8 [N, frame_bytes] -- what read_y4m and
         render_clip(pixel_format="yuv420p") return -- or one frame, [frame_bytes], of `w` x `h` pixels.  The payloads go
         up as they are (1.5 bytes per pixel) and are expanded to the drawable's words on the GPU
         (mmhip_set_image_sequence_yuv420_host) in the mode `yuv_matrix`, `yuv_range`, with `chroma` "bilinear" (default)
-        or "replicate"; alpha is 255.  From there on the sequence is what set_image binds."""
+        or "replicate"; alpha is 255.  From there on the sequence is what set_image binds.  `chroma_siting`="left" reads
+        the chroma as co-sited with the even luma columns (C420mpeg2, what decoders emit;
+        mmhip_set_image_sequence_yuv420_host_sited); "replicate" ignores it."""
         matrix, rng = yuv_mode(yuv_matrix, yuv_range)
         mode = yuv_chroma(chroma)
+        siting = yuv_siting(chroma_siting)
         w, h = int(w), int(h)
         if w < 1 or h < 1:
             raise ValueError("set_image_yuv420: w and h must be at least 1, not %d x %d" % (w, h))
@@ -695,18 +734,24 @@ class Invocation:
             raise ValueError("set_image_yuv420: uint8 [N, %d] for frames of %d x %d, not %s %r" % (frame_bytes, w, h, a.dtype, a.shape))
         a = np.ascontiguousarray(a)
         u = self._index(name)
+        if siting:
+            self._check(lib().mmhip_set_image_sequence_yuv420_host_sited(self._h, u["index"], a.ctypes.data_as(C.c_void_p), frame_bytes, w, h,
+                                                                         a.shape[0], matrix, rng, mode, siting))
+            return
         self._check(lib().mmhip_set_image_sequence_yuv420_host(self._h, u["index"], a.ctypes.data_as(C.c_void_p), frame_bytes, w, h, a.shape[0],
                                                                matrix, rng, mode))
 
-    def set_image_yuv420p10(self, name, yuv, w, h, yuv_matrix="bt709", yuv_range="limited", chroma="bilinear"):
+    def set_image_yuv420p10(self, name, yuv, w, h, yuv_matrix="bt709", yuv_range="limited", chroma="bilinear", chroma_siting="center"):
         """Binds 10-bit planar Y'CbCr 4:2:0 frames as float32 input drawable: `yuv` is uint16 [N, frame_bytes / 2] -- what
         read_y4m(pixel_format="yuv420p10") and render_clip(pixel_format="yuv420p10") return -- or one frame, of `w` x `h`
         pixels.  The payloads go up as they are (3 bytes per pixel) and are expanded to float4 texels on the GPU
         (mmhip_set_image_sequence_yuv420p10_host) in the mode `yuv_matrix`, `yuv_range`, with `chroma` "bilinear"
         (default) or "replicate": unclamped, alpha 1.0, no 8-bit step.  From there on the sequence is what set_image
-        binds for a float32 array; the filter must have been compiled with deep_inputs=True."""
+        binds for a float32 array; the filter must have been compiled with deep_inputs=True.  `chroma_siting` as in
+        set_image_yuv420 (mmhip_set_image_sequence_yuv420p10_host_sited)."""
         matrix, rng = yuv_mode(yuv_matrix, yuv_range)
         mode = yuv_chroma(chroma)
+        siting = yuv_siting(chroma_siting)
         w, h = int(w), int(h)
         if w < 1 or h < 1:
             raise ValueError("set_image_yuv420p10: w and h must be at least 1, not %d x %d" % (w, h))
@@ -718,6 +763,10 @@ class Invocation:
             raise ValueError("set_image_yuv420p10: uint16 [N, %d] for frames of %d x %d, not %s %r" % (samples, w, h, a.dtype, a.shape))
         a = np.ascontiguousarray(a, np.uint16)      # (the host's byte order, which the library reads)
         u = self._index(name)
+        if siting:
+            self._check(lib().mmhip_set_image_sequence_yuv420p10_host_sited(self._h, u["index"], a.ctypes.data_as(C.c_void_p), 2 * samples, w, h,
+                                                                            a.shape[0], matrix, rng, mode, siting))
+            return
         self._check(lib().mmhip_set_image_sequence_yuv420p10_host(self._h, u["index"], a.ctypes.data_as(C.c_void_p), 2 * samples, w, h, a.shape[0],
                                                                   matrix, rng, mode))
 
@@ -845,7 +894,7 @@ class Invocation:
     def render_clip(self, num_frames=None, frames=None, ts=None, out_ptr=None, rows=None, region=None, row_stride=None,
                     frame_stride=None, bpp=4, floatmap=False, stream=0, supersample=False, shutter_samples=1, shutter_span=None,
                     shutter=None, shutter_mode="maps", aa=1, aa_threshold=None, aa_refine="list", aa_filter=None, aa_radius=None,
-                    pixel_format=None, yuv_matrix="bt709", yuv_range="limited"):
+                    pixel_format=None, yuv_matrix="bt709", yuv_range="limited", chroma_siting=None):
         """Renders a clip in batched launches (mmhip_render_clip): frame i at frame number frames[i] and time ts[i].
         `num_frames`=N alone is the CLI's animation: frame = i, t = (float)i / (float)N.  `rows` = (first_row,
         last_row) and `region`, `row_stride`, `bpp`, `floatmap`, `stream` as in render_rows; frame i lands
@@ -891,8 +940,16 @@ class Invocation:
         (mmhip_clip_float_to_yuv420p10): the groups are rendered with floatmap=True into a float staging buffer, 16 bytes
         per pixel under the same budget, and converted there.  Without `out_ptr` returns uint16 [N, frame_bytes / 2]
         (little-endian, the value in the low 10 bits); with it the payloads land yuv420_frame_bytes(w, h, "yuv420p10")
-        apart.  Everything else as with "yuv420p"; `supersample`=True with it is a ValueError (that path lands bytes)."""
+        apart.  Everything else as with "yuv420p"; `supersample`=True with it is a ValueError (that path lands bytes).
+        `chroma_siting`="center" (the default with a `pixel_format`: C420jpeg, every call above exactly as it is) or "left"
+        (C420mpeg2, what video encoders assume: mmhip_clip_to_yuv420_sited, mmhip_clip_float_to_yuv420p10_sited) places the
+        chroma samples of either YUV format.  Another value, or `chroma_siting` without a YUV `pixel_format`, is a
+        ValueError."""
         from .striping import animation_frame_t
+        if chroma_siting is not None:
+            if pixel_format is None:
+                raise ValueError("render_clip: chroma_siting goes with pixel_format=\"yuv420p\" or \"yuv420p10\"")
+            yuv_siting(chroma_siting)
         if pixel_format is not None:
             keywords = dict(num_frames=num_frames, frames=frames, ts=ts, supersample=supersample, shutter_samples=shutter_samples,
                             shutter_span=shutter_span, shutter=shutter, shutter_mode=shutter_mode, aa=aa, aa_threshold=aa_threshold,
@@ -905,7 +962,8 @@ class Invocation:
                     raise ValueError("render_clip: pixel_format is not combined with %s: whole RGBA8 frames are converted" % name)
             if pixel_format == "yuv420p10" and supersample:
                 raise ValueError("render_clip: pixel_format=\"yuv420p10\" is not combined with supersample=True: that path lands bytes only")
-            return self._render_clip_yuv420(yuv_mode(yuv_matrix, yuv_range), out_ptr, rows, stream, keywords, pixel_format)
+            return self._render_clip_yuv420(yuv_mode(yuv_matrix, yuv_range), out_ptr, rows, stream, keywords, pixel_format,
+                                            yuv_siting(chroma_siting) if chroma_siting is not None else 0)
         grid = sample_grid(aa)
         filtered = aa_filter is not None
         if aa_radius is not None and not filtered:
@@ -1020,13 +1078,15 @@ class Invocation:
         return out
 
     def clip_to_yuv420(self, src_ptr, dst_ptr, num_frames, width=None, height=None, rows=None, src_row_stride=None, src_frame_stride=None,
-                       dst_frame_stride=None, yuv_matrix="bt709", yuv_range="limited", stream=0):
+                       dst_frame_stride=None, yuv_matrix="bt709", yuv_range="limited", stream=0, chroma_siting="center"):
         """Converts RGBA8 frames in device memory to planar Y'CbCr 4:2:0 payloads in device memory (mmhip_clip_to_yuv420),
         asynchronously.  `src_ptr` is the first converted row of frame 0 -- row rows[0] of the `rows` = (first_row,
         last_row) band, default the whole frame -- rows `src_row_stride` bytes apart (default 4 * width) and frames
         `src_frame_stride` (default: the band's rows); `dst_ptr` is the base of frame 0's payload, frames
-        `dst_frame_stride` apart (default yuv420_frame_bytes).  The size defaults to the render size."""
+        `dst_frame_stride` apart (default yuv420_frame_bytes).  The size defaults to the render size.
+        `chroma_siting`="left" sites the chroma samples as C420mpeg2 does (mmhip_clip_to_yuv420_sited)."""
         matrix, rng = yuv_mode(yuv_matrix, yuv_range)
+        siting = yuv_siting(chroma_siting)
         w = self.render_width if width is None else int(width)
         h = self.render_height if height is None else int(height)
         first_row, last_row = rows if rows is not None else (0, h)
@@ -1036,51 +1096,70 @@ class Invocation:
             src_frame_stride = max(last_row - first_row, 0) * src_row_stride
         if dst_frame_stride is None:
             dst_frame_stride = w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1)
+        if siting:
+            self._check(lib().mmhip_clip_to_yuv420_sited(self._h, C.c_void_p(src_ptr), src_row_stride, src_frame_stride, w, h, first_row, last_row,
+                                                         int(num_frames), matrix, rng, siting, C.c_void_p(dst_ptr), dst_frame_stride,
+                                                         C.c_void_p(stream)))
+            return
         self._check(lib().mmhip_clip_to_yuv420(self._h, C.c_void_p(src_ptr), src_row_stride, src_frame_stride, w, h, first_row, last_row,
                                                int(num_frames), matrix, rng, C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
 
     def clip_from_yuv420(self, src_ptr, dst_ptr, num_frames, width=None, height=None, src_frame_stride=None, dst_frame_stride=None,
-                         yuv_matrix="bt709", yuv_range="limited", chroma="bilinear", stream=0):
+                         yuv_matrix="bt709", yuv_range="limited", chroma="bilinear", stream=0, chroma_siting="center"):
         """Converts planar Y'CbCr 4:2:0 payloads in device memory to drawable words (0xRRGGBBAA, alpha 255) in device
         memory (mmhip_clip_from_yuv420), asynchronously: what set_image_device takes.  Payloads are `src_frame_stride`
         bytes apart (default yuv420_frame_bytes), frames of words `dst_frame_stride` (default 4 * width * height).  The
-        size defaults to the render size."""
+        size defaults to the render size.  `chroma_siting`="left" reads the chroma as C420mpeg2 sites it
+        (mmhip_clip_from_yuv420_sited)."""
         matrix, rng = yuv_mode(yuv_matrix, yuv_range)
         mode = yuv_chroma(chroma)
+        siting = yuv_siting(chroma_siting)
         w = self.render_width if width is None else int(width)
         h = self.render_height if height is None else int(height)
         if src_frame_stride is None:
             src_frame_stride = w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1)
         if dst_frame_stride is None:
             dst_frame_stride = 4 * w * h
+        if siting:
+            self._check(lib().mmhip_clip_from_yuv420_sited(self._h, C.c_void_p(src_ptr), src_frame_stride, w, h, int(num_frames), matrix, rng, mode,
+                                                           siting, C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
+            return
         self._check(lib().mmhip_clip_from_yuv420(self._h, C.c_void_p(src_ptr), src_frame_stride, w, h, int(num_frames), matrix, rng, mode,
                                                  C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
 
     def clip_from_yuv420p10(self, src_ptr, dst_ptr, num_frames, width=None, height=None, src_frame_stride=None, dst_frame_stride=None,
-                            yuv_matrix="bt709", yuv_range="limited", chroma="bilinear", stream=0):
+                            yuv_matrix="bt709", yuv_range="limited", chroma="bilinear", stream=0, chroma_siting="center"):
         """Converts 10-bit planar Y'CbCr 4:2:0 payloads in device memory (16-bit samples) to float4 texels in device
         memory (mmhip_clip_from_yuv420p10), asynchronously: what set_image_device_float takes.  Payloads are
         `src_frame_stride` bytes apart (default yuv420_frame_bytes(w, h, "yuv420p10")), frames of texels
-        `dst_frame_stride` (default 16 * width * height).  The size defaults to the render size."""
+        `dst_frame_stride` (default 16 * width * height).  The size defaults to the render size.  `chroma_siting`="left"
+        reads the chroma as C420mpeg2 sites it (mmhip_clip_from_yuv420p10_sited)."""
         matrix, rng = yuv_mode(yuv_matrix, yuv_range)
         mode = yuv_chroma(chroma)
+        siting = yuv_siting(chroma_siting)
         w = self.render_width if width is None else int(width)
         h = self.render_height if height is None else int(height)
         if src_frame_stride is None:
             src_frame_stride = 2 * (w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1))
         if dst_frame_stride is None:
             dst_frame_stride = 16 * w * h
+        if siting:
+            self._check(lib().mmhip_clip_from_yuv420p10_sited(self._h, C.c_void_p(src_ptr), src_frame_stride, w, h, int(num_frames), matrix, rng, mode,
+                                                              siting, C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
+            return
         self._check(lib().mmhip_clip_from_yuv420p10(self._h, C.c_void_p(src_ptr), src_frame_stride, w, h, int(num_frames), matrix, rng, mode,
                                                     C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
 
     def clip_float_to_yuv420p10(self, src_ptr, dst_ptr, num_frames, width=None, height=None, rows=None, src_row_stride=None,
-                                src_frame_stride=None, dst_frame_stride=None, yuv_matrix="bt709", yuv_range="limited", stream=0):
+                                src_frame_stride=None, dst_frame_stride=None, yuv_matrix="bt709", yuv_range="limited", stream=0,
+                                chroma_siting="center"):
         """Converts float frames in device memory (float4 RGBA, what floatmap=True lands) to 10-bit planar Y'CbCr 4:2:0
         payloads in device memory (mmhip_clip_float_to_yuv420p10), asynchronously.  The arguments are clip_to_yuv420's:
         rows are `src_row_stride` bytes apart (default 16 * width), frames `src_frame_stride` (default: the band's rows),
         payloads `dst_frame_stride` (default yuv420_frame_bytes(w, h, "yuv420p10")).  The size defaults to the render
-        size."""
+        size.  `chroma_siting`="left" sites the chroma samples as C420mpeg2 does (mmhip_clip_float_to_yuv420p10_sited)."""
         matrix, rng = yuv_mode(yuv_matrix, yuv_range)
+        siting = yuv_siting(chroma_siting)
         w = self.render_width if width is None else int(width)
         h = self.render_height if height is None else int(height)
         first_row, last_row = rows if rows is not None else (0, h)
@@ -1090,6 +1169,11 @@ class Invocation:
             src_frame_stride = max(last_row - first_row, 0) * src_row_stride
         if dst_frame_stride is None:
             dst_frame_stride = 2 * (w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1))
+        if siting:
+            self._check(lib().mmhip_clip_float_to_yuv420p10_sited(self._h, C.c_void_p(src_ptr), src_row_stride, src_frame_stride, w, h, first_row,
+                                                                  last_row, int(num_frames), matrix, rng, siting, C.c_void_p(dst_ptr),
+                                                                  dst_frame_stride, C.c_void_p(stream)))
+            return
         self._check(lib().mmhip_clip_float_to_yuv420p10(self._h, C.c_void_p(src_ptr), src_row_stride, src_frame_stride, w, h, first_row, last_row,
                                                         int(num_frames), matrix, rng, C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
 
@@ -1099,7 +1183,7 @@ class Invocation:
             raise ValueError("clip_float_to_yuv420p10_launches: path must be \"aligned\" or \"bytes\", not %r" % (path,))
         return lib().mmhip_clip_float_to_yuv420p10_launches(self._h, 0 if path == "aligned" else 1)
 
-    def _render_clip_yuv420(self, mode, out_ptr, rows, stream, keywords, pixel_format="yuv420p"):
+    def _render_clip_yuv420(self, mode, out_ptr, rows, stream, keywords, pixel_format="yuv420p", siting=0):
         """render_clip(pixel_format="yuv420p"): the clip of `keywords` in groups of frames through an RGBA8 staging buffer;
         with "yuv420p10" through a staging buffer of float maps."""
         import os
@@ -1147,6 +1231,11 @@ class Invocation:
         pixel_bytes = 16 if deep else 4
         band_bytes = (last_row - first_row) * w * pixel_bytes
         convert = lib().mmhip_clip_float_to_yuv420p10 if deep else lib().mmhip_clip_to_yuv420
+        if siting:
+            sited = lib().mmhip_clip_float_to_yuv420p10_sited if deep else lib().mmhip_clip_to_yuv420_sited
+
+            def convert(h, src, row_stride, frame_stride, w, height, first, last, n, matrix, rng, *landing):
+                return sited(h, src, row_stride, frame_stride, w, height, first, last, n, matrix, rng, siting, *landing)
         try:
             budget = int(os.environ.get("MMHIP_CLIP_YUV_BYTES", "") or 0)
         except ValueError:

@@ -134,6 +134,15 @@ void usage() {
            "      --input-chroma=MODE     with a .y4m input: bilinear (default, chroma\n"
            "                              interpolated between the 2 x 2 blocks' centres) or\n"
            "                              replicate (a block's four pixels share its chroma)\n"
+           "      --chroma-siting=SITING  with a .y4m output: center (default, a chroma sample\n"
+           "                              at the centre of its 2 x 2 block, C420jpeg) or left\n"
+           "                              (co-sited with the even luma column, what H.264,\n"
+           "                              HEVC and AV1 encoders assume; an 8-bit stream is\n"
+           "                              tagged C420mpeg2, C420p10 has no tag for it)\n"
+           "      --input-chroma-siting=SITING  with a .y4m input: center (default), left\n"
+           "                              (C420mpeg2, what video decoders emit) or auto (left\n"
+           "                              where the stream's header says C420mpeg2, else\n"
+           "                              center); replicate chroma ignores it\n"
            "\n"
            "Report bugs and suggestions to schani@complang.tuwien.ac.at\n",
            cache_size);
@@ -261,6 +270,7 @@ struct Define { std::string name, value; };
 struct Y4mStream {
     int uv = -1;      // the image user value it is bound to
     int width = 0, height = 0, fps_num = 25, fps_den = 1, range = -1, bits = 8, frames = 0;
+    int siting = MMHIP_YUV_SITING_CENTER;      // what the header's C tag states (mmhip_y4m_stream_siting)
     std::vector<unsigned char> payloads;
 };
 bool is_y4m_name(const std::string &v) { return v == "-" || (v.size() >= 4 && v.compare(v.size() - 4, 4, ".y4m") == 0); }
@@ -285,7 +295,8 @@ bool read_y4m(const std::string &name, int max_frames, Y4mStream &out, std::stri
     read_line(f, line, 4096);
     int header_len = 0;
     if (mmhip_y4m_parse_stream_header(line.data(), (int)line.size(), &out.width, &out.height, &out.fps_num, &out.fps_den, &out.range, &out.bits,
-                                      &header_len) != 0) {
+                                      &header_len) != 0 ||
+        mmhip_y4m_stream_siting(line.data(), (int)line.size(), &out.siting) != 0) {
         err = "`" + name + "': " + mmhip_last_error();
         return done(false);
     }
@@ -336,7 +347,8 @@ enum {
     OPT_VERSION = 256, OPT_HELP, OPT_HTMLDOC, OPT_BENCH_NO_OUTPUT, OPT_BENCH_ONLY_COMPILE,
     OPT_BENCH_NO_COMPILE_TIME_LIMIT, OPT_BENCH_NO_BACKEND, OPT_BENCH_RENDER_COUNT, OPT_GAUSS_MODE, OPT_INPUT_FRAMES, OPT_BATCH_FRAMES,
     OPT_NATIVE_INPUT_FRAME, OPT_SHUTTER_SAMPLES, OPT_SHUTTER, OPT_SHUTTER_MODE, OPT_AA, OPT_AA_THRESHOLD, OPT_AA_REFINE, OPT_AA_FILTER,
-    OPT_YUV_MATRIX, OPT_YUV_RANGE, OPT_FPS, OPT_INPUT_YUV_MATRIX, OPT_INPUT_YUV_RANGE, OPT_INPUT_CHROMA, OPT_PIXEL_FORMAT
+    OPT_YUV_MATRIX, OPT_YUV_RANGE, OPT_FPS, OPT_INPUT_YUV_MATRIX, OPT_INPUT_YUV_RANGE, OPT_INPUT_CHROMA, OPT_PIXEL_FORMAT,
+    OPT_CHROMA_SITING, OPT_INPUT_CHROMA_SITING
 };
 
 int main(int argc, char **argv) {
@@ -357,6 +369,8 @@ int main(int argc, char **argv) {
     bool pixel_format_set = false, deep = false;      // --pixel-format, and whether it is yuv420p10
     int input_yuv_matrix = MMHIP_YUV_BT709, input_yuv_range = -1, input_chroma = MMHIP_YUV_CHROMA_BILINEAR;      // -1: the stream's, else limited
     bool input_yuv_options = false, frames_set = false, fps_set = false;
+    bool chroma_siting_set = false, input_chroma_siting_set = false;
+    int chroma_siting = MMHIP_YUV_SITING_CENTER, input_chroma_siting = MMHIP_YUV_SITING_CENTER;      // the latter -1 for auto: the stream's tag
     const char *generator = nullptr;
     std::vector<Define> defines;
     static struct option long_options[] = {
@@ -379,6 +393,7 @@ int main(int argc, char **argv) {
         {"yuv-range", required_argument, 0, OPT_YUV_RANGE}, {"fps", required_argument, 0, OPT_FPS},
         {"input-yuv-matrix", required_argument, 0, OPT_INPUT_YUV_MATRIX}, {"input-yuv-range", required_argument, 0, OPT_INPUT_YUV_RANGE},
         {"input-chroma", required_argument, 0, OPT_INPUT_CHROMA}, {"pixel-format", required_argument, 0, OPT_PIXEL_FORMAT},
+        {"chroma-siting", required_argument, 0, OPT_CHROMA_SITING}, {"input-chroma-siting", required_argument, 0, OPT_INPUT_CHROMA_SITING},
         {0, 0, 0, 0}};
     for (;;) {
         int idx;
@@ -484,6 +499,19 @@ int main(int argc, char **argv) {
                 else if (!strcmp(optarg, "yuv420p10")) deep = true;
                 else { fprintf(stderr, "Error: --pixel-format takes yuv420p or yuv420p10.\n"); return 1; }
                 pixel_format_set = true;
+                break;
+            case OPT_CHROMA_SITING:
+                if (!strcmp(optarg, "center")) chroma_siting = MMHIP_YUV_SITING_CENTER;
+                else if (!strcmp(optarg, "left")) chroma_siting = MMHIP_YUV_SITING_LEFT;
+                else { fprintf(stderr, "Error: --chroma-siting takes center or left.\n"); return 1; }
+                chroma_siting_set = true;
+                break;
+            case OPT_INPUT_CHROMA_SITING:
+                if (!strcmp(optarg, "center")) input_chroma_siting = MMHIP_YUV_SITING_CENTER;
+                else if (!strcmp(optarg, "left")) input_chroma_siting = MMHIP_YUV_SITING_LEFT;
+                else if (!strcmp(optarg, "auto")) input_chroma_siting = -1;
+                else { fprintf(stderr, "Error: --input-chroma-siting takes center, left or auto.\n"); return 1; }
+                input_chroma_siting_set = true;
                 break;
             case OPT_INPUT_YUV_MATRIX:
                 if (!strcmp(optarg, "bt601")) input_yuv_matrix = MMHIP_YUV_BT601;
@@ -641,6 +669,10 @@ int main(int argc, char **argv) {
         fprintf(stderr, "Error: --yuv-matrix, --yuv-range and --fps go with an output file name ending in .y4m (or -).\n");
         return 1;
     }
+    if (chroma_siting_set && !y4m) {
+        fprintf(stderr, "Error: --chroma-siting goes with an output file name ending in .y4m (or -).\n");
+        return 1;
+    }
     if (pixel_format_set && !y4m) {
         fprintf(stderr, "Error: --pixel-format goes with an output file name ending in .y4m (or -).\n");
         return 1;
@@ -697,6 +729,10 @@ int main(int argc, char **argv) {
         from_stdin += d->value == "-";
         streams.emplace_back();
         streams.back().uv = i;
+    }
+    if (input_chroma_siting_set && streams.empty()) {
+        fprintf(stderr, "Error: --input-chroma-siting goes with an input image whose file name ends in .y4m (or is -).\n");
+        return 1;
     }
     if (input_yuv_options && streams.empty()) {
         fprintf(stderr, "Error: --input-yuv-matrix, --input-yuv-range and --input-chroma go with an input image whose file name ends in .y4m (or is -).\n");
@@ -771,6 +807,22 @@ int main(int argc, char **argv) {
             case MMHIP_UV_IMAGE: {
                 if (const Y4mStream *st = stream_of(i)) {
                     const int range = input_yuv_range >= 0 ? input_yuv_range : st->range >= 0 ? st->range : MMHIP_YUV_LIMITED;
+                    // --input-chroma-siting: left, or auto on a stream tagged C420mpeg2, takes the _sited setters; centre is the call below
+                    const int siting = input_chroma_siting >= 0 ? input_chroma_siting : st->siting;
+                    if (siting != MMHIP_YUV_SITING_CENTER) {
+                        const int rc = st->bits == 10
+                                           ? mmhip_set_image_sequence_yuv420p10_host_sited(inv, i, (const uint16_t *)st->payloads.data(),
+                                                                                           mmhip_yuv420p10_frame_bytes(st->width, st->height), st->width,
+                                                                                           st->height, st->frames, input_yuv_matrix, range, input_chroma, siting)
+                                           : mmhip_set_image_sequence_yuv420_host_sited(inv, i, st->payloads.data(),
+                                                                                        mmhip_yuv420_frame_bytes(st->width, st->height), st->width,
+                                                                                        st->height, st->frames, input_yuv_matrix, range, input_chroma, siting);
+                        if (rc != 0) {
+                            fprintf(stderr, "Error: %s\n", mmhip_last_error());
+                            return 1;
+                        }
+                        break;
+                    }
                     if (st->bits == 10) {
                         // (the bytes of a file are little-endian samples, which is this host's order)
                         if (mmhip_set_image_sequence_yuv420p10_host(inv, i, (const uint16_t *)st->payloads.data(),
@@ -855,7 +907,9 @@ int main(int argc, char **argv) {
         if (!yuv_dev) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
         yuv_host.resize(yuv_frame * batch_frames);
         char header[160];
-        const int header_len = (deep ? mmhip_y4m_header_p10 : mmhip_y4m_header)(header, sizeof header, img_width, img_height, fps_num, fps_den, yuv_range);
+        const bool left = chroma_siting == MMHIP_YUV_SITING_LEFT;      // (an 8-bit stream is then tagged C420mpeg2)
+        const int header_len = left ? mmhip_y4m_header_sited(header, sizeof header, img_width, img_height, fps_num, fps_den, yuv_range, deep ? 10 : 8, chroma_siting)
+                                    : (deep ? mmhip_y4m_header_p10 : mmhip_y4m_header)(header, sizeof header, img_width, img_height, fps_num, fps_den, yuv_range);
         if (header_len < 0) { fprintf(stderr, "Error: %s\n", mmhip_last_error()); return 1; }
         if (!bench_no_output) {
             movie = to_stdout ? stdout : fopen(output_filename, "wb");
@@ -865,6 +919,7 @@ int main(int argc, char **argv) {
             }
         }
     }
+    const bool left_sited = y4m && chroma_siting == MMHIP_YUV_SITING_LEFT;      // --chroma-siting=left: the _sited converters
     for (int render_num = 0; render_num < bench_render_count; ++render_num) {
         const bool last_render = render_num == bench_render_count - 1;      // (the movie holds the frames once)
         for (int first = 0; (batch_frames > 1 || shuttered || y4m) && first < num_frames; first += batch_frames) {
@@ -896,10 +951,18 @@ int main(int argc, char **argv) {
                                : mmhip_render_clip(inv, n, frames.data(), ts.data(), 0, 0, img_width, img_height, 0, img_height, dev,
                                                    img_width * 4, (int64_t)landed_frame, 4, landed_floatmap, nullptr);
             if (rc != 0 ||
-                (y4m && !deep && mmhip_clip_to_yuv420(inv, dev, (int64_t)img_width * 4, (int64_t)output.size(), img_width, img_height, 0, img_height, n,
-                                                      yuv_matrix, yuv_range, yuv_dev, (int64_t)yuv_frame, nullptr) != 0) ||
-                (deep && mmhip_clip_float_to_yuv420p10(inv, dev, (int64_t)img_width * 16, (int64_t)landed_frame, img_width, img_height, 0, img_height, n,
-                                                       yuv_matrix, yuv_range, yuv_dev, (int64_t)yuv_frame, nullptr) != 0) ||
+                (y4m && !deep && !left_sited &&
+                 mmhip_clip_to_yuv420(inv, dev, (int64_t)img_width * 4, (int64_t)output.size(), img_width, img_height, 0, img_height, n, yuv_matrix,
+                                      yuv_range, yuv_dev, (int64_t)yuv_frame, nullptr) != 0) ||
+                (deep && !left_sited &&
+                 mmhip_clip_float_to_yuv420p10(inv, dev, (int64_t)img_width * 16, (int64_t)landed_frame, img_width, img_height, 0, img_height, n, yuv_matrix,
+                                               yuv_range, yuv_dev, (int64_t)yuv_frame, nullptr) != 0) ||
+                (y4m && !deep && left_sited &&
+                 mmhip_clip_to_yuv420_sited(inv, dev, (int64_t)img_width * 4, (int64_t)output.size(), img_width, img_height, 0, img_height, n, yuv_matrix,
+                                            yuv_range, chroma_siting, yuv_dev, (int64_t)yuv_frame, nullptr) != 0) ||
+                (deep && left_sited &&
+                 mmhip_clip_float_to_yuv420p10_sited(inv, dev, (int64_t)img_width * 16, (int64_t)landed_frame, img_width, img_height, 0, img_height, n,
+                                                     yuv_matrix, yuv_range, chroma_siting, yuv_dev, (int64_t)yuv_frame, nullptr) != 0) ||
                 mmhip_sync(inv) != 0) {
                 fprintf(stderr, "Error: %s\n", mmhip_last_error());
                 return 1;

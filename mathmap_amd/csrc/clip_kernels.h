@@ -124,5 +124,33 @@ int check_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, int
                                   const void *dst, int64_t dst_frame_stride, std::string *err);
 int launch_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
                                    void *dst, int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err);
+// The four converters with a chroma siting (MM_YUV_SITING_CENTER or MM_YUV_SITING_LEFT of mm_yuv.h; the mmhip_..._sited
+// entry points state the semantics): the functions above are these with MM_YUV_SITING_CENTER under the name of their
+// entry point, and centre siting reaches the kernel instantiations those always launched.  `name` is the entry point the
+// refusals speak for; they are the unsited function's, in its order, and one more after the modes: a siting that is
+// neither.  Left siting launches the SITING = MM_YUV_SITING_LEFT instantiations; the input converters' replicate mode
+// ignores the siting.  *path (may be null for the RGBA8 converter) receives 0 for the aligned path, 1 for the other.
+int check_rgba8_to_yuv420_clip_sited(const char *name, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
+                                     int first_row, int last_row, int frames, int matrix, int range, int siting, const void *dst,
+                                     int64_t dst_frame_stride, std::string *err);
+int launch_rgba8_to_yuv420_clip_sited(const char *name, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
+                                      int first_row, int last_row, int frames, int matrix, int range, int siting, void *dst,
+                                      int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err);
+int check_float_to_yuv420p10_clip_sited(const char *name, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
+                                        int first_row, int last_row, int frames, int matrix, int range, int siting, const void *dst,
+                                        int64_t dst_frame_stride, std::string *err);
+int launch_float_to_yuv420p10_clip_sited(const char *name, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
+                                         int first_row, int last_row, int frames, int matrix, int range, int siting, void *dst,
+                                         int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err);
+int check_yuv420_to_rgba_clip_sited(const char *name, const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix,
+                                    int range, int chroma, int siting, const void *dst, int64_t dst_frame_stride, std::string *err);
+int launch_yuv420_to_rgba_clip_sited(const char *name, const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix,
+                                     int range, int chroma, int siting, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s,
+                                     int *path, std::string *err);
+int check_yuv420p10_to_float_clip_sited(const char *name, const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix,
+                                        int range, int chroma, int siting, const void *dst, int64_t dst_frame_stride, std::string *err);
+int launch_yuv420p10_to_float_clip_sited(const char *name, const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix,
+                                         int range, int chroma, int siting, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws,
+                                         hipStream_t s, int *path, std::string *err);
 
 }  // namespace mm

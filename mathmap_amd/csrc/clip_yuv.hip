@@ -62,7 +62,33 @@ __device__ __forceinline__ void yuv_four(const mm_yuv_mode &m, yuv_u32x4 top, yu
     *y_bot = yb;
 }
 
-template <int PATH, bool NT>
+// Left siting (SITING = MM_YUV_SITING_LEFT; mmhip_clip_to_yuv420_sited): a chroma sample weighs the pixel columns 2 cx - 1,
+// 2 cx, 2 cx + 1 with 1, 2, 1, so a work-item needs the one pixel column left of its first block next to its own -- its
+// last block's right column is its own.  It takes it with one more load per row, of the pixel at max(first column - 1, 0):
+// a clamped load of 4 bytes out of the cache line its left neighbour reads whole (the neighbouring lane holds the pixel
+// too, but a wave's first lane and a row's first work-item need the load anyway; the lane exchange was not built, so
+// nothing was measured against it).  YUV_WORDS has no right edge to clamp (the width is a multiple of 8), YUV_BYTES
+// clamps the right column of an odd width's last block as centre siting does.  Luma is the centre code's.
+
+// Four pixels of both rows of a row pair: their four luma bytes of each row packed into a word, and per pixel column the
+// sums of the two rows.
+__device__ __forceinline__ void yuv_four_columns(const mm_yuv_mode &m, yuv_u32x4 top, yuv_u32x4 bot, unsigned *y_top, unsigned *y_bot, int col[4][3]) {
+    unsigned yt = 0, yb = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int tr = top[k] & 255u, tg = (top[k] >> 8) & 255u, tb = (top[k] >> 16) & 255u;
+        const int br = bot[k] & 255u, bg = (bot[k] >> 8) & 255u, bb = (bot[k] >> 16) & 255u;
+        yt |= (unsigned)mm_yuv_luma(m, tr, tg, tb) << (8 * k);
+        yb |= (unsigned)mm_yuv_luma(m, br, bg, bb) << (8 * k);
+        col[k][0] = tr + br;
+        col[k][1] = tg + bg;
+        col[k][2] = tb + bb;
+    }
+    *y_top = yt;
+    *y_bot = yb;
+}
+
+template <int PATH, bool NT, int SITING = MM_YUV_SITING_CENTER>
 __global__ void __launch_bounds__(256) k_rgba8_to_yuv420_clip(const YuvArgs a) {
     const unsigned item = blockIdx.x * 256u + threadIdx.x;
     if (item >= a.items) return;
@@ -75,6 +101,67 @@ __global__ void __launch_bounds__(256) k_rgba8_to_yuv420_clip(const YuvArgs a) {
     unsigned char *__restrict__ Y = a.dst + fi * a.dst_frame_stride;
     unsigned char *__restrict__ CB = Y + a.cb_offset, *__restrict__ CR = Y + a.cr_offset;
     const mm_yuv_mode m = a.m;
+    if constexpr (SITING == MM_YUV_SITING_LEFT) {
+        if (PATH == YUV_WORDS) {
+            const yuv_u32x4 *top = (const yuv_u32x4 *)(S + (s0 + at * 32u)), *bot = (const yuv_u32x4 *)(S + (s1 + at * 32u));
+            const unsigned lo = at ? at * 32u - 4u : 0u;      // the pixel left of the first, or the first of the row
+            const yuv_u32x4 t0 = yuv_load<NT>(top), t1 = yuv_load<NT>(top + 1), b0 = yuv_load<NT>(bot), b1 = yuv_load<NT>(bot + 1);
+            const unsigned lt = yuv_load<NT>((const unsigned *)(S + (s0 + lo))), lb = yuv_load<NT>((const unsigned *)(S + (s1 + lo)));
+            yuv_u32x2 yt, yb;
+            unsigned w0, w1;
+            int col[9][3];      // pixel columns 8 at - 1 .. 8 at + 7
+            col[0][0] = (int)((lt & 255u) + (lb & 255u));
+            col[0][1] = (int)(((lt >> 8) & 255u) + ((lb >> 8) & 255u));
+            col[0][2] = (int)(((lt >> 16) & 255u) + ((lb >> 16) & 255u));
+            yuv_four_columns(m, t0, b0, &w0, &w1, col + 1);
+            yt.x = w0;
+            yb.x = w1;
+            yuv_four_columns(m, t1, b1, &w0, &w1, col + 5);
+            yt.y = w0;
+            yb.y = w1;
+            unsigned cb = 0, cr = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int rs = mm_yuv_left_sum(col[2 * k][0], col[2 * k + 1][0], col[2 * k + 2][0]);
+                const int gs = mm_yuv_left_sum(col[2 * k][1], col[2 * k + 1][1], col[2 * k + 2][1]);
+                const int bs = mm_yuv_left_sum(col[2 * k][2], col[2 * k + 1][2], col[2 * k + 2][2]);
+                cb |= (unsigned)mm_yuv_cb_left(m, rs, gs, bs) << (8 * k);
+                cr |= (unsigned)mm_yuv_cr_left(m, rs, gs, bs) << (8 * k);
+            }
+            const unsigned yo = r0 * a.width + at * 8u, co = (r0 >> 1) * a.cw + at * 4u;      // below 2^32: a plane is at most 4 GiB
+            __builtin_nontemporal_store(yt, (yuv_u32x2 *)(Y + yo));
+            if (two) __builtin_nontemporal_store(yb, (yuv_u32x2 *)(Y + (yo + a.width)));
+            __builtin_nontemporal_store(cb, (unsigned *)(CB + co));
+            __builtin_nontemporal_store(cr, (unsigned *)(CR + co));
+            return;
+        }
+        // `at` is the chroma column: pixel columns 2 at - 1 (inside the frame), 2 at and, inside the frame, 2 at + 1
+        const unsigned c0 = 2u * at;
+        const bool wide = c0 + 1u < a.width;
+        const unsigned c1 = wide ? c0 + 1u : c0, cl = at ? c0 - 1u : 0u;
+        const unsigned src_off[6] = {s0 + c0 * 4u, s0 + c1 * 4u, s1 + c0 * 4u, s1 + c1 * 4u, s0 + cl * 4u, s1 + cl * 4u};
+        int rs = 0, gs = 0, bs = 0, luma[4];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const unsigned char *p = S + src_off[k];
+            const int r = yuv_load<NT>(p), g = yuv_load<NT>(p + 1), b = yuv_load<NT>(p + 2);
+            if (k < 4) luma[k] = mm_yuv_luma(m, r, g, b);
+            const int weight = (k == 0 || k == 2) ? 2 : 1;      // the own column 2, its neighbours 1
+            rs += weight * r;
+            gs += weight * g;
+            bs += weight * b;
+        }
+        const unsigned yo = r0 * a.width + c0, co = (r0 >> 1) * a.cw + at;
+        __builtin_nontemporal_store((unsigned char)luma[0], Y + yo);
+        if (wide) __builtin_nontemporal_store((unsigned char)luma[1], Y + (yo + 1u));
+        if (two) {
+            __builtin_nontemporal_store((unsigned char)luma[2], Y + (yo + a.width));
+            if (wide) __builtin_nontemporal_store((unsigned char)luma[3], Y + (yo + a.width + 1u));
+        }
+        __builtin_nontemporal_store((unsigned char)mm_yuv_cb_left(m, rs, gs, bs), CB + co);
+        __builtin_nontemporal_store((unsigned char)mm_yuv_cr_left(m, rs, gs, bs), CR + co);
+        return;
+    }
     if (PATH == YUV_WORDS) {
         const yuv_u32x4 *top = (const yuv_u32x4 *)(S + (s0 + at * 32u)), *bot = (const yuv_u32x4 *)(S + (s1 + at * 32u));
         const yuv_u32x4 t0 = yuv_load<NT>(top), t1 = yuv_load<NT>(top + 1), b0 = yuv_load<NT>(bot), b1 = yuv_load<NT>(bot + 1);
@@ -124,10 +211,11 @@ __global__ void __launch_bounds__(256) k_rgba8_to_yuv420_clip(const YuvArgs a) {
     __builtin_nontemporal_store((unsigned char)mm_yuv_cr(m, rs, gs, bs), CR + co);
 }
 
-int check_rgba8_to_yuv420_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
-                               int last_row, int frames, int matrix, int range, const void *dst, int64_t dst_frame_stride, std::string *err) {
+int check_rgba8_to_yuv420_clip_sited(const char *name, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
+                                     int first_row, int last_row, int frames, int matrix, int range, int siting, const void *dst,
+                                     int64_t dst_frame_stride, std::string *err) {
     (void)src_frame_stride;
-    const std::string who = "clip_to_yuv420: ";
+    const std::string who = std::string(name) + ": ";
     auto no = [&](const std::string &what) {
         *err = who + what;
         return -1;
@@ -137,6 +225,8 @@ int check_rgba8_to_yuv420_clip(const void *src, int64_t src_row_stride, int64_t 
     if (frames > 65535) return no("more than 65535 frames in one call (" + std::to_string(frames) + "); convert the clip in groups");
     if (matrix < 0 || matrix >= MM_YUV_MATRICES) return no("matrix must be MMHIP_YUV_BT601 or MMHIP_YUV_BT709 (0 or 1), not " + std::to_string(matrix));
     if (range < 0 || range >= MM_YUV_RANGES) return no("range must be MMHIP_YUV_LIMITED or MMHIP_YUV_FULL (0 or 1), not " + std::to_string(range));
+    if (!mm_yuv_siting_known(siting))
+        return no("siting must be MMHIP_YUV_SITING_CENTER or MMHIP_YUV_SITING_LEFT (0 or 1), not " + std::to_string(siting));
     if (first_row < 0 || last_row > height || first_row >= last_row)
         return no("rows [" + std::to_string(first_row) + ", " + std::to_string(last_row) + ") are not rows of a frame of " + std::to_string(height));
     if (first_row & 1) return no("first_row must be even, not " + std::to_string(first_row));
@@ -154,11 +244,17 @@ int check_rgba8_to_yuv420_clip(const void *src, int64_t src_row_stride, int64_t 
     return 0;
 }
 
-int launch_rgba8_to_yuv420_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
-                                int last_row, int frames, int matrix, int range, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws,
-                                hipStream_t s, std::string *err) {
-    if (check_rgba8_to_yuv420_clip(src, src_row_stride, src_frame_stride, width, height, first_row, last_row, frames, matrix, range, dst,
-                                   dst_frame_stride, err) != 0)
+int check_rgba8_to_yuv420_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
+                               int last_row, int frames, int matrix, int range, const void *dst, int64_t dst_frame_stride, std::string *err) {
+    return check_rgba8_to_yuv420_clip_sited("clip_to_yuv420", src, src_row_stride, src_frame_stride, width, height, first_row, last_row, frames, matrix,
+                                            range, MM_YUV_SITING_CENTER, dst, dst_frame_stride, err);
+}
+
+int launch_rgba8_to_yuv420_clip_sited(const char *name, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
+                                      int first_row, int last_row, int frames, int matrix, int range, int siting, void *dst,
+                                      int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err) {
+    if (check_rgba8_to_yuv420_clip_sited(name, src, src_row_stride, src_frame_stride, width, height, first_row, last_row, frames, matrix, range, siting,
+                                         dst, dst_frame_stride, err) != 0)
         return -1;
     YuvArgs a;
     a.src = (const unsigned char *)src;
@@ -184,17 +280,30 @@ int launch_rgba8_to_yuv420_clip(const void *src, int64_t src_row_stride, int64_t
     const char *loads = getenv("MMHIP_YUV_LOADS");
     const bool nt = !(loads && !strcmp(loads, "cached"));
     const dim3 grid((a.items + 255u) / 256u, (unsigned)frames);
+    const bool left = siting == MM_YUV_SITING_LEFT;
     ws.timed_launch("yuv420_clip", s, [&] {
-        if (words && nt) k_rgba8_to_yuv420_clip<YUV_WORDS, true><<<grid, 256, 0, s>>>(a);
+        if (left && words && nt) k_rgba8_to_yuv420_clip<YUV_WORDS, true, MM_YUV_SITING_LEFT><<<grid, 256, 0, s>>>(a);
+        else if (left && words) k_rgba8_to_yuv420_clip<YUV_WORDS, false, MM_YUV_SITING_LEFT><<<grid, 256, 0, s>>>(a);
+        else if (left && nt) k_rgba8_to_yuv420_clip<YUV_BYTES, true, MM_YUV_SITING_LEFT><<<grid, 256, 0, s>>>(a);
+        else if (left) k_rgba8_to_yuv420_clip<YUV_BYTES, false, MM_YUV_SITING_LEFT><<<grid, 256, 0, s>>>(a);
+        else if (words && nt) k_rgba8_to_yuv420_clip<YUV_WORDS, true><<<grid, 256, 0, s>>>(a);
         else if (words) k_rgba8_to_yuv420_clip<YUV_WORDS, false><<<grid, 256, 0, s>>>(a);
         else if (nt) k_rgba8_to_yuv420_clip<YUV_BYTES, true><<<grid, 256, 0, s>>>(a);
         else k_rgba8_to_yuv420_clip<YUV_BYTES, false><<<grid, 256, 0, s>>>(a);
     });
     if (hipGetLastError() != hipSuccess) {
-        *err = "clip_to_yuv420: kernel launch failed";
+        *err = std::string(name) + ": kernel launch failed";
         return -1;
     }
+    if (path) *path = words ? YUV_WORDS : YUV_BYTES;
     return 0;
+}
+
+int launch_rgba8_to_yuv420_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
+                                int last_row, int frames, int matrix, int range, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws,
+                                hipStream_t s, std::string *err) {
+    return launch_rgba8_to_yuv420_clip_sited("clip_to_yuv420", src, src_row_stride, src_frame_stride, width, height, first_row, last_row, frames,
+                                             matrix, range, MM_YUV_SITING_CENTER, dst, dst_frame_stride, ws, s, nullptr, err);
 }
 
 }  // namespace mm

@@ -64,7 +64,13 @@ __device__ __forceinline__ void yuv10_store(const unsigned *w, uint16_t *p) {
     __builtin_nontemporal_store(v, (typename yuv10_words<WORDS>::type *)p);
 }
 
-template <int COLS, bool NT>
+// Left siting (SITING = MM_YUV_SITING_LEFT; mmhip_clip_float_to_yuv420p10_sited): a chroma sample weighs the pixel columns
+// 2 cx - 1, 2 cx, 2 cx + 1 with 1, 2, 1, so a work-item needs the one pixel column left of its first block: one more
+// 16-byte load per row, of the pixel at max(first column - 1, 0), out of the cache line its left neighbour reads whole
+// (clamped load; the lane exchange was not built).  The aligned path has no right edge to clamp, COLS = 0 clamps the
+// right column of an odd width's last block as centre siting does.  The matrix over the weighted sums ends 32 736 below
+// 2^31, so mm_yuv10_chroma_left forms it in int64 (three 32 x 32 -> 64 multiply-adds).  Luma is the centre code's.
+template <int COLS, bool NT, int SITING = MM_YUV_SITING_CENTER>
 __global__ void __launch_bounds__(256) k_float_to_yuv420p10_clip(const Yuv10Args a) {
     const unsigned item = blockIdx.x * 256u + threadIdx.x;
     if (item >= a.items) return;
@@ -77,7 +83,74 @@ __global__ void __launch_bounds__(256) k_float_to_yuv420p10_clip(const Yuv10Args
     uint16_t *__restrict__ Y = a.dst + fi * a.dst_frame_samples;
     uint16_t *__restrict__ CB = Y + a.cb_offset, *__restrict__ CR = Y + a.cr_offset;
     const mm_yuv_mode m = a.m;
-    if constexpr (COLS != 0) {
+    if constexpr (SITING == MM_YUV_SITING_LEFT && COLS != 0) {
+        const yuv10_f32x4 *top = (const yuv10_f32x4 *)(S + (s0 + at * (16u * COLS))), *bot = (const yuv10_f32x4 *)(S + (s1 + at * (16u * COLS)));
+        const unsigned lo = at ? at * (16u * COLS) - 16u : 0u;      // the pixel left of the first, or the first of the row
+        yuv10_f32x4 t[COLS], b[COLS];
+#pragma unroll
+        for (int k = 0; k < COLS; ++k) t[k] = yuv10_load<NT>(top + k);
+#pragma unroll
+        for (int k = 0; k < COLS; ++k) b[k] = yuv10_load<NT>(bot + k);
+        const yuv10_f32x4 lt = yuv10_load<NT>((const yuv10_f32x4 *)(S + (s0 + lo))), lb = yuv10_load<NT>((const yuv10_f32x4 *)(S + (s1 + lo)));
+        unsigned yt[COLS / 2], yb[COLS / 2], cb[COLS / 4], cr[COLS / 4];
+#pragma unroll
+        for (int k = 0; k < COLS / 2; ++k) yt[k] = yb[k] = 0;
+#pragma unroll
+        for (int k = 0; k < COLS / 4; ++k) cb[k] = cr[k] = 0;
+        int col[COLS + 1][3];      // pixel columns COLS at - 1 .. COLS at + COLS - 1: the sums of the two rows
+        col[0][0] = mm_yuv10_quant(lt.x) + mm_yuv10_quant(lb.x);
+        col[0][1] = mm_yuv10_quant(lt.y) + mm_yuv10_quant(lb.y);
+        col[0][2] = mm_yuv10_quant(lt.z) + mm_yuv10_quant(lb.z);
+#pragma unroll
+        for (int k = 0; k < COLS; ++k) {
+            const int tr = mm_yuv10_quant(t[k].x), tg = mm_yuv10_quant(t[k].y), tb = mm_yuv10_quant(t[k].z);
+            const int br = mm_yuv10_quant(b[k].x), bg = mm_yuv10_quant(b[k].y), bb = mm_yuv10_quant(b[k].z);
+            yt[k / 2] |= (unsigned)mm_yuv10_luma(m, tr, tg, tb) << (16 * (k & 1));
+            yb[k / 2] |= (unsigned)mm_yuv10_luma(m, br, bg, bb) << (16 * (k & 1));
+            col[1 + k][0] = tr + br;
+            col[1 + k][1] = tg + bg;
+            col[1 + k][2] = tb + bb;
+        }
+#pragma unroll
+        for (int k = 0; k < COLS / 2; ++k) {      // one chroma sample
+            const int rs = mm_yuv_left_sum(col[2 * k][0], col[2 * k + 1][0], col[2 * k + 2][0]);
+            const int gs = mm_yuv_left_sum(col[2 * k][1], col[2 * k + 1][1], col[2 * k + 2][1]);
+            const int bs = mm_yuv_left_sum(col[2 * k][2], col[2 * k + 1][2], col[2 * k + 2][2]);
+            cb[k / 2] |= (unsigned)mm_yuv10_cb_left(m, rs, gs, bs) << (16 * (k & 1));
+            cr[k / 2] |= (unsigned)mm_yuv10_cr_left(m, rs, gs, bs) << (16 * (k & 1));
+        }
+        const unsigned yo = r0 * a.width + at * COLS, co = (r0 >> 1) * a.cw + at * (COLS / 2);      // samples, below 2^31: a plane is at most 4 GiB
+        yuv10_store<COLS / 2>(yt, Y + yo);
+        if (two) yuv10_store<COLS / 2>(yb, Y + (yo + a.width));
+        yuv10_store<COLS / 4>(cb, CB + co);
+        yuv10_store<COLS / 4>(cr, CR + co);
+    } else if constexpr (SITING == MM_YUV_SITING_LEFT) {
+        // `at` is the chroma column: pixel columns 2 at - 1 (inside the frame), 2 at and, inside the frame, 2 at + 1
+        const unsigned c0 = 2u * at;
+        const bool wide = c0 + 1u < a.width;
+        const unsigned c1 = wide ? c0 + 1u : c0, cl = at ? c0 - 1u : 0u;
+        const unsigned src_off[6] = {s0 + c0 * 16u, s0 + c1 * 16u, s1 + c0 * 16u, s1 + c1 * 16u, s0 + cl * 16u, s1 + cl * 16u};
+        int rs = 0, gs = 0, bs = 0, luma[4];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const float *p = (const float *)(S + src_off[k]);
+            const int r = mm_yuv10_quant(yuv10_load<NT>(p)), g = mm_yuv10_quant(yuv10_load<NT>(p + 1)), bl = mm_yuv10_quant(yuv10_load<NT>(p + 2));
+            if (k < 4) luma[k] = mm_yuv10_luma(m, r, g, bl);
+            const int weight = (k == 0 || k == 2) ? 2 : 1;      // the own column 2, its neighbours 1
+            rs += weight * r;
+            gs += weight * g;
+            bs += weight * bl;
+        }
+        const unsigned yo = r0 * a.width + c0, co = (r0 >> 1) * a.cw + at;
+        __builtin_nontemporal_store((uint16_t)luma[0], Y + yo);
+        if (wide) __builtin_nontemporal_store((uint16_t)luma[1], Y + (yo + 1u));
+        if (two) {
+            __builtin_nontemporal_store((uint16_t)luma[2], Y + (yo + a.width));
+            if (wide) __builtin_nontemporal_store((uint16_t)luma[3], Y + (yo + a.width + 1u));
+        }
+        __builtin_nontemporal_store((uint16_t)mm_yuv10_cb_left(m, rs, gs, bs), CB + co);
+        __builtin_nontemporal_store((uint16_t)mm_yuv10_cr_left(m, rs, gs, bs), CR + co);
+    } else if constexpr (COLS != 0) {
         const yuv10_f32x4 *top = (const yuv10_f32x4 *)(S + (s0 + at * (16u * COLS))), *bot = (const yuv10_f32x4 *)(S + (s1 + at * (16u * COLS)));
         yuv10_f32x4 t[COLS], b[COLS];
 #pragma unroll
@@ -138,9 +211,10 @@ __global__ void __launch_bounds__(256) k_float_to_yuv420p10_clip(const Yuv10Args
     }
 }
 
-int check_float_to_yuv420p10_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
-                                  int last_row, int frames, int matrix, int range, const void *dst, int64_t dst_frame_stride, std::string *err) {
-    const std::string who = "clip_float_to_yuv420p10: ";
+int check_float_to_yuv420p10_clip_sited(const char *name, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
+                                        int first_row, int last_row, int frames, int matrix, int range, int siting, const void *dst,
+                                        int64_t dst_frame_stride, std::string *err) {
+    const std::string who = std::string(name) + ": ";
     auto no = [&](const std::string &what) {
         *err = who + what;
         return -1;
@@ -150,6 +224,8 @@ int check_float_to_yuv420p10_clip(const void *src, int64_t src_row_stride, int64
     if (frames > 65535) return no("more than 65535 frames in one call (" + std::to_string(frames) + "); convert the clip in groups");
     if (matrix < 0 || matrix >= MM_YUV_MATRICES) return no("matrix must be MMHIP_YUV_BT601 or MMHIP_YUV_BT709 (0 or 1), not " + std::to_string(matrix));
     if (range < 0 || range >= MM_YUV_RANGES) return no("range must be MMHIP_YUV_LIMITED or MMHIP_YUV_FULL (0 or 1), not " + std::to_string(range));
+    if (!mm_yuv_siting_known(siting))
+        return no("siting must be MMHIP_YUV_SITING_CENTER or MMHIP_YUV_SITING_LEFT (0 or 1), not " + std::to_string(siting));
     if (first_row < 0 || last_row > height || first_row >= last_row)
         return no("rows [" + std::to_string(first_row) + ", " + std::to_string(last_row) + ") are not rows of a frame of " + std::to_string(height));
     if (first_row & 1) return no("first_row must be even, not " + std::to_string(first_row));
@@ -170,11 +246,27 @@ int check_float_to_yuv420p10_clip(const void *src, int64_t src_row_stride, int64
     return 0;
 }
 
-int launch_float_to_yuv420p10_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
-                                   int last_row, int frames, int matrix, int range, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws,
-                                   hipStream_t s, int *path, std::string *err) {
-    if (check_float_to_yuv420p10_clip(src, src_row_stride, src_frame_stride, width, height, first_row, last_row, frames, matrix, range, dst,
-                                      dst_frame_stride, err) != 0)
+int check_float_to_yuv420p10_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
+                                  int last_row, int frames, int matrix, int range, const void *dst, int64_t dst_frame_stride, std::string *err) {
+    return check_float_to_yuv420p10_clip_sited("clip_float_to_yuv420p10", src, src_row_stride, src_frame_stride, width, height, first_row, last_row,
+                                               frames, matrix, range, MM_YUV_SITING_CENTER, dst, dst_frame_stride, err);
+}
+
+template <int SITING>
+static void yuv10_launch(bool aligned, bool eight, bool nt, dim3 grid, hipStream_t s, const Yuv10Args &a) {
+    if (aligned && eight && nt) k_float_to_yuv420p10_clip<8, true, SITING><<<grid, 256, 0, s>>>(a);
+    else if (aligned && eight) k_float_to_yuv420p10_clip<8, false, SITING><<<grid, 256, 0, s>>>(a);
+    else if (aligned && nt) k_float_to_yuv420p10_clip<4, true, SITING><<<grid, 256, 0, s>>>(a);
+    else if (aligned) k_float_to_yuv420p10_clip<4, false, SITING><<<grid, 256, 0, s>>>(a);
+    else if (nt) k_float_to_yuv420p10_clip<0, true, SITING><<<grid, 256, 0, s>>>(a);
+    else k_float_to_yuv420p10_clip<0, false, SITING><<<grid, 256, 0, s>>>(a);
+}
+
+int launch_float_to_yuv420p10_clip_sited(const char *name, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
+                                         int first_row, int last_row, int frames, int matrix, int range, int siting, void *dst,
+                                         int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err) {
+    if (check_float_to_yuv420p10_clip_sited(name, src, src_row_stride, src_frame_stride, width, height, first_row, last_row, frames, matrix, range,
+                                            siting, dst, dst_frame_stride, err) != 0)
         return -1;
     Yuv10Args a;
     a.src = (const unsigned char *)src;
@@ -203,18 +295,21 @@ int launch_float_to_yuv420p10_clip(const void *src, int64_t src_row_stride, int6
     *path = aligned ? 0 : 1;
     const dim3 grid((a.items + 255u) / 256u, (unsigned)frames);
     ws.timed_launch("yuv420p10_clip", s, [&] {
-        if (aligned && eight && nt) k_float_to_yuv420p10_clip<8, true><<<grid, 256, 0, s>>>(a);
-        else if (aligned && eight) k_float_to_yuv420p10_clip<8, false><<<grid, 256, 0, s>>>(a);
-        else if (aligned && nt) k_float_to_yuv420p10_clip<4, true><<<grid, 256, 0, s>>>(a);
-        else if (aligned) k_float_to_yuv420p10_clip<4, false><<<grid, 256, 0, s>>>(a);
-        else if (nt) k_float_to_yuv420p10_clip<0, true><<<grid, 256, 0, s>>>(a);
-        else k_float_to_yuv420p10_clip<0, false><<<grid, 256, 0, s>>>(a);
+        if (siting == MM_YUV_SITING_LEFT) yuv10_launch<MM_YUV_SITING_LEFT>(aligned, eight, nt, grid, s, a);
+        else yuv10_launch<MM_YUV_SITING_CENTER>(aligned, eight, nt, grid, s, a);
     });
     if (hipGetLastError() != hipSuccess) {
-        *err = "clip_float_to_yuv420p10: kernel launch failed";
+        *err = std::string(name) + ": kernel launch failed";
         return -1;
     }
     return 0;
+}
+
+int launch_float_to_yuv420p10_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
+                                   int last_row, int frames, int matrix, int range, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws,
+                                   hipStream_t s, int *path, std::string *err) {
+    return launch_float_to_yuv420p10_clip_sited("clip_float_to_yuv420p10", src, src_row_stride, src_frame_stride, width, height, first_row, last_row,
+                                                frames, matrix, range, MM_YUV_SITING_CENTER, dst, dst_frame_stride, ws, s, path, err);
 }
 
 }  // namespace mm

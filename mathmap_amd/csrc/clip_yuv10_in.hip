@@ -96,7 +96,22 @@ __device__ __forceinline__ void yuv10_in_row(const mm_yuv10_float_mode &m, const
     for (int k = 0; k < COLS; ++k) yuv10_in_store<NT>(m, yuv10_in_sample(y, k), u[k], v[k], out + k);
 }
 
-template <int COLS, int CHROMA, bool NT>
+// Left siting (SITING = MM_YUV_SITING_LEFT, bilinear mode only; mmhip_clip_from_yuv420p10_sited): an even pixel column
+// lies on its chroma column and an odd one half way to the next, so a work-item needs its own NC chroma columns and the one
+// to their right, first + NC clamped to the plane, and nothing to their left: NC + 1 column sums per plane and pixel row
+// where centre siting takes NC + 2.  Replicate mode ignores the siting: the launcher takes the centre instantiation.
+template <int NC>
+__device__ __forceinline__ void yuv10_in_columns_left(const uint16_t *__restrict__ P, unsigned own, unsigned nb, unsigned first, unsigned hi,
+                                                      int col[NC + 1]) {
+    unsigned a[(NC + 1) / 2], b[(NC + 1) / 2];
+    yuv10_in_load<NC>(P + (own + first), a);
+    yuv10_in_load<NC>(P + (nb + first), b);
+#pragma unroll
+    for (int k = 0; k < NC; ++k) col[k] = mm_yuv_chroma_column(yuv10_in_sample(a, k), yuv10_in_sample(b, k));
+    col[NC] = mm_yuv_chroma_column(mm_yuv10_sample(P[own + hi]), mm_yuv10_sample(P[nb + hi]));
+}
+
+template <int COLS, int CHROMA, bool NT, int SITING = MM_YUV_SITING_CENTER>
 __global__ void __launch_bounds__(256) k_yuv420p10_to_float_clip(const Yuv10InArgs a) {
     const unsigned item = blockIdx.x * 256u + threadIdx.x;
     if (item >= a.items) return;
@@ -110,7 +125,49 @@ __global__ void __launch_bounds__(256) k_yuv420p10_to_float_clip(const Yuv10InAr
     const mm_yuv10_float_mode m = a.m;
     // the chroma rows above and below, clamped to the plane: what the upper and the lower pixel row blend with
     const unsigned own = cy * a.cw, up = (cy ? cy - 1u : 0u) * a.cw, down = (cy + 1u < a.ch ? cy + 1u : cy) * a.cw;
-    if constexpr (COLS != 0) {
+    if constexpr (SITING == MM_YUV_SITING_LEFT && COLS != 0) {
+        static_assert(CHROMA == MM_YUV_CHROMA_BILINEAR, "replicate mode has no siting");
+        constexpr int NC = COLS / 2;
+        const unsigned yo = r0 * a.width + at * COLS, first = at * NC;      // below 2^28: a destination frame is at most 4 GiB
+        unsigned y_top[NC], y_bot[NC];
+        yuv10_in_load<COLS>(Y + yo, y_top);
+        if (two) yuv10_in_load<COLS>(Y + (yo + a.width), y_bot);
+        const unsigned hi = first + NC < a.cw ? first + NC : a.cw - 1u;
+        int u[COLS], v[COLS], cu[NC + 1], cv[NC + 1];
+        // pixel k has its own column at index k / 2 of the NC + 1, an odd one its right neighbour one further
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (j && !two) break;
+            yuv10_in_columns_left<NC>(CB, own, j ? down : up, first, hi, cu);
+            yuv10_in_columns_left<NC>(CR, own, j ? down : up, first, hi, cv);
+#pragma unroll
+            for (int k = 0; k < COLS; ++k) {
+                u[k] = mm_yuv10_chroma_blend16_left(cu[k >> 1], cu[(k >> 1) + 1], k & 1);
+                v[k] = mm_yuv10_chroma_blend16_left(cv[k >> 1], cv[(k >> 1) + 1], k & 1);
+            }
+            yuv10_in_row<COLS, NT>(m, j ? y_bot : y_top, u, v, D + (yo + (j ? a.width : 0u)));
+        }
+    } else if constexpr (SITING == MM_YUV_SITING_LEFT) {
+        static_assert(CHROMA == MM_YUV_CHROMA_BILINEAR, "replicate mode has no siting");
+        // `at` is the chroma column: pixel columns 2 at and, inside the frame, 2 at + 1
+        const unsigned c0 = 2u * at;
+        const bool wide = c0 + 1u < a.width;
+        const unsigned right = at + 1u < a.cw ? at + 1u : at;
+        const unsigned yo = r0 * a.width + c0;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (j && !two) break;
+            const unsigned nb = j ? down : up;
+            const int cu = mm_yuv_chroma_column(mm_yuv10_sample(CB[own + at]), mm_yuv10_sample(CB[nb + at]));
+            const int cv = mm_yuv_chroma_column(mm_yuv10_sample(CR[own + at]), mm_yuv10_sample(CR[nb + at]));
+            const unsigned o = yo + (j ? a.width : 0u);
+            yuv10_in_store<NT>(m, mm_yuv10_sample(Y[o]), mm_yuv10_chroma_blend16_left(cu, cu, 0), mm_yuv10_chroma_blend16_left(cv, cv, 0), D + o);
+            if (!wide) continue;
+            const int ru = mm_yuv_chroma_column(mm_yuv10_sample(CB[own + right]), mm_yuv10_sample(CB[nb + right]));
+            const int rv = mm_yuv_chroma_column(mm_yuv10_sample(CR[own + right]), mm_yuv10_sample(CR[nb + right]));
+            yuv10_in_store<NT>(m, mm_yuv10_sample(Y[o + 1u]), mm_yuv10_chroma_blend16_left(cu, ru, 1), mm_yuv10_chroma_blend16_left(cv, rv, 1), D + (o + 1u));
+        }
+    } else if constexpr (COLS != 0) {
         constexpr int NC = COLS / 2;
         const unsigned yo = r0 * a.width + at * COLS, first = at * NC;      // below 2^28: a destination frame is at most 4 GiB
         unsigned y_top[NC], y_bot[NC];
@@ -193,10 +250,15 @@ static void yuv10_in_launch(bool rep, bool nt, dim3 grid, hipStream_t s, const Y
     if (rep) yuv10_in_launch<COLS, MM_YUV_CHROMA_REPLICATE>(nt, grid, s, a);
     else yuv10_in_launch<COLS, MM_YUV_CHROMA_BILINEAR>(nt, grid, s, a);
 }
+template <int COLS>
+static void yuv10_in_launch_left(bool nt, dim3 grid, hipStream_t s, const Yuv10InArgs &a) {
+    if (nt) k_yuv420p10_to_float_clip<COLS, MM_YUV_CHROMA_BILINEAR, true, MM_YUV_SITING_LEFT><<<grid, 256, 0, s>>>(a);
+    else k_yuv420p10_to_float_clip<COLS, MM_YUV_CHROMA_BILINEAR, false, MM_YUV_SITING_LEFT><<<grid, 256, 0, s>>>(a);
+}
 
-int check_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
-                                  const void *dst, int64_t dst_frame_stride, std::string *err) {
-    const std::string who = "clip_from_yuv420p10: ";
+int check_yuv420p10_to_float_clip_sited(const char *name, const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix,
+                                        int range, int chroma, int siting, const void *dst, int64_t dst_frame_stride, std::string *err) {
+    const std::string who = std::string(name) + ": ";
     auto no = [&](const std::string &what) {
         *err = who + what;
         return -1;
@@ -208,6 +270,8 @@ int check_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, int
     if (range < 0 || range >= MM_YUV_RANGES) return no("range must be MMHIP_YUV_LIMITED or MMHIP_YUV_FULL (0 or 1), not " + std::to_string(range));
     if (!mm_yuv_chroma_known(chroma))
         return no("chroma must be MMHIP_YUV_CHROMA_BILINEAR or MMHIP_YUV_CHROMA_REPLICATE (0 or 1), not " + std::to_string(chroma));
+    if (!mm_yuv_siting_known(siting))
+        return no("siting must be MMHIP_YUV_SITING_CENTER or MMHIP_YUV_SITING_LEFT (0 or 1), not " + std::to_string(siting));
     if (!src || !dst) return no("src_yuv and dst_float4 must be device pointers");
     if (((uintptr_t)src | (uintptr_t)src_frame_stride) % 2 != 0) return no("src_yuv and src_frame_stride must be even (the samples are 16-bit)");
     const int64_t frame_bytes = mm_yuv10_frame_bytes(width, height), texel_bytes = (int64_t)width * height * 16;
@@ -221,9 +285,18 @@ int check_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, int
     return 0;
 }
 
-int launch_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
-                                   void *dst, int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err) {
-    if (check_yuv420p10_to_float_clip(src, src_frame_stride, width, height, frames, matrix, range, chroma, dst, dst_frame_stride, err) != 0) return -1;
+int check_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
+                                  const void *dst, int64_t dst_frame_stride, std::string *err) {
+    return check_yuv420p10_to_float_clip_sited("clip_from_yuv420p10", src, src_frame_stride, width, height, frames, matrix, range, chroma,
+                                               MM_YUV_SITING_CENTER, dst, dst_frame_stride, err);
+}
+
+int launch_yuv420p10_to_float_clip_sited(const char *name, const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix,
+                                         int range, int chroma, int siting, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws,
+                                         hipStream_t s, int *path, std::string *err) {
+    if (check_yuv420p10_to_float_clip_sited(name, src, src_frame_stride, width, height, frames, matrix, range, chroma, siting, dst, dst_frame_stride,
+                                            err) != 0)
+        return -1;
     Yuv10InArgs a;
     a.src = (const uint16_t *)src;
     a.dst = (float *)dst;
@@ -247,18 +320,29 @@ int launch_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, in
     a.per_pair = aligned ? a.width / cols : a.cw;
     a.items = a.per_pair * a.ch;
     const dim3 grid((a.items + 255u) / 256u, (unsigned)frames);
+    const bool left = siting == MM_YUV_SITING_LEFT && !rep;      // replicate mode ignores the siting
     ws.timed_launch("yuv420p10_to_float_clip", s, [&] {
-        if (aligned && cols == 8) yuv10_in_launch<8>(rep, nt, grid, s, a);
+        if (left && aligned && cols == 8) yuv10_in_launch_left<8>(nt, grid, s, a);
+        else if (left && aligned && cols == 4) yuv10_in_launch_left<4>(nt, grid, s, a);
+        else if (left && aligned) yuv10_in_launch_left<2>(nt, grid, s, a);
+        else if (left) yuv10_in_launch_left<0>(nt, grid, s, a);
+        else if (aligned && cols == 8) yuv10_in_launch<8>(rep, nt, grid, s, a);
         else if (aligned && cols == 4) yuv10_in_launch<4>(rep, nt, grid, s, a);
         else if (aligned) yuv10_in_launch<2>(rep, nt, grid, s, a);
         else yuv10_in_launch<0>(rep, nt, grid, s, a);
     });
     if (hipGetLastError() != hipSuccess) {
-        *err = "clip_from_yuv420p10: kernel launch failed";
+        *err = std::string(name) + ": kernel launch failed";
         return -1;
     }
     if (path) *path = aligned ? 0 : 1;
     return 0;
+}
+
+int launch_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
+                                   void *dst, int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err) {
+    return launch_yuv420p10_to_float_clip_sited("clip_from_yuv420p10", src, src_frame_stride, width, height, frames, matrix, range, chroma,
+                                                MM_YUV_SITING_CENTER, dst, dst_frame_stride, ws, s, path, err);
 }
 
 }  // namespace mm

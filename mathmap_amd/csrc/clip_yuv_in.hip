@@ -70,7 +70,19 @@ __device__ __forceinline__ void yuv_in_row8(const mm_yuv_rgba_mode &m, yuv_in_u3
     yuv_in_store<NT>(hi, (yuv_in_u32x4 *)out + 1);
 }
 
-template <int PATH, int CHROMA, bool NT>
+// Left siting (SITING = MM_YUV_SITING_LEFT, bilinear mode only; mmhip_clip_from_yuv420_sited): an even pixel column lies
+// on its chroma column and an odd one half way to the next, so a work-item needs its own chroma columns and the one to
+// their right, 4 at + 4 clamped to the plane, and nothing to their left: five column sums per plane and pixel row where
+// centre siting takes six.  Replicate mode ignores the siting: the launcher takes the centre instantiation for it.
+__device__ __forceinline__ void yuv_in_columns_left(const unsigned char *__restrict__ P, unsigned own, unsigned nb, unsigned at4, unsigned hi,
+                                                    int col[5]) {
+    const unsigned a = *(const unsigned *)(P + (own + at4)), b = *(const unsigned *)(P + (nb + at4));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) col[k] = mm_yuv_chroma_column((a >> (8 * k)) & 255u, (b >> (8 * k)) & 255u);
+    col[4] = mm_yuv_chroma_column(P[own + hi], P[nb + hi]);
+}
+
+template <int PATH, int CHROMA, bool NT, int SITING = MM_YUV_SITING_CENTER>
 __global__ void __launch_bounds__(256) k_yuv420_to_rgba_clip(const YuvInArgs a) {
     const unsigned item = blockIdx.x * 256u + threadIdx.x;
     if (item >= a.items) return;
@@ -84,6 +96,47 @@ __global__ void __launch_bounds__(256) k_yuv420_to_rgba_clip(const YuvInArgs a) 
     const mm_yuv_rgba_mode m = a.m;
     // the chroma rows above and below, clamped to the plane: what the upper and the lower pixel row blend with
     const unsigned own = cy * a.cw, up = (cy ? cy - 1u : 0u) * a.cw, down = (cy + 1u < a.ch ? cy + 1u : cy) * a.cw;
+    if constexpr (SITING == MM_YUV_SITING_LEFT) {
+        static_assert(CHROMA == MM_YUV_CHROMA_BILINEAR, "replicate mode has no siting");
+        if (PATH == YUV_IN_WORDS) {
+            const unsigned yo = r0 * a.width + at * 8u, at4 = at * 4u;      // below 2^30: a destination frame is at most 4 GiB
+            const yuv_in_u32x2 y_top = *(const yuv_in_u32x2 *)(Y + yo);
+            const yuv_in_u32x2 y_bot = two ? *(const yuv_in_u32x2 *)(Y + (yo + a.width)) : y_top;
+            const unsigned hi = at4 + 4u < a.cw ? at4 + 4u : a.cw - 1u;
+            int u[8], v[8], cu[5], cv[5];
+            // pixel k of the eight has its own column at index k / 2 of the five, an odd one its right neighbour one further
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                if (j && !two) break;
+                yuv_in_columns_left(CB, own, j ? down : up, at4, hi, cu);
+                yuv_in_columns_left(CR, own, j ? down : up, at4, hi, cv);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    u[k] = mm_yuv_chroma_blend_left(cu[k >> 1], cu[(k >> 1) + 1], k & 1);
+                    v[k] = mm_yuv_chroma_blend_left(cv[k >> 1], cv[(k >> 1) + 1], k & 1);
+                }
+                yuv_in_row8<NT>(m, j ? y_bot : y_top, u, v, D + (yo + (j ? a.width : 0u)));
+            }
+            return;
+        }
+        // `at` is the chroma column: pixel columns 2 at and, inside the frame, 2 at + 1
+        const unsigned c0 = 2u * at;
+        const bool wide = c0 + 1u < a.width;
+        const unsigned right = at + 1u < a.cw ? at + 1u : at;
+        const unsigned yo = r0 * a.width + c0;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (j && !two) break;
+            const unsigned nb = j ? down : up;
+            const int cu = mm_yuv_chroma_column(CB[own + at], CB[nb + at]), cv = mm_yuv_chroma_column(CR[own + at], CR[nb + at]);
+            const unsigned o = yo + (j ? a.width : 0u);
+            yuv_in_store<NT>((unsigned)mm_yuv_to_rgba(m, Y[o], mm_yuv_chroma_blend_left(cu, cu, 0), mm_yuv_chroma_blend_left(cv, cv, 0)), D + o);
+            if (!wide) continue;
+            const int ru = mm_yuv_chroma_column(CB[own + right], CB[nb + right]), rv = mm_yuv_chroma_column(CR[own + right], CR[nb + right]);
+            yuv_in_store<NT>((unsigned)mm_yuv_to_rgba(m, Y[o + 1u], mm_yuv_chroma_blend_left(cu, ru, 1), mm_yuv_chroma_blend_left(cv, rv, 1)), D + (o + 1u));
+        }
+        return;
+    }
     if (PATH == YUV_IN_WORDS) {
         const unsigned yo = r0 * a.width + at * 8u, at4 = at * 4u;      // below 2^30: a destination frame is at most 4 GiB
         const yuv_in_u32x2 y_top = *(const yuv_in_u32x2 *)(Y + yo);
@@ -156,10 +209,15 @@ static void yuv_in_launch(bool nt, dim3 grid, hipStream_t s, const YuvInArgs &a)
     if (nt) k_yuv420_to_rgba_clip<PATH, CHROMA, true><<<grid, 256, 0, s>>>(a);
     else k_yuv420_to_rgba_clip<PATH, CHROMA, false><<<grid, 256, 0, s>>>(a);
 }
+template <int PATH>
+static void yuv_in_launch_left(bool nt, dim3 grid, hipStream_t s, const YuvInArgs &a) {
+    if (nt) k_yuv420_to_rgba_clip<PATH, MM_YUV_CHROMA_BILINEAR, true, MM_YUV_SITING_LEFT><<<grid, 256, 0, s>>>(a);
+    else k_yuv420_to_rgba_clip<PATH, MM_YUV_CHROMA_BILINEAR, false, MM_YUV_SITING_LEFT><<<grid, 256, 0, s>>>(a);
+}
 
-int check_yuv420_to_rgba_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
-                              const void *dst, int64_t dst_frame_stride, std::string *err) {
-    const std::string who = "clip_from_yuv420: ";
+int check_yuv420_to_rgba_clip_sited(const char *name, const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix,
+                                    int range, int chroma, int siting, const void *dst, int64_t dst_frame_stride, std::string *err) {
+    const std::string who = std::string(name) + ": ";
     auto no = [&](const std::string &what) {
         *err = who + what;
         return -1;
@@ -171,6 +229,8 @@ int check_yuv420_to_rgba_clip(const void *src, int64_t src_frame_stride, int wid
     if (range < 0 || range >= MM_YUV_RANGES) return no("range must be MMHIP_YUV_LIMITED or MMHIP_YUV_FULL (0 or 1), not " + std::to_string(range));
     if (!mm_yuv_chroma_known(chroma))
         return no("chroma must be MMHIP_YUV_CHROMA_BILINEAR or MMHIP_YUV_CHROMA_REPLICATE (0 or 1), not " + std::to_string(chroma));
+    if (!mm_yuv_siting_known(siting))
+        return no("siting must be MMHIP_YUV_SITING_CENTER or MMHIP_YUV_SITING_LEFT (0 or 1), not " + std::to_string(siting));
     if (!src || !dst) return no("src_yuv and dst_rgba32 must be device pointers");
     const int64_t frame_bytes = mm_yuv_frame_bytes(width, height), words_bytes = (int64_t)width * height * 4;
     if (src_frame_stride < frame_bytes)
@@ -182,9 +242,17 @@ int check_yuv420_to_rgba_clip(const void *src, int64_t src_frame_stride, int wid
     return 0;
 }
 
-int launch_yuv420_to_rgba_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
-                               void *dst, int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err) {
-    if (check_yuv420_to_rgba_clip(src, src_frame_stride, width, height, frames, matrix, range, chroma, dst, dst_frame_stride, err) != 0) return -1;
+int check_yuv420_to_rgba_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
+                              const void *dst, int64_t dst_frame_stride, std::string *err) {
+    return check_yuv420_to_rgba_clip_sited("clip_from_yuv420", src, src_frame_stride, width, height, frames, matrix, range, chroma, MM_YUV_SITING_CENTER,
+                                           dst, dst_frame_stride, err);
+}
+
+int launch_yuv420_to_rgba_clip_sited(const char *name, const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix,
+                                     int range, int chroma, int siting, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s,
+                                     int *path, std::string *err) {
+    if (check_yuv420_to_rgba_clip_sited(name, src, src_frame_stride, width, height, frames, matrix, range, chroma, siting, dst, dst_frame_stride, err) != 0)
+        return -1;
     YuvInArgs a;
     a.src = (const unsigned char *)src;
     a.dst = (unsigned *)dst;
@@ -208,18 +276,27 @@ int launch_yuv420_to_rgba_clip(const void *src, int64_t src_frame_stride, int wi
     const bool nt = stores && !strcmp(stores, "nt");
     const bool rep = chroma == MM_YUV_CHROMA_REPLICATE;
     const dim3 grid((a.items + 255u) / 256u, (unsigned)frames);
+    const bool left = siting == MM_YUV_SITING_LEFT && !rep;      // replicate mode ignores the siting
     ws.timed_launch("yuv420_to_rgba_clip", s, [&] {
-        if (words && rep) yuv_in_launch<YUV_IN_WORDS, MM_YUV_CHROMA_REPLICATE>(nt, grid, s, a);
+        if (left && words) yuv_in_launch_left<YUV_IN_WORDS>(nt, grid, s, a);
+        else if (left) yuv_in_launch_left<YUV_IN_BYTES>(nt, grid, s, a);
+        else if (words && rep) yuv_in_launch<YUV_IN_WORDS, MM_YUV_CHROMA_REPLICATE>(nt, grid, s, a);
         else if (words) yuv_in_launch<YUV_IN_WORDS, MM_YUV_CHROMA_BILINEAR>(nt, grid, s, a);
         else if (rep) yuv_in_launch<YUV_IN_BYTES, MM_YUV_CHROMA_REPLICATE>(nt, grid, s, a);
         else yuv_in_launch<YUV_IN_BYTES, MM_YUV_CHROMA_BILINEAR>(nt, grid, s, a);
     });
     if (hipGetLastError() != hipSuccess) {
-        *err = "clip_from_yuv420: kernel launch failed";
+        *err = std::string(name) + ": kernel launch failed";
         return -1;
     }
     if (path) *path = words ? YUV_IN_WORDS : YUV_IN_BYTES;
     return 0;
+}
+
+int launch_yuv420_to_rgba_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
+                               void *dst, int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err) {
+    return launch_yuv420_to_rgba_clip_sited("clip_from_yuv420", src, src_frame_stride, width, height, frames, matrix, range, chroma, MM_YUV_SITING_CENTER,
+                                            dst, dst_frame_stride, ws, s, path, err);
 }
 
 }  // namespace mm

@@ -305,3 +305,140 @@ inline void mm_yuv10_to_float_frame_host(const mm_yuv10_float_mode &m, int chrom
             mm_yuv10_to_float(m, mm_yuv10_sample(src[(int64_t)y * width + x]), mm_yuv10_chroma16(chroma, cb, cw, ch, x, y),
                               mm_yuv10_chroma16(chroma, cr, cw, ch, x, y), dst + ((int64_t)y * width + x) * 4);
 }
+
+// ---- left-sited chroma (MPEG-2 siting, C420mpeg2: what H.264, HEVC and AV1 streams carry under BT.709 and BT.601): a
+// chroma sample is co-sited with the even luma column of its block and lies between the block's two rows.  The
+// semantics are stated at mmhip_clip_to_yuv420_sited and its three siblings in include/mmhip.h; everything above is the
+// centre siting (C420jpeg) and stays what it is.  Luma, the coefficient tables, the layout and everything after the chroma
+// a pixel sees are shared with the centre functions. ----
+enum { MM_YUV_SITING_CENTER = 0, MM_YUV_SITING_LEFT = 1, MM_YUV_SITINGS = 2 };
+
+inline bool mm_yuv_siting_known(int siting) { return siting >= 0 && siting < MM_YUV_SITINGS; }
+
+// Out: the weighted sum of a channel over the six pixels of chroma sample (cx, cy), from the sums over the two rows of
+// the pixel columns 2 cx - 1, 2 cx and 2 cx + 1 (clamped to the frame): weights 1, 2, 1 per row, 8 in all.
+MM_YUV_FN int mm_yuv_left_sum(int left_column, int own_column, int right_column) { return left_column + 2 * own_column + right_column; }
+
+// One 8-bit chroma sample from the weighted sums (at most 8 * 255 = 2040 each).  The absolute coefficients of a row sum to
+// at most 65 536 (bt601 and bt709 full: 32768 + 27439 + 5329, 32768 + 29763 + 3005), so |k . sums| <= 65 536 * 2040 =
+// 133 693 440 and with the rounding term 2^18 the intermediate stays below 2^27: an int holds it.  A row sums to 0, so grey
+// gives (2^18 >> 19) + 128 = 128.
+MM_YUV_FN int mm_yuv_chroma_left(int kr, int kg, int kb, int rs, int gs, int bs) {
+    const int c = ((kr * rs + kg * gs + kb * bs + (1 << 18)) >> 19) + 128;
+    return c < 0 ? 0 : c > 255 ? 255 : c;
+}
+MM_YUV_FN int mm_yuv_cb_left(const mm_yuv_mode &m, int rs, int gs, int bs) { return mm_yuv_chroma_left(m.cbr, m.cbg, m.cbb, rs, gs, bs); }
+MM_YUV_FN int mm_yuv_cr_left(const mm_yuv_mode &m, int rs, int gs, int bs) { return mm_yuv_chroma_left(m.crr, m.crg, m.crb, rs, gs, bs); }
+
+// One 10-bit chroma sample from the weighted sums of mm_yuv10_quant values (at most 8 * 65535 = 524 280 each).  A row
+// has coefficients of both signs that sum to 0, so k . sums is largest where the channels of the positive coefficients
+// are full and the others 0: within +-4092 * 524 280 = +-2 145 353 760, and every partial sum within that too.  With the
+// rounding term 2^21 the intermediate lies in [-2 143 256 608, 2 147 450 912]: twice the centre form's, and its upper end
+// 32 736 below 2^31 -- the very margin the centre form goes to scale 2^19 to avoid.  An int32 would hold it, by that
+// hair and for these tables only; the products are formed and summed in int64, where nothing hangs on the margin.  The
+// shift is a floor division; it leaves -511 .. 511, so the sample lies in 1 .. 1023 before the clamp.  Grey gives 512.
+MM_YUV_FN int mm_yuv10_chroma_left(int kr, int kg, int kb, int rs, int gs, int bs) {
+    const int64_t t = (int64_t)kr * rs + (int64_t)kg * gs + (int64_t)kb * bs + ((int64_t)1 << 21);
+    const int c = (int)(t >> 22) + 512;
+    return c < 0 ? 0 : c > 1023 ? 1023 : c;
+}
+MM_YUV_FN int mm_yuv10_cb_left(const mm_yuv_mode &m, int rs, int gs, int bs) { return mm_yuv10_chroma_left(m.cbr, m.cbg, m.cbb, rs, gs, bs); }
+MM_YUV_FN int mm_yuv10_cr_left(const mm_yuv_mode &m, int rs, int gs, int bs) { return mm_yuv10_chroma_left(m.crr, m.crg, m.crb, rs, gs, bs); }
+
+// In, bilinear: an even pixel column lies on its chroma column, an odd one half way to the next.  Chroma column of the
+// right neighbour of pixel column x, clamped to the plane; and the horizontal step over mm_yuv_chroma_column's sums,
+// weights 4 | 2, 2 of 16 in all: rounded once at 8 bits, kept at scale 16 at 10.
+MM_YUV_FN int mm_yuv_chroma_right(int x, int cw) {
+    const int r = (x >> 1) + 1;
+    return r > cw - 1 ? cw - 1 : r;
+}
+MM_YUV_FN int mm_yuv10_chroma_blend16_left(int own_column, int right_column, int odd) { return odd ? 2 * own_column + 2 * right_column : 4 * own_column; }
+MM_YUV_FN int mm_yuv_chroma_blend_left(int own_column, int right_column, int odd) {
+    return (mm_yuv10_chroma_blend16_left(own_column, right_column, odd) + 8) >> 4;
+}
+
+// The chroma pixel (x, y) sees in a plane of cw x ch samples with rows cw apart, left siting.
+MM_YUV_FN int mm_yuv_chroma_bilinear_left(const unsigned char *plane, int cw, int ch, int x, int y) {
+    const int cx = x >> 1, cy = y >> 1, rx = mm_yuv_chroma_right(x, cw), ny = mm_yuv_chroma_neighbour(y, ch);
+    const unsigned char *own = plane + (int64_t)cy * cw, *nb = plane + (int64_t)ny * cw;
+    return mm_yuv_chroma_blend_left(mm_yuv_chroma_column(own[cx], nb[cx]), mm_yuv_chroma_column(own[rx], nb[rx]), x & 1);
+}
+MM_YUV_FN int mm_yuv10_chroma16_left(const uint16_t *plane, int cw, int ch, int x, int y) {
+    const int cx = x >> 1, cy = y >> 1, rx = mm_yuv_chroma_right(x, cw), ny = mm_yuv_chroma_neighbour(y, ch);
+    const uint16_t *own = plane + (int64_t)cy * cw, *nb = plane + (int64_t)ny * cw;
+    return mm_yuv10_chroma_blend16_left(mm_yuv_chroma_column(mm_yuv10_sample(own[cx]), mm_yuv10_sample(nb[cx])),
+                                        mm_yuv_chroma_column(mm_yuv10_sample(own[rx]), mm_yuv10_sample(nb[rx])), x & 1);
+}
+
+// Whole frames on the host with a siting, as the kernels convert them: MM_YUV_SITING_CENTER is the functions above.  The
+// arguments are theirs.
+inline void mm_yuv_frame_host_sited(const mm_yuv_mode &m, int siting, const unsigned char *rgba, int64_t row_stride, int width, int height,
+                                    unsigned char *dst) {
+    mm_yuv_frame_host(m, rgba, row_stride, width, height, dst);
+    if (siting != MM_YUV_SITING_LEFT) return;
+    const int cw = mm_yuv_cw(width), ch = mm_yuv_ch(height);
+    unsigned char *cb = dst + mm_yuv_cb_offset(width, height), *cr = dst + mm_yuv_cr_offset(width, height);
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            int s[3][3];      // [column][channel]
+            for (int i = 0; i < 3; ++i) {
+                const int x = 2 * cx - 1 + i, c = x < 0 ? 0 : x < width ? x : width - 1;
+                s[i][0] = s[i][1] = s[i][2] = 0;
+                for (int j = 0; j < 2; ++j) {
+                    const int r = 2 * cy + j < height ? 2 * cy + j : height - 1;
+                    const unsigned char *p = rgba + r * row_stride + (int64_t)c * 4;
+                    for (int k = 0; k < 3; ++k) s[i][k] += p[k];
+                }
+            }
+            const int rs = mm_yuv_left_sum(s[0][0], s[1][0], s[2][0]), gs = mm_yuv_left_sum(s[0][1], s[1][1], s[2][1]),
+                      bs = mm_yuv_left_sum(s[0][2], s[1][2], s[2][2]);
+            cb[(int64_t)cy * cw + cx] = (unsigned char)mm_yuv_cb_left(m, rs, gs, bs);
+            cr[(int64_t)cy * cw + cx] = (unsigned char)mm_yuv_cr_left(m, rs, gs, bs);
+        }
+}
+
+inline void mm_yuv10_frame_host_sited(const mm_yuv_mode &m, int siting, const float *src, int64_t row_stride, int width, int height, uint16_t *dst) {
+    mm_yuv10_frame_host(m, src, row_stride, width, height, dst);
+    if (siting != MM_YUV_SITING_LEFT) return;
+    const int cw = mm_yuv_cw(width), ch = mm_yuv_ch(height);
+    uint16_t *cb = dst + mm_yuv_cb_offset(width, height), *cr = dst + mm_yuv_cr_offset(width, height);
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            int s[3][3];      // [column][channel]
+            for (int i = 0; i < 3; ++i) {
+                const int x = 2 * cx - 1 + i, c = x < 0 ? 0 : x < width ? x : width - 1;
+                s[i][0] = s[i][1] = s[i][2] = 0;
+                for (int j = 0; j < 2; ++j) {
+                    const int r = 2 * cy + j < height ? 2 * cy + j : height - 1;
+                    const float *p = (const float *)((const char *)src + r * row_stride) + (int64_t)c * 4;
+                    for (int k = 0; k < 3; ++k) s[i][k] += mm_yuv10_quant(p[k]);
+                }
+            }
+            const int rs = mm_yuv_left_sum(s[0][0], s[1][0], s[2][0]), gs = mm_yuv_left_sum(s[0][1], s[1][1], s[2][1]),
+                      bs = mm_yuv_left_sum(s[0][2], s[1][2], s[2][2]);
+            cb[(int64_t)cy * cw + cx] = (uint16_t)mm_yuv10_cb_left(m, rs, gs, bs);
+            cr[(int64_t)cy * cw + cx] = (uint16_t)mm_yuv10_cr_left(m, rs, gs, bs);
+        }
+}
+
+inline void mm_yuv_to_rgba_frame_host_sited(const mm_yuv_rgba_mode &m, int chroma, int siting, const unsigned char *src, int width, int height,
+                                            uint32_t *dst) {
+    if (siting != MM_YUV_SITING_LEFT || chroma == MM_YUV_CHROMA_REPLICATE) return mm_yuv_to_rgba_frame_host(m, chroma, src, width, height, dst);
+    const int cw = mm_yuv_cw(width), ch = mm_yuv_ch(height);
+    const unsigned char *cb = src + mm_yuv_cb_offset(width, height), *cr = src + mm_yuv_cr_offset(width, height);
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x)
+            dst[(int64_t)y * width + x] = mm_yuv_to_rgba(m, src[(int64_t)y * width + x], mm_yuv_chroma_bilinear_left(cb, cw, ch, x, y),
+                                                         mm_yuv_chroma_bilinear_left(cr, cw, ch, x, y));
+}
+
+inline void mm_yuv10_to_float_frame_host_sited(const mm_yuv10_float_mode &m, int chroma, int siting, const uint16_t *src, int width, int height,
+                                               float *dst) {
+    if (siting != MM_YUV_SITING_LEFT || chroma == MM_YUV_CHROMA_REPLICATE) return mm_yuv10_to_float_frame_host(m, chroma, src, width, height, dst);
+    const int cw = mm_yuv_cw(width), ch = mm_yuv_ch(height);
+    const uint16_t *cb = src + mm_yuv_cb_offset(width, height), *cr = src + mm_yuv_cr_offset(width, height);
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x)
+            mm_yuv10_to_float(m, mm_yuv10_sample(src[(int64_t)y * width + x]), mm_yuv10_chroma16_left(cb, cw, ch, x, y),
+                              mm_yuv10_chroma16_left(cr, cw, ch, x, y), dst + ((int64_t)y * width + x) * 4);
+}

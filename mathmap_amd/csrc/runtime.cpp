@@ -743,9 +743,10 @@ int mmhip_set_image_sequence_float_host(mmhip_invocation *inv, int index, const 
 
 // Planar Y'CbCr 4:2:0 payloads as a sequence: they go up as they are, in groups through a staging buffer of at most
 // MMHIP_CLIP_YUV_IN_BYTES, and k_yuv420_to_rgba_clip expands every group into the owned sequence.
-int mmhip_set_image_sequence_yuv420_host(mmhip_invocation *inv, int index, const uint8_t *yuv, int64_t frame_stride, int width, int height,
-                                         int num_frames, int matrix, int range, int chroma) {
-    const std::string who = "set_image_sequence_yuv420_host: ";
+static int set_image_sequence_yuv420_host(const std::string &name, bool sited, mmhip_invocation *inv, int index, const uint8_t *yuv, int64_t frame_stride, int width,
+                                          int height, int num_frames, int matrix, int range, int chroma, int siting) {
+    const std::string who = name + ": ";
+    const char *converter = sited ? "clip_from_yuv420_sited" : "clip_from_yuv420";
     if (width < 1 || height < 1) return fail(who + "width and height must be at least 1, not " + std::to_string(width) + " x " + std::to_string(height));
     if (num_frames < 1) return fail("num_frames must be at least 1");
     size_t bytes = 0;
@@ -756,7 +757,8 @@ int mmhip_set_image_sequence_yuv420_host(mmhip_invocation *inv, int index, const
         return fail(who + "frame_stride " + std::to_string(frame_stride) + " is smaller than one frame (" + std::to_string(frame_bytes) + " bytes)");
     std::string err;
     // (the converter's own refusals before anything is allocated: the pointers are placeholders)
-    if (check_yuv420_to_rgba_clip(yuv, frame_bytes, width, height, 1, matrix, range, chroma, yuv, words_bytes, &err) != 0) return fail(err);
+    if (check_yuv420_to_rgba_clip_sited(converter, yuv, frame_bytes, width, height, 1, matrix, range, chroma, siting, yuv, words_bytes, &err) != 0)
+        return fail(err);
     if (!uv_info(inv, index, UvKind::Image)) return -1;
     const char *text = getenv("MMHIP_CLIP_YUV_IN_BYTES");
     long long budget = text ? atoll(text) : 0;
@@ -776,8 +778,9 @@ int mmhip_set_image_sequence_yuv420_host(mmhip_invocation *inv, int index, const
             for (int k = 0; k < n; ++k)
                 HIP_TRY(hipMemcpy(staging.get<char>() + (size_t)k * (size_t)frame_bytes, from + (size_t)k * (size_t)frame_stride, (size_t)frame_bytes,
                                   hipMemcpyHostToDevice));
-        if (mmhip_clip_from_yuv420(inv, staging.get(), frame_bytes, width, height, n, matrix, range, chroma, d.get<char>() + (size_t)g0 * (size_t)words_bytes,
-                                   words_bytes, s) != 0)
+        void *to = d.get<char>() + (size_t)g0 * (size_t)words_bytes;
+        if ((sited ? mmhip_clip_from_yuv420_sited(inv, staging.get(), frame_bytes, width, height, n, matrix, range, chroma, siting, to, words_bytes, s)
+                   : mmhip_clip_from_yuv420(inv, staging.get(), frame_bytes, width, height, n, matrix, range, chroma, to, words_bytes, s)) != 0)
             return -1;
         ++inv->clip_yuv_input_groups;
     }
@@ -795,11 +798,24 @@ int mmhip_set_image_sequence_yuv420_host(mmhip_invocation *inv, int index, const
     return mmhip_set_image_sequence_device(inv, index, dev, width, height, num_frames);
 }
 
+int mmhip_set_image_sequence_yuv420_host(mmhip_invocation *inv, int index, const uint8_t *yuv, int64_t frame_stride, int width, int height,
+                                         int num_frames, int matrix, int range, int chroma) {
+    return set_image_sequence_yuv420_host("set_image_sequence_yuv420_host", false, inv, index, yuv, frame_stride, width, height, num_frames, matrix, range, chroma,
+                                          MMHIP_YUV_SITING_CENTER);
+}
+
+int mmhip_set_image_sequence_yuv420_host_sited(mmhip_invocation *inv, int index, const uint8_t *yuv, int64_t frame_stride, int width, int height,
+                                               int num_frames, int matrix, int range, int chroma, int siting) {
+    return set_image_sequence_yuv420_host("set_image_sequence_yuv420_host_sited", true, inv, index, yuv, frame_stride, width, height, num_frames, matrix, range,
+                                          chroma, siting);
+}
+
 // The same for payloads of 16-bit samples and a deep drawable: 3 bytes a pixel go up, k_yuv420p10_to_float_clip expands
 // every group into the owned sequence of float4 texels.
-int mmhip_set_image_sequence_yuv420p10_host(mmhip_invocation *inv, int index, const uint16_t *yuv, int64_t frame_stride, int width, int height,
-                                            int num_frames, int matrix, int range, int chroma) {
-    const std::string who = "set_image_sequence_yuv420p10_host: ";
+static int set_image_sequence_yuv420p10_host(const std::string &name, bool sited, mmhip_invocation *inv, int index, const uint16_t *yuv, int64_t frame_stride,
+                                             int width, int height, int num_frames, int matrix, int range, int chroma, int siting) {
+    const std::string who = name + ": ";
+    const char *converter = sited ? "clip_from_yuv420p10_sited" : "clip_from_yuv420p10";
     size_t bytes = 0;
     if (check_deep_sequence(who, yuv, false, width, height, num_frames, &bytes) != 0 || check_deep_filter(who, inv) != 0) return -1;
     const int64_t frame_bytes = mmhip_yuv420p10_frame_bytes(width, height), texel_bytes = (int64_t)width * height * 16;
@@ -808,7 +824,8 @@ int mmhip_set_image_sequence_yuv420p10_host(mmhip_invocation *inv, int index, co
         return fail(who + "frame_stride " + std::to_string(frame_stride) + " is smaller than one frame (" + std::to_string(frame_bytes) + " bytes)");
     std::string err;
     // (the converter's own refusals before anything is allocated: the pointers are placeholders)
-    if (check_yuv420p10_to_float_clip((const void *)16, frame_bytes, width, height, 1, matrix, range, chroma, (const void *)16, texel_bytes, &err) != 0)
+    if (check_yuv420p10_to_float_clip_sited(converter, (const void *)16, frame_bytes, width, height, 1, matrix, range, chroma, siting, (const void *)16,
+                                            texel_bytes, &err) != 0)
         return fail(err);
     if (!uv_info(inv, index, UvKind::Image)) return -1;
     const char *text = getenv("MMHIP_CLIP_YUV_IN_BYTES");
@@ -829,8 +846,9 @@ int mmhip_set_image_sequence_yuv420p10_host(mmhip_invocation *inv, int index, co
             for (int k = 0; k < n; ++k)
                 HIP_TRY(hipMemcpy(staging.get<char>() + (size_t)k * (size_t)frame_bytes, from + (size_t)k * (size_t)frame_stride, (size_t)frame_bytes,
                                   hipMemcpyHostToDevice));
-        if (mmhip_clip_from_yuv420p10(inv, staging.get(), frame_bytes, width, height, n, matrix, range, chroma,
-                                      d.get<char>() + (size_t)g0 * (size_t)texel_bytes, texel_bytes, s) != 0)
+        void *to = d.get<char>() + (size_t)g0 * (size_t)texel_bytes;
+        if ((sited ? mmhip_clip_from_yuv420p10_sited(inv, staging.get(), frame_bytes, width, height, n, matrix, range, chroma, siting, to, texel_bytes, s)
+                   : mmhip_clip_from_yuv420p10(inv, staging.get(), frame_bytes, width, height, n, matrix, range, chroma, to, texel_bytes, s)) != 0)
             return -1;
         ++inv->clip_yuv10_input_groups;
     }
@@ -841,6 +859,18 @@ int mmhip_set_image_sequence_yuv420p10_host(mmhip_invocation *inv, int index, co
     inv->owned.push_back(std::move(d));
     bind_deep_image(inv, slot, dev, width, height, num_frames);
     return 0;
+}
+
+int mmhip_set_image_sequence_yuv420p10_host(mmhip_invocation *inv, int index, const uint16_t *yuv, int64_t frame_stride, int width, int height,
+                                            int num_frames, int matrix, int range, int chroma) {
+    return set_image_sequence_yuv420p10_host("set_image_sequence_yuv420p10_host", false, inv, index, yuv, frame_stride, width, height, num_frames, matrix, range,
+                                             chroma, MMHIP_YUV_SITING_CENTER);
+}
+
+int mmhip_set_image_sequence_yuv420p10_host_sited(mmhip_invocation *inv, int index, const uint16_t *yuv, int64_t frame_stride, int width, int height,
+                                                  int num_frames, int matrix, int range, int chroma, int siting) {
+    return set_image_sequence_yuv420p10_host("set_image_sequence_yuv420p10_host_sited", true, inv, index, yuv, frame_stride, width, height, num_frames, matrix,
+                                             range, chroma, siting);
 }
 
 int mmhip_set_image_host(mmhip_invocation *inv, int index, const uint8_t *pixels, int width, int height, int channels) {

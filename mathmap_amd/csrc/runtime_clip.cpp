@@ -1213,31 +1213,61 @@ int64_t mmhip_yuv420_frame_bytes(int width, int height) {
     return mm_yuv_frame_bytes(width, height);
 }
 
-int mmhip_y4m_header(char *buf, int cap, int width, int height, int fps_num, int fps_den, int range) {
-    if (width < 1 || height < 1) return fail("y4m_header: width and height must be at least 1");
-    if (fps_num < 1 || fps_den < 1) return fail("y4m_header: fps_num and fps_den must be at least 1");
+// One stream header line under the name of its entry point: the colour space tag is the only thing that varies.
+static int y4m_header_line(const std::string &who, const char *tag, char *buf, int cap, int width, int height, int fps_num, int fps_den, int range) {
+    if (width < 1 || height < 1) return fail(who + "width and height must be at least 1");
+    if (fps_num < 1 || fps_den < 1) return fail(who + "fps_num and fps_den must be at least 1");
     if (range != MMHIP_YUV_LIMITED && range != MMHIP_YUV_FULL)
-        return fail("y4m_header: range must be MMHIP_YUV_LIMITED or MMHIP_YUV_FULL (0 or 1), not " + std::to_string(range));
+        return fail(who + "range must be MMHIP_YUV_LIMITED or MMHIP_YUV_FULL (0 or 1), not " + std::to_string(range));
     char line[160];
-    const int n = snprintf(line, sizeof line, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=%s\n", width, height, fps_num, fps_den,
+    const int n = snprintf(line, sizeof line, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 %s XCOLORRANGE=%s\n", width, height, fps_num, fps_den, tag,
                            range == MMHIP_YUV_FULL ? "FULL" : "LIMITED");
-    if (!buf || cap < n + 1) return fail("y4m_header: the buffer holds " + std::to_string(buf ? cap : 0) + " bytes, the header needs " + std::to_string(n + 1));
+    if (!buf || cap < n + 1) return fail(who + "the buffer holds " + std::to_string(buf ? cap : 0) + " bytes, the header needs " + std::to_string(n + 1));
     memcpy(buf, line, (size_t)n + 1);
     return n;
 }
 
-int mmhip_clip_to_yuv420(mmhip_invocation *inv, const void *src_rgba, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
-                         int first_row, int last_row, int num_frames, int matrix, int range, void *dst, int64_t dst_frame_stride, void *stream) {
+int mmhip_y4m_header(char *buf, int cap, int width, int height, int fps_num, int fps_den, int range) {
+    return y4m_header_line("y4m_header: ", "C420jpeg", buf, cap, width, height, fps_num, fps_den, range);
+}
+
+static_assert(MMHIP_YUV_SITING_CENTER == MM_YUV_SITING_CENTER && MMHIP_YUV_SITING_LEFT == MM_YUV_SITING_LEFT, "the sitings of mm_yuv.h");
+int mmhip_y4m_header_sited(char *buf, int cap, int width, int height, int fps_num, int fps_den, int range, int bits, int siting) {
+    const std::string who = "y4m_header_sited: ";
+    if (bits != 8 && bits != 10) return fail(who + "bits must be 8 or 10, not " + std::to_string(bits));
+    if (!mm_yuv_siting_known(siting))
+        return fail(who + "siting must be MMHIP_YUV_SITING_CENTER or MMHIP_YUV_SITING_LEFT (0 or 1), not " + std::to_string(siting));
+    // (Y4M has no colour space tag for left-sited 10-bit 4:2:0: C420p10 says nothing of the siting)
+    const char *tag = bits == 10 ? "C420p10" : siting == MMHIP_YUV_SITING_LEFT ? "C420mpeg2" : "C420jpeg";
+    return y4m_header_line(who, tag, buf, cap, width, height, fps_num, fps_den, range);
+}
+
+static int clip_to_yuv420(const char *name, mmhip_invocation *inv, const void *src_rgba, int64_t src_row_stride, int64_t src_frame_stride, int width,
+                          int height, int first_row, int last_row, int num_frames, int matrix, int range, int siting, void *dst,
+                          int64_t dst_frame_stride, void *stream) {
     std::string err;
-    if (check_rgba8_to_yuv420_clip(src_rgba, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix, range, dst,
-                                   dst_frame_stride, &err) != 0)
+    if (check_rgba8_to_yuv420_clip_sited(name, src_rgba, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix,
+                                         range, siting, dst, dst_frame_stride, &err) != 0)
         return fail(err);
-    if (!inv) return fail("clip_to_yuv420: no invocation");
+    if (!inv) return fail(std::string(name) + ": no invocation");
     hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)inv->stream;
-    if (launch_rgba8_to_yuv420_clip(src_rgba, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix, range, dst,
-                                    dst_frame_stride, inv->ws, s, &err) != 0)
+    if (launch_rgba8_to_yuv420_clip_sited(name, src_rgba, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix,
+                                          range, siting, dst, dst_frame_stride, inv->ws, s, nullptr, &err) != 0)
         return fail(err);
     return 0;
+}
+
+int mmhip_clip_to_yuv420(mmhip_invocation *inv, const void *src_rgba, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
+                         int first_row, int last_row, int num_frames, int matrix, int range, void *dst, int64_t dst_frame_stride, void *stream) {
+    return clip_to_yuv420("clip_to_yuv420", inv, src_rgba, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix,
+                          range, MMHIP_YUV_SITING_CENTER, dst, dst_frame_stride, stream);
+}
+
+int mmhip_clip_to_yuv420_sited(mmhip_invocation *inv, const void *src_rgba, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
+                               int first_row, int last_row, int num_frames, int matrix, int range, int siting, void *dst,
+                               int64_t dst_frame_stride, void *stream) {
+    return clip_to_yuv420("clip_to_yuv420_sited", inv, src_rgba, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames,
+                          matrix, range, siting, dst, dst_frame_stride, stream);
 }
 
 // ---- clips as 10-bit planar Y'CbCr 4:2:0 (mmhip_clip_float_to_yuv420p10): float frames in HBM to Y4M payloads in HBM ----
@@ -1247,34 +1277,38 @@ int64_t mmhip_yuv420p10_frame_bytes(int width, int height) {
 }
 
 int mmhip_y4m_header_p10(char *buf, int cap, int width, int height, int fps_num, int fps_den, int range) {
-    if (width < 1 || height < 1) return fail("y4m_header_p10: width and height must be at least 1");
-    if (fps_num < 1 || fps_den < 1) return fail("y4m_header_p10: fps_num and fps_den must be at least 1");
-    if (range != MMHIP_YUV_LIMITED && range != MMHIP_YUV_FULL)
-        return fail("y4m_header_p10: range must be MMHIP_YUV_LIMITED or MMHIP_YUV_FULL (0 or 1), not " + std::to_string(range));
-    char line[160];
-    const int n = snprintf(line, sizeof line, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420p10 XCOLORRANGE=%s\n", width, height, fps_num, fps_den,
-                           range == MMHIP_YUV_FULL ? "FULL" : "LIMITED");
-    if (!buf || cap < n + 1)
-        return fail("y4m_header_p10: the buffer holds " + std::to_string(buf ? cap : 0) + " bytes, the header needs " + std::to_string(n + 1));
-    memcpy(buf, line, (size_t)n + 1);
-    return n;
+    return y4m_header_line("y4m_header_p10: ", "C420p10", buf, cap, width, height, fps_num, fps_den, range);
+}
+
+static int clip_float_to_yuv420p10(const char *name, mmhip_invocation *inv, const void *src, int64_t src_row_stride, int64_t src_frame_stride,
+                                   int width, int height, int first_row, int last_row, int num_frames, int matrix, int range, int siting,
+                                   void *dst, int64_t dst_frame_stride, void *stream) {
+    std::string err;
+    if (check_float_to_yuv420p10_clip_sited(name, src, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix, range,
+                                            siting, dst, dst_frame_stride, &err) != 0)
+        return fail(err);
+    if (!inv) return fail(std::string(name) + ": no invocation");
+    hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)inv->stream;
+    int path = 0;
+    if (launch_float_to_yuv420p10_clip_sited(name, src, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix, range,
+                                             siting, dst, dst_frame_stride, inv->ws, s, &path, &err) != 0)
+        return fail(err);
+    ++inv->clip_yuv10_launches[path];
+    return 0;
 }
 
 int mmhip_clip_float_to_yuv420p10(mmhip_invocation *inv, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
                                   int first_row, int last_row, int num_frames, int matrix, int range, void *dst, int64_t dst_frame_stride,
                                   void *stream) {
-    std::string err;
-    if (check_float_to_yuv420p10_clip(src, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix, range, dst,
-                                      dst_frame_stride, &err) != 0)
-        return fail(err);
-    if (!inv) return fail("clip_float_to_yuv420p10: no invocation");
-    hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)inv->stream;
-    int path = 0;
-    if (launch_float_to_yuv420p10_clip(src, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix, range, dst,
-                                       dst_frame_stride, inv->ws, s, &path, &err) != 0)
-        return fail(err);
-    ++inv->clip_yuv10_launches[path];
-    return 0;
+    return clip_float_to_yuv420p10("clip_float_to_yuv420p10", inv, src, src_row_stride, src_frame_stride, width, height, first_row, last_row,
+                                   num_frames, matrix, range, MMHIP_YUV_SITING_CENTER, dst, dst_frame_stride, stream);
+}
+
+int mmhip_clip_float_to_yuv420p10_sited(mmhip_invocation *inv, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width,
+                                        int height, int first_row, int last_row, int num_frames, int matrix, int range, int siting, void *dst,
+                                        int64_t dst_frame_stride, void *stream) {
+    return clip_float_to_yuv420p10("clip_float_to_yuv420p10_sited", inv, src, src_row_stride, src_frame_stride, width, height, first_row, last_row,
+                                   num_frames, matrix, range, siting, dst, dst_frame_stride, stream);
 }
 
 long mmhip_clip_float_to_yuv420p10_launches(mmhip_invocation *inv, int path) {
@@ -1287,19 +1321,32 @@ long mmhip_clip_float_to_yuv420p10_launches(mmhip_invocation *inv, int path) {
 // ---- planar Y'CbCr 4:2:0 as input (mmhip_clip_from_yuv420): Y4M payloads in HBM to drawable words in HBM ----
 static_assert(MMHIP_YUV_CHROMA_BILINEAR == MM_YUV_CHROMA_BILINEAR && MMHIP_YUV_CHROMA_REPLICATE == MM_YUV_CHROMA_REPLICATE,
               "the chroma modes of mm_yuv.h");
-int mmhip_clip_from_yuv420(mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height, int num_frames, int matrix,
-                           int range, int chroma, void *dst_rgba32, int64_t dst_frame_stride, void *stream) {
+static int clip_from_yuv420(const char *name, mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height,
+                            int num_frames, int matrix, int range, int chroma, int siting, void *dst_rgba32, int64_t dst_frame_stride, void *stream) {
     std::string err;
-    if (check_yuv420_to_rgba_clip(src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, dst_rgba32, dst_frame_stride, &err) != 0)
+    if (check_yuv420_to_rgba_clip_sited(name, src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, siting, dst_rgba32,
+                                        dst_frame_stride, &err) != 0)
         return fail(err);
-    if (!inv) return fail("clip_from_yuv420: no invocation");
+    if (!inv) return fail(std::string(name) + ": no invocation");
     hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)inv->stream;
     int path = 0;
-    if (launch_yuv420_to_rgba_clip(src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, dst_rgba32, dst_frame_stride, inv->ws,
-                                   s, &path, &err) != 0)
+    if (launch_yuv420_to_rgba_clip_sited(name, src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, siting, dst_rgba32,
+                                         dst_frame_stride, inv->ws, s, &path, &err) != 0)
         return fail(err);
     ++inv->clip_yuv_input_launches[path];
     return 0;
+}
+
+int mmhip_clip_from_yuv420(mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height, int num_frames, int matrix,
+                           int range, int chroma, void *dst_rgba32, int64_t dst_frame_stride, void *stream) {
+    return clip_from_yuv420("clip_from_yuv420", inv, src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma,
+                            MMHIP_YUV_SITING_CENTER, dst_rgba32, dst_frame_stride, stream);
+}
+
+int mmhip_clip_from_yuv420_sited(mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height, int num_frames,
+                                 int matrix, int range, int chroma, int siting, void *dst_rgba32, int64_t dst_frame_stride, void *stream) {
+    return clip_from_yuv420("clip_from_yuv420_sited", inv, src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, siting,
+                            dst_rgba32, dst_frame_stride, stream);
 }
 
 long mmhip_clip_from_yuv420_launches(mmhip_invocation *inv, int path) {
@@ -1312,13 +1359,13 @@ int mmhip_clip_yuv_input_groups(mmhip_invocation *inv) { return inv->clip_yuv_in
 
 // The header of either depth: `bits` null refuses C420p10 with the 8-bit reader's words.
 static int y4m_parse(const std::string &who, const char *buf, int len, int *width, int *height, int *fps_num, int *fps_den, int *range, int *bits,
-                     int *header_len) {
+                     int *header_len, int *siting = nullptr) {
     if (!buf || len < 0) return fail(who + "no buffer");
     const char *nl = (const char *)memchr(buf, '\n', (size_t)len);
     if (len < 9 || memcmp(buf, "YUV4MPEG2", 9) != 0 || (len > 9 && buf[9] != ' ' && buf[9] != '\n'))
         return fail(who + "the stream does not begin with the magic word YUV4MPEG2");
     if (!nl) return fail(who + "no newline within the first " + std::to_string(len) + " bytes: not a stream header");
-    int w = 0, h = 0, num = 25, den = 1, rng = -1, depth = 8;
+    int w = 0, h = 0, num = 25, den = 1, rng = -1, depth = 8, sited = MMHIP_YUV_SITING_CENTER;
     // a positive int that fills the whole text, or 0
     auto number = [](const std::string &text) {
         if (text.empty() || text.size() > 9) return 0;
@@ -1347,6 +1394,7 @@ static int y4m_parse(const std::string &who, const char *buf, int len, int *widt
                 if (value != "p" && value != "?") return fail(who + "an interlaced stream (`" + tag + "'): only progressive frames are read");
                 break;
             case 'C':
+                sited = value == "420mpeg2" ? MMHIP_YUV_SITING_LEFT : MMHIP_YUV_SITING_CENTER;      // (C420paldv is not modelled: centre, as it is read)
                 if (bits && value == "420p10") { depth = 10; break; }
                 if (value != "420jpeg" && value != "420mpeg2" && value != "420paldv" && value != "420")
                     return fail(who + "the colour space `" + tag + "' is not " +
@@ -1368,6 +1416,7 @@ static int y4m_parse(const std::string &who, const char *buf, int len, int *widt
     if (fps_den) *fps_den = den;
     if (range) *range = rng;
     if (bits) *bits = depth;
+    if (siting) *siting = sited;
     if (header_len) *header_len = (int)(nl - buf) + 1;
     return 0;
 }
@@ -1382,21 +1431,39 @@ int mmhip_y4m_parse_stream_header(const char *buf, int len, int *width, int *hei
     return y4m_parse("y4m_parse_stream_header: ", buf, len, width, height, fps_num, fps_den, range, bits ? bits : &depth, header_len);
 }
 
+int mmhip_y4m_stream_siting(const char *buf, int len, int *siting) {
+    int depth = 8;
+    return y4m_parse("y4m_stream_siting: ", buf, len, nullptr, nullptr, nullptr, nullptr, nullptr, &depth, nullptr, siting);
+}
+
 // ---- 10-bit planar Y'CbCr 4:2:0 as input (mmhip_clip_from_yuv420p10): Y4M payloads in HBM to float4 texels in HBM ----
-int mmhip_clip_from_yuv420p10(mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height, int num_frames, int matrix,
-                              int range, int chroma, void *dst_float4, int64_t dst_frame_stride, void *stream) {
+static int clip_from_yuv420p10(const char *name, mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height,
+                               int num_frames, int matrix, int range, int chroma, int siting, void *dst_float4, int64_t dst_frame_stride,
+                               void *stream) {
     std::string err;
-    if (check_yuv420p10_to_float_clip(src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, dst_float4, dst_frame_stride,
-                                      &err) != 0)
+    if (check_yuv420p10_to_float_clip_sited(name, src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, siting, dst_float4,
+                                            dst_frame_stride, &err) != 0)
         return fail(err);
-    if (!inv) return fail("clip_from_yuv420p10: no invocation");
+    if (!inv) return fail(std::string(name) + ": no invocation");
     hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)inv->stream;
     int path = 0;
-    if (launch_yuv420p10_to_float_clip(src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, dst_float4, dst_frame_stride,
-                                       inv->ws, s, &path, &err) != 0)
+    if (launch_yuv420p10_to_float_clip_sited(name, src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, siting, dst_float4,
+                                             dst_frame_stride, inv->ws, s, &path, &err) != 0)
         return fail(err);
     ++inv->clip_yuv10_input_launches[path];
     return 0;
+}
+
+int mmhip_clip_from_yuv420p10(mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height, int num_frames, int matrix,
+                              int range, int chroma, void *dst_float4, int64_t dst_frame_stride, void *stream) {
+    return clip_from_yuv420p10("clip_from_yuv420p10", inv, src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma,
+                               MMHIP_YUV_SITING_CENTER, dst_float4, dst_frame_stride, stream);
+}
+
+int mmhip_clip_from_yuv420p10_sited(mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height, int num_frames,
+                                    int matrix, int range, int chroma, int siting, void *dst_float4, int64_t dst_frame_stride, void *stream) {
+    return clip_from_yuv420p10("clip_from_yuv420p10_sited", inv, src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, siting,
+                               dst_float4, dst_frame_stride, stream);
 }
 
 long mmhip_clip_from_yuv420p10_launches(mmhip_invocation *inv, int path) {
