@@ -131,6 +131,15 @@ def yuv_siting(chroma_siting):
     return YUV_SITINGS[chroma_siting]
 
 
+def _yuv_entry(name, siting, at):
+    """mmhip_<name>, or for a `siting` other than centre mmhip_<name>_sited with the siting spliced in as argument `at` (the
+    handle is argument 0): one call site for both."""
+    if not siting:
+        return getattr(lib(), "mmhip_" + name)
+    sited = getattr(lib(), "mmhip_" + name + "_sited")
+    return lambda *args: sited(*args[:at], siting, *args[at:])
+
+
 def _pixel_format_of(who, buf, pixel_format):
     """The format of the frames `buf`: `pixel_format` where given, else by the dtype (uint16: "yuv420p10").  ValueError for an
     unknown name or a dtype the format does not have."""
@@ -734,12 +743,8 @@ class Invocation:
             raise ValueError("set_image_yuv420: uint8 [N, %d] for frames of %d x %d, not %s %r" % (frame_bytes, w, h, a.dtype, a.shape))
         a = np.ascontiguousarray(a)
         u = self._index(name)
-        if siting:
-            self._check(lib().mmhip_set_image_sequence_yuv420_host_sited(self._h, u["index"], a.ctypes.data_as(C.c_void_p), frame_bytes, w, h,
-                                                                         a.shape[0], matrix, rng, mode, siting))
-            return
-        self._check(lib().mmhip_set_image_sequence_yuv420_host(self._h, u["index"], a.ctypes.data_as(C.c_void_p), frame_bytes, w, h, a.shape[0],
-                                                               matrix, rng, mode))
+        self._check(_yuv_entry("set_image_sequence_yuv420_host", siting, 10)(self._h, u["index"], a.ctypes.data_as(C.c_void_p), frame_bytes, w, h,
+                                                                             a.shape[0], matrix, rng, mode))
 
     def set_image_yuv420p10(self, name, yuv, w, h, yuv_matrix="bt709", yuv_range="limited", chroma="bilinear", chroma_siting="center"):
         """Binds 10-bit planar Y'CbCr 4:2:0 frames as float32 input drawable: `yuv` is uint16 [N, frame_bytes / 2] -- what
@@ -763,12 +768,8 @@ class Invocation:
             raise ValueError("set_image_yuv420p10: uint16 [N, %d] for frames of %d x %d, not %s %r" % (samples, w, h, a.dtype, a.shape))
         a = np.ascontiguousarray(a, np.uint16)      # (the host's byte order, which the library reads)
         u = self._index(name)
-        if siting:
-            self._check(lib().mmhip_set_image_sequence_yuv420p10_host_sited(self._h, u["index"], a.ctypes.data_as(C.c_void_p), 2 * samples, w, h,
-                                                                            a.shape[0], matrix, rng, mode, siting))
-            return
-        self._check(lib().mmhip_set_image_sequence_yuv420p10_host(self._h, u["index"], a.ctypes.data_as(C.c_void_p), 2 * samples, w, h, a.shape[0],
-                                                                  matrix, rng, mode))
+        self._check(_yuv_entry("set_image_sequence_yuv420p10_host", siting, 10)(self._h, u["index"], a.ctypes.data_as(C.c_void_p), 2 * samples, w, h,
+                                                                                a.shape[0], matrix, rng, mode))
 
     def clip_yuv10_input_groups(self):
         """The upload groups of the last set_image_yuv420p10 (mmhip_clip_yuv10_input_groups)."""
@@ -1096,13 +1097,8 @@ class Invocation:
             src_frame_stride = max(last_row - first_row, 0) * src_row_stride
         if dst_frame_stride is None:
             dst_frame_stride = w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1)
-        if siting:
-            self._check(lib().mmhip_clip_to_yuv420_sited(self._h, C.c_void_p(src_ptr), src_row_stride, src_frame_stride, w, h, first_row, last_row,
-                                                         int(num_frames), matrix, rng, siting, C.c_void_p(dst_ptr), dst_frame_stride,
-                                                         C.c_void_p(stream)))
-            return
-        self._check(lib().mmhip_clip_to_yuv420(self._h, C.c_void_p(src_ptr), src_row_stride, src_frame_stride, w, h, first_row, last_row,
-                                               int(num_frames), matrix, rng, C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
+        self._check(_yuv_entry("clip_to_yuv420", siting, 11)(self._h, C.c_void_p(src_ptr), src_row_stride, src_frame_stride, w, h, first_row, last_row,
+                                                             int(num_frames), matrix, rng, C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
 
     def clip_from_yuv420(self, src_ptr, dst_ptr, num_frames, width=None, height=None, src_frame_stride=None, dst_frame_stride=None,
                          yuv_matrix="bt709", yuv_range="limited", chroma="bilinear", stream=0, chroma_siting="center"):
@@ -1120,12 +1116,8 @@ class Invocation:
             src_frame_stride = w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1)
         if dst_frame_stride is None:
             dst_frame_stride = 4 * w * h
-        if siting:
-            self._check(lib().mmhip_clip_from_yuv420_sited(self._h, C.c_void_p(src_ptr), src_frame_stride, w, h, int(num_frames), matrix, rng, mode,
-                                                           siting, C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
-            return
-        self._check(lib().mmhip_clip_from_yuv420(self._h, C.c_void_p(src_ptr), src_frame_stride, w, h, int(num_frames), matrix, rng, mode,
-                                                 C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
+        self._check(_yuv_entry("clip_from_yuv420", siting, 9)(self._h, C.c_void_p(src_ptr), src_frame_stride, w, h, int(num_frames), matrix, rng, mode,
+                                                              C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
 
     def clip_from_yuv420p10(self, src_ptr, dst_ptr, num_frames, width=None, height=None, src_frame_stride=None, dst_frame_stride=None,
                             yuv_matrix="bt709", yuv_range="limited", chroma="bilinear", stream=0, chroma_siting="center"):
@@ -1143,12 +1135,8 @@ class Invocation:
             src_frame_stride = 2 * (w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1))
         if dst_frame_stride is None:
             dst_frame_stride = 16 * w * h
-        if siting:
-            self._check(lib().mmhip_clip_from_yuv420p10_sited(self._h, C.c_void_p(src_ptr), src_frame_stride, w, h, int(num_frames), matrix, rng, mode,
-                                                              siting, C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
-            return
-        self._check(lib().mmhip_clip_from_yuv420p10(self._h, C.c_void_p(src_ptr), src_frame_stride, w, h, int(num_frames), matrix, rng, mode,
-                                                    C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
+        self._check(_yuv_entry("clip_from_yuv420p10", siting, 9)(self._h, C.c_void_p(src_ptr), src_frame_stride, w, h, int(num_frames), matrix, rng, mode,
+                                                                 C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
 
     def clip_float_to_yuv420p10(self, src_ptr, dst_ptr, num_frames, width=None, height=None, rows=None, src_row_stride=None,
                                 src_frame_stride=None, dst_frame_stride=None, yuv_matrix="bt709", yuv_range="limited", stream=0,
@@ -1169,13 +1157,9 @@ class Invocation:
             src_frame_stride = max(last_row - first_row, 0) * src_row_stride
         if dst_frame_stride is None:
             dst_frame_stride = 2 * (w * h + 2 * ((w + 1) >> 1) * ((h + 1) >> 1))
-        if siting:
-            self._check(lib().mmhip_clip_float_to_yuv420p10_sited(self._h, C.c_void_p(src_ptr), src_row_stride, src_frame_stride, w, h, first_row,
-                                                                  last_row, int(num_frames), matrix, rng, siting, C.c_void_p(dst_ptr),
-                                                                  dst_frame_stride, C.c_void_p(stream)))
-            return
-        self._check(lib().mmhip_clip_float_to_yuv420p10(self._h, C.c_void_p(src_ptr), src_row_stride, src_frame_stride, w, h, first_row, last_row,
-                                                        int(num_frames), matrix, rng, C.c_void_p(dst_ptr), dst_frame_stride, C.c_void_p(stream)))
+        self._check(_yuv_entry("clip_float_to_yuv420p10", siting, 11)(self._h, C.c_void_p(src_ptr), src_row_stride, src_frame_stride, w, h, first_row,
+                                                                      last_row, int(num_frames), matrix, rng, C.c_void_p(dst_ptr), dst_frame_stride,
+                                                                      C.c_void_p(stream)))
 
     def clip_float_to_yuv420p10_launches(self, path):
         """The launches of clip_float_to_yuv420p10's kernel on `path`: "aligned" or "bytes" (mmhip_clip_float_to_yuv420p10_launches)."""
@@ -1230,12 +1214,7 @@ class Invocation:
         frame_bytes = yuv420_frame_bytes(w, h, pixel_format)
         pixel_bytes = 16 if deep else 4
         band_bytes = (last_row - first_row) * w * pixel_bytes
-        convert = lib().mmhip_clip_float_to_yuv420p10 if deep else lib().mmhip_clip_to_yuv420
-        if siting:
-            sited = lib().mmhip_clip_float_to_yuv420p10_sited if deep else lib().mmhip_clip_to_yuv420_sited
-
-            def convert(h, src, row_stride, frame_stride, w, height, first, last, n, matrix, rng, *landing):
-                return sited(h, src, row_stride, frame_stride, w, height, first, last, n, matrix, rng, siting, *landing)
+        convert = _yuv_entry("clip_float_to_yuv420p10" if deep else "clip_to_yuv420", siting, 11)
         try:
             budget = int(os.environ.get("MMHIP_CLIP_YUV_BYTES", "") or 0)
         except ValueError:

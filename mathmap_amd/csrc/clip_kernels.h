@@ -1,6 +1,7 @@
 // Launchers of the hand-written kernels that finish a clip or convert its frames: the combines, the contrast mask and the
 // reconstruction filter (clip_combine.hip), Y'CbCr 4:2:0 out (clip_yuv.hip, 10-bit from float frames: clip_yuv10.hip) and in (clip_yuv_in.hip,
-// 10-bit to float frames: clip_yuv10_in.hip).
+// 10-bit to float frames: clip_yuv10_in.hip): one job record, one check and one launcher per converter; what the four
+// files share among themselves is in clip_yuv_common.h.
 #pragma once
 #include "native_filters.h"      // NativeWorkspace
 
@@ -78,79 +79,66 @@ int launch_aa_contrast_clip(const void *base, int64_t base_frame_stride, const C
 int launch_filter_combine_clip(const ClipSamples &in, const ClipFilterTaps &taps, const ClipStore &to, const ClipRect &r, float inv_k, int frames,
                                NativeWorkspace &ws, hipStream_t s, std::string *err);
 
+// ---- the Y'CbCr 4:2:0 converters: their job records ----
+// `name` is the entry point the refusals speak for (mmhip_<name>); matrix, range, chroma and siting are mm_yuv.h's.  Centre
+// siting launches the SITING = MM_YUV_SITING_CENTER instantiations, left siting the SITING = MM_YUV_SITING_LEFT ones.
+// Frames out: frame i's source rows [first_row, last_row) from src + i * src_frame_stride (src is the band's first row),
+// rows src_row_stride bytes apart; its planes at dst + i * dst_frame_stride.
+struct YuvOutJob {
+    const char *name;
+    const void *src;
+    int64_t src_row_stride, src_frame_stride;
+    int width, height, first_row, last_row, frames;
+    int matrix, range, siting;
+    void *dst;
+    int64_t dst_frame_stride;
+};
+// Frames in: frame i's planes at src + i * src_frame_stride, its pixels at dst + i * dst_frame_stride.  Replicate mode
+// ignores the siting.
+struct YuvInJob {
+    const char *name;
+    const void *src;
+    int64_t src_frame_stride;
+    int width, height, frames;
+    int matrix, range, chroma, siting;
+    void *dst;
+    int64_t dst_frame_stride;
+};
+// Every check refuses by name in `err` and needs no GPU; every launcher checks first, and *path (may be null) receives 0
+// for the aligned path, 1 for the other.  The refusals all share: a size below 1 x 1, no frame or more than 65 535, an
+// unknown matrix or range, an unknown chroma mode (frames in), a siting that is neither.
+
 // RGBA8 frames of a clip to planar Y'CbCr 4:2:0 in one launch (k_rgba8_to_yuv420_clip, clip_yuv.hip; mmhip_clip_to_yuv420
-// states the semantics and its parameters are these, mm_yuv.h holds the arithmetic).  The launcher takes the path of
+// and mmhip_clip_to_yuv420_sited state the semantics, mm_yuv.h holds the arithmetic).  The launcher takes the path of
 // aligned wide accesses where the width is a multiple of 8, src and both source strides are multiples of 16 and dst and
-// dst_frame_stride multiples of 8, else the path of byte accesses: the same bytes.  Refused, by name, in `err` (the
-// check alone needs no GPU): a size below 1 x 1, no frame or more than 65 535, an unknown matrix or range, rows outside
-// the frame, an odd first_row, an odd last_row that is not the height, a src_row_stride below one row, a
+// dst_frame_stride multiples of 8, else the path of byte accesses: the same bytes.  Refused next: rows outside the
+// frame, an odd first_row, an odd last_row that is not the height, null pointers, a src_row_stride below one row, a
 // dst_frame_stride below one frame, a Y plane or a source band beyond 4 GiB.  Timed through ws.timed_launch as yuv420_clip.
-int check_rgba8_to_yuv420_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
-                               int last_row, int frames, int matrix, int range, const void *dst, int64_t dst_frame_stride, std::string *err);
-int launch_rgba8_to_yuv420_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
-                                int last_row, int frames, int matrix, int range, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws,
-                                hipStream_t s, std::string *err);
-// Planar Y'CbCr 4:2:0 frames of a clip to drawable words in one launch (k_yuv420_to_rgba_clip, clip_yuv_in.hip;
-// mmhip_clip_from_yuv420 states the semantics and its parameters are these, mm_yuv.h holds the arithmetic).  The launcher
-// takes the path of aligned wide accesses (*path = 0) where the width is a multiple of 8, src and src_frame_stride are
-// multiples of 8 and dst and dst_frame_stride multiples of 16, else the path of byte accesses (*path = 1): the same
-// words.  Refused, by name, in `err` (the check alone needs no GPU): a size below 1 x 1, no frame or more than 65 535, an
-// unknown matrix, range or chroma mode, null pointers, a stride below one frame, a dst_frame_stride that is no multiple
-// of 4, a destination frame beyond 4 GiB.  Timed through ws.timed_launch as yuv420_to_rgba_clip.
-int check_yuv420_to_rgba_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
-                              const void *dst, int64_t dst_frame_stride, std::string *err);
-int launch_yuv420_to_rgba_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
-                               void *dst, int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err);
+int check_rgba8_to_yuv420_clip(const YuvOutJob &job, std::string *err);
+int launch_rgba8_to_yuv420_clip(const YuvOutJob &job, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err);
 // Float frames of a clip (float4 RGBA, what floatmap = 1 lands) to planar Y'CbCr 4:2:0 with 10-bit samples in 16-bit
-// words in one launch (k_float_to_yuv420p10_clip, clip_yuv10.hip; mmhip_clip_float_to_yuv420p10 states the semantics and
-// its parameters are these, mm_yuv.h holds the arithmetic).  The launcher takes the path of aligned wide accesses (*path =
-// 0) where the width is a multiple of 8 and src, both source strides, dst and dst_frame_stride are multiples of 16, else
-// the path of per-pixel loads and 2-byte stores (*path = 1): the same samples.  Refused, by name, in `err` (the check
-// alone needs no GPU): what check_rgba8_to_yuv420_clip refuses, a source pointer or stride that is no multiple of 4, an
-// odd dst or dst_frame_stride.  Timed through ws.timed_launch as yuv420p10_clip.
-int check_float_to_yuv420p10_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
-                                  int last_row, int frames, int matrix, int range, const void *dst, int64_t dst_frame_stride, std::string *err);
-int launch_float_to_yuv420p10_clip(const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height, int first_row,
-                                   int last_row, int frames, int matrix, int range, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws,
-                                   hipStream_t s, int *path, std::string *err);
+// words in one launch (k_float_to_yuv420p10_clip, clip_yuv10.hip; mmhip_clip_float_to_yuv420p10 and its _sited twin state
+// the semantics, mm_yuv.h holds the arithmetic).  The aligned path where the width is a multiple of 8 and src, both source
+// strides, dst and dst_frame_stride are multiples of 16, else the path of per-pixel loads and 2-byte stores: the same
+// samples.  Refused next: what check_rgba8_to_yuv420_clip refuses, a source pointer or stride that is no multiple of 4,
+// an odd dst or dst_frame_stride.  Timed through ws.timed_launch as yuv420p10_clip.
+int check_float_to_yuv420p10_clip(const YuvOutJob &job, std::string *err);
+int launch_float_to_yuv420p10_clip(const YuvOutJob &job, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err);
+// Planar Y'CbCr 4:2:0 frames of a clip to drawable words in one launch (k_yuv420_to_rgba_clip, clip_yuv_in.hip;
+// mmhip_clip_from_yuv420 and mmhip_clip_from_yuv420_sited state the semantics, mm_yuv.h holds the arithmetic).  The aligned
+// path where the width is a multiple of 8, src and src_frame_stride are multiples of 8 and dst and dst_frame_stride
+// multiples of 16, else the path of byte accesses: the same words.  Refused next: null pointers, a stride below one
+// frame, a dst_frame_stride that is no multiple of 4, a destination frame beyond 4 GiB.  Timed through ws.timed_launch as
+// yuv420_to_rgba_clip.
+int check_yuv420_to_rgba_clip(const YuvInJob &job, std::string *err);
+int launch_yuv420_to_rgba_clip(const YuvInJob &job, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err);
 // Planar Y'CbCr 4:2:0 frames of 16-bit samples (10 bits used) to the float4 texels of a deep drawable in one launch
-// (k_yuv420p10_to_float_clip, clip_yuv10_in.hip; mmhip_clip_from_yuv420p10 states the semantics and its parameters are
-// these, mm_yuv.h holds the arithmetic).  The launcher takes the path of aligned wide accesses (*path = 0) where the width
-// is a multiple of 8 and src and src_frame_stride are multiples of 16, else the path of 2-byte loads and per-pixel
-// stores (*path = 1): the same floats.  Refused, by name, in `err` (the check alone needs no GPU): what
+// (k_yuv420p10_to_float_clip, clip_yuv10_in.hip; mmhip_clip_from_yuv420p10 and its _sited twin state the semantics, mm_yuv.h
+// holds the arithmetic).  The aligned path where the width is a multiple of 8 and src and src_frame_stride are multiples
+// of 16, else the path of 2-byte loads and per-pixel stores: the same floats.  Refused next: what
 // check_yuv420_to_rgba_clip refuses, an odd src or src_frame_stride, a dst or dst_frame_stride that is no multiple of
 // 16.  Timed through ws.timed_launch as yuv420p10_to_float_clip.
-int check_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
-                                  const void *dst, int64_t dst_frame_stride, std::string *err);
-int launch_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
-                                   void *dst, int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err);
-// The four converters with a chroma siting (MM_YUV_SITING_CENTER or MM_YUV_SITING_LEFT of mm_yuv.h; the mmhip_..._sited
-// entry points state the semantics): the functions above are these with MM_YUV_SITING_CENTER under the name of their
-// entry point, and centre siting reaches the kernel instantiations those always launched.  `name` is the entry point the
-// refusals speak for; they are the unsited function's, in its order, and one more after the modes: a siting that is
-// neither.  Left siting launches the SITING = MM_YUV_SITING_LEFT instantiations; the input converters' replicate mode
-// ignores the siting.  *path (may be null for the RGBA8 converter) receives 0 for the aligned path, 1 for the other.
-int check_rgba8_to_yuv420_clip_sited(const char *name, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
-                                     int first_row, int last_row, int frames, int matrix, int range, int siting, const void *dst,
-                                     int64_t dst_frame_stride, std::string *err);
-int launch_rgba8_to_yuv420_clip_sited(const char *name, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
-                                      int first_row, int last_row, int frames, int matrix, int range, int siting, void *dst,
-                                      int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err);
-int check_float_to_yuv420p10_clip_sited(const char *name, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
-                                        int first_row, int last_row, int frames, int matrix, int range, int siting, const void *dst,
-                                        int64_t dst_frame_stride, std::string *err);
-int launch_float_to_yuv420p10_clip_sited(const char *name, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
-                                         int first_row, int last_row, int frames, int matrix, int range, int siting, void *dst,
-                                         int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err);
-int check_yuv420_to_rgba_clip_sited(const char *name, const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix,
-                                    int range, int chroma, int siting, const void *dst, int64_t dst_frame_stride, std::string *err);
-int launch_yuv420_to_rgba_clip_sited(const char *name, const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix,
-                                     int range, int chroma, int siting, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s,
-                                     int *path, std::string *err);
-int check_yuv420p10_to_float_clip_sited(const char *name, const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix,
-                                        int range, int chroma, int siting, const void *dst, int64_t dst_frame_stride, std::string *err);
-int launch_yuv420p10_to_float_clip_sited(const char *name, const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix,
-                                         int range, int chroma, int siting, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws,
-                                         hipStream_t s, int *path, std::string *err);
+int check_yuv420p10_to_float_clip(const YuvInJob &job, std::string *err);
+int launch_yuv420p10_to_float_clip(const YuvInJob &job, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err);
 
 }  // namespace mm

@@ -4,12 +4,8 @@
 // on both sides.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-#include <cstring>
-#include <string>
-
 #include "mm_yuv.h"
-#include "clip_kernels.h"
+#include "clip_yuv_common.h"
 
 namespace mm {
 
@@ -38,10 +34,6 @@ struct Yuv10InArgs {
     mm_yuv10_float_mode m;
 };
 
-typedef float yuv10_in_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned yuv10_in_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned yuv10_in_u32x2 __attribute__((ext_vector_type(2)));
-
 // N samples in one load, as 32-bit words of two samples each (the even one low: little-endian; one sample alone in the
 // low half)
 template <int N>
@@ -49,12 +41,12 @@ __device__ __forceinline__ void yuv10_in_load(const uint16_t *p, unsigned w[(N +
     if constexpr (N == 1) w[0] = *p;
     else if constexpr (N == 2) w[0] = *(const unsigned *)p;
     else if constexpr (N == 4) {
-        const yuv10_in_u32x2 v = *(const yuv10_in_u32x2 *)p;
+        const yuv_u32x2 v = *(const yuv_u32x2 *)p;
         w[0] = v.x;
         w[1] = v.y;
     } else {
         static_assert(N == 8, "a load of 2, 4, 8 or 16 bytes");
-        const yuv10_in_u32x4 v = *(const yuv10_in_u32x4 *)p;
+        const yuv_u32x4 v = *(const yuv_u32x4 *)p;
         w[0] = v.x;
         w[1] = v.y;
         w[2] = v.z;
@@ -66,32 +58,32 @@ __device__ __forceinline__ int yuv10_in_sample(const unsigned *w, int k) { retur
 
 // One texel from a pixel's luma and the chroma it sees at scale 16
 template <bool NT>
-__device__ __forceinline__ void yuv10_in_store(const mm_yuv10_float_mode &m, int luma, int s_cb, int s_cr, yuv10_in_f32x4 *p) {
+__device__ __forceinline__ void yuv10_in_store(const mm_yuv10_float_mode &m, int luma, int s_cb, int s_cr, yuv_f32x4 *p) {
     float t[4];
     mm_yuv10_to_float(m, luma, s_cb, s_cr, t);
-    const yuv10_in_f32x4 v = {t[0], t[1], t[2], t[3]};
-    if (NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
+    const yuv_f32x4 v = {t[0], t[1], t[2], t[3]};
+    yuv_store<NT>(v, p);
 }
 
-// The NC + 2 column sums of one plane for one pixel row, NC = COLS / 2 the work-item's own chroma columns from `first`:
-// the pixel row's own chroma row `own` weighs 3, its neighbour row `nb` 1.  lo and hi are the clamped columns first - 1 and
-// first + NC.
-template <int NC>
+// The column sums of one plane for one pixel row over the work-item's own NC = COLS / 2 chroma columns from `first` and
+// their neighbours: the pixel row's own chroma row `own` weighs 3, its neighbour row `nb` 1.  Centre siting takes NC + 2,
+// from first - 1 on; left siting NC + 1, from first on (below).  lo and hi are the clamped columns first - 1 and first + NC.
+template <int NC, int SITING>
 __device__ __forceinline__ void yuv10_in_columns(const uint16_t *__restrict__ P, unsigned own, unsigned nb, unsigned first, unsigned lo, unsigned hi,
-                                                 int col[NC + 2]) {
+                                                 int *col) {
+    constexpr int L = SITING == MM_YUV_SITING_LEFT ? 0 : 1;
     unsigned a[(NC + 1) / 2], b[(NC + 1) / 2];
     yuv10_in_load<NC>(P + (own + first), a);
     yuv10_in_load<NC>(P + (nb + first), b);
-    col[0] = mm_yuv_chroma_column(mm_yuv10_sample(P[own + lo]), mm_yuv10_sample(P[nb + lo]));
+    if (L) col[0] = mm_yuv_chroma_column(mm_yuv10_sample(P[own + lo]), mm_yuv10_sample(P[nb + lo]));
 #pragma unroll
-    for (int k = 0; k < NC; ++k) col[1 + k] = mm_yuv_chroma_column(yuv10_in_sample(a, k), yuv10_in_sample(b, k));
-    col[NC + 1] = mm_yuv_chroma_column(mm_yuv10_sample(P[own + hi]), mm_yuv10_sample(P[nb + hi]));
+    for (int k = 0; k < NC; ++k) col[L + k] = mm_yuv_chroma_column(yuv10_in_sample(a, k), yuv10_in_sample(b, k));
+    col[L + NC] = mm_yuv_chroma_column(mm_yuv10_sample(P[own + hi]), mm_yuv10_sample(P[nb + hi]));
 }
 
 // COLS texels of one row from the row's luma words and the chroma each pixel sees
 template <int COLS, bool NT>
-__device__ __forceinline__ void yuv10_in_row(const mm_yuv10_float_mode &m, const unsigned *y, const int *u, const int *v, yuv10_in_f32x4 *out) {
+__device__ __forceinline__ void yuv10_in_row(const mm_yuv10_float_mode &m, const unsigned *y, const int *u, const int *v, yuv_f32x4 *out) {
 #pragma unroll
     for (int k = 0; k < COLS; ++k) yuv10_in_store<NT>(m, yuv10_in_sample(y, k), u[k], v[k], out + k);
 }
@@ -100,20 +92,10 @@ __device__ __forceinline__ void yuv10_in_row(const mm_yuv10_float_mode &m, const
 // lies on its chroma column and an odd one half way to the next, so a work-item needs its own NC chroma columns and the one
 // to their right, first + NC clamped to the plane, and nothing to their left: NC + 1 column sums per plane and pixel row
 // where centre siting takes NC + 2.  Replicate mode ignores the siting: the launcher takes the centre instantiation.
-template <int NC>
-__device__ __forceinline__ void yuv10_in_columns_left(const uint16_t *__restrict__ P, unsigned own, unsigned nb, unsigned first, unsigned hi,
-                                                      int col[NC + 1]) {
-    unsigned a[(NC + 1) / 2], b[(NC + 1) / 2];
-    yuv10_in_load<NC>(P + (own + first), a);
-    yuv10_in_load<NC>(P + (nb + first), b);
-#pragma unroll
-    for (int k = 0; k < NC; ++k) col[k] = mm_yuv_chroma_column(yuv10_in_sample(a, k), yuv10_in_sample(b, k));
-    col[NC] = mm_yuv_chroma_column(mm_yuv10_sample(P[own + hi]), mm_yuv10_sample(P[nb + hi]));
-}
-
 template <int COLS, int CHROMA, bool NT, int SITING = MM_YUV_SITING_CENTER>
 __global__ void __launch_bounds__(256) k_yuv420p10_to_float_clip(const Yuv10InArgs a) {
-    const unsigned item = blockIdx.x * 256u + threadIdx.x;
+    constexpr bool LEFT = SITING == MM_YUV_SITING_LEFT;
+    const unsigned item = yuv_item();
     if (item >= a.items) return;
     const unsigned cy = item / a.per_pair, at = item - cy * a.per_pair;      // cy < ch: items = per_pair * ch
     const unsigned r0 = 2u * cy;
@@ -121,53 +103,12 @@ __global__ void __launch_bounds__(256) k_yuv420p10_to_float_clip(const Yuv10InAr
     const size_t fi = blockIdx.y;
     const uint16_t *__restrict__ Y = a.src + fi * a.src_frame_samples;
     const uint16_t *__restrict__ CB = Y + a.cb_offset, *__restrict__ CR = Y + a.cr_offset;
-    yuv10_in_f32x4 *__restrict__ D = (yuv10_in_f32x4 *)((unsigned char *)a.dst + fi * a.dst_frame_stride);
+    yuv_f32x4 *__restrict__ D = (yuv_f32x4 *)((unsigned char *)a.dst + fi * a.dst_frame_stride);
     const mm_yuv10_float_mode m = a.m;
     // the chroma rows above and below, clamped to the plane: what the upper and the lower pixel row blend with
     const unsigned own = cy * a.cw, up = (cy ? cy - 1u : 0u) * a.cw, down = (cy + 1u < a.ch ? cy + 1u : cy) * a.cw;
-    if constexpr (SITING == MM_YUV_SITING_LEFT && COLS != 0) {
-        static_assert(CHROMA == MM_YUV_CHROMA_BILINEAR, "replicate mode has no siting");
-        constexpr int NC = COLS / 2;
-        const unsigned yo = r0 * a.width + at * COLS, first = at * NC;      // below 2^28: a destination frame is at most 4 GiB
-        unsigned y_top[NC], y_bot[NC];
-        yuv10_in_load<COLS>(Y + yo, y_top);
-        if (two) yuv10_in_load<COLS>(Y + (yo + a.width), y_bot);
-        const unsigned hi = first + NC < a.cw ? first + NC : a.cw - 1u;
-        int u[COLS], v[COLS], cu[NC + 1], cv[NC + 1];
-        // pixel k has its own column at index k / 2 of the NC + 1, an odd one its right neighbour one further
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            if (j && !two) break;
-            yuv10_in_columns_left<NC>(CB, own, j ? down : up, first, hi, cu);
-            yuv10_in_columns_left<NC>(CR, own, j ? down : up, first, hi, cv);
-#pragma unroll
-            for (int k = 0; k < COLS; ++k) {
-                u[k] = mm_yuv10_chroma_blend16_left(cu[k >> 1], cu[(k >> 1) + 1], k & 1);
-                v[k] = mm_yuv10_chroma_blend16_left(cv[k >> 1], cv[(k >> 1) + 1], k & 1);
-            }
-            yuv10_in_row<COLS, NT>(m, j ? y_bot : y_top, u, v, D + (yo + (j ? a.width : 0u)));
-        }
-    } else if constexpr (SITING == MM_YUV_SITING_LEFT) {
-        static_assert(CHROMA == MM_YUV_CHROMA_BILINEAR, "replicate mode has no siting");
-        // `at` is the chroma column: pixel columns 2 at and, inside the frame, 2 at + 1
-        const unsigned c0 = 2u * at;
-        const bool wide = c0 + 1u < a.width;
-        const unsigned right = at + 1u < a.cw ? at + 1u : at;
-        const unsigned yo = r0 * a.width + c0;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            if (j && !two) break;
-            const unsigned nb = j ? down : up;
-            const int cu = mm_yuv_chroma_column(mm_yuv10_sample(CB[own + at]), mm_yuv10_sample(CB[nb + at]));
-            const int cv = mm_yuv_chroma_column(mm_yuv10_sample(CR[own + at]), mm_yuv10_sample(CR[nb + at]));
-            const unsigned o = yo + (j ? a.width : 0u);
-            yuv10_in_store<NT>(m, mm_yuv10_sample(Y[o]), mm_yuv10_chroma_blend16_left(cu, cu, 0), mm_yuv10_chroma_blend16_left(cv, cv, 0), D + o);
-            if (!wide) continue;
-            const int ru = mm_yuv_chroma_column(mm_yuv10_sample(CB[own + right]), mm_yuv10_sample(CB[nb + right]));
-            const int rv = mm_yuv_chroma_column(mm_yuv10_sample(CR[own + right]), mm_yuv10_sample(CR[nb + right]));
-            yuv10_in_store<NT>(m, mm_yuv10_sample(Y[o + 1u]), mm_yuv10_chroma_blend16_left(cu, ru, 1), mm_yuv10_chroma_blend16_left(cv, rv, 1), D + (o + 1u));
-        }
-    } else if constexpr (COLS != 0) {
+    static_assert(!LEFT || CHROMA == MM_YUV_CHROMA_BILINEAR, "replicate mode has no siting");
+    if constexpr (COLS != 0) {
         constexpr int NC = COLS / 2;
         const unsigned yo = r0 * a.width + at * COLS, first = at * NC;      // below 2^28: a destination frame is at most 4 GiB
         unsigned y_top[NC], y_bot[NC];
@@ -187,27 +128,62 @@ __global__ void __launch_bounds__(256) k_yuv420p10_to_float_clip(const Yuv10InAr
             if (two) yuv10_in_row<COLS, NT>(m, y_bot, u, v, D + (yo + a.width));
         } else {
             const unsigned lo = first ? first - 1u : 0u, hi = first + NC < a.cw ? first + NC : a.cw - 1u;
-            int cu[NC + 2], cv[NC + 2];
-            // pixel k has its own column at index 1 + k / 2 of the NC + 2, its neighbour one to the left (k even) or right
-            yuv10_in_columns<NC>(CB, own, up, first, lo, hi, cu);
-            yuv10_in_columns<NC>(CR, own, up, first, lo, hi, cv);
+            int cu[NC + (LEFT ? 1 : 2)], cv[NC + (LEFT ? 1 : 2)];
+            if constexpr (LEFT) {
+                // pixel k has its own column at index k / 2 of the NC + 1, an odd one its right neighbour one further
 #pragma unroll
-            for (int k = 0; k < COLS; ++k) {
-                const int c = 1 + (k >> 1), n = (k & 1) ? c + 1 : c - 1;
-                u[k] = mm_yuv10_chroma_blend16(cu[c], cu[n]);
-                v[k] = mm_yuv10_chroma_blend16(cv[c], cv[n]);
-            }
-            yuv10_in_row<COLS, NT>(m, y_top, u, v, D + yo);
-            if (!two) return;
-            yuv10_in_columns<NC>(CB, own, down, first, lo, hi, cu);
-            yuv10_in_columns<NC>(CR, own, down, first, lo, hi, cv);
+                for (int j = 0; j < 2; ++j) {
+                    if (j && !two) break;
+                    yuv10_in_columns<NC, SITING>(CB, own, j ? down : up, first, lo, hi, cu);
+                    yuv10_in_columns<NC, SITING>(CR, own, j ? down : up, first, lo, hi, cv);
 #pragma unroll
-            for (int k = 0; k < COLS; ++k) {
-                const int c = 1 + (k >> 1), n = (k & 1) ? c + 1 : c - 1;
-                u[k] = mm_yuv10_chroma_blend16(cu[c], cu[n]);
-                v[k] = mm_yuv10_chroma_blend16(cv[c], cv[n]);
+                    for (int k = 0; k < COLS; ++k) {
+                        u[k] = mm_yuv10_chroma_blend16_left(cu[k >> 1], cu[(k >> 1) + 1], k & 1);
+                        v[k] = mm_yuv10_chroma_blend16_left(cv[k >> 1], cv[(k >> 1) + 1], k & 1);
+                    }
+                    yuv10_in_row<COLS, NT>(m, j ? y_bot : y_top, u, v, D + (yo + (j ? a.width : 0u)));
+                }
+            } else {
+                // pixel k has its own column at index 1 + k / 2 of the NC + 2, its neighbour one to the left (k even) or right
+                yuv10_in_columns<NC, SITING>(CB, own, up, first, lo, hi, cu);
+                yuv10_in_columns<NC, SITING>(CR, own, up, first, lo, hi, cv);
+#pragma unroll
+                for (int k = 0; k < COLS; ++k) {
+                    const int c = 1 + (k >> 1), n = (k & 1) ? c + 1 : c - 1;
+                    u[k] = mm_yuv10_chroma_blend16(cu[c], cu[n]);
+                    v[k] = mm_yuv10_chroma_blend16(cv[c], cv[n]);
+                }
+                yuv10_in_row<COLS, NT>(m, y_top, u, v, D + yo);
+                if (!two) return;
+                yuv10_in_columns<NC, SITING>(CB, own, down, first, lo, hi, cu);
+                yuv10_in_columns<NC, SITING>(CR, own, down, first, lo, hi, cv);
+#pragma unroll
+                for (int k = 0; k < COLS; ++k) {
+                    const int c = 1 + (k >> 1), n = (k & 1) ? c + 1 : c - 1;
+                    u[k] = mm_yuv10_chroma_blend16(cu[c], cu[n]);
+                    v[k] = mm_yuv10_chroma_blend16(cv[c], cv[n]);
+                }
+                yuv10_in_row<COLS, NT>(m, y_bot, u, v, D + (yo + a.width));
             }
-            yuv10_in_row<COLS, NT>(m, y_bot, u, v, D + (yo + a.width));
+        }
+    } else if constexpr (LEFT) {
+        // `at` is the chroma column: pixel columns 2 at and, inside the frame, 2 at + 1
+        const unsigned c0 = 2u * at;
+        const bool wide = c0 + 1u < a.width;
+        const unsigned right = at + 1u < a.cw ? at + 1u : at;
+        const unsigned yo = r0 * a.width + c0;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (j && !two) break;
+            const unsigned nb = j ? down : up;
+            const int cu = mm_yuv_chroma_column(mm_yuv10_sample(CB[own + at]), mm_yuv10_sample(CB[nb + at]));
+            const int cv = mm_yuv_chroma_column(mm_yuv10_sample(CR[own + at]), mm_yuv10_sample(CR[nb + at]));
+            const unsigned o = yo + (j ? a.width : 0u);
+            yuv10_in_store<NT>(m, mm_yuv10_sample(Y[o]), mm_yuv10_chroma_blend16_left(cu, cu, 0), mm_yuv10_chroma_blend16_left(cv, cv, 0), D + o);
+            if (!wide) continue;
+            const int ru = mm_yuv_chroma_column(mm_yuv10_sample(CB[own + right]), mm_yuv10_sample(CB[nb + right]));
+            const int rv = mm_yuv_chroma_column(mm_yuv10_sample(CR[own + right]), mm_yuv10_sample(CR[nb + right]));
+            yuv10_in_store<NT>(m, mm_yuv10_sample(Y[o + 1u]), mm_yuv10_chroma_blend16_left(cu, ru, 1), mm_yuv10_chroma_blend16_left(cv, rv, 1), D + (o + 1u));
         }
     } else {
         // `at` is the chroma column: pixel columns 2 at and, inside the frame, 2 at + 1
@@ -256,72 +232,45 @@ static void yuv10_in_launch_left(bool nt, dim3 grid, hipStream_t s, const Yuv10I
     else k_yuv420p10_to_float_clip<COLS, MM_YUV_CHROMA_BILINEAR, false, MM_YUV_SITING_LEFT><<<grid, 256, 0, s>>>(a);
 }
 
-int check_yuv420p10_to_float_clip_sited(const char *name, const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix,
-                                        int range, int chroma, int siting, const void *dst, int64_t dst_frame_stride, std::string *err) {
-    const std::string who = std::string(name) + ": ";
-    auto no = [&](const std::string &what) {
-        *err = who + what;
-        return -1;
-    };
-    if (width < 1 || height < 1) return no("width and height must be at least 1, not " + std::to_string(width) + " x " + std::to_string(height));
-    if (frames < 1) return no("num_frames must be at least 1");
-    if (frames > 65535) return no("more than 65535 frames in one call (" + std::to_string(frames) + "); convert the clip in groups");
-    if (matrix < 0 || matrix >= MM_YUV_MATRICES) return no("matrix must be MMHIP_YUV_BT601 or MMHIP_YUV_BT709 (0 or 1), not " + std::to_string(matrix));
-    if (range < 0 || range >= MM_YUV_RANGES) return no("range must be MMHIP_YUV_LIMITED or MMHIP_YUV_FULL (0 or 1), not " + std::to_string(range));
-    if (!mm_yuv_chroma_known(chroma))
-        return no("chroma must be MMHIP_YUV_CHROMA_BILINEAR or MMHIP_YUV_CHROMA_REPLICATE (0 or 1), not " + std::to_string(chroma));
-    if (!mm_yuv_siting_known(siting))
-        return no("siting must be MMHIP_YUV_SITING_CENTER or MMHIP_YUV_SITING_LEFT (0 or 1), not " + std::to_string(siting));
-    if (!src || !dst) return no("src_yuv and dst_float4 must be device pointers");
-    if (((uintptr_t)src | (uintptr_t)src_frame_stride) % 2 != 0) return no("src_yuv and src_frame_stride must be even (the samples are 16-bit)");
-    const int64_t frame_bytes = mm_yuv10_frame_bytes(width, height), texel_bytes = (int64_t)width * height * 16;
-    if (src_frame_stride < frame_bytes)
-        return no("src_frame_stride " + std::to_string(src_frame_stride) + " is smaller than one frame (" + std::to_string(frame_bytes) + " bytes)");
-    if ((uintptr_t)dst % 16 != 0) return no("dst_float4 is not 16-byte aligned (float4 texels)");
-    if (dst_frame_stride % 16 != 0) return no("dst_frame_stride " + std::to_string(dst_frame_stride) + " is not a multiple of 16");
-    if (dst_frame_stride < texel_bytes)
-        return no("dst_frame_stride " + std::to_string(dst_frame_stride) + " is smaller than one frame (" + std::to_string(texel_bytes) + " bytes)");
+int check_yuv420p10_to_float_clip(const YuvInJob &j, std::string *err) {
+    const YuvRefusal no(j.name, err);
+    if (yuv_check_modes(no, j.width, j.height, j.frames, j.matrix, j.range, &j.chroma, j.siting) != 0) return -1;
+    if (!j.src || !j.dst) return no("src_yuv and dst_float4 must be device pointers");
+    if (((uintptr_t)j.src | (uintptr_t)j.src_frame_stride) % 2 != 0) return no("src_yuv and src_frame_stride must be even (the samples are 16-bit)");
+    const int64_t frame_bytes = mm_yuv10_frame_bytes(j.width, j.height), texel_bytes = (int64_t)j.width * j.height * 16;
+    if (j.src_frame_stride < frame_bytes) return no(yuv_short_stride("src_frame_stride", j.src_frame_stride, "frame", frame_bytes));
+    if ((uintptr_t)j.dst % 16 != 0) return no("dst_float4 is not 16-byte aligned (float4 texels)");
+    if (j.dst_frame_stride % 16 != 0) return no("dst_frame_stride " + std::to_string(j.dst_frame_stride) + " is not a multiple of 16");
+    if (j.dst_frame_stride < texel_bytes) return no(yuv_short_stride("dst_frame_stride", j.dst_frame_stride, "frame", texel_bytes));
     if (texel_bytes > ((int64_t)1 << 32)) return no("a destination frame of more than 4 GiB");
     return 0;
 }
 
-int check_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
-                                  const void *dst, int64_t dst_frame_stride, std::string *err) {
-    return check_yuv420p10_to_float_clip_sited("clip_from_yuv420p10", src, src_frame_stride, width, height, frames, matrix, range, chroma,
-                                               MM_YUV_SITING_CENTER, dst, dst_frame_stride, err);
-}
-
-int launch_yuv420p10_to_float_clip_sited(const char *name, const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix,
-                                         int range, int chroma, int siting, void *dst, int64_t dst_frame_stride, NativeWorkspace &ws,
-                                         hipStream_t s, int *path, std::string *err) {
-    if (check_yuv420p10_to_float_clip_sited(name, src, src_frame_stride, width, height, frames, matrix, range, chroma, siting, dst, dst_frame_stride,
-                                            err) != 0)
-        return -1;
+int launch_yuv420p10_to_float_clip(const YuvInJob &j, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err) {
+    if (check_yuv420p10_to_float_clip(j, err) != 0) return -1;
     Yuv10InArgs a;
-    a.src = (const uint16_t *)src;
-    a.dst = (float *)dst;
-    a.src_frame_samples = src_frame_stride / 2;
-    a.dst_frame_stride = dst_frame_stride;
-    a.cb_offset = (unsigned)mm_yuv_cb_offset(width, height);      // at most 2^28, a source frame at most 1.5 * 2^28 samples
-    a.cr_offset = (unsigned)mm_yuv_cr_offset(width, height);
-    a.width = (unsigned)width;
-    a.height = (unsigned)height;
-    a.cw = (unsigned)mm_yuv_cw(width);
-    a.ch = (unsigned)mm_yuv_ch(height);
-    a.m = MM_YUV10_FLOAT_MODES[matrix][range];
+    a.src = (const uint16_t *)j.src;
+    a.dst = (float *)j.dst;
+    a.src_frame_samples = j.src_frame_stride / 2;
+    a.dst_frame_stride = j.dst_frame_stride;
+    a.cb_offset = (unsigned)mm_yuv_cb_offset(j.width, j.height);      // at most 2^28, a source frame at most 1.5 * 2^28 samples
+    a.cr_offset = (unsigned)mm_yuv_cr_offset(j.width, j.height);
+    a.width = (unsigned)j.width;
+    a.height = (unsigned)j.height;
+    a.cw = (unsigned)mm_yuv_cw(j.width);
+    a.ch = (unsigned)mm_yuv_ch(j.height);
+    a.m = MM_YUV10_FLOAT_MODES[j.matrix][j.range];
     // the aligned path: Y loads of up to 16 bytes at 2 * (row * width + 8 k), chroma loads of up to 8 bytes at 2 * (plane +
     // cy * width / 2 + 4 k): with the width a multiple of 8, 2 * width * height is a multiple of 16 and 2 * cw * ch one of 8
-    const bool aligned = width % 8 == 0 && ((uintptr_t)src | (uintptr_t)src_frame_stride) % 16 == 0;
+    const bool aligned = j.width % 8 == 0 && ((uintptr_t)j.src | (uintptr_t)j.src_frame_stride) % 16 == 0;
     // MMHIP_YUV10_IN_COLUMNS=2|4|8 and MMHIP_YUV10_IN_STORES=cached|nt, read per call: the A/Bs of tools/clip_yuv10_input_cost.py
-    const char *columns = getenv("MMHIP_YUV10_IN_COLUMNS"), *stores = getenv("MMHIP_YUV10_IN_STORES");
-    const unsigned cols = columns && !strcmp(columns, "8") ? 8u : columns && !strcmp(columns, "4") ? 4u : 2u;
-    const bool nt = stores && !strcmp(stores, "nt");
-    const bool rep = chroma == MM_YUV_CHROMA_REPLICATE;
+    const unsigned cols = yuv_knob_is("MMHIP_YUV10_IN_COLUMNS", "8") ? 8u : yuv_knob_is("MMHIP_YUV10_IN_COLUMNS", "4") ? 4u : 2u;
+    const bool nt = yuv_knob_is("MMHIP_YUV10_IN_STORES", "nt");
+    const bool rep = j.chroma == MM_YUV_CHROMA_REPLICATE;
     a.per_pair = aligned ? a.width / cols : a.cw;
     a.items = a.per_pair * a.ch;
-    const dim3 grid((a.items + 255u) / 256u, (unsigned)frames);
-    const bool left = siting == MM_YUV_SITING_LEFT && !rep;      // replicate mode ignores the siting
-    ws.timed_launch("yuv420p10_to_float_clip", s, [&] {
+    const bool left = j.siting == MM_YUV_SITING_LEFT && !rep;      // replicate mode ignores the siting
+    return yuv_launch(j.name, "yuv420p10_to_float_clip", a.items, j.frames, aligned, ws, s, path, err, [&](dim3 grid) {
         if (left && aligned && cols == 8) yuv10_in_launch_left<8>(nt, grid, s, a);
         else if (left && aligned && cols == 4) yuv10_in_launch_left<4>(nt, grid, s, a);
         else if (left && aligned) yuv10_in_launch_left<2>(nt, grid, s, a);
@@ -331,18 +280,6 @@ int launch_yuv420p10_to_float_clip_sited(const char *name, const void *src, int6
         else if (aligned) yuv10_in_launch<2>(rep, nt, grid, s, a);
         else yuv10_in_launch<0>(rep, nt, grid, s, a);
     });
-    if (hipGetLastError() != hipSuccess) {
-        *err = std::string(name) + ": kernel launch failed";
-        return -1;
-    }
-    if (path) *path = aligned ? 0 : 1;
-    return 0;
-}
-
-int launch_yuv420p10_to_float_clip(const void *src, int64_t src_frame_stride, int width, int height, int frames, int matrix, int range, int chroma,
-                                   void *dst, int64_t dst_frame_stride, NativeWorkspace &ws, hipStream_t s, int *path, std::string *err) {
-    return launch_yuv420p10_to_float_clip_sited("clip_from_yuv420p10", src, src_frame_stride, width, height, frames, matrix, range, chroma,
-                                                MM_YUV_SITING_CENTER, dst, dst_frame_stride, ws, s, path, err);
 }
 
 }  // namespace mm

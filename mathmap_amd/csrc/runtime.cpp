@@ -741,6 +741,38 @@ int mmhip_set_image_sequence_float_host(mmhip_invocation *inv, int index, const 
     return 0;
 }
 
+// The staged upload of planar Y'CbCr 4:2:0 payloads, of either depth: frame i's frame_bytes at payloads + i * frame_stride
+// go up as they are, in groups of at most 65 535 frames through a staging buffer of at most MMHIP_CLIP_YUV_IN_BYTES (256
+// MiB where it is not set), and convert(staged, n, to, stream) expands each group of n frames to its place in `landed`,
+// landed_bytes a frame.  *groups counts them.  The stream is waited for before a group overwrites what the launch before
+// it reads, and after the last.
+template <class Convert>
+static int upload_yuv_groups(mmhip_invocation *inv, const void *payloads, int64_t frame_stride, int64_t frame_bytes, char *landed, int64_t landed_bytes,
+                             int num_frames, int *groups, Convert convert) {
+    const char *text = getenv("MMHIP_CLIP_YUV_IN_BYTES");
+    long long budget = text ? atoll(text) : 0;
+    if (budget <= 0) budget = (long long)256 << 20;
+    const int per_group = (int)std::max<long long>(1, std::min<long long>(std::min(num_frames, 65535), budget / frame_bytes));
+    DeviceBuffer staging;
+    HIP_TRY(staging.grow((size_t)per_group * (size_t)frame_bytes));
+    hipStream_t s = (hipStream_t)inv->stream;
+    *groups = 0;
+    for (int g0 = 0; g0 < num_frames; g0 += per_group) {
+        const int n = std::min(per_group, num_frames - g0);
+        if (g0) HIP_TRY(hipStreamSynchronize(s));      // the launch before this one reads the staging buffer
+        const char *from = (const char *)payloads + (size_t)g0 * (size_t)frame_stride;
+        if (frame_stride == frame_bytes) HIP_TRY(hipMemcpy(staging.get(), from, (size_t)n * (size_t)frame_bytes, hipMemcpyHostToDevice));
+        else
+            for (int k = 0; k < n; ++k)
+                HIP_TRY(hipMemcpy(staging.get<char>() + (size_t)k * (size_t)frame_bytes, from + (size_t)k * (size_t)frame_stride, (size_t)frame_bytes,
+                                  hipMemcpyHostToDevice));
+        if (convert(staging.get(), n, landed + (size_t)g0 * (size_t)landed_bytes, s) != 0) return -1;
+        ++*groups;
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
 // Planar Y'CbCr 4:2:0 payloads as a sequence: they go up as they are, in groups through a staging buffer of at most
 // MMHIP_CLIP_YUV_IN_BYTES, and k_yuv420_to_rgba_clip expands every group into the owned sequence.
 static int set_image_sequence_yuv420_host(const std::string &name, bool sited, mmhip_invocation *inv, int index, const uint8_t *yuv, int64_t frame_stride, int width,
@@ -757,34 +789,17 @@ static int set_image_sequence_yuv420_host(const std::string &name, bool sited, m
         return fail(who + "frame_stride " + std::to_string(frame_stride) + " is smaller than one frame (" + std::to_string(frame_bytes) + " bytes)");
     std::string err;
     // (the converter's own refusals before anything is allocated: the pointers are placeholders)
-    if (check_yuv420_to_rgba_clip_sited(converter, yuv, frame_bytes, width, height, 1, matrix, range, chroma, siting, yuv, words_bytes, &err) != 0)
-        return fail(err);
+    const YuvInJob job = {converter, yuv, frame_bytes, width, height, 1, matrix, range, chroma, siting, (void *)yuv, words_bytes};
+    if (check_yuv420_to_rgba_clip(job, &err) != 0) return fail(err);
     if (!uv_info(inv, index, UvKind::Image)) return -1;
-    const char *text = getenv("MMHIP_CLIP_YUV_IN_BYTES");
-    long long budget = text ? atoll(text) : 0;
-    if (budget <= 0) budget = (long long)256 << 20;
-    const int per_group = (int)std::max<long long>(1, std::min<long long>(std::min(num_frames, 65535), budget / frame_bytes));
-    DeviceBuffer d, staging;
+    DeviceBuffer d;
     HIP_TRY(d.grow(bytes));
-    HIP_TRY(staging.grow((size_t)per_group * (size_t)frame_bytes));
-    hipStream_t s = (hipStream_t)inv->stream;
-    inv->clip_yuv_input_groups = 0;
-    for (int g0 = 0; g0 < num_frames; g0 += per_group) {
-        const int n = std::min(per_group, num_frames - g0);
-        if (g0) HIP_TRY(hipStreamSynchronize(s));      // the launch before this one reads the staging buffer
-        const uint8_t *from = yuv + (size_t)g0 * (size_t)frame_stride;
-        if (frame_stride == frame_bytes) HIP_TRY(hipMemcpy(staging.get(), from, (size_t)n * (size_t)frame_bytes, hipMemcpyHostToDevice));
-        else
-            for (int k = 0; k < n; ++k)
-                HIP_TRY(hipMemcpy(staging.get<char>() + (size_t)k * (size_t)frame_bytes, from + (size_t)k * (size_t)frame_stride, (size_t)frame_bytes,
-                                  hipMemcpyHostToDevice));
-        void *to = d.get<char>() + (size_t)g0 * (size_t)words_bytes;
-        if ((sited ? mmhip_clip_from_yuv420_sited(inv, staging.get(), frame_bytes, width, height, n, matrix, range, chroma, siting, to, words_bytes, s)
-                   : mmhip_clip_from_yuv420(inv, staging.get(), frame_bytes, width, height, n, matrix, range, chroma, to, words_bytes, s)) != 0)
-            return -1;
-        ++inv->clip_yuv_input_groups;
-    }
-    HIP_TRY(hipStreamSynchronize(s));
+    if (upload_yuv_groups(inv, yuv, frame_stride, frame_bytes, d.get<char>(), words_bytes, num_frames, &inv->clip_yuv_input_groups,
+                          [&](const void *staged, int n, void *to, hipStream_t s) {
+                              return sited ? mmhip_clip_from_yuv420_sited(inv, staged, frame_bytes, width, height, n, matrix, range, chroma, siting, to, words_bytes, s)
+                                           : mmhip_clip_from_yuv420(inv, staged, frame_bytes, width, height, n, matrix, range, chroma, to, words_bytes, s);
+                          }) != 0)
+        return -1;
     // the upload this one replaces (if it was ours) is freed once nothing in flight reads it
     const void *old = inv->images[inv->image_slot_of_uv[index]].data;
     for (auto it = inv->owned.begin(); it != inv->owned.end(); ++it)
@@ -824,35 +839,17 @@ static int set_image_sequence_yuv420p10_host(const std::string &name, bool sited
         return fail(who + "frame_stride " + std::to_string(frame_stride) + " is smaller than one frame (" + std::to_string(frame_bytes) + " bytes)");
     std::string err;
     // (the converter's own refusals before anything is allocated: the pointers are placeholders)
-    if (check_yuv420p10_to_float_clip_sited(converter, (const void *)16, frame_bytes, width, height, 1, matrix, range, chroma, siting, (const void *)16,
-                                            texel_bytes, &err) != 0)
-        return fail(err);
+    const YuvInJob job = {converter, (const void *)16, frame_bytes, width, height, 1, matrix, range, chroma, siting, (void *)16, texel_bytes};
+    if (check_yuv420p10_to_float_clip(job, &err) != 0) return fail(err);
     if (!uv_info(inv, index, UvKind::Image)) return -1;
-    const char *text = getenv("MMHIP_CLIP_YUV_IN_BYTES");
-    long long budget = text ? atoll(text) : 0;
-    if (budget <= 0) budget = (long long)256 << 20;
-    const int per_group = (int)std::max<long long>(1, std::min<long long>(std::min(num_frames, 65535), budget / frame_bytes));
-    DeviceBuffer d, staging;
+    DeviceBuffer d;
     HIP_TRY(d.grow(bytes));
-    HIP_TRY(staging.grow((size_t)per_group * (size_t)frame_bytes));
-    hipStream_t s = (hipStream_t)inv->stream;
-    inv->clip_yuv10_input_groups = 0;
-    for (int g0 = 0; g0 < num_frames; g0 += per_group) {
-        const int n = std::min(per_group, num_frames - g0);
-        if (g0) HIP_TRY(hipStreamSynchronize(s));      // the launch before this one reads the staging buffer
-        const char *from = (const char *)yuv + (size_t)g0 * (size_t)frame_stride;
-        if (frame_stride == frame_bytes) HIP_TRY(hipMemcpy(staging.get(), from, (size_t)n * (size_t)frame_bytes, hipMemcpyHostToDevice));
-        else
-            for (int k = 0; k < n; ++k)
-                HIP_TRY(hipMemcpy(staging.get<char>() + (size_t)k * (size_t)frame_bytes, from + (size_t)k * (size_t)frame_stride, (size_t)frame_bytes,
-                                  hipMemcpyHostToDevice));
-        void *to = d.get<char>() + (size_t)g0 * (size_t)texel_bytes;
-        if ((sited ? mmhip_clip_from_yuv420p10_sited(inv, staging.get(), frame_bytes, width, height, n, matrix, range, chroma, siting, to, texel_bytes, s)
-                   : mmhip_clip_from_yuv420p10(inv, staging.get(), frame_bytes, width, height, n, matrix, range, chroma, to, texel_bytes, s)) != 0)
-            return -1;
-        ++inv->clip_yuv10_input_groups;
-    }
-    HIP_TRY(hipStreamSynchronize(s));
+    if (upload_yuv_groups(inv, yuv, frame_stride, frame_bytes, d.get<char>(), texel_bytes, num_frames, &inv->clip_yuv10_input_groups,
+                          [&](const void *staged, int n, void *to, hipStream_t s) {
+                              return sited ? mmhip_clip_from_yuv420p10_sited(inv, staged, frame_bytes, width, height, n, matrix, range, chroma, siting, to, texel_bytes, s)
+                                           : mmhip_clip_from_yuv420p10(inv, staged, frame_bytes, width, height, n, matrix, range, chroma, to, texel_bytes, s);
+                          }) != 0)
+        return -1;
     const int slot = inv->image_slot_of_uv[index];
     release_owned_image(inv, slot);
     const void *dev = d.get();

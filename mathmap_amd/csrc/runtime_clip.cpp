@@ -1242,19 +1242,27 @@ int mmhip_y4m_header_sited(char *buf, int cap, int width, int height, int fps_nu
     return y4m_header_line(who, tag, buf, cap, width, height, fps_num, fps_den, range);
 }
 
+// One call of a converter under the name of its entry point: its refusals (they need no GPU), the invocation, the caller's
+// stream or the invocation's, the launch, and the path it took counted where the converter has a counter.
+template <class Job>
+static int clip_yuv_convert(mmhip_invocation *inv, const Job &job, void *stream, int (*check)(const Job &, std::string *),
+                            int (*launch)(const Job &, NativeWorkspace &, hipStream_t, int *, std::string *), long (mmhip_invocation::*launches)[2]) {
+    std::string err;
+    if (check(job, &err) != 0) return fail(err);
+    if (!inv) return fail(std::string(job.name) + ": no invocation");
+    hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)inv->stream;
+    int path = 0;
+    if (launch(job, inv->ws, s, &path, &err) != 0) return fail(err);
+    if (launches) ++(inv->*launches)[path];
+    return 0;
+}
+
 static int clip_to_yuv420(const char *name, mmhip_invocation *inv, const void *src_rgba, int64_t src_row_stride, int64_t src_frame_stride, int width,
                           int height, int first_row, int last_row, int num_frames, int matrix, int range, int siting, void *dst,
                           int64_t dst_frame_stride, void *stream) {
-    std::string err;
-    if (check_rgba8_to_yuv420_clip_sited(name, src_rgba, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix,
-                                         range, siting, dst, dst_frame_stride, &err) != 0)
-        return fail(err);
-    if (!inv) return fail(std::string(name) + ": no invocation");
-    hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)inv->stream;
-    if (launch_rgba8_to_yuv420_clip_sited(name, src_rgba, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix,
-                                          range, siting, dst, dst_frame_stride, inv->ws, s, nullptr, &err) != 0)
-        return fail(err);
-    return 0;
+    const YuvOutJob job = {name, src_rgba, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix, range, siting, dst,
+                           dst_frame_stride};
+    return clip_yuv_convert(inv, job, stream, check_rgba8_to_yuv420_clip, launch_rgba8_to_yuv420_clip, nullptr);
 }
 
 int mmhip_clip_to_yuv420(mmhip_invocation *inv, const void *src_rgba, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
@@ -1283,18 +1291,9 @@ int mmhip_y4m_header_p10(char *buf, int cap, int width, int height, int fps_num,
 static int clip_float_to_yuv420p10(const char *name, mmhip_invocation *inv, const void *src, int64_t src_row_stride, int64_t src_frame_stride,
                                    int width, int height, int first_row, int last_row, int num_frames, int matrix, int range, int siting,
                                    void *dst, int64_t dst_frame_stride, void *stream) {
-    std::string err;
-    if (check_float_to_yuv420p10_clip_sited(name, src, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix, range,
-                                            siting, dst, dst_frame_stride, &err) != 0)
-        return fail(err);
-    if (!inv) return fail(std::string(name) + ": no invocation");
-    hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)inv->stream;
-    int path = 0;
-    if (launch_float_to_yuv420p10_clip_sited(name, src, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix, range,
-                                             siting, dst, dst_frame_stride, inv->ws, s, &path, &err) != 0)
-        return fail(err);
-    ++inv->clip_yuv10_launches[path];
-    return 0;
+    const YuvOutJob job = {name, src, src_row_stride, src_frame_stride, width, height, first_row, last_row, num_frames, matrix, range, siting, dst,
+                           dst_frame_stride};
+    return clip_yuv_convert(inv, job, stream, check_float_to_yuv420p10_clip, launch_float_to_yuv420p10_clip, &mmhip_invocation::clip_yuv10_launches);
 }
 
 int mmhip_clip_float_to_yuv420p10(mmhip_invocation *inv, const void *src, int64_t src_row_stride, int64_t src_frame_stride, int width, int height,
@@ -1323,18 +1322,8 @@ static_assert(MMHIP_YUV_CHROMA_BILINEAR == MM_YUV_CHROMA_BILINEAR && MMHIP_YUV_C
               "the chroma modes of mm_yuv.h");
 static int clip_from_yuv420(const char *name, mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height,
                             int num_frames, int matrix, int range, int chroma, int siting, void *dst_rgba32, int64_t dst_frame_stride, void *stream) {
-    std::string err;
-    if (check_yuv420_to_rgba_clip_sited(name, src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, siting, dst_rgba32,
-                                        dst_frame_stride, &err) != 0)
-        return fail(err);
-    if (!inv) return fail(std::string(name) + ": no invocation");
-    hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)inv->stream;
-    int path = 0;
-    if (launch_yuv420_to_rgba_clip_sited(name, src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, siting, dst_rgba32,
-                                         dst_frame_stride, inv->ws, s, &path, &err) != 0)
-        return fail(err);
-    ++inv->clip_yuv_input_launches[path];
-    return 0;
+    const YuvInJob job = {name, src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, siting, dst_rgba32, dst_frame_stride};
+    return clip_yuv_convert(inv, job, stream, check_yuv420_to_rgba_clip, launch_yuv420_to_rgba_clip, &mmhip_invocation::clip_yuv_input_launches);
 }
 
 int mmhip_clip_from_yuv420(mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height, int num_frames, int matrix,
@@ -1440,18 +1429,9 @@ int mmhip_y4m_stream_siting(const char *buf, int len, int *siting) {
 static int clip_from_yuv420p10(const char *name, mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height,
                                int num_frames, int matrix, int range, int chroma, int siting, void *dst_float4, int64_t dst_frame_stride,
                                void *stream) {
-    std::string err;
-    if (check_yuv420p10_to_float_clip_sited(name, src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, siting, dst_float4,
-                                            dst_frame_stride, &err) != 0)
-        return fail(err);
-    if (!inv) return fail(std::string(name) + ": no invocation");
-    hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)inv->stream;
-    int path = 0;
-    if (launch_yuv420p10_to_float_clip_sited(name, src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, siting, dst_float4,
-                                             dst_frame_stride, inv->ws, s, &path, &err) != 0)
-        return fail(err);
-    ++inv->clip_yuv10_input_launches[path];
-    return 0;
+    const YuvInJob job = {name, src_yuv, src_frame_stride, width, height, num_frames, matrix, range, chroma, siting, dst_float4, dst_frame_stride};
+    return clip_yuv_convert(inv, job, stream, check_yuv420p10_to_float_clip, launch_yuv420p10_to_float_clip,
+                            &mmhip_invocation::clip_yuv10_input_launches);
 }
 
 int mmhip_clip_from_yuv420p10(mmhip_invocation *inv, const void *src_yuv, int64_t src_frame_stride, int width, int height, int num_frames, int matrix,

@@ -6,9 +6,11 @@ mmhip_drain_native_kernel_ms, medians of --rounds rounds with max - min beside t
                  kernels in bilinear mode, everything on its aligned path with the defaults of its knobs), centre against
                  left siting, in one process after a warm-up, the legs alternating.  Each row carries its traffic set against
                  the achievable HBM rate, as the tables of the four converters compute it.
-  --part parent  the centre legs of this build against the same kernels of a build of the parent commit (--parent DIR, a
-                 checkout built in place): one child process per side and round -- parent, new, parent, new, ... -- each
-                 taking the median of --rounds launches after a warm-up through the entry points both builds have.
+  --part parent  the centre and the left legs of this build against the same kernels of a build of the parent commit
+                 (--parent DIR, a checkout built in place): one child process per side and round -- parent, new, parent,
+                 new, ... -- each taking the median of --rounds launches after a warm-up.  A new median counts as within the
+                 band where it lies within the parent's median +- the larger of the two sides' spreads.  --centre-only
+                 times the centre legs alone, through the entry points without a siting: for a parent that has no others.
   --part ab      bench.py's default line, parent and this build alternating, --runs runs each (tools/sequence_cost.py's A/B).
 
     python tools/clip_yuv_siting_cost.py --part sited --out profiles/r25_clip_yuv_siting_cost.json --commit <sha>
@@ -132,44 +134,50 @@ def part_sited(args, record):
 
 
 def child(args):
-    """One side of --part parent: the centre legs through the entry points without a siting, in the tree --tree."""
+    """One side of --part parent: the legs of every kernel in the tree --tree."""
     sys.path.insert(0, os.path.abspath(args.tree))
+    sitings = SITINGS[:1] if args.centre_only else SITINGS
     out = {}
     for name in args.clips.split(","):
-        clip = Clip(name, False)
+        clip = Clip(name, not args.centre_only)
         try:
-            ms = clip.measure([(kernel, "center") for kernel in KERNELS], args.rounds)
+            ms = clip.measure([(kernel, siting) for kernel in KERNELS for siting in sitings], args.rounds)
         finally:
             clip.free()
-        out[name] = {kernel: median(ms[kernel, "center"]) for kernel in KERNELS}
+        out[name] = {kernel: {siting: median(ms[kernel, siting]) for siting in sitings} for kernel in KERNELS}
     print(json.dumps(out), flush=True)
     return 0
 
 
 def part_parent(args, record):
     trees = (("parent", os.path.abspath(args.parent)), ("new", ROOT))
-    series = {side: {name: {kernel: [] for kernel in KERNELS} for name in args.clips.split(",")} for side, _ in trees}
+    sitings = SITINGS[:1] if args.centre_only else SITINGS
+    series = {side: {name: {(kernel, siting): [] for kernel in KERNELS for siting in sitings} for name in args.clips.split(",")} for side, _ in trees}
     for _ in range(args.rounds):
         for side, tree in trees:
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--tree", tree, "--clips", args.clips, "--rounds", str(args.rounds),
-                                "--out", os.devnull], cwd=tree, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=420)
+                                "--out", os.devnull] + (["--centre-only"] if args.centre_only else []), cwd=tree, stdout=subprocess.PIPE,
+                               stderr=subprocess.PIPE, text=True, timeout=420)
             if p.returncode != 0:
                 raise RuntimeError("the %s side failed: %s" % (side, p.stderr[-600:]))
             got = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
             for name in got:
-                for kernel, ms in got[name].items():
-                    series[side][name][kernel].append(ms)
+                for kernel, legs in got[name].items():
+                    for siting, ms in legs.items():
+                        series[side][name][kernel, siting].append(ms)
     rec = {"order": "parent, new, parent, new, ...: one process per side and round, each value the median of %d launches" % args.rounds, "clips": {}}
     for name in args.clips.split(","):
         rec["clips"][name] = {}
-        for kernel in KERNELS:
-            row = {side: summary(series[side][name][kernel]) for side, _ in trees}
+        for kernel, siting in series["new"][name]:
+            row = {side: summary(series[side][name][kernel, siting]) for side, _ in trees}
             row["new_over_parent"] = row["new"]["median_ms"] / row["parent"]["median_ms"]
-            row["within_parent_spread"] = abs(row["new"]["median_ms"] - row["parent"]["median_ms"]) <= row["parent"]["spread_ms"]
-            rec["clips"][name][kernel] = row
-            print(json.dumps({name: {kernel: {"parent": round(row["parent"]["median_ms"], 4), "parent_spread": round(row["parent"]["spread_ms"], 4),
-                                              "new": round(row["new"]["median_ms"], 4), "within_parent_spread": row["within_parent_spread"]}}}), flush=True)
-    record["center_against_parent"] = rec
+            band = max(row["parent"]["spread_ms"], row["new"]["spread_ms"])
+            row["within_the_band"] = abs(row["new"]["median_ms"] - row["parent"]["median_ms"]) <= band
+            rec["clips"][name].setdefault(kernel, {})[siting] = row
+            print(json.dumps({name: {kernel: {siting: {"parent": round(row["parent"]["median_ms"], 4), "parent_spread": round(row["parent"]["spread_ms"], 4),
+                                                       "new": round(row["new"]["median_ms"], 4), "new_spread": round(row["new"]["spread_ms"], 4),
+                                                       "within_the_band": row["within_the_band"]}}}}), flush=True)
+    record["against_parent"] = rec
     yield record
 
 
@@ -193,6 +201,7 @@ def main():
     ap.add_argument("--runs", type=int, default=5, help="bench.py runs per side (--part ab)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--centre-only", action="store_true", help="--part parent: the centre legs alone, without a siting keyword")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--tree", default=ROOT, help=argparse.SUPPRESS)
     args = ap.parse_args()
